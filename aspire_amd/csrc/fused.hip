@@ -165,8 +165,9 @@ __global__ void __launch_bounds__(256, ASPIRE_FUSED_MIN_WAVES) pair_fused_kernel
             const int first = cj0 + 4 * ((int)item - g0);
             const int cand = min(first + p, cj1 - 1);
             x.q_idx = a.job0 + job;
-            x.q_len = a.q.len[x.q_idx];
-            x.q_start = a.q.start[x.q_idx];
+            // wave-uniform: in scalar registers (as vector loads they pushed the batched form into 36 bytes of scratch)
+            x.q_len = __builtin_amdgcn_readfirstlane(a.q.len[x.q_idx]);
+            x.q_start = __builtin_amdgcn_readfirstlane(a.q.start[x.q_idx]);
             x.my_c_real = first + p < cj1;
             x.c_idx = cand;
             x.c_len = a.c.len[cand];

@@ -992,8 +992,10 @@ __device__ __forceinline__ void load_item(RowSet& r, const ScoreArgs& a, uint32_
                           : a.pairing == kPairMapped      ? (int64_t)a.qmap[c_idx]
                                                           : (nq == 1 ? 0 : pair - c_loc * nq);
     const int i0 = 8 * ta, j0 = 8 * tb;
-    c_len = a.c.len[c_idx];
-    q_len = a.q.len[q_idx];
+    // `item` is workgroup-uniform: the lengths go to scalar registers (as vector loads they held four VGPRs across the
+    // item loop and took pair_cost1_kernel to 201 registers, over the co-residency budget above)
+    c_len = __builtin_amdgcn_readfirstlane(a.c.len[c_idx]);
+    q_len = __builtin_amdgcn_readfirstlane(a.q.len[q_idx]);
     const float* cdoc = a.c.rows + (size_t)a.c.start[c_idx] * kD + dofs;
     const float* qdoc = a.q.rows + (size_t)a.q.start[q_idx] * kD + dofs;
 #pragma unroll

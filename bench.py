@@ -1,25 +1,32 @@
 """bench.py -- query x candidate OT alignments per second (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
 Workload at N=1 = BASELINE.json configs[1]: otAspire, 1 query x 1000 candidates, 8 sentences x 768 d, reps ~ N(0,1)
 fp32, resident in HBM before the timed region.  One STEP = one query re-ranked against ITS OWN 1000-candidate pool
 (evaluate.py:58-76: every query of a dataset has its own pool): cost matrix + marginals + Sinkhorn (one epsilon schedule
-per pair, AspireModel.get_similarity) of the 1000 pairs, then the stable descending rank (top-100).  The K steps of a run
-are K independent (query, pool) jobs and go through ONE library call, aspire_ot_rank_batch_f32 -- a small launch that
-builds the job tables and query boxes (batches of more than 64 jobs only), ONE scoring launch over the K x 1000 pairs (costs and Sinkhorn solves fused: a
-wave streams four candidates' rows, then solves those four pairs from its registers while other waves stream), one
-K-workgroup rank launch -- two launches per call.  No hipGraphs.  Consecutive calls are independent requests and go round-robin over --streams
+per pair, AspireModel.get_similarity) of the 1000 pairs, then the stable descending rank (top-100).  The steps of a run
+are independent (query, pool) jobs and go JOBS_PER_CALL = 20 at a time through ONE library call, aspire_ot_rank_batch_f32
+-- a small launch that builds the job tables and query boxes (batches of more than 64 jobs only), ONE scoring launch over
+the 20 x 1000 pairs (costs and Sinkhorn solves fused: a wave streams four candidates' rows, then solves those four pairs
+from its registers while other waves stream), one 20-workgroup rank launch -- two launches per call.  No hipGraphs.  Consecutive calls are independent requests and go round-robin over --streams
 caller streams (default 3), each with its own outputs and workspace: the end of one call (the last Sinkhorn solves,
 the rank launch -- neither touches HBM) overlaps the next call's streaming.  `one_stream` in the JSON is the same schedule
 with one call at a time.
 
-Timing: the K-step schedule is repeated R times back to back (R chosen so that the timed region is >= 50 ms: K = 20 steps
-alone are ~0.1 ms) between barrier + torch.cuda.synchronize() on both sides; ms_per_step = elapsed / (K * R), value =
-N * K * R * 1000 / elapsed.  Every job has its own query and its own pool, and consecutive repetitions walk through a pool
-store of >= 2 K (at least 24) distinct pools (> 256 MiB, the Infinity Cache): the candidate reads come from HBM, not L3.
+Timing: EXACTLY --steps K steps are timed: ceil(K / 20) calls back to back (the last one holds the remainder) between
+barrier + torch.cuda.synchronize() on both sides; ms_per_step = elapsed / K, value = N * K * 1000 / elapsed.  20 steps
+alone are ~0.1 ms: choose K for a timed region of >= 50 ms (the default, 20 000, is ~0.1 s).  The --warmup W steps
+(at least one call per stream) and ~0.3 s of clock settling run untimed before.  Every job has its own query and its own
+pool, and consecutive calls walk through a pool store of (--streams + 1) x 20 (at least 24) distinct pools (> 256 MiB, the
+Infinity Cache): the candidate reads come from HBM, not L3.
+
+--dump-outputs DIR: after the timed region, what its last step returned to the caller -- that job's 1000 scores
+(scores.npy, float32), its top-100 scores (top_scores.npy, float32) and candidate indices (top_indices.npy, float64; global
+indices at N > 1) -- from rank 0.  The inputs are generated from fixed seeds, so two builds run with the same arguments
+can be compared output for output.
 
 At N > 1 every rank holds its own 1000-candidate block of each job's N * 1000-candidate pool (weak scaling), ranks its
 block (key form, global indices), and the per-job top-k lists are merged with ONE RCCL all-gather per call + one merge
@@ -47,6 +54,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -65,7 +73,7 @@ if os.environ.get('ASPIRE_BENCH_SHAPE'):      # "C,S": tuning experiments at oth
     TOPK = min(TOPK, NC)
 HBM_PEAK_GBS = 8000.0            # MI355X_MICROARCH.md: HBM3E 8 TB/s spec (6.3 TB/s achievable)
 L3_BYTES = 256 << 20
-MIN_TIMED_S = 0.05
+JOBS_PER_CALL = 20               # steps (jobs) per aspire_ot_rank_batch_f32 call
 
 
 def algorithmic_bytes(n_jobs):
@@ -433,18 +441,19 @@ def config4_sharded_probe(device, rank, world, J=50, NCAND=125, smax=20, reps=30
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=20)
+    ap.add_argument('--steps', type=int, default=20000, help='timed steps: (query, own 1000-candidate pool) jobs')
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-probes', action='store_true',
                     help='skip the side measurements that launch the scoring kernel at OTHER sizes / forms (Infinity-Cache-resident job set, '
                          'two-kernel form): for counter passes, whose per-kernel sums should hold the 20-job launches only')
-    ap.add_argument('--repeats', type=int, default=0, help='repetitions of the K-step schedule (0 = enough for >= 50 ms)')
     ap.add_argument('--streams', type=int, default=3,
-                    help='independent calls in flight: repetitions go round-robin over this many caller streams, each with its own '
+                    help='independent calls in flight: calls go round-robin over this many caller streams, each with its own '
                          'outputs and workspace (1 = one call at a time)')
     ap.add_argument('--shard-path', action='store_true',
                     help='run the N > 1 code path (key-form rank, gather, merge kernel) on one GPU, for testing')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help="write the timed region's last step (its scores, top-k scores and indices) to DIR/*.npy")
     args = ap.parse_args()
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -487,9 +496,11 @@ def main():
     from aspire_amd.parallel import all_gather_flat
     lib = _lib.lib
     shard_path = world > 1 or args.shard_path
-    K = args.steps
+    K = JOBS_PER_CALL
+    n_steps = args.steps
+    n_calls = -(-n_steps // K)
 
-    # ---- the pool store, resident in HBM: M distinct (query, 1000-candidate pool) jobs; repetition r runs jobs
+    # ---- the pool store, resident in HBM: M distinct (query, 1000-candidate pool) jobs; call r runs jobs
     # [r*K, r*K + K) mod M.  Rank r of a sharded run owns block r of every job's pool. ----------------------------------
     n_lanes = max(1, args.streams)
     M = max((n_lanes + 1) * K, 24)      # calls in flight never share a pool set
@@ -507,9 +518,10 @@ def main():
     null = ctypes.c_void_p(0)
 
     class JobSet:
-        """K consecutive jobs of the store as the two rep sets of one aspire_ot_rank_batch_f32 call."""
+        """K (or fewer) consecutive jobs of the store as the two rep sets of one aspire_ot_rank_batch_f32 call."""
 
         def __init__(self, first, n_jobs=K):
+            self.first = first
             self.q = ops.DeviceRepSet(queries[first * S:(first + n_jobs) * S], (ar[:n_jobs] * S).contiguous(),
                                       torch.full((n_jobs,), S, device=device, dtype=torch.int32), ext=0, max_len=S)
             self.c = ops.DeviceRepSet(cands[first * NC * S:(first + n_jobs) * NC * S], (ar[:n_jobs * NC] * S).contiguous(),
@@ -518,7 +530,12 @@ def main():
             self.n = n_jobs
 
     sets = [JobSet(f) for f in range(0, M, K)]
-    ws_bytes = lib.aspire_ot_rank_batch_workspace_bytes(ctypes.byref(sets[0].qs), ctypes.byref(sets[0].cs), NC, TOPK)
+    # the timed region: n_calls calls walking the store, the last one holding the remainder of --steps
+    timed_sets = [sets[r % len(sets)] for r in range(n_calls)]
+    if n_steps % K:
+        timed_sets[-1] = JobSet(timed_sets[-1].first, n_steps % K)
+    ws_bytes = max(lib.aspire_ot_rank_batch_workspace_bytes(ctypes.byref(js.qs), ctypes.byref(js.cs), NC, TOPK)
+                   for js in (sets[0], timed_sets[-1]))
     ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else null
     P_job_off, P_job_base = ptr(job_off), ptr(job_base)
 
@@ -552,8 +569,8 @@ def main():
         return t.item()
 
     def run_schedule(js, lane=None, exchange=True):
-        """K steps = K jobs = ONE C-ABI call on the lane's stream; sharded: + one all-gather of the K x k keys + one merge launch
-        (exchange=False: this rank's kernels only -- the stage timings below run on rank 0 alone)."""
+        """js.n steps = js.n jobs = ONE C-ABI call on the lane's stream; sharded: + one all-gather of the js.n x k keys + one merge
+        launch (exchange=False: this rank's kernels only -- the stage timings below run on rank 0 alone)."""
         lane = lane or lanes[0]
         rc = lib.aspire_ot_rank_batch_f32(ctypes.byref(js.qs), ctypes.byref(js.cs), D, P_job_off, NC, ctypes.byref(prm), _lib.OT_SIMILARITY,
                                           lane.P[0], TOPK, P_job_base, null if shard_path else lane.P[1], null if shard_path else lane.P[2],
@@ -565,13 +582,14 @@ def main():
             # the collective; collectives of different lanes go out in call order on every rank.  (A separate exchange
             # stream tied to the lanes by events was measured on one GPU, the gather replaced by a copy: 152 instead of 121 us
             # per call -- cross-stream event waits cost more than they hide on this runtime.)
+            n = js.n
             if world > 1:
                 with torch.cuda.stream(lane.stream):
-                    all_gather_flat(lane.gathered.view(-1), lane.keys.view(-1))      # -> [world][K][k]; RCCL over xGMI
+                    all_gather_flat(lane.gathered.view(-1)[:world * n * TOPK], lane.keys[:n].view(-1))      # -> [world][n][k]; RCCL over xGMI
                 src = lane.gathered
             else:
                 src = lane.keys
-            rc = lib.aspire_topk_merge_keys(ptr(src), world, K, TOPK, TOPK, lane.P[1], lane.P[2], lane.sp)
+            rc = lib.aspire_topk_merge_keys(ptr(src), world, n, TOPK, TOPK, lane.P[1], lane.P[2], lane.sp)
             if rc:
                 _lib.check(rc)
 
@@ -581,21 +599,10 @@ def main():
         if rc:
             _lib.check(rc)
 
-    # ---- W untimed warm-up steps, then a calibration pass that sizes R ----------------------------------------------
+    # ---- W untimed warm-up steps (at least one call per lane) ------------------------------------------------------
     for r in range(max(n_lanes, -(-args.warmup // K))):
         run_schedule(sets[r % len(sets)], lanes[r % n_lanes])
     torch.cuda.synchronize()
-    if args.repeats > 0:
-        R = args.repeats
-    else:
-        t0 = time.perf_counter()
-        n_cal = 4 * n_lanes
-        for r in range(n_cal):
-            run_schedule(sets[r % len(sets)], lanes[r % n_lanes])
-        torch.cuda.synchronize()
-        per_call = (time.perf_counter() - t0) / n_cal
-        R = max(4, int(1.3 * MIN_TIMED_S / per_call) + 1)
-        R = int(reduce_max(R))
 
     def timed(fn):
         if world > 1:
@@ -608,22 +615,34 @@ def main():
         torch.cuda.synchronize()          # every stream of the device
         return reduce_max(time.perf_counter() - t0)
 
-    def all_reps(use=None, reps=None):
-        use = use or lanes
-        for r in range(reps or R):
-            run_schedule(sets[r % len(sets)], use[r % len(use)])
+    def timed_calls():
+        for r, js in enumerate(timed_sets):
+            run_schedule(js, lanes[r % n_lanes])
+
+    def one_lane_calls(reps):
+        for r in range(reps):
+            run_schedule(sets[r % len(sets)], lanes[0])
 
     # untimed: clocks settle on the workload itself (~0.3 s), beyond the W warm-up steps
     t_settle = time.perf_counter()
     while time.perf_counter() - t_settle < 0.3:
         for r in range(8):
-            run_schedule(sets[r % len(sets)], lanes[r % n_lanes], exchange=False)      # time-based loop: no collective inside
+            # time-based loop: no collective inside (one rank: the merge keeps each lane's ranked rows those of its scores)
+            run_schedule(sets[r % len(sets)], lanes[r % n_lanes], exchange=world == 1)
         torch.cuda.synchronize()
 
-    elapsed = timed(all_reps)             # EXACTLY K steps x R repetitions, timed once
+    elapsed = timed(timed_calls)          # EXACTLY --steps steps, timed once
+    if args.dump_outputs and rank == 0:
+        # the last step's outputs, before anything else writes its lane
+        ln, j = lanes[(n_calls - 1) % n_lanes], timed_sets[-1].n - 1
+        dump = {'scores': ln.scores[j * NC:(j + 1) * NC].cpu().numpy(), 'top_scores': ln.top_s[j].cpu().numpy(),
+                'top_indices': ln.top_i[j].cpu().numpy().astype('float64')}
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in dump.items():
+            np.save(os.path.join(args.dump_outputs, f'{name}.npy'), arr)
     # the same schedule with ONE call at a time (lane 0 alone), for the record: not the reported value
-    R1 = max(4, R // 2)
-    elapsed_one = timed(lambda: all_reps(lanes[:1], R1)) if n_lanes > 1 else elapsed * R1 / R
+    R1 = max(4, n_calls // 2)
+    elapsed_one = timed(lambda: one_lane_calls(R1)) if n_lanes > 1 else elapsed * R1 * K / n_steps
 
     # ---- checks on every lane's last outputs ------------------------------------------------------------------------
     torch.cuda.synchronize()
@@ -748,7 +767,7 @@ def main():
 
         bytes_per_launch = algorithmic_bytes(K)
         achieved = bytes_per_launch / (cost_ms * 1e-3) / 1e9
-        step_achieved = bytes_per_launch * R / elapsed / 1e9
+        step_achieved = algorithmic_bytes(n_steps) / elapsed / 1e9
         traffic = None
         tpath = os.path.join(ROOT, 'profiles', 'traffic.json')
         if os.path.exists(tpath):
@@ -756,20 +775,20 @@ def main():
             if tj.get('jobs_per_launch') == K:
                 traffic = tj.get('cost_kernel_hbm_bytes_per_launch')
         out = {
-            'metric': 'query x candidate OT alignments/sec', 'value': world * K * R * NC / elapsed,
-            'unit': 'alignments/s', 'n_gpus': world, 'steps': K, 'warmup': args.warmup, 'repeats': R,
-            'ms_per_step': elapsed / (K * R) * 1e3, 'higher_is_better': True, 'scaling': 'weak',
+            'metric': 'query x candidate OT alignments/sec', 'value': world * n_steps * NC / elapsed,
+            'unit': 'alignments/s', 'n_gpus': world, 'steps': n_steps, 'warmup': args.warmup, 'calls': n_calls,
+            'ms_per_step': elapsed / n_steps * 1e3, 'higher_is_better': True, 'scaling': 'weak',
             'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
             'timed_region_ms': elapsed * 1e3,
             'config': {'workload': f'otAspire compsci: 1 query x {NC} candidates per step (per GPU), {S} sents x {D}d, Sinkhorn OT '
                                    f'(blur 0.05, scaling 0.9, one eps schedule per pair) + stable top-{TOPK} rank; every step its own '
                                    f'query and its own pool, {M} distinct pools ({M * algorithmic_bytes(1) / 2**20:.0f} MiB > 256 MiB L3) '
-                                   f'walked by consecutive repetitions'
+                                   f'walked by consecutive calls'
                                    + (f'; sharded: one RCCL all-gather of {K} x {TOPK} keys per call + merge kernel' if shard_path else ''),
                        'queries_per_step': 1, 'candidates_per_gpu_per_step': NC, 'sents': S, 'dim': D, 'topk': TOPK,
                        'parallelism': f'candidate-pool shards x{world}',
-                       'launch': f'the {K} steps of a schedule = {K} independent (query, pool) jobs in ONE aspire_ot_rank_batch_f32 call '
-                                 f'(eager, no hipGraph); schedule repeated {R}x for a >= 50 ms timed region, the repetitions round-robin on '
+                       'launch': f'{K} steps = {K} independent (query, pool) jobs per aspire_ot_rank_batch_f32 call '
+                                 f'(eager, no hipGraph); {n_calls} calls for the {n_steps} timed steps (the last one holds the remainder), round-robin on '
                                  f'{n_lanes} caller stream(s) with their own outputs and workspaces = {n_lanes} independent calls in flight '
                                  f'(a call\'s solve tail and rank launch overlap the next call\'s streaming); one call at a time: see one_stream',
                        'streams': n_lanes},
@@ -787,7 +806,7 @@ def main():
                          'algorithmic_bytes_per_launch': bytes_per_launch, 'jobs_per_launch': K, 'data': 'cold (rotating pools, > L3)',
                          'l3_resident_frac': algorithmic_bytes(n_l3) / (cost_l3_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if cost_l3_ms else None,
                          'l3_resident': {'jobs': n_l3, 'kernel_ms': cost_l3_ms, 'bytes': algorithmic_bytes(n_l3)},
-                         'stages_ms': {'tables+boxes': prep_ms, 'score': cost_ms, 'rank': rank_ms, 'call_elapsed': elapsed / R * 1e3,
+                         'stages_ms': {'tables+boxes': prep_ms, 'score': cost_ms, 'rank': rank_ms, 'call_elapsed': elapsed * K / n_steps * 1e3,
                                        'note': 'score = ONE launch (costs + Sinkhorn solves; a pair whose shifted sums leave fp32 range is re-solved in the max-shifted form by the wave that finds it), rank = the rank launch'},
                          'two_kernel_form': {'cost_ms': cost_only_ms, 'sinkhorn_ms': solve_only_ms,
                                              'cost_frac': bytes_per_launch / (cost_only_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if cost_only_ms else None},

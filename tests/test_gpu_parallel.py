@@ -124,14 +124,13 @@ def test_bench_two_ranks_on_one_gpu():
     and the checks bench.py itself makes on the merged ranking (every rank identical, candidates of both shards)"""
     env = dict(os.environ, ASPIRE_BENCH_ONE_GPU='1', MASTER_ADDR='127.0.0.1', ASPIRE_BENCH_E2E_DOCS='256')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
-           '--master-port', str(_free_port()), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '20', '--warmup', '5',
-           '--repeats', '6']
+           '--master-port', str(_free_port()), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '120', '--warmup', '5']
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     import json
     line = [l for l in out.stdout.splitlines() if l.startswith('{')][-1]
     j = json.loads(line)
-    assert j['n_gpus'] == 2 and j['steps'] == 20 and j['value'] > 0
+    assert j['n_gpus'] == 2 and j['steps'] == 120 and j['calls'] == 6 and j['value'] > 0
     # what the collective backend saw, gathered from every rank (gloo here; 'nccl' and distinct device uuids on a real node)
     r = j['rccl']
     assert r['ranks_seen'] == [0, 1] and r['world_size'] == 2 and r['backend'] == 'gloo'

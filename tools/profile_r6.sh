@@ -8,14 +8,14 @@ OUT=$R/gpurun_out/prof6
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 run() { name=$1; shift; timeout 400 "$@" > $OUT/$name.log 2>&1 || echo "$name: rc=$?"; }
-BENCH="python $R/bench.py --steps 20 --warmup 5 --streams 1 --no-cpu-baseline --no-probes"
+BENCH="python $R/bench.py --warmup 5 --streams 1 --no-cpu-baseline --no-probes"
 SQ="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVES"
 # 1. the bench workload, one call at a time: kernel durations, HBM traffic of the scoring kernel, its issue mix
-run bench_stats rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_stats -o bench -- $BENCH --repeats 60
-run bench_stats_s3 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_stats_s3 -o bench -- python $R/bench.py --steps 20 --warmup 5 --repeats 60 --no-cpu-baseline --no-probes
-run pmc_fetch rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o pmc -- $BENCH --repeats 6
-run pmc_write rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -o pmc -- $BENCH --repeats 6
-run pmc_sq_bench rocprofv3 --pmc $SQ --output-format csv -d $OUT/pmc_sq_bench -o pmc -- $BENCH --repeats 6
+run bench_stats rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_stats -o bench -- $BENCH --steps 1200
+run bench_stats_s3 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_stats_s3 -o bench -- python $R/bench.py --steps 1200 --warmup 5 --no-cpu-baseline --no-probes
+run pmc_fetch rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o pmc -- $BENCH --steps 120
+run pmc_write rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -o pmc -- $BENCH --steps 120
+run pmc_sq_bench rocprofv3 --pmc $SQ --output-format csv -d $OUT/pmc_sq_bench -o pmc -- $BENCH --steps 120
 # 2. config 4's shape: the CHUNK form's launches, their HBM traffic
 for m in ot l2max; do
   run csf_${m}_stats rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/csf_${m}_stats -o csf -- python $R/tools/csfprof.py $m 40
