@@ -12,6 +12,8 @@ Same contract as the reference's ``prepare_abstracts`` / ``prepare_bert_sentence
 Besides the reference's return values, ``spans_to_csr`` flattens the ragged index lists into the
 (tok_idx, span_off) arrays aspire_span_mean_pool_f32 consumes.
 """
+import re
+
 import torch
 
 MAX_NUM_TOKS = 500
@@ -111,3 +113,43 @@ def spans_to_csr(batch_senttok_idxs, max_sents):
             off.append(len(flat))
     return (torch.tensor(flat if flat else [0], dtype=torch.int32)[:len(flat)].contiguous(),
             torch.tensor(off, dtype=torch.int32))
+
+
+# ---- the SPECTER-CoCite bi-encoder's inputs (aspire_amd/bienc.py): one whole-abstract sequence per document --------------------
+_SEP_RE = re.compile(r'\[SEP\]')
+
+
+def prepare_bert_seqs(sents, tokenizer):
+    """SentTripleBatcher.prepare_bert_sentences (src/learning/batchers.py:209-254): every string is ONE sequence, cut to its
+    first 500 word pieces, [CLS] ids [SEP]; ids, segment ids and attention mask right-padded with ``tokenizer.pad_token_id``.
+    :return: bert_batch dict('tokid_tt', 'seg_tt', 'attnmask_tt', 'seq_lens'), tokenized_text list(list(str)),
+             tokenized_batch list(list(int)) (the padded ids)."""
+    tokenized_text, tokenized_batch = [], []
+    for pieces, piece_ids in _word_pieces(tokenizer, list(sents)):
+        tokenized_text.append(pieces[:MAX_NUM_TOKS])
+        tokenized_batch.append(_with_special_tokens(tokenizer, piece_ids[:MAX_NUM_TOKS]))
+    seq_lens = [len(x) for x in tokenized_batch]
+    max_seq_len = max(seq_lens) if seq_lens else -1
+    pad = tokenizer.pad_token_id
+    seg, att = [], []
+    for ids in tokenized_batch:
+        n_pad = max_seq_len - len(ids)
+        seg.append([0] * len(ids) + [pad] * n_pad)
+        att.append([1] * len(ids) + [pad] * n_pad)
+        ids.extend([pad] * n_pad)
+    bert_batch = {'tokid_tt': torch.tensor(tokenized_batch), 'seg_tt': torch.tensor(seg), 'attnmask_tt': torch.tensor(att),
+                  'seq_lens': seq_lens}
+    return bert_batch, tokenized_text, tokenized_batch
+
+
+def prepare_abstract_seqs(batch_abs, pt_lm_tokenizer):
+    """AbsTripleBatcher.prepare_abstracts (src/learning/batchers.py:303-321): title and sentences, each with any literal
+    '[SEP]' removed, joined by ' [SEP] ' into one sequence per document.  :return: bert_batch (prepare_bert_seqs)."""
+    seqs = [' [SEP] '.join(_SEP_RE.sub('', s) for s in [ex_abs['TITLE']] + list(ex_abs['ABSTRACT'])) for ex_abs in batch_abs]
+    return prepare_bert_seqs(seqs, pt_lm_tokenizer)[0]
+
+
+def prepare_eval_seqs(batch_papers, tokenizer):
+    """TrainedAbstractModel.encode's input (src/evaluation/utils/models.py:557-563): TITLE + ' [SEP] ' + ' '.join(ABSTRACT), no
+    '[SEP]' removal.  :return: bert_batch (prepare_bert_seqs)."""
+    return prepare_bert_seqs([p['TITLE'] + ' [SEP] ' + ' '.join(p['ABSTRACT']) for p in batch_papers], tokenizer)[0]

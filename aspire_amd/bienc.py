@@ -1,0 +1,190 @@
+"""AspireBiEnc: the SPECTER-CoCite whole-abstract bi-encoder, drop-in for the class of the same name in
+examples/ex_aspire_bienc.py:33-58 and for the test-time surface of MySPECTER
+(src/learning/facetid_models/disent_models.py:53-205), the ``cospecter`` model of evaluate.py
+(src/evaluation/utils/models.py:509-566).
+
+    model = AspireBiEnc(bert_model=BertModel.from_pretrained(...))
+    model.load_state_dict(torch.load('model_cur_best.pt'))         # bert_encoder.* + bert_layer_weights.weight [1, 13]
+    doc_reps = model.forward(tokenizer(texts, padding=True, return_tensors='pt'))     # [B, 768]
+
+A document's rep is the CLS row of a learned softmax mix of all n_layers + 1 hidden states (``*-full`` checkpoints), or of the last
+hidden state alone when there are no mix weights (the README's plain AutoModel use).  Both come out of ONE library call,
+aspire_bert_forward_cls_f32 (include/aspire_hip.h): the encoder of HipBertEncoder with the CLS rows tapped after every layer and a last
+layer that computes the CLS rows only.  The mix weights are softmaxed on the host, as SoftmaxMixLayers does, and passed in.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import ops
+from ._lib import check, lib
+from .encoder import HipBertEncoder
+
+
+def split_state_dict(sd):
+    """The reference's state dict (AspireBiEnc / MySPECTER) -> (the BertModel's own state dict, layer weights [1, n + 1] or None).
+    Keys: ``bert_encoder.<BertModel key>`` and ``bert_layer_weights.weight``; anything else is an error."""
+    enc, mix, other = {}, None, []
+    for k, v in sd.items():
+        if k.startswith('bert_encoder.'):
+            enc[k[len('bert_encoder.'):]] = v
+        elif k == 'bert_layer_weights.weight':
+            mix = v
+        else:
+            other.append(k)
+    if other:
+        raise KeyError(f'unexpected keys in the bi-encoder state dict: {other}')
+    if mix is not None and (mix.dim() != 2 or mix.shape[0] != 1):
+        raise ValueError(f'bert_layer_weights.weight: expected [1, n_layers + 1], got {tuple(mix.shape)}')
+    return enc, mix
+
+
+def _batch_tensors(bert_batch):
+    """The README's HF tokenizer dict (input_ids / token_type_ids / attention_mask) or the batchers' (tokid_tt / seg_tt / attnmask_tt)."""
+    if 'input_ids' in bert_batch:
+        return bert_batch['input_ids'], bert_batch.get('token_type_ids'), bert_batch.get('attention_mask')
+    return bert_batch['tokid_tt'], bert_batch.get('seg_tt'), bert_batch.get('attnmask_tt')
+
+
+class AspireBiEnc:
+    def __init__(self, model_hparams=None, bert_model=None, layer_weights=None):
+        """
+        :param model_hparams: dict with 'base-pt-layer' (the HF model the reference loads, ex_aspire_bienc.py:40).
+        :param bert_model: an already constructed transformers BertModel (weights are copied to the GPU).
+        :param layer_weights: the SoftmaxMixLayers weight [1, n_layers + 1] (before the softmax), or None: last_hidden_state[:, 0].
+        """
+        self.bert_encoding_dim = 768
+        if bert_model is None:
+            from transformers import AutoModel
+            bert_model = AutoModel.from_pretrained(model_hparams['base-pt-layer'])
+        self.bert_encoder = HipBertEncoder(bert_model)
+        self.bert_layer_count = self.bert_encoder.config.num_hidden_layers + 1   # plus 1 for the bottom most layer
+        self.layer_weights = None
+        if layer_weights is not None:
+            self.set_layer_weights(layer_weights)
+        self._ws = {}
+
+    def eval(self):
+        return self
+
+    def set_layer_weights(self, w):
+        w = torch.as_tensor(w).detach().to('cpu', torch.float32).reshape(1, -1)
+        if w.shape[1] != self.bert_layer_count:
+            raise ValueError(f'layer weights: expected {self.bert_layer_count}, got {w.shape[1]}')
+        self.layer_weights = w
+
+    def load_state_dict(self, sd):
+        """AspireBiEnc / MySPECTER state dict: the encoder is rebuilt from bert_encoder.*, the mix from bert_layer_weights.weight."""
+        enc, mix = split_state_dict(sd)
+        if enc:
+            from transformers import BertModel
+            bm = BertModel(self.bert_encoder.config, add_pooling_layer=any(k.startswith('pooler.') for k in enc))
+            bm.load_state_dict(enc)
+            self.bert_encoder = HipBertEncoder(bm)
+            self.bert_layer_count = self.bert_encoder.config.num_hidden_layers + 1
+        self.layer_weights = None
+        if mix is not None:
+            self.set_layer_weights(mix)
+        return self
+
+    def layer_mix(self):
+        """softmax(W, dim=1) as SoftmaxMixLayers.forward computes it (ex_aspire_bienc.py:24-29), [n_layers + 1] float32, or None."""
+        if self.layer_weights is None:
+            return None
+        return torch.softmax(self.layer_weights, dim=1)[0].numpy().astype(np.float32)
+
+    # ---- the forward ---------------------------------------------------------------------------------------------------
+    def _call(self, tok, typ, msk, want_layers):
+        enc = self.bert_encoder
+        b, l = tok.shape
+        n = enc.config.num_hidden_layers
+        dev = enc.device
+        out = torch.empty(b, 768, device=dev, dtype=torch.float32)
+        layers = torch.empty(n + 1, b, 768, device=dev, dtype=torch.float32) if want_layers else None
+        mix = self.layer_mix()
+        mix_c = ctypes.cast((ctypes.c_float * len(mix))(*mix.tolist()), ctypes.c_void_p) if mix is not None else None
+        need = lib.aspire_bert_cls_workspace_bytes(ctypes.byref(enc._w), b, l)
+        sid = torch.cuda.current_stream().cuda_stream
+        ws = self._ws.get(sid)
+        if ws is None or ws.numel() < need:
+            self._ws[sid] = ws = torch.empty(max(need, 16), device=dev, dtype=torch.uint8)
+        check(lib.aspire_bert_forward_cls_f32(ctypes.byref(enc._w), ops._ptr(tok), ops._ptr(typ), ops._ptr(msk), b, l, mix_c,
+                                              ops._ptr(out), ops._ptr(layers), ops._ptr(ws), ws.numel(), ops._stream()))
+        return out, layers
+
+    def forward_device(self, tokid_tt, token_type_ids=None, attention_mask=None, want_layers=False):
+        """int64 [B, L] tensors (any device) -> (cls reps [B, 768], the CLS rows of every hidden state [n_layers + 1, B, 768] or None),
+        on the GPU.  Same rules as AspireConSent: a LayerNorm-epilogue timeout runs the batch again with the separate LayerNorm pass,
+        non-finite output (an activation beyond the fp16 planes' range) again on the full-range kernels."""
+        enc = self.bert_encoder
+        dev = enc.device
+        tok = tokid_tt.to(device=dev, dtype=torch.int64).contiguous()
+        if tok.numel() and (int(tok.max()) >= enc.config.vocab_size or int(tok.min()) < 0):
+            raise IndexError('token id out of range')   # nn.Embedding raises IndexError on the reference path
+        typ = token_type_ids.to(device=dev, dtype=torch.int64).contiguous() if token_type_ids is not None else None
+        msk = attention_mask.to(device=dev, dtype=torch.int64).contiguous() if attention_mask is not None else torch.ones_like(tok)
+        from ._lib import pinned
+        import warnings
+        out, layers = self._call(tok, typ, msk, want_layers)
+        if enc.status():
+            warnings.warn('AspireBiEnc: the fused GEMM + LayerNorm exchange timed out; encoding again with ASPIRE_HIP_GEMM_LN=off')
+            with pinned(GEMM_LN='off'):
+                out, layers = self._call(tok, typ, msk, want_layers)
+        if not bool(torch.isfinite(out).all()) or (layers is not None and not bool(torch.isfinite(layers).all())):
+            warnings.warn('AspireBiEnc.forward: non-finite reps on the fp16-plane encoder path (an activation beyond 65504); '
+                          'encoding the batch again with ASPIRE_HIP_GEMM=bf16x3, ASPIRE_HIP_ATTN=f32')
+            with pinned(GEMM='bf16x3', ATTN='f32'):
+                out, layers = self._call(tok, typ, msk, want_layers)
+        return out, layers
+
+    def forward(self, bert_batch):
+        """AspireBiEnc.forward (ex_aspire_bienc.py:46-58): [B, 768] CLS reps, on the device of the input ids."""
+        tok, typ, msk = _batch_tensors(bert_batch)
+        return self.forward_device(tok, typ, msk)[0].to(tok.device)
+
+    def __call__(self, bert_batch):
+        return self.forward(bert_batch)
+
+    def partial_forward(self, bert_batch):
+        """MySPECTER.partial_forward (disent_models.py:164-176): [B, 768] on the GPU (a 1-document batch stays [1, 768])."""
+        tok, typ, msk = _batch_tensors(bert_batch)
+        return self.forward_device(tok, typ, msk)[0]
+
+    # ---- MySPECTER's test-time surface ----------------------------------------------------------------------------------
+    def caching_encode(self, batch_dict):
+        """MySPECTER.caching_encode (disent_models.py:96-114): -> list of {'doc_cls_reps': np [768]}."""
+        reps = self.partial_forward(batch_dict['bert_batch']).cpu().numpy()
+        return [{'doc_cls_reps': reps[i, :]} for i in range(reps.shape[0])]
+
+    def encode(self, batch_dict):
+        """MySPECTER.encode (disent_models.py:116-129): -> {'doc_reps': np [B, 768]}."""
+        return {'doc_reps': self.partial_forward(batch_dict['bert_batch']).cpu().numpy()}
+
+    @staticmethod
+    def caching_score(query_encode_ret_dict, cand_encode_ret_dicts):
+        """MySPECTER.caching_score (disent_models.py:56-94): -pairwise_distance(q, c, p=2, eps=1e-6) of the query against every
+        candidate (aspire_cls_l2_f32, PAIRED) -> {'batch_scores', 'pair_scores'} (the same squeezed array twice)."""
+        gpu = ops.require_gpu()
+        c = torch.from_numpy(np.vstack([d['doc_cls_reps'] for d in cand_encode_ret_dicts]).astype(np.float32)).to(gpu)
+        q = torch.from_numpy(np.asarray(query_encode_ret_dict['doc_cls_reps'], dtype=np.float32).reshape(1, -1)).to(gpu)
+        scores = (-1 * ops.cls_l2(q.expand(c.shape[0], -1).contiguous(), c, eps=1e-6)).squeeze().cpu().numpy()
+        return {'batch_scores': scores, 'pair_scores': scores}
+
+    # ---- corpus encoding ------------------------------------------------------------------------------------------------
+    def encode_to_store(self, batches, pids, store=None):
+        """Every bert_batch of `batches` (prepare_abstract_seqs / prepare_eval_seqs / an HF tokenizer dict) encoded; document j
+        overall gets pid pids[j] with a [1, 768] rep.  Returns the RepStore (new, or `store` with the reps added): evaluate.score(...,
+        method='l2max') then ranks a pool by -cdist of the 1 x 1 pair = -euclidean, TrainedAbstractModel.get_similarity (models.py:565)."""
+        from .repstore import RepStore
+        store = RepStore() if store is None else store
+        pids = list(pids)
+        j = 0
+        for bb in batches:
+            reps = self.partial_forward(bb).cpu().numpy()
+            for i in range(reps.shape[0]):
+                store.add(pids[j], reps[i:i + 1])
+                j += 1
+        if j != len(pids):
+            raise ValueError(f'{len(pids)} pids for {j} documents')
+        return store

@@ -2061,6 +2061,333 @@ PlaneOffsets plane_offsets(int ffn_dim) {
     return o;
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------
+// One forward's plan -- the form every step takes, decided once from B, L, the weights and the tuning pins -- and one layer of it.
+// aspire_bert_forward_f32 runs every layer through run_layer; aspire_bert_forward_cls_f32 runs all but the last one the same way.
+// ---------------------------------------------------------------------------------------------------------------
+struct Fwd {
+    const aspire_bert_weights* w;
+    const int64_t* mask;
+    int64_t B, L, M, row_tiles;
+    int Lp, H, dh;
+    unsigned row_blocks;
+    bool pp, ln_fused, attn_p;
+    PlaneOffsets po;
+    Workspace ws;
+    hipStream_t st;
+};
+
+// the forwards' argument checks: all of them before the first launch
+int check_forward_args(const aspire_bert_weights* w, const int64_t* tok_ids, const int64_t* attn_mask, const float* out, int64_t B, int64_t L) {
+    ASPIRE_REQUIRE(w && tok_ids && attn_mask && out, ASPIRE_ERR_INVALID_ARG, "null pointer");
+    ASPIRE_REQUIRE(w->hidden == kD && w->n_heads == 12 && w->ffn_dim % 64 == 0 && w->ffn_dim > 0, ASPIRE_ERR_UNSUPPORTED,
+                   "only BERT-base geometry is built (hidden 768, 12 heads); got hidden %d heads %d", w->hidden, w->n_heads);
+    ASPIRE_REQUIRE(B >= 0 && L > 0 && L <= 512 && L <= w->max_pos, ASPIRE_ERR_INVALID_ARG,
+                   "sequence length %lld outside (0, min(512, max_position_embeddings=%d)]", (long long)L, w->max_pos);
+    ASPIRE_REQUIRE(w->n_layers >= 0 && (w->n_layers == 0 || w->layers), ASPIRE_ERR_INVALID_ARG, "bad layer table");
+    return ASPIRE_OK;
+}
+
+int plan_forward(Fwd& f, const aspire_bert_weights* w, const int64_t* attn_mask, int64_t B, int64_t L, void* workspace, hipStream_t st) {
+    f.w = w;
+    f.mask = attn_mask;
+    f.B = B;
+    f.L = L;
+    f.st = st;
+    f.ws = carve(workspace, B, L, w->n_heads, w->ffn_dim, w->n_layers);
+    f.M = B * L;
+    f.Lp = (int)((L + 3) / 4 * 4);
+    f.H = w->n_heads;
+    f.dh = kD / f.H;
+    f.row_blocks = (unsigned)((f.M + 3) / 4);
+    // P path: the weights' planes are prepared (aspire_bert_prepare_planes), BERT-base shapes tile by 128 -- every nn.Linear GEMM
+    // streams pre-split fp16 operands (gemm_p_kernel), from 1024 token rows on (measured B x L = 4 x 128: 2.46 vs 2.42 ms per batch,
+    // 8 x 128: 2.55 vs 2.81, 16 x 128: 2.90 vs 3.52, 32 x 256: 6.64 vs 9.8); below -- and with ASPIRE_HIP_GEMM=f32 | bf16x3, or without
+    // planes -- the round-2 kernels, which pick smaller tiles for small M
+    f.pp = w->planes != nullptr && (tuning().gemm_form == 0 ? f.M >= 1024 : tuning().gemm_form == 3) && f.dh == 64 && !tuning().attn_gemm &&
+           w->ffn_dim % 128 == 0;
+    f.po = plane_offsets(w->ffn_dim);
+    // LayerNorm in the N = 768 GEMMs' epilogue (ASPIRE_HIP_GEMM_LN=off: the separate layernorm_kernel pass)
+    // from 48 row tiles on (measured, fused / separate ms per batch: 64 x 256 9.00 - 9.18 / 9.45, 128 x 128 8.99 / 9.40, 64 x 128 5.05 / 5.15,
+    // 32 x 256 5.16 / 5.30, 40 x 100 3.09 / 3.17, 16 x 256 3.18 / 3.14, 8 x 256 2.37 / 2.30: below, the launch is a fraction of one round of
+    // workgroups and a waiting workgroup has nothing running under it)
+    f.row_tiles = (f.M + 127) / 128;
+    f.ln_fused = f.pp && (tuning().gemm_ln == 2 || (tuning().gemm_ln == 0 && f.row_tiles >= 48 && ln_fused_supported()));
+    // Round 6 (default on the plane path; ASPIRE_HIP_ATTN=f16x2 pins round 5's form, which splits fp32 Q / K / V inside the attention kernel):
+    // the QKV GEMM writes the attention's operands as fp16 planes, the attention stages them by LDS-DMA (flash_attn_p_kernel)
+    f.attn_p = f.pp && w->n_layers > 0 && tuning().attn_form != 1 && !tuning().attn_f32 && tuning().gemm_tile == 0;
+    return ASPIRE_OK;
+}
+
+// embeddings + LayerNorm -> x (fp32) and, on the P path, actp; then the LayerNorm-epilogue counters of this forward
+int launch_embed(const Fwd& f, const int64_t* tok_ids, const int64_t* type_ids, float* x) {
+    const aspire_bert_weights* w = f.w;
+    hipLaunchKernelGGL(embed_layernorm_kernel, dim3(f.row_blocks), dim3(256), 0, f.st, tok_ids, type_ids, w->word_emb, w->pos_emb,
+                       w->type_emb, w->emb_ln_g, w->emb_ln_b, w->ln_eps, x, f.M, f.L, f.pp && w->n_layers > 0 ? f.ws.actp : nullptr);
+    ASPIRE_LAUNCH_OK();
+    // the P layout's slot offsets are 32-bit byte offsets (p_slot / p_slot8: ((k >> 4) R + r) << 6): the widest operand is [M, ffn_dim]
+    ASPIRE_REQUIRE(!f.pp || (uint64_t)f.M * (uint64_t)(w->ffn_dim > 3 * kD ? w->ffn_dim : 3 * kD) * 4 < (1ull << 32), ASPIRE_ERR_UNSUPPORTED,
+                   "%lld token rows in one forward: the fp16-plane layout addresses < 4 GB per operand (split the batch)", (long long)f.M);
+    if (f.ln_fused && w->n_layers > 0) ASPIRE_HIP_OK(hipMemsetAsync(f.ws.ln_count, 0, f.ws.ln_count_bytes, f.st));
+    return ASPIRE_OK;
+}
+
+// layer l: x (its input, fp32; on the fused form the input lives in actp) -> out.  last: out is the caller's [M, 768] and no P copy of
+// it is written.  qkv_only: step 1 alone (the CLS forward's last layer)
+int run_layer(const Fwd& f, int l, const float* x, float* out, bool last, bool qkv_only) {
+    const aspire_bert_weights* w = f.w;
+    const Workspace& ws = f.ws;
+    const PlaneOffsets& po = f.po;
+    const bool pp = f.pp, ln_fused = f.ln_fused, attn_p = f.attn_p;
+    const int64_t B = f.B, L = f.L, M = f.M, row_tiles = f.row_tiles;
+    const int Lp = f.Lp, H = f.H, dh = f.dh;
+    const unsigned row_blocks = f.row_blocks;
+    const int64_t* attn_mask = f.mask;
+    hipStream_t st = f.st;
+    const aspire_bert_layer& ly = w->layers[l];
+    const char* lp = (const char*)w->planes + (size_t)l * po.per_layer;
+    GemmArgs g{};
+    PGemmArgs pg{};
+    // 1. fused QKV projection: qkv [M, 2304] = x . Wqkv^T + bqkv
+    if (attn_p) {
+        // Q, K and V go out as the attention kernel's fp16 planes (no fp32 qkv exists in this form)
+        pg = PGemmArgs{ws.actp, lp + po.qkv, nullptr, nullptr, ly.b_qkv, nullptr, (int)M, 3 * kD, kD, 0, 0, 0};
+        pg.Xp = ws.qkvp;
+        if (int rc = launch_gemm_p_qkv(pg, st)) return rc;
+    } else if (pp) {
+        pg = PGemmArgs{ws.actp, lp + po.qkv, ws.qkv, nullptr, ly.b_qkv, nullptr, (int)M, 3 * kD, kD, 3 * kD, 0, 0};
+        if (int rc = launch_gemm_p<false>(pg, st)) return rc;
+    } else {
+        g = GemmArgs{};
+        g.A = x; g.B = ly.w_qkv; g.C = ws.qkv; g.bias = ly.b_qkv;
+        g.M = (int)M; g.N = 3 * kD; g.K = kD; g.lda = kD; g.ldb = kD; g.ldc = 3 * kD; g.nz2 = 1; g.alpha = 1.f;
+        if (int rc = launch_gemm<false>(g, 1, st)) return rc;
+    }
+    if (qkv_only) return ASPIRE_OK;
+    // 2-4. attention.  Fused kernel (scores never leave the chip) unless ASPIRE_HIP_ATTN=gemm pins the
+    // three-kernel form (QK^T GEMM, masked soft-max, PV GEMM) that the fused one is tested against.
+    if (attn_p) {
+        const unsigned qblocks = (unsigned)((L + 127) / 128);
+        if (tuning().attn_form == 2)
+            hipLaunchKernelGGL(flash_attn_p64_kernel, dim3((unsigned)(B * H) * qblocks), dim3(256), 0, st, ws.qkvp, attn_mask, ws.ctx, (int)L, H, ws.ctxp, M);
+        else
+            hipLaunchKernelGGL(flash_attn_p_kernel, dim3((unsigned)(B * H) * qblocks), dim3(256), 0, st, ws.qkvp, attn_mask, ws.ctx, (int)L, H, ws.ctxp, M);
+        ASPIRE_LAUNCH_OK();
+    } else if (dh == 64 && !tuning().attn_gemm) {
+        const unsigned qblocks = (unsigned)((L + 127) / 128);
+        if (tuning().attn_f32)
+            hipLaunchKernelGGL(flash_attn_f32_kernel, dim3((unsigned)(B * H) * qblocks), dim3(256), 0, st, ws.qkv, attn_mask, ws.ctx,
+                               (int)L, H, pp ? ws.ctxp : nullptr, M);
+        else
+            hipLaunchKernelGGL(flash_attn_f16x2_kernel, dim3((unsigned)(B * H) * qblocks), dim3(256), 0, st, ws.qkv, attn_mask, ws.ctx,
+                               (int)L, H, pp ? ws.ctxp : nullptr, M);
+        ASPIRE_LAUNCH_OK();
+    } else {
+        // 2. scores[b,h] = Q_bh . K_bh^T   (scale and mask are applied by the softmax kernel)
+        g = GemmArgs{};
+        g.A = ws.qkv; g.B = ws.qkv + kD; g.C = ws.scores;
+        g.M = (int)L; g.N = (int)L; g.K = dh; g.lda = 3 * kD; g.ldb = 3 * kD; g.ldc = Lp; g.nz2 = H; g.alpha = 1.f;
+        g.sa1 = (long long)L * 3 * kD; g.sa2 = dh; g.sb1 = g.sa1; g.sb2 = dh;
+        g.sc1 = (long long)H * L * Lp; g.sc2 = (long long)L * Lp;
+        if (int rc = launch_gemm<false>(g, (int)(B * H), st)) return rc;
+        // 3. masked softmax over keys
+        const int64_t srows = B * H * L;
+        hipLaunchKernelGGL(softmax_mask_kernel, dim3((unsigned)((srows + 3) / 4)), dim3(256), 0, st, ws.scores, attn_mask, srows,
+                           (int)L, Lp, (int)(H * L), 1.0f / sqrtf((float)dh));
+        ASPIRE_LAUNCH_OK();
+        // 4. ctx[b, :, h*64:(h+1)*64] = P_bh . V_bh        (V is [K = L keys, N = 64] n-contiguous)
+        g = GemmArgs{};
+        g.A = ws.scores; g.B = ws.qkv + 2 * kD; g.C = ws.ctx;
+        g.M = (int)L; g.N = dh; g.K = (int)L; g.lda = Lp; g.ldb = 3 * kD; g.ldc = kD; g.nz2 = H; g.alpha = 1.f;
+        g.sa1 = (long long)H * L * Lp; g.sa2 = (long long)L * Lp; g.sb1 = (long long)L * 3 * kD; g.sb2 = dh;
+        g.sc1 = (long long)L * kD; g.sc2 = dh;
+        if (int rc = launch_gemm<true>(g, (int)(B * H), st)) return rc;
+    }
+    // 5. attention output projection + residual, LayerNorm
+    if (ln_fused) {
+        // x lives in actp (written by the embedding LayerNorm / the previous layer's FFN2 epilogue, read by the QKV GEMM): read as the
+        // residual and replaced by h = LN1(.) slot by slot; no fp32 copy of x or h exists in this form
+        pg = PGemmArgs{ws.ctxp, lp + po.o, nullptr, ws.actp, ly.b_o, nullptr, (int)M, kD, kD, kD, kD, 0};
+        pg.resp = ws.actp;
+        pg.gamma = ly.ln1_g; pg.beta = ly.ln1_b; pg.eps = w->ln_eps;
+        pg.ln_stats = ws.ln_stats; pg.ln_count = ws.ln_count + (size_t)(2 * l) * row_tiles;
+        if (int rc = launch_gemm_p_ln(pg, st)) return rc;
+    } else if (pp) {
+        pg = PGemmArgs{ws.ctxp, lp + po.o, ws.tmp, nullptr, ly.b_o, x, (int)M, kD, kD, kD, kD, 0};
+        if (int rc = launch_gemm_p<false>(pg, st)) return rc;
+    } else {
+        g = GemmArgs{};
+        g.A = ws.ctx; g.B = ly.w_o; g.C = ws.tmp; g.bias = ly.b_o; g.res = x; g.ldr = kD;
+        g.M = (int)M; g.N = kD; g.K = kD; g.lda = kD; g.ldb = kD; g.ldc = kD; g.nz2 = 1; g.alpha = 1.f;
+        if (int rc = launch_gemm<false>(g, 1, st)) return rc;
+    }
+    if (!ln_fused) {
+        hipLaunchKernelGGL(layernorm_kernel, dim3(row_blocks), dim3(256), 0, st, ws.tmp, ly.ln1_g, ly.ln1_b, w->ln_eps, ws.ctx, M,
+                           pp ? ws.actp : nullptr);
+        ASPIRE_LAUNCH_OK();
+    }
+    // 6. FFN: GELU(h . W1^T + b1) . W2^T + b2 + h, LayerNorm          (h = ws.ctx)
+    if (pp) {
+        pg = PGemmArgs{ws.actp, lp + po.ffn1, nullptr, ws.ffnp, ly.b_ffn1, nullptr, (int)M, w->ffn_dim, kD, 0, 0, 0};
+        if (int rc = launch_gemm_p<true>(pg, st)) return rc;
+        if (ln_fused) {
+            pg = PGemmArgs{ws.ffnp, lp + po.ffn2, last ? out : nullptr, last ? nullptr : ws.actp, ly.b_ffn2, nullptr, (int)M, kD, w->ffn_dim, kD, kD, 0};
+            pg.resp = ws.actp;
+            pg.gamma = ly.ln2_g; pg.beta = ly.ln2_b; pg.eps = w->ln_eps;
+            pg.ln_stats = ws.ln_stats; pg.ln_count = ws.ln_count + (size_t)(2 * l + 1) * row_tiles;
+            if (int rc = launch_gemm_p_ln(pg, st)) return rc;
+        } else {
+            pg = PGemmArgs{ws.ffnp, lp + po.ffn2, ws.tmp, nullptr, ly.b_ffn2, ws.ctx, (int)M, kD, w->ffn_dim, kD, kD, 0};
+            if (int rc = launch_gemm_p<false>(pg, st)) return rc;
+        }
+    } else {
+        g = GemmArgs{};
+        g.A = ws.ctx; g.B = ly.w_ffn1; g.C = ws.ffn; g.bias = ly.b_ffn1; g.gelu = 1;
+        g.M = (int)M; g.N = w->ffn_dim; g.K = kD; g.lda = kD; g.ldb = kD; g.ldc = w->ffn_dim; g.nz2 = 1; g.alpha = 1.f;
+        if (int rc = launch_gemm<false>(g, 1, st)) return rc;
+        g = GemmArgs{};
+        g.A = ws.ffn; g.B = ly.w_ffn2; g.C = ws.tmp; g.bias = ly.b_ffn2; g.res = ws.ctx; g.ldr = kD;
+        g.M = (int)M; g.N = kD; g.K = w->ffn_dim; g.lda = w->ffn_dim; g.ldb = w->ffn_dim; g.ldc = kD; g.nz2 = 1; g.alpha = 1.f;
+        if (int rc = launch_gemm<false>(g, 1, st)) return rc;
+    }
+    if (!ln_fused) {
+        hipLaunchKernelGGL(layernorm_kernel, dim3(row_blocks), dim3(256), 0, st, ws.tmp, ly.ln2_g, ly.ln2_b, w->ln_eps, out, M,
+                           pp && !last ? ws.actp : nullptr);
+        ASPIRE_LAUNCH_OK();
+    }
+    return ASPIRE_OK;
+}
+
+// The CLS forward's own workspace, behind the forward's (carve): the B gathered rows of the last layer
+struct ClsWorkspace {
+    float *gin, *ctx, *tmp, *h, *y, *ffn;      // residual input (hidden state n - 1), attention context, pre-norm, LN1, LN2, GELU(FFN1)
+    size_t total;
+};
+ClsWorkspace carve_cls(void* base, int64_t B, int ffn_dim) {
+    char* p = (char*)base;
+    ClsWorkspace c;
+    size_t off = 0;
+    auto take = [&](size_t nfloats) {
+        float* r = (float*)(p + off);
+        off += align_up(nfloats * sizeof(float));
+        return r;
+    };
+    c.gin = take((size_t)B * kD);
+    c.ctx = take((size_t)B * kD);
+    c.tmp = take((size_t)B * kD);
+    c.h = take((size_t)B * kD);
+    c.y = take((size_t)B * kD);
+    c.ffn = take((size_t)B * ffn_dim);
+    c.total = off;
+    return c;
+}
+
+// The CLS row (row b L) of each of the B documents of one hidden state, read from fp32 x [rows, 768] or from the P-layout planes xp
+// (the fused-LayerNorm form's actp: p_slot, as the GEMMs that write it): -> layer_cls [B, 768] and gather [B, 768] (each optional);
+// mode 1: cls_out = wt x row, 2: cls_out += wt x row, 0: cls_out untouched.  One wave per document.
+__global__ void __launch_bounds__(256) cls_tap_kernel(const float* __restrict__ x, const void* __restrict__ xp, int64_t rows, int64_t L,
+                                                      int64_t B, float wt, int mode, float* __restrict__ cls_out,
+                                                      float* __restrict__ layer_cls, float* __restrict__ gather) {
+    const int lane = threadIdx.x & 63;
+    const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const int64_t r = b * L;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const int d = 4 * lane + 256 * c;
+        const float4 v = xp ? p_load4_at(xp, p_slot((uint32_t)rows, (uint32_t)r, (uint32_t)d)) : *reinterpret_cast<const float4*>(x + r * kD + d);
+        const size_t o = (size_t)b * kD + d;
+        if (layer_cls) *reinterpret_cast<float4*>(layer_cls + o) = v;
+        if (gather) *reinterpret_cast<float4*>(gather + o) = v;
+        if (mode) {
+            float4 a = make_float4(wt * v.x, wt * v.y, wt * v.z, wt * v.w);
+            if (mode == 2) {
+                const float4 p = *reinterpret_cast<const float4*>(cls_out + o);
+                a = make_float4(p.x + a.x, p.y + a.y, p.z + a.z, p.w + a.w);
+            }
+            *reinterpret_cast<float4*>(cls_out + o) = a;
+        }
+    }
+}
+
+// Attention of the CLS query alone, one workgroup per (document, head): softmax_j(q . k_j / 8 + (mask_j ? 0 : finfo.min)) v_j over the
+// document's L <= 512 keys, in fp32 (the scores and the mask bias as softmax_mask_kernel forms them).  Q / K / V come from the fp32 qkv
+// [rows, 2304] of the round-2 / f32 / f16x2 forms, or (qkvp != NULL) from the planes [plane h | l][Q | K | V][head][rows][64] fp16 that
+// launch_gemm_p_qkv writes for flash_attn_p_kernel.  ctx [B, 768]: head h at columns 64 h .. + 63.
+__device__ __forceinline__ void cls_attn_row(const float* qkv, const unsigned char* qkvp, int which, int H, int h, int64_t rows, int64_t row,
+                                             float (&v)[64]) {
+    if (qkvp) {
+        const size_t plane_b = (size_t)3 * H * rows * 128;
+        const unsigned char* p = qkvp + ((size_t)(which * H + h) * rows + row) * 128;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            const f16x8_t hi = *reinterpret_cast<const f16x8_t*>(p + 16 * c), lo = *reinterpret_cast<const f16x8_t*>(p + plane_b + 16 * c);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[8 * c + e] = (float)hi[e] + (float)lo[e];
+        }
+    } else {
+        const float* p = qkv + row * 3 * kD + which * kD + h * 64;
+#pragma unroll
+        for (int c = 0; c < 16; ++c) {
+            const float4 t = *reinterpret_cast<const float4*>(p + 4 * c);
+            v[4 * c] = t.x, v[4 * c + 1] = t.y, v[4 * c + 2] = t.z, v[4 * c + 3] = t.w;
+        }
+    }
+}
+__device__ __forceinline__ float cls_attn_elem(const float* qkv, const unsigned char* qkvp, int which, int H, int h, int64_t rows, int64_t row, int d) {
+    if (qkvp) {
+        const unsigned char* p = qkvp + ((size_t)(which * H + h) * rows + row) * 128 + 2 * d;
+        return (float)*reinterpret_cast<const _Float16*>(p) + (float)*reinterpret_cast<const _Float16*>(p + (size_t)3 * H * rows * 128);
+    }
+    return qkv[row * 3 * kD + which * kD + h * 64 + d];
+}
+__global__ void __launch_bounds__(256) cls_attn_kernel(const float* __restrict__ qkv, const unsigned char* __restrict__ qkvp,
+                                                       const int64_t* __restrict__ mask, float* __restrict__ ctx, int L, int H, int64_t rows) {
+    __shared__ float qs[64];
+    __shared__ float pr[512];
+    __shared__ float red[4];
+    __shared__ float part[4][64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int h = (int)(blockIdx.x % H);
+    const int64_t b = blockIdx.x / H, doc0 = b * L;
+    if (tid < 64) qs[tid] = cls_attn_elem(qkv, qkvp, 0, H, h, rows, doc0, tid);
+    __syncthreads();
+    // scores: thread t takes keys t and t + 256
+    float m = -INFINITY;
+    for (int j = tid; j < L; j += 256) {
+        float k[64];
+        cls_attn_row(qkv, qkvp, 1, H, h, rows, doc0 + j, k);
+        float s = 0.f;
+#pragma unroll
+        for (int d = 0; d < 64; ++d) s = fmaf(qs[d], k[d], s);
+        s = s * 0.125f + (mask[doc0 + j] != 0 ? 0.f : -3.4028234663852886e38f);
+        pr[j] = s;
+        m = fmaxf(m, s);
+    }
+    m = wave_max(m);
+    if (lane == 0) red[wave] = m;
+    __syncthreads();
+    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    __syncthreads();
+    float sum = 0.f;
+    for (int j = tid; j < L; j += 256) {
+        const float e = expf(pr[j] - m);
+        pr[j] = e;
+        sum += e;
+    }
+    sum = wave_sum(sum);
+    if (lane == 0) red[wave] = sum;
+    __syncthreads();
+    const float inv = 1.0f / ((red[0] + red[1]) + (red[2] + red[3]));
+    // context: wave w sums keys w, w + 4, ..; lane = dim
+    float acc = 0.f;
+    for (int j = wave; j < L; j += 4) acc = fmaf(pr[j], cls_attn_elem(qkv, qkvp, 2, H, h, rows, doc0 + j, lane), acc);
+    part[wave][lane] = acc;
+    __syncthreads();
+    if (tid < 64) ctx[b * kD + h * 64 + tid] = ((part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid])) * inv;
+}
+
 }  // namespace
 }  // namespace aspire
 
@@ -2074,162 +2401,90 @@ extern "C" size_t aspire_bert_workspace_bytes(const aspire_bert_weights* w, int6
 extern "C" int aspire_bert_forward_f32(const aspire_bert_weights* w, const int64_t* tok_ids, const int64_t* type_ids,
                                        const int64_t* attn_mask, int64_t B, int64_t L, float* hidden_out, void* workspace,
                                        size_t workspace_bytes, void* stream) {
-    ASPIRE_REQUIRE(w && tok_ids && attn_mask && hidden_out, ASPIRE_ERR_INVALID_ARG, "null pointer");
-    ASPIRE_REQUIRE(w->hidden == kD && w->n_heads == 12 && w->ffn_dim % 64 == 0 && w->ffn_dim > 0, ASPIRE_ERR_UNSUPPORTED,
-                   "only BERT-base geometry is built (hidden 768, 12 heads); got hidden %d heads %d", w->hidden, w->n_heads);
-    ASPIRE_REQUIRE(B >= 0 && L > 0 && L <= 512 && L <= w->max_pos, ASPIRE_ERR_INVALID_ARG,
-                   "sequence length %lld outside (0, min(512, max_position_embeddings=%d)]", (long long)L, w->max_pos);
-    ASPIRE_REQUIRE(w->n_layers >= 0 && (w->n_layers == 0 || w->layers), ASPIRE_ERR_INVALID_ARG, "bad layer table");
+    if (int rc = check_forward_args(w, tok_ids, attn_mask, hidden_out, B, L)) return rc;
     if (B == 0) return ASPIRE_OK;
     const size_t need = carve(nullptr, B, L, w->n_heads, w->ffn_dim, w->n_layers).total;
     ASPIRE_REQUIRE(workspace && workspace_bytes >= need, ASPIRE_ERR_INVALID_ARG, "workspace too small: need %zu bytes", need);
-    hipStream_t st = (hipStream_t)stream;
-    Workspace ws = carve(workspace, B, L, w->n_heads, w->ffn_dim, w->n_layers);
-    const int64_t M = B * L;
-    const int Lp = (int)((L + 3) / 4 * 4), H = w->n_heads, dh = kD / H;
-    const unsigned row_blocks = (unsigned)((M + 3) / 4);
-
-    // P path: the weights' planes are prepared (aspire_bert_prepare_planes), BERT-base shapes tile by 128 -- every nn.Linear GEMM
-    // streams pre-split fp16 operands (gemm_p_kernel), from 1024 token rows on (measured B x L = 4 x 128: 2.46 vs 2.42 ms per batch,
-    // 8 x 128: 2.55 vs 2.81, 16 x 128: 2.90 vs 3.52, 32 x 256: 6.64 vs 9.8); below -- and with ASPIRE_HIP_GEMM=f32 | bf16x3, or without
-    // planes -- the round-2 kernels, which pick smaller tiles for small M
-    const bool pp = w->planes != nullptr && (tuning().gemm_form == 0 ? M >= 1024 : tuning().gemm_form == 3) && dh == 64 && !tuning().attn_gemm &&
-                    w->ffn_dim % 128 == 0;
-    const PlaneOffsets po = plane_offsets(w->ffn_dim);
-    float* x = w->n_layers == 0 ? hidden_out : ws.x;
-    hipLaunchKernelGGL(embed_layernorm_kernel, dim3(row_blocks), dim3(256), 0, st, tok_ids, type_ids, w->word_emb, w->pos_emb,
-                       w->type_emb, w->emb_ln_g, w->emb_ln_b, w->ln_eps, x, M, L, pp && w->n_layers > 0 ? ws.actp : nullptr);
-    ASPIRE_LAUNCH_OK();
-
-    // LayerNorm in the N = 768 GEMMs' epilogue (ASPIRE_HIP_GEMM_LN=off: the separate layernorm_kernel pass)
-    // from 48 row tiles on (measured, fused / separate ms per batch: 64 x 256 9.00 - 9.18 / 9.45, 128 x 128 8.99 / 9.40, 64 x 128 5.05 / 5.15,
-    // 32 x 256 5.16 / 5.30, 40 x 100 3.09 / 3.17, 16 x 256 3.18 / 3.14, 8 x 256 2.37 / 2.30: below, the launch is a fraction of one round of
-    // workgroups and a waiting workgroup has nothing running under it)
-    const int64_t row_tiles = (M + 127) / 128;
-    const bool ln_fused = pp && (tuning().gemm_ln == 2 || (tuning().gemm_ln == 0 && row_tiles >= 48 && ln_fused_supported()));
-    // the P layout's slot offsets are 32-bit byte offsets (p_slot / p_slot8: ((k >> 4) R + r) << 6): the widest operand is [M, ffn_dim]
-    ASPIRE_REQUIRE(!pp || (uint64_t)M * (uint64_t)(w->ffn_dim > 3 * kD ? w->ffn_dim : 3 * kD) * 4 < (1ull << 32), ASPIRE_ERR_UNSUPPORTED,
-                   "%lld token rows in one forward: the fp16-plane layout addresses < 4 GB per operand (split the batch)", (long long)M);
-    if (ln_fused && w->n_layers > 0) ASPIRE_HIP_OK(hipMemsetAsync(ws.ln_count, 0, ws.ln_count_bytes, st));
-    // Round 6 (default on the plane path; ASPIRE_HIP_ATTN=f16x2 pins round 5's form, which splits fp32 Q / K / V inside the attention kernel):
-    // the QKV GEMM writes the attention's operands as fp16 planes, the attention stages them by LDS-DMA (flash_attn_p_kernel)
-    const bool attn_p = pp && w->n_layers > 0 && tuning().attn_form != 1 && !tuning().attn_f32 && tuning().gemm_tile == 0;
+    Fwd f;
+    if (int rc = plan_forward(f, w, attn_mask, B, L, workspace, (hipStream_t)stream)) return rc;
+    float* x = w->n_layers == 0 ? hidden_out : f.ws.x;
+    if (int rc = launch_embed(f, tok_ids, type_ids, x)) return rc;
     for (int l = 0; l < w->n_layers; ++l) {
-        const aspire_bert_layer& ly = w->layers[l];
         const bool last = l == w->n_layers - 1;
-        float* out = last ? hidden_out : ws.x;  // LN2 writes the layer output (x is dead by then)
-        const char* lp = (const char*)w->planes + (size_t)l * po.per_layer;
-        GemmArgs g{};
-        PGemmArgs pg{};
-        // 1. fused QKV projection: qkv [M, 2304] = x . Wqkv^T + bqkv
-        if (attn_p) {
-            // Q, K and V go out as the attention kernel's fp16 planes (no fp32 qkv exists in this form)
-            pg = PGemmArgs{ws.actp, lp + po.qkv, nullptr, nullptr, ly.b_qkv, nullptr, (int)M, 3 * kD, kD, 0, 0, 0};
-            pg.Xp = ws.qkvp;
-            if (int rc = launch_gemm_p_qkv(pg, st)) return rc;
-        } else if (pp) {
-            pg = PGemmArgs{ws.actp, lp + po.qkv, ws.qkv, nullptr, ly.b_qkv, nullptr, (int)M, 3 * kD, kD, 3 * kD, 0, 0};
-            if (int rc = launch_gemm_p<false>(pg, st)) return rc;
-        } else {
-            g = GemmArgs{};
-            g.A = x; g.B = ly.w_qkv; g.C = ws.qkv; g.bias = ly.b_qkv;
-            g.M = (int)M; g.N = 3 * kD; g.K = kD; g.lda = kD; g.ldb = kD; g.ldc = 3 * kD; g.nz2 = 1; g.alpha = 1.f;
-            if (int rc = launch_gemm<false>(g, 1, st)) return rc;
-        }
-        // 2-4. attention.  Fused kernel (scores never leave the chip) unless ASPIRE_HIP_ATTN=gemm pins the
-        // three-kernel form (QK^T GEMM, masked soft-max, PV GEMM) that the fused one is tested against.
-        if (attn_p) {
-            const unsigned qblocks = (unsigned)((L + 127) / 128);
-            if (tuning().attn_form == 2)
-                hipLaunchKernelGGL(flash_attn_p64_kernel, dim3((unsigned)(B * H) * qblocks), dim3(256), 0, st, ws.qkvp, attn_mask, ws.ctx, (int)L, H, ws.ctxp, M);
-            else
-                hipLaunchKernelGGL(flash_attn_p_kernel, dim3((unsigned)(B * H) * qblocks), dim3(256), 0, st, ws.qkvp, attn_mask, ws.ctx, (int)L, H, ws.ctxp, M);
-            ASPIRE_LAUNCH_OK();
-        } else if (dh == 64 && !tuning().attn_gemm) {
-            const unsigned qblocks = (unsigned)((L + 127) / 128);
-            if (tuning().attn_f32)
-                hipLaunchKernelGGL(flash_attn_f32_kernel, dim3((unsigned)(B * H) * qblocks), dim3(256), 0, st, ws.qkv, attn_mask, ws.ctx,
-                                   (int)L, H, pp ? ws.ctxp : nullptr, M);
-            else
-                hipLaunchKernelGGL(flash_attn_f16x2_kernel, dim3((unsigned)(B * H) * qblocks), dim3(256), 0, st, ws.qkv, attn_mask, ws.ctx,
-                                   (int)L, H, pp ? ws.ctxp : nullptr, M);
-            ASPIRE_LAUNCH_OK();
-        } else {
-            // 2. scores[b,h] = Q_bh . K_bh^T   (scale and mask are applied by the softmax kernel)
-            g = GemmArgs{};
-            g.A = ws.qkv; g.B = ws.qkv + kD; g.C = ws.scores;
-            g.M = (int)L; g.N = (int)L; g.K = dh; g.lda = 3 * kD; g.ldb = 3 * kD; g.ldc = Lp; g.nz2 = H; g.alpha = 1.f;
-            g.sa1 = (long long)L * 3 * kD; g.sa2 = dh; g.sb1 = g.sa1; g.sb2 = dh;
-            g.sc1 = (long long)H * L * Lp; g.sc2 = (long long)L * Lp;
-            if (int rc = launch_gemm<false>(g, (int)(B * H), st)) return rc;
-            // 3. masked softmax over keys
-            const int64_t srows = B * H * L;
-            hipLaunchKernelGGL(softmax_mask_kernel, dim3((unsigned)((srows + 3) / 4)), dim3(256), 0, st, ws.scores, attn_mask, srows,
-                               (int)L, Lp, (int)(H * L), 1.0f / sqrtf((float)dh));
-            ASPIRE_LAUNCH_OK();
-            // 4. ctx[b, :, h*64:(h+1)*64] = P_bh . V_bh        (V is [K = L keys, N = 64] n-contiguous)
-            g = GemmArgs{};
-            g.A = ws.scores; g.B = ws.qkv + 2 * kD; g.C = ws.ctx;
-            g.M = (int)L; g.N = dh; g.K = (int)L; g.lda = Lp; g.ldb = 3 * kD; g.ldc = kD; g.nz2 = H; g.alpha = 1.f;
-            g.sa1 = (long long)H * L * Lp; g.sa2 = (long long)L * Lp; g.sb1 = (long long)L * 3 * kD; g.sb2 = dh;
-            g.sc1 = (long long)L * kD; g.sc2 = dh;
-            if (int rc = launch_gemm<true>(g, (int)(B * H), st)) return rc;
-        }
-        // 5. attention output projection + residual, LayerNorm
-        if (ln_fused) {
-            // x lives in actp (written by the embedding LayerNorm / the previous layer's FFN2 epilogue, read by the QKV GEMM): read as the
-            // residual and replaced by h = LN1(.) slot by slot; no fp32 copy of x or h exists in this form
-            pg = PGemmArgs{ws.ctxp, lp + po.o, nullptr, ws.actp, ly.b_o, nullptr, (int)M, kD, kD, kD, kD, 0};
-            pg.resp = ws.actp;
-            pg.gamma = ly.ln1_g; pg.beta = ly.ln1_b; pg.eps = w->ln_eps;
-            pg.ln_stats = ws.ln_stats; pg.ln_count = ws.ln_count + (size_t)(2 * l) * row_tiles;
-            if (int rc = launch_gemm_p_ln(pg, st)) return rc;
-        } else if (pp) {
-            pg = PGemmArgs{ws.ctxp, lp + po.o, ws.tmp, nullptr, ly.b_o, x, (int)M, kD, kD, kD, kD, 0};
-            if (int rc = launch_gemm_p<false>(pg, st)) return rc;
-        } else {
-            g = GemmArgs{};
-            g.A = ws.ctx; g.B = ly.w_o; g.C = ws.tmp; g.bias = ly.b_o; g.res = x; g.ldr = kD;
-            g.M = (int)M; g.N = kD; g.K = kD; g.lda = kD; g.ldb = kD; g.ldc = kD; g.nz2 = 1; g.alpha = 1.f;
-            if (int rc = launch_gemm<false>(g, 1, st)) return rc;
-        }
-        if (!ln_fused) {
-            hipLaunchKernelGGL(layernorm_kernel, dim3(row_blocks), dim3(256), 0, st, ws.tmp, ly.ln1_g, ly.ln1_b, w->ln_eps, ws.ctx, M,
-                               pp ? ws.actp : nullptr);
-            ASPIRE_LAUNCH_OK();
-        }
-        // 6. FFN: GELU(h . W1^T + b1) . W2^T + b2 + h, LayerNorm          (h = ws.ctx)
-        if (pp) {
-            pg = PGemmArgs{ws.actp, lp + po.ffn1, nullptr, ws.ffnp, ly.b_ffn1, nullptr, (int)M, w->ffn_dim, kD, 0, 0, 0};
-            if (int rc = launch_gemm_p<true>(pg, st)) return rc;
-            if (ln_fused) {
-                pg = PGemmArgs{ws.ffnp, lp + po.ffn2, last ? hidden_out : nullptr, last ? nullptr : ws.actp, ly.b_ffn2, nullptr, (int)M, kD, w->ffn_dim, kD, kD, 0};
-                pg.resp = ws.actp;
-                pg.gamma = ly.ln2_g; pg.beta = ly.ln2_b; pg.eps = w->ln_eps;
-                pg.ln_stats = ws.ln_stats; pg.ln_count = ws.ln_count + (size_t)(2 * l + 1) * row_tiles;
-                if (int rc = launch_gemm_p_ln(pg, st)) return rc;
-            } else {
-                pg = PGemmArgs{ws.ffnp, lp + po.ffn2, ws.tmp, nullptr, ly.b_ffn2, ws.ctx, (int)M, kD, w->ffn_dim, kD, kD, 0};
-                if (int rc = launch_gemm_p<false>(pg, st)) return rc;
-            }
-        } else {
-            g = GemmArgs{};
-            g.A = ws.ctx; g.B = ly.w_ffn1; g.C = ws.ffn; g.bias = ly.b_ffn1; g.gelu = 1;
-            g.M = (int)M; g.N = w->ffn_dim; g.K = kD; g.lda = kD; g.ldb = kD; g.ldc = w->ffn_dim; g.nz2 = 1; g.alpha = 1.f;
-            if (int rc = launch_gemm<false>(g, 1, st)) return rc;
-            g = GemmArgs{};
-            g.A = ws.ffn; g.B = ly.w_ffn2; g.C = ws.tmp; g.bias = ly.b_ffn2; g.res = ws.ctx; g.ldr = kD;
-            g.M = (int)M; g.N = kD; g.K = w->ffn_dim; g.lda = w->ffn_dim; g.ldb = w->ffn_dim; g.ldc = kD; g.nz2 = 1; g.alpha = 1.f;
-            if (int rc = launch_gemm<false>(g, 1, st)) return rc;
-        }
-        if (!ln_fused) {
-            hipLaunchKernelGGL(layernorm_kernel, dim3(row_blocks), dim3(256), 0, st, ws.tmp, ly.ln2_g, ly.ln2_b, w->ln_eps, out, M,
-                               pp && !last ? ws.actp : nullptr);
-            ASPIRE_LAUNCH_OK();
-        }
+        float* out = last ? hidden_out : f.ws.x;  // LN2 writes the layer output (x is dead by then)
+        if (int rc = run_layer(f, l, x, out, last, false)) return rc;
         x = out;
     }
     return ASPIRE_OK;
+}
+
+extern "C" size_t aspire_bert_cls_workspace_bytes(const aspire_bert_weights* w, int64_t B, int64_t L) {
+    if (!w || B <= 0 || L <= 0) return 0;
+    const size_t base = carve(nullptr, B, L, w->n_heads, w->ffn_dim, w->n_layers).total;
+    return base + carve_cls(nullptr, B, w->ffn_dim).total;
+}
+
+// The CLS rows of every hidden state and their mix (ex_aspire_bienc.py:23-58, disent_models.py:183-205): layers 0 .. n - 2 are
+// aspire_bert_forward_f32's own launches; after the embedding LayerNorm and after every layer cls_tap_kernel reads the B CLS rows
+// where that form left them (fp32 x, or the fp16 planes of actp on the fused-LayerNorm form) and adds w_l x row to cls_out.  The last
+// layer runs its QKV GEMM over all rows, then ONE query per (document, head) (cls_attn_kernel) and the rest of the layer on the B
+// gathered rows only: nothing after the keys and values of a non-CLS row is ever read.
+extern "C" int aspire_bert_forward_cls_f32(const aspire_bert_weights* w, const int64_t* tok_ids, const int64_t* type_ids,
+                                           const int64_t* attn_mask, int64_t B, int64_t L, const float* layer_mix, float* cls_out,
+                                           float* layer_cls, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_forward_args(w, tok_ids, attn_mask, cls_out, B, L)) return rc;
+    if (layer_mix)
+        for (int i = 0; i <= w->n_layers; ++i)
+            ASPIRE_REQUIRE(isfinite(layer_mix[i]), ASPIRE_ERR_INVALID_ARG, "layer_mix[%d] is not finite", i);
+    if (B == 0) return ASPIRE_OK;
+    const size_t need = aspire_bert_cls_workspace_bytes(w, B, L);
+    ASPIRE_REQUIRE(workspace && workspace_bytes >= need, ASPIRE_ERR_INVALID_ARG, "workspace too small: need %zu bytes", need);
+    Fwd f;
+    if (int rc = plan_forward(f, w, attn_mask, B, L, workspace, (hipStream_t)stream)) return rc;
+    const ClsWorkspace cw = carve_cls((char*)workspace + f.ws.total, B, w->ffn_dim);
+    const int n = w->n_layers;
+    const unsigned tap_blocks = (unsigned)((B + 3) / 4);
+    // hidden state i: its CLS row -> layer_cls[i], cls_out (+)= mix[i] x row, and (i = n - 1) the last layer's residual input
+    auto tap = [&](int i, const float* x, const void* xp, int64_t rows, int64_t ld_rows) -> int {
+        const int mode = layer_mix ? (i == 0 ? 1 : 2) : (i == n ? 1 : 0);
+        const float wt = layer_mix ? layer_mix[i] : 1.f;
+        hipLaunchKernelGGL(cls_tap_kernel, dim3(tap_blocks), dim3(256), 0, f.st, x, xp, rows, ld_rows, B, wt, mode, cls_out,
+                           layer_cls ? layer_cls + (size_t)i * B * kD : nullptr, i == n - 1 ? cw.gin : nullptr);
+        ASPIRE_LAUNCH_OK();
+        return ASPIRE_OK;
+    };
+    if (int rc = launch_embed(f, tok_ids, type_ids, f.ws.x)) return rc;
+    if (int rc = tap(0, f.ws.x, nullptr, f.M, L)) return rc;
+    for (int l = 0; l + 1 < n; ++l) {
+        if (int rc = run_layer(f, l, f.ws.x, f.ws.x, false, false)) return rc;
+        // the fused form keeps a layer's output only as the planes of actp; the others write fp32 x
+        if (int rc = f.ln_fused ? tap(l + 1, nullptr, f.ws.actp, f.M, L) : tap(l + 1, f.ws.x, nullptr, f.M, L)) return rc;
+    }
+    if (n == 0) return ASPIRE_OK;
+    // the last layer: Q, K, V of every row as the forward's attention form lays them out ...
+    const aspire_bert_layer& ly = w->layers[n - 1];
+    if (int rc = run_layer(f, n - 1, f.ws.x, f.ws.x, true, true)) return rc;
+    hipLaunchKernelGGL(cls_attn_kernel, dim3((unsigned)(B * f.H)), dim3(256), 0, f.st, f.attn_p ? nullptr : f.ws.qkv,
+                       f.attn_p ? f.ws.qkvp : nullptr, attn_mask, cw.ctx, (int)L, f.H, f.M);
+    ASPIRE_LAUNCH_OK();
+    // ... then the rest of the layer on the B context rows: out-proj + residual, LN1, GELU(FFN1), FFN2 + residual, LN2
+    GemmArgs g{};
+    g.A = cw.ctx; g.B = ly.w_o; g.C = cw.tmp; g.bias = ly.b_o; g.res = cw.gin; g.ldr = kD;
+    g.M = (int)B; g.N = kD; g.K = kD; g.lda = kD; g.ldb = kD; g.ldc = kD; g.nz2 = 1; g.alpha = 1.f;
+    if (int rc = launch_gemm<false>(g, 1, f.st)) return rc;
+    hipLaunchKernelGGL(layernorm_kernel, dim3(tap_blocks), dim3(256), 0, f.st, cw.tmp, ly.ln1_g, ly.ln1_b, w->ln_eps, cw.h, B, nullptr);
+    ASPIRE_LAUNCH_OK();
+    g = GemmArgs{};
+    g.A = cw.h; g.B = ly.w_ffn1; g.C = cw.ffn; g.bias = ly.b_ffn1; g.gelu = 1;
+    g.M = (int)B; g.N = w->ffn_dim; g.K = kD; g.lda = kD; g.ldb = kD; g.ldc = w->ffn_dim; g.nz2 = 1; g.alpha = 1.f;
+    if (int rc = launch_gemm<false>(g, 1, f.st)) return rc;
+    g = GemmArgs{};
+    g.A = cw.ffn; g.B = ly.w_ffn2; g.C = cw.tmp; g.bias = ly.b_ffn2; g.res = cw.h; g.ldr = kD;
+    g.M = (int)B; g.N = kD; g.K = w->ffn_dim; g.lda = w->ffn_dim; g.ldb = w->ffn_dim; g.ldc = kD; g.nz2 = 1; g.alpha = 1.f;
+    if (int rc = launch_gemm<false>(g, 1, f.st)) return rc;
+    hipLaunchKernelGGL(layernorm_kernel, dim3(tap_blocks), dim3(256), 0, f.st, cw.tmp, ly.ln2_g, ly.ln2_b, w->ln_eps, cw.y, B, nullptr);
+    ASPIRE_LAUNCH_OK();
+    return tap(n, cw.y, nullptr, B, 1);
 }
 
 extern "C" int aspire_bert_status(int32_t* status_host, void* stream) {

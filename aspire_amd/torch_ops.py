@@ -7,6 +7,8 @@ implementation so that shapes propagate under FakeTensor / torch.compile tracing
 
     torch.ops.aspire.span_mean_pool(hidden, tok_idx, span_off, max_sents) -> (cls, sent)         A2/A3  ex_aspire_consent.py:75-100
     torch.ops.aspire.bert_encoder_forward(ids, type_ids, mask, weights, n_heads, ln_eps) -> hidden  A1   ex_aspire_consent.py:72-73
+    torch.ops.aspire.bert_cls_forward(ids, type_ids, mask, weights, n_heads, ln_eps, layer_mix) -> cls [B, 768]
+                                                                                   A1b  ex_aspire_bienc.py:23-58
     torch.ops.aspire.l2max_scores(q, q_lens, c, c_lens, paired) -> scores                          A9   pair_distances.py:138-186
     torch.ops.aspire.ot_sinkhorn_scores(q, q_lens, c, c_lens, blur, scaling, temp, group, want, paired, extras)
                                          -> (scores, q_distr, c_distr, pair_sims, plan)           A5-A8 pair_distances.py:21-92
@@ -88,6 +90,41 @@ def bert_encoder_forward(ids: Tensor, type_ids: Tensor, mask: Tensor, weights: L
 @bert_encoder_forward.register_fake
 def _(ids, type_ids, mask, weights, n_heads, ln_eps):
     return weights[0].new_empty(ids.shape[0], ids.shape[1], weights[0].shape[1])
+
+
+# the bi-encoder read-out (aspire_bert_forward_cls_f32): the same weights list; layer_mix = the softmaxed mix of the n_layers + 1 hidden
+# states' CLS rows (ex_aspire_bienc.py:23-58), or [] for the last hidden state's CLS row alone
+@torch.library.custom_op('aspire::bert_cls_forward', mutates_args=(), device_types='cuda')
+def bert_cls_forward(ids: Tensor, type_ids: Tensor, mask: Tensor, weights: List[Tensor], n_heads: int, ln_eps: float,
+                     layer_mix: List[float]) -> Tensor:
+    assert (len(weights) - 5) % 12 == 0 and len(weights) >= 5, 'weights: 5 embedding tensors + 12 per layer'
+    n_layers = (len(weights) - 5) // 12
+    assert len(layer_mix) in (0, n_layers + 1), 'layer_mix: n_layers + 1 weights, or none'
+    w = [t.contiguous() for t in weights]
+    assert all(t.is_cuda and t.dtype == torch.float32 for t in w)
+    layers = (_lib.BertLayer * max(n_layers, 1))()
+    for i in range(n_layers):
+        for f, t in zip(_lib.BertLayer._fields_, w[5 + 12 * i:17 + 12 * i]):
+            setattr(layers[i], f[0], ctypes.c_void_p(t.data_ptr()))
+    hidden_size = w[0].shape[1]
+    ffn = w[5 + 6].shape[0] if n_layers else 4 * hidden_size
+    bw = _lib.BertWeights(*(ctypes.c_void_p(t.data_ptr()) for t in w[:5]), layers, n_layers, n_heads, hidden_size, ffn,
+                          w[0].shape[0], w[1].shape[0], w[2].shape[0], float(ln_eps))
+    ids = ids.to(torch.int64).contiguous()
+    b, l = ids.shape
+    out = torch.empty(b, hidden_size, device=ids.device, dtype=torch.float32)
+    mix = ctypes.cast((ctypes.c_float * len(layer_mix))(*layer_mix), ctypes.c_void_p) if layer_mix else None
+    need = lib.aspire_bert_cls_workspace_bytes(ctypes.byref(bw), b, l)
+    ws = torch.empty(max(need, 16), device=ids.device, dtype=torch.uint8)
+    check(lib.aspire_bert_forward_cls_f32(ctypes.byref(bw), ops._ptr(ids), ops._ptr(type_ids.to(torch.int64).contiguous()),
+                                          ops._ptr(mask.to(torch.int64).contiguous()), b, l, mix, ops._ptr(out), None, ops._ptr(ws),
+                                          ws.numel(), ops._stream()))
+    return out
+
+
+@bert_cls_forward.register_fake
+def _(ids, type_ids, mask, weights, n_heads, ln_eps, layer_mix):
+    return weights[0].new_empty(ids.shape[0], weights[0].shape[1])
 
 
 def _npairs(qn, cn, paired):
@@ -206,5 +243,5 @@ def _(q_rows, q_start, q_len, q_max, c_rows, c_start, c_len, c_max, job_off, max
     return (q_rows.new_empty(c_start.shape[0]), q_rows.new_empty(j, k), q_rows.new_empty(j, k, dtype=torch.int64))
 
 
-OPS = ('span_mean_pool', 'bert_encoder_forward', 'l2max_scores', 'ot_sinkhorn_scores', 'topk_desc', 'topk_keys', 'topk_merge',
+OPS = ('span_mean_pool', 'bert_encoder_forward', 'bert_cls_forward', 'l2max_scores', 'ot_sinkhorn_scores', 'topk_desc', 'topk_keys', 'topk_merge',
        'l2max_scores_csr', 'ot_scores_csr', 'ot_rank_batch')

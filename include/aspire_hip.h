@@ -125,6 +125,28 @@ int aspire_bert_forward_f32(const aspire_bert_weights* w, const int64_t* tok_ids
 int aspire_bert_status(int32_t* status_host, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * A1b  SPECTER-CoCite bi-encoder read-out.  Replaces `SoftmaxMixLayers(13 -> 1, bias=False)` over
+ * `bert_encoder(..., output_hidden_states=True).hidden_states` at examples/ex_aspire_bienc.py:23-58
+ * (linear(stack(hidden_states, dim=3), softmax(W, dim=1))[:, 0, :]) and MySPECTER.doc_reps_bert,
+ * src/learning/facetid_models/disent_models.py:183-205; with layer_mix NULL the plain AutoModel read-out
+ * last_hidden_state[:, 0, :] of the README (:101-164).  The encoder is aspire_bert_forward_f32's, with the
+ * same weights, forms and accuracy, except that the last layer computes the CLS rows only: its QKV GEMM
+ * runs over every row, then one attention query per (document, head) and the rest of the layer on the B
+ * CLS rows.
+ *   layer_mix   NULL, or a HOST array of n_layers + 1 weights (already softmaxed): hidden state 0 is the
+ *               embedding LayerNorm output, i the output of layer i
+ *   cls_out     [B, 768]  sum_i layer_mix[i] x hidden_states[i][:, 0, :]  (NULL mix: the last one's)
+ *   layer_cls   NULL, or [n_layers + 1, B, 768]: the CLS row of every hidden state
+ *   workspace   device scratch of aspire_bert_cls_workspace_bytes(w, B, L) bytes
+ * The same argument checks as aspire_bert_forward_f32 (plus a finite layer_mix), all before any launch;
+ * aspire_bert_status covers these forwards too.
+ * ------------------------------------------------------------------------------------------- */
+size_t aspire_bert_cls_workspace_bytes(const aspire_bert_weights* w, int64_t B, int64_t L);
+int aspire_bert_forward_cls_f32(const aspire_bert_weights* w, const int64_t* tok_ids, const int64_t* type_ids,
+                                const int64_t* attn_mask, int64_t B, int64_t L, const float* layer_mix, float* cls_out,
+                                float* layer_cls, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * caching_score's document-level term (src/learning/facetid_models/disent_models.py:305-307, taken when
  * abs_loss_prop > 0): functional.pairwise_distance(query_cls_reps, cand_cls_reps, p=2.0) = ||q - c + eps||_2 with torch's
  * eps = 1e-6 added to every coordinate of the difference.  (The caller negates and scales it.)
