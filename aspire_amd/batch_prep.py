@@ -14,6 +14,7 @@ Besides the reference's return values, ``spans_to_csr`` flattens the ragged inde
 """
 import re
 
+import numpy as np
 import torch
 
 MAX_NUM_TOKS = 500
@@ -153,3 +154,50 @@ def prepare_eval_seqs(batch_papers, tokenizer):
     """TrainedAbstractModel.encode's input (src/evaluation/utils/models.py:557-563): TITLE + ' [SEP] ' + ' '.join(ABSTRACT), no
     '[SEP]' removal.  :return: bert_batch (prepare_bert_seqs)."""
     return prepare_bert_seqs([p['TITLE'] + ' [SEP] ' + ' '.join(p['ABSTRACT']) for p in batch_papers], tokenizer)[0]
+
+
+# ---- the cosentbert / ictsentbert sentence encoder's inputs (aspire_amd/sentenc.py): one sequence per sentence ------------------
+def prepare_sentence_batch(sents, tokenizer, max_seq_length=512):
+    """The tokenisation of SentenceTransformer.encode with models.Transformer(max_seq_length=512) (TrainedSentModel,
+    src/evaluation/utils/models.py:568-604; recalled from sentence-transformers, which the reference imports): every text
+    ``.strip()``ed, then ``tokenizer(texts, padding=True, truncation='longest_first', max_length=max_seq_length,
+    return_tensors='pt')``.  :return: the HF dict (input_ids, token_type_ids, attention_mask), right-padded to the longest."""
+    return tokenizer([str(s).strip() for s in sents], padding=True, truncation='longest_first', max_length=max_seq_length,
+                     return_tensors='pt')
+
+
+def sentence_buckets(n_tokens, max_tokens=16384):
+    """Encoder calls for sentences of n_tokens[i] word pieces each (specials included): the sentences sorted by length
+    (stable) and cut into consecutive runs whose padded size, run length x longest member, stays within max_tokens rows (a
+    single sentence longer than that is a run of its own).  Returns a list of index arrays into n_tokens: together a
+    permutation of range(len(n_tokens))."""
+    n_tokens = np.asarray(n_tokens, dtype=np.int64)
+    order = np.argsort(n_tokens, kind='stable')
+    runs, lo = [], 0
+    for i in range(1, len(order) + 1):
+        if i == len(order) or (i + 1 - lo) * int(n_tokens[order[i]]) > max_tokens:
+            runs.append(order[lo:i])
+            lo = i
+    return runs
+
+
+def tokenize_sentences(sents, tokenizer, max_seq_length=512):
+    """prepare_sentence_batch's tokenizer call without the padding: (input id lists, token type id lists), one per sentence."""
+    enc = tokenizer([str(s).strip() for s in sents], padding=False, truncation='longest_first', max_length=max_seq_length)
+    return enc['input_ids'], enc['token_type_ids']
+
+
+def pad_sentences(ids, types, idx, pad_id):
+    """The sentences idx of tokenize_sentences' lists, right-padded to the longest of them as the tokenizer's padding=True pads
+    (ids with pad_id, token types and attention mask with 0): int64 (input_ids, token_type_ids, attention_mask) [len(idx), L]."""
+    idx = list(idx)
+    L = max(len(ids[i]) for i in idx)
+    tok = np.full((len(idx), L), pad_id, dtype=np.int64)
+    typ = np.zeros((len(idx), L), dtype=np.int64)
+    msk = np.zeros((len(idx), L), dtype=np.int64)
+    for r, i in enumerate(idx):
+        n = len(ids[i])
+        tok[r, :n] = ids[i]
+        typ[r, :n] = types[i]
+        msk[r, :n] = 1
+    return torch.from_numpy(tok), torch.from_numpy(typ), torch.from_numpy(msk)

@@ -37,7 +37,8 @@ def score(results_dir, test_pool, rep_store, facet=None, pred_labels=None, metho
     predicted label matches the facet (models.py:127-163; pred_labels: {paper_id: [label per sentence]}).
     Writes and returns {query_id: [(cand_id, -sim), ...]}.
 
-    With the per-pair schedule (the reference's own: one get_similarity call per candidate, evaluate.py:68-72) the queries go
+    With the per-pair schedule (the reference's own: one get_similarity call per candidate, evaluate.py:68-72) and method 'ot',
+    'l2max' or cosentbert's 'cosine' / 'dotlse' (TrainedSentModel.get_similarity, models.py:602-604) the queries go
     through scorer.rank_pools `queries_per_call` at a time -- every query against ITS OWN pool in one library call; any other
     schedule / aggregation keeps one rank_pool call per query.  resident: the candidates of all pools are uploaded once
     (RepStore.to_device: a paper in many pools is stored once) and the pools are index lists into that matrix.
@@ -68,7 +69,7 @@ def score(results_dir, test_pool, rep_store, facet=None, pred_labels=None, metho
     def query_reps(query_id):
         return rep_store.faceted(query_id, facet, pred_labels[query_id]) if facet is not None else rep_store.get(query_id)
 
-    if schedule == 'pair' and method in ('ot', 'l2max') and queries_per_call > 1:
+    if schedule == 'pair' and method in scorer.BATCH_METHODS and queries_per_call > 1:
         for lo in range(0, len(query_ids), queries_per_call):
             ids = query_ids[lo:lo + queries_per_call]
             cand_lists = [test_pool[i]['cands'] for i in ids]

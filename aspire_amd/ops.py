@@ -449,6 +449,61 @@ def l2max_rank_batch(q, c, job_off, max_job, k, cdist_mode=_lib.CDIST_AUTO, out=
     return (scores, keys) if key_form else (scores, top_s, top_i)
 
 
+def _dot_ready(*sets):
+    """The host-side contract of the dot-product max-sim entries: every document has a row (np.max over an empty similarity
+    block raises in the reference) and every row is finite (sklearn's check_array raises ValueError on inf / NaN).  The finite
+    check runs once per row matrix and is kept until its rows are written (_rows_key)."""
+    for s in sets:
+        if s.n == 0:
+            continue
+        if (min(s.lens_host) if s.lens_host is not None else int(s.len.min())) <= 0:
+            raise ValueError('a document without sentence rows cannot be scored (np.max over an empty block raises); drop it')
+        key = _rows_key(s.rows)
+        if getattr(s.rows, '_aspire_finite', None) != key:
+            if not bool(torch.isfinite(s.rows).all()):
+                raise ValueError('Input contains NaN or infinity (sklearn.metrics.pairwise.cosine_similarity rejects it)')
+            s.rows._aspire_finite = key
+
+
+def dotmax_scores(q, c, pairing=_lib.PAIR_CROSS, sim=_lib.SIM_COSINE):
+    """A13 (TrainedSentModel.get_similarity, models.py:602-604): sims [P] = max over the valid sentence pairs of sklearn's
+    cosine similarity (sim=SIM_COSINE) or of the raw dot product (SIM_DOT, rank_pool_sent's 'dotlse')."""
+    _dot_ready(q, c)
+    p = _npairs(q, c, pairing)
+    scores = torch.empty(p, device=q.rows.device, dtype=torch.float32)
+    qs, cs = q.struct(), c.struct()
+    check(lib.aspire_dotmax_scores_f32(ctypes.byref(qs), ctypes.byref(cs), D, pairing, sim, _ptr(scores), _stream()))
+    return scores
+
+
+def dotmax_rank_batch(q, c, job_off, max_job, k, sim=_lib.SIM_COSINE, out=None, workspace=None, job_base=None, key_form=False):
+    """The dot-product max-sim over J independent (query, pool) jobs in ONE call (include/aspire_hip.h:
+    aspire_dotmax_rank_batch_f32); arguments and returns as l2max_rank_batch."""
+    _dot_ready(q, c)
+    dev = q.rows.device
+    _i32(job_off, 'job_off')
+    assert job_off.numel() == q.n + 1, 'job_off must have one entry per job plus one'
+    keys = None
+    if out is not None and key_form:
+        scores, keys = out
+        top_s = top_i = None
+    elif out is not None:
+        scores, top_s, top_i = out
+    else:
+        scores = torch.empty(c.n, device=dev, dtype=torch.float32)
+        top_s = torch.empty(q.n, k, device=dev, dtype=torch.float32) if k > 0 and not key_form else None
+        top_i = torch.empty(q.n, k, device=dev, dtype=torch.int64) if k > 0 and not key_form else None
+        keys = torch.empty(q.n, k, device=dev, dtype=torch.int64) if k > 0 and key_form else None
+    qs, cs = q.struct(), c.struct()
+    if workspace is None:
+        nbytes = lib.aspire_dotmax_rank_batch_workspace_bytes(ctypes.byref(qs), ctypes.byref(cs), max_job, k)
+        workspace = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
+    check(lib.aspire_dotmax_rank_batch_f32(ctypes.byref(qs), ctypes.byref(cs), D, _ptr(job_off), max_job, sim, _ptr(scores), k,
+                                           _ptr(job_base), _ptr(top_s), _ptr(top_i), _ptr(keys), _ptr(workspace), workspace.numel(),
+                                           _stream()))
+    return (scores, keys) if key_form else (scores, top_s, top_i)
+
+
 def topk_desc(scores, k, idx_base=0):
     """A12 (evaluate.py:76): scores [Q, C] -> (top_scores [Q,k], top_idx [Q,k] int64), stable descending."""
     _f32(scores, 'scores')

@@ -50,6 +50,11 @@ class CandidatePool:
         return self
 
 
+# the dot-product max-sims (cosentbert / ictsentbert, pp_gen_nearest.py rank_pool_sent's score_type names): method -> ASPIRE_SIM_*
+DOT_METHODS = {'cosine': _lib.SIM_COSINE, 'dotlse': _lib.SIM_DOT}
+BATCH_METHODS = ('ot', 'l2max') + tuple(DOT_METHODS)
+
+
 def _as_pool(x):
     return x if isinstance(x, CandidatePool) else CandidatePool(x)
 
@@ -98,7 +103,7 @@ def rank_pool_batch(query_reps_list, batch, k=None, hparams=None, method='ot', d
     two small downloads.  Returns per query [(pid, sign * score), ...] as rank_pools does (evaluate.py:77 stores -similarity:
     sign = -1 negates on the way out, one numpy multiply instead of a Python loop over the pairs)."""
     hparams = hparams or {}
-    if method not in ('ot', 'l2max'):
+    if method not in BATCH_METHODS:
         raise ValueError(f'Unknown aggregation: {method}')
     if hparams.get('geoml_reach', None) is not None:
         raise NotImplementedError('unbalanced OT (geoml_reach) is not built')
@@ -123,10 +128,14 @@ def rank_pool_batch(query_reps_list, batch, k=None, hparams=None, method='ot', d
     # the workspace depends on the QUERIES too (longest document of the call: slot size, record count): asked for on every call
     # -- a host-side computation -- and grown when another facet's queries need more than the last call's
     qs, cs = q.struct(), batch.c.struct()
-    need = (_lib.lib.aspire_l2max_rank_batch_workspace_bytes if method == 'l2max' else _lib.lib.aspire_ot_rank_batch_workspace_bytes)(
-        ctypes.byref(qs), ctypes.byref(cs), batch.max_job, k)
+    need = (_lib.lib.aspire_l2max_rank_batch_workspace_bytes if method == 'l2max' else
+            _lib.lib.aspire_dotmax_rank_batch_workspace_bytes if method in DOT_METHODS else
+            _lib.lib.aspire_ot_rank_batch_workspace_bytes)(ctypes.byref(qs), ctypes.byref(cs), batch.max_job, k)
     slot['ws'] = _shared_workspace(dev, need)
-    if method == 'l2max':
+    if method in DOT_METHODS:
+        _, top_s, top_i = ops.dotmax_rank_batch(q, batch.c, batch.job_off, batch.max_job, k, sim=DOT_METHODS[method], out=slot['out'],
+                                                workspace=slot['ws'])
+    elif method == 'l2max':
         _, top_s, top_i = ops.l2max_rank_batch(q, batch.c, batch.job_off, batch.max_job, k, out=slot['out'], workspace=slot['ws'],
                                                one_form=deterministic)
     else:
@@ -167,7 +176,7 @@ def _cdist_runs(q, c, group):
 def score_pool(query_reps_list, pool, method='ot', schedule='pair', hparams=None, score_batch_size=64, deterministic=False):
     """Scores [Q, C] (GPU tensor, higher = more similar) of every query against every candidate.
 
-    deterministic ('ot' with the per-pair schedule, 'l2max'): every pair through ONE kernel form (include/aspire_hip.h:
+    deterministic ('ot' with the per-pair schedule, 'l2max'; 'cosine' and 'dotlse' always are): every pair through ONE kernel form (include/aspire_hip.h:
     ASPIRE_OT_FLAG_ONE_FORM), so that a pair's score -- and with it the order of near-ties -- does not depend on the size of
     the call it is scored in: score_pool / rank_pool per query and rank_pools over all queries then agree bit for bit.
     Several times slower than the default, which picks the kernel family by grid size (scores a few 1e-5 apart).
@@ -179,15 +188,21 @@ def score_pool(query_reps_list, pool, method='ot', schedule='pair', hparams=None
                       (disent_models.py:297, pp_gen_nearest.py:182-196).
              'l2max'  tsAspire max-sim (caching_score's 'l2lse' branch, disent_models.py:294-295).
              'l2top2' / 'l2attention'  the sibling aggregations (disent_models.py:238-245); hparams['cdatt_sm_temp'].
+             'cosine' cosentbert / ictsentbert: max over the sentence pairs of sklearn's cosine similarity
+                      (TrainedSentModel.get_similarity, models.py:602-604).  'dotlse': the same max over raw dot products
+                      (pp_gen_nearest.py rank_pool_sent).  Both kernel forms give the same bits for a pair; `schedule` and
+                      `score_batch_size` do not apply.
     """
     hparams = hparams or {}
     pool = _as_pool(pool)
     q = ops.DeviceRepSet.from_list(query_reps_list)
     c = pool.repset
-    if method not in ('ot', 'l2max', 'l2top2', 'l2attention'):
+    if method not in ('ot', 'l2max', 'l2top2', 'l2attention') + tuple(DOT_METHODS):
         raise ValueError(f'Unknown aggregation: {method}')
     if schedule not in ('pair', 'batch'):
         raise ValueError(f'Unknown schedule: {schedule}')
+    if method in DOT_METHODS:
+        return ops.dotmax_scores(q, c, pairing=_lib.PAIR_CROSS, sim=DOT_METHODS[method]).view(q.n, c.n)
     # schedule 'pair': one pair per reference call (evaluate.py) -> cdist's formula per pair (AUTO).  'batch': per padded
     # group of score_batch_size candidates (caching_score) -> per group, see _cdist_runs.
     if schedule == 'batch' and q.n > 1 and q.max_len > 25 and c.n > 0:
@@ -240,7 +255,7 @@ def _score_run(q, c, method, schedule, hparams, score_batch_size, cdist_mode, de
 def rank_pool(query_reps_list, pool, k=None, method='ot', schedule='pair', hparams=None, score_batch_size=64, deterministic=False):
     """Per query: [(pid, score), ...] best first, ties in pool order (evaluate.py:76).  otAspire goes through ONE
     C-ABI call that scores and ranks (aspire_ot_rank_f32).  deterministic: see score_pool."""
-    if deterministic and not (method == 'l2max' or (method == 'ot' and schedule == 'pair')):
+    if deterministic and not (method in ('l2max',) + tuple(DOT_METHODS) or (method == 'ot' and schedule == 'pair')):
         raise ValueError("deterministic=True is built for method 'ot' with schedule 'pair' and for 'l2max'")
     pool = _as_pool(pool)
     if len(pool) == 0:
@@ -276,7 +291,7 @@ def _launch_rank_pools(query_reps_list, pools, k, hparams, method='ot', determin
     """Uploads + the one library call of rank_pools on the CURRENT stream; returns (pools, top_scores, top_idx) GPU tensors
     (None for the tensors when every pool is empty)."""
     hparams = hparams or {}
-    if method not in ('ot', 'l2max'):
+    if method not in BATCH_METHODS:
         raise ValueError(f'Unknown aggregation: {method}')
     if hparams.get('geoml_reach', None) is not None:
         raise NotImplementedError('unbalanced OT (geoml_reach) is not built')
@@ -309,6 +324,9 @@ def _launch_rank_pools(query_reps_list, pools, k, hparams, method='ot', determin
                              torch.cat([r.start + int(b) for r, b in zip(nonempty, bases)]).to(torch.int32).contiguous(),
                              torch.cat([r.len for r in nonempty]).contiguous(), ext=0, max_len=max(r.max_len for r in nonempty))
     job_off = torch.tensor(np.concatenate([[0], np.cumsum(sizes)]), dtype=torch.int32, device=dev)
+    if method in DOT_METHODS:
+        _, top_s, top_i = ops.dotmax_rank_batch(q, c, job_off, max_job, k, sim=DOT_METHODS[method])
+        return pools, top_s, top_i
     if method == 'l2max':
         _, top_s, top_i = ops.l2max_rank_batch(q, c, job_off, max_job, k, one_form=deterministic)
         return pools, top_s, top_i
@@ -328,7 +346,8 @@ def _ranked_lists(pools, top_s, top_i):
 def rank_pools(query_reps_list, pools, k=None, hparams=None, method='ot', deterministic=False):
     """The whole per-query loop of evaluate.py:58-76 in ONE library call: query j is scored against ITS OWN pool
     pools[j] (every query of a dataset has its own candidate pool, evaluate.py:60-62) with otAspire, one epsilon schedule
-    per pair (AspireModel.get_similarity, models.py:190-197) -- or, method='l2max', tsAspire's max-sim -- and each pool is
+    per pair (AspireModel.get_similarity, models.py:190-197) -- or, method='l2max', tsAspire's max-sim, or 'cosine' / 'dotlse',
+    cosentbert's (score_pool) -- and each pool is
     ranked on its own (stable descending, evaluate.py:76).  pools: list of CandidatePool or lists of [S_i, 768] arrays.
     Returns per query [(pid, score), ...].  deterministic: one kernel form whatever the batch's size -- the same bits and the
     same order as rank_pool(..., deterministic=True) query by query (see score_pool)."""

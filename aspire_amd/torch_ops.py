@@ -12,6 +12,7 @@ implementation so that shapes propagate under FakeTensor / torch.compile tracing
     torch.ops.aspire.l2max_scores(q, q_lens, c, c_lens, paired) -> scores                          A9   pair_distances.py:138-186
     torch.ops.aspire.ot_sinkhorn_scores(q, q_lens, c, c_lens, blur, scaling, temp, group, want, paired, extras)
                                          -> (scores, q_distr, c_distr, pair_sims, plan)           A5-A8 pair_distances.py:21-92
+    torch.ops.aspire.dotmax_scores(q, q_lens, c, c_lens, paired, cosine) -> scores                A13  models.py:602-604
     torch.ops.aspire.topk_desc(scores, k, idx_base) -> (top_scores, top_idx)                       A12  evaluate.py:76
     torch.ops.aspire.topk_keys(scores, k, idx_base) -> keys          } the shard merge of section 8(e): local top-k in key
     torch.ops.aspire.topk_merge(gathered_keys, k) -> (top_scores, top_idx)  } form, (all-gather by the caller), merge
@@ -142,6 +143,19 @@ def l2max_scores(q: Tensor, q_lens: Tensor, c: Tensor, c_lens: Tensor, paired: b
 
 @l2max_scores.register_fake
 def _(q, q_lens, c, c_lens, paired):
+    return q.new_empty(_npairs(q.shape[0], c.shape[0], paired))
+
+
+# cosine: max over the sentence pairs of sklearn's cosine similarity (TrainedSentModel.get_similarity); False: of the raw dot
+@torch.library.custom_op('aspire::dotmax_scores', mutates_args=(), device_types='cuda')
+def dotmax_scores(q: Tensor, q_lens: Tensor, c: Tensor, c_lens: Tensor, paired: bool, cosine: bool) -> Tensor:
+    return ops.dotmax_scores(_padded_repset(q, q_lens), _padded_repset(c, c_lens),
+                             pairing=_lib.PAIR_PAIRED if paired else _lib.PAIR_CROSS,
+                             sim=_lib.SIM_COSINE if cosine else _lib.SIM_DOT)
+
+
+@dotmax_scores.register_fake
+def _(q, q_lens, c, c_lens, paired, cosine):
     return q.new_empty(_npairs(q.shape[0], c.shape[0], paired))
 
 

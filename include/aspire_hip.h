@@ -428,6 +428,32 @@ int aspire_l2max_rank_batch_f32(const aspire_repset* q, const aspire_repset* c, 
                                 size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * A13  cosentbert / ictsentbert max-sim.  Replaces TrainedSentModel.get_similarity,
+ * src/evaluation/utils/models.py:602-604 (float(np.max(sklearn.metrics.pairwise.cosine_similarity(x, y)))), and the
+ * per-query scoring of pp_gen_nearest.py rank_pool_sent (:863-986; 'dotlse' takes np.matmul instead).
+ *   scores [P] out: max over valid (i < q_len, j < c_len) of sim(q_i, c_j); P, pairing, CSR / padded rep sets and the
+ *                   128-row limit as aspire_l2max_scores_f32.  The planes and doc_box fields are ignored.
+ *   sim  ASPIRE_SIM_COSINE: sklearn's float32 path -- each row divided by n = sqrt(fp32 sum of squares), n < 10 * FLT_EPSILON
+ *        replaced by 1 (a zero row scores 0, a row whose sum of squares underflows keeps its raw dot), a row whose sum of
+ *        squares overflows to inf divides to zeros (scores 0 against everything, never NaN).  Non-finite rows are outside
+ *        the contract (the host layer rejects them, as sklearn's check_array does).
+ *        ASPIRE_SIM_DOT: the raw dot product.
+ *   Exact fp32 matrix products (v_mfma_f32_16x16x4_f32), four independent accumulators over k; the similarity block is never
+ *   written.  aspire_dotmax_rank_batch_f32 is the per-query loop over J (query, pool) jobs with the job_off / max_job /
+ *   job_base / top-k / keys contract of aspire_l2max_rank_batch_f32 (CSR rep sets, ties in pool order); its workspace,
+ *   16-byte aligned, is aspire_dotmax_rank_batch_workspace_bytes(q, c, max_job, k) bytes (0 for pools of <= 4096).
+ * ------------------------------------------------------------------------------------------- */
+#define ASPIRE_SIM_COSINE 0   /* sklearn cosine_similarity: rows / fp32 L2 norm, then dot (models.py:602-604) */
+#define ASPIRE_SIM_DOT 1      /* np.matmul (pp_gen_nearest.py rank_pool_sent, 'dotlse') */
+int aspire_dotmax_scores_f32(const aspire_repset* q, const aspire_repset* c, int64_t D, int pairing, int sim,
+                             float* scores, void* stream);
+size_t aspire_dotmax_rank_batch_workspace_bytes(const aspire_repset* q, const aspire_repset* c, int64_t max_job, int64_t k);
+int aspire_dotmax_rank_batch_f32(const aspire_repset* q, const aspire_repset* c, int64_t D, const int32_t* job_off,
+                                 int64_t max_job, int sim, float* scores, int64_t k, const int32_t* job_base,
+                                 float* top_scores, int64_t* top_idx, uint64_t* keys, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * SURVEY.md 8(e)  shard merge.  The same rank in KEY form for the candidate-pool shards of a multi-GPU job:
  *   aspire_topk_keys_f32    per-query local top-k as sortable 64-bit keys [Q, k]:
  *                           (order-preserving score bits << 32) | (0xFFFFFFFF - global index), 0 = padding.
