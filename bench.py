@@ -1,8 +1,13 @@
 """bench.py -- query x candidate OT alignments per second (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
-         --master-port P bench.py --gpus N --steps K --warmup W
+         --master-port P bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does what the headline needs and nothing else: it builds the pool store, runs the warm-up, times the K steps,
+writes --dump-outputs and prints the result line.  --full adds everything else the bench measures and checks, all after the
+timed region: the checks on the ranked outputs, the per-stage kernel durations and rooflines, the other calling patterns,
+the other configs, the CPU baseline and, at N > 1, the `rccl` block and the per-rank side measurements.
 
 Workload at N=1 = BASELINE.json configs[1]: otAspire, 1 query x 1000 candidates, 8 sentences x 768 d, reps ~ N(0,1)
 fp32, resident in HBM before the timed region.  One STEP = one query re-ranked against ITS OWN 1000-candidate pool
@@ -32,8 +37,8 @@ At N > 1 every rank holds its own 1000-candidate block of each job's N * 1000-ca
 block (key form, global indices), and the per-job top-k lists are merged with ONE RCCL all-gather per call + one merge
 kernel.  No data-path collective.
 
-Rank 0 prints ONE JSON line.  `roofline` prices the dominant kernel (the scoring kernel: it streams every rep once)
-against HBM: algorithmic bytes per launch = 24 605 B/pair x pairs per launch over the kernel's duration
+Rank 0 prints ONE JSON line.  What follows is in it under --full only.  `roofline` prices the dominant kernel (the
+scoring kernel: it streams every rep once) against HBM: algorithmic bytes per launch = 24 605 B/pair x pairs per launch over the kernel's duration
 measured live with HIP events around launches of that stage alone on the launch stream
 (aspire_debug_ot_rank_batch_stages_f32), on the rotating (cold) pools; `l3_resident_frac` is the same on ONE pool set small
 enough to stay in the Infinity Cache; `step` prices the whole step (all kernels, timed region) against the same bytes;
@@ -443,10 +448,13 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20000, help='timed steps: (query, own 1000-candidate pool) jobs')
     ap.add_argument('--warmup', type=int, default=20)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also run the checks and every side measurement (stages, rooflines, other calling '
+                         'patterns and configs, CPU baseline; at N > 1 the rccl block and the per-rank probes)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baselines')
     ap.add_argument('--no-probes', action='store_true',
-                    help='skip the side measurements that launch the scoring kernel at OTHER sizes / forms (Infinity-Cache-resident job set, '
-                         'two-kernel form): for counter passes, whose per-kernel sums should hold the 20-job launches only')
+                    help='with --full: skip the side measurements that launch the scoring kernel at OTHER sizes / forms (Infinity-Cache-resident '
+                         'job set, two-kernel form): for counter passes, whose per-kernel sums should hold the 20-job launches only')
     ap.add_argument('--streams', type=int, default=3,
                     help='independent calls in flight: calls go round-robin over this many caller streams, each with its own '
                          'outputs and workspace (1 = one call at a time)')
@@ -483,7 +491,8 @@ def main():
     # has run this code yet -- DESIGN.md section 5) ---------------------------------------------------------------------------
     rccl = None
     if world > 1:
-        dist.barrier()
+        dist.barrier()                  # the other ranks import the library rank 0 has built
+    if world > 1 and args.full:
         props = torch.cuda.get_device_properties(device)
         mine = {'rank': rank, 'local_rank': local_rank, 'device': torch.cuda.get_device_name(device), 'uuid': str(getattr(props, 'uuid', '')),
                 'gcn_arch': getattr(props, 'gcnArchName', ''), 'cus': props.multi_processor_count, 'xcds': props.multi_processor_count // 32,
@@ -640,6 +649,41 @@ def main():
         os.makedirs(args.dump_outputs, exist_ok=True)
         for name, arr in dump.items():
             np.save(os.path.join(args.dump_outputs, f'{name}.npy'), arr)
+    headline = None
+    if rank == 0:
+        headline = {
+            'metric': 'query x candidate OT alignments/sec', 'value': world * n_steps * NC / elapsed,
+            'unit': 'alignments/s', 'n_gpus': world, 'steps': n_steps, 'warmup': args.warmup, 'calls': n_calls,
+            'ms_per_step': elapsed / n_steps * 1e3, 'higher_is_better': True, 'scaling': 'weak',
+            'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
+            'timed_region_ms': elapsed * 1e3,
+            'config': {'workload': f'otAspire compsci: 1 query x {NC} candidates per step (per GPU), {S} sents x {D}d, Sinkhorn OT '
+                                   f'(blur 0.05, scaling 0.9, one eps schedule per pair) + stable top-{TOPK} rank; every step its own '
+                                   f'query and its own pool, {M} distinct pools ({M * algorithmic_bytes(1) / 2**20:.0f} MiB > 256 MiB L3) '
+                                   f'walked by consecutive calls'
+                                   + (f'; sharded: one RCCL all-gather of {K} x {TOPK} keys per call + merge kernel' if shard_path else ''),
+                       'queries_per_step': 1, 'candidates_per_gpu_per_step': NC, 'sents': S, 'dim': D, 'topk': TOPK,
+                       'parallelism': f'candidate-pool shards x{world}',
+                       'launch': f'{K} steps = {K} independent (query, pool) jobs per aspire_ot_rank_batch_f32 call '
+                                 f'(eager, no hipGraph); {n_calls} calls for the {n_steps} timed steps (the last one holds the remainder), round-robin on '
+                                 f'{n_lanes} caller stream(s) with their own outputs and workspaces = {n_lanes} independent calls in flight '
+                                 f'(a call\'s solve tail and rank launch overlap the next call\'s streaming); one call at a time: see one_stream '
+                                 f'(--full)',
+                       'streams': n_lanes},
+        }
+
+    def finish(out):
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:
+        finish(headline)
+        return
+
+    # ---- --full: the checks and side measurements, none of them inside the timed region --------------------------------
     # the same schedule with ONE call at a time (lane 0 alone), for the record: not the reported value
     R1 = max(4, n_calls // 2)
     elapsed_one = timed(lambda: one_lane_calls(R1)) if n_lanes > 1 else elapsed * R1 * K / n_steps
@@ -775,23 +819,7 @@ def main():
             if tj.get('jobs_per_launch') == K:
                 traffic = tj.get('cost_kernel_hbm_bytes_per_launch')
         out = {
-            'metric': 'query x candidate OT alignments/sec', 'value': world * n_steps * NC / elapsed,
-            'unit': 'alignments/s', 'n_gpus': world, 'steps': n_steps, 'warmup': args.warmup, 'calls': n_calls,
-            'ms_per_step': elapsed / n_steps * 1e3, 'higher_is_better': True, 'scaling': 'weak',
-            'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
-            'timed_region_ms': elapsed * 1e3,
-            'config': {'workload': f'otAspire compsci: 1 query x {NC} candidates per step (per GPU), {S} sents x {D}d, Sinkhorn OT '
-                                   f'(blur 0.05, scaling 0.9, one eps schedule per pair) + stable top-{TOPK} rank; every step its own '
-                                   f'query and its own pool, {M} distinct pools ({M * algorithmic_bytes(1) / 2**20:.0f} MiB > 256 MiB L3) '
-                                   f'walked by consecutive calls'
-                                   + (f'; sharded: one RCCL all-gather of {K} x {TOPK} keys per call + merge kernel' if shard_path else ''),
-                       'queries_per_step': 1, 'candidates_per_gpu_per_step': NC, 'sents': S, 'dim': D, 'topk': TOPK,
-                       'parallelism': f'candidate-pool shards x{world}',
-                       'launch': f'{K} steps = {K} independent (query, pool) jobs per aspire_ot_rank_batch_f32 call '
-                                 f'(eager, no hipGraph); {n_calls} calls for the {n_steps} timed steps (the last one holds the remainder), round-robin on '
-                                 f'{n_lanes} caller stream(s) with their own outputs and workspaces = {n_lanes} independent calls in flight '
-                                 f'(a call\'s solve tail and rank launch overlap the next call\'s streaming); one call at a time: see one_stream',
-                       'streams': n_lanes},
+            **headline,
             # the three calling patterns, all at top level: `value` = calls in flight on several caller streams; one call (of K jobs) at a
             # time; ONE job alone (BASELINE config 2 as worded: 1 query x 1000 candidates, one aspire_ot_rank_f32 call, latency bound)
             'one_stream_value': world * K * R1 * NC / elapsed_one,
@@ -911,11 +939,7 @@ def main():
                               'pairs_per_s': sum(r['pairs_per_s'] for r in e2e_ranks),
                               'merged_top1_agrees': len({r['top1_of_query0'] for r in e2e_ranks}) == 1, 'ranks': e2e_ranks}
                 out['config']['e2e_docs_per_s'] = out['e2e']['docs_per_s']
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish(out)
 
 
 if __name__ == '__main__':

@@ -120,11 +120,11 @@ def test_empty_shard(tmp_path):
 
 
 def test_bench_two_ranks_on_one_gpu():
-    """bench.py --gpus 2 with both ranks on cuda:0 over gloo: sharded global indices, all-gather layout, merge kernel,
+    """bench.py --gpus 2 --full with both ranks on cuda:0 over gloo: sharded global indices, all-gather layout, merge kernel,
     and the checks bench.py itself makes on the merged ranking (every rank identical, candidates of both shards)"""
     env = dict(os.environ, ASPIRE_BENCH_ONE_GPU='1', MASTER_ADDR='127.0.0.1', ASPIRE_BENCH_E2E_DOCS='256')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
-           '--master-port', str(_free_port()), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '120', '--warmup', '5']
+           '--master-port', str(_free_port()), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '120', '--warmup', '5', '--full']
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     import json

@@ -5,7 +5,7 @@
 #   bash tools/experiments/rehearse8.sh [out.json]
 out=${1:-gpurun_out/r6_rehearse8.json}
 export ASPIRE_BENCH_ONE_GPU=1 MASTER_ADDR=127.0.0.1 ASPIRE_BENCH_E2E_DOCS=${ASPIRE_BENCH_E2E_DOCS:-1024} HSA_ENABLE_IPC_MODE_LEGACY=0
-python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 8 --steps 20 --warmup 5 --repeats 6 \
+python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 8 --steps 20 --warmup 5 --full \
     2> ${out%.json}.stderr | grep '^{' | tail -1 > $out
 python - "$out" <<'PY'
 import json, sys
