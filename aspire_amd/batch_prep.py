@@ -120,6 +120,14 @@ def spans_to_csr(batch_senttok_idxs, max_sents):
 _SEP_RE = re.compile(r'\[SEP\]')
 
 
+def batch_tensors(bert_batch):
+    """(ids, token type ids or None, attention mask or None) of the README's HF tokenizer dict (input_ids / token_type_ids /
+    attention_mask) or of the batchers' (tokid_tt / seg_tt / attnmask_tt)."""
+    if 'input_ids' in bert_batch:
+        return bert_batch['input_ids'], bert_batch.get('token_type_ids'), bert_batch.get('attention_mask')
+    return bert_batch['tokid_tt'], bert_batch.get('seg_tt'), bert_batch.get('attnmask_tt')
+
+
 def prepare_bert_seqs(sents, tokenizer):
     """SentTripleBatcher.prepare_bert_sentences (src/learning/batchers.py:209-254): every string is ONE sequence, cut to its
     first 500 word pieces, [CLS] ids [SEP]; ids, segment ids and attention mask right-padded with ``tokenizer.pad_token_id``.

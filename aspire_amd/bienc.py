@@ -8,17 +8,15 @@ examples/ex_aspire_bienc.py:33-58 and for the test-time surface of MySPECTER
     doc_reps = model.forward(tokenizer(texts, padding=True, return_tensors='pt'))     # [B, 768]
 
 A document's rep is the CLS row of a learned softmax mix of all n_layers + 1 hidden states (``*-full`` checkpoints), or of the last
-hidden state alone when there are no mix weights (the README's plain AutoModel use).  Both come out of ONE library call,
-aspire_bert_forward_cls_f32 (include/aspire_hip.h): the encoder of HipBertEncoder with the CLS rows tapped after every layer and a last
-layer that computes the CLS rows only.  The mix weights are softmaxed on the host, as SoftmaxMixLayers does, and passed in.
+hidden state alone when there are no mix weights (the README's plain AutoModel use).  Both come out of ONE encoder call,
+HipBertEncoder.forward_cls: the encoder with the CLS rows tapped after every layer and a last layer that computes the CLS rows only.
+The mix weights are softmaxed on the host, as SoftmaxMixLayers does, and passed in.
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from . import ops
-from ._lib import check, lib
+from .batch_prep import batch_tensors
 from .encoder import HipBertEncoder
 
 
@@ -40,13 +38,6 @@ def split_state_dict(sd):
     return enc, mix
 
 
-def _batch_tensors(bert_batch):
-    """The README's HF tokenizer dict (input_ids / token_type_ids / attention_mask) or the batchers' (tokid_tt / seg_tt / attnmask_tt)."""
-    if 'input_ids' in bert_batch:
-        return bert_batch['input_ids'], bert_batch.get('token_type_ids'), bert_batch.get('attention_mask')
-    return bert_batch['tokid_tt'], bert_batch.get('seg_tt'), bert_batch.get('attnmask_tt')
-
-
 class AspireBiEnc:
     def __init__(self, model_hparams=None, bert_model=None, layer_weights=None):
         """
@@ -63,7 +54,6 @@ class AspireBiEnc:
         self.layer_weights = None
         if layer_weights is not None:
             self.set_layer_weights(layer_weights)
-        self._ws = {}
 
     def eval(self):
         return self
@@ -78,10 +68,7 @@ class AspireBiEnc:
         """AspireBiEnc / MySPECTER state dict: the encoder is rebuilt from bert_encoder.*, the mix from bert_layer_weights.weight."""
         enc, mix = split_state_dict(sd)
         if enc:
-            from transformers import BertModel
-            bm = BertModel(self.bert_encoder.config, add_pooling_layer=any(k.startswith('pooler.') for k in enc))
-            bm.load_state_dict(enc)
-            self.bert_encoder = HipBertEncoder(bm)
+            self.bert_encoder = HipBertEncoder.from_state_dict(self.bert_encoder.config, enc)
             self.bert_layer_count = self.bert_encoder.config.num_hidden_layers + 1
         self.layer_weights = None
         if mix is not None:
@@ -95,52 +82,19 @@ class AspireBiEnc:
         return torch.softmax(self.layer_weights, dim=1)[0].numpy().astype(np.float32)
 
     # ---- the forward ---------------------------------------------------------------------------------------------------
-    def _call(self, tok, typ, msk, want_layers):
-        enc = self.bert_encoder
-        b, l = tok.shape
-        n = enc.config.num_hidden_layers
-        dev = enc.device
-        out = torch.empty(b, 768, device=dev, dtype=torch.float32)
-        layers = torch.empty(n + 1, b, 768, device=dev, dtype=torch.float32) if want_layers else None
-        mix = self.layer_mix()
-        mix_c = ctypes.cast((ctypes.c_float * len(mix))(*mix.tolist()), ctypes.c_void_p) if mix is not None else None
-        need = lib.aspire_bert_cls_workspace_bytes(ctypes.byref(enc._w), b, l)
-        sid = torch.cuda.current_stream().cuda_stream
-        ws = self._ws.get(sid)
-        if ws is None or ws.numel() < need:
-            self._ws[sid] = ws = torch.empty(max(need, 16), device=dev, dtype=torch.uint8)
-        check(lib.aspire_bert_forward_cls_f32(ctypes.byref(enc._w), ops._ptr(tok), ops._ptr(typ), ops._ptr(msk), b, l, mix_c,
-                                              ops._ptr(out), ops._ptr(layers), ops._ptr(ws), ws.numel(), ops._stream()))
-        return out, layers
-
     def forward_device(self, tokid_tt, token_type_ids=None, attention_mask=None, want_layers=False):
         """int64 [B, L] tensors (any device) -> (cls reps [B, 768], the CLS rows of every hidden state [n_layers + 1, B, 768] or None),
-        on the GPU.  Same rules as AspireConSent: a LayerNorm-epilogue timeout runs the batch again with the separate LayerNorm pass,
-        non-finite output (an activation beyond the fp16 planes' range) again on the full-range kernels."""
+        on the GPU, under the encoder's fall-back rule (encoder.run_checked)."""
         enc = self.bert_encoder
-        dev = enc.device
-        tok = tokid_tt.to(device=dev, dtype=torch.int64).contiguous()
-        if tok.numel() and (int(tok.max()) >= enc.config.vocab_size or int(tok.min()) < 0):
-            raise IndexError('token id out of range')   # nn.Embedding raises IndexError on the reference path
-        typ = token_type_ids.to(device=dev, dtype=torch.int64).contiguous() if token_type_ids is not None else None
-        msk = attention_mask.to(device=dev, dtype=torch.int64).contiguous() if attention_mask is not None else torch.ones_like(tok)
-        from ._lib import pinned
-        import warnings
-        out, layers = self._call(tok, typ, msk, want_layers)
-        if enc.status():
-            warnings.warn('AspireBiEnc: the fused GEMM + LayerNorm exchange timed out; encoding again with ASPIRE_HIP_GEMM_LN=off')
-            with pinned(GEMM_LN='off'):
-                out, layers = self._call(tok, typ, msk, want_layers)
-        if not bool(torch.isfinite(out).all()) or (layers is not None and not bool(torch.isfinite(layers).all())):
-            warnings.warn('AspireBiEnc.forward: non-finite reps on the fp16-plane encoder path (an activation beyond 65504); '
-                          'encoding the batch again with ASPIRE_HIP_GEMM=bf16x3, ASPIRE_HIP_ATTN=f32')
-            with pinned(GEMM='bf16x3', ATTN='f32'):
-                out, layers = self._call(tok, typ, msk, want_layers)
-        return out, layers
+        tok, typ, msk = enc.device_inputs(tokid_tt, token_type_ids, attention_mask)
+        mix = self.layer_mix()
+        return enc.checked(lambda: enc.forward_cls(tok, typ, msk, mix, want_layers, check_ids=False),
+                           lambda r: bool(torch.isfinite(r[0]).all()) and (r[1] is None or bool(torch.isfinite(r[1]).all())),
+                           'AspireBiEnc')
 
     def forward(self, bert_batch):
         """AspireBiEnc.forward (ex_aspire_bienc.py:46-58): [B, 768] CLS reps, on the device of the input ids."""
-        tok, typ, msk = _batch_tensors(bert_batch)
+        tok, typ, msk = batch_tensors(bert_batch)
         return self.forward_device(tok, typ, msk)[0].to(tok.device)
 
     def __call__(self, bert_batch):
@@ -148,7 +102,7 @@ class AspireBiEnc:
 
     def partial_forward(self, bert_batch):
         """MySPECTER.partial_forward (disent_models.py:164-176): [B, 768] on the GPU (a 1-document batch stays [1, 768])."""
-        tok, typ, msk = _batch_tensors(bert_batch)
+        tok, typ, msk = batch_tensors(bert_batch)
         return self.forward_device(tok, typ, msk)[0]
 
     # ---- MySPECTER's test-time surface ----------------------------------------------------------------------------------

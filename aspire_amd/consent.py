@@ -66,32 +66,19 @@ class AspireConSent:
         tokid_tt, seg_tt, attnmask_tt = bert_batch['tokid_tt'], bert_batch['seg_tt'], bert_batch['attnmask_tt']
         out_dev = tokid_tt.device
         assert tokid_tt.shape == (batch_size, max_seq_len)
-        final_hidden_state = self.bert_encoder.forward_hidden(tokid_tt, token_type_ids=seg_tt,
-                                                              attention_mask=attnmask_tt)
+        enc = self.bert_encoder
+        tok, typ, msk = enc.device_inputs(tokid_tt, seg_tt, attnmask_tt)
         for doc in batch_senttok_idxs:
             for span in doc:
                 if span and (min(span) < 0 or max(span) >= max_seq_len):
                     raise IndexError('sentence token index out of range')   # numpy fancy indexing raises too
-        tok_idx, span_off = spans_to_csr(batch_senttok_idxs, max_sents)
-        dev = final_hidden_state.device
-        doc_cls_reps, sent_reps = ops.span_mean_pool(final_hidden_state, tok_idx.to(dev), span_off.to(dev), max_sents)
-        if self.bert_encoder.status():
-            # a LayerNorm-epilogue GEMM gave up waiting for its row block (encoder.hip: gemm_p_ln_kernel's bounded wait): once more with
-            # the LayerNorm as its own pass
-            from ._lib import pinned
-            import warnings
-            warnings.warn('AspireConSent: the fused GEMM + LayerNorm exchange timed out; encoding again with ASPIRE_HIP_GEMM_LN=off')
-            with pinned(GEMM_LN='off'):
-                final_hidden_state = self.bert_encoder.forward_hidden(tokid_tt, token_type_ids=seg_tt, attention_mask=attnmask_tt,
-                                                                      check_ids=False)
-            doc_cls_reps, sent_reps = ops.span_mean_pool(final_hidden_state, tok_idx.to(dev), span_off.to(dev), max_sents)
-        if not bool(torch.isfinite(sent_reps).all() & torch.isfinite(doc_cls_reps).all()):      # (the CLS token belongs to no sentence span)
-            # an activation beyond the fp16 planes' range (encoder.py: forward_full_range): once more on the full-range kernels
-            import warnings
-            warnings.warn('AspireConSent.forward: non-finite sentence reps on the fp16-plane encoder path (an activation beyond 65504); '
-                          'encoding the batch again with ASPIRE_HIP_GEMM=bf16x3, ASPIRE_HIP_ATTN=f32')
-            final_hidden_state = self.bert_encoder.forward_full_range(tokid_tt, seg_tt, attnmask_tt)
-            doc_cls_reps, sent_reps = ops.span_mean_pool(final_hidden_state, tok_idx.to(dev), span_off.to(dev), max_sents)
+        tok_idx, span_off = (t.to(enc.device) for t in spans_to_csr(batch_senttok_idxs, max_sents))
+
+        def run():
+            return ops.span_mean_pool(enc.forward_hidden(tok, typ, msk, check_ids=False), tok_idx, span_off, max_sents)
+        # (the CLS token belongs to no sentence span: both outputs are checked)
+        doc_cls_reps, sent_reps = enc.checked(run, lambda r: bool(torch.isfinite(r[1]).all() & torch.isfinite(r[0]).all()),
+                                              'AspireConSent')
         # the reference squeezes and re-unsqueezes (:76, :46-49): shapes are [B,768] and [B,S,768] for every B.
         return doc_cls_reps.to(out_dev), sent_reps.to(out_dev)
 
@@ -210,7 +197,7 @@ class AspireConSent:
             yield out, ids
 
     def encode_to_pool(self, batches, pids=None, want_cls=False, docs_per_forward=64, planes=False, sort_by_length=True,
-                       _full_range=False, stage_events=None, rows_per_forward=16384, streams=1, _ln_off=False):
+                       stage_events=None, rows_per_forward=16384, streams=1):
         """Encode document batches straight into a resident candidate pool.
 
         batches: iterable of (bert_batch, abs_lens, sent_tok_idxs) as prepare_abstracts returns them (it is consumed
@@ -233,17 +220,16 @@ class AspireConSent:
         second forward in flight fills those slots.  1: everything on the current stream.
         stage_events: a list that receives one (start, encoded, pooled) triple of HIP events per encoder call, recorded on the
         current stream INSIDE this call (tools/e2ebench.py: the stage's own time split; the caller reads them after a sync).
+        The finished store goes through the encoder's fall-back rule (encoder.run_checked) once: one status read and one range check
+        for the whole corpus; a re-run encodes everything again and its events replace the first run's.
         Returns a scorer.CandidatePool (and the [N, 768] CLS reps on the GPU with want_cls)."""
         from .scorer import CandidatePool
         dev = ops.require_gpu()
         batches = list(batches)
-        given = batches
         all_lens = [int(n) for _, abs_lens, _ in batches for n in abs_lens]       # corpus order
         n_docs, total = len(all_lens), int(sum(all_lens))
         lens_t = torch.tensor(all_lens, dtype=torch.int32)
         start_t = (torch.cumsum(lens_t, 0) - lens_t).to(torch.int32)
-        rows = torch.empty(max(total, 1), 768, device=dev, dtype=torch.float32)[:total]
-        cls_all = torch.empty(n_docs, 768, device=dev, dtype=torch.float32) if want_cls else None
         # token ids of every batch validated with ONE device round trip (nn.Embedding raises IndexError on the reference path);
         # per batch that check is a host sync in front of every encoder call
         if batches:
@@ -253,6 +239,33 @@ class AspireConSent:
                                  for i in range(0, len(batches), 64)])
             if int(lo_hi[:, 0].min()) < 0 or int(lo_hi[:, 1].max()) >= self.bert_encoder.config.vocab_size:
                 raise IndexError('token id out of range')
+        n_events = len(stage_events) if stage_events is not None else 0
+
+        def fill():
+            if stage_events is not None:
+                del stage_events[n_events:]
+            return self._fill_store(batches, start_t.numpy(), total, want_cls, docs_per_forward, sort_by_length, rows_per_forward,
+                                    streams, stage_events)
+        if total:
+            rows, cls_all = self.bert_encoder.checked(
+                fill, lambda r: bool(torch.isfinite(r[0]).all() & (torch.isfinite(r[1]).all() if want_cls else True)),
+                'AspireConSent.encode_to_pool')
+        else:
+            rows, cls_all = fill()
+        repset = ops.DeviceRepSet(rows, start_t.to(dev), lens_t.to(dev), ext=0, max_len=max(all_lens) if all_lens else 0,
+                                  lens_host=all_lens)
+        pool = CandidatePool.from_repset(repset, pids=pids)
+        if planes and total:
+            pool.prepare_planes()
+        return (pool, cls_all) if want_cls else pool
+
+    def _fill_store(self, batches, start_np, total, want_cls, docs_per_forward, sort_by_length, rows_per_forward, streams,
+                    stage_events):
+        """encode_to_pool's encoder calls and pooling: a new store (rows [total, 768], CLS reps [n_docs, 768] or None), filled."""
+        dev = ops.require_gpu()
+        n_docs = len(start_np)
+        rows = torch.empty(max(total, 1), 768, device=dev, dtype=torch.float32)[:total]
+        cls_all = torch.empty(n_docs, 768, device=dev, dtype=torch.float32) if want_cls else None
         # Per group of batches: (host) every batch's pooling tables -- token positions (CSR), slot -> store row -- uploaded as ONE int32
         # buffer, then the group's kernels.  (Uploaded batch by batch from pageable memory, each copy waited behind the encoder
         # kernels queued before it, and the next batch's kernels were launched late: the GPU sat idle ~0.5 ms per batch of 32
@@ -267,7 +280,6 @@ class AspireConSent:
             window_iter = iter([(self._merge_batches(batches, docs_per_forward), None)])
         else:
             window_iter = iter([(batches, None)])
-        start_np = start_t.numpy()
         doc0 = 0
         first = True
         cur = torch.cuda.current_stream()
@@ -340,35 +352,4 @@ class AspireConSent:
                 rows.record_stream(st)
                 if cls_all is not None:
                     cls_all.record_stream(st)
-        if total and not _ln_off and self.bert_encoder.status():
-            # a LayerNorm-epilogue GEMM gave up waiting for its row block (encoder.hip: gemm_p_ln_kernel's bounded wait): the whole corpus
-            # once more with the LayerNorm as its own pass (one sync over the finished store, as the range check below)
-            from ._lib import pinned
-            import warnings
-            warnings.warn('AspireConSent.encode_to_pool: the fused GEMM + LayerNorm exchange timed out; encoding again with '
-                          'ASPIRE_HIP_GEMM_LN=off')
-            with pinned(GEMM_LN='off'):
-                if stage_events is not None:
-                    del stage_events[:]
-                return self.encode_to_pool(given, pids=pids, want_cls=want_cls, docs_per_forward=docs_per_forward, planes=planes,
-                                           sort_by_length=sort_by_length, _full_range=_full_range, stage_events=stage_events,
-                                           rows_per_forward=rows_per_forward, streams=streams, _ln_off=True)
-        if total and not _full_range and not bool(torch.isfinite(rows).all() & (torch.isfinite(cls_all).all() if want_cls else True)):
-            # an activation left the fp16 planes' range somewhere (one check over the finished store): encode again on the kernels
-            # that take any fp32 value
-            from ._lib import pinned
-            import warnings
-            warnings.warn('AspireConSent.encode_to_pool: non-finite sentence reps on the fp16-plane encoder path; encoding again with '
-                          'ASPIRE_HIP_GEMM=bf16x3, ASPIRE_HIP_ATTN=f32')
-            with pinned(GEMM='bf16x3', ATTN='f32'):
-                if stage_events is not None:
-                    del stage_events[:]
-                return self.encode_to_pool(given, pids=pids, want_cls=want_cls, docs_per_forward=docs_per_forward, planes=planes,
-                                           sort_by_length=sort_by_length, _full_range=True, stage_events=stage_events,
-                                           rows_per_forward=rows_per_forward, streams=streams, _ln_off=True)
-        repset = ops.DeviceRepSet(rows, start_t.to(dev), lens_t.to(dev), ext=0, max_len=max(all_lens) if all_lens else 0,
-                                  lens_host=all_lens)
-        pool = CandidatePool.from_repset(repset, pids=pids)
-        if planes and total:
-            pool.prepare_planes()
-        return (pool, cls_all) if want_cls else pool
+        return rows, cls_all

@@ -4,15 +4,61 @@
 ``AutoModel.from_pretrained`` at examples/ex_aspire_consent.py:33) and exposes the one call the reference
 makes on it: ``encoder(tokid_tt, token_type_ids=seg_tt, attention_mask=attnmask_tt).last_hidden_state``
 (:72-73).  Weights are copied to HBM once, in nn.Linear layout; query/key/value are concatenated so the three
-projections are one GEMM.
+projections are one GEMM.  The bi-encoders' CLS read-out (aspire_bert_forward_cls_f32) runs on the same weights
+(forward_cls), and run_checked is the one fall-back rule every model class applies to what it hands out.
 """
 import ctypes
+import warnings
 from types import SimpleNamespace
 
 import torch
 
 from . import ops
-from ._lib import BertLayer, BertWeights, lib, check
+from ._lib import BertLayer, BertWeights, check, lib, pinned
+
+_LAYER_KEYS = ('attention.output.dense.weight', 'attention.output.dense.bias', 'attention.output.LayerNorm.weight',
+               'attention.output.LayerNorm.bias', 'intermediate.dense.weight', 'intermediate.dense.bias', 'output.dense.weight',
+               'output.dense.bias', 'output.LayerNorm.weight', 'output.LayerNorm.bias')
+
+
+def pack_weights(weights, n_heads, ln_eps):
+    """struct aspire_bert_weights over fp32 GPU tensors [word_emb, pos_emb, type_emb, emb_ln_g, emb_ln_b] + per layer [w_qkv, b_qkv,
+    w_o, b_o, ln1_g, ln1_b, w_ffn1, b_ffn1, w_ffn2, b_ffn2, ln2_g, ln2_b] (struct aspire_bert_layer, nn.Linear layout); the geometry
+    comes from the tensors' shapes.  The struct keeps the (contiguous) tensors and its layer array alive."""
+    assert (len(weights) - 5) % 12 == 0 and len(weights) >= 5, 'weights: 5 embedding tensors + 12 per layer'
+    w = [t.contiguous() for t in weights]
+    assert all(t.is_cuda and t.dtype == torch.float32 for t in w)
+    n_layers = (len(w) - 5) // 12
+    layers = (BertLayer * max(n_layers, 1))()
+    for i in range(n_layers):
+        for (f, _), t in zip(BertLayer._fields_, w[5 + 12 * i:17 + 12 * i]):
+            setattr(layers[i], f, ctypes.c_void_p(t.data_ptr()))
+    hidden_size = w[0].shape[1]
+    ffn = w[5 + 6].shape[0] if n_layers else 4 * hidden_size
+    bw = BertWeights(*(ctypes.c_void_p(t.data_ptr()) for t in w[:5]), layers, n_layers, n_heads, hidden_size, ffn,
+                     w[0].shape[0], w[1].shape[0], w[2].shape[0], float(ln_eps), None)
+    bw._keep = (layers, w)
+    return bw
+
+
+def run_checked(run, outputs_finite, who, status):
+    """The encoder's fall-back rule around run() (a forward and whatever reads it out), each re-run at most once, in this order:
+      * status() non-zero: a LayerNorm-epilogue GEMM gave up waiting for its row block (encoder.hip: gemm_p_ln_kernel's bounded
+        wait) and what run() made is invalid -- run again with the LayerNorm as its own pass, pinned(GEMM_LN='off');
+      * outputs_finite(result) false: an activation left the fp16 planes' range (HipBertEncoder.forward_full_range) -- run again
+        on the kernels that take any fp32 value, pinned(GEMM='bf16x3', ATTN='f32').
+    status() and outputs_finite() are the host syncs of the rule: one of each per call.  Returns run()'s last result."""
+    out = run()
+    if status():
+        warnings.warn(f'{who}: the fused GEMM + LayerNorm exchange timed out; encoding again with ASPIRE_HIP_GEMM_LN=off')
+        with pinned(GEMM_LN='off'):
+            out = run()
+    if not outputs_finite(out):
+        warnings.warn(f'{who}: non-finite reps on the fp16-plane encoder path (an activation beyond 65504); encoding again with '
+                      'ASPIRE_HIP_GEMM=bf16x3, ASPIRE_HIP_ATTN=f32')
+        with pinned(GEMM='bf16x3', ATTN='f32'):
+            out = run()
+    return out
 
 
 class HipBertEncoder:
@@ -28,35 +74,17 @@ class HipBertEncoder:
         sd = {k: v.detach() for k, v in bert_model.state_dict().items()}
         self.config = cfg
         self.device = dev
-        self._keep = []
-
-        def put(t):
-            t = t.to(device=dev, dtype=torch.float32).contiguous()
-            self._keep.append(t)
-            return ctypes.c_void_p(t.data_ptr())
-
         pre = 'bert.' if any(k.startswith('bert.') for k in sd) else ''
         emb = pre + 'embeddings.'
-        n_layers = cfg.num_hidden_layers
-        self._layers = (BertLayer * max(n_layers, 1))()
-        for i in range(n_layers):
+        w = [sd[emb + k] for k in ('word_embeddings.weight', 'position_embeddings.weight', 'token_type_embeddings.weight',
+                                   'LayerNorm.weight', 'LayerNorm.bias')]
+        for i in range(cfg.num_hidden_layers):
             p = f'{pre}encoder.layer.{i}.'
             att = p + 'attention.self.'
-            ly = self._layers[i]
-            ly.w_qkv = put(torch.cat([sd[att + 'query.weight'], sd[att + 'key.weight'], sd[att + 'value.weight']], 0))
-            ly.b_qkv = put(torch.cat([sd[att + 'query.bias'], sd[att + 'key.bias'], sd[att + 'value.bias']], 0))
-            ly.w_o, ly.b_o = put(sd[p + 'attention.output.dense.weight']), put(sd[p + 'attention.output.dense.bias'])
-            ly.ln1_g = put(sd[p + 'attention.output.LayerNorm.weight'])
-            ly.ln1_b = put(sd[p + 'attention.output.LayerNorm.bias'])
-            ly.w_ffn1, ly.b_ffn1 = put(sd[p + 'intermediate.dense.weight']), put(sd[p + 'intermediate.dense.bias'])
-            ly.w_ffn2, ly.b_ffn2 = put(sd[p + 'output.dense.weight']), put(sd[p + 'output.dense.bias'])
-            ly.ln2_g, ly.ln2_b = put(sd[p + 'output.LayerNorm.weight']), put(sd[p + 'output.LayerNorm.bias'])
-        self._w = BertWeights(
-            put(sd[emb + 'word_embeddings.weight']), put(sd[emb + 'position_embeddings.weight']),
-            put(sd[emb + 'token_type_embeddings.weight']), put(sd[emb + 'LayerNorm.weight']),
-            put(sd[emb + 'LayerNorm.bias']), self._layers, n_layers, cfg.num_attention_heads, cfg.hidden_size,
-            cfg.intermediate_size, cfg.vocab_size, cfg.max_position_embeddings, cfg.type_vocab_size,
-            float(cfg.layer_norm_eps), None)
+            w += [torch.cat([sd[att + 'query.weight'], sd[att + 'key.weight'], sd[att + 'value.weight']], 0),
+                  torch.cat([sd[att + 'query.bias'], sd[att + 'key.bias'], sd[att + 'value.bias']], 0)]
+            w += [sd[p + k] for k in _LAYER_KEYS]
+        self._w = pack_weights([t.to(device=dev, dtype=torch.float32) for t in w], cfg.num_attention_heads, cfg.layer_norm_eps)
         self._ws = {}                       # one workspace per HIP stream: forwards on different streams overlap
         # the nn.Linear weights' fp16 planes, formed once (include/aspire_hip.h: aspire_bert_prepare_planes)
         nbytes = lib.aspire_bert_planes_bytes(ctypes.byref(self._w))
@@ -66,51 +94,88 @@ class HipBertEncoder:
                 check(lib.aspire_bert_prepare_planes(ctypes.byref(self._w), ops._ptr(self._planes), nbytes, ops._stream()))
                 self._w.planes = ctypes.c_void_p(self._planes.data_ptr())
             except NotImplementedError as e:        # a weight beyond the fp16 planes' range: the on-the-fly bf16x3 GEMMs take any fp32
-                import warnings
                 warnings.warn(f'HipBertEncoder: {e}; running without pre-split weights')
                 self._planes = None
+
+    @classmethod
+    def from_state_dict(cls, config, sd):
+        """The encoder of a BertModel(config) holding state dict sd (with a pooler when sd has one: load_state_dict is strict)."""
+        from transformers import BertModel
+        bm = BertModel(config, add_pooling_layer=any(k.startswith('pooler.') for k in sd))
+        bm.load_state_dict(sd)
+        return cls(bm)
 
     def eval(self):
         return self
 
+    def device_inputs(self, tokid_tt, token_type_ids=None, attention_mask=None, check_ids=True):
+        """int64 [B, L] tensors (any device) -> (ids, type ids or None, mask) contiguous int64 on the GPU; no mask: all ones.
+        check_ids: token ids outside the vocabulary raise IndexError (one host sync); False: the caller has validated them."""
+        dev = self.device
+        tok = tokid_tt.to(device=dev, dtype=torch.int64).contiguous()
+        if check_ids and tok.numel() and (int(tok.max()) >= self.config.vocab_size or int(tok.min()) < 0):
+            raise IndexError('token id out of range')   # nn.Embedding raises IndexError on the reference path
+        typ = token_type_ids.to(device=dev, dtype=torch.int64).contiguous() if token_type_ids is not None else None
+        msk = attention_mask.to(device=dev, dtype=torch.int64).contiguous() if attention_mask is not None \
+            else torch.ones_like(tok)
+        return tok, typ, msk
+
+    def _workspace(self, need):
+        """The current stream's workspace, grown to `need` bytes: a forward's scratch is reused by the next one on its stream."""
+        sid = torch.cuda.current_stream().cuda_stream
+        ws = self._ws.get(sid)
+        if ws is None or ws.numel() < need:
+            self._ws[sid] = ws = torch.empty(max(need, 16), device=self.device, dtype=torch.uint8)
+        return ws
+
     def forward_full_range(self, tokid_tt, token_type_ids=None, attention_mask=None):
         """The forward on the kernels that take ANY fp32 activation: GEMM operands split into three bf16 planes on the fly, attention
         on the fp32-input MFMA.  The default path keeps activations as two fp16 planes (|x| <= 65504: far above what BERT-base
-        checkpoints produce, but a fine-tuned model with an outlier feature beyond it turns into inf there); callers that find
-        non-finite hidden states (AspireConSent.forward / encode_to_pool check what they hand out) come here."""
-        from ._lib import pinned
+        checkpoints produce, but a fine-tuned model with an outlier feature beyond it turns into inf there); run_checked re-runs a
+        forward with non-finite output on these kernels."""
         with pinned(GEMM='bf16x3', ATTN='f32'):
             return self.forward_hidden(tokid_tt, token_type_ids, attention_mask, check_ids=False)
 
     def forward_hidden(self, tokid_tt, token_type_ids=None, attention_mask=None, check_ids=True):
         """int64 [B, L] tensors (any device) -> last_hidden_state [B, L, 768] on the GPU.  check_ids=False: the caller has
         validated the token ids already (encode_to_pool checks all its batches with one device round trip)."""
-        dev = self.device
-        tok = tokid_tt.to(device=dev, dtype=torch.int64).contiguous()
+        tok, typ, msk = self.device_inputs(tokid_tt, token_type_ids, attention_mask, check_ids)
         b, l = tok.shape
-        if check_ids and (int(tok.max()) >= self.config.vocab_size or int(tok.min()) < 0):
-            raise IndexError('token id out of range')   # nn.Embedding raises IndexError on the reference path
-        typ = token_type_ids.to(device=dev, dtype=torch.int64).contiguous() if token_type_ids is not None else None
-        msk = attention_mask.to(device=dev, dtype=torch.int64).contiguous() if attention_mask is not None \
-            else torch.ones_like(tok)
-        out = torch.empty(b, l, 768, device=dev, dtype=torch.float32)
-        need = lib.aspire_bert_workspace_bytes(ctypes.byref(self._w), b, l)
-        sid = torch.cuda.current_stream().cuda_stream
-        ws = self._ws.get(sid)
-        if ws is None or ws.numel() < need:
-            self._ws[sid] = ws = torch.empty(need, device=dev, dtype=torch.uint8)
+        out = torch.empty(b, l, 768, device=self.device, dtype=torch.float32)
+        ws = self._workspace(lib.aspire_bert_workspace_bytes(ctypes.byref(self._w), b, l))
         check(lib.aspire_bert_forward_f32(ctypes.byref(self._w), ops._ptr(tok), ops._ptr(typ), ops._ptr(msk), b, l,
                                           ops._ptr(out), ops._ptr(ws), ws.numel(), ops._stream()))
         return out
+
+    def forward_cls(self, tokid_tt, token_type_ids=None, attention_mask=None, layer_mix=None, want_layers=False, check_ids=True):
+        """The bi-encoders' read-out (aspire_bert_forward_cls_f32): int64 [B, L] tensors (any device) -> (the CLS rows of the
+        layer_mix-weighted sum of the n_layers + 1 hidden states [B, 768] -- of the last hidden state alone when layer_mix is None --,
+        the CLS rows of every hidden state [n_layers + 1, B, 768] with want_layers, else None), on the GPU.  layer_mix: n_layers + 1
+        float32 weights, already softmaxed.  check_ids as forward_hidden."""
+        tok, typ, msk = self.device_inputs(tokid_tt, token_type_ids, attention_mask, check_ids)
+        b, l = tok.shape
+        dev = self.device
+        out = torch.empty(b, 768, device=dev, dtype=torch.float32)
+        layers = torch.empty(self.config.num_hidden_layers + 1, b, 768, device=dev, dtype=torch.float32) if want_layers else None
+        mix = ctypes.cast((ctypes.c_float * len(layer_mix))(*[float(x) for x in layer_mix]), ctypes.c_void_p) \
+            if layer_mix is not None else None
+        ws = self._workspace(lib.aspire_bert_cls_workspace_bytes(ctypes.byref(self._w), b, l))
+        check(lib.aspire_bert_forward_cls_f32(ctypes.byref(self._w), ops._ptr(tok), ops._ptr(typ), ops._ptr(msk), b, l, mix,
+                                              ops._ptr(out), ops._ptr(layers), ops._ptr(ws), ws.numel(), ops._stream()))
+        return out, layers
 
     @staticmethod
     def status():
         """The encoder kernels' sticky status word (include/aspire_hip.h: aspire_bert_status), read and cleared; synchronises the current
         stream.  Non-zero: a LayerNorm-epilogue GEMM gave up waiting for its row block (ASPIRE_BERT_STATUS_LN_TIMEOUT) -- the forwards
-        since the last check are invalid; the callers in consent.py run them again under pinned(GEMM_LN='off')."""
+        since the last check are invalid; run_checked runs them again under pinned(GEMM_LN='off')."""
         v = ctypes.c_int32(0)
         check(lib.aspire_bert_status(ctypes.byref(v), ops._stream()))
         return int(v.value)
+
+    def checked(self, run, outputs_finite, who):
+        """run_checked with this encoder's status word."""
+        return run_checked(run, outputs_finite, who, self.status)
 
     def __call__(self, tokid_tt, token_type_ids=None, attention_mask=None):
         return SimpleNamespace(last_hidden_state=self.forward_hidden(tokid_tt, token_type_ids, attention_mask))

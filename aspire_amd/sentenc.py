@@ -8,15 +8,15 @@ surface of TrainedSentModel (src/evaluation/utils/models.py:568-604), SentBERTWr
     sim = model.get_similarity(reps[0], reps[1])                           # max cosine over the sentence pairs
 
 Every abstract sentence goes through SciBERT on its own; its rep is the CLS row of last_hidden_state (Pooling('cls')).  The
-encoder is aspire_bert_forward_cls_f32 with no layer mix (AspireBiEnc's call), the score aspire_dotmax_scores_f32 /
+encoder is HipBertEncoder.forward_cls with no layer mix (AspireBiEnc's read-out), the score aspire_dotmax_scores_f32 /
 aspire_dotmax_rank_batch_f32 (include/aspire_hip.h, A13).
 """
 import numpy as np
 import torch
 
 from . import _lib, ops
-from .batch_prep import pad_sentences, sentence_buckets, tokenize_sentences
-from .bienc import AspireBiEnc, _batch_tensors
+from .batch_prep import batch_tensors, pad_sentences, sentence_buckets, tokenize_sentences
+from .encoder import HipBertEncoder
 
 
 def split_state_dict(sd):
@@ -59,32 +59,29 @@ class AspireSentEnc:
             from transformers import AutoTokenizer
             tokenizer = AutoTokenizer.from_pretrained(hf_model_name)
         self.tokenizer = tokenizer
-        self.config = bert_model.config
-        self._enc = AspireBiEnc(bert_model=bert_model)
+        self.bert_encoder = HipBertEncoder(bert_model)
 
     def eval(self):
         return self
 
     def load_state_dict(self, sd):
         """sent_encoder_cur_best.pt (a BertModel state dict) or a SentBERTWrapper / ICTBERTWrapper one (split_state_dict)."""
-        enc = split_state_dict(sd)
-        from transformers import BertModel
-        bm = BertModel(self.config, add_pooling_layer=any(k.startswith('pooler.') for k in enc))
-        bm.load_state_dict(enc)
-        self._enc = AspireBiEnc(bert_model=bm)
+        self.bert_encoder = HipBertEncoder.from_state_dict(self.bert_encoder.config, split_state_dict(sd))
         return self
 
     # ---- the forward ---------------------------------------------------------------------------------------------------
     def forward_device(self, tokid_tt, token_type_ids=None, attention_mask=None):
-        """int64 [B, L] -> last_hidden_state[:, 0] [B, 768] on the GPU, with AspireBiEnc.forward_device's two retry rules (the
-        LayerNorm-exchange status, non-finite output)."""
-        return self._enc.forward_device(tokid_tt, token_type_ids, attention_mask)[0]
+        """int64 [B, L] -> last_hidden_state[:, 0] [B, 768] on the GPU, under the encoder's fall-back rule (encoder.run_checked)."""
+        enc = self.bert_encoder
+        tok, typ, msk = enc.device_inputs(tokid_tt, token_type_ids, attention_mask)
+        return enc.checked(lambda: enc.forward_cls(tok, typ, msk, check_ids=False)[0], lambda out: bool(torch.isfinite(out).all()),
+                           'AspireSentEnc')
 
     @staticmethod
     def sent_reps_bert(bert_batch, model=None):
         """SentBERTWrapper.sent_reps_bert (sentsim_models.py:62-78) on an HF or batcher dict: the CLS rows, ``.squeeze()``d
         ([B, 768]; [768] for one sentence).  The reference's bert_model argument is the encoder; here `model` (an AspireSentEnc)."""
-        tok, typ, msk = _batch_tensors(bert_batch)
+        tok, typ, msk = batch_tensors(bert_batch)
         return model.forward_device(tok, typ, msk).squeeze()
 
     def encode(self, sentences, batch_size=32, show_progress_bar=False, convert_to_numpy=True, max_tokens=16384):

@@ -31,6 +31,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import lib, check
+from .encoder import pack_weights
 
 Tensor = torch.Tensor
 _D = 768
@@ -65,21 +66,10 @@ def _(hidden, tok_idx, span_off, max_sents):
 # b_ffn1, w_ffn2, b_ffn2, ln2_g, ln2_b] (struct aspire_bert_layer, nn.Linear layout)
 @torch.library.custom_op('aspire::bert_encoder_forward', mutates_args=(), device_types='cuda')
 def bert_encoder_forward(ids: Tensor, type_ids: Tensor, mask: Tensor, weights: List[Tensor], n_heads: int, ln_eps: float) -> Tensor:
-    assert (len(weights) - 5) % 12 == 0 and len(weights) >= 5, 'weights: 5 embedding tensors + 12 per layer'
-    n_layers = (len(weights) - 5) // 12
-    w = [t.contiguous() for t in weights]
-    assert all(t.is_cuda and t.dtype == torch.float32 for t in w)
-    layers = (_lib.BertLayer * max(n_layers, 1))()
-    for i in range(n_layers):
-        for f, t in zip(_lib.BertLayer._fields_, w[5 + 12 * i:17 + 12 * i]):
-            setattr(layers[i], f[0], ctypes.c_void_p(t.data_ptr()))
-    hidden_size = w[0].shape[1]
-    ffn = w[5 + 6].shape[0] if n_layers else 4 * hidden_size
-    bw = _lib.BertWeights(*(ctypes.c_void_p(t.data_ptr()) for t in w[:5]), layers, n_layers, n_heads, hidden_size, ffn,
-                          w[0].shape[0], w[1].shape[0], w[2].shape[0], float(ln_eps))
+    bw = pack_weights(weights, n_heads, ln_eps)
     ids = ids.to(torch.int64).contiguous()
     b, l = ids.shape
-    out = torch.empty(b, l, hidden_size, device=ids.device, dtype=torch.float32)
+    out = torch.empty(b, l, bw.hidden, device=ids.device, dtype=torch.float32)
     need = lib.aspire_bert_workspace_bytes(ctypes.byref(bw), b, l)
     ws = torch.empty(max(need, 16), device=ids.device, dtype=torch.uint8)
     check(lib.aspire_bert_forward_f32(ctypes.byref(bw), ops._ptr(ids), ops._ptr(type_ids.to(torch.int64).contiguous()),
@@ -98,22 +88,11 @@ def _(ids, type_ids, mask, weights, n_heads, ln_eps):
 @torch.library.custom_op('aspire::bert_cls_forward', mutates_args=(), device_types='cuda')
 def bert_cls_forward(ids: Tensor, type_ids: Tensor, mask: Tensor, weights: List[Tensor], n_heads: int, ln_eps: float,
                      layer_mix: List[float]) -> Tensor:
-    assert (len(weights) - 5) % 12 == 0 and len(weights) >= 5, 'weights: 5 embedding tensors + 12 per layer'
-    n_layers = (len(weights) - 5) // 12
-    assert len(layer_mix) in (0, n_layers + 1), 'layer_mix: n_layers + 1 weights, or none'
-    w = [t.contiguous() for t in weights]
-    assert all(t.is_cuda and t.dtype == torch.float32 for t in w)
-    layers = (_lib.BertLayer * max(n_layers, 1))()
-    for i in range(n_layers):
-        for f, t in zip(_lib.BertLayer._fields_, w[5 + 12 * i:17 + 12 * i]):
-            setattr(layers[i], f[0], ctypes.c_void_p(t.data_ptr()))
-    hidden_size = w[0].shape[1]
-    ffn = w[5 + 6].shape[0] if n_layers else 4 * hidden_size
-    bw = _lib.BertWeights(*(ctypes.c_void_p(t.data_ptr()) for t in w[:5]), layers, n_layers, n_heads, hidden_size, ffn,
-                          w[0].shape[0], w[1].shape[0], w[2].shape[0], float(ln_eps))
+    bw = pack_weights(weights, n_heads, ln_eps)
+    assert len(layer_mix) in (0, bw.n_layers + 1), 'layer_mix: n_layers + 1 weights, or none'
     ids = ids.to(torch.int64).contiguous()
     b, l = ids.shape
-    out = torch.empty(b, hidden_size, device=ids.device, dtype=torch.float32)
+    out = torch.empty(b, bw.hidden, device=ids.device, dtype=torch.float32)
     mix = ctypes.cast((ctypes.c_float * len(layer_mix))(*layer_mix), ctypes.c_void_p) if layer_mix else None
     need = lib.aspire_bert_cls_workspace_bytes(ctypes.byref(bw), b, l)
     ws = torch.empty(max(need, 16), device=ids.device, dtype=torch.uint8)

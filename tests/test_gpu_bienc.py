@@ -104,6 +104,38 @@ def test_heavy_checkpoint_like_weights():
         assert (got - hs64[-1]).abs().max().item() <= max(1e-4, 1.5 * ref_err), ref_err
 
 
+def _outlier_bert():
+    """tests/test_gpu_encoder.py's model with an activation beyond fp16 (one channel of the embedding LayerNorm scaled by 2e5, its input
+    weights in layer 0 scaled down), with two layers: layer 0 runs on every token row in the CLS forward too."""
+    from transformers import BertConfig, BertModel
+    torch.manual_seed(11)
+    cfg = BertConfig(vocab_size=400, hidden_size=768, num_hidden_layers=2, num_attention_heads=12, intermediate_size=3072,
+                     max_position_embeddings=128)
+    m = BertModel(cfg, add_pooling_layer=False).eval()
+    ch = 5
+    with torch.no_grad():
+        m.embeddings.LayerNorm.weight[ch] = 2e5
+        lyr = m.encoder.layer[0]
+        for lin in (lyr.attention.self.query, lyr.attention.self.key, lyr.attention.self.value, lyr.intermediate.dense):
+            lin.weight[:, ch] *= 1e-5
+    tok = torch.randint(0, 400, (8, 128), generator=torch.Generator().manual_seed(12))      # 1024 token rows: the fp16-plane GEMMs
+    return m, tok, torch.zeros_like(tok), torch.ones_like(tok)
+
+
+def test_activation_beyond_fp16_falls_back_to_the_full_range_kernels():
+    """forward_device on a model whose fp16-plane path overflows (asserted): the 'non-finite' warning, then the full-range kernels'
+    reps, which match HF (tests/test_gpu_encoder.py's bar for this model)."""
+    from aspire_amd.bienc import AspireBiEnc
+    m, tok, seg, mask = _outlier_bert()
+    want = _hidden_states(m, tok, seg, mask)[-1]
+    model = AspireBiEnc(bert_model=m)
+    assert not bool(torch.isfinite(model.bert_encoder.forward_cls(tok, seg, mask)[0]).all())
+    with pytest.warns(UserWarning, match='non-finite'):
+        cls, layers = model.forward_device(tok, seg, mask, want_layers=True)
+    assert torch.isfinite(cls).all() and torch.isfinite(layers).all() and torch.equal(cls, layers[-1])
+    np.testing.assert_allclose(cls.cpu().numpy(), want.numpy(), atol=2e-5 * float(want.abs().max()), rtol=0)
+
+
 def test_readme_dict_and_myspecter_methods():
     from aspire_amd.bienc import AspireBiEnc
     m = _bert(2, seed=41)

@@ -25,8 +25,10 @@ def _spans(lens, n_sents=3):
 def test_a_broken_exchange_times_out_and_the_host_falls_back():
     """Fault injection (GEMM_PROBE=48: the first column tile of every row block never counts itself, so its five partners can never
     see the full count): the launch ENDS (bounded wait), the status word reads ASPIRE_BERT_STATUS_LN_TIMEOUT and is cleared by the
-    read; AspireConSent.forward notices, warns, and returns the reps of the separate-LayerNorm path (equal to HuggingFace)."""
+    read; AspireConSent.forward, AspireBiEnc.forward_device and encode_to_pool notice, warn, and return the reps of the
+    separate-LayerNorm path (equal to HuggingFace)."""
     from aspire_amd._lib import pinned
+    from aspire_amd.bienc import AspireBiEnc
     from aspire_amd.consent import AspireConSent
     from aspire_amd.encoder import HipBertEncoder
     m = _bert(1, seed=31)
@@ -51,13 +53,24 @@ def test_a_broken_exchange_times_out_and_the_host_falls_back():
     model = AspireConSent(bert_model=m)
     bb = {'tokid_tt': tok, 'seg_tt': seg, 'attnmask_tt': mask, 'seq_lens': lens}
     spans = _spans(lens)
+    docs = [(bb, [3] * len(lens), spans)]
+    bi = AspireBiEnc(bert_model=_bert(2, seed=32))                   # (its first layer runs on all 6 656 rows: the CLS-only last does not)
     with pinned(GEMM='planes', GEMM_LN='off'):
         want_cls, want_sent = model.forward(bb, [3] * len(lens), spans)
+        want_bi, want_layers = bi.forward_device(tok, seg, mask, want_layers=True)
+        want_pool, want_pool_cls = model.encode_to_pool(docs, want_cls=True)
     with pinned(GEMM='planes', GEMM_LN='on', GEMM_PROBE='48'):
         with pytest.warns(UserWarning, match='timed out'):
             got_cls, got_sent = model.forward(bb, [3] * len(lens), spans)
+        # the bi-encoder's forward and the store fill run under the same rule
+        with pytest.warns(UserWarning, match='timed out'):
+            got_bi, got_layers = bi.forward_device(tok, seg, mask, want_layers=True)
+        with pytest.warns(UserWarning, match='timed out'):
+            got_pool, got_pool_cls = model.encode_to_pool(docs, want_cls=True)
     assert torch.equal(got_cls, want_cls) and torch.equal(got_sent, want_sent)
-    assert model.bert_encoder.status() == 0
+    assert torch.equal(got_bi, want_bi) and torch.equal(got_layers, want_layers)
+    assert torch.equal(got_pool.repset.rows, want_pool.repset.rows) and torch.equal(got_pool_cls, want_pool_cls)
+    assert model.bert_encoder.status() == 0 and bi.bert_encoder.status() == 0
 
 
 @pytest.mark.timeout(600)

@@ -72,6 +72,21 @@ def test_encode_matches_sentence_transformers(n_layers, tmp_path):
     assert r.shape == (3, 768) and np.abs(r - want[:3]).max() < ENC_TOL
 
 
+def test_forward_device_falls_back_on_an_activation_beyond_fp16():
+    """forward_device on tests/test_gpu_bienc.py's model whose fp16-plane path overflows: the 'non-finite' warning, then the
+    full-range kernels' CLS rows, which match HF."""
+    from test_gpu_bienc import _outlier_bert
+    from aspire_amd.sentenc import AspireSentEnc
+    m, tok, seg, mask = _outlier_bert()
+    with torch.no_grad():
+        want = m(tok, token_type_ids=seg, attention_mask=mask).last_hidden_state
+    model = AspireSentEnc(bert_model=m)
+    with pytest.warns(UserWarning, match='non-finite'):
+        got = model.forward_device(tok, seg, mask).cpu()
+    assert torch.isfinite(got).all()
+    np.testing.assert_allclose(got.numpy(), want[:, 0].numpy(), atol=2e-5 * float(want.abs().max()), rtol=0)
+
+
 def _rows(rng, n, kind):
     if kind == 'normal':
         return rng.standard_normal((n, 768)).astype(np.float32)

@@ -43,7 +43,7 @@ def main():
         tok = torch.randint(1000, 30000, (B, L), generator=g).cuda()
         seg = torch.zeros_like(tok)
         mask = torch.ones_like(tok)
-        cls = lambda: bi._call(tok, seg, mask, False)[0]
+        cls = lambda: enc.forward_cls(tok, seg, mask, bi.layer_mix(), check_ids=False)[0]
         full = lambda: enc.forward_hidden(tok, seg, mask, check_ids=False)[:, 0]
         if a.once:            # one warm-up forward and one measured one of the chosen form: the stats count two forwards
             for _ in range(2):

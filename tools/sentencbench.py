@@ -62,10 +62,10 @@ def encode_part(once=False, n=65536, max_tokens=16384):
 
     def encode_all():
         for (tok, typ, msk), ix in zip(calls, idx):
-            out[ix] = model._enc._call(tok, typ, msk, False)[0]
+            out[ix] = model.bert_encoder.forward_cls(tok, typ, msk, check_ids=False)[0]
     encode_all()
     torch.cuda.synchronize()
-    assert model._enc.bert_encoder.status() == 0 and bool(torch.isfinite(out).all())
+    assert model.bert_encoder.status() == 0 and bool(torch.isfinite(out).all())
     if once:
         encode_all()
         torch.cuda.synchronize()
