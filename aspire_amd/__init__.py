@@ -9,3 +9,4 @@ from .batch_prep import prepare_abstracts, prepare_bert_sentences  # noqa: F401
 from .pair_distances import (AllPairMaskedWasserstein, AllPairMaskedAttention, allpair_masked_dist_l2max,  # noqa: F401
                              allpair_masked_dist_l2topk, rep_len_tup)
 from .consent import AspireConSent  # noqa: F401
+from .contextner import AspireConSenContextual, AspireContextNER, AspireNER  # noqa: F401

@@ -10,7 +10,9 @@ Same contract as the reference's ``prepare_abstracts`` / ``prepare_bert_sentence
   * ids / segment ids / attention mask are right-padded with ``tokenizer.pad_token_id``
 
 Besides the reference's return values, ``spans_to_csr`` flattens the ragged index lists into the
-(tok_idx, span_off) arrays aspire_span_mean_pool_f32 consumes.
+(tok_idx, span_off) arrays aspire_span_mean_pool_f32 consumes, and ``span_range_tables`` turns sentence and entity spans into
+the (document, first token, token count) rows aspire_span_pool_ranges_f32 consumes (the contextual-entity model,
+aspire_amd/contextner.py).
 """
 import re
 
@@ -45,16 +47,20 @@ def _word_pieces(tokenizer, sents, want_text=True):
     return out
 
 
-def prepare_bert_sentences(batch_doc_sents, tokenizer, want_text=True):
+def prepare_bert_sentences(batch_doc_sents, tokenizer, want_text=True, tokenized=None):
     """
     :param batch_doc_sents: list(list(string)); per document: title sentence then abstract sentences.
     :param want_text: False: batch_tokenized_text comes back as ids instead of word-piece strings (prepare_abstracts drops it).
+    :param tokenized: _word_pieces' output for the sentences of all documents in order, where the caller has it already
+        (prepare_abstracts_entities matches the entities against the same tokenisation); None: tokenised here.
     :return: bert_batch dict('tokid_tt', 'seg_tt', 'attnmask_tt', 'seq_lens'),
              batch_tokenized_text list(list(string)),
              batch_sent_token_idxs list(list(list(int))) -- title excluded.
     """
     docs_ids, docs_text, docs_spans = [], [], []
-    tokenized = iter(_word_pieces(tokenizer, [sent for doc_sents in batch_doc_sents for sent in doc_sents], want_text))
+    if tokenized is None:
+        tokenized = _word_pieces(tokenizer, [sent for doc_sents in batch_doc_sents for sent in doc_sents], want_text)
+    tokenized = iter(tokenized)
     for doc_sents in batch_doc_sents:
         ids, text, spans = [], [], []
         used = 0
@@ -114,6 +120,110 @@ def spans_to_csr(batch_senttok_idxs, max_sents):
             off.append(len(flat))
     return (torch.tensor(flat if flat else [0], dtype=torch.int32)[:len(flat)].contiguous(),
             torch.tensor(off, dtype=torch.int32))
+
+
+# ---- the contextual-entity model's inputs (aspire_amd/contextner.py): sentence spans + one span per named entity ----------------
+def find_sublist_range(suplist, sublist):
+    """AspireContextNER.find_sublist_range (src/evaluation/utils/models.py:684-697): the positions of the FIRST occurrence of
+    sublist inside suplist as a list of consecutive ints, None when there is none ([] for an empty sublist of a non-empty suplist)."""
+    n, m = len(suplist), len(sublist)
+    for i in range(n):
+        if i + m <= n and suplist[i:i + m] == sublist:
+            return list(range(i, i + m))
+    return None
+
+
+def _ner_token_idxs(batch_papers, sent_token_idxs, sent_ids, ner_ids):
+    """ner_token_idxs on word-piece ids: sent_ids[d][i] the ids of ABSTRACT sentence i of paper d (at least the kept ones), ner_ids an
+    iterator over the ids of the entities of the kept sentences in paper / sentence / entity order."""
+    out = []
+    for paper, paper_sent_idxs, paper_sent_ids in zip(batch_papers, sent_token_idxs, sent_ids):
+        paper_out = []
+        # (zip: the entities of sentences beyond the kept ones -- dropped by the 500-piece cap -- get NO entry, models.py:668)
+        for ners, tokens, token_idxs in zip(paper['ENTITIES'], paper_sent_ids, paper_sent_idxs):
+            tokens = list(tokens)
+            for _ in ners:
+                ner_range = find_sublist_range(tokens, list(next(ner_ids)))
+                # only an entity wholly inside what the cap kept of its sentence has token positions (models.py:674-679)
+                if ner_range and ner_range[-1] < len(token_idxs):
+                    paper_out.append([token_idxs[i] for i in ner_range])
+                else:
+                    paper_out.append([])
+        out.append(paper_out)
+    return out
+
+
+def _kept_entities(batch_papers, sent_token_idxs):
+    return [ner for paper, idxs in zip(batch_papers, sent_token_idxs)
+            for ners, _, _ in zip(paper['ENTITIES'], paper['ABSTRACT'], idxs) for ner in ners]
+
+
+def ner_token_idxs(batch_papers, sent_token_idxs, tokenizer):
+    """AspireContextNER._get_ner_token_idxs (models.py:649-682): per paper one entry per entity of its kept sentences (ENTITIES[i]
+    are the entity strings of ABSTRACT[i]), in order: the token positions of the entity's first occurrence in its sentence's own
+    tokenisation, or [] when its word pieces are not found there or reach into the part of the sentence the 500-piece cap cut.
+    Pieces are compared as vocabulary ids (a word piece and its id name each other; both sides go through the same tokenizer)."""
+    sents = [list(paper['ABSTRACT'])[:len(idxs)] for paper, idxs in zip(batch_papers, sent_token_idxs)]
+    pieces = iter(_word_pieces(tokenizer, [s for doc in sents for s in doc], want_text=False))
+    sent_ids = [[next(pieces)[1] for _ in doc] for doc in sents]
+    ner_ids = (ids for _, ids in _word_pieces(tokenizer, _kept_entities(batch_papers, sent_token_idxs), want_text=False))
+    return _ner_token_idxs(batch_papers, sent_token_idxs, sent_ids, ner_ids)
+
+
+def prepare_abstracts_entities(batch_abs, tokenizer):
+    """AspireContextNER._preprocess_input (models.py:641-647): prepare_abstracts plus the entities' token positions.  Every
+    sentence is tokenised ONCE (one batched call with a fast tokenizer) for both; the entities in one more call.
+    :param batch_abs: list(dict) with 'TITLE', 'ABSTRACT' (list of sentences) and 'ENTITIES' (per sentence a list of strings).
+    :return: bert_batch, abs_lens, sent_token_idxs, ner_token_idxs"""
+    batch_abs_seqs = [[ex_abs['TITLE'] + ' [SEP] '] + list(ex_abs['ABSTRACT']) for ex_abs in batch_abs]
+    tokenized = _word_pieces(tokenizer, [sent for doc_sents in batch_abs_seqs for sent in doc_sents], want_text=False)
+    bert_batch, _, sent_token_idxs = prepare_bert_sentences(batch_abs_seqs, tokenizer, want_text=False, tokenized=tokenized)
+    abs_lens = [len(x) for x in sent_token_idxs]
+    assert all(n > 0 for n in abs_lens)   # ex_aspire_consent.py:210
+    sent_ids, at = [], 0
+    for doc_sents in batch_abs_seqs:
+        sent_ids.append([ids for _, ids in tokenized[at + 1:at + len(doc_sents)]])      # (the title is no entity sentence)
+        at += len(doc_sents)
+    ner_ids = (ids for _, ids in _word_pieces(tokenizer, _kept_entities(batch_abs, sent_token_idxs), want_text=False))
+    return bert_batch, abs_lens, sent_token_idxs, _ner_token_idxs(batch_abs, sent_token_idxs, sent_ids, ner_ids)
+
+
+def append_entities(batch_papers):
+    """AspireNER._append_entities (models.py:224-233): every paper's entity strings appended to its abstract as further sentences."""
+    return [{'TITLE': paper['TITLE'], 'ABSTRACT': list(paper['ABSTRACT']) + [ner for ners in paper['ENTITIES'] for ner in ners]}
+            for paper in batch_papers]
+
+
+def span_range_tables(sent_token_idxs, ner_token_idxs, row_base=None, pad_sents=None, max_seq_len=None):
+    """The rows aspire_span_pool_ranges_f32 pools, document by document: a document's sentence spans, then its NON-EMPTY entity
+    spans (the reference drops the empty ones at models.py:636).  Every span must be a run of consecutive positions (sentence
+    spans are: SURVEY.md section 8 A0; entity spans are: find_sublist_range), else ValueError; an empty sentence span is a row of
+    length 0 (exact zeros).
+    :param row_base: per document the row of a rows + CSR store where its rows begin -> out_row; None: out_row is None (row r).
+    :param pad_sents: every document's sentence rows filled up to this many with zero-length rows (the padded [B, S, 768] form).
+    :param max_seq_len: positions outside [0, max_seq_len) raise IndexError (as fancy indexing does on the reference path).
+    :return: (doc, tok_start, tok_len, out_row) int32 numpy arrays [R] and n_entities, the valid-entity count per document."""
+    doc, start, length, out_row, n_entities = [], [], [], [], []
+    for d, sents in enumerate(sent_token_idxs):
+        ners = [x for x in (ner_token_idxs[d] if ner_token_idxs is not None else []) if len(x) > 0]
+        spans = [list(x) for x in sents]
+        if pad_sents is not None:
+            spans += [[] for _ in range(pad_sents - len(spans))]
+        spans += [list(x) for x in ners]
+        for k, span in enumerate(spans):
+            n = len(span)
+            if n and span != list(range(span[0], span[0] + n)):
+                raise ValueError(f'document {d}: span {span} is not a run of consecutive token positions')
+            if n and max_seq_len is not None and (span[0] < 0 or span[-1] >= max_seq_len):
+                raise IndexError('span token index out of range')
+            doc.append(d)
+            start.append(span[0] if n else 0)
+            length.append(n)
+            if row_base is not None:
+                out_row.append(int(row_base[d]) + k)
+        n_entities.append(len(ners))
+    as_i32 = lambda x: np.asarray(x, dtype=np.int32)
+    return (as_i32(doc), as_i32(start), as_i32(length), as_i32(out_row) if row_base is not None else None), n_entities
 
 
 # ---- the SPECTER-CoCite bi-encoder's inputs (aspire_amd/bienc.py): one whole-abstract sequence per document --------------------

@@ -50,6 +50,65 @@ __global__ void __launch_bounds__(192) span_mean_pool_kernel(const float* __rest
     *reinterpret_cast<float4*>(sent_reps + (size_t)orow * kD + d) = acc;
 }
 
+// Ragged span pooling (aspire_span_pool_ranges_f32): every output row is a RANGE of token rows of one document, so the grid is over
+// the rows that exist and no token-index list is read.  One 192-thread workgroup per output row, thread t owns the float4 at d = 4t
+// (span_mean_pool_kernel's access pattern: a token row is one coalesced 3 KB read), but 16 token rows in flight per thread instead
+// of 4: the kernel's time is the LONGEST span's chain of dependent load rounds (a row's sum keeps the token order, so a span is
+// not split over workgroups), and every entity span (1 - 6 tokens) and most sentence spans are a single round.  (One wave per row
+// with three float4s per lane, four rows per workgroup, was measured first: 38 us where span_mean_pool_kernel takes 28 us on the
+// same spans -- a wave holds a quarter of the loads in flight per token row)  The sum runs in ascending
+// token order and is divided by max(tok_len, 1): the same bits as span_mean_pool_kernel on the same span.
+// Workgroups beyond the R row blocks copy the CLS rows, one document each.
+constexpr int kRangeDepth = 16;
+
+__global__ void __launch_bounds__(192) span_pool_ranges_kernel(const float* __restrict__ hidden, int64_t B, int64_t L,
+                                                               const int32_t* __restrict__ row_doc,
+                                                               const int32_t* __restrict__ row_start,
+                                                               const int32_t* __restrict__ row_len, int64_t R,
+                                                               const int32_t* __restrict__ out_row, float* __restrict__ rows,
+                                                               float* __restrict__ cls_reps) {
+    const int d = threadIdx.x * 4;
+    const int64_t r = blockIdx.x;
+    if (r >= R) {
+        const int64_t b = r - R;
+        if (cls_reps == nullptr || b >= B) return;
+        *reinterpret_cast<float4*>(cls_reps + (size_t)b * kD + d) =
+            *reinterpret_cast<const float4*>(hidden + (size_t)b * L * kD + d);
+        return;
+    }
+    const int64_t orow = out_row != nullptr ? (int64_t)out_row[r] : r;
+    const int n = row_len[r];
+    const float* src = hidden + ((size_t)row_doc[r] * L + (size_t)row_start[r]) * kD + d;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    int t = 0;
+    for (; t + kRangeDepth <= n; t += kRangeDepth) {
+        float4 v[kRangeDepth];
+#pragma unroll
+        for (int u = 0; u < kRangeDepth; ++u) v[u] = ld4_stream(src + (size_t)(t + u) * kD);
+#pragma unroll
+        for (int u = 0; u < kRangeDepth; ++u) {
+            acc.x += v[u].x; acc.y += v[u].y; acc.z += v[u].z; acc.w += v[u].w;
+        }
+    }
+    for (; t + 4 <= n; t += 4) {
+        float4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = ld4_stream(src + (size_t)(t + u) * kD);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            acc.x += v[u].x; acc.y += v[u].y; acc.z += v[u].z; acc.w += v[u].w;
+        }
+    }
+    for (; t < n; ++t) {
+        const float4 v = ld4_stream(src + (size_t)t * kD);
+        acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+    }
+    // an empty span stays exactly zero (span_mean_pool_kernel's empty-slot rule)
+    const float cnt = (float)max(n, 1);
+    acc.x /= cnt; acc.y /= cnt; acc.z /= cnt; acc.w /= cnt;
+    *reinterpret_cast<float4*>(rows + (size_t)orow * kD + d) = acc;
+}
+
 // caching_score's document-level term: ||q_cls - c_cls + eps||_2 (torch.nn.functional.pairwise_distance), one wave per
 // pair, 12 coordinates per lane.
 __global__ void __launch_bounds__(256) cls_l2_kernel(const float* __restrict__ q_cls, int64_t Q, const float* __restrict__ c_cls,
@@ -118,6 +177,26 @@ extern "C" int aspire_span_mean_pool_rows_f32(const float* hidden, int64_t B, in
     if (B == 0) return ASPIRE_OK;
     hipLaunchKernelGGL(span_mean_pool_kernel, dim3((unsigned)(B * S)), dim3(192), 0, (hipStream_t)stream, hidden, L,
                        tok_idx, span_off, S, rows, cls_reps, out_row);
+    ASPIRE_LAUNCH_OK();
+    return ASPIRE_OK;
+}
+
+extern "C" int aspire_span_pool_ranges_f32(const float* hidden, int64_t B, int64_t L, int64_t D, const int32_t* row_doc,
+                                           const int32_t* row_start, const int32_t* row_len, int64_t R, const int32_t* out_row,
+                                           float* rows, float* cls_reps, void* stream) {
+    ASPIRE_REQUIRE(D == kD, ASPIRE_ERR_UNSUPPORTED, "encoding dim %lld unsupported (kernels are built for 768)",
+                   (long long)D);
+    ASPIRE_REQUIRE(B >= 0 && L > 0 && R >= 0, ASPIRE_ERR_INVALID_ARG, "bad shape B=%lld L=%lld R=%lld", (long long)B,
+                   (long long)L, (long long)R);
+    ASPIRE_REQUIRE(hidden || B == 0, ASPIRE_ERR_INVALID_ARG, "null pointer");
+    ASPIRE_REQUIRE(R == 0 || (row_doc && row_start && row_len && rows), ASPIRE_ERR_INVALID_ARG, "null pointer");
+    ASPIRE_REQUIRE(R == 0 || B > 0, ASPIRE_ERR_INVALID_ARG, "%lld rows of a batch without documents", (long long)R);
+    const int64_t row_blocks = R;
+    const int64_t cls_blocks = cls_reps != nullptr ? B : 0;
+    if (row_blocks + cls_blocks == 0) return ASPIRE_OK;
+    ASPIRE_REQUIRE(row_blocks + cls_blocks <= 0x7fffffffLL, ASPIRE_ERR_UNSUPPORTED, "%lld rows in one call", (long long)R);
+    hipLaunchKernelGGL(span_pool_ranges_kernel, dim3((unsigned)(row_blocks + cls_blocks)), dim3(192), 0, (hipStream_t)stream,
+                       hidden, B, L, row_doc, row_start, row_len, R, out_row, rows, cls_reps);
     ASPIRE_LAUNCH_OK();
     return ASPIRE_OK;
 }

@@ -282,6 +282,28 @@ def span_mean_pool_rows(hidden, tok_idx, span_off, max_sents, out_row, rows, cls
     _rows_written(rows)
 
 
+def span_pool_ranges(hidden, row_doc, row_start, row_len, rows=None, out_row=None, cls=None):
+    """Ragged span pooling (include/aspire_hip.h: aspire_span_pool_ranges_f32; models.py:437-477): row r = the mean of
+    hidden[row_doc[r], row_start[r] : row_start[r] + row_len[r]] (int32 [R] GPU tensors; the caller has checked their ranges),
+    written to rows[out_row[r]] (rows[r] without out_row).  rows None: a new [R, 768] matrix.  cls [B, 768] optional, filled with
+    hidden[:, 0].  Returns rows."""
+    _f32(hidden, 'hidden')
+    b, l, d = hidden.shape
+    r = int(row_doc.numel())
+    assert row_start.numel() == r and row_len.numel() == r and (out_row is None or out_row.numel() == r)
+    if rows is None:
+        assert out_row is None, 'out_row needs the row matrix it indexes'
+        rows = torch.empty(r, d, device=hidden.device, dtype=torch.float32)
+    _f32(rows, 'rows')
+    if cls is not None:
+        assert _f32(cls, 'cls').shape == (b, d)
+    check(lib.aspire_span_pool_ranges_f32(_ptr(hidden), b, l, d, _ptr(_i32(row_doc, 'row_doc')), _ptr(_i32(row_start, 'row_start')),
+                                          _ptr(_i32(row_len, 'row_len')), r, _ptr(_i32(out_row, 'out_row') if out_row is not None else None),
+                                          _ptr(rows), _ptr(cls), _stream()))
+    _rows_written(rows)
+    return rows
+
+
 def cls_l2(q_cls, c_cls, pairing=_lib.PAIR_PAIRED, eps=1e-6):
     """functional.pairwise_distance(q_cls, c_cls, p=2.0) (disent_models.py:306): ||q - c + eps||_2, [P] on the GPU."""
     _f32(q_cls, 'q_cls')

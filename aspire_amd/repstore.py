@@ -17,6 +17,8 @@ class RepStore:
     def __init__(self, pid2reps=None):
         # pid -> np.ndarray [S, 768] float32
         self.pid2reps = dict(pid2reps or {})
+        # pid -> (n_sents, entity rows per sentence) for 'sentence-entity' reps (contextner.AspireContextNER.encode_to_store); optional
+        self.pid2layout = {}
 
     # ---- loaders --------------------------------------------------------------------------------
     @classmethod
@@ -50,8 +52,14 @@ class RepStore:
         np.savez(path, pids=np.array(pids), offsets=off, rows=rows)
 
     # ---- access ---------------------------------------------------------------------------------
-    def add(self, pid, sent_reps):
+    def add(self, pid, sent_reps, layout=None):
+        """layout (optional; 'sentence-entity' reps: rows = the sentences, then entity rows): (n_sents, per sentence the number of
+        entity rows the facet filter counts for it -- None where the reference's filter raises IndexError on the paper)."""
         self.pid2reps[pid] = np.asarray(sent_reps, dtype=np.float32)
+        if layout is not None:
+            self.pid2layout[pid] = layout
+        else:
+            self.pid2layout.pop(pid, None)
 
     def __contains__(self, pid):
         return pid in self.pid2reps
@@ -64,12 +72,23 @@ class RepStore:
 
     def faceted(self, pid, facet, pred_labels):
         """Rows of `pid` whose sentence label is `<facet>_label`; 'objective_label' counts as background
-        (pp_gen_nearest.py:173-181).  facet 'all' / None returns every row."""
+        (pp_gen_nearest.py:173-181).  facet 'all' / None returns every row.
+        A paper added with a row layout ('sentence-entity' reps) also keeps the entity rows of those sentences, numbered the way
+        SimilarityModel.get_faceted_encoding numbers them (models.py:127-163: from len(pred_labels) on, in sentence order)."""
         reps = self.pid2reps[pid]
         if facet in (None, 'all'):
             return reps
         labs = ['background_label' if lab == 'objective_label' else lab for lab in pred_labels]
         idxs = [i for i, lab in enumerate(labs) if lab == f'{facet}_label']
+        layout = self.__dict__.get('pid2layout', {}).get(pid)
+        if layout is not None:
+            if layout[1] is None:
+                raise IndexError(f'paper {pid!r}: the reference\'s entity filter runs out of entities on it (models.py:722)')
+            sent_ids, row = set(idxs), len(labs)
+            for i, n_ents in enumerate(layout[1]):
+                if i in sent_ids:
+                    idxs += list(range(row, row + n_ents))
+                row += n_ents
         return reps[idxs, :]
 
     def to_device(self, pids=None, planes=False, chunk_rows=1 << 18):

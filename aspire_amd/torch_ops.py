@@ -6,6 +6,7 @@ implementation ONLY -- calling one with CPU tensors fails in the dispatcher, the
 implementation so that shapes propagate under FakeTensor / torch.compile tracing.
 
     torch.ops.aspire.span_mean_pool(hidden, tok_idx, span_off, max_sents) -> (cls, sent)         A2/A3  ex_aspire_consent.py:75-100
+    torch.ops.aspire.span_pool_ranges(hidden, row_doc, row_start, row_len) -> (cls, rows [R, 768])  A2r  models.py:437-477
     torch.ops.aspire.bert_encoder_forward(ids, type_ids, mask, weights, n_heads, ln_eps) -> hidden  A1   ex_aspire_consent.py:72-73
     torch.ops.aspire.bert_cls_forward(ids, type_ids, mask, weights, n_heads, ln_eps, layer_mix) -> cls [B, 768]
                                                                                    A1b  ex_aspire_bienc.py:23-58
@@ -60,6 +61,21 @@ def span_mean_pool(hidden: Tensor, tok_idx: Tensor, span_off: Tensor, max_sents:
 def _(hidden, tok_idx, span_off, max_sents):
     b, _, d = hidden.shape
     return hidden.new_empty(b, d), hidden.new_empty(b, max_sents, d)
+
+
+# ragged span pooling (aspire_span_pool_ranges_f32): row r = mean of hidden[row_doc[r], row_start[r] : row_start[r] + row_len[r]]
+@torch.library.custom_op('aspire::span_pool_ranges', mutates_args=(), device_types='cuda')
+def span_pool_ranges(hidden: Tensor, row_doc: Tensor, row_start: Tensor, row_len: Tensor) -> Tuple[Tensor, Tensor]:
+    hidden = hidden.contiguous()
+    cls = torch.empty(hidden.shape[0], hidden.shape[2], device=hidden.device, dtype=torch.float32)
+    rows = ops.span_pool_ranges(hidden, row_doc, row_start, row_len, cls=cls)
+    return cls, rows
+
+
+@span_pool_ranges.register_fake
+def _(hidden, row_doc, row_start, row_len):
+    b, _, d = hidden.shape
+    return hidden.new_empty(b, d), hidden.new_empty(row_doc.shape[0], d)
 
 
 # weights: [word_emb, pos_emb, type_emb, emb_ln_g, emb_ln_b] + per layer [w_qkv, b_qkv, w_o, b_o, ln1_g, ln1_b, w_ffn1,
@@ -236,5 +252,5 @@ def _(q_rows, q_start, q_len, q_max, c_rows, c_start, c_len, c_max, job_off, max
     return (q_rows.new_empty(c_start.shape[0]), q_rows.new_empty(j, k), q_rows.new_empty(j, k, dtype=torch.int64))
 
 
-OPS = ('span_mean_pool', 'bert_encoder_forward', 'bert_cls_forward', 'l2max_scores', 'ot_sinkhorn_scores', 'topk_desc', 'topk_keys', 'topk_merge',
+OPS = ('span_mean_pool', 'span_pool_ranges', 'bert_encoder_forward', 'bert_cls_forward', 'l2max_scores', 'ot_sinkhorn_scores', 'topk_desc', 'topk_keys', 'topk_merge',
        'l2max_scores_csr', 'ot_scores_csr', 'ot_rank_batch')

@@ -65,6 +65,24 @@ int aspire_span_mean_pool_f32(const float* hidden, int64_t B, int64_t L, int64_t
 int aspire_span_mean_pool_rows_f32(const float* hidden, int64_t B, int64_t L, int64_t D,
                                    const int32_t* tok_idx, const int32_t* span_off, int64_t S,
                                    const int32_t* out_row, float* rows, float* cls_reps, void* stream);
+/* Ragged span pooling: R output rows, each the mean of a RANGE of token rows of one document.  Replaces
+ * AspireConSenContextual._get_sent_reps / _get_ner_reps, src/evaluation/utils/models.py:437-477 (one [B, L, 768] mask pass per
+ * sentence slot, then one fancy-indexed mean per entity): sentence spans and entity spans (find_sublist_range, models.py:684-697)
+ * are runs of consecutive positions, so a row is (document, first token, token count) and no token-index list is read.  The grid
+ * is over the R rows that exist: no per-batch slot maximum, no padding rows.  Spans may overlap freely (an entity always overlaps
+ * its sentence).
+ *   hidden    [B, L, D]  final hidden states
+ *   row_doc, row_start, row_len   device int32 [R]: row r = sum, in ascending token order, of
+ *             hidden[row_doc[r], row_start[r] .. row_start[r] + row_len[r]) / max(row_len[r], 1); row_len 0 yields exact zeros.
+ *             The caller guarantees 0 <= row_doc < B and 0 <= row_start, row_start + row_len <= L (checked where the tables are
+ *             built, on the host).
+ *   out_row   device int32 [R] or NULL: row r is written to rows[out_row[r]] (a rows + CSR rep store); NULL = rows[r]
+ *   rows      [>= max out_row + 1, D]  out
+ *   cls_reps  [B, D]     out (may be NULL): hidden[b, 0, :]; written also when R == 0
+ * On the same span the result has the bits of aspire_span_mean_pool_f32 (same order of the sum, same division). */
+int aspire_span_pool_ranges_f32(const float* hidden, int64_t B, int64_t L, int64_t D,
+                                const int32_t* row_doc, const int32_t* row_start, const int32_t* row_len, int64_t R,
+                                const int32_t* out_row, float* rows, float* cls_reps, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * A1  BERT-base encoder forward.  Replaces `self.bert_encoder(tokid_tt, token_type_ids=seg_tt,
