@@ -23,7 +23,7 @@
 #include <math.h>
 
 #include "common.h"
-#include "topk_device.h"
+#include "batch_host.h"
 
 namespace aspire {
 int generic_max_rows(void);
@@ -339,22 +339,14 @@ extern "C" int aspire_dotmax_rank_batch_f32(const aspire_repset* q, const aspire
                                             size_t workspace_bytes, void* stream) {
     if (int rc = check_dot_sets(q, c, D, ASPIRE_PAIR_CROSS, sim)) return rc;
     const int64_t J = q->n, C = c->n;
-    ASPIRE_REQUIRE(q->ext == 0 && c->ext == 0, ASPIRE_ERR_INVALID_ARG, "batched jobs take CSR rep sets (ext == 0)");
-    ASPIRE_REQUIRE(k >= 0 && (k == 0 || (top_scores && top_idx) || keys), ASPIRE_ERR_INVALID_ARG,
-                   "k > 0 needs (top_scores, top_idx) or keys");
-    if (J == 0) return ASPIRE_OK;
-    ASPIRE_REQUIRE(job_off && max_job >= 0 && max_job <= C, ASPIRE_ERR_INVALID_ARG, "need job_off and 0 <= max_job <= C");
-    ASPIRE_REQUIRE(J < ((int64_t)1 << 30) && C < ((int64_t)1 << 31) - 8, ASPIRE_ERR_UNSUPPORTED, "batch too large for 32-bit offsets");
-    if (C == 0) {
-        const float* unread = reinterpret_cast<const float*>(job_off);     // every segment is empty: never dereferenced
-        if (k > 0) return topk_run(unread, J, 0, k, 0, top_scores, top_idx, keys, nullptr, 0, stream, job_off, job_base);
-        return ASPIRE_OK;
-    }
-    ASPIRE_REQUIRE(scores, ASPIRE_ERR_INVALID_ARG, "null scores");
+    BatchRank rank{J, max_job, k, top_scores, top_idx, keys, job_off, job_base, stream};
+    bool go_on;
+    if (int rc = batch_preamble(q, c, scores, rank, go_on); !go_on) return rc;
     const size_t need = aspire_dotmax_rank_batch_workspace_bytes(q, c, max_job, k);
     ASPIRE_REQUIRE(workspace_bytes >= need && (need == 0 || workspace), ASPIRE_ERR_INVALID_ARG,
                    "workspace too small: %zu bytes given, aspire_dotmax_rank_batch_workspace_bytes says %zu", workspace_bytes, need);
     ASPIRE_REQUIRE(((uintptr_t)workspace & 15) == 0, ASPIRE_ERR_INVALID_ARG, "workspace must be 16-byte aligned");
+    rank.scratch_at(workspace);
     DotArgs a{};
     a.q = to_dot(q);
     a.c = to_dot(c);
@@ -364,8 +356,5 @@ extern "C" int aspire_dotmax_rank_batch_f32(const aspire_repset* q, const aspire
     a.job_off = job_off;
     a.J = (int32_t)J;
     if (int rc = launch_pairs(a, C, (hipStream_t)stream)) return rc;
-    if (k > 0)
-        return topk_run(scores, J, max_job, k, 0, keys ? nullptr : top_scores, keys ? nullptr : top_idx, keys,
-                        need ? workspace : nullptr, need, stream, job_off, job_base);
-    return ASPIRE_OK;
+    return rank.rank(scores);
 }

@@ -141,8 +141,6 @@ bool tuning_get(const char* key, char* buf, size_t len) {
     return render_tuning(g_tuning, key, buf, len);
 }
 
-namespace {
-}
 void set_error(const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);

@@ -14,6 +14,15 @@
 //   * the Sinkhorn solve of one (query, candidate) pair runs in ONE wave with lane (li,lj) = (l>>3,l&7)
 //     holding the T x T entries (8a+li, 8b+lj): row log-sum-exps are DPP reductions over lane bits 0-2,
 //     column ones over bits 3-5 (permlane swaps); potentials stay in registers for all ~70 eps-steps.
+//
+// Host side (the last third of the file, top to bottom): argument checks and ScoreArgs fills (check_repsets, fill_set_args,
+// fill_ot_args); the max-sim entry points; the two stage launchers (launch_cost_stage, launch_sinkhorn_stage); the preparation
+// kernels of the batched / CHUNK / REC forms with their host helpers -- form rules (chunk_size_ok, one_wave_form_ok), workspace
+// layouts (batch_layout, l2_batch_layout, batch_tables), launches (launch_batch_tables, launch_chunk_prep, launch_rec_prep,
+// arm_long_pair_gate, launch_fused_form); otAspire per call (ot_run_tiles, ot_run); the batched entry points (ot_rank_batch,
+// aspire_l2max_rank_batch_f32).  Which kernel family scores a pair decides the pair's bits, so every rule that picks one is
+// written once and asked by every entry point; the batched entry points share their argument checks and their rank with
+// dotmax.hip through batch_host.h (batch_preamble, BatchRank).
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -25,6 +34,7 @@
 #include "score_types.h"
 #include "score_device.h"
 #include "topk_device.h"
+#include "batch_host.h"
 
 namespace aspire {
 namespace {
@@ -2165,6 +2175,15 @@ int check_repsets(const aspire_repset* q, const aspire_repset* c, int64_t D, int
 }
 
 RepSet to_dev(const aspire_repset* s) { return RepSet{s->rows, s->start, s->len, s->n, s->ext}; }
+// the rep sets of a call and what travels with them (a field added here reaches every entry point)
+void fill_set_args(ScoreArgs& a, const aspire_repset* q, const aspire_repset* c, int pairing) {
+    a.q = to_dev(q);
+    a.c = to_dev(c);
+    a.q_planes = q->planes;
+    a.c_planes = c->planes;
+    a.c_box = c->doc_box;
+    a.pairing = pairing;
+}
 
 int max_rows_of(const aspire_repset* q, const aspire_repset* c) {
     const int mq = q->ext > 0 ? q->ext : q->max_len;
@@ -2230,12 +2249,7 @@ extern "C" int aspire_l2agg_scores_f32(const aspire_repset* q, const aspire_reps
     cdist_mode &= ~(ASPIRE_CDIST_ONE_FORM | ASPIRE_CDIST_CENTER);
     ASPIRE_REQUIRE(!one_form || agg == ASPIRE_AGG_MAX, ASPIRE_ERR_UNSUPPORTED, "ASPIRE_CDIST_ONE_FORM is built for the max-sim score only");
     ScoreArgs a{};
-    a.q = to_dev(q);
-    a.c = to_dev(c);
-    a.q_planes = q->planes;
-    a.c_planes = c->planes;
-    a.c_box = c->doc_box;
-    a.pairing = pairing;
+    fill_set_args(a, q, c, pairing);
     a.cdist_mode = cdist_mode;
     a.agg = agg;
     a.temp = temp;
@@ -2327,6 +2341,12 @@ struct RankReq {
     float* top_scores;
     int64_t* top_idx;
     uint64_t* keys;
+    // the rank of Q x C scores; its scratch sits `scratch_off` bytes into the call's workspace
+    int rank(const float* scores, int64_t Q, int64_t C, void* workspace, size_t scratch_off, void* stream) const {
+        if (k <= 0) return ASPIRE_OK;
+        const size_t need = aspire_topk_workspace_bytes(Q, C, k);
+        return topk_run(scores, Q, C, k, idx_base, top_scores, top_idx, keys, need ? (char*)workspace + scratch_off : nullptr, need, stream);
+    }
 };
 
 int check_ot_params(const aspire_ot_params* prm, int want) {
@@ -2340,12 +2360,7 @@ int check_ot_params(const aspire_ot_params* prm, int want) {
 
 void fill_ot_args(ScoreArgs& a, const aspire_repset* q, const aspire_repset* c, int pairing, const aspire_ot_params* prm,
                   const float* diameter, int64_t diam_group, int want, float* scores) {
-    a.q = to_dev(q);
-    a.c = to_dev(c);
-    a.q_planes = q->planes;
-    a.c_planes = c->planes;
-    a.c_box = c->doc_box;
-    a.pairing = pairing;
+    fill_set_args(a, q, c, pairing);
     a.cdist_mode = prm->cdist_mode;
     a.blur = prm->blur;
     a.scaling = prm->scaling;
@@ -2495,238 +2510,20 @@ int launch_sinkhorn_stage(const ScoreArgs& a, const PairWs<T>& ws, int64_t n_slo
     return ASPIRE_OK;
 }
 
-int ot_run_tiles(const aspire_repset* q, const aspire_repset* c, int64_t D, int pairing, const aspire_ot_params* prm,
-                 const float* diameter, int64_t diam_group, int want, float* scores, float* out_qdistr, float* out_cdistr,
-                 float* out_pairsims, float* out_plan, void* workspace, size_t workspace_bytes, void* stream, const RankReq& rank,
-                 bool cost_only);
-}  // namespace
-namespace aspire {
-namespace {
-// (defined with the batched entry points below)
-__global__ void chunk_prep_kernel(RepSet q, RepSet c, const int32_t* __restrict__ job_off, float* __restrict__ qbox, int32_t* __restrict__ cand_job,
-                                  int32_t* __restrict__ counter, int32_t* __restrict__ grp_rec, int region_cap);
-// CHUNK items without a counter (ScoreArgs::chunk_regions): slices = J * parts <= 64; a slice's region holds min(384, max_job) records
-inline int chunk_regions_of(int64_t J, int64_t max_job);
-inline int chunk_region_cap_of(int64_t max_job) { return (int)(max_job < 384 ? (max_job > 0 ? max_job : 1) : 384); }
-int64_t chunk_parts(int64_t max_job);
-int64_t chunk_items_bound(int64_t J, int64_t C, int64_t max_job);
-// smallest pool / batch (candidates) that takes the CHUNK / REC forms (below: the small-batch kernels; tools/csfbench.py sweeps)
-constexpr int64_t kChunkMinCands = 256;
-// pairs of short documents per single-pool call that take pair_one_kernel (tools/experiments/singlejob.py sweeps)
-constexpr int64_t kOneMinPairs = 1, kOneMaxPairs = 8192;        // (ONE form for every small grid: a pair scored alone, in a subset or in a shard gets the same bits)
-}  // namespace
-}  // namespace aspire
-namespace {
-
-// Documents beyond the tile kernels' 32 rows: padded tensors that wide go through the one-workgroup-per-pair kernel
-// (generic.hip) for every pair; CSR pools run the tile kernels with their documents' bound clamped to 32 rows (every pair
-// of short documents is scored there, a pair that holds a longer one gets NaN) and the long-document kernel then rewrites
-// exactly those pairs.  The rank follows.
-int ot_run(const aspire_repset* q, const aspire_repset* c, int64_t D, int pairing, const aspire_ot_params* prm,
-           const float* diameter, int64_t diam_group, int want, float* scores, float* out_qdistr, float* out_cdistr,
-           float* out_pairsims, float* out_plan, void* workspace, size_t workspace_bytes, void* stream, const RankReq& rank,
-           bool cost_only = false) {
-    if (int rc = check_repsets(q, c, D, pairing)) return rc;
-    const int tile_max = 8 * kMaxT;
-    // ONE_FORM (include/aspire_hip.h): every pair through the long-form kernel, whatever the size of the call
-    const bool one_form = prm && (prm->flags & ASPIRE_OT_FLAG_ONE_FORM) && !cost_only;
-    if (q->n == 0 || c->n == 0 || (max_rows_of(q, c) <= tile_max && !one_form))
-        return ot_run_tiles(q, c, D, pairing, prm, diameter, diam_group, want, scores, out_qdistr, out_cdistr, out_pairsims, out_plan,
-                            workspace, workspace_bytes, stream, rank, cost_only);
-    if (int rc = check_ot_params(prm, want)) return rc;
-    ASPIRE_REQUIRE(scores, ASPIRE_ERR_INVALID_ARG, "null scores");
-    ASPIRE_REQUIRE(!diameter || diam_group > 0, ASPIRE_ERR_INVALID_ARG, "diam_group must be positive");
-    const bool extra = out_qdistr || out_cdistr || out_pairsims || out_plan;
-    ASPIRE_REQUIRE(!extra || (q->ext > 0 && c->ext > 0), ASPIRE_ERR_INVALID_ARG, "pair outputs need padded extents (ext > 0)");
-    const int rows_q = q->ext > 0 ? q->ext : q->max_len, rows_c = c->ext > 0 ? c->ext : c->max_len;
-    ScoreArgs a{};
-    fill_ot_args(a, q, c, pairing, prm, diameter, diam_group, want, scores);
-    a.out_qdistr = out_qdistr;
-    a.out_cdistr = out_cdistr;
-    a.out_pairsims = out_pairsims;
-    a.out_plan = out_plan;
-    int skip = 0;
-    if (q->ext == 0 && c->ext == 0 && !one_form) {
-        aspire_repset q32 = *q, c32 = *c;
-        q32.max_len = q->max_len < tile_max ? q->max_len : tile_max;
-        c32.max_len = c->max_len < tile_max ? c->max_len : tile_max;
-        if (int rc = ot_run_tiles(&q32, &c32, D, pairing, prm, diameter, diam_group, want, scores, nullptr, nullptr, nullptr, nullptr,
-                                  workspace, workspace_bytes, stream, RankReq{0, 0, nullptr, nullptr, nullptr}, cost_only))
-            return rc;
-        skip = tile_max;
-    }
-    if (cost_only) return ASPIRE_OK;
-    if (int rc = launch_pair_generic(a, 0, skip, rows_q, rows_c, (hipStream_t)stream)) return rc;
-    if (rank.k > 0) {
-        const size_t need = aspire_topk_workspace_bytes(q->n, c->n, rank.k);
-        void* tws = need ? (char*)workspace + workspace_bytes : nullptr;
-        return topk_run(scores, q->n, c->n, rank.k, rank.idx_base, rank.top_scores, rank.top_idx, rank.keys, tws, need, stream);
-    }
-    return ASPIRE_OK;
-}
-
-int ot_run_tiles(const aspire_repset* q, const aspire_repset* c, int64_t D, int pairing, const aspire_ot_params* prm,
-                 const float* diameter, int64_t diam_group, int want, float* scores, float* out_qdistr, float* out_cdistr,
-                 float* out_pairsims, float* out_plan, void* workspace, size_t workspace_bytes, void* stream, const RankReq& rank,
-                 bool cost_only) {
-    if (int rc = check_repsets(q, c, D, pairing)) return rc;
-    if (q->n == 0 || c->n == 0) return ASPIRE_OK;   // nothing to score (an empty pool has no buffers either)
-    if (int rc = check_ot_params(prm, want)) return rc;
-    ASPIRE_REQUIRE(scores, ASPIRE_ERR_INVALID_ARG, "null scores");
-    const bool extra = out_qdistr || out_cdistr || out_pairsims || out_plan;
-    ASPIRE_REQUIRE(!extra || (q->ext > 0 && c->ext > 0), ASPIRE_ERR_INVALID_ARG,
-                   "pair outputs need padded extents (ext > 0)");
-    ASPIRE_REQUIRE(!diameter || diam_group > 0, ASPIRE_ERR_INVALID_ARG, "diam_group must be positive");
-    const int max_rows = max_rows_of(q, c);
-    const size_t per_cand = per_cand_bytes(q, c, pairing);
-    // ONE query against a big pool of 9 .. 16-row documents: the streaming kernel (tile16.hip) beats the 32-column Gram tiles,
-    // whose 12 .. 16 real query rows fill a third to a half of the MFMA tile (1 x 20 000 x 12 otAspire: 247 vs 363 us; at two
-    // queries they tie, from three the Gram tiles win: 623 vs 565 us)
-    // both sides on fp16 planes, the pool's boxes cached: the plane tiles whatever the number of queries (gram.hip)
-    const bool planes_ot = !extra && gram_planes_wanted_ot(q, c, pairing, diameter != nullptr) && tuning().ot_form == 0;
-    const bool stream16 = !planes_ot && q->n == 1 && c->n >= 4096 && tile16_path_ok(q, c, pairing) && tuning().cost_path != 1 &&
-                          tuning().ot_form != 1;
-    const int form_t = tuning().ot_form;
-    // ONE short query (facet-selected rows) against a pool of abstracts of up to 32 rows: the fused kernel's CHUNK form, as in
-    // ot_rank_batch (1 x 20 000 x (3..20): 674 us on the Gram tiles + block Sinkhorn before) -- the item records and their counter
-    // take the (unused) front of the pair-slot workspace.
-    const bool chunk1 = pairing == ASPIRE_PAIR_CROSS && q->n == 1 && q->ext == 0 && c->ext == 0 && q->max_len <= 8 && c->max_len > 8 &&
-                        c->max_len <= 8 * kMaxT && c->n >= kChunkMinCands && c->n < ((int64_t)1 << 30) && !extra && !cost_only && !diameter &&
-                        (form_t == 0 || form_t == 4) && prm->scaling >= 0.25 && !tuning().fused_nosolve && !tuning().fused_valu &&
-                        tuning().cost_path == 0 && workspace &&
-                        (size_t)(chunk_items_bound(1, c->n, c->n) + 2) * 64 + 256 + qbox_bytes(q) + 64 <= workspace_bytes;
-    const bool gram = (gram_path_wanted(q, c, pairing) || planes_ot) && !stream16 && !chunk1;
-    ASPIRE_REQUIRE(workspace && workspace_bytes >= per_cand + qbox_bytes(q) + kWsSlack, ASPIRE_ERR_INVALID_ARG,
-                   "workspace too small: %zu bytes given, at least %zu needed (aspire_ot_workspace_bytes suggests %zu)",
-                   workspace_bytes, per_cand, aspire_ot_workspace_bytes(q, c, pairing));
-    ScoreArgs a{};
-    fill_ot_args(a, q, c, pairing, prm, diameter, diam_group, want, scores);
-    a.out_qdistr = out_qdistr;
-    a.out_cdistr = out_cdistr;
-    a.out_pairsims = out_pairsims;
-    a.out_plan = out_plan;
-    // the matrix-pipe cost tiles derive -cdist and geomloss's cost from ONE distance: they store -cdist only and the solve stage takes
-    // cost = max(cdist, 1e-4) from it -- half the tile bytes written and read (the debug cost stage keeps both buffers)
-    a.cost_from_neg = gram && !cost_only;
-    const int qchunks = query_chunks(a);
-    const int64_t cand_per_chunk = (int64_t)((((workspace_bytes - qbox_bytes(q)) & ~(size_t)15) - 32) / per_cand);
-    const int64_t pairs_per_cand = pairing == ASPIRE_PAIR_PAIRED ? 1 : q->n;
-    const size_t ot_bytes = workspace_bytes;
-    // query boxes sit at a fixed place (the tail of the workspace) so that every candidate chunk finds them
-    float* qbox = (float*)((char*)workspace + ((workspace_bytes - qbox_bytes(q)) & ~(size_t)15));
-    // Few queries against a big pool of short documents: costs and solves in ONE launch, no workspace slots, no candidate
-    // chunks (fused.hip).
-    const int64_t groups4_all = (c->n + 3) / 4 * q->n;
-    const bool fused = pairing == ASPIRE_PAIR_CROSS && !extra && !gram && !cost_only && fused_path_ok(q, c) &&
-                       (form_t == 3 || (form_t == 0 && groups4_all >= (q->n == 1 ? kStreamMinGroups1 : 2048)));
-    if (fused) {
-        a.cand0 = 0;
-        a.cand1 = c->n;
-        const bool inbox = fused_inbox_ok(q, diameter);      // ONE query: the kernel forms its box itself
-        if (!diameter && !inbox) {   // per-coordinate boxes of the queries (the kernel adds each candidate's rows)
-            hipLaunchKernelGGL(doc_box_kernel, dim3((unsigned)q->n), dim3(192), 0, (hipStream_t)stream, a.q, qbox);
-            ASPIRE_LAUNCH_OK();
-        }
-#ifdef ASPIRE_EXPERIMENT_SPLIT      // round 5's role-split kernel: an experiment that lost, built only by tools/experiments/split/build.sh
-        if (inbox && split_path_ok(groups4_all, prm) && c->n < ((int64_t)1 << 31) - 8) {
-            if (int rc = launch_pair_split(a, (hipStream_t)stream)) return rc;
-        } else
-#endif
-        if (int rc = launch_pair_fused(a, groups4_all, inbox ? nullptr : qbox, (hipStream_t)stream)) return rc;
-    }
-    if (chunk1) {
-        a.cand0 = 0;
-        a.cand1 = c->n;
-        int32_t* counter = (int32_t*)workspace;
-        int32_t* recs = (int32_t*)((char*)workspace + 256);
-        a.grp_off = counter;
-        a.grp_rec = recs;
-        a.chunk_regions = chunk_regions_of(1, c->n);
-        a.chunk_region_cap = chunk_region_cap_of(c->n);
-        if (a.chunk_regions == 0) ASPIRE_HIP_OK(hipMemsetAsync(counter, 0, sizeof(int32_t), (hipStream_t)stream));
-        hipLaunchKernelGGL(chunk_prep_kernel, dim3(1, (unsigned)chunk_parts(c->n) + 1), dim3(192), 0, (hipStream_t)stream, a.q, a.c,
-                           (const int32_t*)nullptr, qbox, (int32_t*)nullptr, counter, recs, a.chunk_regions > 0 ? a.chunk_region_cap : 0);
-        ASPIRE_LAUNCH_OK();
-        if (int rc = launch_pair_fused_chunk(a, chunk_items_bound(1, c->n, c->n), qbox, (hipStream_t)stream)) return rc;
-    }
-    const int rc_run = (fused || chunk1) ? (int)ASPIRE_OK : dispatch_T(max_rows, [&](auto tc) -> int {
-        constexpr int T = decltype(tc)::value;
-        for (int64_t c0 = 0; c0 < c->n; c0 += cand_per_chunk) {
-            a.cand0 = c0;
-            a.cand1 = c0 + cand_per_chunk < c->n ? c0 + cand_per_chunk : c->n;
-            const int64_t n_slots = (a.cand1 - a.cand0) * pairs_per_cand;
-            PairWs<T> ws;
-            ws.cost = (float*)workspace;
-            ws.neg = ws.cost + n_slots * PairWs<T>::kEntries;
-            ws.diam2 = ws.neg + n_slots * PairWs<T>::kEntries;
-            float* cbox = (float*)(((uintptr_t)(ws.diam2 + n_slots) + 15) & ~(uintptr_t)15);
-            if constexpr (T == 1) {
-                // a small pool of short documents (the per-query call of evaluate.py:58-76): one wave per pair, costs and solve in ONE
-                // launch (pair_one_kernel) instead of the cost launch + the Sinkhorn launch and the workspace between them
-                const int64_t groups4 = (a.cand1 - a.cand0 + 3) / 4 * (pairing == ASPIRE_PAIR_CROSS ? q->n : 1);
-                const bool small_grid = !(pairing == ASPIRE_PAIR_CROSS && groups4 >= 2048);        // (beyond: the tiled cost kernel's grid)
-                if (q->ext == 0 && c->ext == 0 && !gram && !cost_only && small_grid && n_slots >= kOneMinPairs && n_slots <= kOneMaxPairs &&
-                    (form_t == 5 || (form_t == 0 && tuning().sinkhorn_form == 0 && tuning().cost_path == 0 && tuning().cost1_blocks == 0))) {
-                    hipLaunchKernelGGL(pair_one_kernel, dim3((unsigned)((n_slots + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a, n_slots);
-                    ASPIRE_LAUNCH_OK();
-                    continue;
-                }
-            }
-            if (int rc = launch_cost_stage<T>(a, q, c, ws, n_slots, qchunks, gram, qbox, cbox, c0 == 0, (hipStream_t)stream)) return rc;
-            if (cost_only) continue;
-            if (int rc = launch_sinkhorn_stage<T>(a, ws, n_slots, max_rows, extra, 0, (hipStream_t)stream)) return rc;
-        }
-        return (int)ASPIRE_OK;
-    });
-    if (rc_run) return rc_run;
-    if (rank.k > 0) {
-        // the rank kernels follow the scores on the same stream (their scratch sits behind the OT workspace proper,
-        // which aspire_ot_workspace_bytes keeps a multiple of 16 bytes)
-        const size_t need = aspire_topk_workspace_bytes(q->n, c->n, rank.k);
-        void* tws = need ? (char*)workspace + ot_bytes : nullptr;
-        return topk_run(scores, q->n, c->n, rank.k, rank.idx_base, rank.top_scores, rank.top_idx, rank.keys, tws, need, stream);
-    }
-    return ASPIRE_OK;
+// the pair slots of `n_slots` pairs at `base` (cost tiles, -cdist tiles, squared diameters)
+template <int T>
+PairWs<T> pair_ws_at(void* base, int64_t n_slots) {
+    PairWs<T> ws;
+    ws.cost = (float*)base;
+    ws.neg = ws.cost + n_slots * PairWs<T>::kEntries;
+    ws.diam2 = ws.neg + n_slots * PairWs<T>::kEntries;
+    return ws;
 }
 }  // namespace
-
-extern "C" int aspire_ot_sinkhorn_f32(const aspire_repset* q, const aspire_repset* c, int64_t D, int pairing,
-                                      const aspire_ot_params* prm, const float* diameter, int64_t diam_group, int want,
-                                      float* scores, float* out_qdistr, float* out_cdistr, float* out_pairsims,
-                                      float* out_plan, void* workspace, size_t workspace_bytes, void* stream) {
-    return ot_run(q, c, D, pairing, prm, diameter, diam_group, want, scores, out_qdistr, out_cdistr, out_pairsims, out_plan,
-                  workspace, workspace_bytes, stream, RankReq{0, 0, nullptr, nullptr, nullptr});
-}
-
-// Diagnostics: the cost stage of aspire_ot_sinkhorn_f32 alone (bench.py times the HBM-bound kernel of a pass this way).
-extern "C" int aspire_debug_ot_cost_stage_f32(const aspire_repset* q, const aspire_repset* c, int64_t D, int pairing,
-                                              const aspire_ot_params* prm, float* scores, void* workspace,
-                                              size_t workspace_bytes, void* stream) {
-    return ot_run(q, c, D, pairing, prm, nullptr, 0, ASPIRE_OT_DISTANCE, scores, nullptr, nullptr, nullptr, nullptr, workspace,
-                  workspace_bytes, stream, RankReq{0, 0, nullptr, nullptr, nullptr}, true);
-}
-
-extern "C" size_t aspire_ot_rank_workspace_bytes(const aspire_repset* q, const aspire_repset* c, int64_t k) {
-    if (!q || !c || q->n <= 0 || c->n <= 0) return 0;
-    return aspire_ot_workspace_bytes(q, c, ASPIRE_PAIR_CROSS) + aspire_topk_workspace_bytes(q->n, c->n, k);
-}
-
-extern "C" int aspire_ot_rank_f32(const aspire_repset* q, const aspire_repset* c, int64_t D, const aspire_ot_params* prm,
-                                  const float* diameter, int64_t diam_group, int want, float* scores, int64_t k,
-                                  int64_t idx_base, float* top_scores, int64_t* top_idx, uint64_t* keys, void* workspace,
-                                  size_t workspace_bytes, void* stream) {
-    ASPIRE_REQUIRE(k > 0, ASPIRE_ERR_INVALID_ARG, "k must be positive");
-    ASPIRE_REQUIRE((top_scores && top_idx) || keys, ASPIRE_ERR_INVALID_ARG, "need (top_scores, top_idx) or keys");
-    ASPIRE_REQUIRE(q && c, ASPIRE_ERR_INVALID_ARG, "null repset");
-    const size_t tneed = aspire_topk_workspace_bytes(q->n, c->n, k);
-    ASPIRE_REQUIRE(workspace_bytes >= tneed, ASPIRE_ERR_INVALID_ARG, "workspace too small for the rank scratch");
-    // the OT part is what is left, rounded down to 16 bytes so that the 64-bit rank scratch behind it stays aligned
-    return ot_run(q, c, D, ASPIRE_PAIR_CROSS, prm, diameter, diam_group, want, scores, nullptr, nullptr, nullptr, nullptr, workspace,
-                  (workspace_bytes - tneed) & ~(size_t)15, stream, RankReq{k, idx_base, top_scores, top_idx, keys});
-}
 
 // ---------------------------------------------------------------------------------------------
-// Batched jobs: J independent (query, pool) re-ranks in one call
+// Preparation kernels: the tables of batched jobs (J independent (query, pool) re-ranks in one call) and the items of the
+// CHUNK / REC forms, which the single-pool calls take too
 // ---------------------------------------------------------------------------------------------
 namespace aspire {
 namespace {
@@ -2967,18 +2764,47 @@ __global__ void __launch_bounds__(192) chunk16_prep_kernel(RepSet q, RepSet c, c
         }
     }
 }
+
+// ---- host side of the preparation kernels: sizes, form rules, workspace layouts, launches ---------------------------------
 // parts (classification blocks) per job, and the bound on the items the launch can make
 int64_t chunk_parts(int64_t max_job) { return max_job > 0 ? (max_job + kChunkPrepPart - 1) / kChunkPrepPart : 1; }
-inline int chunk_regions_of(int64_t J, int64_t max_job) {
+// CHUNK items without a counter (ScoreArgs::chunk_regions): slices = J * parts <= 64; a slice's region holds min(384, max_job) records
+int chunk_regions_of(int64_t J, int64_t max_job) {
     const int64_t n = J * chunk_parts(max_job);
     return n <= 64 ? (int)n : 0;
 }
+int chunk_region_cap_of(int64_t max_job) { return (int)(max_job < 384 ? (max_job > 0 ? max_job : 1) : 384); }
 int64_t chunk_items_bound(int64_t J, int64_t C, int64_t max_job) {
     const int64_t by_count = C + 3 * J * chunk_parts(max_job);
     const int64_t by_region = (int64_t)chunk_regions_of(J, max_job) * chunk_region_cap_of(max_job);      // (regions mode: every slice its own region)
     return by_count > by_region ? by_count : by_region;
 }
 
+// smallest pool / batch (candidates) that takes the CHUNK / REC forms (below: the small-batch kernels; tools/csfbench.py sweeps)
+constexpr int64_t kChunkMinCands = 256;
+// the size rule of the CHUNK / REC forms: pinned (OT_FORM 4), or by default from kChunkMinCands candidates in the call
+bool chunk_size_ok(int64_t C) {
+    const int form_t = tuning().ot_form;
+    return form_t == 4 || (form_t == 0 && C >= kChunkMinCands);
+}
+// pairs of short documents per call that take pair_one_kernel (tools/experiments/singlejob.py sweeps)
+constexpr int64_t kOneMinPairs = 1, kOneMaxPairs = 8192;        // (ONE form for every small grid: a pair scored alone, in a subset or in a shard gets the same bits)
+// May a call of `pairs` pairs of documents of <= 8 rows take the one-launch form (pair_one_kernel: one wave per pair, costs and
+// solve)?  The single-pool and the batched entry points ask the same question, so that a pair gets the same kernel -- the same
+// bits -- whether it is scored in a call of its own or in a batch.
+//   plain_call: CSR sets, no Gram tiles, every stage of the call wanted.  Single-pool: ext == 0 on both sides && !gram &&
+//               !cost_only; batched: the full stage mask (batched sets are CSR and never take the Gram tiles).
+//   small_grid: the call stays below the throughput kernels.  The two callers' rules differ and stay their own: single-pool calls
+//               go by groups of four (CROSS pairing from 2048 groups: the tiled cost kernel's grid), batches by !a.tile_form
+//               (from kStreamMinGroupsBatch groups the fused kernel, which also carries the OT_FORM pins 2 and 3).
+bool one_wave_form_ok(int64_t pairs, bool plain_call, bool small_grid) {
+    const int form_t = tuning().ot_form;
+    return plain_call && small_grid && pairs >= kOneMinPairs && pairs <= kOneMaxPairs &&
+           (form_t == 5 || (form_t == 0 && tuning().sinkhorn_form == 0 && tuning().cost_path == 0 && tuning().cost1_blocks == 0));
+}
+
+// Workspace of a batched call (byte offsets): otAspire's pair slots, then the tables the preparation kernels write, the hybrid
+// forms' gate word and the rank scratch.
 struct BatchLayout {
     size_t slots, qbox, cand_job, grp_job, grp_off, grp_rec, gate, topk, total;
 };
@@ -2999,9 +2825,283 @@ BatchLayout batch_layout(int64_t J, int64_t C, int max_rows, int64_t max_job, in
     L.total = o;
     return L;
 }
+// tsAspire over batched jobs: no pair slots (max-sim is one launch), its own order
+BatchLayout l2_batch_layout(int64_t J, int64_t C, int64_t max_job, int64_t k) {
+    BatchLayout L{};
+    size_t o = 0;
+    L.cand_job = o; o = align16(o + (size_t)C * sizeof(int32_t));
+    L.grp_job = o; o = align16(o + (size_t)(C / 4 + J + 1) * sizeof(int32_t));
+    L.grp_off = o; o = align16(o + (size_t)(J + 1 > 64 ? J + 1 : 64) * sizeof(int32_t));
+    L.grp_rec = o; o = align16(o + (2 * (size_t)chunk_items_bound(J, C, max_job) + 1) * 16 * sizeof(int32_t));     // (room for the CHUNK / REC forms' items)
+    L.qbox = o; o = align16(o + (size_t)J * 2 * kD * sizeof(float));      // (written by the tables kernel, unused by max-sim)
+    L.gate = o; o = align16(o + 16);
+    L.topk = o; o = align16(o + aspire_topk_workspace_bytes(J, max_job, k));
+    L.total = o;
+    return L;
+}
+// the layout's pieces as pointers into a call's workspace
+struct BatchTables {
+    float* slots;
+    float* qbox;
+    int32_t *cand_job, *grp_job, *grp_off, *grp_rec, *gate;
+    void* topk;
+};
+BatchTables batch_tables(void* workspace, const BatchLayout& L) {
+    char* w = (char*)workspace;
+    return BatchTables{(float*)(w + L.slots), (float*)(w + L.qbox), (int32_t*)(w + L.cand_job), (int32_t*)(w + L.grp_job),
+                       (int32_t*)(w + L.grp_off), (int32_t*)(w + L.grp_rec), (int32_t*)(w + L.gate), w + L.topk};
+}
+// MAPPED pairing (ScoreArgs::qmap): J jobs over C candidates in one launch, on the tables `t`
+void fill_mapped_args(ScoreArgs& a, const BatchTables& t, const int32_t* job_off, int64_t J, int64_t C, int64_t max_job) {
+    a.cand0 = 0;
+    a.cand1 = C;
+    a.qmap = t.cand_job;
+    a.job_off = job_off;
+    a.grp_off = t.grp_off;
+    a.grp_job = t.grp_job;
+    a.grp_rec = t.grp_rec;
+    a.job0 = 0;
+    a.job1 = (int32_t)J;
+    a.max_job_groups = (int32_t)((max_job + 3) / 4);
+}
+
+// The tables of a batch on the groups-of-four kernels: batch_prep_kernel fills t.qbox, t.cand_job, t.grp_off, t.grp_job, t.grp_rec.
+int launch_batch_tables(const ScoreArgs& a, const BatchTables& t, const int32_t* job_off, int64_t J, int64_t max_job, hipStream_t s) {
+    // parts per job: enough blocks that a job's groups take a couple of trips each
+    const int64_t work = ((max_job + 3) / 4) * 16;
+    int64_t parts = (work + 2 * 192 - 1) / (2 * 192);
+    parts = parts < 1 ? 1 : parts > 64 ? 64 : parts;
+    while (parts > 1 && J * parts > 4096) parts /= 2;
+    hipLaunchKernelGGL(batch_prep_kernel, dim3((unsigned)J, (unsigned)parts + 1), dim3(192), 0, s, a.q, a.c, job_off, (int)J, t.qbox, t.cand_job,
+                       t.grp_off, t.grp_job, t.grp_rec);
+    ASPIRE_LAUNCH_OK();
+    return ASPIRE_OK;
+}
+// The items of the CHUNK form (chunk_prep_kernel): records into t.grp_rec, their count(s) into t.grp_off, the queries' boxes into
+// t.qbox; sets a.chunk_regions / a.chunk_region_cap for the scoring launch.  The single-pool caller passes job_off = nullptr, J = 1,
+// max_job = the pool (t.cand_job may be null then).
+int launch_chunk_prep(ScoreArgs& a, const BatchTables& t, const int32_t* job_off, int64_t J, int64_t max_job, hipStream_t s) {
+    a.chunk_regions = chunk_regions_of(J, max_job);
+    a.chunk_region_cap = chunk_region_cap_of(max_job);
+    if (a.chunk_regions == 0) ASPIRE_HIP_OK(hipMemsetAsync(t.grp_off, 0, sizeof(int32_t), s));
+    hipLaunchKernelGGL(chunk_prep_kernel, dim3((unsigned)J, (unsigned)chunk_parts(max_job) + 1), dim3(192), 0, s, a.q, a.c, job_off, t.qbox,
+                       t.cand_job, t.grp_off, t.grp_rec, a.chunk_regions > 0 ? a.chunk_region_cap : 0);
+    ASPIRE_LAUNCH_OK();
+    return ASPIRE_OK;
+}
+// The items of the REC form (chunk16_prep_kernel), counted in t.grp_off[0].
+int launch_rec_prep(const ScoreArgs& a, const BatchTables& t, const int32_t* job_off, int64_t J, int64_t max_job, hipStream_t s) {
+    ASPIRE_HIP_OK(hipMemsetAsync(t.grp_off, 0, sizeof(int32_t), s));
+    hipLaunchKernelGGL(chunk16_prep_kernel, dim3((unsigned)J, (unsigned)chunk_parts(max_job) + 1), dim3(192), 0, s, a.q, a.c, job_off, t.qbox,
+                       t.cand_job, t.grp_off, t.grp_rec);
+    ASPIRE_LAUNCH_OK();
+    return ASPIRE_OK;
+}
+// The hybrid forms' gate (ScoreArgs::gate): a census of the long pairs on the device, and the limit the queued kernels compare it to --
+// up to ~4 % long pairs (measured crossover at 20 x 1000: 5 %): fused kernel + the 16-row kernels on the long pairs only.
+int arm_long_pair_gate(ScoreArgs& a, int32_t* gate, int64_t C, hipStream_t s) {
+    ASPIRE_HIP_OK(hipMemsetAsync(gate, 0, sizeof(int32_t), s));
+    hipLaunchKernelGGL(long_pair_census_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, a, gate);
+    ASPIRE_LAUNCH_OK();
+    a.gate = gate;
+    a.gate_limit = (int32_t)(C / 24);
+    return ASPIRE_OK;
+}
+// The fused launch of a call of short documents.  own_box: the kernel forms the query boxes itself (single-pool: ONE query;
+// batched: the SELF form) and takes no qbox.  whole_call: every stage is wanted (always, but for the batched debug stage masks).
+int launch_fused_form(const ScoreArgs& a, int64_t groups, bool own_box, bool whole_call, const float* qbox, const aspire_ot_params* prm,
+                      hipStream_t s) {
+#ifdef ASPIRE_EXPERIMENT_SPLIT      // round 5's role-split kernel: an experiment that lost, built only by tools/experiments/split/build.sh
+    if (own_box && whole_call && split_path_ok(groups, prm) && a.c.n < ((int64_t)1 << 31) - 8) return launch_pair_split(a, s);
+#endif
+    return launch_pair_fused(a, groups, own_box ? nullptr : qbox, s);
+}
 }  // namespace
 }  // namespace aspire
 
+// ---------------------------------------------------------------------------------------------
+// otAspire, one call = queries x one pool (CROSS) or pair by pair (PAIRED)
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+// The tile-kernel forms (documents of up to 32 rows) of a call that ot_run has checked and described in `a`: non-empty sets, sound
+// parameters, a.scores set.  q / c carry the row bound the kernels are to use (ot_run clamps max_len for pools with longer
+// documents).  Scores only: the rank is ot_run's.
+int ot_run_tiles(ScoreArgs a, const aspire_repset* q, const aspire_repset* c, const aspire_ot_params* prm, void* workspace,
+                 size_t workspace_bytes, hipStream_t stream, bool cost_only) {
+    const int pairing = a.pairing;
+    const float* diameter = a.diameter;
+    const bool extra = a.out_qdistr || a.out_cdistr || a.out_pairsims || a.out_plan;
+    const int max_rows = max_rows_of(q, c);
+    const size_t per_cand = per_cand_bytes(q, c, pairing);
+    // ONE query against a big pool of 9 .. 16-row documents: the streaming kernel (tile16.hip) beats the 32-column Gram tiles,
+    // whose 12 .. 16 real query rows fill a third to a half of the MFMA tile (1 x 20 000 x 12 otAspire: 247 vs 363 us; at two
+    // queries they tie, from three the Gram tiles win: 623 vs 565 us)
+    // both sides on fp16 planes, the pool's boxes cached: the plane tiles whatever the number of queries (gram.hip)
+    const bool planes_ot = !extra && gram_planes_wanted_ot(q, c, pairing, diameter != nullptr) && tuning().ot_form == 0;
+    const bool stream16 = !planes_ot && q->n == 1 && c->n >= 4096 && tile16_path_ok(q, c, pairing) && tuning().cost_path != 1 &&
+                          tuning().ot_form != 1;
+    const int form_t = tuning().ot_form;
+    // ONE short query (facet-selected rows) against a pool of abstracts of up to 32 rows: the fused kernel's CHUNK form, as in
+    // ot_rank_batch (1 x 20 000 x (3..20): 674 us on the Gram tiles + block Sinkhorn before) -- the item records and their counter
+    // take the (unused) front of the pair-slot workspace.  (From kChunkMinCands candidates even where the form is pinned: the
+    // call's workspace is sized for the pair slots.)
+    const bool chunk1 = pairing == ASPIRE_PAIR_CROSS && q->n == 1 && q->ext == 0 && c->ext == 0 && q->max_len <= 8 && c->max_len > 8 &&
+                        c->max_len <= 8 * kMaxT && c->n >= kChunkMinCands && c->n < ((int64_t)1 << 30) && !extra && !cost_only && !diameter &&
+                        chunk_size_ok(c->n) && prm->scaling >= 0.25 && !tuning().fused_nosolve && !tuning().fused_valu &&
+                        tuning().cost_path == 0 && workspace &&
+                        (size_t)(chunk_items_bound(1, c->n, c->n) + 2) * 64 + 256 + qbox_bytes(q) + 64 <= workspace_bytes;
+    const bool gram = (gram_path_wanted(q, c, pairing) || planes_ot) && !stream16 && !chunk1;
+    ASPIRE_REQUIRE(workspace && workspace_bytes >= per_cand + qbox_bytes(q) + kWsSlack, ASPIRE_ERR_INVALID_ARG,
+                   "workspace too small: %zu bytes given, at least %zu needed (aspire_ot_workspace_bytes suggests %zu)",
+                   workspace_bytes, per_cand, aspire_ot_workspace_bytes(q, c, pairing));
+    // the matrix-pipe cost tiles derive -cdist and geomloss's cost from ONE distance: they store -cdist only and the solve stage takes
+    // cost = max(cdist, 1e-4) from it -- half the tile bytes written and read (the debug cost stage keeps both buffers)
+    a.cost_from_neg = gram && !cost_only;
+    const int qchunks = query_chunks(a);
+    const int64_t cand_per_chunk = (int64_t)((((workspace_bytes - qbox_bytes(q)) & ~(size_t)15) - 32) / per_cand);
+    const int64_t pairs_per_cand = pairing == ASPIRE_PAIR_PAIRED ? 1 : q->n;
+    // query boxes sit at a fixed place (the tail of the workspace) so that every candidate chunk finds them
+    float* qbox = (float*)((char*)workspace + ((workspace_bytes - qbox_bytes(q)) & ~(size_t)15));
+    // Few queries against a big pool of short documents: costs and solves in ONE launch, no workspace slots, no candidate
+    // chunks (fused.hip).
+    const int64_t groups4_all = (c->n + 3) / 4 * q->n;
+    const bool fused = pairing == ASPIRE_PAIR_CROSS && !extra && !gram && !cost_only && fused_path_ok(q, c) &&
+                       (form_t == 3 || (form_t == 0 && groups4_all >= (q->n == 1 ? kStreamMinGroups1 : 2048)));
+    if (fused) {
+        a.cand0 = 0;
+        a.cand1 = c->n;
+        const bool inbox = fused_inbox_ok(q, diameter);      // ONE query: the kernel forms its box itself
+        if (!diameter && !inbox) {   // per-coordinate boxes of the queries (the kernel adds each candidate's rows)
+            hipLaunchKernelGGL(doc_box_kernel, dim3((unsigned)q->n), dim3(192), 0, stream, a.q, qbox);
+            ASPIRE_LAUNCH_OK();
+        }
+        return launch_fused_form(a, groups4_all, inbox, true, qbox, prm, stream);
+    }
+    if (chunk1) {
+        a.cand0 = 0;
+        a.cand1 = c->n;
+        // counter and records at the front of the workspace; no candidate -> job table (ONE query)
+        const BatchTables t{nullptr, qbox, nullptr, nullptr, (int32_t*)workspace, (int32_t*)((char*)workspace + 256), nullptr, nullptr};
+        a.grp_off = t.grp_off;
+        a.grp_rec = t.grp_rec;
+        if (int rc = launch_chunk_prep(a, t, nullptr, 1, c->n, stream)) return rc;
+        return launch_pair_fused_chunk(a, chunk_items_bound(1, c->n, c->n), qbox, stream);
+    }
+    return dispatch_T(max_rows, [&](auto tc) -> int {
+        constexpr int T = decltype(tc)::value;
+        for (int64_t c0 = 0; c0 < c->n; c0 += cand_per_chunk) {
+            a.cand0 = c0;
+            a.cand1 = c0 + cand_per_chunk < c->n ? c0 + cand_per_chunk : c->n;
+            const int64_t n_slots = (a.cand1 - a.cand0) * pairs_per_cand;
+            const PairWs<T> ws = pair_ws_at<T>(workspace, n_slots);
+            float* cbox = (float*)(((uintptr_t)(ws.diam2 + n_slots) + 15) & ~(uintptr_t)15);
+            if constexpr (T == 1) {
+                // a small pool of short documents (the per-query call of evaluate.py:58-76): one wave per pair, costs and solve in ONE
+                // launch (pair_one_kernel) instead of the cost launch + the Sinkhorn launch and the workspace between them
+                const int64_t groups4 = (a.cand1 - a.cand0 + 3) / 4 * (pairing == ASPIRE_PAIR_CROSS ? q->n : 1);
+                const bool small_grid = !(pairing == ASPIRE_PAIR_CROSS && groups4 >= 2048);        // (beyond: the tiled cost kernel's grid)
+                if (one_wave_form_ok(n_slots, q->ext == 0 && c->ext == 0 && !gram && !cost_only, small_grid)) {
+                    hipLaunchKernelGGL(pair_one_kernel, dim3((unsigned)((n_slots + 3) / 4)), dim3(256), 0, stream, a, n_slots);
+                    ASPIRE_LAUNCH_OK();
+                    continue;
+                }
+            }
+            if (int rc = launch_cost_stage<T>(a, q, c, ws, n_slots, qchunks, gram, qbox, cbox, c0 == 0, stream)) return rc;
+            if (cost_only) continue;
+            if (int rc = launch_sinkhorn_stage<T>(a, ws, n_slots, max_rows, extra, 0, stream)) return rc;
+        }
+        return (int)ASPIRE_OK;
+    });
+}
+
+// One otAspire call: the argument checks, the form by document length, the rank.
+// Documents beyond the tile kernels' 32 rows: padded tensors that wide go through the one-workgroup-per-pair kernel
+// (generic.hip) for every pair; CSR pools run the tile kernels with their documents' bound clamped to 32 rows (every pair
+// of short documents is scored there, a pair that holds a longer one gets NaN) and the long-document kernel then rewrites
+// exactly those pairs.  The rank follows.
+int ot_run(const aspire_repset* q, const aspire_repset* c, int64_t D, int pairing, const aspire_ot_params* prm,
+           const float* diameter, int64_t diam_group, int want, float* scores, float* out_qdistr, float* out_cdistr,
+           float* out_pairsims, float* out_plan, void* workspace, size_t workspace_bytes, void* stream, const RankReq& rank,
+           bool cost_only = false) {
+    if (int rc = check_repsets(q, c, D, pairing)) return rc;
+    if (q->n == 0 || c->n == 0) return ASPIRE_OK;   // nothing to score (an empty pool has no buffers either)
+    if (int rc = check_ot_params(prm, want)) return rc;
+    ASPIRE_REQUIRE(scores, ASPIRE_ERR_INVALID_ARG, "null scores");
+    const bool extra = out_qdistr || out_cdistr || out_pairsims || out_plan;
+    ASPIRE_REQUIRE(!extra || (q->ext > 0 && c->ext > 0), ASPIRE_ERR_INVALID_ARG, "pair outputs need padded extents (ext > 0)");
+    ASPIRE_REQUIRE(!diameter || diam_group > 0, ASPIRE_ERR_INVALID_ARG, "diam_group must be positive");
+    ScoreArgs a{};
+    fill_ot_args(a, q, c, pairing, prm, diameter, diam_group, want, scores);
+    a.out_qdistr = out_qdistr;
+    a.out_cdistr = out_cdistr;
+    a.out_pairsims = out_pairsims;
+    a.out_plan = out_plan;
+    hipStream_t s = (hipStream_t)stream;
+    const int tile_max = 8 * kMaxT;
+    // ONE_FORM (include/aspire_hip.h): every pair through the long-form kernel, whatever the size of the call
+    const bool one_form = (prm->flags & ASPIRE_OT_FLAG_ONE_FORM) && !cost_only;
+    if (max_rows_of(q, c) <= tile_max && !one_form) {
+        if (int rc = ot_run_tiles(a, q, c, prm, workspace, workspace_bytes, s, cost_only)) return rc;
+    } else {
+        int skip = 0;
+        if (q->ext == 0 && c->ext == 0 && !one_form) {      // (CSR: no pair outputs, `a` serves the tile kernels as it is)
+            aspire_repset q32 = *q, c32 = *c;
+            q32.max_len = q->max_len < tile_max ? q->max_len : tile_max;
+            c32.max_len = c->max_len < tile_max ? c->max_len : tile_max;
+            if (int rc = ot_run_tiles(a, &q32, &c32, prm, workspace, workspace_bytes, s, cost_only)) return rc;
+            skip = tile_max;
+        }
+        if (cost_only) return ASPIRE_OK;
+        const int rows_q = q->ext > 0 ? q->ext : q->max_len, rows_c = c->ext > 0 ? c->ext : c->max_len;
+        if (int rc = launch_pair_generic(a, 0, skip, rows_q, rows_c, s)) return rc;
+    }
+    // the rank kernels follow the scores on the same stream (their scratch sits behind the OT workspace proper,
+    // which aspire_ot_workspace_bytes keeps a multiple of 16 bytes)
+    return rank.rank(scores, q->n, c->n, workspace, workspace_bytes, stream);
+}
+}  // namespace
+
+extern "C" int aspire_ot_sinkhorn_f32(const aspire_repset* q, const aspire_repset* c, int64_t D, int pairing,
+                                      const aspire_ot_params* prm, const float* diameter, int64_t diam_group, int want,
+                                      float* scores, float* out_qdistr, float* out_cdistr, float* out_pairsims,
+                                      float* out_plan, void* workspace, size_t workspace_bytes, void* stream) {
+    return ot_run(q, c, D, pairing, prm, diameter, diam_group, want, scores, out_qdistr, out_cdistr, out_pairsims, out_plan,
+                  workspace, workspace_bytes, stream, RankReq{0, 0, nullptr, nullptr, nullptr});
+}
+
+// Diagnostics: the cost stage of aspire_ot_sinkhorn_f32 alone (bench.py times the HBM-bound kernel of a pass this way).
+extern "C" int aspire_debug_ot_cost_stage_f32(const aspire_repset* q, const aspire_repset* c, int64_t D, int pairing,
+                                              const aspire_ot_params* prm, float* scores, void* workspace,
+                                              size_t workspace_bytes, void* stream) {
+    return ot_run(q, c, D, pairing, prm, nullptr, 0, ASPIRE_OT_DISTANCE, scores, nullptr, nullptr, nullptr, nullptr, workspace,
+                  workspace_bytes, stream, RankReq{0, 0, nullptr, nullptr, nullptr}, true);
+}
+
+extern "C" size_t aspire_ot_rank_workspace_bytes(const aspire_repset* q, const aspire_repset* c, int64_t k) {
+    if (!q || !c || q->n <= 0 || c->n <= 0) return 0;
+    return aspire_ot_workspace_bytes(q, c, ASPIRE_PAIR_CROSS) + aspire_topk_workspace_bytes(q->n, c->n, k);
+}
+
+extern "C" int aspire_ot_rank_f32(const aspire_repset* q, const aspire_repset* c, int64_t D, const aspire_ot_params* prm,
+                                  const float* diameter, int64_t diam_group, int want, float* scores, int64_t k,
+                                  int64_t idx_base, float* top_scores, int64_t* top_idx, uint64_t* keys, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+    ASPIRE_REQUIRE(k > 0, ASPIRE_ERR_INVALID_ARG, "k must be positive");
+    ASPIRE_REQUIRE((top_scores && top_idx) || keys, ASPIRE_ERR_INVALID_ARG, "need (top_scores, top_idx) or keys");
+    ASPIRE_REQUIRE(q && c, ASPIRE_ERR_INVALID_ARG, "null repset");
+    const size_t tneed = aspire_topk_workspace_bytes(q->n, c->n, k);
+    ASPIRE_REQUIRE(workspace_bytes >= tneed, ASPIRE_ERR_INVALID_ARG, "workspace too small for the rank scratch");
+    // the OT part is what is left, rounded down to 16 bytes so that the 64-bit rank scratch behind it stays aligned
+    return ot_run(q, c, D, ASPIRE_PAIR_CROSS, prm, diameter, diam_group, want, scores, nullptr, nullptr, nullptr, nullptr, workspace,
+                  (workspace_bytes - tneed) & ~(size_t)15, stream, RankReq{k, idx_base, top_scores, top_idx, keys});
+}
+
+// ---------------------------------------------------------------------------------------------
+// Batched jobs: J independent (query, pool) re-ranks in one call.  Every entry point reads: its own set check, the shared
+// argument checks (batch_host.h: batch_preamble), its workspace layout, its choice of form, its launches, the shared rank
+// (BatchRank::rank).
+// ---------------------------------------------------------------------------------------------
 extern "C" size_t aspire_ot_rank_batch_workspace_bytes(const aspire_repset* q, const aspire_repset* c, int64_t max_job, int64_t k) {
     if (!q || !c || q->n <= 0 || c->n <= 0) return 0;
     const int mr = max_rows_of(q, c);
@@ -3016,20 +3116,10 @@ int ot_rank_batch(const aspire_repset* q, const aspire_repset* c, int64_t D, con
     if (int rc = check_repsets(q, c, D, ASPIRE_PAIR_CROSS)) return rc;
     if (int rc = check_ot_params(prm, want)) return rc;
     const int64_t J = q->n, C = c->n;
-    ASPIRE_REQUIRE(q->ext == 0 && c->ext == 0, ASPIRE_ERR_INVALID_ARG, "batched jobs take CSR rep sets (ext == 0)");
-    ASPIRE_REQUIRE(k >= 0 && (k == 0 || (top_scores && top_idx) || keys), ASPIRE_ERR_INVALID_ARG,
-                   "k > 0 needs (top_scores, top_idx) or keys");
-    if (J == 0) return ASPIRE_OK;
-    ASPIRE_REQUIRE(job_off && max_job >= 0 && max_job <= C, ASPIRE_ERR_INVALID_ARG, "need job_off and 0 <= max_job <= C");
-    ASPIRE_REQUIRE(J < ((int64_t)1 << 30) && C < ((int64_t)1 << 31) - 8, ASPIRE_ERR_UNSUPPORTED, "batch too large for 32-bit offsets");
+    BatchRank rank{J, max_job, k, top_scores, top_idx, keys, job_off, job_base, stream};
+    bool go_on;
+    if (int rc = batch_preamble(q, c, scores, rank, go_on); !go_on) return rc;
     hipStream_t s0 = (hipStream_t)stream;
-    if (C == 0) {
-        // every pool is empty: the lists are all padding
-        const float* unread = reinterpret_cast<const float*>(job_off);     // every segment is empty: never dereferenced
-        if (k > 0) return topk_run(unread, J, 0, k, 0, top_scores, top_idx, keys, nullptr, 0, stream, job_off, job_base);
-        return ASPIRE_OK;
-    }
-    ASPIRE_REQUIRE(scores, ASPIRE_ERR_INVALID_ARG, "null scores");
     // Documents beyond the tile kernels' 32 rows (AspireNER's appended entity rows, models.py:224-233), as in ot_run: the tile
     // kernels run with their documents' bound clamped to 32 rows (a pair that holds a longer document gets NaN there) and the
     // long-document kernel (generic.hip) then rewrites exactly those pairs, in front of the rank.
@@ -3041,25 +3131,13 @@ int ot_rank_batch(const aspire_repset* q, const aspire_repset* c, int64_t D, con
     ASPIRE_REQUIRE(workspace && workspace_bytes >= L.total, ASPIRE_ERR_INVALID_ARG,
                    "workspace too small: %zu bytes given, aspire_ot_rank_batch_workspace_bytes says %zu", workspace_bytes, L.total);
     ASPIRE_REQUIRE(((uintptr_t)workspace & 15) == 0, ASPIRE_ERR_INVALID_ARG, "workspace must be 16-byte aligned");
-    char* wsb = (char*)workspace;
-    float* qbox = (float*)(wsb + L.qbox);
-    int32_t* cand_job = (int32_t*)(wsb + L.cand_job);
-    int32_t* grp_job = (int32_t*)(wsb + L.grp_job);
-    int32_t* grp_off = (int32_t*)(wsb + L.grp_off);
-    int32_t* grp_rec = (int32_t*)(wsb + L.grp_rec);
+    const BatchTables t = batch_tables(workspace, L);
+    rank.scratch_at(t.topk);
+    if (!(stages & kStageRank)) rank.k = 0;      // (a stage mask of the debug entry point without the rank: scores only)
     ScoreArgs a{};
     fill_ot_args(a, q, c, kPairMapped, prm, nullptr, 0, want, scores);
     a.q_per_block = 1;
-    a.cand0 = 0;
-    a.cand1 = C;
-    a.qmap = cand_job;
-    a.job_off = job_off;
-    a.grp_off = grp_off;
-    a.grp_job = grp_job;
-    a.grp_rec = grp_rec;
-    a.job0 = 0;
-    a.job1 = (int32_t)J;
-    a.max_job_groups = (int32_t)((max_job + 3) / 4);
+    fill_mapped_args(a, t, job_off, J, C, max_job);
     // Forms.  Small batches are latency bound and take the kernels the single-pool entry points use.  Once the batch fills
     // the chip (documents of <= 8 rows): the fused kernel -- four candidates of a job per wave, costs and solves in one
     // launch (fused.hip) -- or, pinned for A/B tests, the same cost kernel + the block Sinkhorn kernel as two launches.
@@ -3070,15 +3148,10 @@ int ot_rank_batch(const aspire_repset* q, const aspire_repset* c, int64_t D, con
         a.qmap = nullptr;
         if (stages & kStageSolve)
             if (int rc = launch_pair_generic(a, 0, 0, q->max_len, c->max_len, s0)) return rc;
-        const size_t need = aspire_topk_workspace_bytes(J, max_job, k);
-        if (k > 0 && (stages & kStageRank))
-            return topk_run(scores, J, max_job, k, 0, keys ? nullptr : top_scores, keys ? nullptr : top_idx, keys,
-                            need ? wsb + L.topk : nullptr, need, stream, job_off, job_base);
-        return ASPIRE_OK;
+        return rank.rank(scores);
     }
     const int64_t groups_bound = J * ((max_job + 3) / 4);
     const int form_t = tuning().ot_form;
-    const size_t topk_need = aspire_topk_workspace_bytes(J, max_job, k);
     const bool big = max_rows <= 8 && groups_bound >= kStreamMinGroupsBatch;
     const bool fused = max_rows <= 8 && (form_t == 3 || (form_t == 0 && big));
     a.tile_form = max_rows <= 8 && (form_t == 2 || fused);
@@ -3092,99 +3165,57 @@ int ot_rank_batch(const aspire_repset* q, const aspire_repset* c, int64_t D, con
                         sinkhorn_form_honours_gate();
     // Short queries (facet-selected rows, models.py:127-163) against abstracts of up to 32 rows -- config 4's shape: the fused
     // kernel's CHUNK form, costs and solves of every pair in one launch behind a launch that sorts the candidates into items.
-    const bool chunked = q->max_len <= 8 && max_rows > 8 && max_rows_all <= 8 * kMaxT && (form_t == 4 || (form_t == 0 && C >= kChunkMinCands)) &&
-                         stages == kStageAll && prm->scaling >= 0.25 && !tuning().fused_valu;
+    const bool chunked = q->max_len <= 8 && max_rows > 8 && max_rows_all <= 8 * kMaxT && chunk_size_ok(C) && stages == kStageAll &&
+                         prm->scaling >= 0.25 && !tuning().fused_valu;
     if (chunked) {
-        a.chunk_regions = chunk_regions_of(J, max_job);
-        a.chunk_region_cap = chunk_region_cap_of(max_job);
-        if (a.chunk_regions == 0) ASPIRE_HIP_OK(hipMemsetAsync(grp_off, 0, sizeof(int32_t), s0));
-        hipLaunchKernelGGL(chunk_prep_kernel, dim3((unsigned)J, (unsigned)chunk_parts(max_job) + 1), dim3(192), 0, s0, a.q, a.c, job_off, qbox,
-                           cand_job, grp_off, grp_rec, a.chunk_regions > 0 ? a.chunk_region_cap : 0);
-        ASPIRE_LAUNCH_OK();
-        if (int rc = launch_pair_fused_chunk(a, chunk_items_bound(J, C, max_job), qbox, s0)) return rc;
-        if (k > 0)
-            return topk_run(scores, J, max_job, k, 0, keys ? nullptr : top_scores, keys ? nullptr : top_idx, keys,
-                            topk_need ? wsb + L.topk : nullptr, topk_need, stream, job_off, job_base);
-        return ASPIRE_OK;
+        if (int rc = launch_chunk_prep(a, t, job_off, J, max_job, s0)) return rc;
+        if (int rc = launch_pair_fused_chunk(a, chunk_items_bound(J, C, max_job), t.qbox, s0)) return rc;
+        return rank.rank(scores);
     }
     // Whole abstracts on both sides, documents of 17 .. 32 rows among them (un-faceted queries: pp_settings.py:2-3): the 16-row
     // streaming kernel on record items (a query half against two candidate halves) + the block Sinkhorn kernel on 24- / 32-row
     // workspace slots.  (Before: the VALU tile loop, one workgroup per candidate.)
-    const bool rec16 = !chunked && max_rows > 16 && max_rows_all <= 8 * kMaxT && (form_t == 4 || (form_t == 0 && C >= kChunkMinCands)) &&
-                       stages == kStageAll && tuning().cost_path != 2;
+    const bool rec16 = max_rows > 16 && max_rows_all <= 8 * kMaxT && chunk_size_ok(C) && stages == kStageAll && tuning().cost_path != 2;
     if (rec16) {
-        ASPIRE_HIP_OK(hipMemsetAsync(grp_off, 0, sizeof(int32_t), s0));
-        hipLaunchKernelGGL(chunk16_prep_kernel, dim3((unsigned)J, (unsigned)chunk_parts(max_job) + 1), dim3(192), 0, s0, a.q, a.c, job_off, qbox,
-                           cand_job, grp_off, grp_rec);
-        ASPIRE_LAUNCH_OK();
+        if (int rc = launch_rec_prep(a, t, job_off, J, max_job, s0)) return rc;
         const int rc_run = dispatch_T(max_rows, [&](auto tc) -> int {
             constexpr int T = decltype(tc)::value;
             if constexpr (T >= 3) {
-                PairWs<T> ws;
-                ws.cost = (float*)(wsb + L.slots);
-                ws.neg = ws.cost + C * PairWs<T>::kEntries;
-                ws.diam2 = ws.neg + C * PairWs<T>::kEntries;
-                if (int rc = launch_pair_tile16_rec(a, T, ws.cost, ws.neg, ws.diam2, 2 * chunk_items_bound(J, C, max_job), qbox, s0)) return rc;
+                const PairWs<T> ws = pair_ws_at<T>(t.slots, C);
+                if (int rc = launch_pair_tile16_rec(a, T, ws.cost, ws.neg, ws.diam2, 2 * chunk_items_bound(J, C, max_job), t.qbox, s0)) return rc;
                 return launch_sinkhorn_stage<T>(a, ws, C, max_rows, false, 3, s0);
             }
             return (int)ASPIRE_ERR_UNSUPPORTED;
         });
         if (rc_run) return rc_run;
-        if (k > 0)
-            return topk_run(scores, J, max_job, k, 0, keys ? nullptr : top_scores, keys ? nullptr : top_idx, keys,
-                            topk_need ? wsb + L.topk : nullptr, topk_need, stream, job_off, job_base);
-        return ASPIRE_OK;
+        return rank.rank(scores);
     }
     // batches of <= 64 jobs on the fused kernel need no tables launch: the kernel's waves derive them (fused.hip, SELF)
     const bool self = fused && fused_self_ok(J, prm);
-    if ((stages & kStagePrep) && !self) {
-        // parts per job: enough blocks that a job's groups take a couple of trips each
-        const int64_t work = ((max_job + 3) / 4) * 16;
-        int64_t parts = (work + 2 * 192 - 1) / (2 * 192);
-        parts = parts < 1 ? 1 : parts > 64 ? 64 : parts;
-        while (parts > 1 && J * parts > 4096) parts /= 2;
-        hipLaunchKernelGGL(batch_prep_kernel, dim3((unsigned)J, (unsigned)parts + 1), dim3(192), 0, s0, a.q, a.c, job_off, (int)J, qbox, cand_job,
-                           grp_off, grp_job, grp_rec);
-        ASPIRE_LAUNCH_OK();
-    }
+    if ((stages & kStagePrep) && !self)
+        if (int rc = launch_batch_tables(a, t, job_off, J, max_job, s0)) return rc;
     if (hybrid) {
-        int32_t* gate = (int32_t*)(wsb + L.gate);
-        ASPIRE_HIP_OK(hipMemsetAsync(gate, 0, sizeof(int32_t), s0));
-        hipLaunchKernelGGL(long_pair_census_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s0, a, gate);
-        ASPIRE_LAUNCH_OK();
-        a.gate = gate;
-        a.gate_limit = (int32_t)(C / 24);     // up to ~4 % long pairs (measured crossover at 20 x 1000: 5 %): fused kernel + the 16-row kernels on the long pairs only
-        if (int rc = launch_pair_fused(a, groups_bound, qbox, s0)) return rc;
+        if (int rc = arm_long_pair_gate(a, t.gate, C, s0)) return rc;
+        if (int rc = launch_pair_fused(a, groups_bound, t.qbox, s0)) return rc;
     }
     if (fused) {
         if (stages & (kStageCost | kStageSolve))
-        {
-#ifdef ASPIRE_EXPERIMENT_SPLIT
-            if (self && stages == kStageAll && split_path_ok(groups_bound, prm)) {
-                if (int rc = launch_pair_split(a, s0)) return rc;
-            } else
-#endif
-            if (int rc = launch_pair_fused(a, groups_bound, self ? nullptr : qbox, s0)) return rc;
-        }
+            if (int rc = launch_fused_form(a, groups_bound, self, stages == kStageAll, t.qbox, prm, s0)) return rc;
     } else {
         const int rc_run = dispatch_T(max_rows, [&](auto tc) -> int {
             constexpr int T = decltype(tc)::value;
             if constexpr (T == 1) {
                 // a small batch of short documents: the single-pool calls' one-launch form (pair_one_kernel: one wave per pair) -- the
                 // same kernel whether a pair is scored in a batch or in a call of its own: the same bits
-                if (stages == kStageAll && !a.tile_form && C <= kOneMaxPairs &&
-                    (form_t == 5 || (form_t == 0 && tuning().sinkhorn_form == 0 && tuning().cost_path == 0 && tuning().cost1_blocks == 0))) {
+                if (one_wave_form_ok(C, stages == kStageAll, !a.tile_form)) {
                     hipLaunchKernelGGL(pair_one_kernel, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, s0, a, C);
                     ASPIRE_LAUNCH_OK();
                     return (int)ASPIRE_OK;
                 }
             }
-            PairWs<T> ws;
-            ws.cost = (float*)(wsb + L.slots);
-            ws.neg = ws.cost + C * PairWs<T>::kEntries;
-            ws.diam2 = ws.neg + C * PairWs<T>::kEntries;
+            const PairWs<T> ws = pair_ws_at<T>(t.slots, C);
             if (stages & kStageCost)
-                if (int rc = launch_cost_stage<T>(a, q, c, ws, C, 1, false, qbox, nullptr, true, s0)) return rc;
+                if (int rc = launch_cost_stage<T>(a, q, c, ws, C, 1, false, t.qbox, nullptr, true, s0)) return rc;
             if (stages & kStageSolve)
                 if (int rc = launch_sinkhorn_stage<T>(a, ws, C, max_rows, false, a.tile_form ? 3 : 0, s0)) return rc;
             return (int)ASPIRE_OK;
@@ -3193,10 +3224,7 @@ int ot_rank_batch(const aspire_repset* q, const aspire_repset* c, int64_t D, con
         if (max_rows_all > max_rows && (stages & kStageSolve))
             if (int rc = launch_pair_generic(a, 0, max_rows, q->max_len, c->max_len, s0)) return rc;
     }
-    if (k > 0 && (stages & kStageRank))
-        return topk_run(scores, J, max_job, k, 0, keys ? nullptr : top_scores, keys ? nullptr : top_idx, keys,
-                        topk_need ? wsb + L.topk : nullptr, topk_need, stream, job_off, job_base);
-    return ASPIRE_OK;
+    return rank.rank(scores);
 }
 }  // namespace
 
@@ -3212,22 +3240,6 @@ extern "C" int aspire_ot_rank_batch_f32(const aspire_repset* q, const aspire_rep
 namespace {
 // groups of four candidates from which aspire_l2max_rank_batch_f32 takes the streaming kernels (measured, tools/l2batchbench.py)
 constexpr int64_t kL2StreamMinGroups = 384;
-struct L2BatchLayout {
-    size_t cand_job, grp_job, grp_off, grp_rec, qbox, gate, topk, total;
-};
-L2BatchLayout l2_batch_layout(int64_t J, int64_t C, int64_t max_job, int64_t k) {
-    L2BatchLayout L{};
-    size_t o = 0;
-    L.cand_job = o; o = align16(o + (size_t)C * sizeof(int32_t));
-    L.grp_job = o; o = align16(o + (size_t)(C / 4 + J + 1) * sizeof(int32_t));
-    L.grp_off = o; o = align16(o + (size_t)(J + 1 > 64 ? J + 1 : 64) * sizeof(int32_t));
-    L.grp_rec = o; o = align16(o + (2 * (size_t)chunk_items_bound(J, C, max_job) + 1) * 16 * sizeof(int32_t));     // (room for the CHUNK / REC forms' items)
-    L.qbox = o; o = align16(o + (size_t)J * 2 * kD * sizeof(float));      // (written by the tables kernel, unused by max-sim)
-    L.gate = o; o = align16(o + 16);
-    L.topk = o; o = align16(o + aspire_topk_workspace_bytes(J, max_job, k));
-    L.total = o;
-    return L;
-}
 }  // namespace
 
 extern "C" size_t aspire_l2max_rank_batch_workspace_bytes(const aspire_repset* q, const aspire_repset* c, int64_t max_job, int64_t k) {
@@ -3241,99 +3253,52 @@ extern "C" int aspire_l2max_rank_batch_f32(const aspire_repset* q, const aspire_
                                            size_t workspace_bytes, void* stream) {
     if (int rc = check_repsets(q, c, D, ASPIRE_PAIR_CROSS)) return rc;
     const int64_t J = q->n, C = c->n;
-    ASPIRE_REQUIRE(q->ext == 0 && c->ext == 0, ASPIRE_ERR_INVALID_ARG, "batched jobs take CSR rep sets (ext == 0)");
-    ASPIRE_REQUIRE(k >= 0 && (k == 0 || (top_scores && top_idx) || keys), ASPIRE_ERR_INVALID_ARG,
-                   "k > 0 needs (top_scores, top_idx) or keys");
-    if (J == 0) return ASPIRE_OK;
-    ASPIRE_REQUIRE(job_off && max_job >= 0 && max_job <= C, ASPIRE_ERR_INVALID_ARG, "need job_off and 0 <= max_job <= C");
-    ASPIRE_REQUIRE(J < ((int64_t)1 << 30) && C < ((int64_t)1 << 31) - 8, ASPIRE_ERR_UNSUPPORTED, "batch too large for 32-bit offsets");
+    BatchRank rank{J, max_job, k, top_scores, top_idx, keys, job_off, job_base, stream};
+    bool go_on;
+    if (int rc = batch_preamble(q, c, scores, rank, go_on); !go_on) return rc;
     hipStream_t s0 = (hipStream_t)stream;
-    if (C == 0) {
-        const float* unread = reinterpret_cast<const float*>(job_off);     // every segment is empty: never dereferenced
-        if (k > 0) return topk_run(unread, J, 0, k, 0, top_scores, top_idx, keys, nullptr, 0, stream, job_off, job_base);
-        return ASPIRE_OK;
-    }
-    ASPIRE_REQUIRE(scores, ASPIRE_ERR_INVALID_ARG, "null scores");
     const int max_rows = max_rows_of(q, c);
     ASPIRE_REQUIRE(max_rows <= generic_max_rows(), ASPIRE_ERR_UNSUPPORTED, "documents with more than %d sentence rows are not supported (got %d)",
                    generic_max_rows(), max_rows);
-    const L2BatchLayout L = l2_batch_layout(J, C, max_job, k);
+    const BatchLayout L = l2_batch_layout(J, C, max_job, k);
     ASPIRE_REQUIRE(workspace && workspace_bytes >= L.total, ASPIRE_ERR_INVALID_ARG,
                    "workspace too small: %zu bytes given, aspire_l2max_rank_batch_workspace_bytes says %zu", workspace_bytes, L.total);
     ASPIRE_REQUIRE(((uintptr_t)workspace & 15) == 0, ASPIRE_ERR_INVALID_ARG, "workspace must be 16-byte aligned");
-    char* wsb = (char*)workspace;
+    const BatchTables t = batch_tables(workspace, L);
+    rank.scratch_at(t.topk);
     const bool one_form = (cdist_mode & ASPIRE_CDIST_ONE_FORM) != 0, center = (cdist_mode & ASPIRE_CDIST_CENTER) != 0;
     cdist_mode &= ~(ASPIRE_CDIST_ONE_FORM | ASPIRE_CDIST_CENTER);
     ScoreArgs a{};
-    a.q = to_dev(q);
-    a.c = to_dev(c);
-    a.q_planes = q->planes;
-    a.c_planes = c->planes;
-    a.c_box = c->doc_box;
-    a.pairing = kPairMapped;
+    fill_set_args(a, q, c, kPairMapped);
     a.cdist_mode = cdist_mode;
     a.center = center;
     a.agg = ASPIRE_AGG_MAX;
     a.temp = 1.0;
     a.scores = scores;
-    a.cand0 = 0;
-    a.cand1 = C;
-    a.qmap = (int32_t*)(wsb + L.cand_job);
-    a.job_off = job_off;
-    a.grp_off = (int32_t*)(wsb + L.grp_off);
-    a.grp_job = (int32_t*)(wsb + L.grp_job);
-    a.grp_rec = (int32_t*)(wsb + L.grp_rec);
-    a.job0 = 0;
-    a.job1 = (int32_t)J;
-    a.max_job_groups = (int32_t)((max_job + 3) / 4);
+    fill_mapped_args(a, t, job_off, J, C, max_job);
     const int64_t groups_bound = J * ((max_job + 3) / 4);
     const int form_t = tuning().ot_form;
     const bool big = groups_bound >= 2048 && C >= 6000 && form_t != 1;
     // (small batches too: a wave walks an item's twelve stages in ~15 us, what a one-workgroup-per-pair launch takes anyway)
-    // batches of <= 64 jobs of short documents: the streaming kernel's waves derive the tables themselves (fused.hip, SELF) --
-    // one launch in front of the rank, at any size (2 x 20: 19 us either way)
     // short queries against abstracts of up to 32 rows (config 4's shape): the CHUNK items of ot_rank_batch, max epilogue
-    if (q->max_len <= 8 && max_rows > 8 && max_rows <= 8 * kMaxT && (form_t == 4 || (form_t == 0 && C >= kChunkMinCands)) && !one_form) {
-        a.chunk_regions = chunk_regions_of(J, max_job);
-        a.chunk_region_cap = chunk_region_cap_of(max_job);
-        if (a.chunk_regions == 0) ASPIRE_HIP_OK(hipMemsetAsync((int32_t*)(wsb + L.grp_off), 0, sizeof(int32_t), s0));
-        hipLaunchKernelGGL(chunk_prep_kernel, dim3((unsigned)J, (unsigned)chunk_parts(max_job) + 1), dim3(192), 0, s0, a.q, a.c, job_off,
-                           (float*)(wsb + L.qbox), (int32_t*)(wsb + L.cand_job), (int32_t*)(wsb + L.grp_off), (int32_t*)(wsb + L.grp_rec),
-                           a.chunk_regions > 0 ? a.chunk_region_cap : 0);
-        ASPIRE_LAUNCH_OK();
+    if (q->max_len <= 8 && max_rows > 8 && max_rows <= 8 * kMaxT && chunk_size_ok(C) && !one_form) {
+        if (int rc = launch_chunk_prep(a, t, job_off, J, max_job, s0)) return rc;
         if (int rc = launch_pair_fused_chunk_l2max(a, chunk_items_bound(J, C, max_job), s0)) return rc;
-        const size_t need = aspire_topk_workspace_bytes(J, max_job, k);
-        if (k > 0)
-            return topk_run(scores, J, max_job, k, 0, keys ? nullptr : top_scores, keys ? nullptr : top_idx, keys,
-                            need ? wsb + L.topk : nullptr, need, stream, job_off, job_base);
-        return ASPIRE_OK;
+        return rank.rank(scores);
     }
     // whole abstracts of up to 32 rows against queries of 9 .. 16: the 16-row streaming kernel on record items, max epilogue (a
     // query of more than 16 rows would need its two halves' maxima joined across items: the per-candidate kernel keeps those)
-    if (q->max_len <= 16 && max_rows > 16 && max_rows <= 8 * kMaxT && (form_t == 4 || (form_t == 0 && C >= kChunkMinCands)) && !one_form) {
-        ASPIRE_HIP_OK(hipMemsetAsync((int32_t*)(wsb + L.grp_off), 0, sizeof(int32_t), s0));
-        hipLaunchKernelGGL(chunk16_prep_kernel, dim3((unsigned)J, (unsigned)chunk_parts(max_job) + 1), dim3(192), 0, s0, a.q, a.c, job_off,
-                           (float*)(wsb + L.qbox), (int32_t*)(wsb + L.cand_job), (int32_t*)(wsb + L.grp_off), (int32_t*)(wsb + L.grp_rec));
-        ASPIRE_LAUNCH_OK();
+    if (q->max_len <= 16 && max_rows > 16 && max_rows <= 8 * kMaxT && chunk_size_ok(C) && !one_form) {
+        if (int rc = launch_rec_prep(a, t, job_off, J, max_job, s0)) return rc;
         if (int rc = launch_pair_tile16_rec_l2max(a, 2 * chunk_items_bound(J, C, max_job), s0)) return rc;
-        const size_t need = aspire_topk_workspace_bytes(J, max_job, k);
-        if (k > 0)
-            return topk_run(scores, J, max_job, k, 0, keys ? nullptr : top_scores, keys ? nullptr : top_idx, keys,
-                            need ? wsb + L.topk : nullptr, need, stream, job_off, job_base);
-        return ASPIRE_OK;
+        return rank.rank(scores);
     }
+    // batches of <= 64 jobs of short documents: the streaming kernel's waves derive the tables themselves (fused.hip, SELF) --
+    // one launch in front of the rank, at any size (2 x 20: 19 us either way)
     const bool self = form_t != 1 && max_rows <= 8 && J <= 64 && !tuning().fused_noself && !one_form;
     const bool streaming = form_t != 1 && (self || big || form_t >= 2 || groups_bound >= kL2StreamMinGroups) && !one_form;
-    if (!self) {
-        const int64_t work = ((max_job + 3) / 4) * 16;
-        int64_t parts = (work + 2 * 192 - 1) / (2 * 192);
-        parts = parts < 1 ? 1 : parts > 64 ? 64 : parts;
-        while (parts > 1 && J * parts > 4096) parts /= 2;
-        hipLaunchKernelGGL(batch_prep_kernel, dim3((unsigned)J, (unsigned)parts + 1), dim3(192), 0, s0, a.q, a.c, job_off, (int)J,
-                           (float*)(wsb + L.qbox), (int32_t*)(wsb + L.cand_job), (int32_t*)(wsb + L.grp_off), (int32_t*)(wsb + L.grp_job),
-                           (int32_t*)(wsb + L.grp_rec));
-        ASPIRE_LAUNCH_OK();
-    }
+    if (!self)
+        if (int rc = launch_batch_tables(a, t, job_off, J, max_job, s0)) return rc;
     // Forms: the streaming kernels once the batch fills the chip (documents of <= 8 rows: fused.hip's max-sim form, four
     // candidates of a job per wave; 9 .. 16 rows: tile16.hip, two), else -- small batches, longer documents -- the
     // one-workgroup-per-pair kernel (generic.hip).
@@ -3342,12 +3307,7 @@ extern "C" int aspire_l2max_rank_batch_f32(const aspire_repset* q, const aspire_
     } else if (streaming && max_rows <= 16) {
         // mostly short documents with a few of 9 .. 16 rows: the hybrid of ot_rank_batch (ScoreArgs::gate)
         if (big && form_t == 0) {
-            int32_t* gate = (int32_t*)(wsb + L.gate);
-            ASPIRE_HIP_OK(hipMemsetAsync(gate, 0, sizeof(int32_t), s0));
-            hipLaunchKernelGGL(long_pair_census_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s0, a, gate);
-            ASPIRE_LAUNCH_OK();
-            a.gate = gate;
-            a.gate_limit = (int32_t)(C / 24);
+            if (int rc = arm_long_pair_gate(a, t.gate, C, s0)) return rc;
             if (int rc = launch_pair_fused_l2max(a, groups_bound, s0)) return rc;
         }
         if (int rc = launch_pair_tile16_l2max(a, 2 * groups_bound, s0)) return rc;
@@ -3363,11 +3323,7 @@ extern "C" int aspire_l2max_rank_batch_f32(const aspire_repset* q, const aspire_
     } else {
         if (int rc = launch_pair_generic(a, 1, 0, q->max_len, c->max_len, s0)) return rc;
     }
-    const size_t topk_need = aspire_topk_workspace_bytes(J, max_job, k);
-    if (k > 0)
-        return topk_run(scores, J, max_job, k, 0, keys ? nullptr : top_scores, keys ? nullptr : top_idx, keys,
-                        topk_need ? wsb + L.topk : nullptr, topk_need, stream, job_off, job_base);
-    return ASPIRE_OK;
+    return rank.rank(scores);
 }
 
 // Diagnostics: chosen stages of aspire_ot_rank_batch_f32 on the caller's stream alone (1 tables + query boxes, 2 cost
@@ -3388,12 +3344,7 @@ extern "C" int aspire_group_diameter_f32(const aspire_repset* q, const aspire_re
     ASPIRE_REQUIRE(group > 0 && diameter, ASPIRE_ERR_INVALID_ARG, "group must be positive, diameter non-null");
     if (q->n == 0 || c->n == 0) return ASPIRE_OK;
     ScoreArgs a{};
-    a.q = to_dev(q);
-    a.c = to_dev(c);
-    a.q_planes = q->planes;
-    a.c_planes = c->planes;
-    a.c_box = c->doc_box;
-    a.pairing = pairing;
+    fill_set_args(a, q, c, pairing);
     const int64_t ngroups = (c->n + group - 1) / group;
     const int64_t blocks = pairing == ASPIRE_PAIR_PAIRED ? ngroups : ngroups * q->n;     // (query, group) folded into grid.x
     ASPIRE_REQUIRE(blocks < ((int64_t)1 << 31), ASPIRE_ERR_UNSUPPORTED, "too many (query, group) boxes: %lld", (long long)blocks);
