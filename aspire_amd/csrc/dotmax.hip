@@ -254,7 +254,7 @@ __global__ void __launch_bounds__(256) dotmax_cross_kernel(DotArgs a) {
                     if (v % vstep) continue;
                     const int64_t cdoc = (slot0 + 16 * t + 4 * g + v) >> a.wc_log;
                     if (cdoc >= C) continue;
-                    const bool too_long = qlen > Wq || a.c.len[cdoc] > Wc;
+                    const bool too_long = qlen > a.q.bound || a.c.len[cdoc] > a.c.bound;     // (the bound, not its row slots)
                     a.scores[qdoc * C + cdoc] = too_long ? __builtin_nanf("") : m[v];
                 }
             }
