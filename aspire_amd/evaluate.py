@@ -39,8 +39,9 @@ def score(results_dir, test_pool, rep_store, facet=None, pred_labels=None, metho
 
     With the per-pair schedule (the reference's own: one get_similarity call per candidate, evaluate.py:68-72) and method 'ot',
     'l2max' or cosentbert's 'cosine' / 'dotlse' (TrainedSentModel.get_similarity, models.py:602-604) the queries go
-    through scorer.rank_pools `queries_per_call` at a time -- every query against ITS OWN pool in one library call; any other
-    schedule / aggregation keeps one rank_pool call per query.  resident: the candidates of all pools are uploaded once
+    through scorer.rank_pools' one library call `queries_per_call` at a time -- every query against ITS OWN pool (rank_pool_batch on
+    resident pools, else _launch_rank_pools); any other schedule / aggregation keeps one rank_pool call (_launch_rank_pool) per query.
+    All three hand scorer.ranked_lists their (top_s, top_i) with sign = -1 (evaluate.py:77).  resident: the candidates of all pools are uploaded once
     (RepStore.to_device: a paper in many pools is stored once) and the pools are index lists into that matrix.
 
     sharded (default: whenever torch.distributed is initialised with more than one rank; `group`: the process group): the step on
@@ -66,9 +67,6 @@ def score(results_dir, test_pool, rep_store, facet=None, pred_labels=None, metho
             rep_store.to_device([c for pool in test_pool.values() for c in pool['cands']])
         all_resident = bool(wanted)
 
-    def query_reps(query_id):
-        return rep_store.faceted(query_id, facet, pred_labels[query_id]) if facet is not None else rep_store.get(query_id)
-
     if schedule == 'pair' and method in scorer.BATCH_METHODS and queries_per_call > 1:
         for lo in range(0, len(query_ids), queries_per_call):
             ids = query_ids[lo:lo + queries_per_call]
@@ -76,23 +74,27 @@ def score(results_dir, test_pool, rep_store, facet=None, pred_labels=None, metho
             if resident and all_resident:
                 # the pools' device tables are built once and cached (RepStore.pool_batch): one upload of the queries, one call;
                 # evaluate.py:77 stores -similarity
-                ranked = scorer.rank_pool_batch([query_reps(i) for i in ids], rep_store.pool_batch(cand_lists), method=method,
-                                                hparams=hparams, sign=-1.0, deterministic=deterministic)
-                results.update(zip(ids, ranked))
-                continue
+                qreps = [_query_reps(rep_store, i, facet, pred_labels) for i in ids]
+                ranked = scorer.rank_pool_batch(qreps, rep_store.pool_batch(cand_lists), method=method, hparams=hparams, sign=-1.0,
+                                                deterministic=deterministic)
             else:
                 pools = [rep_store.pool(list(cl)) for cl in cand_lists]
-                ranked = scorer.rank_pools([query_reps(i) for i in ids], pools, method=method, hparams=hparams,
-                                           deterministic=deterministic)
-            for query_id, r in zip(ids, ranked):
-                results[query_id] = [(cid, -1 * sim) for cid, sim in r]     # evaluate.py:77
+                qreps = [_query_reps(rep_store, i, facet, pred_labels) for i in ids]
+                ranked = scorer.ranked_lists(*scorer._launch_rank_pools(qreps, pools, None, hparams, method, deterministic), sign=-1.0)
+            results.update(zip(ids, ranked))
     else:
         for query_id in query_ids:
             pool = rep_store.pool(list(test_pool[query_id]['cands']))
-            ranked = scorer.rank_pool([query_reps(query_id)], pool, method=method, schedule=schedule, hparams=hparams)[0]
-            results[query_id] = [(cid, -1 * sim) for cid, sim in ranked]     # evaluate.py:77
+            qreps = [_query_reps(rep_store, query_id, facet, pred_labels)]
+            results[query_id] = scorer.ranked_lists(*scorer._launch_rank_pool(qreps, pool, method=method, schedule=schedule, hparams=hparams),
+                                                    sign=-1.0)[0]
     _write_scores(results_dir, facet, results)
     return results
+
+
+def _query_reps(rep_store, query_id, facet, pred_labels):
+    """A faceted query keeps only the sentence rows whose predicted label matches the facet (models.py:127-163)."""
+    return rep_store.faceted(query_id, facet, pred_labels[query_id]) if facet is not None else rep_store.get(query_id)
 
 
 def _write_scores(results_dir, facet, results):
@@ -132,23 +134,18 @@ def _score_sharded(results_dir, test_pool, rep_store, facet, pred_labels, method
         step = max(1, int(queries_per_call))
         for b0 in range(0, len(mine), step):
             ids = mine[b0:b0 + step]
-            qreps = [rep_store.faceted(i, facet, pred_labels[i]) if facet is not None else rep_store.get(i) for i in ids]
+            qreps = [_query_reps(rep_store, i, facet, pred_labels) for i in ids]
             pools = [rep_store.pool(list(test_pool[i]['cands'])) for i in ids]
             _, ts, ti = scorer._launch_rank_pools(qreps, pools, None, hparams, method, deterministic)
             if ts is not None:
                 local_s[b0:b0 + len(ids), :ts.shape[1]] = ts
                 local_i[b0:b0 + len(ids), :ti.shape[1]] = ti
     top_s, top_i = all_gather_ranked_jobs(local_s, local_i, n_jobs, k, group, device=dev)
-    top_s, top_i = top_s.cpu().numpy().astype('float64'), top_i.cpu().numpy()
-    results = {}
-    for qid, n, rs, ri in zip(query_ids, sizes, top_s, top_i):
-        cands = test_pool[qid]['cands']
-        results[qid] = [(cands[i], -1 * float(sc)) for sc, i in zip(rs[:n], ri[:n])]           # evaluate.py:77
+    results = dict(zip(query_ids, scorer.ranked_lists([test_pool[i]['cands'] for i in query_ids], top_s, top_i, sign=-1.0)))
     if rank == 0:
         _write_scores(results_dir, facet, results)
     dist.barrier(group)                                                                        # the file exists when any rank returns
     return results
-
 
 
 def load_score_results(results_dir, gold, facet):

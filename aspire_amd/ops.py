@@ -314,13 +314,26 @@ def cls_l2(q_cls, c_cls, pairing=_lib.PAIR_PAIRED, eps=1e-6):
     return out
 
 
-def l2max_scores(q, c, pairing=_lib.PAIR_CROSS, cdist_mode=_lib.CDIST_AUTO, want_pair_sims=False, one_form=False):
-    """A9 (pair_distances.py:138-186).  Returns sims [P] (and pair_sims [P, q.ext, c.ext]).  one_form: see
-    include/aspire_hip.h, ASPIRE_CDIST_ONE_FORM."""
+def _ot_params(c, blur, scaling, sent_sm_temp, cdist_mode, one_form):
+    """struct aspire_ot_params of an otAspire call with its flag word: ONE_FORM as the caller asks, CENTER from the candidates' rows
+    (DeviceRepSet.center_hint)."""
+    return OtParams(float(blur), float(scaling), float(sent_sm_temp), cdist_mode,
+                    (_lib.OT_FLAG_ONE_FORM if one_form else 0) | (_lib.OT_FLAG_CENTER if c.center_hint() else 0))
+
+
+def _cdist_flags(c, cdist_mode, one_form):
+    """The same two flags on the cdist_mode word of the max-sim entries (ASPIRE_CDIST_ONE_FORM / ASPIRE_CDIST_CENTER)."""
     if one_form:
         cdist_mode |= _lib.CDIST_ONE_FORM
     if c.center_hint():
         cdist_mode |= _lib.CDIST_CENTER
+    return cdist_mode
+
+
+def l2max_scores(q, c, pairing=_lib.PAIR_CROSS, cdist_mode=_lib.CDIST_AUTO, want_pair_sims=False, one_form=False):
+    """A9 (pair_distances.py:138-186).  Returns sims [P] (and pair_sims [P, q.ext, c.ext]).  one_form: see
+    include/aspire_hip.h, ASPIRE_CDIST_ONE_FORM."""
+    cdist_mode = _cdist_flags(c, cdist_mode, one_form)
     p = _npairs(q, c, pairing)
     dev = q.rows.device
     scores = torch.empty(p, device=dev, dtype=torch.float32)
@@ -371,7 +384,7 @@ def ot_sinkhorn(q, c, pairing=_lib.PAIR_CROSS, blur=0.05, scaling=0.9, sent_sm_t
     if want_extras:
         extras = [torch.empty(p, q.ext, device=dev), torch.empty(p, c.ext, device=dev),
                   torch.empty(p, q.ext, c.ext, device=dev), torch.empty(p, q.ext, c.ext, device=dev)]
-    prm = OtParams(float(blur), float(scaling), float(sent_sm_temp), cdist_mode, (_lib.OT_FLAG_ONE_FORM if one_form else 0) | (_lib.OT_FLAG_CENTER if c.center_hint() else 0))
+    prm = _ot_params(c, blur, scaling, sent_sm_temp, cdist_mode, one_form)
     _match_planes(q, c, pairing)
     qs, cs = q.struct(), c.struct()
     nbytes = lib.aspire_ot_workspace_bytes(ctypes.byref(qs), ctypes.byref(cs), pairing)
@@ -390,7 +403,7 @@ def ot_rank(q, c, k, blur=0.05, scaling=0.9, sent_sm_temp=1.0, cdist_mode=_lib.C
     is of the OUTPUT; pass want=OT_PLAN_SIM for similarities) -- or (scores, keys [Q, k]) with key_form."""
     dev = q.rows.device
     scores = torch.empty(q.n, c.n, device=dev, dtype=torch.float32)
-    prm = OtParams(float(blur), float(scaling), float(sent_sm_temp), cdist_mode, (_lib.OT_FLAG_ONE_FORM if one_form else 0) | (_lib.OT_FLAG_CENTER if c.center_hint() else 0))
+    prm = _ot_params(c, blur, scaling, sent_sm_temp, cdist_mode, one_form)
     _match_planes(q, c, _lib.PAIR_CROSS)
     qs, cs = q.struct(), c.struct()
     nbytes = lib.aspire_ot_rank_workspace_bytes(ctypes.byref(qs), ctypes.byref(cs), k)
@@ -406,6 +419,34 @@ def ot_rank(q, c, k, blur=0.05, scaling=0.9, sent_sm_temp=1.0, cdist_mode=_lib.C
     return (scores, keys) if key_form else (scores, top_s, top_i)
 
 
+def _rank_batch(entry, mid, q, c, job_off, max_job, k, out, workspace, job_base, key_form):
+    """What the batched rank wrappers share.  `entry` names the pair of library entries (_RANK_BATCH); `mid()` gives the arguments
+    that sit between max_job and scores in its C signature -- all that differs between them -- once the checks have passed."""
+    call, workspace_bytes = _RANK_BATCH[entry]
+    dev = q.rows.device
+    _i32(job_off, 'job_off')
+    assert job_off.numel() == q.n + 1, 'job_off must have one entry per job plus one'
+    keys = None
+    if out is not None and key_form:
+        scores, keys = out
+        top_s = top_i = None
+    elif out is not None:
+        scores, top_s, top_i = out
+    else:
+        scores = torch.empty(c.n, device=dev, dtype=torch.float32)
+        top_s = torch.empty(q.n, k, device=dev, dtype=torch.float32) if k > 0 and not key_form else None
+        top_i = torch.empty(q.n, k, device=dev, dtype=torch.int64) if k > 0 and not key_form else None
+        keys = torch.empty(q.n, k, device=dev, dtype=torch.int64) if k > 0 and key_form else None
+    mid = mid()
+    qs, cs = q.struct(), c.struct()
+    if workspace is None:
+        nbytes = workspace_bytes(ctypes.byref(qs), ctypes.byref(cs), max_job, k)
+        workspace = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
+    check(call(ctypes.byref(qs), ctypes.byref(cs), D, _ptr(job_off), max_job, *mid, _ptr(scores), k, _ptr(job_base), _ptr(top_s),
+               _ptr(top_i), _ptr(keys), _ptr(workspace), workspace.numel(), _stream()))
+    return (scores, keys) if key_form else (scores, top_s, top_i)
+
+
 def ot_rank_batch(q, c, job_off, max_job, k, blur=0.05, scaling=0.9, sent_sm_temp=1.0, cdist_mode=_lib.CDIST_AUTO,
                   want=_lib.OT_SIMILARITY, out=None, workspace=None, job_base=None, key_form=False, one_form=False):
     """J independent (query, pool) re-ranks in ONE call (include/aspire_hip.h: aspire_ot_rank_batch_f32; the per-query
@@ -414,61 +455,17 @@ def ot_rank_batch(q, c, job_off, max_job, k, blur=0.05, scaling=0.9, sent_sm_tem
     with top_idx = position inside the job's own pool (+ job_base[j], int32 GPU tensor [J], when this rank holds one
     block of every pool); `out` = preallocated (scores, top_scores, top_idx).  key_form: (scores, keys [J, k]) -- the
     sortable keys of topk_keys, what a shard contributes to the all-gather."""
-    dev = q.rows.device
-    _i32(job_off, 'job_off')
-    assert job_off.numel() == q.n + 1, 'job_off must have one entry per job plus one'
-    keys = None
-    if out is not None and key_form:
-        scores, keys = out
-        top_s = top_i = None
-    elif out is not None:
-        scores, top_s, top_i = out
-    else:
-        scores = torch.empty(c.n, device=dev, dtype=torch.float32)
-        top_s = torch.empty(q.n, k, device=dev, dtype=torch.float32) if k > 0 and not key_form else None
-        top_i = torch.empty(q.n, k, device=dev, dtype=torch.int64) if k > 0 and not key_form else None
-        keys = torch.empty(q.n, k, device=dev, dtype=torch.int64) if k > 0 and key_form else None
-    prm = OtParams(float(blur), float(scaling), float(sent_sm_temp), cdist_mode, (_lib.OT_FLAG_ONE_FORM if one_form else 0) | (_lib.OT_FLAG_CENTER if c.center_hint() else 0))
-    qs, cs = q.struct(), c.struct()
-    if workspace is None:
-        nbytes = lib.aspire_ot_rank_batch_workspace_bytes(ctypes.byref(qs), ctypes.byref(cs), max_job, k)
-        workspace = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
-    check(lib.aspire_ot_rank_batch_f32(ctypes.byref(qs), ctypes.byref(cs), D, _ptr(job_off), max_job, ctypes.byref(prm), want,
-                                       _ptr(scores), k, _ptr(job_base), _ptr(top_s), _ptr(top_i), _ptr(keys), _ptr(workspace),
-                                       workspace.numel(), _stream()))
-    return (scores, keys) if key_form else (scores, top_s, top_i)
+    def mid():
+        return ctypes.byref(_ot_params(c, blur, scaling, sent_sm_temp, cdist_mode, one_form)), want
+    return _rank_batch('ot', mid, q, c, job_off, max_job, k, out, workspace, job_base, key_form)
 
 
 def l2max_rank_batch(q, c, job_off, max_job, k, cdist_mode=_lib.CDIST_AUTO, out=None, workspace=None, job_base=None, key_form=False,
                      one_form=False):
     """tsAspire over J independent (query, pool) jobs in ONE call (include/aspire_hip.h: aspire_l2max_rank_batch_f32); arguments
     and returns as ot_rank_batch: (scores [C], top_scores [J, k], top_idx [J, k]) or (scores, keys [J, k]) with key_form."""
-    dev = q.rows.device
-    if one_form:
-        cdist_mode |= _lib.CDIST_ONE_FORM
-    if c.center_hint():
-        cdist_mode |= _lib.CDIST_CENTER
-    _i32(job_off, 'job_off')
-    assert job_off.numel() == q.n + 1, 'job_off must have one entry per job plus one'
-    keys = None
-    if out is not None and key_form:
-        scores, keys = out
-        top_s = top_i = None
-    elif out is not None:
-        scores, top_s, top_i = out
-    else:
-        scores = torch.empty(c.n, device=dev, dtype=torch.float32)
-        top_s = torch.empty(q.n, k, device=dev, dtype=torch.float32) if k > 0 and not key_form else None
-        top_i = torch.empty(q.n, k, device=dev, dtype=torch.int64) if k > 0 and not key_form else None
-        keys = torch.empty(q.n, k, device=dev, dtype=torch.int64) if k > 0 and key_form else None
-    qs, cs = q.struct(), c.struct()
-    if workspace is None:
-        nbytes = lib.aspire_l2max_rank_batch_workspace_bytes(ctypes.byref(qs), ctypes.byref(cs), max_job, k)
-        workspace = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
-    check(lib.aspire_l2max_rank_batch_f32(ctypes.byref(qs), ctypes.byref(cs), D, _ptr(job_off), max_job, cdist_mode, _ptr(scores), k,
-                                          _ptr(job_base), _ptr(top_s), _ptr(top_i), _ptr(keys), _ptr(workspace), workspace.numel(),
-                                          _stream()))
-    return (scores, keys) if key_form else (scores, top_s, top_i)
+    cdist_mode = _cdist_flags(c, cdist_mode, one_form)
+    return _rank_batch('l2max', lambda: (cdist_mode,), q, c, job_off, max_job, k, out, workspace, job_base, key_form)
 
 
 def _dot_ready(*sets):
@@ -502,28 +499,26 @@ def dotmax_rank_batch(q, c, job_off, max_job, k, sim=_lib.SIM_COSINE, out=None, 
     """The dot-product max-sim over J independent (query, pool) jobs in ONE call (include/aspire_hip.h:
     aspire_dotmax_rank_batch_f32); arguments and returns as l2max_rank_batch."""
     _dot_ready(q, c)
-    dev = q.rows.device
-    _i32(job_off, 'job_off')
-    assert job_off.numel() == q.n + 1, 'job_off must have one entry per job plus one'
-    keys = None
-    if out is not None and key_form:
-        scores, keys = out
-        top_s = top_i = None
-    elif out is not None:
-        scores, top_s, top_i = out
-    else:
-        scores = torch.empty(c.n, device=dev, dtype=torch.float32)
-        top_s = torch.empty(q.n, k, device=dev, dtype=torch.float32) if k > 0 and not key_form else None
-        top_i = torch.empty(q.n, k, device=dev, dtype=torch.int64) if k > 0 and not key_form else None
-        keys = torch.empty(q.n, k, device=dev, dtype=torch.int64) if k > 0 and key_form else None
+    return _rank_batch('dotmax', lambda: (sim,), q, c, job_off, max_job, k, out, workspace, job_base, key_form)
+
+
+# <entry>_rank_batch -> (its library entry, that entry's workspace query)
+_RANK_BATCH = {'ot': (lib.aspire_ot_rank_batch_f32, lib.aspire_ot_rank_batch_workspace_bytes),
+               'l2max': (lib.aspire_l2max_rank_batch_f32, lib.aspire_l2max_rank_batch_workspace_bytes),
+               'dotmax': (lib.aspire_dotmax_rank_batch_f32, lib.aspire_dotmax_rank_batch_workspace_bytes)}
+
+
+def rank_batch_workspace_bytes(entry, q, c, max_job, k):
+    """Bytes of `workspace` that <entry>_rank_batch (entry 'ot', 'l2max' or 'dotmax') needs for these sets: a host-side
+    computation, for callers that keep one buffer over many calls."""
     qs, cs = q.struct(), c.struct()
-    if workspace is None:
-        nbytes = lib.aspire_dotmax_rank_batch_workspace_bytes(ctypes.byref(qs), ctypes.byref(cs), max_job, k)
-        workspace = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
-    check(lib.aspire_dotmax_rank_batch_f32(ctypes.byref(qs), ctypes.byref(cs), D, _ptr(job_off), max_job, sim, _ptr(scores), k,
-                                           _ptr(job_base), _ptr(top_s), _ptr(top_i), _ptr(keys), _ptr(workspace), workspace.numel(),
-                                           _stream()))
-    return (scores, keys) if key_form else (scores, top_s, top_i)
+    return _RANK_BATCH[entry][1](ctypes.byref(qs), ctypes.byref(cs), max_job, k)
+
+
+def _topk_workspace(scores, k):
+    qn, cn = scores.shape
+    nbytes = lib.aspire_topk_workspace_bytes(qn, cn, k)
+    return torch.empty(max(nbytes, 8), device=scores.device, dtype=torch.uint8), nbytes
 
 
 def topk_desc(scores, k, idx_base=0):
@@ -532,8 +527,7 @@ def topk_desc(scores, k, idx_base=0):
     qn, cn = scores.shape
     top_s = torch.empty(qn, k, device=scores.device, dtype=torch.float32)
     top_i = torch.empty(qn, k, device=scores.device, dtype=torch.int64)
-    nbytes = lib.aspire_topk_workspace_bytes(qn, cn, k)
-    ws = torch.empty(max(nbytes, 8), device=scores.device, dtype=torch.uint8)
+    ws, nbytes = _topk_workspace(scores, k)
     check(lib.aspire_topk_desc_f32(_ptr(scores), qn, cn, k, idx_base, _ptr(top_s), _ptr(top_i), _ptr(ws), nbytes,
                                    _stream()))
     return top_s, top_i
@@ -545,8 +539,7 @@ def topk_keys(scores, k, idx_base=0, out=None):
     _f32(scores, 'scores')
     qn, cn = scores.shape
     keys = out if out is not None else torch.empty(qn, k, device=scores.device, dtype=torch.int64)
-    nbytes = lib.aspire_topk_workspace_bytes(qn, cn, k)
-    ws = torch.empty(max(nbytes, 8), device=scores.device, dtype=torch.uint8)
+    ws, nbytes = _topk_workspace(scores, k)
     check(lib.aspire_topk_keys_f32(_ptr(scores), qn, cn, k, idx_base, _ptr(keys), _ptr(ws), nbytes, _stream()))
     return keys
 

@@ -27,15 +27,23 @@ def _to_repsets(query, cand):
     return q, c, query_reps.device
 
 
+def ot_kwargs(hparams):
+    """Model hyper-parameters -> the blur / scaling / sent_sm_temp keyword arguments of ops.ot_sinkhorn, ot_rank and ot_rank_batch,
+    with the reference's defaults (pair_distances.py:16-19).  Every otAspire caller of the host layer reads them here."""
+    if hparams.get('geoml_reach', None) is not None:
+        # No reference config sets it (config/models_config/**: geoml_reach absent everywhere).
+        raise NotImplementedError('unbalanced OT (geoml_reach) is not built')
+    return dict(blur=hparams.get('geoml_blur', 0.05), scaling=hparams.get('geoml_scaling', 0.9),
+                sent_sm_temp=hparams.get('sent_sm_temp', 1.0))
+
+
 class AllPairMaskedWasserstein:
     def __init__(self, model_hparams):
-        self.geoml_blur = model_hparams.get('geoml_blur', 0.05)
-        self.geoml_scaling = model_hparams.get('geoml_scaling', 0.9)
-        self.geoml_reach = model_hparams.get('geoml_reach', None)
-        self.sent_sm_temp = model_hparams.get('sent_sm_temp', 1.0)
-        if self.geoml_reach is not None:
-            # No reference config sets it (config/models_config/**: geoml_reach absent everywhere).
-            raise NotImplementedError('unbalanced OT (geoml_reach) is not built')
+        kw = ot_kwargs(model_hparams)
+        self.geoml_blur = kw['blur']
+        self.geoml_scaling = kw['scaling']
+        self.geoml_reach = None
+        self.sent_sm_temp = kw['sent_sm_temp']
 
     def compute_distance(self, query, cand, return_pair_sims=False):
         """

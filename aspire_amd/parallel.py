@@ -32,11 +32,22 @@ def shard_bounds(n_items, world_size, rank, multiple=1):
     return min(lo_u * multiple, n_items), min(hi_u * multiple, n_items)
 
 
+def rank_world(group=None):
+    """(this process's rank, the number of ranks) in `group`; (0, 1) when torch.distributed is not initialised."""
+    if dist.is_available() and dist.is_initialized():
+        return dist.get_rank(group), dist.get_world_size(group)
+    return 0, 1
+
+
+def _through_host(t, group):
+    """RCCL ("nccl") moves GPU tensors in place over xGMI; the gloo backend (CPU tests, the one-GPU rehearsals of the multi-rank
+    code) has no GPU collectives, so there a GPU tensor takes a round trip through host memory."""
+    return dist.get_backend(group) == 'gloo' and t.is_cuda
+
+
 def all_gather_flat(out, inp, group=None):
-    """dist.all_gather_into_tensor(out, inp) for 1-D tensors.  RCCL ("nccl") gathers GPU tensors in place over xGMI; the gloo
-    backend (CPU tests, the one-GPU rehearsals of the multi-rank code) has no GPU all-gather, so there the data takes a
-    round trip through host memory."""
-    if dist.get_backend(group) == 'gloo' and inp.is_cuda:
+    """dist.all_gather_into_tensor(out, inp) for 1-D tensors, on either backend (_through_host)."""
+    if _through_host(inp, group):
         host = torch.empty(out.shape, dtype=out.dtype)
         dist.all_gather_into_tensor(host, inp.cpu(), group=group)
         out.copy_(host)
@@ -63,9 +74,9 @@ def merge_topk(scores, idx, k):
 
 def all_gather_topk(local_scores, local_idx, k, group=None):
     """All-gather every rank's per-query local top-k and merge.  local_* are [Q, k_local]."""
-    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+    world = rank_world(group)[1]
+    if world == 1:
         return merge_topk(local_scores, local_idx, k)
-    world = dist.get_world_size(group)
     qn, kl = local_scores.shape
     # one fused buffer per rank: scores as fp32 bits next to int64 indices would need two collectives;
     # pack both into int64 (score bits in the low word) so ONE all_gather moves everything.
@@ -83,8 +94,8 @@ def all_gather_topk_keys(local_keys, k, group=None):
     candidate indices (ops.topk_keys); ONE all-gather, then one merge kernel (ops.topk_merge_keys).
     local_keys int64 [Q, k_local] on the GPU -> (top scores [Q, k], top idx [Q, k])."""
     from . import ops
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
-        world = dist.get_world_size(group)
+    world = rank_world(group)[1]
+    if world > 1:
         gathered = torch.empty((world,) + tuple(local_keys.shape), dtype=local_keys.dtype, device=local_keys.device)
         all_gather_flat(gathered.view(-1), local_keys.contiguous().view(-1), group)
     else:
@@ -103,8 +114,7 @@ class ShardedPoolRanker:
         self.group = group
         self.multiple = multiple
         self.n_total = n_total if presharded else len(pool_reps)
-        self.rank = dist.get_rank(group) if dist.is_initialized() else 0
-        self.world = dist.get_world_size(group) if dist.is_initialized() else 1
+        self.rank, self.world = rank_world(group)
         if presharded:
             self.lo = global_offset
             block = pool_reps
@@ -122,8 +132,7 @@ class ShardedPoolRanker:
         broadcast once: every shard then rounds its rows around the same point."""
         self = cls.__new__(cls)
         self.group, self.multiple, self.n_total = group, multiple, n_total
-        self.rank = dist.get_rank(group) if dist.is_initialized() else 0
-        self.world = dist.get_world_size(group) if dist.is_initialized() else 1
+        self.rank, self.world = rank_world(group)
         self.lo = int(global_offset)
         self.pool = pool          # (its pids stay the caller's; the rankings carry GLOBAL positions lo + i: rank_queries, idx_base)
         if planes:
@@ -146,12 +155,9 @@ class ShardedPoolRanker:
                 mu = torch.zeros(768, device=dev)
             else:
                 mu = torch.empty(768, device=dev)
-            if dist.get_backend(self.group) == 'gloo':
-                host = mu.cpu()
-                dist.broadcast(host, src=dist.get_global_rank(self.group, 0) if self.group is not None else 0, group=self.group)
-                mu = host.to(dev)
-            else:
-                dist.broadcast(mu, src=dist.get_global_rank(self.group, 0) if self.group is not None else 0, group=self.group)
+            host = mu.cpu() if _through_host(mu, self.group) else mu
+            dist.broadcast(host, src=dist.get_global_rank(self.group, 0) if self.group is not None else 0, group=self.group)
+            mu = host.to(dev)
             if self.rank != 0 and len(self.pool) > 0:
                 self.pool.prepare_planes(mu=mu)
         elif len(self.pool) > 0:
@@ -235,9 +241,9 @@ def all_gather_ranked_jobs(local_s, local_i, n_jobs, k, group=None, device=None)
     when the rank's longest pool is shorter than k; None for a rank without jobs or whose pools are all empty).  ONE all-gather of
     [ceil(n_jobs / world), k] int64 per rank (50 jobs x 125 at world 8: 7 KB per rank) -> (scores [n_jobs, k], idx [n_jobs, k]) on every
     rank, jobs in the caller's order, columns beyond a pool's size (-inf, -1)."""
-    dev = device if device is not None else (local_s.device if local_s is not None else ops_device())
-    world = dist.get_world_size(group) if dist.is_initialized() else 1
-    rank = dist.get_rank(group) if dist.is_initialized() else 0
+    from . import ops
+    dev = device if device is not None else (local_s.device if local_s is not None else ops.require_gpu())
+    rank, world = rank_world(group)
     lo, hi = job_bounds(n_jobs, world, rank)
     per = (n_jobs + world - 1) // world if n_jobs else 0
     s = torch.full((per, k), float('-inf'), device=dev, dtype=torch.float32)
@@ -265,19 +271,18 @@ def rank_pools_sharded(query_reps_list, pools, k=None, hparams=None, method='ot'
     `pool_sizes`, the pools' lengths, given on every rank), so a rank uploads only its block's candidates.  Each rank makes one
     aspire_ot_rank_batch_f32 (or aspire_l2max_rank_batch_f32) call; one all-gather exchanges the ranked lists; no merge.
     Returns (scores [J, k], idx [J, k]) on every rank: idx = position in the job's own pool, best first, ties in pool order
-    (evaluate.py:76), (-inf, -1) beyond a pool's size.  k: default the longest pool (full ranking).  ranked_lists_from maps them
+    (evaluate.py:76), (-inf, -1) beyond a pool's size.  k: default the longest pool (full ranking).  scorer.ranked_lists maps them
     to the [(pid, score), ...] lists rank_pools returns."""
-    from . import scorer
+    from . import ops, scorer
     n_jobs = len(pools)
     assert len(query_reps_list) == n_jobs, 'one pool per query'
     sizes = [int(n) for n in pool_sizes] if pool_sizes is not None else [len(p) for p in pools]
     assert len(sizes) == n_jobs
-    world = dist.get_world_size(group) if dist.is_initialized() else 1
-    rank = dist.get_rank(group) if dist.is_initialized() else 0
+    rank, world = rank_world(group)
     max_job = max(sizes) if sizes else 0
     k = max_job if k is None else min(int(k), max_job)
     if n_jobs == 0 or k == 0:
-        dev = ops_device()
+        dev = ops.require_gpu()
         return torch.empty(n_jobs, 0, device=dev), torch.empty(n_jobs, 0, dtype=torch.int64, device=dev)
     lo, hi = job_bounds(n_jobs, world, rank)
     top_s = top_i = None
@@ -285,15 +290,3 @@ def rank_pools_sharded(query_reps_list, pools, k=None, hparams=None, method='ot'
         assert all(len(pools[j]) == sizes[j] for j in range(lo, hi)), 'pool_sizes disagree with this rank\'s pools'
         _, top_s, top_i = scorer._launch_rank_pools(query_reps_list[lo:hi], pools[lo:hi], k, hparams, method, deterministic)
     return all_gather_ranked_jobs(top_s, top_i, n_jobs, k, group)
-
-
-def ops_device():
-    from . import ops
-    return ops.require_gpu()
-
-
-def ranked_lists_from(pids_lists, top_s, top_i):
-    """(scores [J, k], idx [J, k]) of rank_pools_sharded + every job's candidate ids -> per job [(pid, score), ...], as
-    scorer.rank_pools returns them."""
-    top_s, top_i = top_s.cpu().numpy(), top_i.cpu().numpy()
-    return [[(pids[i], float(sc)) for sc, i in zip(rs, ri) if i >= 0] for pids, rs, ri in zip(pids_lists, top_s, top_i)]

@@ -10,13 +10,13 @@ Here a whole candidate pool is scored by ONE launch against sentence reps that s
 two reference loops differ only in how geomloss's epsilon schedule is grouped, which is the
 ``schedule`` argument.
 """
-import ctypes
+import collections
 
 import numpy as np
 import torch
 
 from . import _lib, ops
-from .pair_distances import (rep_len_tup, AllPairMaskedWasserstein, AllPairMaskedAttention, allpair_masked_dist_l2max,
+from .pair_distances import (rep_len_tup, ot_kwargs, AllPairMaskedWasserstein, AllPairMaskedAttention, allpair_masked_dist_l2max,
                              allpair_masked_dist_l2topk)
 
 
@@ -50,11 +50,6 @@ class CandidatePool:
         return self
 
 
-# the dot-product max-sims (cosentbert / ictsentbert, pp_gen_nearest.py rank_pool_sent's score_type names): method -> ASPIRE_SIM_*
-DOT_METHODS = {'cosine': _lib.SIM_COSINE, 'dotlse': _lib.SIM_DOT}
-BATCH_METHODS = ('ot', 'l2max') + tuple(DOT_METHODS)
-
-
 def _as_pool(x):
     return x if isinstance(x, CandidatePool) else CandidatePool(x)
 
@@ -77,11 +72,10 @@ class PoolBatch:
             raise ValueError('a document without sentence rows cannot be scored (the reference raises on it: pair_distances.py:57)')
         job_off = np.concatenate([[0], np.cumsum(self.sizes)]).astype(np.int32)
         meta = torch.from_numpy(np.concatenate([flat_start, flat_len, job_off])).to(dev)
-        self.max_job = max(self.sizes) if self.sizes else 0
         self.job_off = meta[2 * c_total:]
         self.c = ops.DeviceRepSet(rows, meta[:c_total], meta[c_total:2 * c_total], ext=0,
                                   max_len=int(flat_len.max()) if c_total else 0) if c_total else None
-        self._out = {}          # (k, key_form) -> preallocated outputs + workspace of the last call with that k
+        self._out = {}          # (k, method) -> preallocated (scores, top_scores, top_idx) of the calls with that k
 
 
 _WORKSPACE = {}
@@ -98,19 +92,44 @@ def _shared_workspace(dev, nbytes):
     return ws
 
 
+def _batch_call(n_queries, sizes, k, hparams, method, deterministic):
+    """What rank_pool_batch and _launch_rank_pools share ahead of the one library call: the checks, the k clamp and the METHODS
+    row.  Returns (entry, wrapper, kw, max_job, k) for wrapper(q, c, job_off, max_job, k, **kw), `entry` being the wrapper's name for
+    ops.rank_batch_workspace_bytes; max_job == 0: every pool is empty, there is nothing to call."""
+    hparams = hparams or {}
+    row = METHODS.get(method)
+    if row is None or row.batch is None:
+        raise ValueError(f'Unknown aggregation: {method}')
+    ot_kwargs(hparams)          # geoml_reach is rejected whatever the method
+    assert n_queries == len(sizes), 'one pool per query'
+    max_job = max(sizes) if sizes else 0
+    k = max_job if k is None else min(k, max_job)
+    return row.batch(hparams, deterministic) + (max_job, k)
+
+
+def ranked_lists(pids_lists, top_s, top_i, sign=1.0):
+    """(top_scores [J, k], top_idx [J, k]) of a score + rank call + every job's candidate ids -> per job [(pid, sign * score), ...]
+    best first (evaluate.py:77 stores -similarity: sign = -1).  The library pads a job's row with idx -1 from its pool's end on
+    (include/aspire_hip.h), as all_gather_ranked_jobs does: those entries are dropped.  top_s None (every pool empty): empty lists.
+    Two downloads, one multiply for the sign and, for ids kept as an object array (PoolBatch), one fancy index per job; a Python
+    loop over the (pid, score) pairs here was most of the config-4 score step's host time (NOTES, "Host path of the reference-shaped
+    entry").  Ids given as a list are picked entry by entry: k lookups, whatever the pool's size (k = 100 of 50 000)."""
+    if top_s is None:
+        return [[] for _ in pids_lists]
+    top_s, top_i = top_s.cpu().numpy().astype(np.float64) * sign, top_i.cpu().numpy()
+    ranked = []
+    for pids, n, rs, ri in zip(pids_lists, (top_i >= 0).sum(1).tolist(), top_s, top_i):
+        picked = pids[ri[:n]].tolist() if isinstance(pids, np.ndarray) else [pids[i] for i in ri[:n].tolist()]
+        ranked.append(list(zip(picked, rs[:n].tolist())))
+    return ranked
+
+
 def rank_pool_batch(query_reps_list, batch, k=None, hparams=None, method='ot', deterministic=False, sign=1.0):
     """rank_pools on a prepared PoolBatch (RepStore.pool_batch): ONE upload of the queries (rows + index list), one library call,
-    two small downloads.  Returns per query [(pid, sign * score), ...] as rank_pools does (evaluate.py:77 stores -similarity:
-    sign = -1 negates on the way out, one numpy multiply instead of a Python loop over the pairs)."""
-    hparams = hparams or {}
-    if method not in BATCH_METHODS:
-        raise ValueError(f'Unknown aggregation: {method}')
-    if hparams.get('geoml_reach', None) is not None:
-        raise NotImplementedError('unbalanced OT (geoml_reach) is not built')
-    assert len(query_reps_list) == len(batch.sizes), 'one pool per query'
-    if batch.max_job == 0:
+    two small downloads.  Returns per query [(pid, sign * score), ...] as rank_pools does (ranked_lists)."""
+    entry, wrapper, kw, max_job, k = _batch_call(len(query_reps_list), batch.sizes, k, hparams, method, deterministic)
+    if max_job == 0:
         return [[] for _ in batch.sizes]
-    k = batch.max_job if k is None else min(k, batch.max_job)
     dev = batch.c.rows.device
     q_lens = [int(np.shape(r)[0]) for r in query_reps_list]
     if min(q_lens) <= 0:
@@ -120,34 +139,15 @@ def rank_pool_batch(query_reps_list, batch, k=None, hparams=None, method='ot', d
     q_meta = torch.from_numpy(np.concatenate([np.cumsum(q_len_np) - q_len_np, q_len_np]).astype(np.int32)).to(dev)
     j = len(q_lens)
     q = ops.DeviceRepSet(q_rows, q_meta[:j], q_meta[j:], ext=0, max_len=max(q_lens))
-    slot = batch._out.get((k, method))
-    if slot is None:
-        slot = batch._out[(k, method)] = {
-            'out': (torch.empty(batch.c.n, device=dev), torch.empty(j, k, device=dev), torch.empty(j, k, device=dev, dtype=torch.int64)),
-            }
+    out = batch._out.get((k, method))
+    if out is None:
+        out = batch._out[(k, method)] = (torch.empty(batch.c.n, device=dev), torch.empty(j, k, device=dev),
+                                         torch.empty(j, k, device=dev, dtype=torch.int64))
     # the workspace depends on the QUERIES too (longest document of the call: slot size, record count): asked for on every call
     # -- a host-side computation -- and grown when another facet's queries need more than the last call's
-    qs, cs = q.struct(), batch.c.struct()
-    need = (_lib.lib.aspire_l2max_rank_batch_workspace_bytes if method == 'l2max' else
-            _lib.lib.aspire_dotmax_rank_batch_workspace_bytes if method in DOT_METHODS else
-            _lib.lib.aspire_ot_rank_batch_workspace_bytes)(ctypes.byref(qs), ctypes.byref(cs), batch.max_job, k)
-    slot['ws'] = _shared_workspace(dev, need)
-    if method in DOT_METHODS:
-        _, top_s, top_i = ops.dotmax_rank_batch(q, batch.c, batch.job_off, batch.max_job, k, sim=DOT_METHODS[method], out=slot['out'],
-                                                workspace=slot['ws'])
-    elif method == 'l2max':
-        _, top_s, top_i = ops.l2max_rank_batch(q, batch.c, batch.job_off, batch.max_job, k, out=slot['out'], workspace=slot['ws'],
-                                               one_form=deterministic)
-    else:
-        _, top_s, top_i = ops.ot_rank_batch(q, batch.c, batch.job_off, batch.max_job, k, blur=hparams.get('geoml_blur', 0.05),
-                                            scaling=hparams.get('geoml_scaling', 0.9), sent_sm_temp=hparams.get('sent_sm_temp', 1.0),
-                                            want=_lib.OT_SIMILARITY, out=slot['out'], workspace=slot['ws'], one_form=deterministic)
-    top_s, top_i = top_s.cpu().numpy().astype(np.float64) * sign, top_i.cpu().numpy()
-    ranked = []
-    for pids, n, rs, ri in zip(batch.pids, batch.sizes, top_s, top_i):
-        kk = min(k, n)
-        ranked.append(list(zip(pids[ri[:kk]].tolist(), rs[:kk].tolist())))
-    return ranked
+    ws = _shared_workspace(dev, ops.rank_batch_workspace_bytes(entry, q, batch.c, max_job, k))
+    _, top_s, top_i = wrapper(q, batch.c, batch.job_off, max_job, k, out=out, workspace=ws, **kw)
+    return ranked_lists(batch.pids, top_s, top_i, sign)
 
 
 def _cdist_runs(q, c, group):
@@ -197,12 +197,12 @@ def score_pool(query_reps_list, pool, method='ot', schedule='pair', hparams=None
     pool = _as_pool(pool)
     q = ops.DeviceRepSet.from_list(query_reps_list)
     c = pool.repset
-    if method not in ('ot', 'l2max', 'l2top2', 'l2attention') + tuple(DOT_METHODS):
+    if method not in METHODS:
         raise ValueError(f'Unknown aggregation: {method}')
     if schedule not in ('pair', 'batch'):
         raise ValueError(f'Unknown schedule: {schedule}')
-    if method in DOT_METHODS:
-        return ops.dotmax_scores(q, c, pairing=_lib.PAIR_CROSS, sim=DOT_METHODS[method]).view(q.n, c.n)
+    if not METHODS[method].schedule:
+        return METHODS[method].cross(q, c, hparams, _lib.CDIST_AUTO, deterministic, schedule, score_batch_size).view(q.n, c.n)
     # schedule 'pair': one pair per reference call (evaluate.py) -> cdist's formula per pair (AUTO).  'batch': per padded
     # group of score_batch_size candidates (caching_score) -> per group, see _cdist_runs.
     if schedule == 'batch' and q.n > 1 and q.max_len > 25 and c.n > 0:
@@ -218,19 +218,13 @@ def score_pool(query_reps_list, pool, method='ot', schedule='pair', hparams=None
 
 
 def _score_run(q, c, method, schedule, hparams, score_batch_size, cdist_mode, deterministic=False):
-    if deterministic and not (method == 'l2max' or (method == 'ot' and schedule == 'pair')):
+    if deterministic and METHODS[method].deterministic not in ('any', schedule):
         raise ValueError("deterministic=True is built for method 'ot' with schedule 'pair' and for 'l2max'")
-    if method == 'l2max':
-        return ops.l2max_scores(q, c, pairing=_lib.PAIR_CROSS, cdist_mode=cdist_mode, one_form=deterministic).view(q.n, c.n)
-    if method == 'l2top2':
-        return ops.l2agg_scores(q, c, _lib.AGG_TOP2, pairing=_lib.PAIR_CROSS, cdist_mode=cdist_mode).view(q.n, c.n)
-    if method == 'l2attention':
-        return ops.l2agg_scores(q, c, _lib.AGG_ATTENTION, temp=hparams.get('cdatt_sm_temp', 1.0),
-                                pairing=_lib.PAIR_CROSS, cdist_mode=cdist_mode).view(q.n, c.n)
-    kw = dict(blur=hparams.get('geoml_blur', 0.05), scaling=hparams.get('geoml_scaling', 0.9),
-              sent_sm_temp=hparams.get('sent_sm_temp', 1.0), cdist_mode=cdist_mode)
-    if hparams.get('geoml_reach', None) is not None:
-        raise NotImplementedError('unbalanced OT (geoml_reach) is not built')
+    return METHODS[method].cross(q, c, hparams, cdist_mode, deterministic, schedule, score_batch_size).view(q.n, c.n)
+
+
+def _score_ot(q, c, hparams, cdist_mode, deterministic, schedule, score_batch_size):
+    kw = dict(ot_kwargs(hparams), cdist_mode=cdist_mode)
     if schedule == 'pair':
         if 1 < q.n <= 32 and q.max_len <= 8 and 8 < c.max_len <= 32 and c.ext == 0 and c.n >= 256 and not deterministic:
             # a few short queries (the facets of one paper, models.py:127-163) against ONE pool of whole abstracts: as batched jobs
@@ -238,28 +232,75 @@ def _score_run(q, c, method, schedule, hparams, score_batch_size, cdist_mode, de
             # entry would take the Gram tiles + a Sinkhorn launch, built for many queries)
             dev = c.rows.device
             cc = ops.DeviceRepSet(c.rows, c.start.repeat(q.n), c.len.repeat(q.n), ext=0, max_len=c.max_len)
-            qs, cs = q.struct(), cc.struct()
-            need = _lib.lib.aspire_ot_rank_batch_workspace_bytes(ctypes.byref(qs), ctypes.byref(cs), c.n, 0)
+            need = ops.rank_batch_workspace_bytes('ot', q, cc, c.n, 0)
             if need <= (1 << 30):      # (the batched entry reserves pair slots for EVERY candidate: beyond 1 GiB the chunked path below)
                 job_off = (torch.arange(q.n + 1, dtype=torch.int64) * c.n).to(torch.int32).to(dev)
                 sims, _, _ = ops.ot_rank_batch(q, cc, job_off, c.n, 0, want=_lib.OT_SIMILARITY, workspace=_shared_workspace(dev, need), **kw)
-                return sims.view(q.n, c.n)
-        dist = ops.ot_sinkhorn(q, c, pairing=_lib.PAIR_CROSS, want=_lib.OT_DISTANCE, one_form=deterministic, **kw)
-        return (-dist).view(q.n, c.n)
+                return sims
+        return -ops.ot_sinkhorn(q, c, pairing=_lib.PAIR_CROSS, want=_lib.OT_DISTANCE, one_form=deterministic, **kw)
     diam = ops.group_diameter(q, c, _lib.PAIR_CROSS, group=score_batch_size)
-    sims = ops.ot_sinkhorn(q, c, pairing=_lib.PAIR_CROSS, want=_lib.OT_PLAN_SIM, diameter=diam,
-                           diam_group=score_batch_size, **kw)
-    return sims.view(q.n, c.n)
+    return ops.ot_sinkhorn(q, c, pairing=_lib.PAIR_CROSS, want=_lib.OT_PLAN_SIM, diameter=diam, diam_group=score_batch_size, **kw)
+
+
+Method = collections.namedtuple('Method', 'cross batch deterministic schedule sim', defaults=(None,))
+Method.__doc__ = """One aggregation of the host layer; METHODS is the only place that maps a method name to library calls.
+    cross          (q, c, hparams, cdist_mode, deterministic, schedule, score_batch_size) -> scores [Q * C] of every query against
+                   every candidate, higher = more similar: what score_pool calls (per run of _cdist_runs)
+    batch          (hparams, deterministic) -> (entry, ops wrapper, its keyword arguments) of the batched score + rank entry that
+                   rank_pools / rank_pool_batch call as wrapper(q, c, job_off, max_job, k, **kw), `entry` being its key in
+                   ops._RANK_BATCH (the workspace query); None: the method has none
+    deterministic  'any' / 'pair': deterministic=True is accepted under every schedule / under schedule 'pair' only; None: not built
+    schedule       False: `schedule` and `score_batch_size` do not apply (both kernel forms give the same bits for a pair)
+    sim            the ASPIRE_SIM_* of a dot-product max-sim (DOT_METHODS)
+A further batched aggregation is one ops wrapper of a few lines (ops._RANK_BATCH), its entries in _lib.SIGNATURES and one row here."""
+
+
+def _dot_method(sim):
+    """cosentbert / ictsentbert's max-sims (pp_gen_nearest.py rank_pool_sent's score_type names)."""
+    return Method(cross=lambda q, c, *_: ops.dotmax_scores(q, c, pairing=_lib.PAIR_CROSS, sim=sim),
+                  batch=lambda hparams, deterministic: ('dotmax', ops.dotmax_rank_batch, dict(sim=sim)),
+                  deterministic='any', schedule=False, sim=sim)
+
+
+METHODS = {
+    'ot': Method(cross=_score_ot,
+                 batch=lambda hparams, deterministic: ('ot', ops.ot_rank_batch, dict(ot_kwargs(hparams), want=_lib.OT_SIMILARITY,
+                                                                                     one_form=deterministic)),
+                 deterministic='pair', schedule=True),
+    'l2max': Method(cross=lambda q, c, hparams, cdist_mode, deterministic, *_: ops.l2max_scores(
+                        q, c, pairing=_lib.PAIR_CROSS, cdist_mode=cdist_mode, one_form=deterministic),
+                    batch=lambda hparams, deterministic: ('l2max', ops.l2max_rank_batch, dict(one_form=deterministic)),
+                    deterministic='any', schedule=True),
+    'l2top2': Method(cross=lambda q, c, hparams, cdist_mode, *_: ops.l2agg_scores(
+                         q, c, _lib.AGG_TOP2, pairing=_lib.PAIR_CROSS, cdist_mode=cdist_mode),
+                     batch=None, deterministic=None, schedule=True),
+    'l2attention': Method(cross=lambda q, c, hparams, cdist_mode, *_: ops.l2agg_scores(
+                              q, c, _lib.AGG_ATTENTION, temp=hparams.get('cdatt_sm_temp', 1.0), pairing=_lib.PAIR_CROSS,
+                              cdist_mode=cdist_mode),
+                          batch=None, deterministic=None, schedule=True),
+    'cosine': _dot_method(_lib.SIM_COSINE),
+    'dotlse': _dot_method(_lib.SIM_DOT),
+}
+DOT_METHODS = {name: m.sim for name, m in METHODS.items() if m.sim is not None}          # method -> ASPIRE_SIM_*
+BATCH_METHODS = tuple(name for name, m in METHODS.items() if m.batch is not None)
 
 
 def rank_pool(query_reps_list, pool, k=None, method='ot', schedule='pair', hparams=None, score_batch_size=64, deterministic=False):
     """Per query: [(pid, score), ...] best first, ties in pool order (evaluate.py:76).  otAspire goes through ONE
     C-ABI call that scores and ranks (aspire_ot_rank_f32).  deterministic: see score_pool."""
-    if deterministic and not (method in ('l2max',) + tuple(DOT_METHODS) or (method == 'ot' and schedule == 'pair')):
+    return ranked_lists(*_launch_rank_pool(query_reps_list, pool, k, method, schedule, hparams, score_batch_size, deterministic))
+
+
+def _launch_rank_pool(query_reps_list, pool, k=None, method='ot', schedule='pair', hparams=None, score_batch_size=64,
+                      deterministic=False):
+    """The uploads and library calls of rank_pool; returns (the pool's ids once per query, top_scores, top_idx) for ranked_lists
+    (None for the tensors when the pool is empty)."""
+    if deterministic and (method not in METHODS or METHODS[method].deterministic not in ('any', schedule)):
         raise ValueError("deterministic=True is built for method 'ot' with schedule 'pair' and for 'l2max'")
     pool = _as_pool(pool)
+    pids_lists = [pool.pids] * len(query_reps_list)
     if len(pool) == 0:
-        return [[] for _ in query_reps_list]
+        return pids_lists, None, None
     k = len(pool) if k is None else min(k, len(pool))
     q = ops.DeviceRepSet.from_list(query_reps_list)
     # one fused score + rank call unless caching_score's per-group cdist formula differs between groups (documents of more
@@ -267,11 +308,7 @@ def rank_pool(query_reps_list, pool, k=None, method='ot', schedule='pair', hpara
     one_call = method == 'ot' and (schedule == 'pair' or (schedule == 'batch' and (
         q.max_len <= 25 or q.n == 1) and len(_cdist_runs(q, pool.repset, score_batch_size)) == 1))
     if one_call:
-        hparams = hparams or {}
-        if hparams.get('geoml_reach', None) is not None:
-            raise NotImplementedError('unbalanced OT (geoml_reach) is not built')
-        kw = dict(blur=hparams.get('geoml_blur', 0.05), scaling=hparams.get('geoml_scaling', 0.9),
-                  sent_sm_temp=hparams.get('sent_sm_temp', 1.0))
+        kw = ot_kwargs(hparams or {})
         if schedule == 'pair':
             _, top_s, top_i = ops.ot_rank(q, pool.repset, k, want=_lib.OT_SIMILARITY, one_form=deterministic, **kw)
         else:
@@ -283,25 +320,18 @@ def rank_pool(query_reps_list, pool, k=None, method='ot', schedule='pair', hpara
         scores = score_pool(query_reps_list, pool, method=method, schedule=schedule, hparams=hparams,
                             score_batch_size=score_batch_size, deterministic=deterministic)
         top_s, top_i = ops.topk_desc(scores.contiguous(), k)
-    top_s, top_i = top_s.cpu().numpy(), top_i.cpu().numpy()
-    return [[(pool.pids[i], float(s)) for s, i in zip(rs, ri) if i >= 0] for rs, ri in zip(top_s, top_i)]
+    return pids_lists, top_s, top_i
 
 
 def _launch_rank_pools(query_reps_list, pools, k, hparams, method='ot', deterministic=False):
-    """Uploads + the one library call of rank_pools on the CURRENT stream; returns (pools, top_scores, top_idx) GPU tensors
-    (None for the tensors when every pool is empty)."""
-    hparams = hparams or {}
-    if method not in BATCH_METHODS:
-        raise ValueError(f'Unknown aggregation: {method}')
-    if hparams.get('geoml_reach', None) is not None:
-        raise NotImplementedError('unbalanced OT (geoml_reach) is not built')
-    assert len(query_reps_list) == len(pools), 'one pool per query'
-    pools = [_as_pool(p) for p in pools]
+    """Uploads + the one library call of rank_pools on the CURRENT stream; returns (every pool's ids, top_scores, top_idx) for
+    ranked_lists, the tensors on the GPU (None when every pool is empty)."""
     sizes = [len(p) for p in pools]
-    max_job = max(sizes) if sizes else 0
+    _, wrapper, kw, max_job, k = _batch_call(len(query_reps_list), sizes, k, hparams, method, deterministic)
+    pools = [_as_pool(p) for p in pools]
+    pids_lists = [p.pids for p in pools]
     if max_job == 0:
-        return pools, None, None
-    k = max_job if k is None else min(k, max_job)
+        return pids_lists, None, None
     dev = ops.require_gpu()
     q = ops.DeviceRepSet.from_list(query_reps_list)
     nonempty = [p.repset for p in pools if len(p)]
@@ -324,23 +354,8 @@ def _launch_rank_pools(query_reps_list, pools, k, hparams, method='ot', determin
                              torch.cat([r.start + int(b) for r, b in zip(nonempty, bases)]).to(torch.int32).contiguous(),
                              torch.cat([r.len for r in nonempty]).contiguous(), ext=0, max_len=max(r.max_len for r in nonempty))
     job_off = torch.tensor(np.concatenate([[0], np.cumsum(sizes)]), dtype=torch.int32, device=dev)
-    if method in DOT_METHODS:
-        _, top_s, top_i = ops.dotmax_rank_batch(q, c, job_off, max_job, k, sim=DOT_METHODS[method])
-        return pools, top_s, top_i
-    if method == 'l2max':
-        _, top_s, top_i = ops.l2max_rank_batch(q, c, job_off, max_job, k, one_form=deterministic)
-        return pools, top_s, top_i
-    _, top_s, top_i = ops.ot_rank_batch(q, c, job_off, max_job, k, blur=hparams.get('geoml_blur', 0.05),
-                                        scaling=hparams.get('geoml_scaling', 0.9), sent_sm_temp=hparams.get('sent_sm_temp', 1.0),
-                                        want=_lib.OT_SIMILARITY, one_form=deterministic)
-    return pools, top_s, top_i
-
-
-def _ranked_lists(pools, top_s, top_i):
-    if top_s is None:
-        return [[] for _ in pools]
-    top_s, top_i = top_s.cpu().numpy(), top_i.cpu().numpy()
-    return [[(p.pids[i], float(sc)) for sc, i in zip(rs, ri) if i >= 0] for p, rs, ri in zip(pools, top_s, top_i)]
+    _, top_s, top_i = wrapper(q, c, job_off, max_job, k, **kw)
+    return pids_lists, top_s, top_i
 
 
 def rank_pools(query_reps_list, pools, k=None, hparams=None, method='ot', deterministic=False):
@@ -353,7 +368,7 @@ def rank_pools(query_reps_list, pools, k=None, hparams=None, method='ot', determ
     same order as rank_pool(..., deterministic=True) query by query (see score_pool)."""
     if not pools:
         return []
-    return _ranked_lists(*_launch_rank_pools(query_reps_list, pools, k, hparams, method, deterministic))
+    return ranked_lists(*_launch_rank_pools(query_reps_list, pools, k, hparams, method, deterministic))
 
 
 class InFlightRanker:
@@ -388,7 +403,7 @@ class InFlightRanker:
     def result(self, ticket):
         ticket['done'].synchronize()
         with torch.cuda.stream(self.lanes[ticket['lane']]):
-            return _ranked_lists(*ticket['out'])
+            return ranked_lists(*ticket['out'])
 
 
 def get_similarity(x, y, hparams=None):
