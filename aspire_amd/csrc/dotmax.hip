@@ -24,25 +24,10 @@
 
 #include "common.h"
 #include "batch_host.h"
+#include "dot_tiles.h"
 
 namespace aspire {
-int generic_max_rows(void);
-
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kModeCross = 0, kModePaired = 1, kModeMapped = 2;
-constexpr int kXRows = 32;              // candidate row slots per cross workgroup
-constexpr int kXStride = kD + 4;        // LDS row stride (floats): rows 16 B apart in the banks
-
-struct DotSet {
-    const float* rows;
-    const int32_t* start;
-    const int32_t* len;
-    int64_t n;
-    int32_t bound;      // host-known upper bound of len[] (ext, or max_len): a longer document scores NaN
-};
 
 struct DotArgs {
     DotSet q, c;
@@ -54,8 +39,6 @@ struct DotArgs {
     float* scores;
 };
 
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-
 // sklearn's row norm: sqrt of the fp32 sum of squares, near-zero -> 1
 __device__ __forceinline__ float row_norm(float ss) {
     const float n = sqrtf(ss);
@@ -66,22 +49,6 @@ __device__ __forceinline__ float finish(float dot, float nq, float nc, int sim) 
     if (sim == ASPIRE_SIM_DOT) return dot;
     if (isinf(nq) || isinf(nc)) return 0.0f;      // x / inf = 0 row: no inf / inf
     return dot / nq / nc;
-}
-
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-// eight k values of one row against eight of one column into acc[0..3] (k = e spread over the four accumulators)
-__device__ __forceinline__ void mfma8(const f32x4& a0, const f32x4& a1, const f32x4& b0, const f32x4& b1, f32x4 (&acc)[4]) {
-    acc[0] = mfma4(a0.x, b0.x, acc[0]);
-    acc[1] = mfma4(a0.y, b0.y, acc[1]);
-    acc[2] = mfma4(a0.z, b0.z, acc[2]);
-    acc[3] = mfma4(a0.w, b0.w, acc[3]);
-    acc[0] = mfma4(a1.x, b1.x, acc[0]);
-    acc[1] = mfma4(a1.y, b1.y, acc[1]);
-    acc[2] = mfma4(a1.z, b1.z, acc[2]);
-    acc[3] = mfma4(a1.w, b1.w, acc[3]);
 }
 
 __device__ __forceinline__ float sumsq8(float ss, const f32x4& x0, const f32x4& x1) {
@@ -99,16 +66,6 @@ __device__ __forceinline__ float sumsq8(float ss, const f32x4& x0, const f32x4& 
 __device__ __forceinline__ float rowgroup_sum(float v) {
     v += lane_xor<16>(v);
     return v + lane_xor<32>(v);
-}
-
-// job of candidate p: the last j with job_off[j] <= p (empty jobs skipped)
-__device__ __forceinline__ int32_t job_of(const int32_t* __restrict__ job_off, int32_t J, int64_t p) {
-    int32_t lo = 0, hi = J;          // invariant: job_off[lo] <= p < job_off[hi]
-    while (hi - lo > 1) {
-        const int32_t mid = (lo + hi) >> 1;
-        if (job_off[mid] <= p) lo = mid; else hi = mid;
-    }
-    return lo;
 }
 
 // ---- one wave per pair --------------------------------------------------------------------------------------------------
@@ -260,35 +217,6 @@ __global__ void __launch_bounds__(256) dotmax_cross_kernel(DotArgs a) {
             }
         }
     }
-}
-
-int log2_slots(int rows) {
-    int l = 0;
-    while ((1 << l) < rows) ++l;
-    return l;
-}
-
-DotSet to_dot(const aspire_repset* s) {
-    return DotSet{s->rows, s->start, s->len, s->n, s->ext > 0 ? s->ext : s->max_len};
-}
-
-int check_dot_sets(const aspire_repset* q, const aspire_repset* c, int64_t D, int pairing, int sim) {
-    ASPIRE_REQUIRE(q && c, ASPIRE_ERR_INVALID_ARG, "null repset");
-    ASPIRE_REQUIRE(D == kD, ASPIRE_ERR_UNSUPPORTED, "encoding dim %lld unsupported (kernels are built for 768)", (long long)D);
-    ASPIRE_REQUIRE(pairing == ASPIRE_PAIR_CROSS || pairing == ASPIRE_PAIR_PAIRED, ASPIRE_ERR_INVALID_ARG, "bad pairing %d", pairing);
-    ASPIRE_REQUIRE(sim == ASPIRE_SIM_COSINE || sim == ASPIRE_SIM_DOT, ASPIRE_ERR_INVALID_ARG, "bad similarity %d", sim);
-    ASPIRE_REQUIRE(q->n >= 0 && c->n >= 0, ASPIRE_ERR_INVALID_ARG, "negative document count");
-    ASPIRE_REQUIRE(pairing != ASPIRE_PAIR_PAIRED || q->n == c->n, ASPIRE_ERR_INVALID_ARG,
-                   "paired scoring needs equal batch sizes (query %lld vs cand %lld)", (long long)q->n, (long long)c->n);
-    ASPIRE_REQUIRE(q->ext >= 0 && c->ext >= 0 && q->max_len >= 0 && c->max_len >= 0, ASPIRE_ERR_INVALID_ARG, "negative ext / max_len");
-    const int bq = to_dot(q).bound, bc = to_dot(c).bound;
-    ASPIRE_REQUIRE(bq <= generic_max_rows() && bc <= generic_max_rows(), ASPIRE_ERR_UNSUPPORTED,
-                   "documents with more than %d sentence rows are not supported (got %d x %d)", generic_max_rows(), bq, bc);
-    if (q->n == 0 || c->n == 0) return ASPIRE_OK;
-    ASPIRE_REQUIRE(q->rows && q->start && q->len && c->rows && c->start && c->len, ASPIRE_ERR_INVALID_ARG, "null rows / start / len");
-    ASPIRE_REQUIRE(((uintptr_t)q->rows & 15) == 0 && ((uintptr_t)c->rows & 15) == 0, ASPIRE_ERR_INVALID_ARG,
-                   "rows must be 16-byte aligned");
-    return ASPIRE_OK;
 }
 
 int launch_pairs(const DotArgs& a, int64_t P, hipStream_t s) {

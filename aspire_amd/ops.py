@@ -502,14 +502,36 @@ def dotmax_rank_batch(q, c, job_off, max_job, k, sim=_lib.SIM_COSINE, out=None, 
     return _rank_batch('dotmax', lambda: (sim,), q, c, job_off, max_job, k, out, workspace, job_base, key_form)
 
 
+def jointsm_scores(q, c, pairing=_lib.PAIR_CROSS, want_pair_softmax=False):
+    """A14 (pair_distances.py:348-402 as WordSentAlignPolyEnc.score negates it back, disent_models.py:905-906): sims [P] =
+    2 sum_ij p_ij <q_i, c_j> with p the soft-max of the scaled dot products over the pair's whole valid block.  With
+    want_pair_softmax (padded rep sets) also pair_softmax [P, q.ext, c.ext]: p inside the valid block, 0.0 outside."""
+    _dot_ready(q, c)
+    p = _npairs(q, c, pairing)
+    dev = q.rows.device
+    scores = torch.empty(p, device=dev, dtype=torch.float32)
+    soft = torch.empty(p, q.ext, c.ext, device=dev, dtype=torch.float32) if want_pair_softmax else None
+    qs, cs = q.struct(), c.struct()
+    check(lib.aspire_jointsm_scores_f32(ctypes.byref(qs), ctypes.byref(cs), D, pairing, _ptr(scores), _ptr(soft), _stream()))
+    return (scores, soft) if want_pair_softmax else scores
+
+
+def jointsm_rank_batch(q, c, job_off, max_job, k, out=None, workspace=None, job_base=None, key_form=False):
+    """The joint soft-max alignment score over J independent (query, pool) jobs in ONE call (include/aspire_hip.h:
+    aspire_jointsm_rank_batch_f32); arguments and returns as l2max_rank_batch."""
+    _dot_ready(q, c)
+    return _rank_batch('jointsm', lambda: (), q, c, job_off, max_job, k, out, workspace, job_base, key_form)
+
+
 # <entry>_rank_batch -> (its library entry, that entry's workspace query)
 _RANK_BATCH = {'ot': (lib.aspire_ot_rank_batch_f32, lib.aspire_ot_rank_batch_workspace_bytes),
                'l2max': (lib.aspire_l2max_rank_batch_f32, lib.aspire_l2max_rank_batch_workspace_bytes),
-               'dotmax': (lib.aspire_dotmax_rank_batch_f32, lib.aspire_dotmax_rank_batch_workspace_bytes)}
+               'dotmax': (lib.aspire_dotmax_rank_batch_f32, lib.aspire_dotmax_rank_batch_workspace_bytes),
+               'jointsm': (lib.aspire_jointsm_rank_batch_f32, lib.aspire_jointsm_rank_batch_workspace_bytes)}
 
 
 def rank_batch_workspace_bytes(entry, q, c, max_job, k):
-    """Bytes of `workspace` that <entry>_rank_batch (entry 'ot', 'l2max' or 'dotmax') needs for these sets: a host-side
+    """Bytes of `workspace` that <entry>_rank_batch (entry 'ot', 'l2max', 'dotmax' or 'jointsm') needs for these sets: a host-side
     computation, for callers that keep one buffer over many calls."""
     qs, cs = q.struct(), c.struct()
     return _RANK_BATCH[entry][1](ctypes.byref(qs), ctypes.byref(cs), max_job, k)

@@ -2,7 +2,7 @@
 meaning and error behaviour; the arithmetic runs in libaspire_hip.so on the GPU.
 
 Reference: src/learning/facetid_models/pair_distances.py (AllPairMaskedWasserstein :14-92,
-allpair_masked_dist_l2max :138-186); copy at examples/ex_aspire_consent_multimatch.py:111-189.
+allpair_masked_dist_l2max :138-186, allpair_joint_sm_negscore :348-402); copy at examples/ex_aspire_consent_multimatch.py:111-189.
 
 Inputs may live on the CPU (as in the reference's examples) or on the GPU; outputs come back on the
 device of ``query.embed``.  There is no CPU code path: without a GPU these raise.
@@ -104,3 +104,15 @@ class AllPairMaskedAttention:
             sims, pair, soft = ops.l2agg_scores(q, c, _lib.AGG_ATTENTION, want_pair_sims=True, **kw)
             return sims.to(out_dev), [t.to(out_dev) for t in (pair, soft, soft * pair)]
         return (-1 * ops.l2agg_scores(q, c, _lib.AGG_ATTENTION, **kw)).to(out_dev)
+
+
+def allpair_joint_sm_negscore(query, cand, return_pair_sims=False):
+    """pair_distances.py:348-402 (score_aggregation 'jointsm'): the query's and the candidate's sentences re-expressed through the
+    joint soft-max of their scaled dot products, the dot similarities to the aligned reps summed -- 2 sum_ij p_ij <q_i, c_j>.
+    :return: a distance [batch_size] (minus that sum: "because the optimizer calls for it"), or with return_pair_sims
+        (distance, pair_sm [batch_size, q_max_sents, c_max_sents]: the soft-max, 0.0 outside a pair's valid block)."""
+    q, c, out_dev = _to_repsets(query, cand)
+    if return_pair_sims:
+        sims, pair_sm = ops.jointsm_scores(q, c, pairing=_lib.PAIR_PAIRED, want_pair_softmax=True)
+        return (-1.0 * sims).to(out_dev), pair_sm.to(out_dev)
+    return (-1.0 * ops.jointsm_scores(q, c, pairing=_lib.PAIR_PAIRED)).to(out_dev)

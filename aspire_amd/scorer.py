@@ -176,7 +176,7 @@ def _cdist_runs(q, c, group):
 def score_pool(query_reps_list, pool, method='ot', schedule='pair', hparams=None, score_batch_size=64, deterministic=False):
     """Scores [Q, C] (GPU tensor, higher = more similar) of every query against every candidate.
 
-    deterministic ('ot' with the per-pair schedule, 'l2max'; 'cosine' and 'dotlse' always are): every pair through ONE kernel form (include/aspire_hip.h:
+    deterministic ('ot' with the per-pair schedule, 'l2max', 'jointsm'; 'cosine' and 'dotlse' always are): every pair through ONE kernel form (include/aspire_hip.h:
     ASPIRE_OT_FLAG_ONE_FORM), so that a pair's score -- and with it the order of near-ties -- does not depend on the size of
     the call it is scored in: score_pool / rank_pool per query and rank_pools over all queries then agree bit for bit.
     Several times slower than the default, which picks the kernel family by grid size (scores a few 1e-5 apart).
@@ -192,6 +192,9 @@ def score_pool(query_reps_list, pool, method='ot', schedule='pair', hparams=None
                       (TrainedSentModel.get_similarity, models.py:602-604).  'dotlse': the same max over raw dot products
                       (pp_gen_nearest.py rank_pool_sent).  Both kernel forms give the same bits for a pair; `schedule` and
                       `score_batch_size` do not apply.
+             'jointsm' miswordpolyenc: the joint soft-max alignment score of WordSentAlignPolyEnc.score (disent_models.py:877-925;
+                      pair_distances.py:348-402).  Per pair, so `schedule` and `score_batch_size` do not apply either; its two
+                      kernel forms agree to rounding, deterministic=True takes one of them for every call.
     """
     hparams = hparams or {}
     pool = _as_pool(pool)
@@ -250,9 +253,21 @@ Method.__doc__ = """One aggregation of the host layer; METHODS is the only place
                    rank_pools / rank_pool_batch call as wrapper(q, c, job_off, max_job, k, **kw), `entry` being its key in
                    ops._RANK_BATCH (the workspace query); None: the method has none
     deterministic  'any' / 'pair': deterministic=True is accepted under every schedule / under schedule 'pair' only; None: not built
-    schedule       False: `schedule` and `score_batch_size` do not apply (both kernel forms give the same bits for a pair)
+    schedule       False: `schedule` and `score_batch_size` do not apply (a pair's score depends on its two documents only: both
+                   kernel forms give the same bits for a pair -- 'jointsm': the same value to rounding, see _score_jointsm)
     sim            the ASPIRE_SIM_* of a dot-product max-sim (DOT_METHODS)
 A further batched aggregation is one ops wrapper of a few lines (ops._RANK_BATCH), its entries in _lib.SIGNATURES and one row here."""
+
+
+def _score_jointsm(q, c, hparams, cdist_mode, deterministic, *_):
+    """miswordpolyenc's joint soft-max alignment (WordSentAlignPolyEnc.score, disent_models.py:877-925).  Its two kernel forms
+    agree to rounding, not in every bit, so deterministic goes through the batched entry's one-wave-per-pair form (every query a job
+    over the same index list, k = 0: scores only) -- the bits rank_pools gives, whatever the size of the call."""
+    if not deterministic or q.n == 0 or c.n == 0 or c.ext or q.ext:
+        return ops.jointsm_scores(q, c, pairing=_lib.PAIR_CROSS)
+    cc = ops.DeviceRepSet(c.rows, c.start.repeat(q.n), c.len.repeat(q.n), ext=0, max_len=c.max_len)
+    job_off = (torch.arange(q.n + 1, dtype=torch.int64) * c.n).to(torch.int32).to(c.rows.device)
+    return ops.jointsm_rank_batch(q, cc, job_off, c.n, 0)[0]
 
 
 def _dot_method(sim):
@@ -280,6 +295,8 @@ METHODS = {
                           batch=None, deterministic=None, schedule=True),
     'cosine': _dot_method(_lib.SIM_COSINE),
     'dotlse': _dot_method(_lib.SIM_DOT),
+    'jointsm': Method(cross=_score_jointsm, batch=lambda hparams, deterministic: ('jointsm', ops.jointsm_rank_batch, {}),
+                      deterministic='any', schedule=False),
 }
 DOT_METHODS = {name: m.sim for name, m in METHODS.items() if m.sim is not None}          # method -> ASPIRE_SIM_*
 BATCH_METHODS = tuple(name for name, m in METHODS.items() if m.batch is not None)

@@ -14,6 +14,7 @@ implementation so that shapes propagate under FakeTensor / torch.compile tracing
     torch.ops.aspire.ot_sinkhorn_scores(q, q_lens, c, c_lens, blur, scaling, temp, group, want, paired, extras)
                                          -> (scores, q_distr, c_distr, pair_sims, plan)           A5-A8 pair_distances.py:21-92
     torch.ops.aspire.dotmax_scores(q, q_lens, c, c_lens, paired, cosine) -> scores                A13  models.py:602-604
+    torch.ops.aspire.jointsm_scores(q, q_lens, c, c_lens, paired) -> scores                       A14  pair_distances.py:348-402
     torch.ops.aspire.topk_desc(scores, k, idx_base) -> (top_scores, top_idx)                       A12  evaluate.py:76
     torch.ops.aspire.topk_keys(scores, k, idx_base) -> keys          } the shard merge of section 8(e): local top-k in key
     torch.ops.aspire.topk_merge(gathered_keys, k) -> (top_scores, top_idx)  } form, (all-gather by the caller), merge
@@ -154,6 +155,18 @@ def _(q, q_lens, c, c_lens, paired, cosine):
     return q.new_empty(_npairs(q.shape[0], c.shape[0], paired))
 
 
+# the joint soft-max alignment similarity (WordSentAlignPolyEnc.score's batch_scores: minus allpair_joint_sm_negscore)
+@torch.library.custom_op('aspire::jointsm_scores', mutates_args=(), device_types='cuda')
+def jointsm_scores(q: Tensor, q_lens: Tensor, c: Tensor, c_lens: Tensor, paired: bool) -> Tensor:
+    return ops.jointsm_scores(_padded_repset(q, q_lens), _padded_repset(c, c_lens),
+                              pairing=_lib.PAIR_PAIRED if paired else _lib.PAIR_CROSS)
+
+
+@jointsm_scores.register_fake
+def _(q, q_lens, c, c_lens, paired):
+    return q.new_empty(_npairs(q.shape[0], c.shape[0], paired))
+
+
 # group: 0 = one epsilon schedule per pair (models.py:190-197); n > 0 = one per consecutive group of n candidates
 # (caching_score's padded batches, pp_gen_nearest.py:182-196; paired: one per n pairs).  want: 0 distance, 1 plan-weighted
 # similarity, 2 -distance.  extras: also return query_distr, cand_distr, pair_sims, transport plan (else empty tensors).
@@ -252,5 +265,5 @@ def _(q_rows, q_start, q_len, q_max, c_rows, c_start, c_len, c_max, job_off, max
     return (q_rows.new_empty(c_start.shape[0]), q_rows.new_empty(j, k), q_rows.new_empty(j, k, dtype=torch.int64))
 
 
-OPS = ('span_mean_pool', 'span_pool_ranges', 'bert_encoder_forward', 'bert_cls_forward', 'l2max_scores', 'ot_sinkhorn_scores', 'topk_desc', 'topk_keys', 'topk_merge',
+OPS = ('span_mean_pool', 'span_pool_ranges', 'bert_encoder_forward', 'bert_cls_forward', 'l2max_scores', 'jointsm_scores', 'ot_sinkhorn_scores', 'topk_desc', 'topk_keys', 'topk_merge',
        'l2max_scores_csr', 'ot_scores_csr', 'ot_rank_batch')

@@ -472,6 +472,36 @@ int aspire_dotmax_rank_batch_f32(const aspire_repset* q, const aspire_repset* c,
                                  size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * A14  miswordpolyenc joint soft-max alignment ('jointsm').  Replaces pair_distances.allpair_joint_sm_negscore,
+ * src/learning/facetid_models/pair_distances.py:348-402 with the mask of models_common/activations.py:35-61, as
+ * WordSentAlignPolyEnc.score calls it (disent_models.py:877-925) under TrainedScoringModel.predict and its ranking callers
+ * (src/pre_process/pp_gen_nearest.py:36-87, :366-466).
+ *   scores [P] out: the SIMILARITY 2 * sum_ij p_ij d_ij with d_ij = <q_i, c_j> and p = the soft-max of d_ij / sqrtf(768) over
+ *                   ALL valid (i < q_len, j < c_len) of the pair jointly -- what the reference forms as
+ *                   sum_i <q_i, sum_j p_ij c_j> + sum_j <c_j, sum_i p_ij q_i> (allpair_joint_sm_negscore returns its negation,
+ *                   score() negates back).  P, pairing, CSR / padded rep sets, the 128-row limit and NaN for a document
+ *                   longer than its host bound (ext, or max_len) as aspire_dotmax_scores_f32; D must be 768.  The planes and
+ *                   doc_box fields are ignored.  A pair's score depends on its two documents only: no schedule, no cdist mode.
+ *   pair_softmax    NULL, or [P, q.ext, c.ext] out (padded rep sets only: ext > 0 on both): p_ij inside the valid block, exactly
+ *                   0.0f outside it (the reference's pair_sm); NaN throughout for a document longer than its bound.
+ *   Exact fp32 matrix products (v_mfma_f32_16x16x4_f32) as A13; the soft-max is shifted by the running maximum of the block and
+ *   the similarity block is never written unless pair_softmax is asked for.  CROSS calls on documents of <= 16 rows take a
+ *   kernel that keeps candidate rows in LDS; every other call one wave per pair.  The two sum the soft-max in different orders:
+ *   a pair's score agrees between them to rounding, not bit for bit.
+ *   aspire_jointsm_rank_batch_f32 is the per-query loop of pp_gen_nearest.py:412-456 over J (query, pool) jobs (scores [C], then
+ *   each pool's stable descending rank, :450) with exactly the job_off / max_job / job_base / k / top_scores / top_idx / keys /
+ *   workspace contract of aspire_dotmax_rank_batch_f32; its scores are the bits aspire_jointsm_scores_f32 gives the same pairs
+ *   PAIRED.  Workspace: aspire_jointsm_rank_batch_workspace_bytes(q, c, max_job, k) bytes, 16-byte aligned (0 for pools of <= 4096).
+ * ------------------------------------------------------------------------------------------- */
+int aspire_jointsm_scores_f32(const aspire_repset* q, const aspire_repset* c, int64_t D, int pairing, float* scores,
+                              float* pair_softmax, void* stream);
+size_t aspire_jointsm_rank_batch_workspace_bytes(const aspire_repset* q, const aspire_repset* c, int64_t max_job, int64_t k);
+int aspire_jointsm_rank_batch_f32(const aspire_repset* q, const aspire_repset* c, int64_t D, const int32_t* job_off,
+                                  int64_t max_job, float* scores, int64_t k, const int32_t* job_base,
+                                  float* top_scores, int64_t* top_idx, uint64_t* keys, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * SURVEY.md 8(e)  shard merge.  The same rank in KEY form for the candidate-pool shards of a multi-GPU job:
  *   aspire_topk_keys_f32    per-query local top-k as sortable 64-bit keys [Q, k]:
  *                           (order-preserving score bits << 32) | (0xFFFFFFFF - global index), 0 = padding.
