@@ -1,6 +1,6 @@
 // otAspire throughput kernel: pairwise sentence costs AND the Sinkhorn solve of a pair in ONE launch, nothing handed over
 // through HBM (A5-A8; reference arithmetic: src/learning/facetid_models/pair_distances.py:21-92 + geomloss 0.2.4's
-// sinkhorn_tensorized, restated -- see score.hip).
+// sinkhorn_tensorized, restated -- see sinkhorn.hip).
 //
 // Why fused.  For few queries per candidate the cost stage is HBM bound (24.6 KB of candidate rows per pair, 98 K flop)
 // and the Sinkhorn stage is VALU / transcendental bound (~80 epsilon steps on an 8 x 8 problem).  As two kernels they
@@ -26,7 +26,7 @@
 //     two row_ror DPP adds, both inside a DPP row of 16 lanes; four solves per wave, every pair on its own epsilon schedule
 //     (the loop runs to the longest of the four, finished pairs idle with h = 0).  One exponential per entry and step,
 //     K_ij = 2^((f_i + g_j - C_ij) log2e / eps), weights as plain factors, f_i -= h log2(sum_j b_j K_ij) (see
-//     sinkhorn_block_kernel in score.hip for the derivation).  A sum that leaves fp32 range (extreme scaling, never at the
+//     sinkhorn_block_kernel in sinkhorn.hip for the derivation).  A sum that leaves fp32 range (extreme scaling, never at the
 //     reference's hyper-parameters) poisons the pair's score with NaN; with such hyper-parameters the launcher follows up
 //     with the long-form kernel (generic.hip: max-shifted log-sum-exps), which re-solves exactly the NaN pairs.
 #include <math.h>
@@ -73,7 +73,7 @@ static __device__ long long* g_fdbg = nullptr;
 // CHUNK (batched jobs whose candidates reach 9 .. 32 rows, queries of <= 8: config 4's facet-selected queries against whole
 // abstracts -- pp_settings.py:2-3, models.py:127-163): an item's four 16-lane groups hold four 8-row CHUNKS instead of four
 // candidates -- four candidates of <= 8 rows, two of 9 .. 16 (two chunks each) or one of 17 .. 32 (four); chunk_prep_kernel
-// (score.hip) sorts a job's candidates into such items.  The streaming phase is the same (a group stages rows row0 .. row0 + 7
+// (batch_prep.hip) sorts a job's candidates into such items.  The streaming phase is the same (a group stages rows row0 .. row0 + 7
 // of its document; the candidate's per-coordinate box is joined across its groups), the solve's row sums and the marginals'
 // normalisations cross the candidate's groups (xg_sum / xg_max).
 // (-DASPIRE_FUSED_WAVES3: the experiment of NOTES.md -- the same kernel built for three workgroups per CU, 168 registers: the

@@ -3,7 +3,7 @@
 // The reference has no sentence-count limit, only the 500-word-piece cap (examples/ex_aspire_consent.py:120, 142-155), and
 // AspireNER appends entity "sentences" to an abstract (src/evaluation/utils/models.py:224-233), so an evaluation pool can
 // hold the odd document of 40 or 60 rows.  Such pairs are rare: this kernel favours being obviously right over being
-// fast -- geomloss 0.2.4's own formulation (sinkhorn_tensorized restated, see score.hip): log-weights in the exponent,
+// fast -- geomloss 0.2.4's own formulation (sinkhorn_tensorized restated, see sinkhorn.hip): log-weights in the exponent,
 // max-shifted log-sum-exps, the float64 epsilon schedule exactly as numpy builds it, expf / logf from libm.
 //   * the regular kernels run first and leave NaN for a pair that holds a document longer than their tile; this kernel is
 //     then launched over ALL pairs and a workgroup returns at once unless its pair is one of those (`skip_up_to`);

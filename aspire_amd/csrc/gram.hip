@@ -3,10 +3,10 @@
 // Reference arithmetic: src/learning/facetid_models/pair_distances.py:48-55 (torch.cdist of every query
 // sentence against every candidate sentence) and geomloss 0.2.4's squared_distances (|x|^2 - 2 x.y + |y|^2).
 //
-// With one query the cost stage streams every candidate row once and is HBM bound (score.hip: pair_tile_kernel).
+// With one query the cost stage streams every candidate row once and is HBM bound (cost_valu.hip: pair_tile_kernel).
 // With Q queries each candidate row meets Q * S_q query rows and the stage is 2 * 768 flops per (row, row) entry:
 // at 32 queries x 8 sentences that is 128 flop per candidate byte, far on the compute side of the ridge, and the
-// VALU kernels of score.hip top out near 20 T entries*coords/s.  The x.y term IS a GEMM (fp32 in, fp32 out), so
+// VALU kernels of cost_valu.hip top out near 20 T entries*coords/s.  The x.y term IS a GEMM (fp32 in, fp32 out), so
 // here it runs on v_mfma_f32_32x32x2_f32 -- exact fp32 multiply-adds, 4x the VALU rate -- and the epilogue turns the
 // Gram tile into the two distance forms.  torch.cdist's direct (x - y)^2 formula (used by the reference below 26
 // rows) is reproduced to ~1e-5 by the expansion except where x ~ y (cancellation); those entries -- squared distance

@@ -1,4 +1,4 @@
-// Small device helpers shared by the scoring kernels (score.hip, fused.hip).
+// Small device helpers shared by the scoring kernels (cost_valu.hip, sinkhorn.hip, batch_prep.hip, fused.hip).
 #pragma once
 #include "score_types.h"
 

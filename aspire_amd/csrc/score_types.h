@@ -1,5 +1,8 @@
-// Device-side argument structs shared by the scoring kernels (score.hip, gram.hip).
+// What the scoring units share: the device-side argument structs of the kernels, the constants kernels and host agree on, and the
+// host launchers each kernel family's unit offers to the dispatch in score.hip (one comment line names the unit).
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace aspire {
@@ -73,6 +76,11 @@ struct ScoreArgs {
     long long* dbg;  // phase cycle stamps (only with -DASPIRE_PHASE_CLOCK)
 };
 
+// The VALU tile kernels (cost_valu.hip): a workgroup is three waves, a third of the 768 coordinates each
+constexpr int kWaves = 3;
+constexpr int kBlock = 64 * kWaves;
+constexpr int kMaxT = 4;  // sentence rows per document <= 8 * kMaxT
+
 // Internal third pairing next to ASPIRE_PAIR_CROSS / ASPIRE_PAIR_PAIRED (see ScoreArgs::qmap).
 constexpr int kPairMapped = 2;
 // Floor of a pair's bounding-box diameter in the Sinkhorn solvers: two documents that are one and the same point (a
@@ -122,6 +130,43 @@ __device__ __forceinline__ bool use_mm_formula(int mode, int nq, int nc) {
     return mode == ASPIRE_CDIST_MM || (mode == ASPIRE_CDIST_AUTO && (nq > 25 || nc > 25));
 }
 
+// The tile count T (8 T x 8 T entries per pair) of documents of up to `max_rows` rows, as a compile-time constant: f(integral_constant<int, T>)
+template <typename F>
+int dispatch_T(int max_rows, F&& f) {
+    if (max_rows <= 8) return f(std::integral_constant<int, 1>{});
+    if (max_rows <= 16) return f(std::integral_constant<int, 2>{});
+    if (max_rows <= 24) return f(std::integral_constant<int, 3>{});
+    if (max_rows <= 32) return f(std::integral_constant<int, 4>{});
+    set_error("documents with more than %d sentence rows are not supported (got %d)", 8 * kMaxT, max_rows);
+    return ASPIRE_ERR_UNSUPPORTED;
+}
+
+// cost_valu.hip: the VALU cost and max-sim tiles for documents of up to 32 rows (T tiles of 8 rows a side), the documents' boxes,
+// the census of long pairs behind the hybrid forms' gate, the batch diameter
+int launch_l2max_tiles(const ScoreArgs& a, int max_rows, int qchunks, hipStream_t stream);
+int launch_doc_box(const RepSet& d, float* box, hipStream_t stream);
+int launch_cost_stage(const ScoreArgs& a, int T, const aspire_repset* q, const aspire_repset* c, float* cost, float* neg, float* diam2,
+                      int64_t n_slots, int qchunks, bool gram, float* qbox, float* cbox, bool first_chunk, hipStream_t stream);
+int arm_long_pair_gate(ScoreArgs& a, int32_t* gate, int64_t C, hipStream_t stream);
+int launch_group_diameter(const ScoreArgs& a, int64_t group, int64_t ngroups, int64_t blocks, float* diameter, hipStream_t stream);
+
+// sinkhorn.hip: the Sinkhorn solvers on workspace slots, and costs + solve of a short pair in one wave
+int launch_sinkhorn_stage(const ScoreArgs& a, int T, float* cost, float* neg, float* diam2, int64_t n_slots, int max_rows, bool extra,
+                          int form_hint, hipStream_t stream);
+int launch_pair_one(const ScoreArgs& a, int64_t n_slots, hipStream_t stream);
+
+// batch_prep.hip: the tables of batched jobs and the items of the CHUNK / REC forms, written into the pieces of a call's workspace
+// (BatchTables: score.hip's batch_layout as pointers)
+struct BatchTables {
+    float* slots;
+    float* qbox;
+    int32_t *cand_job, *grp_job, *grp_off, *grp_rec, *gate;
+    void* topk;
+};
+int64_t chunk_items_bound(int64_t J, int64_t C, int64_t max_job);
+int launch_batch_tables(const ScoreArgs& a, const BatchTables& t, const int32_t* job_off, int64_t J, int64_t max_job, hipStream_t stream);
+int launch_chunk_prep(ScoreArgs& a, const BatchTables& t, const int32_t* job_off, int64_t J, int64_t max_job, hipStream_t stream);
+int launch_rec_prep(const ScoreArgs& a, const BatchTables& t, const int32_t* job_off, int64_t J, int64_t max_job, hipStream_t stream);
 
 // gram.hip: matrix-core form of the pairwise-cost stage (host launchers; see the file header)
 bool gram_path_wanted(const aspire_repset* q, const aspire_repset* c, int pairing);

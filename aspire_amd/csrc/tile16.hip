@@ -1,5 +1,5 @@
 // otAspire cost stage for documents of 9 .. 16 sentence rows, few queries per candidate, CSR inputs (A5; reference arithmetic:
-// src/learning/facetid_models/pair_distances.py:39-56 + geomloss 0.2.4's squared_distances, restated -- see score.hip).
+// src/learning/facetid_models/pair_distances.py:39-56 + geomloss 0.2.4's squared_distances, restated -- see cost_valu.hip).
 //
 // Real abstracts are often longer than the 8 sentences of the benchmark configurations.  Until now such pools went through
 // the per-pair tile-loop kernel (pair_cost_kernel<2>: one workgroup per candidate, VALU difference sums: 20 x 1000 x 12

@@ -271,7 +271,7 @@ def test_kernel_register_budgets():
     sink = one(r'sinkhorn_kernelILi1E')
     topk = one(r'topk_select_kernelILi4E')
     assert cost['vgpr'] <= 200 and cost['scratch'] == 0
-    sub = one(r'pair_cost1_sub_kernel')             # sub-tile form (long documents, small pools): capped, see score.hip
+    sub = one(r'pair_cost1_sub_kernel')             # sub-tile form (long documents, small pools): capped, see cost_valu.hip
     assert sub['vgpr'] <= 216 and sub['scratch'] == 0
     assert sink['vgpr'] <= 56 and sink['scratch'] == 0
     assert topk['vgpr'] <= 56 and topk['scratch'] == 0

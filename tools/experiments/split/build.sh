@@ -1,6 +1,6 @@
 #!/bin/bash
-# The product library + round 5's role-split kernel (split.hip, an experiment that lost: NOTES.md round 5): score.hip recompiled with
-# -DASPIRE_EXPERIMENT_SPLIT (its two call sites), split.hip beside it -> build/variants/split/libaspire_hip.so  (ASPIRE_HIP_LIB=... to load it)
+# The product library + round 5's role-split kernel (split.hip, an experiment that lost: NOTES.md round 5): score.hip (launch_fused_form) recompiled with
+# -DASPIRE_EXPERIMENT_SPLIT (launch_fused_form is the one call site; no other unit reads the macro), split.hip beside it -> build/variants/split/libaspire_hip.so  (ASPIRE_HIP_LIB=... to load it)
 set -eu
 R=$(cd "$(dirname "$0")/../../.." && pwd)
 OUT=$R/build/variants/split
