@@ -1,0 +1,102 @@
+// What the encoder's units share: the argument structs the GEMM kernels take by value (the forward in encoder.hip fills them), the
+// two device-side names that kernels of more than one unit use, and the host launchers each kernel family's unit offers to the
+// forward in encoder.hip (one comment line names the unit).  The fp16-plane layout has a header of its own, enc_planes.h.
+#pragma once
+#include "common.h"
+
+namespace aspire {
+
+struct GemmArgs {
+    const float* A;     // [batch][M][lda]
+    const float* B;     // B_KN ? [batch][K][ldb] : [batch][N][ldb]
+    float* C;           // [batch][M][ldc]
+    const float* bias;  // [N] or null
+    const float* res;   // [M][ldr] residual or null (not batched)
+    int M, N, K;
+    int lda, ldb, ldc, ldr;
+    // batch index z = z1 * nz2 + z2; operand offsets are z1 * s?1 + z2 * s?2 (attention: z1 = doc, z2 = head)
+    int nz2;
+    long long sa1, sa2, sb1, sb2, sc1, sc2;
+    float alpha;
+    int gelu;
+};
+
+struct PGemmArgs {
+    const void* Ap;      // P layout [M, K]
+    const void* Bp;      // P layout [N, K] (nn.Linear weight, scaled by kPWeightScale)
+    float* C;            // fp32 [M, ldc] out (F32 epilogue)
+    void* Cp;            // P layout [M, N] out (GELU_P epilogue: the next GEMM's A operand, its k dimension = N)
+    const float* bias;   // [N] or null
+    const float* res;    // [M, ldr] residual or null
+    int M, N, K, ldc, ldr;
+    int n_off;           // first column of this launch (a GEMM may run as a launch of 128-wide and one of 64-wide column tiles)
+    int probe;           // timing probes (ASPIRE_HIP_GEMM_PROBE): 1 no MFMAs, 2 no LDS-DMA
+    int tiles_x, tiles_y;   // PERSIST / LN: the tile grid (PERSIST: a workgroup walks several tiles; the launch grid is the resident workgroups)
+    // LN epilogue (N = 768 = the whole row): y = LayerNorm(acc + bias + residual) * gamma + beta -> C (fp32, optional) and Cp (P layout,
+    // optional); the residual is READ from a P layout [M, 768] (resp; h + l = the fp32 value to fp32's own rounding) and may BE Cp:
+    // every 8-byte slot is read and later written by the one lane that owns it
+    const void* resp;
+    const float *gamma, *beta;
+    float eps;
+    float2* ln_stats;    // [M][768 / BN] (mean, sum of squared deviations) of a row's BN columns, one entry per column tile
+    int* ln_count;       // [row blocks] zeroed before the launch: column tiles of the row block that have published their entry
+    // QKV epilogue (EPI 1, launch_gemm_p_qkv): the attention kernel's operands, already split -- Xp = the planes
+    // [plane h | l][Q | K | V][head][M][64] fp16 (flash_attn_p_kernel)
+    void* Xp;
+};
+
+namespace {
+
+using f32x16 = __attribute__((ext_vector_type(16))) float;
+
+// GELU as HF BertModel's "gelu" (0.5 x (1 + erf(x / sqrt 2))), written around erfc: e = erfc(|x| / sqrt 2) = 2^q(|x|), q a degree-8 polynomial
+// (a weighted Chebyshev fit of log2 erfc(t / sqrt 2) on [0, 5.8]; beyond, erfc < 7e-9), then x - 0.5 x e for x > 0 and 0.5 x e otherwise: no
+// cancellation on either side, 15 VALU instructions where 0.5 x (1 + erff(.)) takes 37 (50 M activations per FFN1 launch at 64 x 256 tokens).
+// Max |error| against float64 over [-9, 9]: 2.5e-7 (the erff form, rounded in fp32: 4.5e-7).
+__device__ __forceinline__ float gelu_erf(float x) {
+    const float t = fminf(fabsf(x), 5.8f);
+    float q = -1.9605818124546204e-06f;
+    q = fmaf(q, t, 2.8825294066336937e-05f);
+    q = fmaf(q, t, -0.0001355033746222034f);
+    q = fmaf(q, t, -0.0002612900862004608f);
+    q = fmaf(q, t, 0.007229907438158989f);
+    q = fmaf(q, t, -0.05261624604463577f);
+    q = fmaf(q, t, -0.4591653645038605f);
+    q = fmaf(q, t, -1.1511112451553345f);
+    q = fmaf(q, t, 1.7379414884999278e-07f);
+    const float r = 0.5f * x * __builtin_amdgcn_exp2f(q);
+    return x > 0.f ? x - r : r;
+}
+
+}  // namespace
+
+// enc_gemm.hip: C = alpha A.B^T (+bias)(+GELU)(+residual) on fp32 operands, batched; b_kn: B is [K, N] n-contiguous (V of attention)
+int launch_gemm(const GemmArgs& g, int batch, bool b_kn, hipStream_t st);
+
+// enc_gemm_p.hip: the GEMMs on pre-split fp16 planes (enc_planes.h) and the split of an fp32 matrix into them (weight: the B side,
+// scaled by kPWeightScale; too_big: optional device flag).  swap: the GELU -> P-layout epilogue.  The unit also owns the encoder's
+// device globals and the entry points that touch them: aspire_bert_status, aspire_debug_gemm_buffer.
+int launch_split_planes(const float* X, int64_t R, int K, void* P, bool weight, int* too_big, hipStream_t st);
+int launch_gemm_p(const PGemmArgs& g, bool swap, hipStream_t st);
+int launch_gemm_p_qkv(PGemmArgs g, hipStream_t st);
+int launch_gemm_p_ln(const PGemmArgs& g, hipStream_t st);
+bool ln_fused_supported();
+
+// enc_attn.hip: the masked soft-max of the three-kernel form, fused attention on fp32 Q / K / V (f32: fp32-input MFMAs, else fp16
+// planes split in the kernel) and on the QKV GEMM's planes (keys64: 64-key tiles), and the CLS query's attention
+int launch_softmax_mask(float* s, const int64_t* mask, int64_t rows, int L, int ld, int rows_per_doc, float scale, hipStream_t st);
+int launch_flash_attn(const float* qkv, const int64_t* mask, float* ctx, int64_t B, int L, int H, void* ctxp, int64_t rows, bool f32,
+                      hipStream_t st);
+int launch_flash_attn_p(const unsigned char* qkvp, const int64_t* mask, float* ctx, int64_t B, int L, int H, void* ctxp, int64_t rows,
+                        bool keys64, hipStream_t st);
+int launch_cls_attn(const float* qkv, const unsigned char* qkvp, const int64_t* mask, float* ctx, int64_t B, int L, int H, int64_t rows,
+                    hipStream_t st);
+
+// enc_rows.hip: one wave per row of 768 -- LayerNorm, embeddings + LayerNorm, the CLS rows of a hidden state
+int launch_layernorm(const float* x, const float* gamma, const float* beta, float eps, float* y, int64_t rows, void* yp, hipStream_t st);
+int launch_embed_layernorm(const int64_t* tok, const int64_t* typ, const float* word, const float* pos, const float* type_emb,
+                           const float* gamma, const float* beta, float eps, float* y, int64_t rows, int64_t L, void* yp, hipStream_t st);
+int launch_cls_tap(const float* x, const void* xp, int64_t rows, int64_t L, int64_t B, float wt, int mode, float* cls_out, float* layer_cls,
+                   float* gather, hipStream_t st);
+
+}  // namespace aspire

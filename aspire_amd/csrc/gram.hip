@@ -113,7 +113,7 @@ __device__ __noinline__ float direct_d2(unsigned long long x, unsigned long long
 // spills (178 / 194 registers) 1 x 20 000 x 12 is 8 % slower (371 vs 340 us) and 2 x 10 000 x 12 4 - 20 % faster (240 vs 248 us
 // otAspire, 103 vs 126 us max-sim).
 // X3 (the 128-column forms): the Gram tile on the bf16 matrix pipe at fp32 accuracy -- operands split into three bf16 planes
-// when a tile is staged, six v_mfma_f32_32x32x16_bf16 products per term (see gemm_bf16x3_kernel in encoder.hip: same error
+// when a tile is staged, six v_mfma_f32_32x32x16_bf16 products per term (see gemm_bf16x3_kernel in enc_gemm.hip: same error
 // against float64 as the fp32-input MFMA at 3/8 of its matrix-pipe time).
 template <int BN, bool L2MAX, bool BOX, bool X3 = false>
 __global__ void __launch_bounds__(256, 2) pair_gram_kernel(GramArgs g) {

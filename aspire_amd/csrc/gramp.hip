@@ -8,7 +8,7 @@
 // gram.hip's 128-column form splits every fp32 tile into three bf16 planes while it is staged (VALU work in the main loop,
 // SIX matrix products per term).  Here the split is done ONCE per resident store (include/aspire_hip.h: aspire_rep_planes --
 // per-row power-of-two scale, the store's common vector mu taken off first, h + l fp16 planes, |x - mu|^2 per row) and the
-// kernel is the encoder's gemm_p_kernel loop (encoder.hip) with the Gram epilogue of gram.hip:
+// kernel is the encoder's gemm_p_kernel loop (enc_gemm_p.hip) with the Gram epilogue of gram.hip:
 //   * tile = whole documents in slots of mr rows, 128 candidate rows (MFMA M side: a lane's four consecutive accumulator
 //     rows are four consecutive candidate sentences) x 128 query rows; every (query, candidate) pair lives in one workgroup;
 //   * a stage = one 16-coordinate k block: 8 KB of candidate rows + 8 KB of query rows, gathered row by row (64 B per row

@@ -43,7 +43,7 @@ def pack_weights(weights, n_heads, ln_eps):
 
 def run_checked(run, outputs_finite, who, status):
     """The encoder's fall-back rule around run() (a forward and whatever reads it out), each re-run at most once, in this order:
-      * status() non-zero: a LayerNorm-epilogue GEMM gave up waiting for its row block (encoder.hip: gemm_p_ln_kernel's bounded
+      * status() non-zero: a LayerNorm-epilogue GEMM gave up waiting for its row block (enc_gemm_p.hip: gemm_p_ln_kernel's bounded
         wait) and what run() made is invalid -- run again with the LayerNorm as its own pass, pinned(GEMM_LN='off');
       * outputs_finite(result) false: an activation left the fp16 planes' range (HipBertEncoder.forward_full_range) -- run again
         on the kernels that take any fp32 value, pinned(GEMM='bf16x3', ATTN='f32').

@@ -136,9 +136,10 @@ int aspire_bert_forward_f32(const aspire_bert_weights* w, const int64_t* tok_ids
  * and a tile WAITS inside the kernel for its partners.  The wait is bounded (20 ms): a tile that gives up sets
  * ASPIRE_BERT_STATUS_LN_TIMEOUT and the outputs of the forwards in flight are invalid.  aspire_bert_status copies the word to
  * *status_host, SYNCHRONISES `stream`, and clears it; on a non-zero word run the forwards since the last check again with
- * aspire_debug_set("GEMM_LN", "off") (the separate LayerNorm pass; aspire_amd/encoder.py and consent.py do exactly that).  Never seen
- * set outside the fault-injection test (tests/test_gpu_encoder.py); the bound turns a hang under a broken dispatch-order assumption
- * (CU masking, a serialising debugger) into an error. */
+ * aspire_debug_set("GEMM_LN", "off") (the separate LayerNorm pass; run_checked in aspire_amd/encoder.py is that rule, and the model
+ * classes -- consent.py, bienc.py, sentenc.py, contextner.py -- apply it to what they hand out).  Never seen set outside the
+ * fault-injection test (tests/test_gpu_encoder_wait.py); the bound turns a hang under a broken dispatch-order assumption (CU masking,
+ * a serialising debugger) into an error. */
 #define ASPIRE_BERT_STATUS_LN_TIMEOUT 1
 int aspire_bert_status(int32_t* status_host, void* stream);
 

@@ -1,4 +1,4 @@
-"""GPU: the bounded wait of the LayerNorm-epilogue GEMMs (encoder.hip: gemm_p_ln_kernel; VERDICT r5 item 5 / ADVICE r5): a tile that
+"""GPU: the bounded wait of the LayerNorm-epilogue GEMMs (enc_gemm_p.hip: gemm_p_ln_kernel; VERDICT r5 item 5 / ADVICE r5): a tile that
 waits for its row block's partners gives up after 20 ms and says so in the encoder's status word (include/aspire_hip.h:
 aspire_bert_status); the host layer then runs the forward again with the LayerNorm as its own pass.  Reference call site of the
 forward: examples/ex_aspire_consent.py:72-73."""
