@@ -274,6 +274,15 @@ def prepare_eval_seqs(batch_papers, tokenizer):
     return prepare_bert_seqs([p['TITLE'] + ' [SEP] ' + ' '.join(p['ABSTRACT']) for p in batch_papers], tokenizer)[0]
 
 
+def prepare_eval_ner_seqs(batch_papers, tokenizer):
+    """BertNER._pre_process_input_batch (src/evaluation/utils/models.py:368-376): prepare_eval_seqs' text + ' ' + the entity strings
+    of all sentences, in order, joined by '. ' + '.'; a paper without entities still gets the trailing ' .'.
+    :return: bert_batch (prepare_bert_seqs)."""
+    seqs = [p['TITLE'] + ' [SEP] ' + ' '.join(p['ABSTRACT']) + ' ' + '. '.join(ner for ners in p['ENTITIES'] for ner in ners) + '.'
+            for p in batch_papers]
+    return prepare_bert_seqs(seqs, tokenizer)[0]
+
+
 # ---- the cosentbert / ictsentbert sentence encoder's inputs (aspire_amd/sentenc.py): one sequence per sentence ------------------
 def prepare_sentence_batch(sents, tokenizer, max_seq_length=512):
     """The tokenisation of SentenceTransformer.encode with models.Transformer(max_seq_length=512) (TrainedSentModel,

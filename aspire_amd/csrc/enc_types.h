@@ -99,4 +99,7 @@ int launch_embed_layernorm(const int64_t* tok, const int64_t* typ, const float* 
 int launch_cls_tap(const float* x, const void* xp, int64_t rows, int64_t L, int64_t B, float wt, int mode, float* cls_out, float* layer_cls,
                    float* gather, hipStream_t st);
 
+// enc_pooler.hip: pooled = tanh(cls . w_pool^T + b_pool) on [B, 768] rows (HF BertPooler)
+int launch_pooler(const float* cls, int64_t B, const float* w_pool, const float* b_pool, float* pooled, hipStream_t st);
+
 }  // namespace aspire

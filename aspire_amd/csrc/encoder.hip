@@ -22,6 +22,7 @@
 //   enc_attn.hip     flash_attn_p_kernel, flash_attn_p64_kernel, flash_attn_f16x2_kernel, flash_attn_f32_kernel,
 //                    softmax_mask_kernel, cls_attn_kernel                                                    launch_flash_attn_p, launch_flash_attn, launch_softmax_mask, launch_cls_attn
 //   enc_rows.hip     layernorm_kernel, embed_layernorm_kernel, cls_tap_kernel                                launch_layernorm, launch_embed_layernorm, launch_cls_tap
+//   enc_pooler.hip   bert_pooler_kernel: tanh(cls . W^T + b) behind the CLS forward (aspire_bert_pooler_f32)   launch_pooler
 //   enc_planes.h     the fp16-plane layout: constants and device helpers
 #include <math.h>
 
@@ -381,6 +382,21 @@ extern "C" int aspire_bert_forward_cls_f32(const aspire_bert_weights* w, const i
     if (int rc = launch_gemm(g, 1, false, f.st)) return rc;
     if (int rc = launch_layernorm(cw.tmp, ly.ln2_g, ly.ln2_b, w->ln_eps, cw.y, B, nullptr, f.st)) return rc;
     return tap(n, cw.y, nullptr, B, 1);
+}
+
+// HF BertPooler on the CLS rows a forward wrote (src/evaluation/utils/models.py:350: model_out.pooler_output, the SimCSE baselines'
+// rep): the checks here, the kernel in enc_pooler.hip.  The pooler's weights travel as plain arguments: aspire_bert_weights keeps
+// its layout.
+extern "C" int aspire_bert_pooler_f32(const float* cls, int64_t B, int64_t D, const float* w_pool, const float* b_pool, float* pooled,
+                                      void* stream) {
+    ASPIRE_REQUIRE(D == kD, ASPIRE_ERR_UNSUPPORTED, "hidden size %lld unsupported (the pooler is built for 768)", (long long)D);
+    ASPIRE_REQUIRE(B >= 0, ASPIRE_ERR_INVALID_ARG, "negative row count %lld", (long long)B);
+    if (B == 0) return ASPIRE_OK;
+    ASPIRE_REQUIRE(cls && w_pool && b_pool && pooled, ASPIRE_ERR_INVALID_ARG, "null pointer");
+    ASPIRE_REQUIRE(pooled != cls, ASPIRE_ERR_INVALID_ARG, "pooled must not be cls: a workgroup reads whole rows that others write");
+    ASPIRE_REQUIRE(((uintptr_t)cls & 15) == 0 && ((uintptr_t)w_pool & 15) == 0, ASPIRE_ERR_INVALID_ARG,
+                   "cls and w_pool must be 16-byte aligned");
+    return launch_pooler(cls, B, w_pool, b_pool, pooled, (hipStream_t)stream);
 }
 
 // The weights' fp16 planes, formed ONCE when the model is loaded: a device buffer of aspire_bert_planes_bytes(w) bytes that the

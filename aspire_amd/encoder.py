@@ -5,7 +5,8 @@
 makes on it: ``encoder(tokid_tt, token_type_ids=seg_tt, attention_mask=attnmask_tt).last_hidden_state``
 (:72-73).  Weights are copied to HBM once, in nn.Linear layout; query/key/value are concatenated so the three
 projections are one GEMM.  The bi-encoders' CLS read-out (aspire_bert_forward_cls_f32) runs on the same weights
-(forward_cls), and run_checked is the one fall-back rule every model class applies to what it hands out.
+(forward_cls), the pooler (aspire_bert_pooler_f32) behind it where the model has one (forward_pooled), and run_checked is the
+one fall-back rule every model class applies to what it hands out.
 """
 import ctypes
 import warnings
@@ -85,6 +86,10 @@ class HipBertEncoder:
                   torch.cat([sd[att + 'query.bias'], sd[att + 'key.bias'], sd[att + 'value.bias']], 0)]
             w += [sd[p + k] for k in _LAYER_KEYS]
         self._w = pack_weights([t.to(device=dev, dtype=torch.float32) for t in w], cfg.num_attention_heads, cfg.layer_norm_eps)
+        # HF BertPooler's dense layer, where the model has one (forward_pooled); it is no part of struct aspire_bert_weights
+        self._pooler = None
+        if pre + 'pooler.dense.weight' in sd:
+            self._pooler = tuple(sd[pre + 'pooler.dense.' + k].to(device=dev, dtype=torch.float32).contiguous() for k in ('weight', 'bias'))
         self._ws = {}                       # one workspace per HIP stream: forwards on different streams overlap
         # the nn.Linear weights' fp16 planes, formed once (include/aspire_hip.h: aspire_bert_prepare_planes)
         nbytes = lib.aspire_bert_planes_bytes(ctypes.byref(self._w))
@@ -163,6 +168,15 @@ class HipBertEncoder:
         check(lib.aspire_bert_forward_cls_f32(ctypes.byref(self._w), ops._ptr(tok), ops._ptr(typ), ops._ptr(msk), b, l, mix,
                                               ops._ptr(out), ops._ptr(layers), ops._ptr(ws), ws.numel(), ops._stream()))
         return out, layers
+
+    def forward_pooled(self, tokid_tt, token_type_ids=None, attention_mask=None, check_ids=True):
+        """BertModel's two read-outs: int64 [B, L] tensors (any device) -> (last_hidden_state[:, 0] [B, 768], pooler_output [B, 768]
+        = tanh(dense(that row))), on the GPU: forward_cls with no layer mix, then aspire_bert_pooler_f32.  ValueError for a model
+        without a pooler.  Under run_checked, judge finiteness on the CLS rows: tanh turns an overflowed activation into +-1."""
+        if self._pooler is None:
+            raise ValueError('forward_pooled: the model has no pooler (pooler.dense.weight / pooler.dense.bias)')
+        cls = self.forward_cls(tokid_tt, token_type_ids, attention_mask, check_ids=check_ids)[0]
+        return cls, ops.bert_pooler(cls, *self._pooler)
 
     @staticmethod
     def status():

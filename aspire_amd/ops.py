@@ -314,6 +314,19 @@ def cls_l2(q_cls, c_cls, pairing=_lib.PAIR_PAIRED, eps=1e-6):
     return out
 
 
+def bert_pooler(cls, weight, bias):
+    """HF BertPooler on CLS rows (aspire_bert_pooler_f32): tanh(cls @ weight.T + bias), cls [B, 768], weight [768, 768] (nn.Linear
+    layout), bias [768] -> [B, 768] on the GPU."""
+    _f32(cls, 'cls')
+    _f32(weight, 'weight')
+    _f32(bias, 'bias')
+    assert cls.dim() == 2 and tuple(weight.shape) == (cls.shape[1], cls.shape[1]) and tuple(bias.shape) == (cls.shape[1],), \
+        'bert_pooler: cls [B, D], weight [D, D], bias [D]'
+    out = torch.empty_like(cls)
+    check(lib.aspire_bert_pooler_f32(_ptr(cls), cls.shape[0], cls.shape[1], _ptr(weight), _ptr(bias), _ptr(out), _stream()))
+    return out
+
+
 def _ot_params(c, blur, scaling, sent_sm_temp, cdist_mode, one_form):
     """struct aspire_ot_params of an otAspire call with its flag word: ONE_FORM as the caller asks, CENTER from the candidates' rows
     (DeviceRepSet.center_hint)."""

@@ -10,6 +10,7 @@ implementation so that shapes propagate under FakeTensor / torch.compile tracing
     torch.ops.aspire.bert_encoder_forward(ids, type_ids, mask, weights, n_heads, ln_eps) -> hidden  A1   ex_aspire_consent.py:72-73
     torch.ops.aspire.bert_cls_forward(ids, type_ids, mask, weights, n_heads, ln_eps, layer_mix) -> cls [B, 768]
                                                                                    A1b  ex_aspire_bienc.py:23-58
+    torch.ops.aspire.bert_pooler(cls, weight, bias) -> pooled [B, 768]                             A1c  models.py:350
     torch.ops.aspire.l2max_scores(q, q_lens, c, c_lens, paired) -> scores                          A9   pair_distances.py:138-186
     torch.ops.aspire.ot_sinkhorn_scores(q, q_lens, c, c_lens, blur, scaling, temp, group, want, paired, extras)
                                          -> (scores, q_distr, c_distr, pair_sims, plan)           A5-A8 pair_distances.py:21-92
@@ -122,6 +123,17 @@ def bert_cls_forward(ids: Tensor, type_ids: Tensor, mask: Tensor, weights: List[
 @bert_cls_forward.register_fake
 def _(ids, type_ids, mask, weights, n_heads, ln_eps, layer_mix):
     return weights[0].new_empty(ids.shape[0], weights[0].shape[1])
+
+
+# HF BertPooler on the CLS rows (aspire_bert_pooler_f32): tanh(cls @ weight.T + bias), the SimCSE baselines' pooler_output
+@torch.library.custom_op('aspire::bert_pooler', mutates_args=(), device_types='cuda')
+def bert_pooler(cls: Tensor, weight: Tensor, bias: Tensor) -> Tensor:
+    return ops.bert_pooler(cls.contiguous(), weight.contiguous(), bias.contiguous())
+
+
+@bert_pooler.register_fake
+def _(cls, weight, bias):
+    return cls.new_empty(cls.shape[0], weight.shape[0])
 
 
 def _npairs(qn, cn, paired):
@@ -265,5 +277,5 @@ def _(q_rows, q_start, q_len, q_max, c_rows, c_start, c_len, c_max, job_off, max
     return (q_rows.new_empty(c_start.shape[0]), q_rows.new_empty(j, k), q_rows.new_empty(j, k, dtype=torch.int64))
 
 
-OPS = ('span_mean_pool', 'span_pool_ranges', 'bert_encoder_forward', 'bert_cls_forward', 'l2max_scores', 'jointsm_scores', 'ot_sinkhorn_scores', 'topk_desc', 'topk_keys', 'topk_merge',
+OPS = ('span_mean_pool', 'span_pool_ranges', 'bert_encoder_forward', 'bert_cls_forward', 'bert_pooler', 'l2max_scores', 'jointsm_scores', 'ot_sinkhorn_scores', 'topk_desc', 'topk_keys', 'topk_merge',
        'l2max_scores_csr', 'ot_scores_csr', 'ot_rank_batch')

@@ -88,8 +88,9 @@ int aspire_span_pool_ranges_f32(const float* hidden, int64_t B, int64_t L, int64
  * A1  BERT-base encoder forward.  Replaces `self.bert_encoder(tokid_tt, token_type_ids=seg_tt,
  * attention_mask=attnmask_tt).last_hidden_state` at examples/ex_aspire_consent.py:72-73 (HuggingFace
  * BertModel: embeddings + LayerNorm, 12 x [QKV, masked softmax attention, output proj + residual +
- * LayerNorm, 768->3072 GELU(erf) 3072->768 + residual + LayerNorm]; the pooler is not computed, the
- * reference never reads it).  fp32 ACCURACY throughout (1e-4 of HuggingFace's fp32 CPU forward, also on weights with a trained
+ * LayerNorm, 768->3072 GELU(erf) 3072->768 + residual + LayerNorm]; the pooler is not part of the
+ * forward: the one reference model that reads pooler_output gets it from aspire_bert_pooler_f32, A1c).
+ * fp32 ACCURACY throughout (1e-4 of HuggingFace's fp32 CPU forward, also on weights with a trained
  * checkpoint's outliers: tests/test_gpu_encoder_heavy.py): with `planes` prepared and >= 1024 token rows every GEMM and the
  * attention run on the fp16 matrix pipe over operands held as two fp16 planes (three exact products per term, fp32 sums); otherwise
  * on operands split on the fly / the fp32-input matrix cores.  An activation beyond fp16's range (|x| > 65504) makes the plane path
@@ -164,6 +165,22 @@ size_t aspire_bert_cls_workspace_bytes(const aspire_bert_weights* w, int64_t B, 
 int aspire_bert_forward_cls_f32(const aspire_bert_weights* w, const int64_t* tok_ids, const int64_t* type_ids,
                                 const int64_t* attn_mask, int64_t B, int64_t L, const float* layer_mix, float* cls_out,
                                 float* layer_cls, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * A1c  BERT pooler read-out.  Replaces `model_out.pooler_output` at src/evaluation/utils/models.py:350
+ * (SimCSE.encode, :322-357: the 'supsimcse' / 'unsupsimcse' baselines; pre_proc_buildreps.py:105-127 writes
+ * the same reps).  HuggingFace BertPooler: nn.Linear(768, 768) on last_hidden_state[:, 0], then nn.Tanh:
+ *   pooled[b, n] = tanh( sum_k cls[b, k] * w_pool[n, k] + b_pool[n] )
+ * fp32 throughout (exact fp32 products on the matrix cores, fp32 sums, the library's tanhf).
+ *   cls     [B, 768]   the CLS rows aspire_bert_forward_cls_f32 wrote (layer_mix NULL)
+ *   w_pool  [768, 768] pooler.dense.weight, nn.Linear layout;  b_pool [768] pooler.dense.bias
+ *   pooled  [B, 768]   out; must not be cls
+ * All four are contiguous device pointers, cls and w_pool 16-byte aligned.  Checked before any launch:
+ * D != 768 -> ASPIRE_ERR_UNSUPPORTED; B < 0, a NULL pointer with B > 0, pooled == cls -> ASPIRE_ERR_INVALID_ARG;
+ * B == 0 -> ASPIRE_OK without a launch.
+ * ------------------------------------------------------------------------------------------- */
+int aspire_bert_pooler_f32(const float* cls, int64_t B, int64_t D, const float* w_pool, const float* b_pool,
+                           float* pooled, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * caching_score's document-level term (src/learning/facetid_models/disent_models.py:305-307, taken when
