@@ -12,4 +12,5 @@ from .consent import AspireConSent  # noqa: F401
 from .contextner import AspireConSenContextual, AspireContextNER, AspireNER  # noqa: F401
 from .polyenc import WordSentAlignPolyEnc, TrainedScoringModel  # noqa: F401
 from .baselines import BertMLM, BertNER, SimCSE  # noqa: F401
+from .sbert import SentenceModel  # noqa: F401
 from .models import MODEL_TABLE, get_model  # noqa: F401

@@ -62,6 +62,11 @@ class BertWeights(ctypes.Structure):
                 ('max_pos', c_int32), ('n_types', c_int32), ('ln_eps', ctypes.c_float), ('planes', c_void_p)]
 
 
+class BertExtras(ctypes.Structure):
+    """struct aspire_bert_extras"""
+    _fields_ = [('pos_ids', c_void_p), ('rel_bias', c_void_p), ('rel_span', c_int32)]
+
+
 class AspireHipError(RuntimeError):
     pass
 
@@ -83,6 +88,9 @@ SIGNATURES = {
     'aspire_bert_workspace_bytes': (c_size_t, [ctypes.POINTER(BertWeights), c_int64, c_int64]),
     'aspire_bert_forward_f32': (c_int, [ctypes.POINTER(BertWeights), c_void_p, c_void_p, c_void_p, c_int64, c_int64,
                                         c_void_p, c_void_p, c_size_t, c_void_p]),
+    'aspire_bert_forward_var_f32': (c_int, [ctypes.POINTER(BertWeights), ctypes.POINTER(BertExtras), c_void_p, c_void_p, c_void_p,
+                                            c_int64, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'aspire_token_mean_pool_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p]),
     'aspire_bert_status': (c_int, [ctypes.POINTER(ctypes.c_int32), c_void_p]),
     'aspire_bert_cls_workspace_bytes': (c_size_t, [ctypes.POINTER(BertWeights), c_int64, c_int64]),
     'aspire_bert_forward_cls_f32': (c_int, [ctypes.POINTER(BertWeights), c_void_p, c_void_p, c_void_p, c_int64, c_int64,

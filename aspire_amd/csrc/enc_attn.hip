@@ -10,6 +10,15 @@
 //   softmax_mask_kernel      rows of scores: x*scale + key-padding bias, softmax in place (one wave per row); between the two batched GEMMs
 //                            of the three-kernel form (ASPIRE_HIP_ATTN=gemm) that the fused kernels are tested against
 //   cls_attn_kernel          attention of the CLS query alone, one workgroup per (document, head) (aspire_bert_forward_cls_f32's last layer)
+//
+// BIAS (template parameter of every kernel but flash_attn_p64_kernel and cls_attn_kernel): MPNet's relative-position bias
+// (aspire_bert_extras::rel_bias: HF MPNetSelfAttention, q.k / 8, + position_bias, + mask, soft-max).  rel_bias is
+// [heads][2 rel_span - 1], entry (j - i) + rel_span - 1 the bias of (query i, key j); it is the same in every layer.  BIAS = false is
+// BertModel's attention: the instantiations the BERT forwards run contain nothing of the bias (if constexpr).
+// The fused kernels keep the head's table in LDS (stage_rel_bias: 4 KB, the 2 L - 1 <= 1023 distances of this document length,
+// already times log2(e) as their exp2 soft-max wants the scores): a lane reads 16 n entries per n-key tile, at addresses that differ
+// by (key - query) only -- consecutive words across the lanes of a wave, no bank conflict -- and LDS reads count on lgkmcnt, apart from
+// the vmcnt that flash_attn_p_kernel's LDS-DMA waits on.  66 + 4 KB still fits twice per CU.
 #include <math.h>
 
 #include "enc_planes.h"
@@ -20,8 +29,11 @@ namespace {
 
 // scores [rows = B*H*L][ld] in place: softmax_j(x_j * scale + (mask[b][j] ? 0 : -FLT_MAX)); columns in [L, ld)
 // are written as zeros so that the P.V GEMM can run K up to ld.
+// BIAS: + rel_bias[h][(j - i) + rel_span - 1] between the scaling and the mask (row = (b H + h) L + i)
+template <bool BIAS>
 __global__ void __launch_bounds__(256) softmax_mask_kernel(float* __restrict__ s, const int64_t* __restrict__ mask, int64_t rows,
-                                                           int L, int ld, int rows_per_doc, float scale) {
+                                                           int L, int ld, int rows_per_doc, float scale,
+                                                           const float* __restrict__ rel_bias, int rel_span) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
@@ -31,12 +43,20 @@ __global__ void __launch_bounds__(256) softmax_mask_kernel(float* __restrict__ s
     constexpr int kMaxPer = 8;  // L <= 512
     float v[kMaxPer];
     float m = -INFINITY;
+    const float* rb = nullptr;   // BIAS: this row's bias of key j at rb[j]
+    if constexpr (BIAS) {
+        const int i = (int)(row % L), h = (int)((row % rows_per_doc) / L);
+        rb = rel_bias + (size_t)h * (2 * rel_span - 1) + (rel_span - 1 - i);
+    }
 #pragma unroll
     for (int c = 0; c < kMaxPer; ++c) {
         const int j = lane + 64 * c;
         if (j < L) {
             // (1 - mask) * finfo(float32).min added to the scaled scores, as BertModel's extended mask
-            v[c] = p[j] * scale + (mk[j] != 0 ? 0.f : -3.4028234663852886e38f);
+            if constexpr (BIAS)
+                v[c] = (p[j] * scale + rb[j]) + (mk[j] != 0 ? 0.f : -3.4028234663852886e38f);
+            else
+                v[c] = p[j] * scale + (mk[j] != 0 ? 0.f : -3.4028234663852886e38f);
             m = fmaxf(m, v[c]);
         } else {
             v[c] = -INFINITY;
@@ -75,13 +95,23 @@ __global__ void __launch_bounds__(256) softmax_mask_kernel(float* __restrict__ s
 // HF semantics kept: scores / sqrt(64) + (1 - mask) * finfo.min, soft-max over keys (modeling_bert.py).
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int kFaLdK = 132, kFaLdV = 72;
+// The fused kernels' bias table (BIAS): tab[t] = log2(e) x the bias of distance (key - query) = t - (L - 1) of head h, zero beyond
+// the 2 L - 1 distances of this length (a tile's padding keys and a block's padding queries read there; their scores are masked or
+// never stored, but must stay finite).  Query i, key j: tab[j - min(i, L - 1) + L - 1], j <= 511: an index in [0, 1022].
+constexpr int kRelTab = 1024;
+__device__ __forceinline__ void stage_rel_bias(float* tab, const float* __restrict__ rel_bias, int rel_span, int h, int L, int tid) {
+    const float* rb = rel_bias + (size_t)h * (2 * rel_span - 1) + (rel_span - L);
+    for (int t = tid; t < kRelTab; t += 256) tab[t] = t < 2 * L - 1 ? rb[t] * 1.44269504088896340736f : 0.f;
+}
 // ctxp (optional, instead of ctx): the context rows go out in the P layout [rows, 768] -- the A operand of the output projection
+template <bool BIAS>
 __global__ void __launch_bounds__(256, 2) flash_attn_f32_kernel(const float* __restrict__ qkv, const int64_t* __restrict__ mask,
                                                                 float* __restrict__ ctx, int L, int H, void* __restrict__ ctxp,
-                                                                int64_t rows) {
+                                                                int64_t rows, const float* __restrict__ rel_bias, int rel_span) {
     __shared__ __attribute__((aligned(16))) float Ks[64][kFaLdK];     // [dim][key]
     __shared__ __attribute__((aligned(16))) float Vs[128][kFaLdV];    // [key][dim]
     __shared__ float kbias[128];
+    __shared__ float rtab[BIAS ? kRelTab : 1];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 31, lk = lane >> 5;
     const int qblocks = (L + 127) / 128;
     const int qb = blockIdx.x % qblocks, h = (blockIdx.x / qblocks) % H, b = blockIdx.x / (qblocks * H);
@@ -89,6 +119,11 @@ __global__ void __launch_bounds__(256, 2) flash_attn_f32_kernel(const float* __r
     const float* base = qkv + (size_t)b * L * ld + h * 64;
     const int q_row = qb * 128 + wave * 32 + lr;                      // this lane's query
     const bool q_ok = q_row < L;
+    const float* rq = nullptr;                                         // BIAS: this lane's bias of key j (log2 units) at rq[j]
+    if constexpr (BIAS) {
+        stage_rel_bias(rtab, rel_bias, rel_span, h, L, tid);           // (read behind the key loop's barriers)
+        rq = rtab + (L - 1 - min(q_row, L - 1));
+    }
     // Q^T operand registers: step t = 8 G + j multiplies dims (16 G + j | 16 G + 8 + j) in lanes (< 32 | >= 32)
     float qreg[32];
     {
@@ -157,7 +192,10 @@ __global__ void __launch_bounds__(256, 2) flash_attn_f32_kernel(const float* __r
                 const int key = 32 * rb + 8 * (r >> 2) + 4 * lk + (r & 3);
                 // scores * (1/8) + mask, then to log2 units; the mask constant times log2(e) overflows to -inf, which
                 // exp2 maps to the same 0 that exp(-3.4e38 - max) gives
-                sacc[rb][r] = fmaf(sacc[rb][r], kScaleLog2, kbias[key] * 1.44269504088896340736f);
+                if constexpr (BIAS)
+                    sacc[rb][r] = fmaf(sacc[rb][r], kScaleLog2, rq[k0 + key]) + kbias[key] * 1.44269504088896340736f;
+                else
+                    sacc[rb][r] = fmaf(sacc[rb][r], kScaleLog2, kbias[key] * 1.44269504088896340736f);
                 tmax = fmaxf(tmax, sacc[rb][r]);
             }
         tmax = fmaxf(tmax, lane_xor<32>(tmax));
@@ -223,12 +261,14 @@ __global__ void __launch_bounds__(256, 2) flash_attn_f32_kernel(const float* __r
 //                  pieces XORed with the dim's low 4 bits).  V is transposed while it is staged: a thread owns 4 consecutive
 //                  keys x 8 dims and writes 8-byte runs of 4 keys.
 // ---------------------------------------------------------------------------------------------------------------
+template <bool BIAS>
 __global__ void __launch_bounds__(256, 2) flash_attn_f16x2_kernel(const float* __restrict__ qkv, const int64_t* __restrict__ mask,
                                                                   float* __restrict__ ctx, int L, int H, void* __restrict__ ctxp,
-                                                                  int64_t rows) {
+                                                                  int64_t rows, const float* __restrict__ rel_bias, int rel_span) {
     __shared__ __attribute__((aligned(16))) unsigned char Kp[2][128 * 128];    // [plane][key][64 dims fp16]
     __shared__ __attribute__((aligned(16))) unsigned char Vp[2][64 * 256];     // [plane][dim][128 key slots fp16]
     __shared__ float kbias[128];
+    __shared__ float rtab[BIAS ? kRelTab : 1];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 31, lk = lane >> 5;
     const int qblocks = (L + 127) / 128;
     // XCD-aware order (as the GEMMs'): XCD x = workgroup id mod 8 takes a contiguous run of the (document, head, query block) sequence, so the
@@ -243,6 +283,11 @@ __global__ void __launch_bounds__(256, 2) flash_attn_f16x2_kernel(const float* _
     const float* base = qkv + (size_t)b * L * ld + h * 64;
     const int q_row = qb * 128 + wave * 32 + lr;                      // this lane's query
     const bool q_ok = q_row < L;
+    const float* rq = nullptr;                                         // BIAS: this lane's bias of key j (log2 units) at rq[j]
+    if constexpr (BIAS) {
+        stage_rel_bias(rtab, rel_bias, rel_span, h, L, tid);           // (read behind the key loop's barriers)
+        rq = rtab + (L - 1 - min(q_row, L - 1));
+    }
     f16x8_t qh[4], ql[4];                                              // k step ks: dims 16 ks + 8 lk .. + 7
     {
         const float* qp = base + (size_t)min(q_row, L - 1) * ld + 8 * lk;
@@ -341,13 +386,20 @@ __global__ void __launch_bounds__(256, 2) flash_attn_f16x2_kernel(const float* _
         // ---- online soft-max over this tile's keys (registers of this lane + the other half-wave) -------------
         float tmax = -INFINITY;
 #pragma unroll
-        for (int rb = 0; rb < 4; ++rb)
+        for (int rb = 0; rb < 4; ++rb) {
+            // (BIAS: a compiler fence per key block keeps the table reads 16 at a time: hoisted together, all 64 of a tile cost two
+            // registers more than the 256 this kernel has)
+            if constexpr (BIAS) asm volatile("" ::: "memory");
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int key = 32 * rb + 8 * (r >> 2) + 4 * lk + (r & 3);
-                sacc[rb][r] = fmaf(sacc[rb][r], kScaleLog2, kbias[key] * 1.44269504088896340736f);
+                if constexpr (BIAS)
+                    sacc[rb][r] = fmaf(sacc[rb][r], kScaleLog2, rq[k0 + key]) + kbias[key] * 1.44269504088896340736f;
+                else
+                    sacc[rb][r] = fmaf(sacc[rb][r], kScaleLog2, kbias[key] * 1.44269504088896340736f);
                 tmax = fmaxf(tmax, sacc[rb][r]);
             }
+        }
         tmax = fmaxf(tmax, lane_xor<32>(tmax));
         const float m_new = fmaxf(m_run, tmax);
         const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);     // exp2(-inf) = 0 on the first tile
@@ -455,13 +507,15 @@ __device__ __forceinline__ f16x8_t lds_tr_pair(const unsigned char* a0, const un
 
 // KT = keys per tile: 128 (two workgroups per CU: 66 KB of LDS each) or 64 (ASPIRE_HIP_ATTN=p64: 33 KB and 32 accumulator registers fewer -- three per CU;
 // other tile edges, so other online-soft-max groupings: equal to the 128-key form to rounding, not bit for bit)
-template <int KT>
+template <int KT, bool BIAS>
 __device__ __forceinline__ void flash_attn_p_body(const unsigned char* __restrict__ qkvp, const int64_t* __restrict__ mask,
-                                                  float* __restrict__ ctx, int L, int H, void* __restrict__ ctxp, int64_t rows) {
+                                                  float* __restrict__ ctx, int L, int H, void* __restrict__ ctxp, int64_t rows,
+                                                  const float* __restrict__ rel_bias, int rel_span) {
     constexpr int NRB = KT / 32;                                               // 32-key blocks per tile
     __shared__ __attribute__((aligned(16))) unsigned char Kp[2][KT * 128];    // [plane][key][64 dims fp16], piece ^ ((key >> 1) & 7)
     __shared__ __attribute__((aligned(16))) unsigned char Vp[2][KT * 128];    // [plane][key][64 dims fp16], piece ^ 4 ((key >> 1) & 1)
     __shared__ float kbias[KT];
+    __shared__ float rtab[BIAS ? kRelTab : 1];
     const int tid = threadIdx.x, lane = tid & 63, lr = lane & 31, lk = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int qblocks = (L + 127) / 128;
@@ -474,6 +528,11 @@ __device__ __forceinline__ void flash_attn_p_body(const unsigned char* __restric
     const int64_t doc0 = (int64_t)b * L;                               // first row of the document
     const int q_row = qb * 128 + wave * 32 + lr;                       // this lane's query
     const bool q_ok = q_row < L;
+    const float* rq = nullptr;                                          // BIAS: this lane's bias of key j (log2 units) at rq[j]
+    if constexpr (BIAS) {
+        stage_rel_bias(rtab, rel_bias, rel_span, h, L, tid);            // (read behind tile 0's barriers X and Y)
+        rq = rtab + (L - 1 - min(q_row, L - 1));
+    }
     const size_t plane_b = (size_t)3 * H * rows * 128;                 // bytes of one plane
     f16x8_t qh[4], ql[4];                                              // k step ks: dims 16 ks + 8 lk .. + 7 = piece 2 ks + lk of the row
     {
@@ -561,7 +620,10 @@ __device__ __forceinline__ void flash_attn_p_body(const unsigned char* __restric
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int key = 32 * rb + 8 * (r >> 2) + 4 * lk + (r & 3);
-                sacc[rb][r] = fmaf(sacc[rb][r], kScaleLog2, kbias[key]);
+                if constexpr (BIAS)
+                    sacc[rb][r] = fmaf(sacc[rb][r], kScaleLog2, rq[k0 + key]) + kbias[key];
+                else
+                    sacc[rb][r] = fmaf(sacc[rb][r], kScaleLog2, kbias[key]);
                 tmax = fmaxf(tmax, sacc[rb][r]);
             }
         tmax = fmaxf(tmax, lane_xor<32>(tmax));
@@ -640,16 +702,18 @@ __device__ __forceinline__ void flash_attn_p_body(const unsigned char* __restric
     }
 }
 
+template <bool BIAS>
 __global__ void __launch_bounds__(256, 2) flash_attn_p_kernel(const unsigned char* __restrict__ qkvp, const int64_t* __restrict__ mask,
-                                                              float* __restrict__ ctx, int L, int H, void* __restrict__ ctxp, int64_t rows) {
-    flash_attn_p_body<128>(qkvp, mask, ctx, L, H, ctxp, rows);
+                                                              float* __restrict__ ctx, int L, int H, void* __restrict__ ctxp, int64_t rows,
+                                                              const float* __restrict__ rel_bias, int rel_span) {
+    flash_attn_p_body<128, BIAS>(qkvp, mask, ctx, L, H, ctxp, rows, rel_bias, rel_span);
 }
 #ifndef ASPIRE_ATTN64_WAVES      // (experiment builds: 2 = leave a third of the SIMD's registers to another stream's GEMM waves)
 #define ASPIRE_ATTN64_WAVES 3
 #endif
 __global__ void __launch_bounds__(256, ASPIRE_ATTN64_WAVES) flash_attn_p64_kernel(const unsigned char* __restrict__ qkvp, const int64_t* __restrict__ mask,
                                                                 float* __restrict__ ctx, int L, int H, void* __restrict__ ctxp, int64_t rows) {
-    flash_attn_p_body<64>(qkvp, mask, ctx, L, H, ctxp, rows);
+    flash_attn_p_body<64, false>(qkvp, mask, ctx, L, H, ctxp, rows, nullptr, 0);
 }
 
 // Attention of the CLS query alone, one workgroup per (document, head): softmax_j(q . k_j / 8 + (mask_j ? 0 : finfo.min)) v_j over the
@@ -731,31 +795,45 @@ __global__ void __launch_bounds__(256) cls_attn_kernel(const float* __restrict__
 
 }  // namespace
 
-int launch_softmax_mask(float* s, const int64_t* mask, int64_t rows, int L, int ld, int rows_per_doc, float scale, hipStream_t st) {
-    hipLaunchKernelGGL(softmax_mask_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, s, mask, rows, L, ld, rows_per_doc, scale);
+// rel_bias (all launchers below but the CLS query's): NULL = BertModel's attention, the kernels instantiated without the bias
+int launch_softmax_mask(float* s, const int64_t* mask, int64_t rows, int L, int ld, int rows_per_doc, float scale, const float* rel_bias,
+                        int rel_span, hipStream_t st) {
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    if (rel_bias)
+        hipLaunchKernelGGL(softmax_mask_kernel<true>, grid, dim3(256), 0, st, s, mask, rows, L, ld, rows_per_doc, scale, rel_bias, rel_span);
+    else
+        hipLaunchKernelGGL(softmax_mask_kernel<false>, grid, dim3(256), 0, st, s, mask, rows, L, ld, rows_per_doc, scale, rel_bias, rel_span);
     ASPIRE_LAUNCH_OK();
     return ASPIRE_OK;
 }
 
 // the fused kernels: one workgroup per (document, head, 128 queries)
 int launch_flash_attn(const float* qkv, const int64_t* mask, float* ctx, int64_t B, int L, int H, void* ctxp, int64_t rows, bool f32,
-                      hipStream_t st) {
-    const unsigned qblocks = (unsigned)((L + 127) / 128);
-    if (f32)
-        hipLaunchKernelGGL(flash_attn_f32_kernel, dim3((unsigned)(B * H) * qblocks), dim3(256), 0, st, qkv, mask, ctx, L, H, ctxp, rows);
+                      const float* rel_bias, int rel_span, hipStream_t st) {
+    const dim3 grid((unsigned)(B * H) * (unsigned)((L + 127) / 128));
+    if (f32 && rel_bias)
+        hipLaunchKernelGGL(flash_attn_f32_kernel<true>, grid, dim3(256), 0, st, qkv, mask, ctx, L, H, ctxp, rows, rel_bias, rel_span);
+    else if (f32)
+        hipLaunchKernelGGL(flash_attn_f32_kernel<false>, grid, dim3(256), 0, st, qkv, mask, ctx, L, H, ctxp, rows, rel_bias, rel_span);
+    else if (rel_bias)
+        hipLaunchKernelGGL(flash_attn_f16x2_kernel<true>, grid, dim3(256), 0, st, qkv, mask, ctx, L, H, ctxp, rows, rel_bias, rel_span);
     else
-        hipLaunchKernelGGL(flash_attn_f16x2_kernel, dim3((unsigned)(B * H) * qblocks), dim3(256), 0, st, qkv, mask, ctx, L, H, ctxp, rows);
+        hipLaunchKernelGGL(flash_attn_f16x2_kernel<false>, grid, dim3(256), 0, st, qkv, mask, ctx, L, H, ctxp, rows, rel_bias, rel_span);
     ASPIRE_LAUNCH_OK();
     return ASPIRE_OK;
 }
 
 int launch_flash_attn_p(const unsigned char* qkvp, const int64_t* mask, float* ctx, int64_t B, int L, int H, void* ctxp, int64_t rows,
-                        bool keys64, hipStream_t st) {
-    const unsigned qblocks = (unsigned)((L + 127) / 128);
+                        bool keys64, const float* rel_bias, int rel_span, hipStream_t st) {
+    ASPIRE_REQUIRE(!(keys64 && rel_bias), ASPIRE_ERR_UNSUPPORTED,
+                   "the 64-key attention form (ASPIRE_HIP_ATTN=p64) is not built with a relative-position bias");
+    const dim3 grid((unsigned)(B * H) * (unsigned)((L + 127) / 128));
     if (keys64)
-        hipLaunchKernelGGL(flash_attn_p64_kernel, dim3((unsigned)(B * H) * qblocks), dim3(256), 0, st, qkvp, mask, ctx, L, H, ctxp, rows);
+        hipLaunchKernelGGL(flash_attn_p64_kernel, grid, dim3(256), 0, st, qkvp, mask, ctx, L, H, ctxp, rows);
+    else if (rel_bias)
+        hipLaunchKernelGGL(flash_attn_p_kernel<true>, grid, dim3(256), 0, st, qkvp, mask, ctx, L, H, ctxp, rows, rel_bias, rel_span);
     else
-        hipLaunchKernelGGL(flash_attn_p_kernel, dim3((unsigned)(B * H) * qblocks), dim3(256), 0, st, qkvp, mask, ctx, L, H, ctxp, rows);
+        hipLaunchKernelGGL(flash_attn_p_kernel<false>, grid, dim3(256), 0, st, qkvp, mask, ctx, L, H, ctxp, rows, rel_bias, rel_span);
     ASPIRE_LAUNCH_OK();
     return ASPIRE_OK;
 }

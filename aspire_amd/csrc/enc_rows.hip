@@ -3,6 +3,7 @@
 // Kernels
 //   layernorm_kernel         y = LN(x) * gamma + beta, eps 1e-12; optionally also into the P layout (enc_planes.h)  (one wave per token)
 //   embed_layernorm_kernel   word + position + token-type gather, LayerNorm; same outputs                          (one wave per token)
+//                            the position row is the token's index (BertModel) or pos_ids[token] (RoBERTa / MPNet: aspire_bert_extras)
 //   cls_tap_kernel           the CLS row of every document of a hidden state (fp32 or planes) -> layer_cls, the layer mix, the last
 //                            layer's residual input (aspire_bert_forward_cls_f32)                                   (one wave per document)
 #include "enc_planes.h"
@@ -53,14 +54,14 @@ __global__ void __launch_bounds__(256) layernorm_kernel(const float* __restrict_
 }
 
 __global__ void __launch_bounds__(256) embed_layernorm_kernel(const int64_t* __restrict__ tok, const int64_t* __restrict__ typ,
-                                                              const float* __restrict__ word, const float* __restrict__ pos,
+                                                              const int64_t* __restrict__ pos_ids, const float* __restrict__ word, const float* __restrict__ pos,
                                                               const float* __restrict__ type_emb, const float* __restrict__ gamma,
                                                               const float* __restrict__ beta, float eps, float* __restrict__ y,
                                                               int64_t rows, int64_t L, void* __restrict__ yp) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
-    const int64_t t = tok[row], ty = typ ? typ[row] : 0, p = row % L;
+    const int64_t t = tok[row], ty = typ ? typ[row] : 0, p = pos_ids ? pos_ids[row] : row % L;
     float4 v[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -68,7 +69,8 @@ __global__ void __launch_bounds__(256) embed_layernorm_kernel(const int64_t* __r
         const float4 a = *reinterpret_cast<const float4*>(word + t * kD + d);
         const float4 b = *reinterpret_cast<const float4*>(type_emb + ty * kD + d);
         const float4 e = *reinterpret_cast<const float4*>(pos + p * kD + d);
-        // BertEmbeddings: inputs_embeds + token_type_embeddings, then + position_embeddings
+        // BertEmbeddings / RobertaEmbeddings: inputs_embeds + token_type_embeddings, then + position_embeddings (MPNet has no token
+        // types: its one type row is zero, and (a + 0) + e = a + e)
         v[c] = make_float4((a.x + b.x) + e.x, (a.y + b.y) + e.y, (a.z + b.z) + e.z, (a.w + b.w) + e.w);
     }
     layernorm_row(v, gamma, beta, eps, y + row * kD, lane, yp, rows, row);
@@ -110,10 +112,11 @@ int launch_layernorm(const float* x, const float* gamma, const float* beta, floa
     return ASPIRE_OK;
 }
 
-int launch_embed_layernorm(const int64_t* tok, const int64_t* typ, const float* word, const float* pos, const float* type_emb,
-                           const float* gamma, const float* beta, float eps, float* y, int64_t rows, int64_t L, void* yp, hipStream_t st) {
-    hipLaunchKernelGGL(embed_layernorm_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, tok, typ, word, pos, type_emb, gamma, beta,
-                       eps, y, rows, L, yp);
+int launch_embed_layernorm(const int64_t* tok, const int64_t* typ, const int64_t* pos_ids, const float* word, const float* pos,
+                           const float* type_emb, const float* gamma, const float* beta, float eps, float* y, int64_t rows, int64_t L,
+                           void* yp, hipStream_t st) {
+    hipLaunchKernelGGL(embed_layernorm_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, tok, typ, pos_ids, word, pos, type_emb,
+                       gamma, beta, eps, y, rows, L, yp);
     ASPIRE_LAUNCH_OK();
     return ASPIRE_OK;
 }

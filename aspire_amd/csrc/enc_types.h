@@ -83,19 +83,23 @@ int launch_gemm_p_ln(const PGemmArgs& g, hipStream_t st);
 bool ln_fused_supported();
 
 // enc_attn.hip: the masked soft-max of the three-kernel form, fused attention on fp32 Q / K / V (f32: fp32-input MFMAs, else fp16
-// planes split in the kernel) and on the QKV GEMM's planes (keys64: 64-key tiles), and the CLS query's attention
-int launch_softmax_mask(float* s, const int64_t* mask, int64_t rows, int L, int ld, int rows_per_doc, float scale, hipStream_t st);
+// planes split in the kernel) and on the QKV GEMM's planes (keys64: 64-key tiles), and the CLS query's attention.
+// rel_bias [H][2 rel_span - 1] or NULL: aspire_bert_extras' relative-position bias (keys64 with it: ASPIRE_ERR_UNSUPPORTED)
+int launch_softmax_mask(float* s, const int64_t* mask, int64_t rows, int L, int ld, int rows_per_doc, float scale, const float* rel_bias,
+                        int rel_span, hipStream_t st);
 int launch_flash_attn(const float* qkv, const int64_t* mask, float* ctx, int64_t B, int L, int H, void* ctxp, int64_t rows, bool f32,
-                      hipStream_t st);
+                      const float* rel_bias, int rel_span, hipStream_t st);
 int launch_flash_attn_p(const unsigned char* qkvp, const int64_t* mask, float* ctx, int64_t B, int L, int H, void* ctxp, int64_t rows,
-                        bool keys64, hipStream_t st);
+                        bool keys64, const float* rel_bias, int rel_span, hipStream_t st);
 int launch_cls_attn(const float* qkv, const unsigned char* qkvp, const int64_t* mask, float* ctx, int64_t B, int L, int H, int64_t rows,
                     hipStream_t st);
 
-// enc_rows.hip: one wave per row of 768 -- LayerNorm, embeddings + LayerNorm, the CLS rows of a hidden state
+// enc_rows.hip: one wave per row of 768 -- LayerNorm, embeddings + LayerNorm (pos_ids [rows] or NULL: the row of pos each token takes,
+// NULL = its index in the document), the CLS rows of a hidden state
 int launch_layernorm(const float* x, const float* gamma, const float* beta, float eps, float* y, int64_t rows, void* yp, hipStream_t st);
-int launch_embed_layernorm(const int64_t* tok, const int64_t* typ, const float* word, const float* pos, const float* type_emb,
-                           const float* gamma, const float* beta, float eps, float* y, int64_t rows, int64_t L, void* yp, hipStream_t st);
+int launch_embed_layernorm(const int64_t* tok, const int64_t* typ, const int64_t* pos_ids, const float* word, const float* pos,
+                           const float* type_emb, const float* gamma, const float* beta, float eps, float* y, int64_t rows, int64_t L,
+                           void* yp, hipStream_t st);
 int launch_cls_tap(const float* x, const void* xp, int64_t rows, int64_t L, int64_t B, float wt, int mode, float* cls_out, float* layer_cls,
                    float* gather, hipStream_t st);
 

@@ -13,6 +13,11 @@
 // cores (v_mfma_f32_32x32x2_f32: exact fp32 FMA chains, 157 TFLOP/s peak on MI355X -- still the figure the encoder's
 // throughput is quoted against, so the split forms can exceed 100 % of it).  Plain bf16 inputs give ~1e-2: not an option.
 //
+// A1d: the same forward for the BERT-shaped encoders of the SentenceTransformer baselines (src/evaluation/utils/models.py:379-410:
+// SentenceModel.encode = SentenceTransformer(name).encode; RobertaModel, MPNetModel): aspire_bert_forward_var_f32 takes the position
+// row of every token from a table (aspire_bert_extras::pos_ids) and adds MPNet's relative-position bias to the attention scores
+// (::rel_bias); without either it is aspire_bert_forward_f32 launch for launch.  The masked-mean read-out behind it is pool.hip's.
+//
 // This file is host only: the workspace, the forward's plan (plan_forward), one layer of it (run_layer), the CLS forward's tail and the C entry
 // points (aspire_bert_status and the clock build's aspire_debug_gemm_buffer sit with their device globals in enc_gemm_p.hip).  The kernels and their launch rules, one unit per family, each
 // kernel launched from one host function of its unit (enc_types.h declares them):
@@ -100,6 +105,9 @@ PlaneOffsets plane_offsets(int ffn_dim) {
 struct Fwd {
     const aspire_bert_weights* w;
     const int64_t* mask;
+    const int64_t* pos_ids;         // aspire_bert_extras (forward_var): NULL = BertModel's positions / no bias
+    const float* rel_bias;
+    int rel_span;
     int64_t B, L, M, row_tiles;
     int Lp, H, dh;
     bool pp, ln_fused, attn_p;
@@ -122,6 +130,9 @@ int check_forward_args(const aspire_bert_weights* w, const int64_t* tok_ids, con
 int plan_forward(Fwd& f, const aspire_bert_weights* w, const int64_t* attn_mask, int64_t B, int64_t L, void* workspace, hipStream_t st) {
     f.w = w;
     f.mask = attn_mask;
+    f.pos_ids = nullptr;
+    f.rel_bias = nullptr;
+    f.rel_span = 0;
     f.B = B;
     f.L = L;
     f.st = st;
@@ -152,7 +163,7 @@ int plan_forward(Fwd& f, const aspire_bert_weights* w, const int64_t* attn_mask,
 // embeddings + LayerNorm -> x (fp32) and, on the P path, actp; then the LayerNorm-epilogue counters of this forward
 int launch_embed(const Fwd& f, const int64_t* tok_ids, const int64_t* type_ids, float* x) {
     const aspire_bert_weights* w = f.w;
-    if (int rc = launch_embed_layernorm(tok_ids, type_ids, w->word_emb, w->pos_emb, w->type_emb, w->emb_ln_g, w->emb_ln_b, w->ln_eps, x, f.M, f.L,
+    if (int rc = launch_embed_layernorm(tok_ids, type_ids, f.pos_ids, w->word_emb, w->pos_emb, w->type_emb, w->emb_ln_g, w->emb_ln_b, w->ln_eps, x, f.M, f.L,
                                         f.pp && w->n_layers > 0 ? f.ws.actp : nullptr, f.st))
         return rc;
     // the P layout's slot offsets are 32-bit byte offsets (p_slot / p_slot8: ((k >> 4) R + r) << 6): the widest operand is [M, ffn_dim]
@@ -196,9 +207,12 @@ int run_layer(const Fwd& f, int l, const float* x, float* out, bool last, bool q
     // 2-4. attention.  Fused kernel (scores never leave the chip) unless ASPIRE_HIP_ATTN=gemm pins the
     // three-kernel form (QK^T GEMM, masked soft-max, PV GEMM) that the fused one is tested against.
     if (attn_p) {
-        if (int rc = launch_flash_attn_p(ws.qkvp, attn_mask, ws.ctx, B, (int)L, H, ws.ctxp, M, tuning().attn_form == 2, st)) return rc;
+        if (int rc = launch_flash_attn_p(ws.qkvp, attn_mask, ws.ctx, B, (int)L, H, ws.ctxp, M, tuning().attn_form == 2, f.rel_bias, f.rel_span, st))
+            return rc;
     } else if (dh == 64 && !tuning().attn_gemm) {
-        if (int rc = launch_flash_attn(ws.qkv, attn_mask, ws.ctx, B, (int)L, H, pp ? ws.ctxp : nullptr, M, tuning().attn_f32 != 0, st)) return rc;
+        if (int rc = launch_flash_attn(ws.qkv, attn_mask, ws.ctx, B, (int)L, H, pp ? ws.ctxp : nullptr, M, tuning().attn_f32 != 0, f.rel_bias,
+                                       f.rel_span, st))
+            return rc;
     } else {
         // 2. scores[b,h] = Q_bh . K_bh^T   (scale and mask are applied by the softmax kernel)
         g = GemmArgs{};
@@ -209,7 +223,8 @@ int run_layer(const Fwd& f, int l, const float* x, float* out, bool last, bool q
         if (int rc = launch_gemm(g, (int)(B * H), false, st)) return rc;
         // 3. masked softmax over keys
         const int64_t srows = B * H * L;
-        if (int rc = launch_softmax_mask(ws.scores, attn_mask, srows, (int)L, Lp, (int)(H * L), 1.0f / sqrtf((float)dh), st)) return rc;
+        if (int rc = launch_softmax_mask(ws.scores, attn_mask, srows, (int)L, Lp, (int)(H * L), 1.0f / sqrtf((float)dh), f.rel_bias, f.rel_span, st))
+            return rc;
         // 4. ctx[b, :, h*64:(h+1)*64] = P_bh . V_bh        (V is [K = L keys, N = 64] n-contiguous)
         g = GemmArgs{};
         g.A = ws.scores; g.B = ws.qkv + 2 * kD; g.C = ws.ctx;
@@ -301,15 +316,33 @@ extern "C" size_t aspire_bert_workspace_bytes(const aspire_bert_weights* w, int6
     return carve(nullptr, B, L, w->n_heads, w->ffn_dim, w->n_layers).total;
 }
 
+// BertModel's forward is the forward below without extras: one body, so the two cannot drift apart
 extern "C" int aspire_bert_forward_f32(const aspire_bert_weights* w, const int64_t* tok_ids, const int64_t* type_ids,
                                        const int64_t* attn_mask, int64_t B, int64_t L, float* hidden_out, void* workspace,
                                        size_t workspace_bytes, void* stream) {
+    return aspire_bert_forward_var_f32(w, nullptr, tok_ids, type_ids, attn_mask, B, L, hidden_out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int aspire_bert_forward_var_f32(const aspire_bert_weights* w, const aspire_bert_extras* x_, const int64_t* tok_ids,
+                                           const int64_t* type_ids, const int64_t* attn_mask, int64_t B, int64_t L, float* hidden_out,
+                                           void* workspace, size_t workspace_bytes, void* stream) {
     if (int rc = check_forward_args(w, tok_ids, attn_mask, hidden_out, B, L)) return rc;
+    ASPIRE_REQUIRE(!x_ || !x_->rel_bias || x_->rel_span >= L, ASPIRE_ERR_INVALID_ARG,
+                   "rel_span %d < sequence length %lld: the bias table does not cover every (query, key) distance", x_ ? x_->rel_span : 0,
+                   (long long)L);
     if (B == 0) return ASPIRE_OK;
     const size_t need = carve(nullptr, B, L, w->n_heads, w->ffn_dim, w->n_layers).total;
     ASPIRE_REQUIRE(workspace && workspace_bytes >= need, ASPIRE_ERR_INVALID_ARG, "workspace too small: need %zu bytes", need);
     Fwd f;
     if (int rc = plan_forward(f, w, attn_mask, B, L, workspace, (hipStream_t)stream)) return rc;
+    if (x_) {
+        f.pos_ids = x_->pos_ids;
+        f.rel_bias = x_->rel_bias;
+        f.rel_span = x_->rel_bias ? x_->rel_span : 0;
+    }
+    // (the 64-key attention form is not built with the bias: refused here, before the embedding launch, not in layer 0)
+    ASPIRE_REQUIRE(!(f.rel_bias && f.attn_p && tuning().attn_form == 2), ASPIRE_ERR_UNSUPPORTED,
+                   "the 64-key attention form (ASPIRE_HIP_ATTN=p64) is not built with a relative-position bias");
     float* x = w->n_layers == 0 ? hidden_out : f.ws.x;
     if (int rc = launch_embed(f, tok_ids, type_ids, x)) return rc;
     for (int l = 0; l < w->n_layers; ++l) {

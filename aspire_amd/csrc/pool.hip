@@ -1,4 +1,4 @@
-// A2 + A3: CLS read-out and span mean pooling.
+// A2 + A3: CLS read-out and span mean pooling; A1d's masked token mean (token_mean_pool_kernel, further down).
 // Reference: AspireConSent.consent_reps_bert, examples/ex_aspire_consent.py:75-100 -- one full
 // [B, L, 768] mask-multiply-sum pass per sentence slot.  Here every token row is read at most once:
 // one workgroup of 192 threads per (document, sentence slot); thread t owns the float4 at d = 4t, so a
@@ -109,6 +109,48 @@ __global__ void __launch_bounds__(192) span_pool_ranges_kernel(const float* __re
     *reinterpret_cast<float4*>(rows + (size_t)orow * kD + d) = acc;
 }
 
+// A1d's read-out: sentence-transformers' Pooling in mean mode and its Normalize module (SentenceModel.encode,
+// src/evaluation/utils/models.py:392-406, through SentenceTransformer.encode).  One 192-thread workgroup per sentence, thread t owns
+// the float4 at d = 4t as above; the token rows with mask != 0 are summed in token order, eight in flight per thread, rows of masked
+// tokens are never read (the mask words are the same for the whole workgroup: the skip is a uniform branch).  Then / max(count, 1e-9)
+// (torch.clamp(sum_mask, min=1e-9)) and, with normalize, / max(||x||_2, 1e-12) (F.normalize): the 768 squares summed per thread, per
+// wave and over the three waves through LDS.  A sentence without a valid token gives exact zeros (0 / 1e-9, then 0 / 1e-12).
+__global__ void __launch_bounds__(192) token_mean_pool_kernel(const float* __restrict__ hidden, const int64_t* __restrict__ mask, int64_t L,
+                                                              int normalize, float* __restrict__ out) {
+    __shared__ float part[3];
+    const int64_t b = blockIdx.x;
+    const int d = threadIdx.x * 4;
+    const float* src = hidden + (size_t)b * L * kD + d;
+    const int64_t* mk = mask + b * L;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    int count = 0;
+    for (int64_t t = 0; t < L; t += 8) {
+        float4 v[8];
+        bool on[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            on[u] = t + u < L && mk[min(t + u, L - 1)] != 0;
+            if (on[u]) v[u] = ld4_stream(src + (size_t)(t + u) * kD);
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            if (on[u]) {
+                acc.x += v[u].x; acc.y += v[u].y; acc.z += v[u].z; acc.w += v[u].w;
+                ++count;
+            }
+    }
+    const float cnt = fmaxf((float)count, 1e-9f);
+    acc.x /= cnt; acc.y /= cnt; acc.z /= cnt; acc.w /= cnt;
+    if (normalize) {
+        const float q = wave_sum((acc.x * acc.x + acc.y * acc.y) + (acc.z * acc.z + acc.w * acc.w));
+        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = q;
+        __syncthreads();
+        const float nrm = fmaxf(sqrtf((part[0] + part[1]) + part[2]), 1e-12f);
+        acc.x /= nrm; acc.y /= nrm; acc.z /= nrm; acc.w /= nrm;
+    }
+    *reinterpret_cast<float4*>(out + (size_t)b * kD + d) = acc;
+}
+
 // caching_score's document-level term: ||q_cls - c_cls + eps||_2 (torch.nn.functional.pairwise_distance), one wave per
 // pair, 12 coordinates per lane.
 __global__ void __launch_bounds__(256) cls_l2_kernel(const float* __restrict__ q_cls, int64_t Q, const float* __restrict__ c_cls,
@@ -197,6 +239,20 @@ extern "C" int aspire_span_pool_ranges_f32(const float* hidden, int64_t B, int64
     ASPIRE_REQUIRE(row_blocks + cls_blocks <= 0x7fffffffLL, ASPIRE_ERR_UNSUPPORTED, "%lld rows in one call", (long long)R);
     hipLaunchKernelGGL(span_pool_ranges_kernel, dim3((unsigned)(row_blocks + cls_blocks)), dim3(192), 0, (hipStream_t)stream,
                        hidden, B, L, row_doc, row_start, row_len, R, out_row, rows, cls_reps);
+    ASPIRE_LAUNCH_OK();
+    return ASPIRE_OK;
+}
+
+extern "C" int aspire_token_mean_pool_f32(const float* hidden, const int64_t* attn_mask, int64_t B, int64_t L, int64_t D, int normalize,
+                                          float* out, void* stream) {
+    ASPIRE_REQUIRE(D == kD, ASPIRE_ERR_UNSUPPORTED, "encoding dim %lld unsupported (kernels are built for 768)", (long long)D);
+    ASPIRE_REQUIRE(B >= 0 && L > 0, ASPIRE_ERR_INVALID_ARG, "bad shape B=%lld L=%lld", (long long)B, (long long)L);
+    if (B == 0) return ASPIRE_OK;
+    ASPIRE_REQUIRE(hidden && attn_mask && out, ASPIRE_ERR_INVALID_ARG, "null pointer");
+    ASPIRE_REQUIRE(((uintptr_t)hidden & 15) == 0 && ((uintptr_t)out & 15) == 0, ASPIRE_ERR_INVALID_ARG,
+                   "hidden and out must be 16-byte aligned");
+    ASPIRE_REQUIRE(B <= 0x7fffffffLL, ASPIRE_ERR_UNSUPPORTED, "%lld sentences in one call", (long long)B);
+    hipLaunchKernelGGL(token_mean_pool_kernel, dim3((unsigned)B), dim3(192), 0, (hipStream_t)stream, hidden, attn_mask, L, normalize, out);
     ASPIRE_LAUNCH_OK();
     return ASPIRE_OK;
 }

@@ -7,19 +7,57 @@ makes on it: ``encoder(tokid_tt, token_type_ids=seg_tt, attention_mask=attnmask_
 projections are one GEMM.  The bi-encoders' CLS read-out (aspire_bert_forward_cls_f32) runs on the same weights
 (forward_cls), the pooler (aspire_bert_pooler_f32) behind it where the model has one (forward_pooled), and run_checked is the
 one fall-back rule every model class applies to what it hands out.
+
+The encoder also takes a ``RobertaModel`` or an ``MPNetModel`` (the SentenceTransformer baselines, aspire_amd/sbert.py): their
+forward is aspire_bert_forward_var_f32 with the position ids those models number real tokens by (position_ids_from_input_ids)
+and, for MPNet, the relative-position bias expanded per distance (relative_bias_table); forward_mean is the masked-mean read-out
+(aspire_token_mean_pool_f32) behind it.  Nothing changes for a BertModel.
 """
 import ctypes
+import math
 import warnings
 from types import SimpleNamespace
 
 import torch
 
 from . import ops
-from ._lib import BertLayer, BertWeights, check, lib, pinned
+from ._lib import BertExtras, BertLayer, BertWeights, check, lib, pinned
 
 _LAYER_KEYS = ('attention.output.dense.weight', 'attention.output.dense.bias', 'attention.output.LayerNorm.weight',
                'attention.output.LayerNorm.bias', 'intermediate.dense.weight', 'intermediate.dense.bias', 'output.dense.weight',
                'output.dense.bias', 'output.LayerNorm.weight', 'output.LayerNorm.bias')
+
+
+# MPNetLayer's parameter names in struct aspire_bert_layer's order behind w_qkv / b_qkv
+_MPNET_LAYER_KEYS = ('attention.attn.o.weight', 'attention.attn.o.bias', 'attention.LayerNorm.weight', 'attention.LayerNorm.bias',
+                     'intermediate.dense.weight', 'intermediate.dense.bias', 'output.dense.weight', 'output.dense.bias',
+                     'output.LayerNorm.weight', 'output.LayerNorm.bias')
+REL_SPAN = 512          # the bias table covers key - query in (-512, 512): every distance of the forward's L <= 512
+
+
+def position_ids_from_input_ids(ids, padding_idx):
+    """HF create_position_ids_from_input_ids (modeling_roberta.py, modeling_mpnet.py): real tokens count from padding_idx + 1,
+    pad tokens get padding_idx.  int64 [B, L], on ids' device."""
+    real = (ids != padding_idx).to(torch.int64)
+    return torch.cumsum(real, dim=1) * real + padding_idx
+
+
+def relative_bias_table(weight, span=REL_SPAN, num_buckets=32, max_distance=128):
+    """MPNetEncoder.compute_position_bias per distance: float32 [n_heads, 2 span - 1], entry [h, (j - i) + span - 1] the bias of
+    (query i, key j).  weight: relative_attention_bias.weight [num_buckets, n_heads].  The bucket arithmetic is HF's
+    relative_position_bucket operation for operation (torch, the logarithm in float32), so bucket edges fall where HF puts them;
+    the bias depends on j - i alone (compute_position_bias is called without position ids: the indices, not the RoBERTa-style ids)."""
+    rel = torch.arange(-(span - 1), span, dtype=torch.long)        # memory_position - context_position
+    n = -rel
+    half = num_buckets // 2
+    ret = (n < 0).to(torch.long) * half
+    n = torch.abs(n)
+    max_exact = half // 2
+    is_small = n < max_exact
+    val_if_large = max_exact + (torch.log(n.float() / max_exact) / math.log(max_distance / max_exact) * (half - max_exact)).to(torch.long)
+    val_if_large = torch.min(val_if_large, torch.full_like(val_if_large, half - 1))
+    bucket = ret + torch.where(is_small, n, val_if_large)
+    return weight.detach().to(device='cpu', dtype=torch.float32)[bucket].t().contiguous()
 
 
 def pack_weights(weights, n_heads, ln_eps):
@@ -75,16 +113,26 @@ class HipBertEncoder:
         sd = {k: v.detach() for k, v in bert_model.state_dict().items()}
         self.config = cfg
         self.device = dev
-        pre = 'bert.' if any(k.startswith('bert.') for k in sd) else ''
+        # 'bert': BertModel.  'roberta' / 'mpnet': position ids from the token ids (padding_idx: RobertaEmbeddings takes the config's
+        # pad_token_id, MPNetEmbeddings always 1), MPNet also the relative-position bias and no token types
+        self.kind = kind = cfg.model_type if getattr(cfg, 'model_type', None) in ('roberta', 'mpnet') else 'bert'
+        self.padding_idx = {'bert': None, 'roberta': cfg.pad_token_id, 'mpnet': 1}[kind]
+        pre = next((p for p in ('bert.', 'roberta.', 'mpnet.') if any(k.startswith(p) for k in sd)), '')
         emb = pre + 'embeddings.'
-        w = [sd[emb + k] for k in ('word_embeddings.weight', 'position_embeddings.weight', 'token_type_embeddings.weight',
-                                   'LayerNorm.weight', 'LayerNorm.bias')]
+        w = [sd[emb + k] for k in ('word_embeddings.weight', 'position_embeddings.weight')]
+        # (MPNet: one zero row stands for the token-type table: (word + 0) + position is exact)
+        w.append(torch.zeros(1, cfg.hidden_size) if kind == 'mpnet' else sd[emb + 'token_type_embeddings.weight'])
+        w += [sd[emb + k] for k in ('LayerNorm.weight', 'LayerNorm.bias')]
         for i in range(cfg.num_hidden_layers):
             p = f'{pre}encoder.layer.{i}.'
-            att = p + 'attention.self.'
-            w += [torch.cat([sd[att + 'query.weight'], sd[att + 'key.weight'], sd[att + 'value.weight']], 0),
-                  torch.cat([sd[att + 'query.bias'], sd[att + 'key.bias'], sd[att + 'value.bias']], 0)]
-            w += [sd[p + k] for k in _LAYER_KEYS]
+            att = p + ('attention.attn.' if kind == 'mpnet' else 'attention.self.')
+            q, k, v = ('q', 'k', 'v') if kind == 'mpnet' else ('query', 'key', 'value')
+            w += [torch.cat([sd[att + q + '.weight'], sd[att + k + '.weight'], sd[att + v + '.weight']], 0),
+                  torch.cat([sd[att + q + '.bias'], sd[att + k + '.bias'], sd[att + v + '.bias']], 0)]
+            w += [sd[p + k] for k in (_MPNET_LAYER_KEYS if kind == 'mpnet' else _LAYER_KEYS)]
+        self._rel_bias = None
+        if kind == 'mpnet':
+            self._rel_bias = relative_bias_table(sd[pre + 'encoder.relative_attention_bias.weight']).to(dev)
         self._w = pack_weights([t.to(device=dev, dtype=torch.float32) for t in w], cfg.num_attention_heads, cfg.layer_norm_eps)
         # HF BertPooler's dense layer, where the model has one (forward_pooled); it is no part of struct aspire_bert_weights
         self._pooler = None
@@ -141,22 +189,50 @@ class HipBertEncoder:
         with pinned(GEMM='bf16x3', ATTN='f32'):
             return self.forward_hidden(tokid_tt, token_type_ids, attention_mask, check_ids=False)
 
+    def _extras(self, tok):
+        """struct aspire_bert_extras of a RoBERTa / MPNet forward over the device ids tok (None for a BertModel), and the tensors it
+        points to.  The position ids are at most padding_idx + L by construction: checked against the table's rows without a sync."""
+        if self.kind == 'bert':
+            return None, None
+        if self.padding_idx + tok.shape[1] >= self.config.max_position_embeddings:
+            raise IndexError(f'{tok.shape[1]} tokens: position ids reach {self.padding_idx + tok.shape[1]}, beyond '
+                             f'max_position_embeddings={self.config.max_position_embeddings}')
+        pos = position_ids_from_input_ids(tok, self.padding_idx).contiguous()
+        x = BertExtras(ctypes.c_void_p(pos.data_ptr()), ops._ptr(self._rel_bias), REL_SPAN if self._rel_bias is not None else 0)
+        return x, pos
+
     def forward_hidden(self, tokid_tt, token_type_ids=None, attention_mask=None, check_ids=True):
         """int64 [B, L] tensors (any device) -> last_hidden_state [B, L, 768] on the GPU.  check_ids=False: the caller has
-        validated the token ids already (encode_to_pool checks all its batches with one device round trip)."""
+        validated the token ids already (encode_to_pool checks all its batches with one device round trip).  A RoBERTa / MPNet
+        encoder runs aspire_bert_forward_var_f32 (MPNet takes no token types: they are ignored, as MPNetModel ignores them)."""
         tok, typ, msk = self.device_inputs(tokid_tt, token_type_ids, attention_mask, check_ids)
         b, l = tok.shape
         out = torch.empty(b, l, 768, device=self.device, dtype=torch.float32)
         ws = self._workspace(lib.aspire_bert_workspace_bytes(ctypes.byref(self._w), b, l))
-        check(lib.aspire_bert_forward_f32(ctypes.byref(self._w), ops._ptr(tok), ops._ptr(typ), ops._ptr(msk), b, l,
-                                          ops._ptr(out), ops._ptr(ws), ws.numel(), ops._stream()))
+        if self.kind == 'bert':
+            check(lib.aspire_bert_forward_f32(ctypes.byref(self._w), ops._ptr(tok), ops._ptr(typ), ops._ptr(msk), b, l,
+                                              ops._ptr(out), ops._ptr(ws), ws.numel(), ops._stream()))
+            return out
+        x, _pos = self._extras(tok)         # (_pos: alive until the launches are queued; the stream orders its reuse)
+        check(lib.aspire_bert_forward_var_f32(ctypes.byref(self._w), ctypes.byref(x), ops._ptr(tok),
+                                              None if self.kind == 'mpnet' else ops._ptr(typ), ops._ptr(msk), b, l, ops._ptr(out),
+                                              ops._ptr(ws), ws.numel(), ops._stream()))
         return out
+
+    def forward_mean(self, tokid_tt, token_type_ids=None, attention_mask=None, normalize=False, check_ids=True):
+        """sentence-transformers' read-out: int64 [B, L] tensors (any device) -> the mean of last_hidden_state over the tokens with
+        attention_mask != 0 [B, 768] on the GPU (Pooling in mean mode), with normalize divided by max(its L2 norm, 1e-12)
+        (Normalize): forward_hidden, then aspire_token_mean_pool_f32.  check_ids as forward_hidden."""
+        tok, typ, msk = self.device_inputs(tokid_tt, token_type_ids, attention_mask, check_ids)
+        return ops.token_mean_pool(self.forward_hidden(tok, typ, msk, check_ids=False), msk, normalize)
 
     def forward_cls(self, tokid_tt, token_type_ids=None, attention_mask=None, layer_mix=None, want_layers=False, check_ids=True):
         """The bi-encoders' read-out (aspire_bert_forward_cls_f32): int64 [B, L] tensors (any device) -> (the CLS rows of the
         layer_mix-weighted sum of the n_layers + 1 hidden states [B, 768] -- of the last hidden state alone when layer_mix is None --,
         the CLS rows of every hidden state [n_layers + 1, B, 768] with want_layers, else None), on the GPU.  layer_mix: n_layers + 1
         float32 weights, already softmaxed.  check_ids as forward_hidden."""
+        if self.kind != 'bert':
+            raise NotImplementedError(f'forward_cls: the CLS-only forward is built for BertModel, not {self.kind}')
         tok, typ, msk = self.device_inputs(tokid_tt, token_type_ids, attention_mask, check_ids)
         b, l = tok.shape
         dev = self.device

@@ -64,7 +64,7 @@ MODEL_TABLE = {
     'cospecter': AspireBiEnc,
     'cosentbert': AspireSentEnc, 'ictsentbert': AspireSentEnc,
 }
-SENTENCE_TRANSFORMER_NAMES = ('sbtinybertsota', 'sbrobertanli', 'sbmpnet1B')       # SentenceModel, models.py:379-410
+SENTENCE_TRANSFORMER_NAMES = ('sbtinybertsota', 'sbrobertanli', 'sbmpnet1B')       # SentenceModel, models.py:379-410: aspire_amd/sbert.py
 
 
 def _default_hf_name(kw, name):
@@ -79,7 +79,8 @@ def get_model(model_name, trained_model_path=None, **kw):
     downloaded when both are given).  trained_model_path: the run directory of 'cospecter' (run_info.json + model_cur_best.pt,
     models.py:522-555) or of 'cosentbert' / 'ictsentbert' (sent_encoder_cur_best.pt, models.py:573-582)."""
     if model_name in SENTENCE_TRANSFORMER_NAMES:
-        raise NotImplementedError(f'{model_name}: the SentenceTransformer baselines (RoBERTa / MPNet encoders) are not built')
+        raise NotImplementedError(f'{model_name}: the SentenceTransformer baselines (TinyBERT / RoBERTa / MPNet encoders) are not built '
+                                  f'into get_model: construct aspire_amd.SentenceModel({model_name!r}, model=..., tokenizer=...)')
     if model_name not in MODEL_TABLE:
         raise NotImplementedError(f"No Implementation for model {model_name}")
     cls = MODEL_TABLE[model_name]

@@ -327,6 +327,18 @@ def bert_pooler(cls, weight, bias):
     return out
 
 
+def token_mean_pool(hidden, mask, normalize=False):
+    """sentence-transformers' Pooling(mean) [+ Normalize] (aspire_token_mean_pool_f32): hidden [B, L, 768] fp32, mask [B, L] (non-zero
+    = real token) -> [B, 768] on the GPU: the masked mean of the token rows, then, with normalize, x / max(||x||, 1e-12)."""
+    _f32(hidden, 'hidden')
+    assert hidden.dim() == 3 and tuple(mask.shape) == tuple(hidden.shape[:2]), 'token_mean_pool: hidden [B, L, D], mask [B, L]'
+    mask = mask.to(device=hidden.device, dtype=torch.int64).contiguous()
+    b, l, d = hidden.shape
+    out = torch.empty(b, d, device=hidden.device, dtype=torch.float32)
+    check(lib.aspire_token_mean_pool_f32(_ptr(hidden), _ptr(mask), b, l, d, 1 if normalize else 0, _ptr(out), _stream()))
+    return out
+
+
 def _ot_params(c, blur, scaling, sent_sm_temp, cdist_mode, one_form):
     """struct aspire_ot_params of an otAspire call with its flag word: ONE_FORM as the caller asks, CENTER from the candidates' rows
     (DeviceRepSet.center_hint)."""

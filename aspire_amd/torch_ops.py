@@ -11,6 +11,7 @@ implementation so that shapes propagate under FakeTensor / torch.compile tracing
     torch.ops.aspire.bert_cls_forward(ids, type_ids, mask, weights, n_heads, ln_eps, layer_mix) -> cls [B, 768]
                                                                                    A1b  ex_aspire_bienc.py:23-58
     torch.ops.aspire.bert_pooler(cls, weight, bias) -> pooled [B, 768]                             A1c  models.py:350
+    torch.ops.aspire.token_mean_pool(hidden, mask, normalize) -> reps [B, 768]                     A1d  models.py:402
     torch.ops.aspire.l2max_scores(q, q_lens, c, c_lens, paired) -> scores                          A9   pair_distances.py:138-186
     torch.ops.aspire.ot_sinkhorn_scores(q, q_lens, c, c_lens, blur, scaling, temp, group, want, paired, extras)
                                          -> (scores, q_distr, c_distr, pair_sims, plan)           A5-A8 pair_distances.py:21-92
@@ -134,6 +135,18 @@ def bert_pooler(cls: Tensor, weight: Tensor, bias: Tensor) -> Tensor:
 @bert_pooler.register_fake
 def _(cls, weight, bias):
     return cls.new_empty(cls.shape[0], weight.shape[0])
+
+
+# sentence-transformers' Pooling(mean) [+ Normalize] on a forward's hidden states (aspire_token_mean_pool_f32): the mean of the token
+# rows with mask != 0, then with normalize x / max(||x||, 1e-12); the SentenceTransformer baselines' rep
+@torch.library.custom_op('aspire::token_mean_pool', mutates_args=(), device_types='cuda')
+def token_mean_pool(hidden: Tensor, mask: Tensor, normalize: bool) -> Tensor:
+    return ops.token_mean_pool(hidden.contiguous(), mask, normalize)
+
+
+@token_mean_pool.register_fake
+def _(hidden, mask, normalize):
+    return hidden.new_empty(hidden.shape[0], hidden.shape[2])
 
 
 def _npairs(qn, cn, paired):
@@ -277,5 +290,5 @@ def _(q_rows, q_start, q_len, q_max, c_rows, c_start, c_len, c_max, job_off, max
     return (q_rows.new_empty(c_start.shape[0]), q_rows.new_empty(j, k), q_rows.new_empty(j, k, dtype=torch.int64))
 
 
-OPS = ('span_mean_pool', 'span_pool_ranges', 'bert_encoder_forward', 'bert_cls_forward', 'bert_pooler', 'l2max_scores', 'jointsm_scores', 'ot_sinkhorn_scores', 'topk_desc', 'topk_keys', 'topk_merge',
+OPS = ('span_mean_pool', 'span_pool_ranges', 'bert_encoder_forward', 'bert_cls_forward', 'bert_pooler', 'token_mean_pool', 'l2max_scores', 'jointsm_scores', 'ot_sinkhorn_scores', 'topk_desc', 'topk_keys', 'topk_merge',
        'l2max_scores_csr', 'ot_scores_csr', 'ot_rank_batch')

@@ -183,6 +183,44 @@ int aspire_bert_pooler_f32(const float* cls, int64_t B, int64_t D, const float* 
                            float* pooled, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * A1d  The SentenceTransformer baselines' encoders.  Replaces `self.model.encode(batch, show_progress_bar=False)` at
+ * src/evaluation/utils/models.py:402 (SentenceModel.encode, :379-410: 'sbtinybertsota', 'sbrobertanli', 'sbmpnet1B'), i.e.
+ * sentence-transformers' Transformer -> Pooling(mean) [-> Normalize] over HuggingFace BertModel / RobertaModel / MPNetModel.
+ * All three have BERT-base geometry, erf-GELU and post-LayerNorm; what RoBERTa and MPNet add to aspire_bert_forward_f32 travels
+ * in aspire_bert_extras:
+ *   pos_ids   RoBERTa / MPNet number the real tokens from padding_idx + 1 and give every pad token padding_idx
+ *             (create_position_ids_from_input_ids); the caller builds the table and guarantees 0 <= pos_ids < max_pos
+ *             (aspire_amd checks it on the host, as it does token ids).
+ *   rel_bias  MPNet's relative_attention_bias, expanded by the caller per key-minus-query distance (the bucket arithmetic of
+ *             MPNetEncoder.relative_position_bucket stays on the host): scores are q.k / 8, + rel_bias, + the key-padding mask,
+ *             then the soft-max, as HF MPNetSelfAttention; the same table in every layer.
+ * aspire_bert_forward_var_f32 with x == NULL, or both pointers NULL, IS aspire_bert_forward_f32: the same plan, the same kernels
+ * (instantiated without the bias), the same bits, the same workspace size (aspire_bert_workspace_bytes).  The same argument checks,
+ * before any launch, plus rel_bias != NULL with rel_span < L -> ASPIRE_ERR_INVALID_ARG.  Every attention form carries the bias
+ * except the 64-key tiles of aspire_debug_set("ATTN", "p64"): with a bias that form returns ASPIRE_ERR_UNSUPPORTED (before any
+ * launch).  aspire_bert_status covers this forward too.  The CLS-only forward takes no extras.
+ * MPNet has no token types: pass a type_emb of one zero row and type_ids NULL ((word + 0) + pos is exact).
+ *
+ * aspire_token_mean_pool_f32: the read-out behind it.
+ *   out[b] = (sum over the tokens t with attn_mask[b, t] != 0, in token order, of hidden[b, t]) / max(count, 1e-9)
+ *   normalize != 0: then out[b] / max(||out[b]||_2, 1e-12)                          (torch.nn.functional.normalize)
+ * A row without a valid token gives zeros.  hidden [B, L, 768] and out [B, 768] contiguous, 16-byte aligned; rows of masked tokens
+ * are not read.  D != 768 -> ASPIRE_ERR_UNSUPPORTED; B < 0, L <= 0, a NULL pointer with B > 0 -> ASPIRE_ERR_INVALID_ARG;
+ * B == 0 -> ASPIRE_OK without a launch.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {
+    const int64_t* pos_ids;   /* device [B, L] or NULL: the row of pos_emb each token takes (NULL: its index, as BERT) */
+    const float*   rel_bias;  /* device [n_heads, 2 * rel_span - 1] or NULL: added to the scaled score of (query i, key j):
+                                 rel_bias[h][(j - i) + rel_span - 1], before the key-padding mask, in every layer */
+    int32_t        rel_span;  /* >= L when rel_bias != NULL */
+} aspire_bert_extras;
+int aspire_bert_forward_var_f32(const aspire_bert_weights* w, const aspire_bert_extras* x, const int64_t* tok_ids,
+                                const int64_t* type_ids, const int64_t* attn_mask, int64_t B, int64_t L, float* hidden_out,
+                                void* workspace, size_t workspace_bytes, void* stream);
+int aspire_token_mean_pool_f32(const float* hidden, const int64_t* attn_mask, int64_t B, int64_t L, int64_t D,
+                               int normalize, float* out /* [B, D] */, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * caching_score's document-level term (src/learning/facetid_models/disent_models.py:305-307, taken when
  * abs_loss_prop > 0): functional.pairwise_distance(query_cls_reps, cand_cls_reps, p=2.0) = ||q - c + eps||_2 with torch's
  * eps = 1e-6 added to every coordinate of the difference.  (The caller negates and scales it.)
