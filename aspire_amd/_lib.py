@@ -126,6 +126,10 @@ SIGNATURES = {
     'aspire_l2max_rank_batch_workspace_bytes': (c_size_t, [ctypes.POINTER(RepSet), ctypes.POINTER(RepSet), c_int64, c_int64]),
     'aspire_l2max_rank_batch_f32': (c_int, [ctypes.POINTER(RepSet), ctypes.POINTER(RepSet), c_int64, c_void_p, c_int64, c_int,
                                             c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'aspire_l2agg_rank_batch_workspace_bytes': (c_size_t, [ctypes.POINTER(RepSet), ctypes.POINTER(RepSet), c_int64, c_int64]),
+    'aspire_l2agg_rank_batch_f32': (c_int, [ctypes.POINTER(RepSet), ctypes.POINTER(RepSet), c_int64, c_void_p, c_int64, c_int, c_int,
+                                            ctypes.c_double, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_size_t, c_void_p]),
     'aspire_dotmax_scores_f32': (c_int, [ctypes.POINTER(RepSet), ctypes.POINTER(RepSet), c_int64, c_int, c_int, c_void_p,
                                          c_void_p]),
     'aspire_dotmax_rank_batch_workspace_bytes': (c_size_t, [ctypes.POINTER(RepSet), ctypes.POINTER(RepSet), c_int64, c_int64]),

@@ -1,9 +1,9 @@
 // What the kernels that form sentence-pair dot products on v_mfma_f32_16x16x4_f32 share (dotmax.hip: max over the block;
-// jointsm.hip: joint soft-max over the block): the rep-set view the kernels read, the operand loads and the eight-k product
+// jointsm.hip: joint soft-max over the block; l2agg_pair.hip: top-2 / soft-max of the negated L2 distances): the rep-set view the kernels read, the operand loads and the eight-k product
 // step, the job lookup of the batched form, and the host-side set check.  A lane holds A[row l & 15][k] and B[k][col l & 15] for
 // k = 32 s + 8 (l >> 4) + e: the k order inside a block of 32 is permuted identically for both operands, so the sums are the
 // same dot products -- and the same bits in every kernel that spreads the k blocks over its accumulators the same way (the two
-// kernels of dotmax.hip: four accumulators; the two of jointsm.hip: sixteen).
+// kernels of dotmax.hip: four accumulators; the two of jointsm.hip and l2agg_pair.hip's: sixteen).
 #pragma once
 #include "common.h"
 
@@ -42,6 +42,14 @@ __device__ __forceinline__ void mfma8(const f32x4& a0, const f32x4& a1, const f3
     acc[1] = mfma4(a1.y, b1.y, acc[1]);
     acc[2] = mfma4(a1.z, b1.z, acc[2]);
     acc[3] = mfma4(a1.w, b1.w, acc[3]);
+}
+
+// a tile's dot products from sixteen accumulators (jointsm.hip, l2agg_pair.hip; set u: k blocks s = u mod 4)
+__device__ __forceinline__ f32x4 tile_dots(const f32x4 (&acc)[4][4]) {
+    f32x4 t[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) t[u] = (acc[u][0] + acc[u][1]) + (acc[u][2] + acc[u][3]);
+    return (t[0] + t[1]) + (t[2] + t[3]);
 }
 
 // job of candidate p: the last j with job_off[j] <= p (empty jobs skipped)

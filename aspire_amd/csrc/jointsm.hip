@@ -49,14 +49,6 @@ struct JsmArgs {
     float* pair_softmax;        // pair kernel, padded sets: [P, q.bound, c.bound], or null
 };
 
-// the tile's dot products from its sixteen accumulators (set u: k blocks s = u mod 4)
-__device__ __forceinline__ f32x4 tile_dots(const f32x4 (&acc)[4][4]) {
-    f32x4 t[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) t[u] = (acc[u][0] + acc[u][1]) + (acc[u][2] + acc[u][3]);
-    return (t[0] + t[1]) + (t[2] + t[3]);
-}
-
 // exp((d - m) / sqrt(encoding_dim)) for d <= m: torch.div(pair_sims, math.sqrt(encoding_dim)) behind the max shift
 __device__ __forceinline__ float shifted_exp(float y) { return expf(y / sqrtf((float)kD)); }
 

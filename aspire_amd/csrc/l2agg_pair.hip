@@ -1,0 +1,238 @@
+// The sibling aggregations of the negated L2 block over batched jobs: 'l2top2' and 'l2attention' (include/aspire_hip.h,
+// aspire_l2agg_rank_batch_f32; allpair_masked_dist_l2topk, pair_distances.py:295-345, and AllPairMaskedAttention, :95-135).
+//
+//   d_ij  = sqrt(max(|q_i|^2 + |c_j|^2 - 2 <q_i, c_j>, 0))        over the valid block (i < q_len, j < c_len), s_ij = -d_ij
+//   TOP2       score = the sum of the two largest s_ij (by entries: two equal distances both count, as torch.topk(k = 2) counts
+//              them); a 1 x 1 block takes -10e8 as the missing one (the header's contract for rep sets without padded extents)
+//   ATTENTION  score = sum_ij p_ij s_ij,  p = soft-max of s_ij / temp over the valid block
+//
+// One kernel, l2agg_pair_kernel<AGG>: one wave per (candidate, its job's query) pair, four pairs per workgroup, 16 x 16 tiles over
+// documents of 1 .. 128 rows -- jointsm_pair_kernel's frame (kModeMapped) with another tile epilogue.  One form for every call size:
+// a pair's bits depend on its two documents only.
+//
+// Dot products: dot_tiles.h (exact fp32 on v_mfma_f32_16x16x4_f32) over SIXTEEN accumulators per tile, as jointsm.hip.  What counts
+// here is d^2 = |q|^2 + |c|^2 - 2 q.c, whose three terms are each far larger than their difference once rows share a common
+// component: at the cancel rule's own threshold (below) d^2 = 1e-4 (|q|^2 + |c|^2)^2, so a relative error e of the 2 q.c term
+// reaches the distance as e (|q|^2 + |c|^2) / 2 d = 50 e (unit-free: it does not depend on the rows' scale).  jointsm.hip's header
+// measured e = 2.7e-7 for four chains of 192 (1.4e-5 in d) and 6e-8 for sixteen of 48 (3e-6); with the two norms' error beside it
+// four chains would spend a quarter of the 1e-4 parity bar on the kernel's own rounding, sixteen a twentieth.  The registers are
+// there (two waves per SIMD).
+// Row norms: from the SAME loaded operands -- no pre-pass and no second read.  A lane squares the 8 k values per block it holds of
+// its A row (candidate row c0 + r) and of its B row (query row q0 + r) into four chains each (the x / y / z / w of an f32x4: 48 fmaf
+// per chain, the dots' chain length), the four lane groups' partial sums are added across lanes 16 and 32 apart (the same bits in
+// all four), and the candidate norm of accumulator row 4 g + v is read from lane 4 g + v.  A row's norm is recomputed in every tile
+// it takes part in -- 8 VALU fmaf per 8 MFMAs, hidden under the matrix pipe -- from its own values in one fixed order: the same bits
+// in every tile and every pair.
+// SHARED SENTENCES (include/aspire_hip.h): an entry with d^2 < 1e-4 (|q|^2 + |c|^2)^2 is redone by its lane from the exact sum of
+// squared differences (exact_d2: the arithmetic of generic.hip's cancelling entries and gram.hip's direct_d2), so a shared sentence
+// scores -d ~ 0, not -sqrt(rounding noise).
+// ATTENTION keeps the soft-max shifted by the running maximum m of s (wave-uniform: one wave_max per tile) and sums, beside
+// S = sum e_ij with e_ij = expf((s_ij - m) / temp), the CENTRED T = sum e_ij (s_ij - m): score = m + T / S.  Scores are about -40
+// and their spread a few units: T / S is a small correction to m, so the rounding of the two long sums reaches the score scaled
+// down by that ratio.  A new maximum m' rescales with f = expf((m - m') / temp): S <- f S, T <- f (T + (m - m') S) (jointsm.hip).
+// S and T stay per lane until the end, then wave_sum in its fixed order.  TOP2 keeps (first, second) per lane and merges them
+// across the wave by entries; max / min only, so the order of the merge does not reach the bits.
+#include <math.h>
+
+#include "common.h"
+#include "batch_host.h"
+#include "dot_tiles.h"
+
+namespace aspire {
+namespace {
+
+struct L2aggArgs {
+    DotSet q, c;
+    const int32_t* job_off;     // [J + 1]
+    int32_t J;
+    float temp;                 // ATTENTION
+    float* scores;
+};
+
+// sum_d (x_d - y_d)^2 over the 768 coordinates (rare path: a candidate row that (nearly) equals a query row)
+__device__ __noinline__ float exact_d2(const float* __restrict__ x, const float* __restrict__ y) {
+    float s0 = 0.f, s1 = 0.f;
+#pragma unroll 1
+    for (int k = 0; k < kD; k += 8) {
+        const f32x4 a = ld4(x + k), b = ld4(y + k), c = ld4(x + k + 4), d = ld4(y + k + 4);
+        const float e0 = a.x - b.x, e1 = a.y - b.y, e2 = a.z - b.z, e3 = a.w - b.w;
+        const float f0 = c.x - d.x, f1 = c.y - d.y, f2 = c.z - d.z, f3 = c.w - d.w;
+        s0 = fmaf(e3, e3, fmaf(e2, e2, fmaf(e1, e1, fmaf(e0, e0, s0))));
+        s1 = fmaf(f3, f3, fmaf(f2, f2, fmaf(f1, f1, fmaf(f0, f0, s1))));
+    }
+    return s0 + s1;
+}
+
+// |row|^2 of the lane's operand row from the four lane groups' chains: the same bits in the four lanes that share lane & 15
+__device__ __forceinline__ float row_norm(const f32x4& n) {
+    float s = (n.x + n.y) + (n.z + n.w);
+    s += lane_xor<16>(s);
+    return s + lane_xor<32>(s);
+}
+
+// (first, second) of the union of two (first, second) pairs, by entries
+__device__ __forceinline__ void top2_merge(float& t1, float& t2, float o1, float o2) {
+    t2 = fmaxf(fminf(t1, o1), fmaxf(t2, o2));
+    t1 = fmaxf(t1, o1);
+}
+
+template <int M>
+__device__ __forceinline__ void top2_fold(float& t1, float& t2) {
+    const float o1 = lane_xor<M>(t1), o2 = lane_xor<M>(t2);
+    top2_merge(t1, t2, o1, o2);
+}
+
+template <int AGG>
+__global__ void __launch_bounds__(256) l2agg_pair_kernel(L2aggArgs a, int64_t P) {
+    static_assert(AGG == ASPIRE_AGG_TOP2 || AGG == ASPIRE_AGG_ATTENTION, "the batched siblings; max-sim has its own entry");
+    const int lane = threadIdx.x & 63, g = lane >> 4, r = lane & 15;
+    const int64_t p = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (p >= P) return;
+    const int64_t ci = p, qi = job_of(a.job_off, a.J, p);
+    const int ql = a.q.len[qi], cl = a.c.len[ci];
+    if (ql > a.q.bound || cl > a.c.bound) {
+        if (lane == 0) a.scores[p] = __builtin_nanf("");
+        return;
+    }
+    const float* qdoc = a.q.rows + (int64_t)a.q.start[qi] * kD;
+    const float* cdoc = a.c.rows + (int64_t)a.c.start[ci] * kD;
+    float m = -INFINITY, S = 0.f, T = 0.f;          // ATTENTION
+    float t1 = -INFINITY, t2 = -INFINITY;           // TOP2
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    for (int c0 = 0; c0 < cl; c0 += 16) {
+        const bool va = c0 + r < cl;
+        const float* pa = cdoc + (int64_t)(va ? c0 + r : 0) * kD + 8 * g;
+        for (int q0 = 0; q0 < ql; q0 += 16) {
+            const bool vb = q0 + r < ql;
+            const float* pb = qdoc + (int64_t)(vb ? q0 + r : 0) * kD + 8 * g;
+            f32x4 acc[4][4] = {{zero, zero, zero, zero}, {zero, zero, zero, zero}, {zero, zero, zero, zero}, {zero, zero, zero, zero}};
+            f32x4 na = zero, nb = zero;
+#pragma unroll 1
+            for (int s0 = 0; s0 < kD / 32; s0 += 4) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int s = s0 + u;
+                    const f32x4 a0 = va ? ld4(pa + 32 * s) : zero, a1 = va ? ld4(pa + 32 * s + 4) : zero;
+                    const f32x4 b0 = vb ? ld4(pb + 32 * s) : zero, b1 = vb ? ld4(pb + 32 * s + 4) : zero;
+                    mfma8(a0, a1, b0, b1, acc[u]);
+                    na = __builtin_elementwise_fma(a1, a1, __builtin_elementwise_fma(a0, a0, na));
+                    nb = __builtin_elementwise_fma(b1, b1, __builtin_elementwise_fma(b0, b0, nb));
+                }
+            }
+            // C[row 4 g + v][col r]: candidate row c0 + 4 g + v, query row q0 + r
+            const f32x4 dot = tile_dots(acc);
+            const float qn = row_norm(nb), cn_own = row_norm(na);
+            float s[4], cn[4];
+            bool valid[4];
+#pragma unroll
+            for (int v = 0; v < 4; ++v) cn[v] = __shfl(cn_own, 4 * g + v);          // (every lane: ahead of the divergent redo)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                valid[v] = c0 + 4 * g + v < cl && vb;
+                const float ns = qn + cn[v];
+                float d2 = fmaf(-2.0f, dot[v], ns);
+                if (valid[v] && d2 < 1e-4f * ns * ns)
+                    d2 = exact_d2(qdoc + (int64_t)(q0 + r) * kD, cdoc + (int64_t)(c0 + 4 * g + v) * kD);
+                s[v] = -sqrtf(fmaxf(d2, 0.0f));
+            }
+            if constexpr (AGG == ASPIRE_AGG_TOP2) {
+#pragma unroll
+                for (int v = 0; v < 4; ++v)
+                    if (valid[v]) top2_merge(t1, t2, s[v], -INFINITY);
+            } else {
+                float tile_max = -INFINITY;
+#pragma unroll
+                for (int v = 0; v < 4; ++v)
+                    if (valid[v]) tile_max = fmaxf(tile_max, s[v]);
+                tile_max = wave_max(tile_max);
+                if (tile_max > m) {                 // wave-uniform
+                    if (m > -INFINITY) {
+                        const float dm = m - tile_max, f = expf(dm / a.temp);
+                        T = f * fmaf(dm, S, T);
+                        S = f * S;
+                    }
+                    m = tile_max;
+                }
+#pragma unroll
+                for (int v = 0; v < 4; ++v) {
+                    if (valid[v]) {
+                        const float y = s[v] - m, e = expf(y / a.temp);
+                        S += e;
+                        T = fmaf(e, y, T);
+                    }
+                }
+            }
+        }
+    }
+    if constexpr (AGG == ASPIRE_AGG_TOP2) {
+        top2_fold<1>(t1, t2);
+        top2_fold<2>(t1, t2);
+        top2_fold<4>(t1, t2);
+        top2_fold<8>(t1, t2);
+        top2_fold<16>(t1, t2);
+        top2_fold<32>(t1, t2);
+        if (lane == 0) a.scores[p] = t1 + (t2 == -INFINITY ? -10e8f : t2);
+    } else {
+        S = wave_sum(S);
+        T = wave_sum(T);
+        if (lane == 0) a.scores[p] = m + T / S;
+    }
+}
+
+int launch_pairs(const L2aggArgs& a, int agg, int64_t P, hipStream_t s) {
+    ASPIRE_REQUIRE((P + 3) / 4 < ((int64_t)1 << 31), ASPIRE_ERR_UNSUPPORTED, "too many pairs: %lld", (long long)P);
+    const dim3 grid((unsigned)((P + 3) / 4)), block(256);
+    if (agg == ASPIRE_AGG_TOP2) hipLaunchKernelGGL(l2agg_pair_kernel<ASPIRE_AGG_TOP2>, grid, block, 0, s, a, P);
+    else hipLaunchKernelGGL(l2agg_pair_kernel<ASPIRE_AGG_ATTENTION>, grid, block, 0, s, a, P);
+    ASPIRE_LAUNCH_OK();
+    return ASPIRE_OK;
+}
+
+}  // namespace
+}  // namespace aspire
+
+using namespace aspire;
+
+extern "C" size_t aspire_l2agg_rank_batch_workspace_bytes(const aspire_repset* q, const aspire_repset* c, int64_t max_job, int64_t k) {
+    if (!q || !c || q->n <= 0 || c->n <= 0 || k <= 0) return 0;
+    return aspire_topk_workspace_bytes(q->n, max_job, k);
+}
+
+extern "C" int aspire_l2agg_rank_batch_f32(const aspire_repset* q, const aspire_repset* c, int64_t D, const int32_t* job_off,
+                                           int64_t max_job, int cdist_mode, int agg, double temp, float* scores, int64_t k,
+                                           const int32_t* job_base, float* top_scores, int64_t* top_idx, uint64_t* keys,
+                                           void* workspace, size_t workspace_bytes, void* stream) {
+    ASPIRE_REQUIRE(q && c, ASPIRE_ERR_INVALID_ARG, "null repset");
+    {   // (the text of aspire_l2max_rank_batch_f32's limit; check_dot_sets would word it per side)
+        const int max_rows = to_dot(q).bound > to_dot(c).bound ? to_dot(q).bound : to_dot(c).bound;
+        ASPIRE_REQUIRE(max_rows <= generic_max_rows(), ASPIRE_ERR_UNSUPPORTED,
+                       "documents with more than %d sentence rows are not supported (got %d)", generic_max_rows(), max_rows);
+    }
+    if (int rc = check_dot_sets(q, c, D, ASPIRE_PAIR_CROSS, ASPIRE_SIM_DOT)) return rc;
+    ASPIRE_REQUIRE(agg != ASPIRE_AGG_MAX, ASPIRE_ERR_INVALID_ARG,
+                   "ASPIRE_AGG_MAX over batched jobs is aspire_l2max_rank_batch_f32; this entry takes ASPIRE_AGG_TOP2 or ASPIRE_AGG_ATTENTION");
+    ASPIRE_REQUIRE(agg == ASPIRE_AGG_TOP2 || agg == ASPIRE_AGG_ATTENTION, ASPIRE_ERR_INVALID_ARG, "bad aggregation %d", agg);
+    ASPIRE_REQUIRE(agg != ASPIRE_AGG_ATTENTION || temp > 0, ASPIRE_ERR_INVALID_ARG, "attention temperature must be positive");
+    // one formula serves AUTO / DIRECT / MM, and there is one form: ONE_FORM and CENTER have nothing to select
+    cdist_mode &= ~(ASPIRE_CDIST_ONE_FORM | ASPIRE_CDIST_CENTER);
+    ASPIRE_REQUIRE(cdist_mode == ASPIRE_CDIST_AUTO || cdist_mode == ASPIRE_CDIST_DIRECT || cdist_mode == ASPIRE_CDIST_MM,
+                   ASPIRE_ERR_INVALID_ARG, "bad cdist_mode %d", cdist_mode);
+    const int64_t J = q->n, C = c->n;
+    BatchRank rank{J, max_job, k, top_scores, top_idx, keys, job_off, job_base, stream};
+    bool go_on;
+    if (int rc = batch_preamble(q, c, scores, rank, go_on); !go_on) return rc;
+    const size_t need = aspire_l2agg_rank_batch_workspace_bytes(q, c, max_job, k);
+    ASPIRE_REQUIRE(workspace_bytes >= need && (need == 0 || workspace), ASPIRE_ERR_INVALID_ARG,
+                   "workspace too small: %zu bytes given, aspire_l2agg_rank_batch_workspace_bytes says %zu", workspace_bytes, need);
+    ASPIRE_REQUIRE(((uintptr_t)workspace & 15) == 0, ASPIRE_ERR_INVALID_ARG, "workspace must be 16-byte aligned");
+    rank.scratch_at(workspace);
+    L2aggArgs a{};
+    a.q = to_dot(q);
+    a.c = to_dot(c);
+    a.job_off = job_off;
+    a.J = (int32_t)J;
+    a.temp = (float)temp;
+    a.scores = scores;
+    if (int rc = launch_pairs(a, agg, C, (hipStream_t)stream)) return rc;
+    return rank.rank(scores);
+}

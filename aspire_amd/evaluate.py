@@ -38,7 +38,8 @@ def score(results_dir, test_pool, rep_store, facet=None, pred_labels=None, metho
     Writes and returns {query_id: [(cand_id, -sim), ...]}.
 
     With the per-pair schedule (the reference's own: one get_similarity call per candidate, evaluate.py:68-72) and method 'ot',
-    'l2max', cosentbert's 'cosine' / 'dotlse' (TrainedSentModel.get_similarity, models.py:602-604) or miswordpolyenc's 'jointsm'
+    'l2max', its siblings 'l2top2' / 'l2attention' (disent_models.py:238-245), cosentbert's 'cosine' / 'dotlse'
+    (TrainedSentModel.get_similarity, models.py:602-604) or miswordpolyenc's 'jointsm'
     (WordSentAlignPolyEnc.score, disent_models.py:877-925) the queries go
     through scorer.rank_pools' one library call `queries_per_call` at a time -- every query against ITS OWN pool (rank_pool_batch on
     resident pools, else _launch_rank_pools); any other schedule / aggregation keeps one rank_pool call (_launch_rank_pool) per query.

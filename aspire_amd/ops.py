@@ -493,6 +493,14 @@ def l2max_rank_batch(q, c, job_off, max_job, k, cdist_mode=_lib.CDIST_AUTO, out=
     return _rank_batch('l2max', lambda: (cdist_mode,), q, c, job_off, max_job, k, out, workspace, job_base, key_form)
 
 
+def l2agg_rank_batch(q, c, job_off, max_job, k, agg, temp=1.0, cdist_mode=_lib.CDIST_AUTO, out=None, key_form=False, job_base=None,
+                     workspace=None):
+    """The sibling aggregations 'l2top2' (agg=AGG_TOP2) / 'l2attention' (AGG_ATTENTION, temp = cdatt_sm_temp) over J independent
+    (query, pool) jobs in ONE call (include/aspire_hip.h: aspire_l2agg_rank_batch_f32); arguments and returns as l2max_rank_batch.
+    One kernel form whatever the call's size: a pair's score depends on its two documents only."""
+    return _rank_batch('l2agg', lambda: (cdist_mode, agg, float(temp)), q, c, job_off, max_job, k, out, workspace, job_base, key_form)
+
+
 def _dot_ready(*sets):
     """The host-side contract of the dot-product max-sim entries: every document has a row (np.max over an empty similarity
     block raises in the reference) and every row is finite (sklearn's check_array raises ValueError on inf / NaN).  The finite
@@ -551,12 +559,13 @@ def jointsm_rank_batch(q, c, job_off, max_job, k, out=None, workspace=None, job_
 # <entry>_rank_batch -> (its library entry, that entry's workspace query)
 _RANK_BATCH = {'ot': (lib.aspire_ot_rank_batch_f32, lib.aspire_ot_rank_batch_workspace_bytes),
                'l2max': (lib.aspire_l2max_rank_batch_f32, lib.aspire_l2max_rank_batch_workspace_bytes),
+               'l2agg': (lib.aspire_l2agg_rank_batch_f32, lib.aspire_l2agg_rank_batch_workspace_bytes),
                'dotmax': (lib.aspire_dotmax_rank_batch_f32, lib.aspire_dotmax_rank_batch_workspace_bytes),
                'jointsm': (lib.aspire_jointsm_rank_batch_f32, lib.aspire_jointsm_rank_batch_workspace_bytes)}
 
 
 def rank_batch_workspace_bytes(entry, q, c, max_job, k):
-    """Bytes of `workspace` that <entry>_rank_batch (entry 'ot', 'l2max', 'dotmax' or 'jointsm') needs for these sets: a host-side
+    """Bytes of `workspace` that <entry>_rank_batch (entry 'ot', 'l2max', 'l2agg', 'dotmax' or 'jointsm') needs for these sets: a host-side
     computation, for callers that keep one buffer over many calls."""
     qs, cs = q.struct(), c.struct()
     return _RANK_BATCH[entry][1](ctypes.byref(qs), ctypes.byref(cs), max_job, k)

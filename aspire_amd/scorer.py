@@ -79,6 +79,7 @@ class PoolBatch:
 
 
 _WORKSPACE = {}
+_NOT_DETERMINISTIC = "deterministic=True is built for method 'ot' with schedule 'pair' and for 'l2max'"
 
 
 def _shared_workspace(dev, nbytes):
@@ -100,6 +101,8 @@ def _batch_call(n_queries, sizes, k, hparams, method, deterministic):
     row = METHODS.get(method)
     if row is None or row.batch is None:
         raise ValueError(f'Unknown aggregation: {method}')
+    if deterministic and row.deterministic is None:
+        raise ValueError(_NOT_DETERMINISTIC)
     ot_kwargs(hparams)          # geoml_reach is rejected whatever the method
     assert n_queries == len(sizes), 'one pool per query'
     max_job = max(sizes) if sizes else 0
@@ -187,7 +190,8 @@ def score_pool(query_reps_list, pool, method='ot', schedule='pair', hparams=None
                       candidates, exactly caching_score with return_pair_sims=True
                       (disent_models.py:297, pp_gen_nearest.py:182-196).
              'l2max'  tsAspire max-sim (caching_score's 'l2lse' branch, disent_models.py:294-295).
-             'l2top2' / 'l2attention'  the sibling aggregations (disent_models.py:238-245); hparams['cdatt_sm_temp'].
+             'l2top2' / 'l2attention'  the sibling aggregations (disent_models.py:238-245); hparams['cdatt_sm_temp'].  Not built
+                      for deterministic=True here; their batched entry (rank_pools) has one kernel form at every call size.
              'cosine' cosentbert / ictsentbert: max over the sentence pairs of sklearn's cosine similarity
                       (TrainedSentModel.get_similarity, models.py:602-604).  'dotlse': the same max over raw dot products
                       (pp_gen_nearest.py rank_pool_sent).  Both kernel forms give the same bits for a pair; `schedule` and
@@ -222,7 +226,7 @@ def score_pool(query_reps_list, pool, method='ot', schedule='pair', hparams=None
 
 def _score_run(q, c, method, schedule, hparams, score_batch_size, cdist_mode, deterministic=False):
     if deterministic and METHODS[method].deterministic not in ('any', schedule):
-        raise ValueError("deterministic=True is built for method 'ot' with schedule 'pair' and for 'l2max'")
+        raise ValueError(_NOT_DETERMINISTIC)
     return METHODS[method].cross(q, c, hparams, cdist_mode, deterministic, schedule, score_batch_size).view(q.n, c.n)
 
 
@@ -288,11 +292,14 @@ METHODS = {
                     deterministic='any', schedule=True),
     'l2top2': Method(cross=lambda q, c, hparams, cdist_mode, *_: ops.l2agg_scores(
                          q, c, _lib.AGG_TOP2, pairing=_lib.PAIR_CROSS, cdist_mode=cdist_mode),
-                     batch=None, deterministic=None, schedule=True),
+                     batch=lambda hparams, deterministic: ('l2agg', ops.l2agg_rank_batch, dict(agg=_lib.AGG_TOP2)),
+                     deterministic=None, schedule=True),
     'l2attention': Method(cross=lambda q, c, hparams, cdist_mode, *_: ops.l2agg_scores(
                               q, c, _lib.AGG_ATTENTION, temp=hparams.get('cdatt_sm_temp', 1.0), pairing=_lib.PAIR_CROSS,
                               cdist_mode=cdist_mode),
-                          batch=None, deterministic=None, schedule=True),
+                          batch=lambda hparams, deterministic: ('l2agg', ops.l2agg_rank_batch, dict(
+                              agg=_lib.AGG_ATTENTION, temp=hparams.get('cdatt_sm_temp', 1.0))),
+                          deterministic=None, schedule=True),
     'cosine': _dot_method(_lib.SIM_COSINE),
     'dotlse': _dot_method(_lib.SIM_DOT),
     'jointsm': Method(cross=_score_jointsm, batch=lambda hparams, deterministic: ('jointsm', ops.jointsm_rank_batch, {}),
@@ -313,7 +320,7 @@ def _launch_rank_pool(query_reps_list, pool, k=None, method='ot', schedule='pair
     """The uploads and library calls of rank_pool; returns (the pool's ids once per query, top_scores, top_idx) for ranked_lists
     (None for the tensors when the pool is empty)."""
     if deterministic and (method not in METHODS or METHODS[method].deterministic not in ('any', schedule)):
-        raise ValueError("deterministic=True is built for method 'ot' with schedule 'pair' and for 'l2max'")
+        raise ValueError(_NOT_DETERMINISTIC)
     pool = _as_pool(pool)
     pids_lists = [pool.pids] * len(query_reps_list)
     if len(pool) == 0:
@@ -378,11 +385,13 @@ def _launch_rank_pools(query_reps_list, pools, k, hparams, method='ot', determin
 def rank_pools(query_reps_list, pools, k=None, hparams=None, method='ot', deterministic=False):
     """The whole per-query loop of evaluate.py:58-76 in ONE library call: query j is scored against ITS OWN pool
     pools[j] (every query of a dataset has its own candidate pool, evaluate.py:60-62) with otAspire, one epsilon schedule
-    per pair (AspireModel.get_similarity, models.py:190-197) -- or, method='l2max', tsAspire's max-sim, or 'cosine' / 'dotlse',
-    cosentbert's (score_pool) -- and each pool is
+    per pair (AspireModel.get_similarity, models.py:190-197) -- or, method='l2max', tsAspire's max-sim, 'l2top2' / 'l2attention',
+    its sibling aggregations (hparams['cdatt_sm_temp']; aspire_l2agg_rank_batch_f32), 'cosine' / 'dotlse', cosentbert's, or 'jointsm',
+    miswordpolyenc's (score_pool) -- and each pool is
     ranked on its own (stable descending, evaluate.py:76).  pools: list of CandidatePool or lists of [S_i, 768] arrays.
     Returns per query [(pid, score), ...].  deterministic: one kernel form whatever the batch's size -- the same bits and the
-    same order as rank_pool(..., deterministic=True) query by query (see score_pool)."""
+    same order as rank_pool(..., deterministic=True) query by query (see score_pool); ValueError for 'l2top2' / 'l2attention', whose
+    batched scores do not depend on the call's size anyway but are not the bits of rank_pool's kernels."""
     if not pools:
         return []
     return ranked_lists(*_launch_rank_pools(query_reps_list, pools, k, hparams, method, deterministic))

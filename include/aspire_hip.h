@@ -502,6 +502,35 @@ int aspire_l2max_rank_batch_f32(const aspire_repset* q, const aspire_repset* c, 
                                 size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The same per-query loop for the sibling aggregations (score_agg_type 'l2top2' / 'l2attention', disent_models.py:238-245;
+ * pp_gen_nearest.py rank_pool_sent*, :941-959): J independent (query, pool) re-ranks in ONE call.
+ *   job_off, max_job, scores [C], k, job_base, top_scores, top_idx, keys, workspace: exactly the contract of
+ *              aspire_jointsm_rank_batch_f32 (CSR rep sets, ties in pool order, (-inf, -1) beyond a pool's size, k == 0: scores only);
+ *              the workspace, 16-byte aligned, is aspire_l2agg_rank_batch_workspace_bytes(q, c, max_job, k) bytes: the rank's
+ *              scratch only, 0 for pools of <= 4096.
+ *   agg        ASPIRE_AGG_TOP2 or ASPIRE_AGG_ATTENTION.  ASPIRE_AGG_MAX is ASPIRE_ERR_INVALID_ARG: aspire_l2max_rank_batch_f32 is the
+ *              max-sim's batched entry.  temp (cdatt_sm_temp) must be positive with ATTENTION and is ignored with TOP2.
+ *   scores [C] out: candidate p against its job's query, the similarity that aspire_l2agg_scores_f32 documents for CSR rep sets
+ *              (TOP2: the two largest -d_ij of the valid block, a missing second entry counting -10e8; ATTENTION: sum_ij p_ij (-d_ij)).
+ *              The value agrees with that entry point to rounding, NOT bit for bit: another kernel, another summation order.
+ *   cdist_mode ASPIRE_CDIST_AUTO / DIRECT / MM are validated and all three are served by ONE formula,
+ *                  d_ij = sqrt(max(|q_i|^2 + |c_j|^2 - 2 <q_i, c_j>, 0)),
+ *              with exact fp32 products (v_mfma_f32_16x16x4_f32, sixteen accumulators per tile) and the row norms from the same
+ *              operands.  Away from cancelling entries torch.cdist's two formulas differ by less than the 1e-4 parity bar, and a
+ *              cancelling entry (d^2 < 1e-4 (|q|^2 + |c|^2)^2) follows the SHARED SENTENCES rule above in either mode: it is
+ *              redone from the exact sum of squared differences.  ASPIRE_CDIST_ONE_FORM and ASPIRE_CDIST_CENTER may be or'ed in and
+ *              change nothing: there is one kernel form (one wave per pair, 16 x 16 tiles) for every call size, so a pair's bits
+ *              depend on its two documents only.
+ *   Documents of 1 .. aspire_max_sents() rows (more: ASPIRE_ERR_UNSUPPORTED); a document longer than its set's max_len scores NaN;
+ *   more than 2^33 - 4 pairs: ASPIRE_ERR_UNSUPPORTED.  Launches on `stream`: the scoring kernel, then the segmented rank.
+ * ------------------------------------------------------------------------------------------- */
+size_t aspire_l2agg_rank_batch_workspace_bytes(const aspire_repset* q, const aspire_repset* c, int64_t max_job, int64_t k);
+int aspire_l2agg_rank_batch_f32(const aspire_repset* q, const aspire_repset* c, int64_t D, const int32_t* job_off,
+                                int64_t max_job, int cdist_mode, int agg, double temp, float* scores, int64_t k,
+                                const int32_t* job_base, float* top_scores, int64_t* top_idx, uint64_t* keys,
+                                void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * A13  cosentbert / ictsentbert max-sim.  Replaces TrainedSentModel.get_similarity,
  * src/evaluation/utils/models.py:602-604 (float(np.max(sklearn.metrics.pairwise.cosine_similarity(x, y)))), and the
  * per-query scoring of pp_gen_nearest.py rank_pool_sent (:863-986; 'dotlse' takes np.matmul instead).
