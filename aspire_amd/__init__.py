@@ -14,3 +14,4 @@ from .polyenc import WordSentAlignPolyEnc, TrainedScoringModel  # noqa: F401
 from .baselines import BertMLM, BertNER, SimCSE  # noqa: F401
 from .sbert import SentenceModel  # noqa: F401
 from .models import MODEL_TABLE, get_model  # noqa: F401
+from .nearest import DenseReps, rank_pool, rank_pool_faceted, write_ranked  # noqa: F401

@@ -28,6 +28,7 @@ PAIR_CROSS, PAIR_PAIRED = 0, 1
 OT_DISTANCE, OT_PLAN_SIM, OT_SIMILARITY = 0, 1, 2
 AGG_MAX, AGG_TOP2, AGG_ATTENTION = 0, 1, 2
 SIM_COSINE, SIM_DOT = 0, 1
+DENSE_L2, DENSE_COSINE, DENSE_DOT = 0, 1, 2
 
 
 class RepPlanes(ctypes.Structure):
@@ -140,6 +141,9 @@ SIGNATURES = {
     'aspire_jointsm_rank_batch_workspace_bytes': (c_size_t, [ctypes.POINTER(RepSet), ctypes.POINTER(RepSet), c_int64, c_int64]),
     'aspire_jointsm_rank_batch_f32': (c_int, [ctypes.POINTER(RepSet), ctypes.POINTER(RepSet), c_int64, c_void_p, c_int64,
                                               c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'aspire_dense_rank_batch_workspace_bytes': (c_size_t, [c_int64, c_int64, c_int64, c_int64]),
+    'aspire_dense_rank_batch_f32': (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int,
+                                            c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     'aspire_debug_set': (c_int, [ctypes.c_char_p, ctypes.c_char_p]),
     'aspire_debug_get': (c_int, [ctypes.c_char_p, ctypes.c_char_p, c_size_t]),
     'aspire_debug_ot_cost_stage_f32': (c_int, [ctypes.POINTER(RepSet), ctypes.POINTER(RepSet), c_int64, c_int,

@@ -444,6 +444,20 @@ def ot_rank(q, c, k, blur=0.05, scaling=0.9, sent_sm_temp=1.0, cdist_mode=_lib.C
     return (scores, keys) if key_form else (scores, top_s, top_i)
 
 
+def _rank_outputs(J, C, k, dev, out, key_form):
+    """(scores, top_scores, top_idx, keys) of a batched rank call over J jobs and C candidates: the caller's `out` taken apart, or
+    fresh tensors (None for what the call does not write)."""
+    if out is not None and key_form:
+        scores, keys = out
+        return scores, None, None, keys
+    if out is not None:
+        return (*out, None)
+    return (torch.empty(C, device=dev, dtype=torch.float32),
+            torch.empty(J, k, device=dev, dtype=torch.float32) if k > 0 and not key_form else None,
+            torch.empty(J, k, device=dev, dtype=torch.int64) if k > 0 and not key_form else None,
+            torch.empty(J, k, device=dev, dtype=torch.int64) if k > 0 and key_form else None)
+
+
 def _rank_batch(entry, mid, q, c, job_off, max_job, k, out, workspace, job_base, key_form):
     """What the batched rank wrappers share.  `entry` names the pair of library entries (_RANK_BATCH); `mid()` gives the arguments
     that sit between max_job and scores in its C signature -- all that differs between them -- once the checks have passed."""
@@ -451,17 +465,7 @@ def _rank_batch(entry, mid, q, c, job_off, max_job, k, out, workspace, job_base,
     dev = q.rows.device
     _i32(job_off, 'job_off')
     assert job_off.numel() == q.n + 1, 'job_off must have one entry per job plus one'
-    keys = None
-    if out is not None and key_form:
-        scores, keys = out
-        top_s = top_i = None
-    elif out is not None:
-        scores, top_s, top_i = out
-    else:
-        scores = torch.empty(c.n, device=dev, dtype=torch.float32)
-        top_s = torch.empty(q.n, k, device=dev, dtype=torch.float32) if k > 0 and not key_form else None
-        top_i = torch.empty(q.n, k, device=dev, dtype=torch.int64) if k > 0 and not key_form else None
-        keys = torch.empty(q.n, k, device=dev, dtype=torch.int64) if k > 0 and key_form else None
+    scores, top_s, top_i, keys = _rank_outputs(q.n, c.n, k, dev, out, key_form)
     mid = mid()
     qs, cs = q.struct(), c.struct()
     if workspace is None:
@@ -554,6 +558,29 @@ def jointsm_rank_batch(q, c, job_off, max_job, k, out=None, workspace=None, job_
     aspire_jointsm_rank_batch_f32); arguments and returns as l2max_rank_batch."""
     _dot_ready(q, c)
     return _rank_batch('jointsm', lambda: (), q, c, job_off, max_job, k, out, workspace, job_base, key_form)
+
+
+def dense_rank_batch(rows, q_idx, cand_idx, job_off, max_job, k, metric=_lib.DENSE_L2, out=None, workspace=None, job_base=None,
+                     key_form=False):
+    """The precomputed-embedding rankers' score + rank (include/aspire_hip.h: aspire_dense_rank_batch_f32; pp_gen_nearest.py
+    rank_pool :683-717, rank_pool_faceted :1166-1191) over J (query, pool) jobs in ONE call on ONE resident matrix: rows [N, 768]
+    fp32; q_idx int32 [J] = the matrix row of each job's query; cand_idx int32 [C] = every job's candidate rows back to back;
+    job_off int32 [J + 1] -- all GPU tensors, nothing is gathered.  metric DENSE_L2 (-Euclidean distance), DENSE_COSINE or DENSE_DOT:
+    similarities, higher is better.  max_job, k, out, workspace, job_base, key_form and the returns as l2max_rank_batch:
+    (scores [C], top_scores [J, k], top_idx [J, k]) or (scores, keys [J, k]).  A row index outside [0, N) scores NaN (the kernel
+    reads nothing for it); callers validate on the host (nearest.py)."""
+    _f32(rows, 'rows')
+    assert rows.dim() == 2 and rows.shape[1] == D, 'rows must be [N, 768]'
+    _i32(q_idx, 'q_idx'), _i32(cand_idx, 'cand_idx'), _i32(job_off, 'job_off')
+    J, C, dev = q_idx.numel(), cand_idx.numel(), rows.device
+    assert job_off.numel() == J + 1, 'job_off must have one entry per job plus one'
+    scores, top_s, top_i, keys = _rank_outputs(J, C, k, dev, out, key_form)
+    if workspace is None:
+        workspace = torch.empty(max(lib.aspire_dense_rank_batch_workspace_bytes(J, C, max_job, k), 16), device=dev, dtype=torch.uint8)
+    check(lib.aspire_dense_rank_batch_f32(_ptr(rows), rows.shape[0], D, _ptr(q_idx), J, _ptr(cand_idx), C, _ptr(job_off), max_job,
+                                          metric, _ptr(scores), k, _ptr(job_base), _ptr(top_s), _ptr(top_i), _ptr(keys),
+                                          _ptr(workspace), workspace.numel(), _stream()))
+    return (scores, keys) if key_form else (scores, top_s, top_i)
 
 
 # <entry>_rank_batch -> (its library entry, that entry's workspace query)

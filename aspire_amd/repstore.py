@@ -43,6 +43,32 @@ class RepStore:
         pids, off, rows = z['pids'], z['offsets'], z['rows']
         return cls({str(p): rows[off[i]:off[i + 1]] for i, p in enumerate(pids)})
 
+    @classmethod
+    def from_npy_sent(cls, npy_path, pid2idx_sent_json_path):
+        """The sentence-level layout of pre_proc_buildreps.py, the input of pp_gen_nearest.py rank_pool_sent* (:894-937): one
+        [total_sents, 768] matrix ({dataset}-sent.npy) and pid2idx-{dataset}-sent.json mapping '{pid}-{i}' -> matrix row, i = the
+        sentence's position in its abstract.  A paper's rows are gathered in i order (i must run 0 .. n - 1); the matrix goes
+        through np.nan_to_num as at :906."""
+        import json
+        with open(pid2idx_sent_json_path, 'r', encoding='utf-8') as fp:
+            sent2idx = json.load(fp)
+        reps = np.array(np.load(npy_path), dtype=np.float32)
+        np.nan_to_num(reps, copy=False)
+        pid2rows = {}
+        for key, row in sent2idx.items():
+            pid, _, i = key.rpartition('-')
+            if not pid or not i.isdigit():
+                raise ValueError(f"sentence id {key!r} is not of the form '<pid>-<i>'")
+            if not 0 <= row < reps.shape[0]:
+                raise IndexError(f'sentence {key!r} maps to row {row}; the matrix has {reps.shape[0]} rows')
+            pid2rows.setdefault(pid, {})[int(i)] = row
+        store = {}
+        for pid, rows in pid2rows.items():
+            if sorted(rows) != list(range(len(rows))):
+                raise ValueError(f'paper {pid!r}: sentence positions {sorted(rows)} are not 0 .. {len(rows) - 1}')
+            store[pid] = reps[[rows[i] for i in range(len(rows))]]
+        return cls(store)
+
     def save_npz(self, path):
         pids = sorted(self.pid2reps)
         lens = [self.pid2reps[p].shape[0] for p in pids]

@@ -24,6 +24,9 @@ implementation so that shapes propagate under FakeTensor / torch.compile tracing
     torch.ops.aspire.l2max_scores_csr / ot_scores_csr(q_rows, q_start, q_len, q_max, c_rows, c_start, c_len, c_max, ...) -> [Q * C]
     torch.ops.aspire.ot_rank_batch(q_rows, q_start, q_len, q_max, c_rows, c_start, c_len, c_max, job_off, max_job, k, ...)
                                          -> (scores [C], top_scores [J, k], top_idx [J, k])        evaluate.py:58-76, batched
+  one resident [N, 768] matrix of whole-document reps, jobs as row-index lists:
+    torch.ops.aspire.dense_rank_batch(rows, q_idx, cand_idx, job_off, max_job, k, metric)
+                                         -> (scores [C], top_scores [J, k], top_idx [J, k])        A15  pp_gen_nearest.py:683-717
 
 Padded inputs are [n, S, 768] fp32 with int32 lens [n] (the reference's RepLen after its permute, disent_models.py:15);
 ``paired`` False scores every query against every candidate ([Q * C], query-major), True scores pair p (Q == C).
@@ -290,5 +293,18 @@ def _(q_rows, q_start, q_len, q_max, c_rows, c_start, c_len, c_max, job_off, max
     return (q_rows.new_empty(c_start.shape[0]), q_rows.new_empty(j, k), q_rows.new_empty(j, k, dtype=torch.int64))
 
 
+@torch.library.custom_op('aspire::dense_rank_batch', mutates_args=(), device_types='cuda')
+def dense_rank_batch(rows: Tensor, q_idx: Tensor, cand_idx: Tensor, job_off: Tensor, max_job: int, k: int,
+                     metric: int) -> Tuple[Tensor, Tensor, Tensor]:
+    assert k > 0, 'the op returns the ranked lists: k > 0 (ops.dense_rank_batch takes k = 0 for scores only)'
+    return ops.dense_rank_batch(rows, q_idx, cand_idx, job_off, max_job, k, metric=metric)
+
+
+@dense_rank_batch.register_fake
+def _(rows, q_idx, cand_idx, job_off, max_job, k, metric):
+    j = q_idx.shape[0]
+    return (rows.new_empty(cand_idx.shape[0]), rows.new_empty(j, k), rows.new_empty(j, k, dtype=torch.int64))
+
+
 OPS = ('span_mean_pool', 'span_pool_ranges', 'bert_encoder_forward', 'bert_cls_forward', 'bert_pooler', 'token_mean_pool', 'l2max_scores', 'jointsm_scores', 'ot_sinkhorn_scores', 'topk_desc', 'topk_keys', 'topk_merge',
-       'l2max_scores_csr', 'ot_scores_csr', 'ot_rank_batch')
+       'l2max_scores_csr', 'ot_scores_csr', 'ot_rank_batch', 'dense_rank_batch')

@@ -587,6 +587,46 @@ int aspire_jointsm_rank_batch_f32(const aspire_repset* q, const aspire_repset* c
                                   size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * A15  precomputed-embedding rankers.  Replaces the per-query body of src/pre_process/pp_gen_nearest.py rank_pool (:683-717) and
+ * rank_pool_faceted (:1166-1191): `all_doc_reps[pool_idxs, :]`, sklearn.neighbors.NearestNeighbors(algorithm='brute').fit on it and
+ * kneighbors of the query row -- for J (query, pool) jobs in ONE call over ONE resident [N, 768] matrix of whole-document reps.
+ * Nothing is gathered into a pool copy: a job is the matrix row of its query and a run of matrix rows, and a row that sits in many
+ * pools is stored once.
+ *   rows       [N, D] fp32, 16-byte aligned; D must be 768 (else ASPIRE_ERR_UNSUPPORTED); N < 2^31
+ *   q_idx      DEVICE int32 [J]: matrix row of job j's query
+ *   cand_idx   DEVICE int32 [C]: matrix rows of all jobs' candidates, back to back (C == job_off[J])
+ *   J, C       the two counts (host values: job_off lives on the device)
+ *   job_off, max_job, scores [C], k, job_base, top_scores, top_idx, keys, workspace: exactly the contract of
+ *              aspire_dotmax_rank_batch_f32 (ties in pool order, (-inf, -1) beyond a pool's size, k == 0: scores only); the
+ *              workspace, 16-byte aligned, is aspire_dense_rank_batch_workspace_bytes(J, C, max_job, k) bytes: the rank's scratch
+ *              only, 0 for pools of <= 4096.
+ *   metric     scores are SIMILARITIES, higher is better:
+ *              ASPIRE_DENSE_L2      -sqrt(sum_k (q_k - c_k)^2) from direct differences in fp32 (what NearestNeighbors' default
+ *                                   metric ranks by, negated): a candidate equal to its query scores exactly -0.0f; no expansion, no
+ *                                   clamp rule, no cdist mode.  That is `scores`; top_scores and keys list it as +0.0f, since -0.0
+ *                                   and +0.0 share one rank key (aspire_topk_desc_f32: a tie, decided by pool order).
+ *              ASPIRE_DENSE_COSINE  the cosine as ASPIRE_SIM_COSINE documents it (sklearn's float32 normalisation rules).
+ *              ASPIRE_DENSE_DOT     the raw dot product.
+ *   One kernel form and one summation order for every call size: a pair's bits depend on its two rows only -- the same
+ *   (query row, candidate row) scores the same bits in a call of one job and in a call of fifty.
+ *   An index outside [0, N) in q_idx or cand_idx reads nothing and scores NaN for the pairs it touches (the host layer,
+ *   aspire_amd.nearest, raises IndexError before it gets here); where such a pair lands in the ranked lists is not defined.
+ *   Checked before any launch: a bad metric, negative counts, k < 0, k > 0 without (top_scores, top_idx) or keys, a null job_off,
+ *   max_job outside [0, C], null scores / q_idx / cand_idx / rows with C > 0, misaligned rows or workspace, a workspace that is too
+ *   small -> ASPIRE_ERR_INVALID_ARG; J >= 2^30 or C >= 2^31 - 8 -> ASPIRE_ERR_UNSUPPORTED; J == 0 -> ASPIRE_OK without a launch.
+ *   Launches on `stream`: the scoring kernel (one wave per 8 consecutive candidates, the query row in registers), then the
+ *   segmented rank.
+ * ------------------------------------------------------------------------------------------- */
+#define ASPIRE_DENSE_L2 0
+#define ASPIRE_DENSE_COSINE 1
+#define ASPIRE_DENSE_DOT 2
+size_t aspire_dense_rank_batch_workspace_bytes(int64_t J, int64_t C, int64_t max_job, int64_t k);
+int aspire_dense_rank_batch_f32(const float* rows, int64_t N, int64_t D, const int32_t* q_idx, int64_t J,
+                                const int32_t* cand_idx, int64_t C, const int32_t* job_off, int64_t max_job, int metric,
+                                float* scores, int64_t k, const int32_t* job_base, float* top_scores, int64_t* top_idx,
+                                uint64_t* keys, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * SURVEY.md 8(e)  shard merge.  The same rank in KEY form for the candidate-pool shards of a multi-GPU job:
  *   aspire_topk_keys_f32    per-query local top-k as sortable 64-bit keys [Q, k]:
  *                           (order-preserving score bits << 32) | (0xFFFFFFFF - global index), 0 = padding.
