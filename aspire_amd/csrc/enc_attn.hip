@@ -92,7 +92,7 @@ __global__ void __launch_bounds__(256) softmax_mask_kernel(float* __restrict__ s
 // workgroup share the K tile (staged k-major, dims paired (d, d+8) so the half-waves read opposite LDS bank
 // halves) and the V tile (row-major, 72-float rows: keys 4 apart land 32 banks apart).  Keys are walked in
 // tiles of 128 with the usual running max / sum rescaling (flash attention), all in fp32 with exp2.
-// HF semantics kept: scores / sqrt(64) + (1 - mask) * finfo.min, soft-max over keys (modeling_bert.py).
+// HF semantics kept: scores / sqrt(64) + (1 - mask) * finfo.min, soft-max over keys (modeling_bert.py), for any 0/1 mask (key_bias_log2).
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int kFaLdK = 132, kFaLdV = 72;
 // The fused kernels' bias table (BIAS): tab[t] = log2(e) x the bias of distance (key - query) = t - (L - 1) of head h, zero beyond
@@ -102,6 +102,15 @@ constexpr int kRelTab = 1024;
 __device__ __forceinline__ void stage_rel_bias(float* tab, const float* __restrict__ rel_bias, int rel_span, int h, int L, int tid) {
     const float* rb = rel_bias + (size_t)h * (2 * rel_span - 1) + (rel_span - L);
     for (int t = tid; t < kRelTab; t += 256) tab[t] = t < 2 * L - 1 ? rb[t] * 1.44269504088896340736f : 0.f;
+}
+// The fused kernels' additive key mask, in the log2 units of their exp2 soft-max.  A masked key gets -FLT_MAX, FINITE, as softmax_mask_kernel
+// and cls_attn_kernel keep it and as HF's (1 - mask) * finfo.min is: a score plus it rounds to -FLT_MAX itself, so next to one real key a
+// masked key weighs exp2(-FLT_MAX - max) = 0, a key tile without a real key leaves a finite running max that the first real key
+// flushes (alpha = exp2(-FLT_MAX - max) = 0), and a row without any real key attends uniformly over its L keys.  (Times log2(e) the
+// constant would overflow to -inf, and a first tile of -inf alone makes alpha = exp2(-inf + inf) = NaN for good.)  Keys past L are tile
+// padding -- other documents' rows -- and weigh exactly 0 in every case: -inf, which a tile never holds alone.
+__device__ __forceinline__ float key_bias_log2(const int64_t* __restrict__ mask_row, int kk, int L) {
+    return kk >= L ? -INFINITY : (mask_row[kk] != 0 ? 0.f : -3.4028234663852886e38f);
 }
 // ctxp (optional, instead of ctx): the context rows go out in the P layout [rows, 768] -- the A operand of the output projection
 template <bool BIAS>
@@ -165,8 +174,7 @@ __global__ void __launch_bounds__(256, 2) flash_attn_f32_kernel(const float* __r
             }
             if (tid < 128) {
                 const int kk = k0 + tid;
-                // additive mask in log2 units; keys past L are tile padding and must weigh exactly 0
-                kbias[tid] = kk >= L ? -INFINITY : (mask[(size_t)b * L + kk] != 0 ? 0.f : -3.4028234663852886e38f);
+                kbias[tid] = key_bias_log2(mask + (size_t)b * L, kk, L);
             }
         }
         __syncthreads();
@@ -190,12 +198,11 @@ __global__ void __launch_bounds__(256, 2) flash_attn_f32_kernel(const float* __r
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int key = 32 * rb + 8 * (r >> 2) + 4 * lk + (r & 3);
-                // scores * (1/8) + mask, then to log2 units; the mask constant times log2(e) overflows to -inf, which
-                // exp2 maps to the same 0 that exp(-3.4e38 - max) gives
+                // scores * (1/8) in log2 units + mask (key_bias_log2)
                 if constexpr (BIAS)
-                    sacc[rb][r] = fmaf(sacc[rb][r], kScaleLog2, rq[k0 + key]) + kbias[key] * 1.44269504088896340736f;
+                    sacc[rb][r] = fmaf(sacc[rb][r], kScaleLog2, rq[k0 + key]) + kbias[key];
                 else
-                    sacc[rb][r] = fmaf(sacc[rb][r], kScaleLog2, kbias[key] * 1.44269504088896340736f);
+                    sacc[rb][r] = fmaf(sacc[rb][r], kScaleLog2, kbias[key]);
                 tmax = fmaxf(tmax, sacc[rb][r]);
             }
         tmax = fmaxf(tmax, lane_xor<32>(tmax));
@@ -362,8 +369,7 @@ __global__ void __launch_bounds__(256, 2) flash_attn_f16x2_kernel(const float* _
             }
             if (tid < 128) {
                 const int kk = k0 + tid;
-                // additive mask; keys past L are tile padding and must weigh exactly 0
-                kbias[tid] = kk >= L ? -INFINITY : (mask[(size_t)b * L + kk] != 0 ? 0.f : -3.4028234663852886e38f);
+                kbias[tid] = key_bias_log2(mask + (size_t)b * L, kk, L);
             }
         }
         __syncthreads();
@@ -394,9 +400,9 @@ __global__ void __launch_bounds__(256, 2) flash_attn_f16x2_kernel(const float* _
             for (int r = 0; r < 16; ++r) {
                 const int key = 32 * rb + 8 * (r >> 2) + 4 * lk + (r & 3);
                 if constexpr (BIAS)
-                    sacc[rb][r] = fmaf(sacc[rb][r], kScaleLog2, rq[k0 + key]) + kbias[key] * 1.44269504088896340736f;
+                    sacc[rb][r] = fmaf(sacc[rb][r], kScaleLog2, rq[k0 + key]) + kbias[key];
                 else
-                    sacc[rb][r] = fmaf(sacc[rb][r], kScaleLog2, kbias[key] * 1.44269504088896340736f);
+                    sacc[rb][r] = fmaf(sacc[rb][r], kScaleLog2, kbias[key]);
                 tmax = fmaxf(tmax, sacc[rb][r]);
             }
         }
@@ -585,9 +591,7 @@ __device__ __forceinline__ void flash_attn_p_body(const unsigned char* __restric
         issue_kv(t, true);
         if (tid < KT) {
             const int kk = k0 + tid;
-            // additive mask; keys past L are tile padding (the next document's rows) and must weigh exactly 0
-            // (stored times log2(e), as the soft-max below wants it: the same product as flash_attn_f16x2_kernel forms per score)
-            kbias[tid] = (kk >= L ? -INFINITY : (mask[(size_t)doc0 + kk] != 0 ? 0.f : -3.4028234663852886e38f)) * 1.44269504088896340736f;
+            kbias[tid] = key_bias_log2(mask + (size_t)doc0, kk, L);      // (tile padding: the next document's rows)
         }
         // ---- S^T tile: 4 blocks of 32 keys x this wave's 32 queries; per k step the products l.h, h.l, h.h ----
         f32x16 sacc[NRB];

@@ -98,6 +98,8 @@ int aspire_span_pool_ranges_f32(const float* hidden, int64_t B, int64_t L, int64
  *   weights are borrowed device pointers in nn.Linear layout ([out, in] row-major);
  *   w_qkv is query/key/value weights concatenated along `out` ([2304, 768]), b_qkv likewise.
  *   tok_ids / type_ids / attn_mask  int64 [B, L] (type_ids may be NULL = all zero); attn_mask != 0 = real token
+ *   Any 0/1 pattern is accepted (left padding, holes, real tokens behind a key tile of padding), in every attention form; a row that
+ *   is all zero attends uniformly over its L keys, as HuggingFace's (1 - mask) * finfo.min does.
  *   hidden_out [B, L, 768]
  *   workspace  device scratch of aspire_bert_workspace_bytes(w, B, L) bytes
  * ------------------------------------------------------------------------------------------- */
