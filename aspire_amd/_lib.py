@@ -105,6 +105,8 @@ SIGNATURES = {
                                         c_void_p, c_void_p, c_void_p]),
     'aspire_l2agg_scores_f32': (c_int, [ctypes.POINTER(RepSet), ctypes.POINTER(RepSet), c_int64, c_int, c_int, c_int,
                                         ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'aspire_l2agg_backward_f32': (c_int, [ctypes.POINTER(RepSet), ctypes.POINTER(RepSet), c_int64, c_int, c_int, ctypes.c_double,
+                                          c_void_p, c_void_p, c_void_p, c_void_p]),
     'aspire_ot_sinkhorn_f32': (c_int, [ctypes.POINTER(RepSet), ctypes.POINTER(RepSet), c_int64, c_int,
                                        ctypes.POINTER(OtParams), c_void_p, c_int64, c_int, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

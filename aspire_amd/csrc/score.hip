@@ -3,7 +3,8 @@
 // batch_prep.hip, gram.hip, gramp.hip, generic.hip, fused.hip, tile16.hip; the rank: topk.hip).  Reference call structure:
 //   src/learning/facetid_models/pair_distances.py:21-92, :138-186; src/evaluation/evaluate.py:58-76 (allenai/aspire).
 //
-// Top to bottom: argument checks and ScoreArgs fills (check_repsets, fill_set_args, fill_ot_args); the max-sim entry points; the
+// Top to bottom: argument checks and ScoreArgs fills (check_repsets, fill_set_args, fill_ot_args); the max-sim entry points and the
+// backward of their aggregations (aspire_l2agg_backward_f32: checks here, the kernel in l2agg_bwd.hip); the
 // host helpers of the batched / CHUNK / REC forms -- form rules (chunk_size_ok, one_wave_form_ok, sinkhorn_form_honours_gate),
 // workspace layouts (batch_layout, l2_batch_layout, batch_tables), launch_fused_form; otAspire per call (ot_run_tiles, ot_run);
 // the batched entry points (ot_rank_batch, aspire_l2max_rank_batch_f32).  Which kernel family scores a pair decides the pair's
@@ -153,6 +154,22 @@ extern "C" int aspire_l2agg_scores_f32(const aspire_repset* q, const aspire_reps
 extern "C" int aspire_l2max_scores_f32(const aspire_repset* q, const aspire_repset* c, int64_t D, int pairing,
                                        int cdist_mode, float* scores, float* pair_sims, void* stream) {
     return aspire_l2agg_scores_f32(q, c, D, pairing, cdist_mode, ASPIRE_AGG_MAX, 1.0, scores, pair_sims, nullptr, stream);
+}
+
+extern "C" int aspire_l2agg_backward_f32(const aspire_repset* q, const aspire_repset* c, int64_t D, int pairing, int agg, double temp,
+                                         const float* grad_scores, float* grad_q_rows, float* grad_c_rows, void* stream) {
+    if (int rc = check_repsets(q, c, D, pairing)) return rc;
+    ASPIRE_REQUIRE(pairing == ASPIRE_PAIR_PAIRED, ASPIRE_ERR_UNSUPPORTED,
+                   "the backward is built for ASPIRE_PAIR_PAIRED: with ASPIRE_PAIR_CROSS a document's gradient is a sum over many pairs, "
+                   "which needs an accumulation across pairs that is not built");
+    ASPIRE_REQUIRE(agg == ASPIRE_AGG_MAX || agg == ASPIRE_AGG_TOP2 || agg == ASPIRE_AGG_ATTENTION, ASPIRE_ERR_INVALID_ARG,
+                   "bad aggregation %d", agg);
+    ASPIRE_REQUIRE(agg != ASPIRE_AGG_ATTENTION || temp > 0, ASPIRE_ERR_INVALID_ARG, "attention temperature must be positive");
+    if (q->n == 0) return ASPIRE_OK;                // no pair, no row
+    ASPIRE_REQUIRE(grad_scores && grad_q_rows && grad_c_rows, ASPIRE_ERR_INVALID_ARG, "grad_scores, grad_q_rows or grad_c_rows is null");
+    const int rows_q = q->ext > 0 ? q->ext : q->max_len, rows_c = c->ext > 0 ? c->ext : c->max_len;
+    return launch_l2agg_backward(to_dev(q), to_dev(c), agg, (float)temp, grad_scores, grad_q_rows, grad_c_rows, rows_q, rows_c,
+                                 (hipStream_t)stream);
 }
 
 namespace {

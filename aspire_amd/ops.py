@@ -388,6 +388,22 @@ def l2agg_scores(q, c, agg, temp=1.0, pairing=_lib.PAIR_CROSS, cdist_mode=_lib.C
     return (scores, pair, soft) if agg == _lib.AGG_ATTENTION else (scores, pair)
 
 
+def l2agg_backward(q, c, agg, grad_scores, temp=1.0, out=None):
+    """The gradient of the PAIRED similarities of l2max_scores (agg = _lib.AGG_MAX) / l2agg_scores (AGG_TOP2, AGG_ATTENTION) with
+    respect to the sentence rows (include/aspire_hip.h: aspire_l2agg_backward_f32).  grad_scores [P] = dLoss / dscore.  Returns
+    (grad_q_rows, grad_c_rows), laid out like q.rows / c.rows: every row of every document is written by the kernel (pad rows with
+    zeros); rows of the matrices that no document owns stay zero.  out: the two buffers to write into instead of new ones."""
+    assert q.n == c.n, 'paired scoring needs equal batch sizes'      # pair_distances.py:46
+    grad_scores = _f32(grad_scores, 'grad_scores')
+    assert grad_scores.numel() == q.n, 'grad_scores: one entry per pair'
+    gq, gc = out if out is not None else (torch.zeros_like(q.rows), torch.zeros_like(c.rows))
+    assert _f32(gq, 'grad_q_rows').shape == q.rows.shape and _f32(gc, 'grad_c_rows').shape == c.rows.shape
+    qs, cs = q.struct(), c.struct()
+    check(lib.aspire_l2agg_backward_f32(ctypes.byref(qs), ctypes.byref(cs), D, _lib.PAIR_PAIRED, agg, ctypes.c_double(temp),
+                                        _ptr(grad_scores), _ptr(gq), _ptr(gc), _stream()))
+    return gq, gc
+
+
 def group_diameter(q, c, pairing, group):
     ngroups = (c.n + group - 1) // group
     n = ngroups if pairing == _lib.PAIR_PAIRED else q.n * ngroups

@@ -6,6 +6,14 @@ allpair_masked_dist_l2max :138-186, allpair_joint_sm_negscore :348-402); copy at
 
 Inputs may live on the CPU (as in the reference's examples) or on the GPU; outputs come back on the
 device of ``query.embed``.  There is no CPU code path: without a GPU these raise.
+
+The three L2 aggregations (allpair_masked_dist_l2max, allpair_masked_dist_l2topk, AllPairMaskedAttention) are differentiable
+with respect to the sentence reps, as the reference's are under its triplet loss: with grad mode on and ``query.embed`` or
+``cand.embed`` requiring grad, the returned distance (or ``sims``) is attached to the graph and ``backward()`` leaves the gradient
+in the caller's [batch_size, encoding_dim, max_sents] layout on the caller's device.  The OT, jointsm, cosine and dot scores
+have no backward.  With ``return_pair_sims=True`` and a rep requiring grad the forward runs twice -- once for the (detached) pair
+matrices, once through the differentiable operator for ``sims`` -- and the inputs are copied to the GPU for each: correct and the same
+bits, twice the work; the train-time branch (``return_pair_sims=False``) runs it once.
 """
 import collections
 
@@ -25,6 +33,30 @@ def _to_repsets(query, cand):
     q = ops.DeviceRepSet.from_padded(query_reps.permute(0, 2, 1), query.abs_lens)
     c = ops.DeviceRepSet.from_padded(cand_reps.permute(0, 2, 1), cand.abs_lens)
     return q, c, query_reps.device
+
+
+def _wants_grad(query, cand):
+    return torch.is_grad_enabled() and (query.embed.requires_grad or cand.embed.requires_grad)
+
+
+def _differentiable_sims(query, cand, agg, temp=1.0):
+    """sims [batch_size] of the pairs (the same bits as ops.l2max_scores / ops.l2agg_scores give), attached to the graph of
+    query.embed / cand.embed: torch.ops.aspire.l2agg_pair_scores on the GPU between differentiable moves and permutes."""
+    from . import torch_ops  # noqa: F401  (registers the operator)
+    dev = ops.require_gpu()
+    assert (query.embed.size(0) == cand.embed.size(0))   # pair_distances.py:46
+    lens = []
+    for rep in (query, cand):
+        host = [int(n) for n in rep.abs_lens]
+        assert len(host) == rep.embed.size(0), 'abs_lens must have one entry per batch element'
+        if any(n <= 0 for n in host):       # (ops.DeviceRepSet's rule)
+            raise ValueError('a document without sentence rows cannot be scored (the reference raises on it: '
+                             'pair_distances.py:57); drop it from the pool')
+        lens.append(torch.as_tensor(host, dtype=torch.int32).to(dev))
+    q = query.embed.permute(0, 2, 1).to(device=dev, dtype=torch.float32)
+    c = cand.embed.permute(0, 2, 1).to(device=dev, dtype=torch.float32)
+    sims = torch.ops.aspire.l2agg_pair_scores(q, lens[0], c, lens[1], agg, float(temp))
+    return sims.to(query.embed.device)
 
 
 def ot_kwargs(hparams):
@@ -69,9 +101,13 @@ def allpair_masked_dist_l2max(query, cand, return_pair_sims=False):
     :return: positive distances [batch_size] (the smallest sentence-pair L2), or with return_pair_sims
         (sims [batch_size], pair_sims [batch_size, q_max_sents, c_max_sents]).
     """
+    if _wants_grad(query, cand) and not return_pair_sims:       # "Happens at train time" (pair_distances.py:184-186)
+        return -1 * _differentiable_sims(query, cand, _lib.AGG_MAX)
     q, c, out_dev = _to_repsets(query, cand)
     if return_pair_sims:
         sims, pair = ops.l2max_scores(q, c, pairing=_lib.PAIR_PAIRED, want_pair_sims=True)
+        if _wants_grad(query, cand):        # the pair matrix stays detached
+            sims = _differentiable_sims(query, cand, _lib.AGG_MAX)
         return sims.to(out_dev), pair.to(out_dev)
     return (-1 * ops.l2max_scores(q, c, pairing=_lib.PAIR_PAIRED)).to(out_dev)
 
@@ -83,9 +119,13 @@ def allpair_masked_dist_l2topk(query, cand, return_pair_sims=False):
     if query.embed.shape[-1] * cand.embed.shape[-1] < 2:
         # torch.topk(k=2) over the [batch, q_max_sents * c_max_sents] view raises for a single entry (pair_distances.py:333)
         raise RuntimeError('selected index k out of range')
+    if _wants_grad(query, cand) and not return_pair_sims:
+        return -1 * _differentiable_sims(query, cand, _lib.AGG_TOP2)
     q, c, out_dev = _to_repsets(query, cand)
     if return_pair_sims:
         sims, pair = ops.l2agg_scores(q, c, _lib.AGG_TOP2, pairing=_lib.PAIR_PAIRED, want_pair_sims=True)
+        if _wants_grad(query, cand):
+            sims = _differentiable_sims(query, cand, _lib.AGG_TOP2)
         return sims.to(out_dev), pair.to(out_dev)
     return (-1 * ops.l2agg_scores(q, c, _lib.AGG_TOP2, pairing=_lib.PAIR_PAIRED)).to(out_dev)
 
@@ -98,10 +138,14 @@ class AllPairMaskedAttention:
 
     def compute_distance(self, query, cand, return_pair_sims=False):
         """:return: doc_dists [batch_size]; with return_pair_sims (doc_sims, [pair_sims, pair_softmax, masked_sims])."""
+        if _wants_grad(query, cand) and not return_pair_sims:
+            return -1 * _differentiable_sims(query, cand, _lib.AGG_ATTENTION, self.cdatt_sm_temp)
         q, c, out_dev = _to_repsets(query, cand)
         kw = dict(temp=self.cdatt_sm_temp, pairing=_lib.PAIR_PAIRED)
         if return_pair_sims:
             sims, pair, soft = ops.l2agg_scores(q, c, _lib.AGG_ATTENTION, want_pair_sims=True, **kw)
+            if _wants_grad(query, cand):
+                sims = _differentiable_sims(query, cand, _lib.AGG_ATTENTION, self.cdatt_sm_temp)
             return sims.to(out_dev), [t.to(out_dev) for t in (pair, soft, soft * pair)]
         return (-1 * ops.l2agg_scores(q, c, _lib.AGG_ATTENTION, **kw)).to(out_dev)
 

@@ -20,6 +20,10 @@ implementation so that shapes propagate under FakeTensor / torch.compile tracing
     torch.ops.aspire.topk_desc(scores, k, idx_base) -> (top_scores, top_idx)                       A12  evaluate.py:76
     torch.ops.aspire.topk_keys(scores, k, idx_base) -> keys          } the shard merge of section 8(e): local top-k in key
     torch.ops.aspire.topk_merge(gathered_keys, k) -> (top_scores, top_idx)  } form, (all-gather by the caller), merge
+  differentiable (padded pairs, pair p = query p with candidate p; agg 0 max-sim / 1 top-2 / 2 attention):
+    torch.ops.aspire.l2agg_pair_scores(q, q_lens, c, c_lens, agg, temp) -> scores [B]              pair_distances.py:138-186, :295-345,
+                                         (autograd registered: the gradient with respect to q and c)                       :95-135
+    torch.ops.aspire.l2agg_pair_backward(grad_scores, q, q_lens, c, c_lens, agg, temp) -> (grad_q, grad_c)   its formula
   resident CSR pools (rows + start + len, struct aspire_repset):
     torch.ops.aspire.l2max_scores_csr / ot_scores_csr(q_rows, q_start, q_len, q_max, c_rows, c_start, c_len, c_max, ...) -> [Q * C]
     torch.ops.aspire.ot_rank_batch(q_rows, q_start, q_len, q_max, c_rows, c_start, c_len, c_max, job_off, max_job, k, ...)
@@ -306,5 +310,52 @@ def _(rows, q_idx, cand_idx, job_off, max_job, k, metric):
     return (rows.new_empty(cand_idx.shape[0]), rows.new_empty(j, k), rows.new_empty(j, k, dtype=torch.int64))
 
 
+# ---- the differentiable pair scores -------------------------------------------------------------------------------------
+# agg: 0 max-sim, 1 top-2, 2 attention (temp = cdatt_sm_temp; read by attention only).  Pair p = query p with candidate p.  The
+# forward is the existing scoring entry (aspire_l2max_scores_f32 for agg 0, aspire_l2agg_scores_f32 else): the same bits as
+# l2max_scores / ops.l2agg_scores; its autograd formula is l2agg_pair_backward (aspire_l2agg_backward_f32), which recomputes
+# the distances -- nothing but the inputs is saved.
+@torch.library.custom_op('aspire::l2agg_pair_scores', mutates_args=(), device_types='cuda')
+def l2agg_pair_scores(q: Tensor, q_lens: Tensor, c: Tensor, c_lens: Tensor, agg: int, temp: float) -> Tensor:
+    qs, cs = _padded_repset(q, q_lens), _padded_repset(c, c_lens)
+    if agg == _lib.AGG_MAX:
+        return ops.l2max_scores(qs, cs, pairing=_lib.PAIR_PAIRED)
+    return ops.l2agg_scores(qs, cs, agg, temp=temp, pairing=_lib.PAIR_PAIRED)
+
+
+@l2agg_pair_scores.register_fake
+def _(q, q_lens, c, c_lens, agg, temp):
+    return q.new_empty(_npairs(q.shape[0], c.shape[0], True))
+
+
+@torch.library.custom_op('aspire::l2agg_pair_backward', mutates_args=(), device_types='cuda')
+def l2agg_pair_backward(grad_scores: Tensor, q: Tensor, q_lens: Tensor, c: Tensor, c_lens: Tensor, agg: int,
+                        temp: float) -> Tuple[Tensor, Tensor]:
+    qs, cs = _padded_repset(q, q_lens), _padded_repset(c, c_lens)
+    gq, gc = ops.l2agg_backward(qs, cs, agg, grad_scores.to(torch.float32).contiguous(), temp=temp,
+                                out=(torch.empty_like(qs.rows), torch.empty_like(cs.rows)))     # padded: every row has its writer
+    return gq.view(q.shape), gc.view(c.shape)
+
+
+@l2agg_pair_backward.register_fake
+def _(grad_scores, q, q_lens, c, c_lens, agg, temp):
+    return q.new_empty(q.shape), c.new_empty(c.shape)
+
+
+def _l2agg_pair_setup(ctx, inputs, output):
+    q, q_lens, c, c_lens, agg, temp = inputs
+    ctx.save_for_backward(q, q_lens, c, c_lens)
+    ctx.agg, ctx.temp = agg, temp
+
+
+def _l2agg_pair_grad(ctx, grad_scores):
+    q, q_lens, c, c_lens = ctx.saved_tensors
+    gq, gc = torch.ops.aspire.l2agg_pair_backward(grad_scores, q, q_lens, c, c_lens, ctx.agg, ctx.temp)
+    return gq, None, gc, None, None, None
+
+
+l2agg_pair_scores.register_autograd(_l2agg_pair_grad, setup_context=_l2agg_pair_setup)
+
+
 OPS = ('span_mean_pool', 'span_pool_ranges', 'bert_encoder_forward', 'bert_cls_forward', 'bert_pooler', 'token_mean_pool', 'l2max_scores', 'jointsm_scores', 'ot_sinkhorn_scores', 'topk_desc', 'topk_keys', 'topk_merge',
-       'l2max_scores_csr', 'ot_scores_csr', 'ot_rank_batch', 'dense_rank_batch')
+       'l2max_scores_csr', 'ot_scores_csr', 'ot_rank_batch', 'dense_rank_batch', 'l2agg_pair_scores', 'l2agg_pair_backward')

@@ -342,6 +342,41 @@ int aspire_l2agg_scores_f32(const aspire_repset* q, const aspire_repset* c, int6
                             float* pair_softmax, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Backward of the three aggregations: what the reference's autograd computes through the branches marked "Happens at
+ * train time" of allpair_masked_dist_l2max (pair_distances.py:184-186), allpair_masked_dist_l2topk (:342-345) and
+ * AllPairMaskedAttention.compute_distance (:130-135; the soft-max is models_common/activations.py:35-61) -- through
+ * torch.max / torch.topk(k = 2) / the masked 2-D soft-max and torch.cdist (:167, :324, :120) down to the sentence rows.
+ * With s_ij = -||q_i - c_j|| over the valid block (i < q_len, j < c_len) and W_ij = dscore / ds_ij:
+ *   ASPIRE_AGG_MAX        W = 1 at the arg-max, 0 elsewhere.
+ *   ASPIRE_AGG_TOP2       W = 1 at the two largest entries.  A block of one entry has one pick: the reference's second
+ *                         pick is a masked pad entry there, its gradient belongs to a pad row and is dropped.
+ *   ASPIRE_AGG_ATTENTION  p = soft-max of s / temp, score = sum p s:  W_ij = p_ij (1 + (s_ij - score) / temp).
+ *   Ties: the first entry in row-major (i, j) order wins; the second pick is the next one.
+ *   grad_q_i = -g sum_j A_ij (q_i - c_j),  grad_c_j = +g sum_i A_ij (q_i - c_j),  A_ij = W_ij / d_ij and 0 where d_ij == 0
+ *   (torch.cdist's backward rule for coincident rows: no NaN).
+ *   pairing      ASPIRE_PAIR_PAIRED only: every document then belongs to one pair, every gradient row has one writer and
+ *                the result is the same bits on every run.  ASPIRE_PAIR_CROSS -> ASPIRE_ERR_UNSUPPORTED (a document's
+ *                gradient would be a sum over many pairs: an accumulation across pairs that is not built).
+ *   grad_scores  [P] in: g_p = dLoss / dscore_p, score_p the SIMILARITY aspire_l2agg_scores_f32 documents (a loss on the
+ *                reference's distance passes minus its gradient)
+ *   grad_q_rows, grad_c_rows  out, laid out like q->rows / c->rows (padded sets, ext > 0, and CSR sets alike).  Every row
+ *                of every document is written: valid rows with the gradient, pad rows (len <= r < ext) with exact zeros;
+ *                rows of the matrices that belong to no document are not touched.
+ *                q->rows, c->rows and both gradient buffers must be 16-byte aligned (they are read and written 16 bytes at a
+ *                time; a row is 3072 bytes, so an aligned base aligns every row).
+ * The distances are recomputed here from direct differences; nothing is kept by the forward.  For documents of more than
+ * 25 rows the forward may have used torch.cdist's matmul formula (ASPIRE_CDIST_AUTO): the pick of MAX / TOP2 can then
+ * differ from the forward's only where two entries are within about 3e-5 of each other.
+ * bad agg, temp <= 0 with ATTENTION, a NULL pointer, q->n != c->n -> ASPIRE_ERR_INVALID_ARG; D != 768, or documents of
+ * more than aspire_max_sents() rows -> ASPIRE_ERR_UNSUPPORTED; no pairs -> ASPIRE_OK without a launch.  A document longer
+ * than its set's max_len gets NaN rows (its score is NaN in the forward).  One launch on `stream`, no workspace.
+ * ------------------------------------------------------------------------------------------- */
+int aspire_l2agg_backward_f32(const aspire_repset* q, const aspire_repset* c, int64_t D, int pairing,
+                              int agg, double temp, const float* grad_scores /* [P] */,
+                              float* grad_q_rows, float* grad_c_rows /* laid out like q->rows / c->rows */,
+                              void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * A5-A8  otAspire.  Replaces AllPairMaskedWasserstein.compute_distance,
  * src/learning/facetid_models/pair_distances.py:21-92 (copy at
  * examples/ex_aspire_consent_multimatch.py:118-189), including the geomloss==0.2.4
