@@ -6,7 +6,8 @@
 // Top to bottom: argument checks and ScoreArgs fills (check_repsets, fill_set_args, fill_ot_args); the max-sim entry points and the
 // backward of their aggregations (aspire_l2agg_backward_f32: checks here, the kernel in l2agg_bwd.hip); the
 // host helpers of the batched / CHUNK / REC forms -- form rules (chunk_size_ok, one_wave_form_ok, sinkhorn_form_honours_gate),
-// workspace layouts (batch_layout, l2_batch_layout, batch_tables), launch_fused_form; otAspire per call (ot_run_tiles, ot_run);
+// workspace layouts (batch_layout, l2_batch_layout, batch_tables), launch_fused_form; otAspire per call (ot_run_tiles, ot_run)
+// and its backward (aspire_ot_backward_f32: checks here, the kernel in ot_bwd.hip);
 // the batched entry points (ot_rank_batch, aspire_l2max_rank_batch_f32).  Which kernel family scores a pair decides the pair's
 // bits, so every rule that picks one is written once and asked by every entry point; the batched entry points share their
 // argument checks and their rank with dotmax.hip through batch_host.h (batch_preamble, BatchRank).
@@ -502,6 +503,24 @@ extern "C" int aspire_ot_sinkhorn_f32(const aspire_repset* q, const aspire_repse
                                       float* out_plan, void* workspace, size_t workspace_bytes, void* stream) {
     return ot_run(q, c, D, pairing, prm, diameter, diam_group, want, scores, out_qdistr, out_cdistr, out_pairsims, out_plan,
                   workspace, workspace_bytes, stream, RankReq{0, 0, nullptr, nullptr, nullptr});
+}
+
+extern "C" int aspire_ot_backward_f32(const aspire_repset* q, const aspire_repset* c, int64_t D, int pairing, const aspire_ot_params* prm,
+                                      const float* diameter, int64_t diam_group, int want, const float* grad_scores, float* grad_q,
+                                      float* grad_c, void* stream) {
+    if (int rc = check_repsets(q, c, D, pairing)) return rc;
+    ASPIRE_REQUIRE(pairing == ASPIRE_PAIR_PAIRED, ASPIRE_ERR_UNSUPPORTED,
+                   "the backward is built for ASPIRE_PAIR_PAIRED: with ASPIRE_PAIR_CROSS a document's gradient is a sum over many pairs, "
+                   "which needs an accumulation across pairs that is not built");
+    if (int rc = check_ot_params(prm, want)) return rc;
+    ASPIRE_REQUIRE(want != ASPIRE_OT_PLAN_SIM, ASPIRE_ERR_UNSUPPORTED,
+                   "ASPIRE_OT_PLAN_SIM has no backward (the reference uses return_pair_sims at test time only)");
+    ASPIRE_REQUIRE(!diameter || diam_group > 0, ASPIRE_ERR_INVALID_ARG, "diam_group must be positive");
+    if (q->n == 0) return ASPIRE_OK;                // no pair, no row
+    ASPIRE_REQUIRE(grad_scores && grad_q && grad_c, ASPIRE_ERR_INVALID_ARG, "grad_scores, grad_q or grad_c is null");
+    const int rows_q = q->ext > 0 ? q->ext : q->max_len, rows_c = c->ext > 0 ? c->ext : c->max_len;
+    return launch_ot_backward(to_dev(q), to_dev(c), prm, diameter, diam_group, want, grad_scores, grad_q, grad_c, rows_q, rows_c,
+                              (hipStream_t)stream);
 }
 
 // Diagnostics: the cost stage of aspire_ot_sinkhorn_f32 alone (bench.py times the HBM-bound kernel of a pass this way).

@@ -193,6 +193,10 @@ int launch_pair_generic(const ScoreArgs& a, int mode, int skip_up_to, int rows_q
 int launch_l2agg_backward(const RepSet& q, const RepSet& c, int agg, float temp, const float* grad_scores, float* grad_q, float* grad_c,
                           int rows_q, int rows_c, hipStream_t stream);
 
+// ot_bwd.hip: the gradient of the otAspire distance with respect to the sentence rows, one workgroup per PAIRED pair
+int launch_ot_backward(const RepSet& q, const RepSet& c, const aspire_ot_params* prm, const float* diameter, int64_t diam_group, int want,
+                       const float* grad_scores, float* grad_q, float* grad_c, int rows_q, int rows_c, hipStream_t stream);
+
 // fused.hip: cost + Sinkhorn solve in one launch for documents of <= 8 rows (CSR inputs, CROSS or MAPPED pairing)
 bool fused_self_ok(int64_t jobs, const aspire_ot_params* prm);
 bool fused_inbox_ok(const aspire_repset* q, const float* diameter);

@@ -404,6 +404,28 @@ def l2agg_backward(q, c, agg, grad_scores, temp=1.0, out=None):
     return gq, gc
 
 
+def ot_backward(q, c, grad_scores, *, blur=0.05, scaling=0.9, sent_sm_temp=1.0, diameter=None, diam_group=0, want=_lib.OT_DISTANCE,
+                out=None):
+    """The gradient of the PAIRED otAspire scores of ot_sinkhorn (want = _lib.OT_DISTANCE or OT_SIMILARITY) with respect to the
+    sentence rows (include/aspire_hip.h: aspire_ot_backward_f32 -- a restatement of geomloss's detach pattern).  grad_scores [P] =
+    dLoss / dscore; diameter / diam_group: what the forward was given (None: every pair's own box).  Returns (grad_q_rows,
+    grad_c_rows), laid out like q.rows / c.rows: every row of every document is written by the kernel (pad rows with zeros); rows of
+    the matrices that no document owns stay zero.  out: the two buffers to write into instead of new ones."""
+    assert q.n == c.n, 'paired scoring needs equal batch sizes'      # pair_distances.py:46
+    grad_scores = _f32(grad_scores, 'grad_scores')
+    assert grad_scores.numel() == q.n, 'grad_scores: one entry per pair'
+    if diameter is not None:
+        assert diam_group > 0, 'diam_group must be positive'
+        assert _f32(diameter, 'diameter').numel() >= (q.n + diam_group - 1) // diam_group, 'diameter: one entry per group of pairs'
+    gq, gc = out if out is not None else (torch.zeros_like(q.rows), torch.zeros_like(c.rows))
+    assert _f32(gq, 'grad_q_rows').shape == q.rows.shape and _f32(gc, 'grad_c_rows').shape == c.rows.shape
+    prm = OtParams(float(blur), float(scaling), float(sent_sm_temp), _lib.CDIST_AUTO, 0)      # (cdist_mode, flags: not read)
+    qs, cs = q.struct(), c.struct()
+    check(lib.aspire_ot_backward_f32(ctypes.byref(qs), ctypes.byref(cs), D, _lib.PAIR_PAIRED, ctypes.byref(prm), _ptr(diameter),
+                                     diam_group, want, _ptr(grad_scores), _ptr(gq), _ptr(gc), _stream()))
+    return gq, gc
+
+
 def group_diameter(q, c, pairing, group):
     ngroups = (c.n + group - 1) // group
     n = ngroups if pairing == _lib.PAIR_PAIRED else q.n * ngroups

@@ -10,10 +10,15 @@ device of ``query.embed``.  There is no CPU code path: without a GPU these raise
 The three L2 aggregations (allpair_masked_dist_l2max, allpair_masked_dist_l2topk, AllPairMaskedAttention) are differentiable
 with respect to the sentence reps, as the reference's are under its triplet loss: with grad mode on and ``query.embed`` or
 ``cand.embed`` requiring grad, the returned distance (or ``sims``) is attached to the graph and ``backward()`` leaves the gradient
-in the caller's [batch_size, encoding_dim, max_sents] layout on the caller's device.  The OT, jointsm, cosine and dot scores
-have no backward.  With ``return_pair_sims=True`` and a rep requiring grad the forward runs twice -- once for the (detached) pair
-matrices, once through the differentiable operator for ``sims`` -- and the inputs are copied to the GPU for each: correct and the same
-bits, twice the work; the train-time branch (``return_pair_sims=False``) runs it once.
+in the caller's [batch_size, encoding_dim, max_sents] layout on the caller's device.  So is the OT distance,
+AllPairMaskedWasserstein.compute_distance with ``return_pair_sims=False`` (the distance function of the reference's flagship triplet
+loss, disent_models.py:241-250): its gradient is a restatement of what geomloss 0.2.4 does for SamplesLoss("sinkhorn", p=1,
+debias=False) -- the epsilon-scaling loop without grad, the last extrapolation with grad on detached arguments, the soft-max marginals
+not detached (include/aspire_hip.h, aspire_ot_backward_f32) -- since geomloss itself is not available to hold it against; with
+``return_pair_sims=True`` its outputs stay detached (the reference marks that branch "only used at test time").  The jointsm, cosine
+and dot scores have no backward.  For the L2 aggregations, with ``return_pair_sims=True`` and a rep requiring grad the forward runs
+twice -- once for the (detached) pair matrices, once through the differentiable operator for ``sims`` -- and the inputs are copied to
+the GPU for each: correct and the same bits, twice the work; the train-time branch (``return_pair_sims=False``) runs it once.
 """
 import collections
 
@@ -39,9 +44,11 @@ def _wants_grad(query, cand):
     return torch.is_grad_enabled() and (query.embed.requires_grad or cand.embed.requires_grad)
 
 
-def _differentiable_sims(query, cand, agg, temp=1.0):
+def _differentiable_sims(query, cand, agg, temp=1.0, ot=None):
     """sims [batch_size] of the pairs (the same bits as ops.l2max_scores / ops.l2agg_scores give), attached to the graph of
-    query.embed / cand.embed: torch.ops.aspire.l2agg_pair_scores on the GPU between differentiable moves and permutes."""
+    query.embed / cand.embed: torch.ops.aspire.l2agg_pair_scores on the GPU between differentiable moves and permutes.
+    ot = (blur, scaling, sent_sm_temp, want): torch.ops.aspire.ot_pair_scores instead (the bits of ops.ot_sinkhorn with one epsilon
+    schedule for the whole batch), `agg` and `temp` unread."""
     from . import torch_ops  # noqa: F401  (registers the operator)
     dev = ops.require_gpu()
     assert (query.embed.size(0) == cand.embed.size(0))   # pair_distances.py:46
@@ -55,7 +62,13 @@ def _differentiable_sims(query, cand, agg, temp=1.0):
         lens.append(torch.as_tensor(host, dtype=torch.int32).to(dev))
     q = query.embed.permute(0, 2, 1).to(device=dev, dtype=torch.float32)
     c = cand.embed.permute(0, 2, 1).to(device=dev, dtype=torch.float32)
-    sims = torch.ops.aspire.l2agg_pair_scores(q, lens[0], c, lens[1], agg, float(temp))
+    if ot is not None:
+        blur, scaling, sent_sm_temp, want = ot
+        # geomloss derives ONE epsilon schedule from the bounding box of the whole batch, pads included: group = batch size
+        sims = torch.ops.aspire.ot_pair_scores(q, lens[0], c, lens[1], float(blur), float(scaling), float(sent_sm_temp),
+                                               max(q.size(0), 1), want)
+    else:
+        sims = torch.ops.aspire.l2agg_pair_scores(q, lens[0], c, lens[1], agg, float(temp))
     return sims.to(query.embed.device)
 
 
@@ -83,7 +96,12 @@ class AllPairMaskedWasserstein:
         :param cand: namedtuple(embed: batch_size x encoding_dim x c_max_sents; abs_lens: list(int))
         :return: wasserstein distances [batch_size]; with return_pair_sims the plan-weighted similarity and
             [query_distr, cand_distr, pair_sims, transport_plan, masked_sims] (pair_distances.py:86).
+        With grad mode on, an embed requiring grad and return_pair_sims=False the distance is attached to the graph (the train-time
+        branch, pair_distances.py:88-92; the same bits as without).  With return_pair_sims=True everything stays detached: the
+        reference marks that branch "only used at test time", and the plan-weighted similarity has no backward here.
         """
+        if _wants_grad(query, cand) and not return_pair_sims:
+            return _differentiable_sims(query, cand, None, ot=(self.geoml_blur, self.geoml_scaling, self.sent_sm_temp, _lib.OT_DISTANCE))
         q, c, out_dev = _to_repsets(query, cand)
         # geomloss derives ONE epsilon schedule from the bounding box of the whole batch, pads included.
         diam = ops.group_diameter(q, c, _lib.PAIR_PAIRED, group=max(q.n, 1))

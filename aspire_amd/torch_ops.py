@@ -24,6 +24,9 @@ implementation so that shapes propagate under FakeTensor / torch.compile tracing
     torch.ops.aspire.l2agg_pair_scores(q, q_lens, c, c_lens, agg, temp) -> scores [B]              pair_distances.py:138-186, :295-345,
                                          (autograd registered: the gradient with respect to q and c)                       :95-135
     torch.ops.aspire.l2agg_pair_backward(grad_scores, q, q_lens, c, c_lens, agg, temp) -> (grad_q, grad_c)   its formula
+    torch.ops.aspire.ot_pair_scores(q, q_lens, c, c_lens, blur, scaling, temp, group, want) -> scores [B]   pair_distances.py:21-92
+                                         (autograd registered; want 0 distance / 2 -distance; group as ot_sinkhorn_scores)
+    torch.ops.aspire.ot_pair_backward(grad_scores, q, q_lens, c, c_lens, blur, scaling, temp, group, want) -> (grad_q, grad_c)
   resident CSR pools (rows + start + len, struct aspire_repset):
     torch.ops.aspire.l2max_scores_csr / ot_scores_csr(q_rows, q_start, q_len, q_max, c_rows, c_start, c_len, c_max, ...) -> [Q * C]
     torch.ops.aspire.ot_rank_batch(q_rows, q_start, q_len, q_max, c_rows, c_start, c_len, c_max, job_off, max_job, k, ...)
@@ -357,5 +360,59 @@ def _l2agg_pair_grad(ctx, grad_scores):
 l2agg_pair_scores.register_autograd(_l2agg_pair_grad, setup_context=_l2agg_pair_setup)
 
 
+# ---- the differentiable otAspire distance ---------------------------------------------------------------------------------
+# group / want as ot_sinkhorn_scores (want: 0 distance, 2 -distance; 1, the plan-weighted similarity, has no backward).  The forward
+# is the existing PAIRED scoring call: the same bits as ot_sinkhorn_scores(..., paired=True, extras=False).  Its autograd formula is
+# ot_pair_backward (aspire_ot_backward_f32: a restatement of geomloss's detach pattern, include/aspire_hip.h), which repeats the solve
+# from the inputs -- nothing else is saved -- and forms the group diameters again from them, so that forward and backward see one
+# epsilon schedule.
+def _ot_pair_diameter(qs, cs, group):
+    return ops.group_diameter(qs, cs, _lib.PAIR_PAIRED, group) if group > 0 else None
+
+
+@torch.library.custom_op('aspire::ot_pair_scores', mutates_args=(), device_types='cuda')
+def ot_pair_scores(q: Tensor, q_lens: Tensor, c: Tensor, c_lens: Tensor, blur: float, scaling: float, temp: float, group: int,
+                   want: int) -> Tensor:
+    qs, cs = _padded_repset(q, q_lens), _padded_repset(c, c_lens)
+    return ops.ot_sinkhorn(qs, cs, pairing=_lib.PAIR_PAIRED, blur=blur, scaling=scaling, sent_sm_temp=temp,
+                           diameter=_ot_pair_diameter(qs, cs, group), diam_group=group, want=want)
+
+
+@ot_pair_scores.register_fake
+def _(q, q_lens, c, c_lens, blur, scaling, temp, group, want):
+    return q.new_empty(_npairs(q.shape[0], c.shape[0], True))
+
+
+@torch.library.custom_op('aspire::ot_pair_backward', mutates_args=(), device_types='cuda')
+def ot_pair_backward(grad_scores: Tensor, q: Tensor, q_lens: Tensor, c: Tensor, c_lens: Tensor, blur: float, scaling: float,
+                     temp: float, group: int, want: int) -> Tuple[Tensor, Tensor]:
+    qs, cs = _padded_repset(q, q_lens), _padded_repset(c, c_lens)
+    gq, gc = ops.ot_backward(qs, cs, grad_scores.to(torch.float32).contiguous(), blur=blur, scaling=scaling, sent_sm_temp=temp,
+                             diameter=_ot_pair_diameter(qs, cs, group), diam_group=group, want=want,
+                             out=(torch.empty_like(qs.rows), torch.empty_like(cs.rows)))     # padded: every row has its writer
+    return gq.view(q.shape), gc.view(c.shape)
+
+
+@ot_pair_backward.register_fake
+def _(grad_scores, q, q_lens, c, c_lens, blur, scaling, temp, group, want):
+    return q.new_empty(q.shape), c.new_empty(c.shape)
+
+
+def _ot_pair_setup(ctx, inputs, output):
+    q, q_lens, c, c_lens, blur, scaling, temp, group, want = inputs
+    ctx.save_for_backward(q, q_lens, c, c_lens)
+    ctx.prm = (blur, scaling, temp, group, want)
+
+
+def _ot_pair_grad(ctx, grad_scores):
+    q, q_lens, c, c_lens = ctx.saved_tensors
+    gq, gc = torch.ops.aspire.ot_pair_backward(grad_scores, q, q_lens, c, c_lens, *ctx.prm)
+    return gq, None, gc, None, None, None, None, None, None
+
+
+ot_pair_scores.register_autograd(_ot_pair_grad, setup_context=_ot_pair_setup)
+
+
 OPS = ('span_mean_pool', 'span_pool_ranges', 'bert_encoder_forward', 'bert_cls_forward', 'bert_pooler', 'token_mean_pool', 'l2max_scores', 'jointsm_scores', 'ot_sinkhorn_scores', 'topk_desc', 'topk_keys', 'topk_merge',
-       'l2max_scores_csr', 'ot_scores_csr', 'ot_rank_batch', 'dense_rank_batch', 'l2agg_pair_scores', 'l2agg_pair_backward')
+       'l2max_scores_csr', 'ot_scores_csr', 'ot_rank_batch', 'dense_rank_batch', 'l2agg_pair_scores', 'l2agg_pair_backward',
+       'ot_pair_scores', 'ot_pair_backward')

@@ -453,6 +453,45 @@ int aspire_ot_sinkhorn_f32(const aspire_repset* q, const aspire_repset* c, int64
                            float* out_pairsims, float* out_plan, void* workspace, size_t workspace_bytes,
                            void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Backward of the otAspire distance: the gradient of OT_eps = <a, f> + <b, g> with respect to the sentence rows, what the
+ * reference's autograd computes through the train-time branch of AllPairMaskedWasserstein.compute_distance
+ * (pair_distances.py:88-92: SamplesLoss("sinkhorn", p=1, debias=False, potentials=False)) and the marginals (:49-60).
+ * A RESTATEMENT: geomloss 0.2.4 is not vendored and its solver is "parity unpinned" here, so this is the gradient of what its
+ * sinkhorn_tensorized is read to do -- costs C_xy = cost(x, y.detach()), C_yx = cost(y, x.detach()); the epsilon-scaling
+ * loop without grad; only the last extrapolation with grad, on detached (log-weight + potential / eps) arguments; the value
+ * <a, b_x> + <b, a_y> with the marginals a, b NOT detached; the diameter a constant.  Per pair, gs = dLoss / dscore, la / lb
+ * geomloss's log-weights, eps = blur, f0 / g0 the potentials after the last averaged step, tau = sent_sm_temp:
+ *   f_i = -eps LSE_j(lb_j + (g0_j - C_ij) / eps),  g_j = -eps LSE_i(la_i + (f0_i - C_ij) / eps)   (the last extrapolation)
+ *   C_ij = sqrt(max(d_ij^2, 1e-8)),  s_ij = -d_ij (the torch.cdist block of the marginals),  d_ij = ||x_i - y_j||
+ *   W_ij = exp(lb_j + (g0_j - C_ij + f_i) / eps)   (every row i sums to 1)
+ *   V_ij = exp(la_i + (f0_i - C_ij + g_j) / eps)   (every column j sums to 1)
+ *   u_i = a_i (f_i - sum_k a_k f_k) / tau  at entry (i, j*(i)), j*(i) = the FIRST arg-max over j of s_ij in the valid block
+ *   v_j = b_j (g_j - sum_l b_l g_l) / tau  at entry (i*(j), j), i*(j) = the first arg-max over i
+ *   M_ij = u_i [j == j*(i)] + v_j [i == i*(j)]
+ *   grad_x_i = gs sum_j ( a_i W_ij [d_ij^2 > 1e-8] / C_ij  -  M_ij [d_ij > 0] / d_ij ) (x_i - y_j)
+ *   grad_y_j = gs sum_i ( M_ij [d_ij > 0] / d_ij  -  b_j V_ij [d_ij^2 > 1e-8] / C_ij ) (x_i - y_j)
+ * x receives the transport term through f only, y through g only (the detach pattern); both receive the marginal term.
+ *   pairing      ASPIRE_PAIR_PAIRED only (every gradient row has one writer: no atomics, the same bits on every run);
+ *                ASPIRE_PAIR_CROSS -> ASPIRE_ERR_UNSUPPORTED.
+ *   prm          blur, scaling, sent_sm_temp as in the forward; cdist_mode and flags are not read: d_ij comes from direct
+ *                differences everywhere (C and s both), also where the forward used the matmul expansion -- the two
+ *                differ by rounding, and the expansion cancels where training drives rows together.
+ *   diameter, diam_group   as aspire_ot_sinkhorn_f32 reads them in PAIRED mode: diameter[p / diam_group], or the box of
+ *                the pair's own valid rows when diameter is NULL.  Pass what the forward was given.
+ *   want         ASPIRE_OT_DISTANCE, or ASPIRE_OT_SIMILARITY (the sign flips); ASPIRE_OT_PLAN_SIM has no backward
+ *                (return_pair_sims is "only used at test time", pair_distances.py:62) -> ASPIRE_ERR_UNSUPPORTED.
+ *   grad_scores  [P] in.   grad_q, grad_c  out, laid out like q->rows / c->rows (padded sets, ext > 0, and CSR sets alike):
+ *                every row of every document is written, pad rows (len <= r < ext) with exact zeros; rows that belong to
+ *                no document are not touched.  Rows and gradient buffers must be 16-byte aligned.
+ * q->n != c->n, bad params, a NULL pointer -> ASPIRE_ERR_INVALID_ARG; D != 768 or documents of more than aspire_max_sents()
+ * rows -> ASPIRE_ERR_UNSUPPORTED; no pairs -> ASPIRE_OK without a launch.  A document longer than its set's max_len gets
+ * NaN rows.  One launch on `stream` (one workgroup per pair, the solve repeated in LDS), no workspace.
+ * ------------------------------------------------------------------------------------------- */
+int aspire_ot_backward_f32(const aspire_repset* q, const aspire_repset* c, int64_t D, int pairing,
+                           const aspire_ot_params* prm, const float* diameter, int64_t diam_group, int want,
+                           const float* grad_scores, float* grad_q, float* grad_c, void* stream);
+
 /* geomloss max_diameter (sinkhorn_divergence.py of geomloss 0.2.4) for batched calls: the L2 norm of
  * the per-coordinate bounding box over ALL rows of the call's x and y tensors, zero pad rows included.
  *   CROSS : diameter[q * ngroups + g] covers query q's rows and the rows of candidates
