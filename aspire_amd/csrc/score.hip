@@ -4,7 +4,8 @@
 //   src/learning/facetid_models/pair_distances.py:21-92, :138-186; src/evaluation/evaluate.py:58-76 (allenai/aspire).
 //
 // Top to bottom: argument checks and ScoreArgs fills (check_repsets, fill_set_args, fill_ot_args); the max-sim entry points and the
-// backward of their aggregations (aspire_l2agg_backward_f32: checks here, the kernel in l2agg_bwd.hip); the
+// backward of their aggregations (aspire_l2agg_backward_f32: checks here, the kernel in l2agg_bwd.hip), the checks of
+// aspire_jointsm_backward_f32 (jointsm_bwd.hip) and of the supervised-alignment pair aspire_l2sup_scores_f32 / _backward_f32 (l2sup.hip); the
 // host helpers of the batched / CHUNK / REC forms -- form rules (chunk_size_ok, one_wave_form_ok, sinkhorn_form_honours_gate),
 // workspace layouts (batch_layout, l2_batch_layout, batch_tables), launch_fused_form; otAspire per call (ot_run_tiles, ot_run)
 // and its backward (aspire_ot_backward_f32: checks here, the kernel in ot_bwd.hip);
@@ -170,6 +171,40 @@ extern "C" int aspire_l2agg_backward_f32(const aspire_repset* q, const aspire_re
     ASPIRE_REQUIRE(grad_scores && grad_q_rows && grad_c_rows, ASPIRE_ERR_INVALID_ARG, "grad_scores, grad_q_rows or grad_c_rows is null");
     const int rows_q = q->ext > 0 ? q->ext : q->max_len, rows_c = c->ext > 0 ? c->ext : c->max_len;
     return launch_l2agg_backward(to_dev(q), to_dev(c), agg, (float)temp, grad_scores, grad_q_rows, grad_c_rows, rows_q, rows_c,
+                                 (hipStream_t)stream);
+}
+
+// Backward of the joint soft-max alignment score (the forward is in jointsm.hip; the kernel in jointsm_bwd.hip)
+extern "C" int aspire_jointsm_backward_f32(const aspire_repset* q, const aspire_repset* c, int64_t D, int pairing,
+                                           const float* grad_scores, float* grad_q_rows, float* grad_c_rows, void* stream) {
+    if (int rc = check_repsets(q, c, D, pairing)) return rc;
+    ASPIRE_REQUIRE(pairing == ASPIRE_PAIR_PAIRED, ASPIRE_ERR_UNSUPPORTED,
+                   "the backward is built for ASPIRE_PAIR_PAIRED: with ASPIRE_PAIR_CROSS a document's gradient is a sum over many pairs, "
+                   "which needs an accumulation across pairs that is not built");
+    if (q->n == 0) return ASPIRE_OK;                // no pair, no row
+    ASPIRE_REQUIRE(grad_scores && grad_q_rows && grad_c_rows, ASPIRE_ERR_INVALID_ARG, "grad_scores, grad_q_rows or grad_c_rows is null");
+    const int rows_q = q->ext > 0 ? q->ext : q->max_len, rows_c = c->ext > 0 ? c->ext : c->max_len;
+    return launch_jointsm_backward(to_dev(q), to_dev(c), grad_scores, grad_q_rows, grad_c_rows, rows_q, rows_c, (hipStream_t)stream);
+}
+
+// The supervised-alignment distances and their backward (kernels in l2sup.hip): PAIRED only, no pairing argument
+extern "C" int aspire_l2sup_scores_f32(const aspire_repset* q, const aspire_repset* c, int64_t D, const int32_t* align, int weighted,
+                                       float* scores, void* stream) {
+    if (int rc = check_repsets(q, c, D, ASPIRE_PAIR_PAIRED)) return rc;
+    if (q->n == 0) return ASPIRE_OK;
+    ASPIRE_REQUIRE(align && scores, ASPIRE_ERR_INVALID_ARG, "align or scores is null");
+    const int rows_q = q->ext > 0 ? q->ext : q->max_len, rows_c = c->ext > 0 ? c->ext : c->max_len;
+    return launch_l2sup_scores(to_dev(q), to_dev(c), align, weighted != 0, scores, rows_q, rows_c, (hipStream_t)stream);
+}
+
+extern "C" int aspire_l2sup_backward_f32(const aspire_repset* q, const aspire_repset* c, int64_t D, const int32_t* align, int weighted,
+                                         const float* grad_scores, float* grad_q_rows, float* grad_c_rows, void* stream) {
+    if (int rc = check_repsets(q, c, D, ASPIRE_PAIR_PAIRED)) return rc;
+    if (q->n == 0) return ASPIRE_OK;
+    ASPIRE_REQUIRE(align && grad_scores && grad_q_rows && grad_c_rows, ASPIRE_ERR_INVALID_ARG,
+                   "align, grad_scores, grad_q_rows or grad_c_rows is null");
+    const int rows_q = q->ext > 0 ? q->ext : q->max_len, rows_c = c->ext > 0 ? c->ext : c->max_len;
+    return launch_l2sup_backward(to_dev(q), to_dev(c), align, weighted != 0, grad_scores, grad_q_rows, grad_c_rows, rows_q, rows_c,
                                  (hipStream_t)stream);
 }
 

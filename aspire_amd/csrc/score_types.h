@@ -197,6 +197,16 @@ int launch_l2agg_backward(const RepSet& q, const RepSet& c, int agg, float temp,
 int launch_ot_backward(const RepSet& q, const RepSet& c, const aspire_ot_params* prm, const float* diameter, int64_t diam_group, int want,
                        const float* grad_scores, float* grad_q, float* grad_c, int rows_q, int rows_c, hipStream_t stream);
 
+// jointsm_bwd.hip: the gradient of the joint soft-max alignment score with respect to the sentence rows, one workgroup per PAIRED pair
+int launch_jointsm_backward(const RepSet& q, const RepSet& c, const float* grad_scores, float* grad_q, float* grad_c, int rows_q,
+                            int rows_c, hipStream_t stream);
+
+// l2sup.hip: the L2 distance of one pre-aligned sentence pair per PAIRED pair (align: device [P, 2]) and its gradient
+int launch_l2sup_scores(const RepSet& q, const RepSet& c, const int32_t* align, int weighted, float* scores, int rows_q, int rows_c,
+                        hipStream_t stream);
+int launch_l2sup_backward(const RepSet& q, const RepSet& c, const int32_t* align, int weighted, const float* grad_scores, float* grad_q,
+                          float* grad_c, int rows_q, int rows_c, hipStream_t stream);
+
 // fused.hip: cost + Sinkhorn solve in one launch for documents of <= 8 rows (CSR inputs, CROSS or MAPPED pairing)
 bool fused_self_ok(int64_t jobs, const aspire_ot_params* prm);
 bool fused_inbox_ok(const aspire_repset* q, const float* diameter);

@@ -591,6 +591,55 @@ def jointsm_scores(q, c, pairing=_lib.PAIR_CROSS, want_pair_softmax=False):
     return (scores, soft) if want_pair_softmax else scores
 
 
+def _grad_call_args(q, c, grad_scores, out):
+    """What the backward entries share: the checked grad_scores [P] and the two gradient buffers laid out like q.rows / c.rows."""
+    assert q.n == c.n, 'paired scoring needs equal batch sizes'      # pair_distances.py:46
+    grad_scores = _f32(grad_scores, 'grad_scores')
+    assert grad_scores.numel() == q.n, 'grad_scores: one entry per pair'
+    gq, gc = out if out is not None else (torch.zeros_like(q.rows), torch.zeros_like(c.rows))
+    assert _f32(gq, 'grad_q_rows').shape == q.rows.shape and _f32(gc, 'grad_c_rows').shape == c.rows.shape
+    return grad_scores, gq, gc
+
+
+def jointsm_backward(q, c, grad_scores, out=None):
+    """The gradient of the PAIRED similarities of jointsm_scores with respect to the sentence rows (include/aspire_hip.h:
+    aspire_jointsm_backward_f32).  grad_scores [P] = dLoss / dscore.  Returns (grad_q_rows, grad_c_rows), laid out like q.rows /
+    c.rows: every row of every document is written by the kernel (pad rows with zeros); rows of the matrices that no document owns
+    stay zero.  out: the two buffers to write into instead of new ones."""
+    grad_scores, gq, gc = _grad_call_args(q, c, grad_scores, out)
+    qs, cs = q.struct(), c.struct()
+    check(lib.aspire_jointsm_backward_f32(ctypes.byref(qs), ctypes.byref(cs), D, _lib.PAIR_PAIRED, _ptr(grad_scores), _ptr(gq), _ptr(gc),
+                                          _stream()))
+    return gq, gc
+
+
+def _align_i32(align, n):
+    assert _i32(align, 'align').shape == (n, 2), 'align: int32 [P, 2] (query row, candidate row)'
+    return align
+
+
+def l2sup_scores(q, c, align, weighted=False):
+    """pair_distances.py:189-292: sims [P] = -||q_i - c_j|| of the PAIRED pairs' pre-aligned sentences, (i, j) = align[p] clipped to
+    the documents' last rows (weighted: divided by q_len * c_len).  align: int32 [P, 2] on the GPU, no negative entries
+    (include/aspire_hip.h: aspire_l2sup_scores_f32)."""
+    assert q.n == c.n, 'paired scoring needs equal batch sizes'      # pair_distances.py:221
+    scores = torch.empty(q.n, device=q.rows.device, dtype=torch.float32)
+    qs, cs = q.struct(), c.struct()
+    check(lib.aspire_l2sup_scores_f32(ctypes.byref(qs), ctypes.byref(cs), D, _ptr(_align_i32(align, q.n)), int(bool(weighted)),
+                                      _ptr(scores), _stream()))
+    return scores
+
+
+def l2sup_backward(q, c, align, grad_scores, weighted=False, out=None):
+    """The gradient of l2sup_scores with respect to the sentence rows (aspire_l2sup_backward_f32): two non-zero rows per pair, exact
+    zeros in every other row of the pair's documents.  Arguments and returns as jointsm_backward."""
+    grad_scores, gq, gc = _grad_call_args(q, c, grad_scores, out)
+    qs, cs = q.struct(), c.struct()
+    check(lib.aspire_l2sup_backward_f32(ctypes.byref(qs), ctypes.byref(cs), D, _ptr(_align_i32(align, q.n)), int(bool(weighted)),
+                                        _ptr(grad_scores), _ptr(gq), _ptr(gc), _stream()))
+    return gq, gc
+
+
 def jointsm_rank_batch(q, c, job_off, max_job, k, out=None, workspace=None, job_base=None, key_form=False):
     """The joint soft-max alignment score over J independent (query, pool) jobs in ONE call (include/aspire_hip.h:
     aspire_jointsm_rank_batch_f32); arguments and returns as l2max_rank_batch."""

@@ -2,7 +2,7 @@
 meaning and error behaviour; the arithmetic runs in libaspire_hip.so on the GPU.
 
 Reference: src/learning/facetid_models/pair_distances.py (AllPairMaskedWasserstein :14-92,
-allpair_masked_dist_l2max :138-186, allpair_joint_sm_negscore :348-402); copy at examples/ex_aspire_consent_multimatch.py:111-189.
+allpair_masked_dist_l2max :138-186, allpair_masked_dist_l2sup / _weighted :189-292, allpair_joint_sm_negscore :348-402); copy at examples/ex_aspire_consent_multimatch.py:111-189.
 
 Inputs may live on the CPU (as in the reference's examples) or on the GPU; outputs come back on the
 device of ``query.embed``.  There is no CPU code path: without a GPU these raise.
@@ -15,8 +15,11 @@ AllPairMaskedWasserstein.compute_distance with ``return_pair_sims=False`` (the d
 loss, disent_models.py:241-250): its gradient is a restatement of what geomloss 0.2.4 does for SamplesLoss("sinkhorn", p=1,
 debias=False) -- the epsilon-scaling loop without grad, the last extrapolation with grad on detached arguments, the soft-max marginals
 not detached (include/aspire_hip.h, aspire_ot_backward_f32) -- since geomloss itself is not available to hold it against; with
-``return_pair_sims=True`` its outputs stay detached (the reference marks that branch "only used at test time").  The jointsm, cosine
-and dot scores have no backward.  For the L2 aggregations, with ``return_pair_sims=True`` and a rep requiring grad the forward runs
+``return_pair_sims=True`` its outputs stay detached (the reference marks that branch "only used at test time").  Differentiable too are
+allpair_joint_sm_negscore, the dist_function of WordSentAlignPolyEnc (aspire_jointsm_backward_f32; ``pair_sm`` stays detached), and the
+supervised-alignment distances allpair_masked_dist_l2sup / allpair_masked_dist_l2sup_weighted, the criterion_sentsup of
+WordSentAbsSupAlignBiEnc (aspire_l2sup_backward_f32).  The cosine and dot scores have no backward: the reference does not train with
+them.  For the L2 aggregations and jointsm, with ``return_pair_sims=True`` and a rep requiring grad the forward runs
 twice -- once for the (detached) pair matrices, once through the differentiable operator for ``sims`` -- and the inputs are copied to
 the GPU for each: correct and the same bits, twice the work; the train-time branch (``return_pair_sims=False``) runs it once.
 """
@@ -27,6 +30,7 @@ import torch
 from . import _lib, ops
 
 rep_len_tup = collections.namedtuple('RepLen', ['embed', 'abs_lens'])
+rep_len_ali_tup = collections.namedtuple('RepLenAli', ['embed', 'abs_lens', 'align_idxs'])      # disent_models.py:17
 
 
 def _to_repsets(query, cand):
@@ -44,11 +48,12 @@ def _wants_grad(query, cand):
     return torch.is_grad_enabled() and (query.embed.requires_grad or cand.embed.requires_grad)
 
 
-def _differentiable_sims(query, cand, agg, temp=1.0, ot=None):
+def _differentiable_sims(query, cand, agg, temp=1.0, ot=None, op=None):
     """sims [batch_size] of the pairs (the same bits as ops.l2max_scores / ops.l2agg_scores give), attached to the graph of
     query.embed / cand.embed: torch.ops.aspire.l2agg_pair_scores on the GPU between differentiable moves and permutes.
     ot = (blur, scaling, sent_sm_temp, want): torch.ops.aspire.ot_pair_scores instead (the bits of ops.ot_sinkhorn with one epsilon
-    schedule for the whole batch), `agg` and `temp` unread."""
+    schedule for the whole batch), `agg` and `temp` unread.  op: a callable (q, q_lens, c, c_lens) -> sims on the GPU tensors instead
+    (the jointsm and l2sup operators)."""
     from . import torch_ops  # noqa: F401  (registers the operator)
     dev = ops.require_gpu()
     assert (query.embed.size(0) == cand.embed.size(0))   # pair_distances.py:46
@@ -62,7 +67,9 @@ def _differentiable_sims(query, cand, agg, temp=1.0, ot=None):
         lens.append(torch.as_tensor(host, dtype=torch.int32).to(dev))
     q = query.embed.permute(0, 2, 1).to(device=dev, dtype=torch.float32)
     c = cand.embed.permute(0, 2, 1).to(device=dev, dtype=torch.float32)
-    if ot is not None:
+    if op is not None:
+        sims = op(q, lens[0], c, lens[1])
+    elif ot is not None:
         blur, scaling, sent_sm_temp, want = ot
         # geomloss derives ONE epsilon schedule from the bounding box of the whole batch, pads included: group = batch size
         sims = torch.ops.aspire.ot_pair_scores(q, lens[0], c, lens[1], float(blur), float(scaling), float(sent_sm_temp),
@@ -172,9 +179,46 @@ def allpair_joint_sm_negscore(query, cand, return_pair_sims=False):
     """pair_distances.py:348-402 (score_aggregation 'jointsm'): the query's and the candidate's sentences re-expressed through the
     joint soft-max of their scaled dot products, the dot similarities to the aligned reps summed -- 2 sum_ij p_ij <q_i, c_j>.
     :return: a distance [batch_size] (minus that sum: "because the optimizer calls for it"), or with return_pair_sims
-        (distance, pair_sm [batch_size, q_max_sents, c_max_sents]: the soft-max, 0.0 outside a pair's valid block)."""
+        (distance, pair_sm [batch_size, q_max_sents, c_max_sents]: the soft-max, 0.0 outside a pair's valid block).
+    With grad mode on and an embed requiring grad the distance is attached to the graph (pair_sm never is); without, today's bits."""
+    if _wants_grad(query, cand) and not return_pair_sims:       # the triplet loss of WordSentAlignPolyEnc (disent_models.py:868-875)
+        return -1.0 * _differentiable_sims(query, cand, None, op=_jointsm_pair_op)
     q, c, out_dev = _to_repsets(query, cand)
     if return_pair_sims:
         sims, pair_sm = ops.jointsm_scores(q, c, pairing=_lib.PAIR_PAIRED, want_pair_softmax=True)
+        if _wants_grad(query, cand):        # pair_sm stays detached
+            sims = _differentiable_sims(query, cand, None, op=_jointsm_pair_op)
         return (-1.0 * sims).to(out_dev), pair_sm.to(out_dev)
     return (-1.0 * ops.jointsm_scores(q, c, pairing=_lib.PAIR_PAIRED)).to(out_dev)
+
+
+def _jointsm_pair_op(q, q_lens, c, c_lens):
+    return torch.ops.aspire.jointsm_pair_scores(q, q_lens, c, c_lens)
+
+
+def _l2sup_dist(query, cand, weighted):
+    """The distance ||q_i - c_j|| of every pair's pre-aligned sentences (i, j) = cand.align_idxs[p], each index clipped to its
+    document's last row (pair_distances.py:214-215; unlike the reference the clipped values are NOT written back into the caller's
+    list), divided by q_len * c_len when `weighted`.  One code path with and without grad: torch.ops.aspire.l2sup_pair_scores."""
+    from . import torch_ops  # noqa: F401  (registers the operator)
+    align = [[int(a) for a in pair] for pair in cand.align_idxs]
+    assert len(align) == query.embed.size(0) and all(len(pair) == 2 for pair in align), \
+        'align_idxs: one (query sentence, candidate sentence) per batch element'
+    if any(a < 0 for pair in align for a in pair):
+        raise ValueError('align_idxs must not be negative (the reference would index from the end of the padded block)')
+    align = torch.as_tensor(align, dtype=torch.int32).reshape(-1, 2).to(ops.require_gpu())
+    sims = _differentiable_sims(query, cand, None, op=lambda q, ql, c, cl: torch.ops.aspire.l2sup_pair_scores(q, ql, c, cl, align, weighted))
+    return -1 * sims
+
+
+def allpair_masked_dist_l2sup(query, cand):
+    """pair_distances.py:189-235: the L2 distance of the (pre) aligned pair of sentences.
+    :param cand: namedtuple(embed, abs_lens, align_idxs: list([int, int]); alignment from query to cand) -- rep_len_ali_tup
+    :return: positive distances [batch_size], attached to the graph when an embed requires grad."""
+    return _l2sup_dist(query, cand, False)
+
+
+def allpair_masked_dist_l2sup_weighted(query, cand):
+    """pair_distances.py:238-292: allpair_masked_dist_l2sup divided by the number of entries q_len * c_len of the pair's cross-document
+    block ("for use in multi tasking with the OT loss")."""
+    return _l2sup_dist(query, cand, True)

@@ -9,7 +9,9 @@ TrainedScoringModel (src/pre_process/pp_gen_nearest.py:36-87: ``predict``), plus
     ranked = model.rank(query_sent_reps, pool_sent_reps, cand_pids)        # [(pid, -sim), ...] best first
 
 The encoder is AspireConSent's (the reference class inherits WordSentAlignBiEnc's partial_forward / sent_reps_bert unchanged); the
-score is aspire_jointsm_scores_f32 (include/aspire_hip.h, A14).  Training (forward_rank, the triplet loss) is not built.
+score is aspire_jointsm_scores_f32 (include/aspire_hip.h, A14).  The model's dist_function,
+pair_distances.allpair_joint_sm_negscore, is differentiable with respect to the sentence reps (aspire_jointsm_backward_f32), so its
+triplet loss can be written; forward_rank and a trainer are still not built.
 """
 import codecs
 import json

@@ -27,6 +27,12 @@ implementation so that shapes propagate under FakeTensor / torch.compile tracing
     torch.ops.aspire.ot_pair_scores(q, q_lens, c, c_lens, blur, scaling, temp, group, want) -> scores [B]   pair_distances.py:21-92
                                          (autograd registered; want 0 distance / 2 -distance; group as ot_sinkhorn_scores)
     torch.ops.aspire.ot_pair_backward(grad_scores, q, q_lens, c, c_lens, blur, scaling, temp, group, want) -> (grad_q, grad_c)
+    torch.ops.aspire.jointsm_pair_scores(q, q_lens, c, c_lens) -> scores [B]                       pair_distances.py:348-402
+                                         (autograd registered; the bits of jointsm_scores(..., paired=True))
+    torch.ops.aspire.jointsm_pair_backward(grad_scores, q, q_lens, c, c_lens) -> (grad_q, grad_c)
+    torch.ops.aspire.l2sup_pair_scores(q, q_lens, c, c_lens, align, weighted) -> scores [B]        pair_distances.py:189-292
+                                         (autograd registered; align int32 [B, 2]: the pre-aligned (query row, candidate row))
+    torch.ops.aspire.l2sup_pair_backward(grad_scores, q, q_lens, c, c_lens, align, weighted) -> (grad_q, grad_c)
   resident CSR pools (rows + start + len, struct aspire_repset):
     torch.ops.aspire.l2max_scores_csr / ot_scores_csr(q_rows, q_start, q_len, q_max, c_rows, c_start, c_len, c_max, ...) -> [Q * C]
     torch.ops.aspire.ot_rank_batch(q_rows, q_start, q_len, q_max, c_rows, c_start, c_len, c_max, job_off, max_job, k, ...)
@@ -413,6 +419,86 @@ def _ot_pair_grad(ctx, grad_scores):
 ot_pair_scores.register_autograd(_ot_pair_grad, setup_context=_ot_pair_setup)
 
 
+# ---- the differentiable joint soft-max alignment score ----------------------------------------------------------------------
+# The forward is the existing PAIRED scoring call: the same bits as jointsm_scores(..., paired=True).  Its autograd formula is
+# jointsm_pair_backward (aspire_jointsm_backward_f32), which forms the dot products again -- nothing but the inputs is saved.
+@torch.library.custom_op('aspire::jointsm_pair_scores', mutates_args=(), device_types='cuda')
+def jointsm_pair_scores(q: Tensor, q_lens: Tensor, c: Tensor, c_lens: Tensor) -> Tensor:
+    return ops.jointsm_scores(_padded_repset(q, q_lens), _padded_repset(c, c_lens), pairing=_lib.PAIR_PAIRED)
+
+
+@jointsm_pair_scores.register_fake
+def _(q, q_lens, c, c_lens):
+    return q.new_empty(_npairs(q.shape[0], c.shape[0], True))
+
+
+@torch.library.custom_op('aspire::jointsm_pair_backward', mutates_args=(), device_types='cuda')
+def jointsm_pair_backward(grad_scores: Tensor, q: Tensor, q_lens: Tensor, c: Tensor, c_lens: Tensor) -> Tuple[Tensor, Tensor]:
+    qs, cs = _padded_repset(q, q_lens), _padded_repset(c, c_lens)
+    gq, gc = ops.jointsm_backward(qs, cs, grad_scores.to(torch.float32).contiguous(),
+                                  out=(torch.empty_like(qs.rows), torch.empty_like(cs.rows)))     # padded: every row has its writer
+    return gq.view(q.shape), gc.view(c.shape)
+
+
+@jointsm_pair_backward.register_fake
+def _(grad_scores, q, q_lens, c, c_lens):
+    return q.new_empty(q.shape), c.new_empty(c.shape)
+
+
+def _jointsm_pair_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs)
+
+
+def _jointsm_pair_grad(ctx, grad_scores):
+    gq, gc = torch.ops.aspire.jointsm_pair_backward(grad_scores, *ctx.saved_tensors)
+    return gq, None, gc, None
+
+
+jointsm_pair_scores.register_autograd(_jointsm_pair_grad, setup_context=_jointsm_pair_setup)
+
+
+# ---- the differentiable supervised-alignment distance -------------------------------------------------------------------------
+# align int32 [B, 2]: (query row, candidate row) of each pair's pre-aligned sentences, clipped on the device to the documents' last
+# rows; weighted: the similarity divided by q_len * c_len.  scores = the SIMILARITY -||q_i - c_j|| (aspire_l2sup_scores_f32); the
+# autograd formula is l2sup_pair_backward (aspire_l2sup_backward_f32); only the inputs are saved.
+@torch.library.custom_op('aspire::l2sup_pair_scores', mutates_args=(), device_types='cuda')
+def l2sup_pair_scores(q: Tensor, q_lens: Tensor, c: Tensor, c_lens: Tensor, align: Tensor, weighted: bool) -> Tensor:
+    return ops.l2sup_scores(_padded_repset(q, q_lens), _padded_repset(c, c_lens), align.to(torch.int32).contiguous(), weighted)
+
+
+@l2sup_pair_scores.register_fake
+def _(q, q_lens, c, c_lens, align, weighted):
+    return q.new_empty(_npairs(q.shape[0], c.shape[0], True))
+
+
+@torch.library.custom_op('aspire::l2sup_pair_backward', mutates_args=(), device_types='cuda')
+def l2sup_pair_backward(grad_scores: Tensor, q: Tensor, q_lens: Tensor, c: Tensor, c_lens: Tensor, align: Tensor,
+                        weighted: bool) -> Tuple[Tensor, Tensor]:
+    qs, cs = _padded_repset(q, q_lens), _padded_repset(c, c_lens)
+    gq, gc = ops.l2sup_backward(qs, cs, align.to(torch.int32).contiguous(), grad_scores.to(torch.float32).contiguous(), weighted,
+                                out=(torch.empty_like(qs.rows), torch.empty_like(cs.rows)))     # padded: every row has its writer
+    return gq.view(q.shape), gc.view(c.shape)
+
+
+@l2sup_pair_backward.register_fake
+def _(grad_scores, q, q_lens, c, c_lens, align, weighted):
+    return q.new_empty(q.shape), c.new_empty(c.shape)
+
+
+def _l2sup_pair_setup(ctx, inputs, output):
+    q, q_lens, c, c_lens, align, weighted = inputs
+    ctx.save_for_backward(q, q_lens, c, c_lens, align)
+    ctx.weighted = weighted
+
+
+def _l2sup_pair_grad(ctx, grad_scores):
+    gq, gc = torch.ops.aspire.l2sup_pair_backward(grad_scores, *ctx.saved_tensors, ctx.weighted)
+    return gq, None, gc, None, None, None
+
+
+l2sup_pair_scores.register_autograd(_l2sup_pair_grad, setup_context=_l2sup_pair_setup)
+
+
 OPS = ('span_mean_pool', 'span_pool_ranges', 'bert_encoder_forward', 'bert_cls_forward', 'bert_pooler', 'token_mean_pool', 'l2max_scores', 'jointsm_scores', 'ot_sinkhorn_scores', 'topk_desc', 'topk_keys', 'topk_merge',
        'l2max_scores_csr', 'ot_scores_csr', 'ot_rank_batch', 'dense_rank_batch', 'l2agg_pair_scores', 'l2agg_pair_backward',
-       'ot_pair_scores', 'ot_pair_backward')
+       'ot_pair_scores', 'ot_pair_backward', 'jointsm_pair_scores', 'jointsm_pair_backward', 'l2sup_pair_scores', 'l2sup_pair_backward')

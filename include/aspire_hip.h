@@ -663,6 +663,56 @@ int aspire_jointsm_rank_batch_f32(const aspire_repset* q, const aspire_repset* c
                                   size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Backward of A14: what the reference's autograd computes for allpair_joint_sm_negscore (pair_distances.py:348-402) under
+ * WordSentAlignPolyEnc's triplet loss (disent_models.py:868-875) -- through torch.bmm, masked_2d_softmax (activations.py:35-61)
+ * and the two alignment loops down to the sentence rows.  Per PAIRED pair, over the valid block i < q_len, j < c_len:
+ *   d_ij = <q_i, c_j>;  p = the soft-max of d_ij / sqrtf(768) over the whole block jointly;  S = 2 sum_ij p_ij d_ij (the similarity
+ *   of aspire_jointsm_scores_f32);  g = dLoss / dS (a loss on the reference's distance -S passes minus its gradient).
+ *     E        = sum_ij p_ij d_ij
+ *     W_ij     = dS / dd_ij = 2 p_ij (1 + (d_ij - E) / sqrtf(768))
+ *     grad_q_i = g sum_j W_ij c_j        grad_c_j = g sum_i W_ij q_i
+ *   formed shifted by the block's maximum m (rows of norm 28 give d of about 1000: d - E must not cancel against a large E):
+ *     e_ij = exp((d_ij - m) / sqrtf(768)),  Z = sum e,  T = sum e (d_ij - m),  E - m = T / Z
+ *     W_ij = 2 (e_ij / Z) (1 + ((d_ij - m) - T / Z) / sqrtf(768))
+ *   pairing      ASPIRE_PAIR_PAIRED only (ASPIRE_PAIR_CROSS -> ASPIRE_ERR_UNSUPPORTED: an accumulation across pairs that is not built).
+ *   grad_scores  [P] in;  grad_q_rows, grad_c_rows  out, laid out like q->rows / c->rows (padded and CSR sets alike): every row of
+ *                every document is written once -- valid rows with the gradient, pad rows (len <= r < ext) with exact zeros; rows
+ *                of the matrices that belong to no document are not touched; pad rows of the inputs are never read; g == 0 gives
+ *                exact zeros.  q->rows, c->rows and both gradient buffers must be 16-byte aligned.
+ * The dot products are recomputed (direct fp32 FMA sums, one per entry); nothing is kept by the forward.  No atomics: the same bits
+ * on every run.  A NULL pointer, a bad pairing, q->n != c->n -> ASPIRE_ERR_INVALID_ARG; D != 768, or documents of more than
+ * aspire_max_sents() rows -> ASPIRE_ERR_UNSUPPORTED; no pairs -> ASPIRE_OK without a launch.  A document longer than its set's
+ * host-known bound gets NaN rows up to the bound.  One launch on `stream`, no workspace.
+ * ------------------------------------------------------------------------------------------- */
+int aspire_jointsm_backward_f32(const aspire_repset* q, const aspire_repset* c, int64_t D, int pairing,
+                                const float* grad_scores /* [P] */,
+                                float* grad_q_rows, float* grad_c_rows /* laid out like q->rows / c->rows */,
+                                void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The supervised-alignment distances, forward and backward.  Replaces allpair_masked_dist_l2sup and
+ * allpair_masked_dist_l2sup_weighted (pair_distances.py:189-292), the criterion_sentsup of WordSentAbsSupAlignBiEnc
+ * (disent_models.py:704-710, :818).  PAIRED only (pair p = query p with candidate p, q->n == c->n): there is no pairing argument.
+ *   align        DEVICE int32 [P, 2]: (query row, candidate row) of the pre-aligned sentence pair.  An index above len - 1 is
+ *                clipped to len - 1 (:214-215).  A negative index is the caller's error (the host layer raises ValueError): it reads
+ *                nothing and gives NaN for that pair's score and for its valid gradient rows.
+ *   weighted     0: similarity = -||q_i - c_j||;  non-zero: that divided by (float)(q_len * c_len)  (:264, :290)
+ *   scores       [P] out: the SIMILARITY (the reference returns its negation), the distance from the direct difference.
+ *   backward     torch.cdist's rule: grad_q_i = -g (q_i - c_j) / d, grad_c_j = +g (q_i - c_j) / d, both 0 where d == 0; every
+ *                other row of the two documents gets exact zeros, pad rows (len <= r < ext) included; rows that belong to no
+ *                document are not touched.  grad_scores, grad_q_rows, grad_c_rows and the alignment of the buffers as above.
+ * A NULL pointer, q->n != c->n -> ASPIRE_ERR_INVALID_ARG; D != 768, or documents of more than aspire_max_sents() rows ->
+ * ASPIRE_ERR_UNSUPPORTED; no pairs -> ASPIRE_OK without a launch; a document longer than its set's host-known bound: NaN score,
+ * NaN rows up to the bound.  One launch on `stream` each, no workspace, no atomics.
+ * ------------------------------------------------------------------------------------------- */
+int aspire_l2sup_scores_f32(const aspire_repset* q, const aspire_repset* c, int64_t D,
+                            const int32_t* align /* [P, 2] device: query row, candidate row */, int weighted,
+                            float* scores /* [P] similarity */, void* stream);
+int aspire_l2sup_backward_f32(const aspire_repset* q, const aspire_repset* c, int64_t D,
+                              const int32_t* align, int weighted, const float* grad_scores,
+                              float* grad_q_rows, float* grad_c_rows, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * A15  precomputed-embedding rankers.  Replaces the per-query body of src/pre_process/pp_gen_nearest.py rank_pool (:683-717) and
  * rank_pool_faceted (:1166-1191): `all_doc_reps[pool_idxs, :]`, sklearn.neighbors.NearestNeighbors(algorithm='brute').fit on it and
  * kneighbors of the query row -- for J (query, pool) jobs in ONE call over ONE resident [N, 768] matrix of whole-document reps.
