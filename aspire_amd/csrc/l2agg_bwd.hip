@@ -12,9 +12,7 @@
 //   through cdist, A_ij = W_ij / d_ij and A_ij = 0 where d_ij == 0 (torch's cdist backward for coincident rows: no NaN):
 //     grad_q_i = -g sum_j A_ij (q_i - c_j)        grad_c_j = +g sum_i A_ij (q_i - c_j)
 //
-// One workgroup of four waves per pair (ASPIRE_PAIR_PAIRED: every document belongs to one pair, so a gradient row has one writer --
-// no atomics, nothing summed across workgroups, the same bits on every run).  A lane owns 12 of the 768 coordinates (three 16-byte
-// pieces, 1 KiB per wave-instruction), a wave the rows r = wave, wave + 4, ...
+// The frame -- one workgroup of four waves per pair, a lane's 12 coordinates, poisoned, empty and pad rows -- is pair_bwd.h's.
 //   1  distances: d_ij = sqrt(sum_k (q_ik - c_jk)^2) from the DIRECT differences into LDS (row-major over the valid block), one
 //      wave_sum per entry.  Nothing comes from the forward: for documents over 25 rows the forward may have used torch.cdist's
 //      matmul formula (score_types.h: use_mm_formula), whose distances differ from these by rounding -- the backward's pick can
@@ -25,67 +23,20 @@
 //      with A_ij in LDS (soft-max shifted by the block's maximum and centred as l2agg_pair.hip does: score - m = T / S).
 //   3  rows: every row the pair owns is written once, by the lanes that own its coordinates, with 16-byte vector stores: the
 //      differences q_i - c_j formed directly and weighted (NOT rowsum(A) q_i - sum_j A_ij c_j: that cancels when a query sentence
-//      nearly equals a candidate sentence, which is where training drives them).  MAX / TOP2 touch their one or two entries;
-//      pad rows of padded sets (len <= r < ext) get exact zeros.
-// A document longer than its set's host-known bound has its rows (up to the bound) set to NaN, as the forward poisons its score.
-#include <math.h>
-
-#include "common.h"
-#include "score_types.h"
+//      nearly equals a candidate sentence, which is where training drives them).  MAX / TOP2 touch their one or two entries.
+#include "pair_bwd.h"
 
 namespace aspire {
 namespace {
 
-constexpr int kBwdThreads = 256, kBwdWaves = kBwdThreads / 64;
-constexpr int kKeyFloats = 2 * kBwdThreads;       // the reduction scratch in front of the distance block: 256 x 8 bytes
+constexpr int kKeyFloats = 2 * kPairBwdThreads;       // the reduction scratch in front of the distance block: 256 x 8 bytes
 
-typedef float v4 __attribute__((ext_vector_type(4)));
-struct Row {          // a lane's 12 coordinates of one row: 4 lane + 256 k + (0 .. 3)
-    v4 x, y, z;
-};
-__device__ __forceinline__ Row load_row(const float* row, int lane) {
-    const v4* p = reinterpret_cast<const v4*>(row) + lane;
-    return Row{p[0], p[64], p[128]};
-}
-__device__ __forceinline__ void store_row(float* row, int lane, const Row& r) {
-    v4* p = reinterpret_cast<v4*>(row) + lane;
-    p[0] = r.x;
-    p[64] = r.y;
-    p[128] = r.z;
-}
-__device__ __forceinline__ Row splat(float v) { return Row{v4{v, v, v, v}, v4{v, v, v, v}, v4{v, v, v, v}}; }
-// acc += w (a - b)
-__device__ __forceinline__ void add_diff(Row& acc, float w, const Row& a, const Row& b) {
-    const v4 ww = {w, w, w, w};
-    acc.x = __builtin_elementwise_fma(ww, a.x - b.x, acc.x);
-    acc.y = __builtin_elementwise_fma(ww, a.y - b.y, acc.y);
-    acc.z = __builtin_elementwise_fma(ww, a.z - b.z, acc.z);
-}
-__device__ __forceinline__ Row scaled(float f, const Row& r) { return Row{f * r.x, f * r.y, f * r.z}; }
-
-// the four waves' sums / maxima in one fixed order (every thread calls; `red` = 4 floats)
-__device__ __forceinline__ float block_sum4(float v, float* red) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const float r = (red[0] + red[1]) + (red[2] + red[3]);
-    __syncthreads();
-    return r;
-}
-__device__ __forceinline__ float block_max4(float v, float* red) {
-    v = wave_max(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const float r = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    __syncthreads();
-    return r;
-}
 // minimum of the 256 threads' keys
 __device__ __forceinline__ uint64_t block_min_key(uint64_t k, uint64_t* keys) {
     const int tid = threadIdx.x;
     keys[tid] = k;
     __syncthreads();
-    for (int s = kBwdThreads / 2; s > 0; s >>= 1) {
+    for (int s = kPairBwdThreads / 2; s > 0; s >>= 1) {
         if (tid < s && keys[tid + s] < keys[tid]) keys[tid] = keys[tid + s];
         __syncthreads();
     }
@@ -105,41 +56,22 @@ struct L2BwdArgs {
     float* grad_c;
 };
 
-__global__ void __launch_bounds__(kBwdThreads) l2agg_bwd_kernel(L2BwdArgs a, int rows_q, int rows_c) {
+__global__ void __launch_bounds__(kPairBwdThreads) l2agg_bwd_kernel(L2BwdArgs a, int rows_q, int rows_c) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     uint64_t* keys = reinterpret_cast<uint64_t*>(lds);
     float* red = lds;                       // (the same scratch: a reduction finishes before the next one starts)
     float* dist = lds + kKeyFloats;         // [ql][cl]: d_ij, then (ATTENTION) A_ij
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t p = blockIdx.x;
-    const int q_len = a.q.len[p], c_len = a.c.len[p];
-    const bool poison = q_len > rows_q || c_len > rows_c;              // longer than the host-known bound
-    const int ql = q_len < 0 ? 0 : (q_len > rows_q ? rows_q : q_len), cl = c_len < 0 ? 0 : (c_len > rows_c ? rows_c : c_len);
-    const int q_own = a.q.ext > 0 ? a.q.ext : ql, c_own = a.c.ext > 0 ? a.c.ext : cl;        // rows this pair writes (pad rows included)
-    const float* qdoc = a.q.rows + (size_t)a.q.start[p] * kD;
-    const float* cdoc = a.c.rows + (size_t)a.c.start[p] * kD;
-    float* gq = a.grad_q + (size_t)a.q.start[p] * kD;
-    float* gc = a.grad_c + (size_t)a.c.start[p] * kD;
-    const int n = ql * cl;
-    if (poison || n == 0) {             // (workgroup-uniform)
-        const float v = poison ? __builtin_nanf("") : 0.f;
-        for (int r = wave; r < q_own; r += kBwdWaves) store_row(gq + (size_t)r * kD, lane, splat(r < ql ? v : 0.f));
-        for (int r = wave; r < c_own; r += kBwdWaves) store_row(gc + (size_t)r * kD, lane, splat(r < cl ? v : 0.f));
-        return;
-    }
+    const PairFrame f = pair_frame(a.q, a.c, a.grad_q, a.grad_c, p, rows_q, rows_c);
+    if (skip_pair(f, lane, wave)) return;
+    const int ql = f.ql, cl = f.cl, n = ql * cl;
+    const float *qdoc = f.qdoc, *cdoc = f.cdoc;
+    float *gq = f.gq, *gc = f.gc;
     const float g = a.grad_scores[p];
 
     // ---- 1  distances from direct differences ---------------------------------------------------------------------------------
-    for (int i = wave; i < ql; i += kBwdWaves) {
-        const Row x = load_row(qdoc + (size_t)i * kD, lane);
-        for (int j = 0; j < cl; ++j) {
-            const Row y = load_row(cdoc + (size_t)j * kD, lane);
-            const v4 e0 = x.x - y.x, e1 = x.y - y.y, e2 = x.z - y.z;
-            const v4 sq = __builtin_elementwise_fma(e2, e2, __builtin_elementwise_fma(e1, e1, e0 * e0));
-            const float d2 = wave_sum((sq.x + sq.y) + (sq.z + sq.w));
-            if (lane == 0) dist[i * cl + j] = sqrtf(d2);
-        }
-    }
+    direct_distances(f, dist, cl, lane, wave);
     __syncthreads();
 
     // ---- 2  weights -----------------------------------------------------------------------------------------------------------
@@ -148,10 +80,10 @@ __global__ void __launch_bounds__(kBwdThreads) l2agg_bwd_kernel(L2BwdArgs a, int
     if (a.agg == ASPIRE_AGG_ATTENTION) {
         const float temp = a.temp;
         float m = -INFINITY;
-        for (int e = tid; e < n; e += kBwdThreads) m = fmaxf(m, -dist[e]);
+        for (int e = tid; e < n; e += kPairBwdThreads) m = fmaxf(m, -dist[e]);
         m = block_max4(m, red);
         float S = 0.f, T = 0.f;
-        for (int e = tid; e < n; e += kBwdThreads) {
+        for (int e = tid; e < n; e += kPairBwdThreads) {
             const float y = -dist[e] - m, w = expf(y / temp);
             S += w;
             T = fmaf(w, y, T);
@@ -159,7 +91,7 @@ __global__ void __launch_bounds__(kBwdThreads) l2agg_bwd_kernel(L2BwdArgs a, int
         S = block_sum4(S, red);
         T = block_sum4(T, red);
         const float centre = T / S;          // score - m
-        for (int e = tid; e < n; e += kBwdThreads) {
+        for (int e = tid; e < n; e += kPairBwdThreads) {
             const float d = dist[e], y = -d - m;
             const float w = (expf(y / temp) / S) * (1.0f + (y - centre) / temp);
             dist[e] = d > 0.f ? w / d : 0.f;
@@ -167,7 +99,7 @@ __global__ void __launch_bounds__(kBwdThreads) l2agg_bwd_kernel(L2BwdArgs a, int
         __syncthreads();
     } else {
         uint64_t k = kNoKey;
-        for (int e = tid; e < n; e += kBwdThreads) {
+        for (int e = tid; e < n; e += kPairBwdThreads) {
             const uint64_t ke = key_of(dist[e], e);
             k = ke < k ? ke : k;
         }
@@ -175,7 +107,7 @@ __global__ void __launch_bounds__(kBwdThreads) l2agg_bwd_kernel(L2BwdArgs a, int
         uint64_t k2 = kNoKey;
         if (a.agg == ASPIRE_AGG_TOP2 && n > 1) {
             k = kNoKey;
-            for (int e = tid; e < n; e += kBwdThreads) {
+            for (int e = tid; e < n; e += kPairBwdThreads) {
                 const uint64_t ke = key_of(dist[e], e);
                 k = (ke != k1 && ke < k) ? ke : k;
             }
@@ -194,14 +126,14 @@ __global__ void __launch_bounds__(kBwdThreads) l2agg_bwd_kernel(L2BwdArgs a, int
     // ---- 3  gradient rows -----------------------------------------------------------------------------------------------------
     const Row zero = splat(0.f);
     if (a.agg == ASPIRE_AGG_ATTENTION) {
-        for (int i = wave; i < ql; i += kBwdWaves) {
+        for (int i = wave; i < ql; i += kPairBwdWaves) {
             const Row x = load_row(qdoc + (size_t)i * kD, lane);
             Row acc = zero;
 #pragma unroll 2
             for (int j = 0; j < cl; ++j) add_diff(acc, dist[i * cl + j], x, load_row(cdoc + (size_t)j * kD, lane));
             store_row(gq + (size_t)i * kD, lane, scaled(-g, acc));
         }
-        for (int j = wave; j < cl; j += kBwdWaves) {
+        for (int j = wave; j < cl; j += kPairBwdWaves) {
             const Row y = load_row(cdoc + (size_t)j * kD, lane);
             Row acc = zero;
 #pragma unroll 2
@@ -215,7 +147,7 @@ __global__ void __launch_bounds__(kBwdThreads) l2agg_bwd_kernel(L2BwdArgs a, int
             pi[t] = pick_e[t] < 0 ? -1 : pick_e[t] / cl;
             pj[t] = pick_e[t] < 0 ? -1 : pick_e[t] - pi[t] * cl;
         }
-        for (int i = wave; i < ql; i += kBwdWaves) {
+        for (int i = wave; i < ql; i += kPairBwdWaves) {
             Row acc = zero;
             if (i == pi[0] || i == pi[1]) {         // (wave-uniform)
                 const Row x = load_row(qdoc + (size_t)i * kD, lane);
@@ -226,7 +158,7 @@ __global__ void __launch_bounds__(kBwdThreads) l2agg_bwd_kernel(L2BwdArgs a, int
             }
             store_row(gq + (size_t)i * kD, lane, acc);
         }
-        for (int j = wave; j < cl; j += kBwdWaves) {
+        for (int j = wave; j < cl; j += kPairBwdWaves) {
             Row acc = zero;
             if (j == pj[0] || j == pj[1]) {
                 const Row y = load_row(cdoc + (size_t)j * kD, lane);
@@ -238,8 +170,7 @@ __global__ void __launch_bounds__(kBwdThreads) l2agg_bwd_kernel(L2BwdArgs a, int
             store_row(gc + (size_t)j * kD, lane, acc);
         }
     }
-    for (int r = ql + wave; r < q_own; r += kBwdWaves) store_row(gq + (size_t)r * kD, lane, zero);
-    for (int r = cl + wave; r < c_own; r += kBwdWaves) store_row(gc + (size_t)r * kD, lane, zero);
+    zero_pad_rows(f, lane, wave);
 }
 
 }  // namespace
@@ -248,20 +179,9 @@ __global__ void __launch_bounds__(kBwdThreads) l2agg_bwd_kernel(L2BwdArgs a, int
 // (<= generic_max_rows()).  grad_q / grad_c are laid out like q.rows / c.rows.
 int launch_l2agg_backward(const RepSet& q, const RepSet& c, int agg, float temp, const float* grad_scores, float* grad_q, float* grad_c,
                           int rows_q, int rows_c, hipStream_t stream) {
-    ASPIRE_REQUIRE(rows_q <= generic_max_rows() && rows_c <= generic_max_rows(), ASPIRE_ERR_UNSUPPORTED,
-                   "documents with more than %d sentence rows are not supported (got %d x %d)", generic_max_rows(), rows_q, rows_c);
-    const int64_t P = c.n;
-    if (P == 0) return ASPIRE_OK;
-    ASPIRE_REQUIRE(P < ((int64_t)1 << 31), ASPIRE_ERR_UNSUPPORTED, "too many pairs: %lld", (long long)P);
-    const size_t lds_bytes = (size_t)(kKeyFloats + rows_q * rows_c) * sizeof(float);
-    if (lds_bytes > 64 * 1024) {      // more than the default dynamic LDS limit: raise it (per function, sticky, harmless to repeat)
-        ASPIRE_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(l2agg_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          80 * 1024));
-    }
-    L2BwdArgs a{q, c, agg, temp, grad_scores, grad_q, grad_c};
-    hipLaunchKernelGGL(l2agg_bwd_kernel, dim3((unsigned)P), dim3(kBwdThreads), lds_bytes, stream, a, rows_q, rows_c);
-    ASPIRE_LAUNCH_OK();
-    return ASPIRE_OK;
+    const size_t lds_bytes = (kKeyFloats + (size_t)rows_q * rows_c) * sizeof(float);
+    return launch_pair_bwd(l2agg_bwd_kernel, L2BwdArgs{q, c, agg, temp, grad_scores, grad_q, grad_c}, c.n, lds_bytes, 80 * 1024, rows_q, rows_c,
+                           stream);
 }
 
 }  // namespace aspire

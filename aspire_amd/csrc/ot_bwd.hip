@@ -21,9 +21,7 @@
 // x receives the transport term through f only and y through g only (the detach pattern); both receive the marginal term.  For
 // ASPIRE_OT_SIMILARITY the sign flips.
 //
-// One workgroup of four waves per pair (ASPIRE_PAIR_PAIRED: every document belongs to one pair, so a gradient row has one writer --
-// no atomics, nothing summed across workgroups, the same bits on every run), l2agg_bwd.hip's frame: a lane owns 12 of the 768
-// coordinates, a wave the rows r = wave, wave + 4, ...
+// The frame -- one workgroup of four waves per pair, a lane's 12 coordinates, poisoned, empty and pad rows -- is pair_bwd.h's.
 //   1  distances: d_ij from the DIRECT differences into one LDS block over the valid entries (row stride cl | 1: odd, so that a
 //      thread per row and a thread per column both read it without bank conflicts).  C = max(d, 1e-4) and s = -d both come from it --
 //      direct differences everywhere, not the matmul expansion of generic.hip: the gradient is taken where training drives rows
@@ -39,49 +37,20 @@
 //      these formulas on the test's 8 x 8 pairs is 1.3e-7 from float64 with the shift and 6.5e-7 without.
 //   3  rows: W_ij / V_ij are wave-uniform scalars recomputed from the vectors in LDS while a row's partners stream past (one expf
 //      per entry beside a 3 KB row load), M stays two index vectors and two value vectors; w (x_i - y_j) is formed directly (NOT
-//      rowsum x_i - sum_j w y_j: that cancels between near-equal rows); every row is written once with 16-byte stores, pad rows of
-//      padded sets (len <= r < ext) get exact zeros.
-// A document longer than its set's host-known bound has its rows (up to the bound) set to NaN, as the forward poisons its score.
-#include <math.h>
-
-#include "common.h"
-#include "score_types.h"
+//      rowsum x_i - sum_j w y_j: that cancels between near-equal rows); every row is written once with 16-byte stores.
+#include "pair_bwd.h"
 
 namespace aspire {
 namespace {
 
-constexpr int kOtBwdThreads = 256, kOtBwdWaves = kOtBwdThreads / 64, kOtBwdSide = kOtBwdThreads / 2;      // rows | columns
-
-typedef float v4 __attribute__((ext_vector_type(4)));
-struct Row {          // a lane's 12 coordinates of one row: 4 lane + 256 k + (0 .. 3)
-    v4 x, y, z;
-};
-__device__ __forceinline__ Row load_row(const float* row, int lane) {
-    const v4* p = reinterpret_cast<const v4*>(row) + lane;
-    return Row{p[0], p[64], p[128]};
-}
-__device__ __forceinline__ void store_row(float* row, int lane, const Row& r) {
-    v4* p = reinterpret_cast<v4*>(row) + lane;
-    p[0] = r.x;
-    p[64] = r.y;
-    p[128] = r.z;
-}
-__device__ __forceinline__ Row splat(float v) { return Row{v4{v, v, v, v}, v4{v, v, v, v}, v4{v, v, v, v}}; }
-// acc += w (a - b)
-__device__ __forceinline__ void add_diff(Row& acc, float w, const Row& a, const Row& b) {
-    const v4 ww = {w, w, w, w};
-    acc.x = __builtin_elementwise_fma(ww, a.x - b.x, acc.x);
-    acc.y = __builtin_elementwise_fma(ww, a.y - b.y, acc.y);
-    acc.z = __builtin_elementwise_fma(ww, a.z - b.z, acc.z);
-}
-__device__ __forceinline__ Row scaled(float f, const Row& r) { return Row{f * r.x, f * r.y, f * r.z}; }
+constexpr int kOtBwdSide = kPairBwdThreads / 2;      // rows | columns
 
 // the 256 threads' sum in one fixed order (every thread calls; `red` = 256 floats): generic.hip's block_reduce
 __device__ __forceinline__ float block_sum(float v, float* red) {
     const int tid = threadIdx.x;
     red[tid] = v;
     __syncthreads();
-    for (int s = kOtBwdThreads / 2; s > 0; s >>= 1) {
+    for (int s = kPairBwdThreads / 2; s > 0; s >>= 1) {
         if (tid < s) red[tid] = red[tid] + red[tid + s];
         __syncthreads();
     }
@@ -94,7 +63,7 @@ __device__ __forceinline__ float block_min(float v, float* red) {
     const int tid = threadIdx.x;
     red[tid] = v;
     __syncthreads();
-    for (int s = kOtBwdThreads / 2; s > 0; s >>= 1) {
+    for (int s = kPairBwdThreads / 2; s > 0; s >>= 1) {
         if (tid < s) red[tid] = fminf(red[tid], red[tid + s]);
         __syncthreads();
     }
@@ -111,7 +80,7 @@ __host__ __device__ inline OtBwdLds ot_bwd_layout(int rows_q, int rows_c) {
     OtBwdLds L;
     const int m = ((rows_q > rows_c ? rows_q : rows_c) + 3) & ~3;
     int o = 0;
-    L.red = o; o += kOtBwdThreads;
+    L.red = o; o += kPairBwdThreads;
     L.f = o; o += m;
     L.g = o; o += m;
     L.ft = o; o += m;
@@ -141,24 +110,15 @@ struct OtBwdArgs {
     float* grad_c;
 };
 
-__global__ void __launch_bounds__(kOtBwdThreads) ot_bwd_kernel(OtBwdArgs a, int rows_q, int rows_c) {
+__global__ void __launch_bounds__(kPairBwdThreads) ot_bwd_kernel(OtBwdArgs a, int rows_q, int rows_c) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t p = blockIdx.x;
-    const int q_len = a.q.len[p], c_len = a.c.len[p];
-    const bool poison = q_len > rows_q || c_len > rows_c;              // longer than the host-known bound
-    const int ql = q_len < 0 ? 0 : (q_len > rows_q ? rows_q : q_len), cl = c_len < 0 ? 0 : (c_len > rows_c ? rows_c : c_len);
-    const int q_own = a.q.ext > 0 ? a.q.ext : ql, c_own = a.c.ext > 0 ? a.c.ext : cl;        // rows this pair writes (pad rows included)
-    const float* qdoc = a.q.rows + (size_t)a.q.start[p] * kD;
-    const float* cdoc = a.c.rows + (size_t)a.c.start[p] * kD;
-    float* gq = a.grad_q + (size_t)a.q.start[p] * kD;
-    float* gc = a.grad_c + (size_t)a.c.start[p] * kD;
-    if (poison || ql * cl == 0) {             // (workgroup-uniform)
-        const float v = poison ? __builtin_nanf("") : 0.f;
-        for (int r = wave; r < q_own; r += kOtBwdWaves) store_row(gq + (size_t)r * kD, lane, splat(r < ql ? v : 0.f));
-        for (int r = wave; r < c_own; r += kOtBwdWaves) store_row(gc + (size_t)r * kD, lane, splat(r < cl ? v : 0.f));
-        return;
-    }
+    const PairFrame fr = pair_frame(a.q, a.c, a.grad_q, a.grad_c, p, rows_q, rows_c);
+    if (skip_pair(fr, lane, wave)) return;
+    const int ql = fr.ql, cl = fr.cl;
+    const float *qdoc = fr.qdoc, *cdoc = fr.cdoc;
+    float *gq = fr.gq, *gc = fr.gc;
     const OtBwdLds L = ot_bwd_layout(rows_q, rows_c);
     const int ld = ot_bwd_stride(cl);          // (the pair's own stride: ql * ld <= rows_q * (rows_c | 1))
     float* red = lds + L.red;
@@ -178,16 +138,7 @@ __global__ void __launch_bounds__(kOtBwdThreads) ot_bwd_kernel(OtBwdArgs a, int 
     const float gs = a.want == ASPIRE_OT_SIMILARITY ? -a.grad_scores[p] : a.grad_scores[p];
 
     // ---- 1  distances from direct differences ---------------------------------------------------------------------------------
-    for (int i = wave; i < ql; i += kOtBwdWaves) {
-        const Row x = load_row(qdoc + (size_t)i * kD, lane);
-        for (int j = 0; j < cl; ++j) {
-            const Row y = load_row(cdoc + (size_t)j * kD, lane);
-            const v4 e0 = x.x - y.x, e1 = x.y - y.y, e2 = x.z - y.z;
-            const v4 sq = __builtin_elementwise_fma(e2, e2, __builtin_elementwise_fma(e1, e1, e0 * e0));
-            const float d2 = wave_sum((sq.x + sq.y) + (sq.z + sq.w));
-            if (lane == 0) dist[i * ld + j] = sqrtf(d2);
-        }
-    }
+    direct_distances(fr, dist, ld, lane, wave);
     // ---- diameter: the caller's (one per group) or the bounding box of the pair's own valid rows ------------------------------
     float diam;
     if (a.diameter != nullptr) {
@@ -195,7 +146,7 @@ __global__ void __launch_bounds__(kOtBwdThreads) ot_bwd_kernel(OtBwdArgs a, int 
         __syncthreads();
     } else {
         float acc = 0.f;
-        for (int d = tid; d < kD; d += kOtBwdThreads) {
+        for (int d = tid; d < kD; d += kPairBwdThreads) {
             float mn = INFINITY, mx = -INFINITY;
             for (int r = 0; r < ql; ++r) { const float w = qdoc[(size_t)r * kD + d]; mn = fminf(mn, w); mx = fmaxf(mx, w); }
             for (int r = 0; r < cl; ++r) { const float w = cdoc[(size_t)r * kD + d]; mn = fminf(mn, w); mx = fmaxf(mx, w); }
@@ -206,7 +157,7 @@ __global__ void __launch_bounds__(kOtBwdThreads) ot_bwd_kernel(OtBwdArgs a, int 
     diam = fmaxf(diam, kMinDiameter);
     // c0: the smallest cost of the block (the solve runs on C - c0, see the header)
     float c0 = INFINITY;
-    for (int e = tid; e < ql * cl; e += kOtBwdThreads) c0 = fminf(c0, fmaxf(dist[(e / cl) * ld + e % cl], 1e-4f));
+    for (int e = tid; e < ql * cl; e += kPairBwdThreads) c0 = fminf(c0, fmaxf(dist[(e / cl) * ld + e % cl], 1e-4f));
     c0 = block_min(c0, red);
 
     // ---- 2  the solve -----------------------------------------------------------------------------------------------------------
@@ -308,7 +259,7 @@ __global__ void __launch_bounds__(kOtBwdThreads) ot_bwd_kernel(OtBwdArgs a, int 
 
     // ---- 3  gradient rows -----------------------------------------------------------------------------------------------------
     const Row zero = splat(0.f);
-    for (int i = wave; i < ql; i += kOtBwdWaves) {
+    for (int i = wave; i < ql; i += kPairBwdWaves) {
         const Row x = load_row(qdoc + (size_t)i * kD, lane);
         const float a_i = wa[i], f_i = ft[i], u_i = u[i];
         const int js = jstar[i];
@@ -323,7 +274,7 @@ __global__ void __launch_bounds__(kOtBwdThreads) ot_bwd_kernel(OtBwdArgs a, int 
         }
         store_row(gq + (size_t)i * kD, lane, scaled(gs, acc));
     }
-    for (int j = wave; j < cl; j += kOtBwdWaves) {
+    for (int j = wave; j < cl; j += kPairBwdWaves) {
         const Row y = load_row(cdoc + (size_t)j * kD, lane);
         const float b_j = wb[j], g_j = gt[j], v_j = v[j];
         const int is = istar[j];
@@ -338,8 +289,7 @@ __global__ void __launch_bounds__(kOtBwdThreads) ot_bwd_kernel(OtBwdArgs a, int 
         }
         store_row(gc + (size_t)j * kD, lane, scaled(gs, acc));
     }
-    for (int r = ql + wave; r < q_own; r += kOtBwdWaves) store_row(gq + (size_t)r * kD, lane, zero);
-    for (int r = cl + wave; r < c_own; r += kOtBwdWaves) store_row(gc + (size_t)r * kD, lane, zero);
+    zero_pad_rows(fr, lane, wave);
 }
 
 }  // namespace
@@ -348,22 +298,14 @@ __global__ void __launch_bounds__(kOtBwdThreads) ot_bwd_kernel(OtBwdArgs a, int 
 // (<= generic_max_rows()).  grad_q / grad_c are laid out like q.rows / c.rows.
 int launch_ot_backward(const RepSet& q, const RepSet& c, const aspire_ot_params* prm, const float* diameter, int64_t diam_group, int want,
                        const float* grad_scores, float* grad_q, float* grad_c, int rows_q, int rows_c, hipStream_t stream) {
-    ASPIRE_REQUIRE(rows_q <= generic_max_rows() && rows_c <= generic_max_rows(), ASPIRE_ERR_UNSUPPORTED,
-                   "documents with more than %d sentence rows are not supported (got %d x %d)", generic_max_rows(), rows_q, rows_c);
+    // the LDS layout below is int arithmetic on the rows, so they are checked before it is formed; launch_pair_bwd asks again,
+    // deliberately redundant (the other launchers form their sizes in size_t and leave the check to it)
+    if (int rc = check_row_bounds(rows_q, rows_c)) return rc;
     ASPIRE_REQUIRE(generic_max_rows() <= kOtBwdSide, ASPIRE_ERR_UNSUPPORTED, "the OT backward holds one row or column per thread of a half workgroup");
-    const int64_t P = c.n;
-    if (P == 0) return ASPIRE_OK;
-    ASPIRE_REQUIRE(P < ((int64_t)1 << 31), ASPIRE_ERR_UNSUPPORTED, "too many pairs: %lld", (long long)P);
     const size_t lds_bytes = (size_t)ot_bwd_layout(rows_q, rows_c).total * sizeof(float);
-    if (lds_bytes > 64 * 1024) {      // more than the default dynamic LDS limit: raise it (per function, sticky, harmless to repeat)
-        ASPIRE_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(ot_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          96 * 1024));
-    }
     OtBwdArgs a{q, c, (float)prm->blur, (float)prm->sent_sm_temp, log(prm->blur), log(prm->scaling), diameter, diameter ? diam_group : 1,
                 want, grad_scores, grad_q, grad_c};
-    hipLaunchKernelGGL(ot_bwd_kernel, dim3((unsigned)P), dim3(kOtBwdThreads), lds_bytes, stream, a, rows_q, rows_c);
-    ASPIRE_LAUNCH_OK();
-    return ASPIRE_OK;
+    return launch_pair_bwd(ot_bwd_kernel, a, c.n, lds_bytes, 96 * 1024, rows_q, rows_c, stream);
 }
 
 }  // namespace aspire

@@ -3,8 +3,8 @@
 // batch_prep.hip, gram.hip, gramp.hip, generic.hip, fused.hip, tile16.hip; the rank: topk.hip).  Reference call structure:
 //   src/learning/facetid_models/pair_distances.py:21-92, :138-186; src/evaluation/evaluate.py:58-76 (allenai/aspire).
 //
-// Top to bottom: argument checks and ScoreArgs fills (check_repsets, fill_set_args, fill_ot_args); the max-sim entry points and the
-// backward of their aggregations (aspire_l2agg_backward_f32: checks here, the kernel in l2agg_bwd.hip), the checks of
+// Top to bottom: argument checks and ScoreArgs fills (check_repsets, check_backward_sets, fill_set_args, fill_ot_args); the max-sim
+// entry points and the backward of their aggregations (aspire_l2agg_backward_f32: checks here, the kernel in l2agg_bwd.hip), the checks of
 // aspire_jointsm_backward_f32 (jointsm_bwd.hip) and of the supervised-alignment pair aspire_l2sup_scores_f32 / _backward_f32 (l2sup.hip); the
 // host helpers of the batched / CHUNK / REC forms -- form rules (chunk_size_ok, one_wave_form_ok, sinkhorn_form_honours_gate),
 // workspace layouts (batch_layout, l2_batch_layout, batch_tables), launch_fused_form; otAspire per call (ot_run_tiles, ot_run)
@@ -62,6 +62,18 @@ int max_rows_of(const aspire_repset* q, const aspire_repset* c) {
     const int mq = q->ext > 0 ? q->ext : q->max_len;
     const int mc = c->ext > 0 ? c->ext : c->max_len;
     return mq > mc ? mq : mc;
+}
+
+// What the backward entries (l2agg, jointsm, l2sup, ot) check first, alike: the sets, PAIRED only.  Yields the host-known bounds of
+// the documents' rows.  (An entry's own argument checks follow, then its null-pointer check once there is a pair to write for.)
+int check_backward_sets(const aspire_repset* q, const aspire_repset* c, int64_t D, int pairing, int& rows_q, int& rows_c) {
+    if (int rc = check_repsets(q, c, D, pairing)) return rc;
+    ASPIRE_REQUIRE(pairing == ASPIRE_PAIR_PAIRED, ASPIRE_ERR_UNSUPPORTED,
+                   "the backward is built for ASPIRE_PAIR_PAIRED: with ASPIRE_PAIR_CROSS a document's gradient is a sum over many pairs, "
+                   "which needs an accumulation across pairs that is not built");
+    rows_q = q->ext > 0 ? q->ext : q->max_len;
+    rows_c = c->ext > 0 ? c->ext : c->max_len;
+    return ASPIRE_OK;
 }
 
 // Query chunking.  CROSS: grid.x = candidates, grid.y = query chunks; queries are split over grid.y only while
@@ -160,16 +172,13 @@ extern "C" int aspire_l2max_scores_f32(const aspire_repset* q, const aspire_reps
 
 extern "C" int aspire_l2agg_backward_f32(const aspire_repset* q, const aspire_repset* c, int64_t D, int pairing, int agg, double temp,
                                          const float* grad_scores, float* grad_q_rows, float* grad_c_rows, void* stream) {
-    if (int rc = check_repsets(q, c, D, pairing)) return rc;
-    ASPIRE_REQUIRE(pairing == ASPIRE_PAIR_PAIRED, ASPIRE_ERR_UNSUPPORTED,
-                   "the backward is built for ASPIRE_PAIR_PAIRED: with ASPIRE_PAIR_CROSS a document's gradient is a sum over many pairs, "
-                   "which needs an accumulation across pairs that is not built");
+    int rows_q, rows_c;
+    if (int rc = check_backward_sets(q, c, D, pairing, rows_q, rows_c)) return rc;
     ASPIRE_REQUIRE(agg == ASPIRE_AGG_MAX || agg == ASPIRE_AGG_TOP2 || agg == ASPIRE_AGG_ATTENTION, ASPIRE_ERR_INVALID_ARG,
                    "bad aggregation %d", agg);
     ASPIRE_REQUIRE(agg != ASPIRE_AGG_ATTENTION || temp > 0, ASPIRE_ERR_INVALID_ARG, "attention temperature must be positive");
     if (q->n == 0) return ASPIRE_OK;                // no pair, no row
     ASPIRE_REQUIRE(grad_scores && grad_q_rows && grad_c_rows, ASPIRE_ERR_INVALID_ARG, "grad_scores, grad_q_rows or grad_c_rows is null");
-    const int rows_q = q->ext > 0 ? q->ext : q->max_len, rows_c = c->ext > 0 ? c->ext : c->max_len;
     return launch_l2agg_backward(to_dev(q), to_dev(c), agg, (float)temp, grad_scores, grad_q_rows, grad_c_rows, rows_q, rows_c,
                                  (hipStream_t)stream);
 }
@@ -177,13 +186,10 @@ extern "C" int aspire_l2agg_backward_f32(const aspire_repset* q, const aspire_re
 // Backward of the joint soft-max alignment score (the forward is in jointsm.hip; the kernel in jointsm_bwd.hip)
 extern "C" int aspire_jointsm_backward_f32(const aspire_repset* q, const aspire_repset* c, int64_t D, int pairing,
                                            const float* grad_scores, float* grad_q_rows, float* grad_c_rows, void* stream) {
-    if (int rc = check_repsets(q, c, D, pairing)) return rc;
-    ASPIRE_REQUIRE(pairing == ASPIRE_PAIR_PAIRED, ASPIRE_ERR_UNSUPPORTED,
-                   "the backward is built for ASPIRE_PAIR_PAIRED: with ASPIRE_PAIR_CROSS a document's gradient is a sum over many pairs, "
-                   "which needs an accumulation across pairs that is not built");
+    int rows_q, rows_c;
+    if (int rc = check_backward_sets(q, c, D, pairing, rows_q, rows_c)) return rc;
     if (q->n == 0) return ASPIRE_OK;                // no pair, no row
     ASPIRE_REQUIRE(grad_scores && grad_q_rows && grad_c_rows, ASPIRE_ERR_INVALID_ARG, "grad_scores, grad_q_rows or grad_c_rows is null");
-    const int rows_q = q->ext > 0 ? q->ext : q->max_len, rows_c = c->ext > 0 ? c->ext : c->max_len;
     return launch_jointsm_backward(to_dev(q), to_dev(c), grad_scores, grad_q_rows, grad_c_rows, rows_q, rows_c, (hipStream_t)stream);
 }
 
@@ -199,11 +205,11 @@ extern "C" int aspire_l2sup_scores_f32(const aspire_repset* q, const aspire_reps
 
 extern "C" int aspire_l2sup_backward_f32(const aspire_repset* q, const aspire_repset* c, int64_t D, const int32_t* align, int weighted,
                                          const float* grad_scores, float* grad_q_rows, float* grad_c_rows, void* stream) {
-    if (int rc = check_repsets(q, c, D, ASPIRE_PAIR_PAIRED)) return rc;
+    int rows_q, rows_c;
+    if (int rc = check_backward_sets(q, c, D, ASPIRE_PAIR_PAIRED, rows_q, rows_c)) return rc;
     if (q->n == 0) return ASPIRE_OK;
     ASPIRE_REQUIRE(align && grad_scores && grad_q_rows && grad_c_rows, ASPIRE_ERR_INVALID_ARG,
                    "align, grad_scores, grad_q_rows or grad_c_rows is null");
-    const int rows_q = q->ext > 0 ? q->ext : q->max_len, rows_c = c->ext > 0 ? c->ext : c->max_len;
     return launch_l2sup_backward(to_dev(q), to_dev(c), align, weighted != 0, grad_scores, grad_q_rows, grad_c_rows, rows_q, rows_c,
                                  (hipStream_t)stream);
 }
@@ -543,17 +549,14 @@ extern "C" int aspire_ot_sinkhorn_f32(const aspire_repset* q, const aspire_repse
 extern "C" int aspire_ot_backward_f32(const aspire_repset* q, const aspire_repset* c, int64_t D, int pairing, const aspire_ot_params* prm,
                                       const float* diameter, int64_t diam_group, int want, const float* grad_scores, float* grad_q,
                                       float* grad_c, void* stream) {
-    if (int rc = check_repsets(q, c, D, pairing)) return rc;
-    ASPIRE_REQUIRE(pairing == ASPIRE_PAIR_PAIRED, ASPIRE_ERR_UNSUPPORTED,
-                   "the backward is built for ASPIRE_PAIR_PAIRED: with ASPIRE_PAIR_CROSS a document's gradient is a sum over many pairs, "
-                   "which needs an accumulation across pairs that is not built");
+    int rows_q, rows_c;
+    if (int rc = check_backward_sets(q, c, D, pairing, rows_q, rows_c)) return rc;
     if (int rc = check_ot_params(prm, want)) return rc;
     ASPIRE_REQUIRE(want != ASPIRE_OT_PLAN_SIM, ASPIRE_ERR_UNSUPPORTED,
                    "ASPIRE_OT_PLAN_SIM has no backward (the reference uses return_pair_sims at test time only)");
     ASPIRE_REQUIRE(!diameter || diam_group > 0, ASPIRE_ERR_INVALID_ARG, "diam_group must be positive");
     if (q->n == 0) return ASPIRE_OK;                // no pair, no row
     ASPIRE_REQUIRE(grad_scores && grad_q && grad_c, ASPIRE_ERR_INVALID_ARG, "grad_scores, grad_q or grad_c is null");
-    const int rows_q = q->ext > 0 ? q->ext : q->max_len, rows_c = c->ext > 0 ? c->ext : c->max_len;
     return launch_ot_backward(to_dev(q), to_dev(c), prm, diameter, diam_group, want, grad_scores, grad_q, grad_c, rows_q, rows_c,
                               (hipStream_t)stream);
 }

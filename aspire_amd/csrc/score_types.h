@@ -189,19 +189,20 @@ int launch_pair_gram_planes(const ScoreArgs& a, const GramGeometry& geo, bool l2
 int generic_max_rows(void);
 int launch_pair_generic(const ScoreArgs& a, int mode, int skip_up_to, int rows_q, int rows_c, hipStream_t stream);
 
-// l2agg_bwd.hip: the gradient of the three aggregations of -cdist with respect to the sentence rows, one workgroup per PAIRED pair
+// The backward kernels: the gradient of a PAIRED pair's score with respect to its sentence rows, one workgroup per pair on the frame
+// of pair_bwd.h (launch_pair_bwd).  l2agg_bwd.hip: the three aggregations of -cdist
 int launch_l2agg_backward(const RepSet& q, const RepSet& c, int agg, float temp, const float* grad_scores, float* grad_q, float* grad_c,
                           int rows_q, int rows_c, hipStream_t stream);
 
-// ot_bwd.hip: the gradient of the otAspire distance with respect to the sentence rows, one workgroup per PAIRED pair
+// ot_bwd.hip: the otAspire distance
 int launch_ot_backward(const RepSet& q, const RepSet& c, const aspire_ot_params* prm, const float* diameter, int64_t diam_group, int want,
                        const float* grad_scores, float* grad_q, float* grad_c, int rows_q, int rows_c, hipStream_t stream);
 
-// jointsm_bwd.hip: the gradient of the joint soft-max alignment score with respect to the sentence rows, one workgroup per PAIRED pair
+// jointsm_bwd.hip: the joint soft-max alignment score
 int launch_jointsm_backward(const RepSet& q, const RepSet& c, const float* grad_scores, float* grad_q, float* grad_c, int rows_q,
                             int rows_c, hipStream_t stream);
 
-// l2sup.hip: the L2 distance of one pre-aligned sentence pair per PAIRED pair (align: device [P, 2]) and its gradient
+// l2sup.hip: the L2 distance of one pre-aligned sentence pair per PAIRED pair (align: device [P, 2]) and its gradient (pair_bwd.h's frame too)
 int launch_l2sup_scores(const RepSet& q, const RepSet& c, const int32_t* align, int weighted, float* scores, int rows_q, int rows_c,
                         hipStream_t stream);
 int launch_l2sup_backward(const RepSet& q, const RepSet& c, const int32_t* align, int weighted, const float* grad_scores, float* grad_q,

@@ -388,16 +388,22 @@ def l2agg_scores(q, c, agg, temp=1.0, pairing=_lib.PAIR_CROSS, cdist_mode=_lib.C
     return (scores, pair, soft) if agg == _lib.AGG_ATTENTION else (scores, pair)
 
 
-def l2agg_backward(q, c, agg, grad_scores, temp=1.0, out=None):
-    """The gradient of the PAIRED similarities of l2max_scores (agg = _lib.AGG_MAX) / l2agg_scores (AGG_TOP2, AGG_ATTENTION) with
-    respect to the sentence rows (include/aspire_hip.h: aspire_l2agg_backward_f32).  grad_scores [P] = dLoss / dscore.  Returns
-    (grad_q_rows, grad_c_rows), laid out like q.rows / c.rows: every row of every document is written by the kernel (pad rows with
-    zeros); rows of the matrices that no document owns stay zero.  out: the two buffers to write into instead of new ones."""
+def _grad_call_args(q, c, grad_scores, out):
+    """What the backward entries share: the checked grad_scores [P] and the two gradient buffers laid out like q.rows / c.rows."""
     assert q.n == c.n, 'paired scoring needs equal batch sizes'      # pair_distances.py:46
     grad_scores = _f32(grad_scores, 'grad_scores')
     assert grad_scores.numel() == q.n, 'grad_scores: one entry per pair'
     gq, gc = out if out is not None else (torch.zeros_like(q.rows), torch.zeros_like(c.rows))
     assert _f32(gq, 'grad_q_rows').shape == q.rows.shape and _f32(gc, 'grad_c_rows').shape == c.rows.shape
+    return grad_scores, gq, gc
+
+
+def l2agg_backward(q, c, agg, grad_scores, temp=1.0, out=None):
+    """The gradient of the PAIRED similarities of l2max_scores (agg = _lib.AGG_MAX) / l2agg_scores (AGG_TOP2, AGG_ATTENTION) with
+    respect to the sentence rows (include/aspire_hip.h: aspire_l2agg_backward_f32).  grad_scores [P] = dLoss / dscore.  Returns
+    (grad_q_rows, grad_c_rows), laid out like q.rows / c.rows: every row of every document is written by the kernel (pad rows with
+    zeros); rows of the matrices that no document owns stay zero.  out: the two buffers to write into instead of new ones."""
+    grad_scores, gq, gc = _grad_call_args(q, c, grad_scores, out)
     qs, cs = q.struct(), c.struct()
     check(lib.aspire_l2agg_backward_f32(ctypes.byref(qs), ctypes.byref(cs), D, _lib.PAIR_PAIRED, agg, ctypes.c_double(temp),
                                         _ptr(grad_scores), _ptr(gq), _ptr(gc), _stream()))
@@ -411,14 +417,10 @@ def ot_backward(q, c, grad_scores, *, blur=0.05, scaling=0.9, sent_sm_temp=1.0, 
     dLoss / dscore; diameter / diam_group: what the forward was given (None: every pair's own box).  Returns (grad_q_rows,
     grad_c_rows), laid out like q.rows / c.rows: every row of every document is written by the kernel (pad rows with zeros); rows of
     the matrices that no document owns stay zero.  out: the two buffers to write into instead of new ones."""
-    assert q.n == c.n, 'paired scoring needs equal batch sizes'      # pair_distances.py:46
-    grad_scores = _f32(grad_scores, 'grad_scores')
-    assert grad_scores.numel() == q.n, 'grad_scores: one entry per pair'
+    grad_scores, gq, gc = _grad_call_args(q, c, grad_scores, out)
     if diameter is not None:
         assert diam_group > 0, 'diam_group must be positive'
         assert _f32(diameter, 'diameter').numel() >= (q.n + diam_group - 1) // diam_group, 'diameter: one entry per group of pairs'
-    gq, gc = out if out is not None else (torch.zeros_like(q.rows), torch.zeros_like(c.rows))
-    assert _f32(gq, 'grad_q_rows').shape == q.rows.shape and _f32(gc, 'grad_c_rows').shape == c.rows.shape
     prm = OtParams(float(blur), float(scaling), float(sent_sm_temp), _lib.CDIST_AUTO, 0)      # (cdist_mode, flags: not read)
     qs, cs = q.struct(), c.struct()
     check(lib.aspire_ot_backward_f32(ctypes.byref(qs), ctypes.byref(cs), D, _lib.PAIR_PAIRED, ctypes.byref(prm), _ptr(diameter),
@@ -589,16 +591,6 @@ def jointsm_scores(q, c, pairing=_lib.PAIR_CROSS, want_pair_softmax=False):
     qs, cs = q.struct(), c.struct()
     check(lib.aspire_jointsm_scores_f32(ctypes.byref(qs), ctypes.byref(cs), D, pairing, _ptr(scores), _ptr(soft), _stream()))
     return (scores, soft) if want_pair_softmax else scores
-
-
-def _grad_call_args(q, c, grad_scores, out):
-    """What the backward entries share: the checked grad_scores [P] and the two gradient buffers laid out like q.rows / c.rows."""
-    assert q.n == c.n, 'paired scoring needs equal batch sizes'      # pair_distances.py:46
-    grad_scores = _f32(grad_scores, 'grad_scores')
-    assert grad_scores.numel() == q.n, 'grad_scores: one entry per pair'
-    gq, gc = out if out is not None else (torch.zeros_like(q.rows), torch.zeros_like(c.rows))
-    assert _f32(gq, 'grad_q_rows').shape == q.rows.shape and _f32(gc, 'grad_c_rows').shape == c.rows.shape
-    return grad_scores, gq, gc
 
 
 def jointsm_backward(q, c, grad_scores, out=None):

@@ -48,13 +48,11 @@ def _wants_grad(query, cand):
     return torch.is_grad_enabled() and (query.embed.requires_grad or cand.embed.requires_grad)
 
 
-def _differentiable_sims(query, cand, agg, temp=1.0, ot=None, op=None):
-    """sims [batch_size] of the pairs (the same bits as ops.l2max_scores / ops.l2agg_scores give), attached to the graph of
-    query.embed / cand.embed: torch.ops.aspire.l2agg_pair_scores on the GPU between differentiable moves and permutes.
-    ot = (blur, scaling, sent_sm_temp, want): torch.ops.aspire.ot_pair_scores instead (the bits of ops.ot_sinkhorn with one epsilon
-    schedule for the whole batch), `agg` and `temp` unread.  op: a callable (q, q_lens, c, c_lens) -> sims on the GPU tensors instead
-    (the jointsm and l2sup operators)."""
-    from . import torch_ops  # noqa: F401  (registers the operator)
+def _differentiable_sims(query, cand, op):
+    """sims [batch_size] of the pairs, attached to the graph of query.embed / cand.embed: op(q, q_lens, c, c_lens) -> sims, one of
+    the differentiable torch.ops.aspire.*_pair_scores operators (the same bits as the plain scoring calls give), on the GPU between
+    differentiable moves and permutes."""
+    from . import torch_ops  # noqa: F401  (registers the operators)
     dev = ops.require_gpu()
     assert (query.embed.size(0) == cand.embed.size(0))   # pair_distances.py:46
     lens = []
@@ -67,16 +65,11 @@ def _differentiable_sims(query, cand, agg, temp=1.0, ot=None, op=None):
         lens.append(torch.as_tensor(host, dtype=torch.int32).to(dev))
     q = query.embed.permute(0, 2, 1).to(device=dev, dtype=torch.float32)
     c = cand.embed.permute(0, 2, 1).to(device=dev, dtype=torch.float32)
-    if op is not None:
-        sims = op(q, lens[0], c, lens[1])
-    elif ot is not None:
-        blur, scaling, sent_sm_temp, want = ot
-        # geomloss derives ONE epsilon schedule from the bounding box of the whole batch, pads included: group = batch size
-        sims = torch.ops.aspire.ot_pair_scores(q, lens[0], c, lens[1], float(blur), float(scaling), float(sent_sm_temp),
-                                               max(q.size(0), 1), want)
-    else:
-        sims = torch.ops.aspire.l2agg_pair_scores(q, lens[0], c, lens[1], agg, float(temp))
-    return sims.to(query.embed.device)
+    return op(q, lens[0], c, lens[1]).to(query.embed.device)
+
+
+def _l2agg_pair_op(agg, temp=1.0):
+    return lambda q, ql, c, cl: torch.ops.aspire.l2agg_pair_scores(q, ql, c, cl, agg, float(temp))
 
 
 def ot_kwargs(hparams):
@@ -108,7 +101,10 @@ class AllPairMaskedWasserstein:
         reference marks that branch "only used at test time", and the plan-weighted similarity has no backward here.
         """
         if _wants_grad(query, cand) and not return_pair_sims:
-            return _differentiable_sims(query, cand, None, ot=(self.geoml_blur, self.geoml_scaling, self.sent_sm_temp, _lib.OT_DISTANCE))
+            # geomloss derives ONE epsilon schedule from the bounding box of the whole batch, pads included: group = batch size
+            return _differentiable_sims(query, cand, lambda q, ql, c, cl: torch.ops.aspire.ot_pair_scores(
+                q, ql, c, cl, float(self.geoml_blur), float(self.geoml_scaling), float(self.sent_sm_temp), max(q.size(0), 1),
+                _lib.OT_DISTANCE))
         q, c, out_dev = _to_repsets(query, cand)
         # geomloss derives ONE epsilon schedule from the bounding box of the whole batch, pads included.
         diam = ops.group_diameter(q, c, _lib.PAIR_PAIRED, group=max(q.n, 1))
@@ -127,12 +123,12 @@ def allpair_masked_dist_l2max(query, cand, return_pair_sims=False):
         (sims [batch_size], pair_sims [batch_size, q_max_sents, c_max_sents]).
     """
     if _wants_grad(query, cand) and not return_pair_sims:       # "Happens at train time" (pair_distances.py:184-186)
-        return -1 * _differentiable_sims(query, cand, _lib.AGG_MAX)
+        return -1 * _differentiable_sims(query, cand, _l2agg_pair_op(_lib.AGG_MAX))
     q, c, out_dev = _to_repsets(query, cand)
     if return_pair_sims:
         sims, pair = ops.l2max_scores(q, c, pairing=_lib.PAIR_PAIRED, want_pair_sims=True)
         if _wants_grad(query, cand):        # the pair matrix stays detached
-            sims = _differentiable_sims(query, cand, _lib.AGG_MAX)
+            sims = _differentiable_sims(query, cand, _l2agg_pair_op(_lib.AGG_MAX))
         return sims.to(out_dev), pair.to(out_dev)
     return (-1 * ops.l2max_scores(q, c, pairing=_lib.PAIR_PAIRED)).to(out_dev)
 
@@ -145,12 +141,12 @@ def allpair_masked_dist_l2topk(query, cand, return_pair_sims=False):
         # torch.topk(k=2) over the [batch, q_max_sents * c_max_sents] view raises for a single entry (pair_distances.py:333)
         raise RuntimeError('selected index k out of range')
     if _wants_grad(query, cand) and not return_pair_sims:
-        return -1 * _differentiable_sims(query, cand, _lib.AGG_TOP2)
+        return -1 * _differentiable_sims(query, cand, _l2agg_pair_op(_lib.AGG_TOP2))
     q, c, out_dev = _to_repsets(query, cand)
     if return_pair_sims:
         sims, pair = ops.l2agg_scores(q, c, _lib.AGG_TOP2, pairing=_lib.PAIR_PAIRED, want_pair_sims=True)
         if _wants_grad(query, cand):
-            sims = _differentiable_sims(query, cand, _lib.AGG_TOP2)
+            sims = _differentiable_sims(query, cand, _l2agg_pair_op(_lib.AGG_TOP2))
         return sims.to(out_dev), pair.to(out_dev)
     return (-1 * ops.l2agg_scores(q, c, _lib.AGG_TOP2, pairing=_lib.PAIR_PAIRED)).to(out_dev)
 
@@ -164,13 +160,13 @@ class AllPairMaskedAttention:
     def compute_distance(self, query, cand, return_pair_sims=False):
         """:return: doc_dists [batch_size]; with return_pair_sims (doc_sims, [pair_sims, pair_softmax, masked_sims])."""
         if _wants_grad(query, cand) and not return_pair_sims:
-            return -1 * _differentiable_sims(query, cand, _lib.AGG_ATTENTION, self.cdatt_sm_temp)
+            return -1 * _differentiable_sims(query, cand, _l2agg_pair_op(_lib.AGG_ATTENTION, self.cdatt_sm_temp))
         q, c, out_dev = _to_repsets(query, cand)
         kw = dict(temp=self.cdatt_sm_temp, pairing=_lib.PAIR_PAIRED)
         if return_pair_sims:
             sims, pair, soft = ops.l2agg_scores(q, c, _lib.AGG_ATTENTION, want_pair_sims=True, **kw)
             if _wants_grad(query, cand):
-                sims = _differentiable_sims(query, cand, _lib.AGG_ATTENTION, self.cdatt_sm_temp)
+                sims = _differentiable_sims(query, cand, _l2agg_pair_op(_lib.AGG_ATTENTION, self.cdatt_sm_temp))
             return sims.to(out_dev), [t.to(out_dev) for t in (pair, soft, soft * pair)]
         return (-1 * ops.l2agg_scores(q, c, _lib.AGG_ATTENTION, **kw)).to(out_dev)
 
@@ -182,12 +178,12 @@ def allpair_joint_sm_negscore(query, cand, return_pair_sims=False):
         (distance, pair_sm [batch_size, q_max_sents, c_max_sents]: the soft-max, 0.0 outside a pair's valid block).
     With grad mode on and an embed requiring grad the distance is attached to the graph (pair_sm never is); without, today's bits."""
     if _wants_grad(query, cand) and not return_pair_sims:       # the triplet loss of WordSentAlignPolyEnc (disent_models.py:868-875)
-        return -1.0 * _differentiable_sims(query, cand, None, op=_jointsm_pair_op)
+        return -1.0 * _differentiable_sims(query, cand, _jointsm_pair_op)
     q, c, out_dev = _to_repsets(query, cand)
     if return_pair_sims:
         sims, pair_sm = ops.jointsm_scores(q, c, pairing=_lib.PAIR_PAIRED, want_pair_softmax=True)
         if _wants_grad(query, cand):        # pair_sm stays detached
-            sims = _differentiable_sims(query, cand, None, op=_jointsm_pair_op)
+            sims = _differentiable_sims(query, cand, _jointsm_pair_op)
         return (-1.0 * sims).to(out_dev), pair_sm.to(out_dev)
     return (-1.0 * ops.jointsm_scores(q, c, pairing=_lib.PAIR_PAIRED)).to(out_dev)
 
@@ -207,7 +203,7 @@ def _l2sup_dist(query, cand, weighted):
     if any(a < 0 for pair in align for a in pair):
         raise ValueError('align_idxs must not be negative (the reference would index from the end of the padded block)')
     align = torch.as_tensor(align, dtype=torch.int32).reshape(-1, 2).to(ops.require_gpu())
-    sims = _differentiable_sims(query, cand, None, op=lambda q, ql, c, cl: torch.ops.aspire.l2sup_pair_scores(q, ql, c, cl, align, weighted))
+    sims = _differentiable_sims(query, cand, lambda q, ql, c, cl: torch.ops.aspire.l2sup_pair_scores(q, ql, c, cl, align, weighted))
     return -1 * sims
 
 

@@ -320,10 +320,47 @@ def _(rows, q_idx, cand_idx, job_off, max_job, k, metric):
 
 
 # ---- the differentiable pair scores -------------------------------------------------------------------------------------
-# agg: 0 max-sim, 1 top-2, 2 attention (temp = cdatt_sm_temp; read by attention only).  Pair p = query p with candidate p.  The
-# forward is the existing scoring entry (aspire_l2max_scores_f32 for agg 0, aspire_l2agg_scores_f32 else): the same bits as
-# l2max_scores / ops.l2agg_scores; its autograd formula is l2agg_pair_backward (aspire_l2agg_backward_f32), which recomputes
-# the distances -- nothing but the inputs is saved.
+# Four operator pairs of one shape: X_pair_scores(q, q_lens, c, c_lens, ...) -> scores [B], pair p = query p with candidate p, is an
+# existing PAIRED scoring entry (the same bits); its autograd formula is X_pair_backward(grad_scores, the same inputs) ->
+# (grad_q, grad_c), which recomputes what it needs from the inputs -- nothing else is saved.
+def _pair_scores_fake(q, q_lens, c, c_lens, *rest):
+    return q.new_empty(_npairs(q.shape[0], c.shape[0], True))
+
+
+def _pair_backward(backward, grad_scores, q, q_lens, c, c_lens):
+    """(grad_q, grad_c) shaped like q / c: backward(qs, cs, grad_scores, out) is the ops.*_backward call on the padded sets."""
+    qs, cs = _padded_repset(q, q_lens), _padded_repset(c, c_lens)
+    gq, gc = backward(qs, cs, grad_scores.to(torch.float32).contiguous(),
+                      (torch.empty_like(qs.rows), torch.empty_like(cs.rows)))     # padded: every row has its writer
+    return gq.view(q.shape), gc.view(c.shape)
+
+
+def _pair_backward_fake(grad_scores, q, q_lens, c, c_lens, *rest):
+    return q.new_empty(q.shape), c.new_empty(c.shape)
+
+
+def _register_pair_autograd(forward_op, backward_op):
+    """The two operators' fakes and the forward's autograd: the tensor inputs (they lead in every schema) are saved, the others kept
+    on ctx; backward_op gives the gradients of q (position 0) and c (position 2), no other input has one."""
+    forward_op.register_fake(_pair_scores_fake)
+    backward_op.register_fake(_pair_backward_fake)
+
+    def setup(ctx, inputs, output):
+        n = sum(isinstance(x, Tensor) for x in inputs)
+        assert all(isinstance(x, Tensor) for x in inputs[:n])
+        ctx.save_for_backward(*inputs[:n])
+        ctx.rest = tuple(inputs[n:])
+
+    def grad(ctx, grad_scores):
+        inputs = (*ctx.saved_tensors, *ctx.rest)
+        gq, gc = backward_op(grad_scores, *inputs)
+        return (gq, None, gc) + (None,) * (len(inputs) - 3)
+
+    forward_op.register_autograd(grad, setup_context=setup)
+
+
+# agg: 0 max-sim, 1 top-2, 2 attention (temp = cdatt_sm_temp; read by attention only).  The forward is aspire_l2max_scores_f32 for
+# agg 0, aspire_l2agg_scores_f32 else: the bits of l2max_scores / ops.l2agg_scores; the backward aspire_l2agg_backward_f32.
 @torch.library.custom_op('aspire::l2agg_pair_scores', mutates_args=(), device_types='cuda')
 def l2agg_pair_scores(q: Tensor, q_lens: Tensor, c: Tensor, c_lens: Tensor, agg: int, temp: float) -> Tensor:
     qs, cs = _padded_repset(q, q_lens), _padded_repset(c, c_lens)
@@ -332,46 +369,19 @@ def l2agg_pair_scores(q: Tensor, q_lens: Tensor, c: Tensor, c_lens: Tensor, agg:
     return ops.l2agg_scores(qs, cs, agg, temp=temp, pairing=_lib.PAIR_PAIRED)
 
 
-@l2agg_pair_scores.register_fake
-def _(q, q_lens, c, c_lens, agg, temp):
-    return q.new_empty(_npairs(q.shape[0], c.shape[0], True))
-
-
 @torch.library.custom_op('aspire::l2agg_pair_backward', mutates_args=(), device_types='cuda')
 def l2agg_pair_backward(grad_scores: Tensor, q: Tensor, q_lens: Tensor, c: Tensor, c_lens: Tensor, agg: int,
                         temp: float) -> Tuple[Tensor, Tensor]:
-    qs, cs = _padded_repset(q, q_lens), _padded_repset(c, c_lens)
-    gq, gc = ops.l2agg_backward(qs, cs, agg, grad_scores.to(torch.float32).contiguous(), temp=temp,
-                                out=(torch.empty_like(qs.rows), torch.empty_like(cs.rows)))     # padded: every row has its writer
-    return gq.view(q.shape), gc.view(c.shape)
+    return _pair_backward(lambda qs, cs, g, out: ops.l2agg_backward(qs, cs, agg, g, temp=temp, out=out), grad_scores, q, q_lens, c, c_lens)
 
 
-@l2agg_pair_backward.register_fake
-def _(grad_scores, q, q_lens, c, c_lens, agg, temp):
-    return q.new_empty(q.shape), c.new_empty(c.shape)
+_register_pair_autograd(l2agg_pair_scores, l2agg_pair_backward)
 
 
-def _l2agg_pair_setup(ctx, inputs, output):
-    q, q_lens, c, c_lens, agg, temp = inputs
-    ctx.save_for_backward(q, q_lens, c, c_lens)
-    ctx.agg, ctx.temp = agg, temp
-
-
-def _l2agg_pair_grad(ctx, grad_scores):
-    q, q_lens, c, c_lens = ctx.saved_tensors
-    gq, gc = torch.ops.aspire.l2agg_pair_backward(grad_scores, q, q_lens, c, c_lens, ctx.agg, ctx.temp)
-    return gq, None, gc, None, None, None
-
-
-l2agg_pair_scores.register_autograd(_l2agg_pair_grad, setup_context=_l2agg_pair_setup)
-
-
-# ---- the differentiable otAspire distance ---------------------------------------------------------------------------------
-# group / want as ot_sinkhorn_scores (want: 0 distance, 2 -distance; 1, the plan-weighted similarity, has no backward).  The forward
-# is the existing PAIRED scoring call: the same bits as ot_sinkhorn_scores(..., paired=True, extras=False).  Its autograd formula is
-# ot_pair_backward (aspire_ot_backward_f32: a restatement of geomloss's detach pattern, include/aspire_hip.h), which repeats the solve
-# from the inputs -- nothing else is saved -- and forms the group diameters again from them, so that forward and backward see one
-# epsilon schedule.
+# The otAspire distance.  group / want as ot_sinkhorn_scores (want: 0 distance, 2 -distance; 1, the plan-weighted similarity, has no
+# backward): the bits of ot_sinkhorn_scores(..., paired=True, extras=False).  The backward (aspire_ot_backward_f32: a restatement of
+# geomloss's detach pattern, include/aspire_hip.h) repeats the solve and forms the group diameters again from the inputs, so that
+# forward and backward see one epsilon schedule.
 def _ot_pair_diameter(qs, cs, group):
     return ops.group_diameter(qs, cs, _lib.PAIR_PAIRED, group) if group > 0 else None
 
@@ -384,119 +394,47 @@ def ot_pair_scores(q: Tensor, q_lens: Tensor, c: Tensor, c_lens: Tensor, blur: f
                            diameter=_ot_pair_diameter(qs, cs, group), diam_group=group, want=want)
 
 
-@ot_pair_scores.register_fake
-def _(q, q_lens, c, c_lens, blur, scaling, temp, group, want):
-    return q.new_empty(_npairs(q.shape[0], c.shape[0], True))
-
-
 @torch.library.custom_op('aspire::ot_pair_backward', mutates_args=(), device_types='cuda')
 def ot_pair_backward(grad_scores: Tensor, q: Tensor, q_lens: Tensor, c: Tensor, c_lens: Tensor, blur: float, scaling: float,
                      temp: float, group: int, want: int) -> Tuple[Tensor, Tensor]:
-    qs, cs = _padded_repset(q, q_lens), _padded_repset(c, c_lens)
-    gq, gc = ops.ot_backward(qs, cs, grad_scores.to(torch.float32).contiguous(), blur=blur, scaling=scaling, sent_sm_temp=temp,
-                             diameter=_ot_pair_diameter(qs, cs, group), diam_group=group, want=want,
-                             out=(torch.empty_like(qs.rows), torch.empty_like(cs.rows)))     # padded: every row has its writer
-    return gq.view(q.shape), gc.view(c.shape)
+    return _pair_backward(lambda qs, cs, g, out: ops.ot_backward(qs, cs, g, blur=blur, scaling=scaling, sent_sm_temp=temp,
+                                                                 diameter=_ot_pair_diameter(qs, cs, group), diam_group=group,
+                                                                 want=want, out=out), grad_scores, q, q_lens, c, c_lens)
 
 
-@ot_pair_backward.register_fake
-def _(grad_scores, q, q_lens, c, c_lens, blur, scaling, temp, group, want):
-    return q.new_empty(q.shape), c.new_empty(c.shape)
+_register_pair_autograd(ot_pair_scores, ot_pair_backward)
 
 
-def _ot_pair_setup(ctx, inputs, output):
-    q, q_lens, c, c_lens, blur, scaling, temp, group, want = inputs
-    ctx.save_for_backward(q, q_lens, c, c_lens)
-    ctx.prm = (blur, scaling, temp, group, want)
-
-
-def _ot_pair_grad(ctx, grad_scores):
-    q, q_lens, c, c_lens = ctx.saved_tensors
-    gq, gc = torch.ops.aspire.ot_pair_backward(grad_scores, q, q_lens, c, c_lens, *ctx.prm)
-    return gq, None, gc, None, None, None, None, None, None
-
-
-ot_pair_scores.register_autograd(_ot_pair_grad, setup_context=_ot_pair_setup)
-
-
-# ---- the differentiable joint soft-max alignment score ----------------------------------------------------------------------
-# The forward is the existing PAIRED scoring call: the same bits as jointsm_scores(..., paired=True).  Its autograd formula is
-# jointsm_pair_backward (aspire_jointsm_backward_f32), which forms the dot products again -- nothing but the inputs is saved.
+# The joint soft-max alignment score: the bits of jointsm_scores(..., paired=True); the backward aspire_jointsm_backward_f32.
 @torch.library.custom_op('aspire::jointsm_pair_scores', mutates_args=(), device_types='cuda')
 def jointsm_pair_scores(q: Tensor, q_lens: Tensor, c: Tensor, c_lens: Tensor) -> Tensor:
     return ops.jointsm_scores(_padded_repset(q, q_lens), _padded_repset(c, c_lens), pairing=_lib.PAIR_PAIRED)
 
 
-@jointsm_pair_scores.register_fake
-def _(q, q_lens, c, c_lens):
-    return q.new_empty(_npairs(q.shape[0], c.shape[0], True))
-
-
 @torch.library.custom_op('aspire::jointsm_pair_backward', mutates_args=(), device_types='cuda')
 def jointsm_pair_backward(grad_scores: Tensor, q: Tensor, q_lens: Tensor, c: Tensor, c_lens: Tensor) -> Tuple[Tensor, Tensor]:
-    qs, cs = _padded_repset(q, q_lens), _padded_repset(c, c_lens)
-    gq, gc = ops.jointsm_backward(qs, cs, grad_scores.to(torch.float32).contiguous(),
-                                  out=(torch.empty_like(qs.rows), torch.empty_like(cs.rows)))     # padded: every row has its writer
-    return gq.view(q.shape), gc.view(c.shape)
+    return _pair_backward(ops.jointsm_backward, grad_scores, q, q_lens, c, c_lens)
 
 
-@jointsm_pair_backward.register_fake
-def _(grad_scores, q, q_lens, c, c_lens):
-    return q.new_empty(q.shape), c.new_empty(c.shape)
+_register_pair_autograd(jointsm_pair_scores, jointsm_pair_backward)
 
 
-def _jointsm_pair_setup(ctx, inputs, output):
-    ctx.save_for_backward(*inputs)
-
-
-def _jointsm_pair_grad(ctx, grad_scores):
-    gq, gc = torch.ops.aspire.jointsm_pair_backward(grad_scores, *ctx.saved_tensors)
-    return gq, None, gc, None
-
-
-jointsm_pair_scores.register_autograd(_jointsm_pair_grad, setup_context=_jointsm_pair_setup)
-
-
-# ---- the differentiable supervised-alignment distance -------------------------------------------------------------------------
-# align int32 [B, 2]: (query row, candidate row) of each pair's pre-aligned sentences, clipped on the device to the documents' last
-# rows; weighted: the similarity divided by q_len * c_len.  scores = the SIMILARITY -||q_i - c_j|| (aspire_l2sup_scores_f32); the
-# autograd formula is l2sup_pair_backward (aspire_l2sup_backward_f32); only the inputs are saved.
+# The supervised-alignment distance.  align int32 [B, 2]: (query row, candidate row) of each pair's pre-aligned sentences, clipped on
+# the device to the documents' last rows; weighted: the similarity divided by q_len * c_len.  scores = the SIMILARITY -||q_i - c_j||
+# (aspire_l2sup_scores_f32); the backward aspire_l2sup_backward_f32.
 @torch.library.custom_op('aspire::l2sup_pair_scores', mutates_args=(), device_types='cuda')
 def l2sup_pair_scores(q: Tensor, q_lens: Tensor, c: Tensor, c_lens: Tensor, align: Tensor, weighted: bool) -> Tensor:
     return ops.l2sup_scores(_padded_repset(q, q_lens), _padded_repset(c, c_lens), align.to(torch.int32).contiguous(), weighted)
 
 
-@l2sup_pair_scores.register_fake
-def _(q, q_lens, c, c_lens, align, weighted):
-    return q.new_empty(_npairs(q.shape[0], c.shape[0], True))
-
-
 @torch.library.custom_op('aspire::l2sup_pair_backward', mutates_args=(), device_types='cuda')
 def l2sup_pair_backward(grad_scores: Tensor, q: Tensor, q_lens: Tensor, c: Tensor, c_lens: Tensor, align: Tensor,
                         weighted: bool) -> Tuple[Tensor, Tensor]:
-    qs, cs = _padded_repset(q, q_lens), _padded_repset(c, c_lens)
-    gq, gc = ops.l2sup_backward(qs, cs, align.to(torch.int32).contiguous(), grad_scores.to(torch.float32).contiguous(), weighted,
-                                out=(torch.empty_like(qs.rows), torch.empty_like(cs.rows)))     # padded: every row has its writer
-    return gq.view(q.shape), gc.view(c.shape)
+    align = align.to(torch.int32).contiguous()
+    return _pair_backward(lambda qs, cs, g, out: ops.l2sup_backward(qs, cs, align, g, weighted, out=out), grad_scores, q, q_lens, c, c_lens)
 
 
-@l2sup_pair_backward.register_fake
-def _(grad_scores, q, q_lens, c, c_lens, align, weighted):
-    return q.new_empty(q.shape), c.new_empty(c.shape)
-
-
-def _l2sup_pair_setup(ctx, inputs, output):
-    q, q_lens, c, c_lens, align, weighted = inputs
-    ctx.save_for_backward(q, q_lens, c, c_lens, align)
-    ctx.weighted = weighted
-
-
-def _l2sup_pair_grad(ctx, grad_scores):
-    gq, gc = torch.ops.aspire.l2sup_pair_backward(grad_scores, *ctx.saved_tensors, ctx.weighted)
-    return gq, None, gc, None, None, None
-
-
-l2sup_pair_scores.register_autograd(_l2sup_pair_grad, setup_context=_l2sup_pair_setup)
+_register_pair_autograd(l2sup_pair_scores, l2sup_pair_backward)
 
 
 OPS = ('span_mean_pool', 'span_pool_ranges', 'bert_encoder_forward', 'bert_cls_forward', 'bert_pooler', 'token_mean_pool', 'l2max_scores', 'jointsm_scores', 'ot_sinkhorn_scores', 'topk_desc', 'topk_keys', 'topk_merge',
