@@ -1,6 +1,8 @@
-// Host side that the batched rank entry points share (score.hip: aspire_ot_rank_batch_f32, aspire_l2max_rank_batch_f32;
-// dotmax.hip: aspire_dotmax_rank_batch_f32): the argument checks every one of them makes after its own set check, and the
-// rank that ends every one of them.  Host only: no kernel, nothing a kernel reads.
+// Host side that the six batched rank entry points share (score.hip: aspire_ot_rank_batch_f32, aspire_l2max_rank_batch_f32;
+// l2agg_pair.hip: aspire_l2agg_rank_batch_f32; dotmax.hip: aspire_dotmax_rank_batch_f32; jointsm.hip:
+// aspire_jointsm_rank_batch_f32; dense.hip: aspire_dense_rank_batch_f32): the argument checks every one of them makes after its
+// own set check, the workspace check behind them, the workspace size of the four that need the rank's scratch only, and the rank
+// that ends every one of them.  Host only: no kernel, nothing a kernel reads.
 #pragma once
 #include "common.h"
 #include "topk_device.h"
@@ -20,16 +22,32 @@ struct BatchRank {
     void* scratch = nullptr;       // the rank's multi-pass scratch (aspire_topk_workspace_bytes; none for short pools)
     size_t scratch_bytes = 0;
 
-    void scratch_at(void* p) {
-        scratch_bytes = aspire_topk_workspace_bytes(J, max_job, k);
-        scratch = scratch_bytes ? p : nullptr;
-    }
     int rank(const float* scores) const {
         if (k <= 0) return ASPIRE_OK;
         return topk_run(scores, J, max_job, k, 0, keys ? nullptr : top_scores, keys ? nullptr : top_idx, keys, scratch, scratch_bytes,
                         stream, job_off, job_base);
     }
 };
+
+// The workspace check of an entry whose `query_fn` asks for `need` bytes, and the rank's scratch placed `scratch_off` bytes into it.
+// A null workspace passes only where nothing is needed: never for the OT and l2max layouts (score.hip), which hold a gate word.
+static int place_scratch(BatchRank& r, void* workspace, size_t workspace_bytes, size_t need, size_t scratch_off, const char* query_fn) {
+    ASPIRE_REQUIRE(workspace_bytes >= need && (need == 0 || workspace), ASPIRE_ERR_INVALID_ARG,
+                   "workspace too small: %zu bytes given, %s says %zu", workspace_bytes, query_fn, need);
+    ASPIRE_REQUIRE(((uintptr_t)workspace & 15) == 0, ASPIRE_ERR_INVALID_ARG, "workspace must be 16-byte aligned");
+    r.scratch_bytes = aspire_topk_workspace_bytes(r.J, r.max_job, r.k);
+    r.scratch = r.scratch_bytes ? (char*)workspace + scratch_off : nullptr;
+    return ASPIRE_OK;
+}
+
+// The workspace of an entry that needs the rank's scratch and nothing else (l2agg, dotmax, jointsm, dense)
+inline size_t rank_scratch_only_bytes(int64_t J, int64_t C, int64_t max_job, int64_t k) {
+    if (J <= 0 || C <= 0 || k <= 0) return 0;
+    return aspire_topk_workspace_bytes(J, max_job, k);
+}
+inline size_t rank_scratch_only_bytes(const aspire_repset* q, const aspire_repset* c, int64_t max_job, int64_t k) {
+    return q && c ? rank_scratch_only_bytes(q->n, c->n, max_job, k) : 0;
+}
 
 // What a batched entry point checks once its rep sets are known to be sound (check_repsets / check_dot_sets).  `go_on` false:
 // the call is finished -- an argument error, no jobs, or only empty pools (the lists are all padding) -- and the entry point

@@ -178,8 +178,7 @@ int launch_dense(const DenseArgs& a, int metric, hipStream_t s) {
 using namespace aspire;
 
 extern "C" size_t aspire_dense_rank_batch_workspace_bytes(int64_t J, int64_t C, int64_t max_job, int64_t k) {
-    if (J <= 0 || C <= 0 || k <= 0) return 0;
-    return aspire_topk_workspace_bytes(J, max_job, k);
+    return rank_scratch_only_bytes(J, C, max_job, k);
 }
 
 extern "C" int aspire_dense_rank_batch_f32(const float* rows, int64_t N, int64_t D, const int32_t* q_idx, int64_t J,
@@ -201,11 +200,8 @@ extern "C" int aspire_dense_rank_batch_f32(const float* rows, int64_t N, int64_t
     ASPIRE_REQUIRE(q_idx && cand_idx, ASPIRE_ERR_INVALID_ARG, "null q_idx / cand_idx");
     ASPIRE_REQUIRE(rows || N == 0, ASPIRE_ERR_INVALID_ARG, "null rows");
     ASPIRE_REQUIRE(((uintptr_t)rows & 15) == 0, ASPIRE_ERR_INVALID_ARG, "rows must be 16-byte aligned");
-    const size_t need = aspire_dense_rank_batch_workspace_bytes(J, C, max_job, k);
-    ASPIRE_REQUIRE(workspace_bytes >= need && (need == 0 || workspace), ASPIRE_ERR_INVALID_ARG,
-                   "workspace too small: %zu bytes given, aspire_dense_rank_batch_workspace_bytes says %zu", workspace_bytes, need);
-    ASPIRE_REQUIRE(((uintptr_t)workspace & 15) == 0, ASPIRE_ERR_INVALID_ARG, "workspace must be 16-byte aligned");
-    rank.scratch_at(workspace);
+    if (int rc = place_scratch(rank, workspace, workspace_bytes, rank_scratch_only_bytes(J, C, max_job, k), 0,
+                               "aspire_dense_rank_batch_workspace_bytes")) return rc;
     const DenseArgs a{rows, N, q_idx, cand_idx, job_off, (int32_t)J, C, scores};
     if (int rc = launch_dense(a, metric, (hipStream_t)stream)) return rc;
     return rank.rank(scores);

@@ -1,6 +1,8 @@
-// What the kernels that form sentence-pair dot products on v_mfma_f32_16x16x4_f32 share (dotmax.hip: max over the block;
-// jointsm.hip: joint soft-max over the block; l2agg_pair.hip: top-2 / soft-max of the negated L2 distances): the rep-set view the kernels read, the operand loads and the eight-k product
-// step, the job lookup of the batched form, and the host-side set check.  A lane holds A[row l & 15][k] and B[k][col l & 15] for
+// The operand and product helpers of the kernels that form sentence-pair dot products on v_mfma_f32_16x16x4_f32 (dotmax.hip: max over
+// the block; jointsm.hip: joint soft-max over the block; l2agg_pair.hip: top-2 / soft-max of the negated L2 distances): the rep-set view
+// the kernels read, the operand loads, the eight-k product step and the sum of squares beside it, the job lookup of the batched form,
+// and the host-side set check.  The frame around them -- which wave works on which pair, the tile walk, the cross kernels' row slots,
+// the launchers -- is pair_fwd.h, which includes this file.  A lane holds A[row l & 15][k] and B[k][col l & 15] for
 // k = 32 s + 8 (l >> 4) + e: the k order inside a block of 32 is permuted identically for both operands, so the sums are the
 // same dot products -- and the same bits in every kernel that spreads the k blocks over its accumulators the same way (the two
 // kernels of dotmax.hip: four accumulators; the two of jointsm.hip and l2agg_pair.hip's: sixteen).
@@ -44,6 +46,18 @@ __device__ __forceinline__ void mfma8(const f32x4& a0, const f32x4& a1, const f3
     acc[3] = mfma4(a1.w, b1.w, acc[3]);
 }
 
+// eight more squares onto a row's sum of squares, in the operands' order (dotmax.hip's norms)
+__device__ __forceinline__ float sumsq8(float ss, const f32x4& x0, const f32x4& x1) {
+    ss = fmaf(x0.x, x0.x, ss);
+    ss = fmaf(x0.y, x0.y, ss);
+    ss = fmaf(x0.z, x0.z, ss);
+    ss = fmaf(x0.w, x0.w, ss);
+    ss = fmaf(x1.x, x1.x, ss);
+    ss = fmaf(x1.y, x1.y, ss);
+    ss = fmaf(x1.z, x1.z, ss);
+    return fmaf(x1.w, x1.w, ss);
+}
+
 // a tile's dot products from sixteen accumulators (jointsm.hip, l2agg_pair.hip; set u: k blocks s = u mod 4)
 __device__ __forceinline__ f32x4 tile_dots(const f32x4 (&acc)[4][4]) {
     f32x4 t[4];
@@ -60,12 +74,6 @@ __device__ __forceinline__ int32_t job_of(const int32_t* __restrict__ job_off, i
         if (job_off[mid] <= p) lo = mid; else hi = mid;
     }
     return lo;
-}
-
-int log2_slots(int rows) {
-    int l = 0;
-    while ((1 << l) < rows) ++l;
-    return l;
 }
 
 DotSet to_dot(const aspire_repset* s) {

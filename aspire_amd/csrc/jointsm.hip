@@ -19,13 +19,13 @@
 // Scores are large (hundreds to thousands) and the logits reach +-70: the shift happens before the division, so the exponent's
 // argument carries the rounding of a small number, and T / S is a correction of a few sqrt(768) to m, so the rounding of the two
 // long sums reaches the score scaled down by that ratio.  A new maximum m' rescales with f = exp((m - m') / sqrtf(768)):
-// S <- f S, T <- f (T + (m - m') S).
+// S <- f S, T <- f (T + (m - m') S) (pair_fwd.h: CentredSoftmax).
 //   jointsm_pair_kernel   one wave per (query, candidate) pair, 16 x 16 tiles over documents of up to 128 rows, m wave-uniform
 //                         (one wave_max per tile), S and T per lane until the end: PAIRED, the jobs of
 //                         aspire_jointsm_rank_batch_f32, CROSS with longer documents, and every call that wants pair_softmax
 //                         (pass 1 leaves d_ij in the output block, pass 2 -- every lane over its own entries -- turns them
 //                         into p_ij once m and S are final, then the pad entries are zeroed).
-//   jointsm_cross_kernel  CROSS with documents of <= 16 rows: dotmax_cross_kernel's layout (32 candidate row slots per workgroup in
+//   jointsm_cross_kernel  CROSS with documents of <= 16 rows: pair_fwd.h's cross layout (32 candidate row slots per workgroup in
 //                         LDS, the query rows streamed in chunks of 16 slots); max, S and T are segmented all-reductions over the
 //                         W_q lanes x W_c rows of a document pair.
 // The two kernels sum S and T in different orders: a pair's score agrees between them to rounding, not
@@ -34,58 +34,42 @@
 
 #include "common.h"
 #include "batch_host.h"
-#include "dot_tiles.h"
+#include "pair_fwd.h"
 
 namespace aspire {
 namespace {
 
-struct JsmArgs {
-    DotSet q, c;
-    int mode;
-    const int32_t* job_off;     // kModeMapped: [J + 1]
-    int32_t J;
-    int32_t wq_log, wc_log;     // cross kernel: log2 of the row slots per document
-    float* scores;
+struct JsmArgs : PairArgs {
     float* pair_softmax;        // pair kernel, padded sets: [P, q.bound, c.bound], or null
 };
 
 // exp((d - m) / sqrt(encoding_dim)) for d <= m: torch.div(pair_sims, math.sqrt(encoding_dim)) behind the max shift
 __device__ __forceinline__ float shifted_exp(float y) { return expf(y / sqrtf((float)kD)); }
 
-// ---- one wave per pair --------------------------------------------------------------------------------------------------
+// ---- one wave per pair (pair_fwd.h) --------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) jointsm_pair_kernel(JsmArgs a, int64_t P) {
-    const int lane = threadIdx.x & 63, g = lane >> 4, r = lane & 15;
-    const int64_t p = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int64_t p = wave_pair();
     if (p >= P) return;
-    int64_t qi, ci;
-    if (a.mode == kModeCross) {
-        qi = p / a.c.n;
-        ci = p - qi * a.c.n;
-    } else if (a.mode == kModePaired) {
-        qi = ci = p;
-    } else {
-        ci = p;
-        qi = job_of(a.job_off, a.J, p);
-    }
-    const int ql = a.q.len[qi], cl = a.c.len[ci];
+    const PairWave w = pair_wave(a.q, a.c, a.mode, a.job_off, a.J, p);
+    const int lane = w.lane, g = w.g, r = w.r, ql = w.ql, cl = w.cl;
     const int qext = a.q.bound, cext = a.c.bound;
     float* soft = a.pair_softmax ? a.pair_softmax + p * qext * cext : nullptr;
-    if (ql > qext || cl > cext) {
-        if (lane == 0) a.scores[p] = __builtin_nanf("");
+    if (w.poison) {
+        poison_score(a.scores, p, lane);
         if (soft)
             for (int e = lane; e < qext * cext; e += 64) soft[e] = __builtin_nanf("");
         return;
     }
-    const float* qbase = a.q.rows + (int64_t)a.q.start[qi] * kD + 8 * g;
-    const float* cbase = a.c.rows + (int64_t)a.c.start[ci] * kD + 8 * g;
-    float m = -INFINITY, S = 0.f, T = 0.f;
+    const float *qbase = w.qdoc + 8 * g, *cbase = w.cdoc + 8 * g;
+    CentredSoftmax sm;
+    const auto ex = [](float y) { return shifted_exp(y); };
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     for (int c0 = 0; c0 < cl; c0 += 16) {
-        const bool va = c0 + r < cl;
-        const float* pa = cbase + (int64_t)(va ? c0 + r : 0) * kD;
+        const bool va = tile_row_valid(r, c0, cl);
+        const float* pa = tile_row(r, cbase, c0, cl);
         for (int q0 = 0; q0 < ql; q0 += 16) {
-            const bool vb = q0 + r < ql;
-            const float* pb = qbase + (int64_t)(vb ? q0 + r : 0) * kD;
+            const bool vb = tile_row_valid(r, q0, ql);
+            const float* pb = tile_row(r, qbase, q0, ql);
             f32x4 acc[4][4] = {{zero, zero, zero, zero}, {zero, zero, zero, zero}, {zero, zero, zero, zero}, {zero, zero, zero, zero}};
             for (int s0 = 0; s0 < kD / 32; s0 += 4) {
 #pragma unroll
@@ -96,34 +80,22 @@ __global__ void __launch_bounds__(256) jointsm_pair_kernel(JsmArgs a, int64_t P)
                     mfma8(a0, a1, b0, b1, acc[u]);
                 }
             }
-            // C[row 4 g + v][col r]: candidate row c0 + 4 g + v, query row q0 + r
             const f32x4 dot = tile_dots(acc);
             float tile_max = -INFINITY;
 #pragma unroll
             for (int v = 0; v < 4; ++v)
-                if (c0 + 4 * g + v < cl && vb) tile_max = fmaxf(tile_max, dot[v]);
-            tile_max = wave_max(tile_max);
-            if (tile_max > m) {                 // wave-uniform
-                if (m > -INFINITY) {
-                    const float dm = m - tile_max, f = shifted_exp(dm);
-                    T = f * fmaf(dm, S, T);
-                    S = f * S;
-                }
-                m = tile_max;
-            }
+                if (entry_valid(w, c0, v, vb)) tile_max = fmaxf(tile_max, dot[v]);
+            sm.raise(wave_max(tile_max), ex);
 #pragma unroll
             for (int v = 0; v < 4; ++v) {
-                if (c0 + 4 * g + v < cl && vb) {
-                    const float y = dot[v] - m, e = shifted_exp(y);
-                    S += e;
-                    T = fmaf(e, y, T);
+                if (entry_valid(w, c0, v, vb)) {
+                    sm.add(dot[v], ex);
                     if (soft) soft[(q0 + r) * cext + c0 + 4 * g + v] = dot[v];
                 }
             }
         }
     }
-    S = wave_sum(S);
-    T = wave_sum(T);
+    const float m = sm.m, S = wave_sum(sm.S), T = wave_sum(sm.T);
     if (lane == 0) a.scores[p] = 2.0f * (m + T / S);
     if (!soft) return;
     // every lane turns the dots it left in the block into p_ij (its own stores: program order), then the pads are zeroed
@@ -144,70 +116,32 @@ __global__ void __launch_bounds__(256) jointsm_pair_kernel(JsmArgs a, int64_t P)
     }
 }
 
-// ---- CROSS, documents of <= 16 rows: 32 candidate row slots per workgroup in LDS --------------------------------------
-// all-reduce over one document pair's entries of a 16 x 16 tile: the query document's rows sit on Wq neighbouring lanes, the
-// candidate document's Wc rows on registers v, then lane groups g
-template <typename Op>
-__device__ __forceinline__ void pair_block_allreduce(float (&m)[4], int Wq, int Wc, Op op) {
-#pragma unroll
-    for (int v = 0; v < 4; ++v)
-        for (int sh = 1; sh < Wq; sh <<= 1) m[v] = op(m[v], __shfl_xor(m[v], sh));
-    if (Wc >= 2) {
-        m[0] = m[1] = op(m[0], m[1]);
-        m[2] = m[3] = op(m[2], m[3]);
-    }
-    if (Wc >= 4) m[0] = m[1] = m[2] = m[3] = op(m[0], m[2]);
-    if (Wc >= 8) {
-        m[0] = op(m[0], __shfl_xor(m[0], 16));
-        if (Wc >= 16) m[0] = op(m[0], __shfl_xor(m[0], 32));
-        m[1] = m[2] = m[3] = m[0];
-    }
-}
-
+// ---- CROSS, documents of <= 16 rows: 32 candidate row slots per workgroup in LDS (pair_fwd.h) ----------------------------
 __global__ void __launch_bounds__(256) jointsm_cross_kernel(JsmArgs a) {
     __shared__ __attribute__((aligned(16))) float As[kXRows * kXStride];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, r = lane & 15;
     const int Wc = 1 << a.wc_log, Wq = 1 << a.wq_log;
-    const int64_t C = a.c.n, Q = a.q.n;
     const int64_t slot0 = (int64_t)blockIdx.x * kXRows;
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-    // stage: four threads per row slot (waves 0 and 1), thread g reads k = 32 s + 8 g .. + 7 -- the k values lane group g of
-    // jointsm_pair_kernel reads, so the two kernels form the same dot products bit for bit
-    if (tid < 4 * kXRows) {
-        const int R = tid >> 2, gs = tid & 3;
-        const int64_t vrow = slot0 + R, doc = vrow >> a.wc_log;
-        const int row = (int)(vrow & (Wc - 1));
-        const bool valid = doc < C && row < a.c.len[doc < C ? doc : 0];
-        const float* src = valid ? a.c.rows + ((int64_t)a.c.start[doc] + row) * kD + 8 * gs : nullptr;
-        float* dst = As + R * kXStride + 8 * gs;
-#pragma unroll 4
-        for (int s = 0; s < kD / 32; ++s) {
-            *reinterpret_cast<f32x4*>(dst + 32 * s) = valid ? ld4(src + 32 * s) : zero;
-            *reinterpret_cast<f32x4*>(dst + 32 * s + 4) = valid ? ld4(src + 32 * s + 4) : zero;
-        }
-    }
+    stage_slots<false>(a.c, a.wc_log, slot0, As, nullptr);
     __syncthreads();
-    const int64_t n_chunks = (Q * Wq + 15) / 16;
+    const int64_t n_chunks = (a.q.n * Wq + 15) / 16;
     for (int64_t qc = wave; qc < n_chunks; qc += 4) {
-        const int64_t vq = qc * 16 + r, qdoc = vq >> a.wq_log;
-        const int qrow = (int)(vq & (Wq - 1));
-        const int qlen = qdoc < Q ? a.q.len[qdoc] : 0;
-        const bool vb = qrow < qlen;
-        const float* pb = a.q.rows + (vb ? ((int64_t)a.q.start[qdoc] + qrow) * kD : 0) + 8 * g;
+        const QueryChunk k = query_chunk(a.q, a.wq_log, qc, g, r);
         f32x4 acc0[4][4], acc1[4][4];
 #pragma unroll
         for (int u = 0; u < 4; ++u)
 #pragma unroll
             for (int e = 0; e < 4; ++e) acc0[u][e] = acc1[u][e] = zero;
-        f32x4 b0 = vb ? ld4(pb) : zero, b1 = vb ? ld4(pb + 4) : zero;
+        f32x4 b0 = k.vb ? ld4(k.pb) : zero, b1 = k.vb ? ld4(k.pb + 4) : zero;
 #pragma unroll 1
         for (int s0 = 0; s0 < kD / 32; s0 += 4) {
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 // the next block's query values are in flight while this block's 16 products issue
                 const int s = s0 + u;
-                const bool more = vb && s + 1 < kD / 32;
-                const f32x4 n0 = more ? ld4(pb + 32 * (s + 1)) : zero, n1 = more ? ld4(pb + 32 * (s + 1) + 4) : zero;
+                const bool more = k.vb && s + 1 < kD / 32;
+                const f32x4 n0 = more ? ld4(k.pb + 32 * (s + 1)) : zero, n1 = more ? ld4(k.pb + 32 * (s + 1) + 4) : zero;
                 const float* la = As + r * kXStride + 32 * s + 8 * g;
                 const f32x4 x0 = *reinterpret_cast<const f32x4*>(la), x1 = *reinterpret_cast<const f32x4*>(la + 4);
                 const f32x4 y0 = *reinterpret_cast<const f32x4*>(la + 16 * kXStride), y1 = *reinterpret_cast<const f32x4*>(la + 16 * kXStride + 4);
@@ -224,9 +158,7 @@ __global__ void __launch_bounds__(256) jointsm_cross_kernel(JsmArgs a) {
             float m[4], S[4], T[4];
 #pragma unroll
             for (int v = 0; v < 4; ++v) {
-                const int64_t vrow = slot0 + 16 * t + 4 * g + v, cdoc = vrow >> a.wc_log;
-                const int crow = (int)(vrow & (Wc - 1));
-                valid[v] = vb && cdoc < C && crow < a.c.len[cdoc < C ? cdoc : 0];
+                valid[v] = k.vb && slot_of(a.c, a.wc_log, slot0 + 16 * t + 4 * g + v).valid;
                 m[v] = valid[v] ? dot[v] : -INFINITY;
             }
             pair_block_allreduce(m, Wq, Wc, [](float x, float y) { return fmaxf(x, y); });
@@ -238,27 +170,9 @@ __global__ void __launch_bounds__(256) jointsm_cross_kernel(JsmArgs a) {
             }
             pair_block_allreduce(S, Wq, Wc, [](float x, float y) { return x + y; });
             pair_block_allreduce(T, Wq, Wc, [](float x, float y) { return x + y; });
-            const int vstep = Wc < 4 ? Wc : 4;
-            const bool g_writes = Wc < 8 || (g & (Wc / 4 - 1)) == 0;
-            if ((r & (Wq - 1)) == 0 && qdoc < Q && g_writes) {
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    if (v % vstep) continue;
-                    const int64_t cdoc = (slot0 + 16 * t + 4 * g + v) >> a.wc_log;
-                    if (cdoc >= C) continue;
-                    const bool too_long = qlen > a.q.bound || a.c.len[cdoc] > a.c.bound;     // (the bound, not its row slots)
-                    a.scores[qdoc * C + cdoc] = too_long ? __builtin_nanf("") : 2.0f * (m[v] + T[v] / S[v]);
-                }
-            }
+            write_pair_scores(a, slot0, t, g, r, k, [=](int v) { return 2.0f * (m[v] + T[v] / S[v]); });
         }
     }
-}
-
-int launch_pairs(const JsmArgs& a, int64_t P, hipStream_t s) {
-    ASPIRE_REQUIRE((P + 3) / 4 < ((int64_t)1 << 31), ASPIRE_ERR_UNSUPPORTED, "too many pairs: %lld", (long long)P);
-    hipLaunchKernelGGL(jointsm_pair_kernel, dim3((unsigned)((P + 3) / 4)), dim3(256), 0, s, a, P);
-    ASPIRE_LAUNCH_OK();
-    return ASPIRE_OK;
 }
 
 }  // namespace
@@ -273,29 +187,13 @@ extern "C" int aspire_jointsm_scores_f32(const aspire_repset* q, const aspire_re
                    "pair_softmax needs padded rep sets (ext > 0): its extents are [P, q.ext, c.ext]");
     if (q->n == 0 || c->n == 0) return ASPIRE_OK;
     ASPIRE_REQUIRE(scores, ASPIRE_ERR_INVALID_ARG, "scores is null");
-    JsmArgs a{};
-    a.q = to_dot(q);
-    a.c = to_dot(c);
-    a.scores = scores;
-    a.pair_softmax = pair_softmax;
-    hipStream_t s = (hipStream_t)stream;
-    if (pairing == ASPIRE_PAIR_CROSS && a.q.bound <= 16 && a.c.bound <= 16 && !pair_softmax) {
-        a.mode = kModeCross;
-        a.wq_log = log2_slots(a.q.bound);
-        a.wc_log = log2_slots(a.c.bound);
-        const int64_t blocks = ((c->n << a.wc_log) + kXRows - 1) / kXRows;
-        ASPIRE_REQUIRE(blocks < ((int64_t)1 << 31), ASPIRE_ERR_UNSUPPORTED, "too many candidates: %lld", (long long)c->n);
-        hipLaunchKernelGGL(jointsm_cross_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a);
-        ASPIRE_LAUNCH_OK();
-        return ASPIRE_OK;
-    }
-    a.mode = pairing == ASPIRE_PAIR_CROSS ? kModeCross : kModePaired;
-    return launch_pairs(a, pairing == ASPIRE_PAIR_CROSS ? q->n * c->n : q->n, s);
+    JsmArgs a{pair_args(q, c, pairing, scores), pair_softmax};
+    if (pairing == ASPIRE_PAIR_CROSS && cross_form(a) && !pair_softmax) return launch_cross_slots(jointsm_cross_kernel, a, (hipStream_t)stream);
+    return launch_pair_waves(jointsm_pair_kernel, a, pairing == ASPIRE_PAIR_CROSS ? q->n * c->n : q->n, (hipStream_t)stream);
 }
 
 extern "C" size_t aspire_jointsm_rank_batch_workspace_bytes(const aspire_repset* q, const aspire_repset* c, int64_t max_job, int64_t k) {
-    if (!q || !c || q->n <= 0 || c->n <= 0 || k <= 0) return 0;
-    return aspire_topk_workspace_bytes(q->n, max_job, k);
+    return rank_scratch_only_bytes(q, c, max_job, k);
 }
 
 extern "C" int aspire_jointsm_rank_batch_f32(const aspire_repset* q, const aspire_repset* c, int64_t D, const int32_t* job_off,
@@ -307,18 +205,9 @@ extern "C" int aspire_jointsm_rank_batch_f32(const aspire_repset* q, const aspir
     BatchRank rank{J, max_job, k, top_scores, top_idx, keys, job_off, job_base, stream};
     bool go_on;
     if (int rc = batch_preamble(q, c, scores, rank, go_on); !go_on) return rc;
-    const size_t need = aspire_jointsm_rank_batch_workspace_bytes(q, c, max_job, k);
-    ASPIRE_REQUIRE(workspace_bytes >= need && (need == 0 || workspace), ASPIRE_ERR_INVALID_ARG,
-                   "workspace too small: %zu bytes given, aspire_jointsm_rank_batch_workspace_bytes says %zu", workspace_bytes, need);
-    ASPIRE_REQUIRE(((uintptr_t)workspace & 15) == 0, ASPIRE_ERR_INVALID_ARG, "workspace must be 16-byte aligned");
-    rank.scratch_at(workspace);
-    JsmArgs a{};
-    a.q = to_dot(q);
-    a.c = to_dot(c);
-    a.scores = scores;
-    a.mode = kModeMapped;
-    a.job_off = job_off;
-    a.J = (int32_t)J;
-    if (int rc = launch_pairs(a, C, (hipStream_t)stream)) return rc;
+    if (int rc = place_scratch(rank, workspace, workspace_bytes, rank_scratch_only_bytes(q, c, max_job, k), 0,
+                               "aspire_jointsm_rank_batch_workspace_bytes")) return rc;
+    const JsmArgs a{mapped_pair_args(q, c, job_off, scores), nullptr};
+    if (int rc = launch_pair_waves(jointsm_pair_kernel, a, C, (hipStream_t)stream)) return rc;
     return rank.rank(scores);
 }

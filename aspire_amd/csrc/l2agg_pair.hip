@@ -7,7 +7,7 @@
 //   ATTENTION  score = sum_ij p_ij s_ij,  p = soft-max of s_ij / temp over the valid block
 //
 // One kernel, l2agg_pair_kernel<AGG>: one wave per (candidate, its job's query) pair, four pairs per workgroup, 16 x 16 tiles over
-// documents of 1 .. 128 rows -- jointsm_pair_kernel's frame (kModeMapped) with another tile epilogue.  One form for every call size:
+// documents of 1 .. 128 rows -- pair_fwd.h's one-wave-per-pair frame (kModeMapped) with its own tile epilogue.  One form for every call size:
 // a pair's bits depend on its two documents only.
 //
 // Dot products: dot_tiles.h (exact fp32 on v_mfma_f32_16x16x4_f32) over SIXTEEN accumulators per tile, as jointsm.hip.  What counts
@@ -29,24 +29,20 @@
 // ATTENTION keeps the soft-max shifted by the running maximum m of s (wave-uniform: one wave_max per tile) and sums, beside
 // S = sum e_ij with e_ij = expf((s_ij - m) / temp), the CENTRED T = sum e_ij (s_ij - m): score = m + T / S.  Scores are about -40
 // and their spread a few units: T / S is a small correction to m, so the rounding of the two long sums reaches the score scaled
-// down by that ratio.  A new maximum m' rescales with f = expf((m - m') / temp): S <- f S, T <- f (T + (m - m') S) (jointsm.hip).
+// down by that ratio.  A new maximum m' rescales with f = expf((m - m') / temp): S <- f S, T <- f (T + (m - m') S) (pair_fwd.h: CentredSoftmax).
 // S and T stay per lane until the end, then wave_sum in its fixed order.  TOP2 keeps (first, second) per lane and merges them
 // across the wave by entries; max / min only, so the order of the merge does not reach the bits.
 #include <math.h>
 
 #include "common.h"
 #include "batch_host.h"
-#include "dot_tiles.h"
+#include "pair_fwd.h"
 
 namespace aspire {
 namespace {
 
-struct L2aggArgs {
-    DotSet q, c;
-    const int32_t* job_off;     // [J + 1]
-    int32_t J;
+struct L2aggArgs : PairArgs {
     float temp;                 // ATTENTION
-    float* scores;
 };
 
 // sum_d (x_d - y_d)^2 over the 768 coordinates (rare path: a candidate row that (nearly) equals a query row)
@@ -64,11 +60,7 @@ __device__ __noinline__ float exact_d2(const float* __restrict__ x, const float*
 }
 
 // |row|^2 of the lane's operand row from the four lane groups' chains: the same bits in the four lanes that share lane & 15
-__device__ __forceinline__ float row_norm(const f32x4& n) {
-    float s = (n.x + n.y) + (n.z + n.w);
-    s += lane_xor<16>(s);
-    return s + lane_xor<32>(s);
-}
+__device__ __forceinline__ float row_sumsq(const f32x4& n) { return rowgroup_sum((n.x + n.y) + (n.z + n.w)); }
 
 // (first, second) of the union of two (first, second) pairs, by entries
 __device__ __forceinline__ void top2_merge(float& t1, float& t2, float o1, float o2) {
@@ -85,26 +77,22 @@ __device__ __forceinline__ void top2_fold(float& t1, float& t2) {
 template <int AGG>
 __global__ void __launch_bounds__(256) l2agg_pair_kernel(L2aggArgs a, int64_t P) {
     static_assert(AGG == ASPIRE_AGG_TOP2 || AGG == ASPIRE_AGG_ATTENTION, "the batched siblings; max-sim has its own entry");
-    const int lane = threadIdx.x & 63, g = lane >> 4, r = lane & 15;
-    const int64_t p = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int64_t p = wave_pair();
     if (p >= P) return;
-    const int64_t ci = p, qi = job_of(a.job_off, a.J, p);
-    const int ql = a.q.len[qi], cl = a.c.len[ci];
-    if (ql > a.q.bound || cl > a.c.bound) {
-        if (lane == 0) a.scores[p] = __builtin_nanf("");
-        return;
-    }
-    const float* qdoc = a.q.rows + (int64_t)a.q.start[qi] * kD;
-    const float* cdoc = a.c.rows + (int64_t)a.c.start[ci] * kD;
-    float m = -INFINITY, S = 0.f, T = 0.f;          // ATTENTION
+    const PairWave w = pair_wave(a.q, a.c, kModeMapped, a.job_off, a.J, p);
+    const int lane = w.lane, g = w.g, r = w.r, ql = w.ql, cl = w.cl;
+    if (w.poison) return poison_score(a.scores, p, lane);
+    const float *qdoc = w.qdoc, *cdoc = w.cdoc;
+    CentredSoftmax sm;                               // ATTENTION
+    const auto ex = [temp = a.temp](float y) { return expf(y / temp); };
     float t1 = -INFINITY, t2 = -INFINITY;           // TOP2
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     for (int c0 = 0; c0 < cl; c0 += 16) {
-        const bool va = c0 + r < cl;
-        const float* pa = cdoc + (int64_t)(va ? c0 + r : 0) * kD + 8 * g;
+        const bool va = tile_row_valid(r, c0, cl);
+        const float* pa = tile_row(r, cdoc + 8 * g, c0, cl);
         for (int q0 = 0; q0 < ql; q0 += 16) {
-            const bool vb = q0 + r < ql;
-            const float* pb = qdoc + (int64_t)(vb ? q0 + r : 0) * kD + 8 * g;
+            const bool vb = tile_row_valid(r, q0, ql);
+            const float* pb = tile_row(r, qdoc + 8 * g, q0, ql);
             f32x4 acc[4][4] = {{zero, zero, zero, zero}, {zero, zero, zero, zero}, {zero, zero, zero, zero}, {zero, zero, zero, zero}};
             f32x4 na = zero, nb = zero;
 #pragma unroll 1
@@ -119,16 +107,15 @@ __global__ void __launch_bounds__(256) l2agg_pair_kernel(L2aggArgs a, int64_t P)
                     nb = __builtin_elementwise_fma(b1, b1, __builtin_elementwise_fma(b0, b0, nb));
                 }
             }
-            // C[row 4 g + v][col r]: candidate row c0 + 4 g + v, query row q0 + r
             const f32x4 dot = tile_dots(acc);
-            const float qn = row_norm(nb), cn_own = row_norm(na);
+            const float qn = row_sumsq(nb), cn_own = row_sumsq(na);
             float s[4], cn[4];
             bool valid[4];
 #pragma unroll
             for (int v = 0; v < 4; ++v) cn[v] = __shfl(cn_own, 4 * g + v);          // (every lane: ahead of the divergent redo)
 #pragma unroll
             for (int v = 0; v < 4; ++v) {
-                valid[v] = c0 + 4 * g + v < cl && vb;
+                valid[v] = entry_valid(w, c0, v, vb);
                 const float ns = qn + cn[v];
                 float d2 = fmaf(-2.0f, dot[v], ns);
                 if (valid[v] && d2 < 1e-4f * ns * ns)
@@ -144,23 +131,10 @@ __global__ void __launch_bounds__(256) l2agg_pair_kernel(L2aggArgs a, int64_t P)
 #pragma unroll
                 for (int v = 0; v < 4; ++v)
                     if (valid[v]) tile_max = fmaxf(tile_max, s[v]);
-                tile_max = wave_max(tile_max);
-                if (tile_max > m) {                 // wave-uniform
-                    if (m > -INFINITY) {
-                        const float dm = m - tile_max, f = expf(dm / a.temp);
-                        T = f * fmaf(dm, S, T);
-                        S = f * S;
-                    }
-                    m = tile_max;
-                }
+                sm.raise(wave_max(tile_max), ex);
 #pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    if (valid[v]) {
-                        const float y = s[v] - m, e = expf(y / a.temp);
-                        S += e;
-                        T = fmaf(e, y, T);
-                    }
-                }
+                for (int v = 0; v < 4; ++v)
+                    if (valid[v]) sm.add(s[v], ex);
             }
         }
     }
@@ -173,19 +147,9 @@ __global__ void __launch_bounds__(256) l2agg_pair_kernel(L2aggArgs a, int64_t P)
         top2_fold<32>(t1, t2);
         if (lane == 0) a.scores[p] = t1 + (t2 == -INFINITY ? -10e8f : t2);
     } else {
-        S = wave_sum(S);
-        T = wave_sum(T);
-        if (lane == 0) a.scores[p] = m + T / S;
+        const float S = wave_sum(sm.S), T = wave_sum(sm.T);
+        if (lane == 0) a.scores[p] = sm.m + T / S;
     }
-}
-
-int launch_pairs(const L2aggArgs& a, int agg, int64_t P, hipStream_t s) {
-    ASPIRE_REQUIRE((P + 3) / 4 < ((int64_t)1 << 31), ASPIRE_ERR_UNSUPPORTED, "too many pairs: %lld", (long long)P);
-    const dim3 grid((unsigned)((P + 3) / 4)), block(256);
-    if (agg == ASPIRE_AGG_TOP2) hipLaunchKernelGGL(l2agg_pair_kernel<ASPIRE_AGG_TOP2>, grid, block, 0, s, a, P);
-    else hipLaunchKernelGGL(l2agg_pair_kernel<ASPIRE_AGG_ATTENTION>, grid, block, 0, s, a, P);
-    ASPIRE_LAUNCH_OK();
-    return ASPIRE_OK;
 }
 
 }  // namespace
@@ -194,8 +158,7 @@ int launch_pairs(const L2aggArgs& a, int agg, int64_t P, hipStream_t s) {
 using namespace aspire;
 
 extern "C" size_t aspire_l2agg_rank_batch_workspace_bytes(const aspire_repset* q, const aspire_repset* c, int64_t max_job, int64_t k) {
-    if (!q || !c || q->n <= 0 || c->n <= 0 || k <= 0) return 0;
-    return aspire_topk_workspace_bytes(q->n, max_job, k);
+    return rank_scratch_only_bytes(q, c, max_job, k);
 }
 
 extern "C" int aspire_l2agg_rank_batch_f32(const aspire_repset* q, const aspire_repset* c, int64_t D, const int32_t* job_off,
@@ -221,18 +184,10 @@ extern "C" int aspire_l2agg_rank_batch_f32(const aspire_repset* q, const aspire_
     BatchRank rank{J, max_job, k, top_scores, top_idx, keys, job_off, job_base, stream};
     bool go_on;
     if (int rc = batch_preamble(q, c, scores, rank, go_on); !go_on) return rc;
-    const size_t need = aspire_l2agg_rank_batch_workspace_bytes(q, c, max_job, k);
-    ASPIRE_REQUIRE(workspace_bytes >= need && (need == 0 || workspace), ASPIRE_ERR_INVALID_ARG,
-                   "workspace too small: %zu bytes given, aspire_l2agg_rank_batch_workspace_bytes says %zu", workspace_bytes, need);
-    ASPIRE_REQUIRE(((uintptr_t)workspace & 15) == 0, ASPIRE_ERR_INVALID_ARG, "workspace must be 16-byte aligned");
-    rank.scratch_at(workspace);
-    L2aggArgs a{};
-    a.q = to_dot(q);
-    a.c = to_dot(c);
-    a.job_off = job_off;
-    a.J = (int32_t)J;
-    a.temp = (float)temp;
-    a.scores = scores;
-    if (int rc = launch_pairs(a, agg, C, (hipStream_t)stream)) return rc;
+    if (int rc = place_scratch(rank, workspace, workspace_bytes, rank_scratch_only_bytes(q, c, max_job, k), 0,
+                               "aspire_l2agg_rank_batch_workspace_bytes")) return rc;
+    const L2aggArgs a{mapped_pair_args(q, c, job_off, scores), (float)temp};
+    const auto kernel = agg == ASPIRE_AGG_TOP2 ? l2agg_pair_kernel<ASPIRE_AGG_TOP2> : l2agg_pair_kernel<ASPIRE_AGG_ATTENTION>;
+    if (int rc = launch_pair_waves(kernel, a, C, (hipStream_t)stream)) return rc;
     return rank.rank(scores);
 }

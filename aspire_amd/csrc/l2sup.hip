@@ -39,7 +39,7 @@ __global__ void __launch_bounds__(kPairBwdThreads) l2sup_fwd_kernel(L2SupArgs a,
     const int i = a0 < q_len - 1 ? a0 : q_len - 1, j = a1 < c_len - 1 ? a1 : c_len - 1;
     const Row x = load_row(a.q.rows + ((size_t)a.q.start[p] + i) * kD, lane);
     const Row y = load_row(a.c.rows + ((size_t)a.c.start[p] + j) * kD, lane);
-    float s = -row_norm(diff(x, y));
+    float s = -row_length(diff(x, y));
     if (a.weighted) s = s / (float)(q_len * c_len);
     if (lane == 0) a.scores[p] = s;
 }
@@ -54,7 +54,7 @@ __global__ void __launch_bounds__(kPairBwdThreads) l2sup_bwd_kernel(L2SupArgs a,
     const int ql = f.ql, cl = f.cl;
     const int i = a0 < ql - 1 ? a0 : ql - 1, j = a1 < cl - 1 ? a1 : cl - 1;
     const Row e = diff(load_row(f.qdoc + (size_t)i * kD, lane), load_row(f.cdoc + (size_t)j * kD, lane));
-    const float d = row_norm(e);
+    const float d = row_length(e);
     const float g = a.grad_scores[p];
     const Row unit = scaled(d > 0.f ? 1.0f / d : 0.f, e);          // (q_i - c_j) / d; 0 for coincident rows (torch.cdist's rule)
     Row row_q = scaled(-g, unit), row_c = scaled(g, unit);

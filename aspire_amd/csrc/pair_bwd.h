@@ -53,7 +53,7 @@ __device__ __forceinline__ void add_scaled(Row& acc, float w, const Row& a) {
     acc.z = __builtin_elementwise_fma(ww, a.z, acc.z);
 }
 // ||e|| of a row spread over the wave
-__device__ __forceinline__ float row_norm(const Row& e) {
+__device__ __forceinline__ float row_length(const Row& e) {
     const v4 sq = __builtin_elementwise_fma(e.z, e.z, __builtin_elementwise_fma(e.y, e.y, e.x * e.x));
     return sqrtf(wave_sum((sq.x + sq.y) + (sq.z + sq.w)));
 }

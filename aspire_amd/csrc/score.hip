@@ -619,11 +619,8 @@ int ot_rank_batch(const aspire_repset* q, const aspire_repset* c, int64_t D, con
                    "documents with more than %d sentence rows are not supported (got %d)", generic_max_rows(), max_rows_all);
     const int max_rows = max_rows_all < 8 * kMaxT ? max_rows_all : 8 * kMaxT;
     const BatchLayout L = batch_layout(J, C, max_rows, max_job, k);
-    ASPIRE_REQUIRE(workspace && workspace_bytes >= L.total, ASPIRE_ERR_INVALID_ARG,
-                   "workspace too small: %zu bytes given, aspire_ot_rank_batch_workspace_bytes says %zu", workspace_bytes, L.total);
-    ASPIRE_REQUIRE(((uintptr_t)workspace & 15) == 0, ASPIRE_ERR_INVALID_ARG, "workspace must be 16-byte aligned");
+    if (int rc = place_scratch(rank, workspace, workspace_bytes, L.total, L.topk, "aspire_ot_rank_batch_workspace_bytes")) return rc;
     const BatchTables t = batch_tables(workspace, L);
-    rank.scratch_at(t.topk);
     if (!(stages & kStageRank)) rank.k = 0;      // (a stage mask of the debug entry point without the rank: scores only)
     ScoreArgs a{};
     fill_ot_args(a, q, c, kPairMapped, prm, nullptr, 0, want, scores);
@@ -748,11 +745,8 @@ extern "C" int aspire_l2max_rank_batch_f32(const aspire_repset* q, const aspire_
     ASPIRE_REQUIRE(max_rows <= generic_max_rows(), ASPIRE_ERR_UNSUPPORTED, "documents with more than %d sentence rows are not supported (got %d)",
                    generic_max_rows(), max_rows);
     const BatchLayout L = l2_batch_layout(J, C, max_job, k);
-    ASPIRE_REQUIRE(workspace && workspace_bytes >= L.total, ASPIRE_ERR_INVALID_ARG,
-                   "workspace too small: %zu bytes given, aspire_l2max_rank_batch_workspace_bytes says %zu", workspace_bytes, L.total);
-    ASPIRE_REQUIRE(((uintptr_t)workspace & 15) == 0, ASPIRE_ERR_INVALID_ARG, "workspace must be 16-byte aligned");
+    if (int rc = place_scratch(rank, workspace, workspace_bytes, L.total, L.topk, "aspire_l2max_rank_batch_workspace_bytes")) return rc;
     const BatchTables t = batch_tables(workspace, L);
-    rank.scratch_at(t.topk);
     const bool one_form = (cdist_mode & ASPIRE_CDIST_ONE_FORM) != 0, center = (cdist_mode & ASPIRE_CDIST_CENTER) != 0;
     cdist_mode &= ~(ASPIRE_CDIST_ONE_FORM | ASPIRE_CDIST_CENTER);
     ScoreArgs a{};

@@ -290,3 +290,9 @@ def test_kernel_register_budgets():
     for bn in (32, 64):
         for r in (v for k, v in res.items() if re.search(rf'pair_gram_kernelILi{bn}E', k)):
             assert r['vgpr'] <= 256 and r['scratch'] == 0
+    # the one-wave-per-pair forward kernels: two waves per SIMD.  jointsm_pair_kernel's 164 depends on the form of pair_fwd.h's
+    # tile_row_valid / tile_row (a struct or a bool parameter there gave 176: NOTES.md, "The pair forward kernels' shared frame")
+    jsm = one(r'jointsm_pair_kernel')
+    assert jsm['vgpr'] <= 164 and jsm['vgpr'] + jsm['agpr'] <= 256
+    for r in (v for k, v in res.items() if re.search(r'l2agg_pair_kernel', k)):
+        assert r['vgpr'] <= 180 and r['vgpr'] + r['agpr'] <= 256
