@@ -8,14 +8,16 @@ gradient (geomloss's matmul cost formula); the kernel gets 4 x its largest absol
 summation orders differ from torch's: 4 is margin for that and nothing else), floored at 1e-6; the fp32 restatement's deviation is
 itself asserted to stay below 1e-4.  Rows are 0.3 N(0, 1), pad rows zero.  Measured on the CPU (valid rows):
 
-    case                          CPU fp32 deviation   bound      largest |gradient|
-    (a) 4 pairs, 8 x 8            2.8e-07              1.1e-06    8.0e-02
-    (b) 2 pairs, 40 x 33          1.0e-07              1.0e-06    1.7e-02
-    (c) 1 pair, 128 x 128         1.4e-08              1.0e-06    2.4e-03
-    (d) (a) with coincident rows  2.8e-07              1.1e-06    9.8e-02
-    (f) (a), temp 0.2, blur 0.1   6.2e-07              2.5e-06    2.2e-01
+    case                          CPU fp32 deviation   bound      largest |gradient|   kernel on an MI355X
+    (a) 4 pairs, 8 x 8            2.8e-07              1.1e-06    8.0e-02              4.4e-08
+    (b) 2 pairs, 40 x 33          1.0e-07              1.0e-06    1.7e-02              3.3e-08
+    (c) 1 pair, 128 x 128         1.4e-08              1.0e-06    2.4e-03              5.4e-09
+    (d) (a) with coincident rows  2.8e-07              1.1e-06    9.8e-02              4.0e-08
+    (f) (a), temp 0.2, blur 0.1   6.2e-07              2.5e-06    2.2e-01              1.6e-07
 
-The kernel's own largest error on an MI355X belongs in NOTES.md ("The backward of the OT distance": not measured so far).  The kernel's solve and the forward's
+The kernel's column is one run on an MI355X (NOTES.md, "The backward of the OT distance"; (e), the CSR call, has (a)'s bits: 4.4e-08;
+the own-box call 5.4e-08, the triplet loss 7.6e-08 / 5.3e-08 / 6.3e-08 on query / pos / neg).  Solver settings, row scales, diameter
+groups and the schedule's discontinuities are in tests/test_gpu_ot_backward_edges.py.  The kernel's solve and the forward's
 kernel family differ by rounding; a flip of an arg-max pick j*(i) / i*(j) cannot hide behind the bound: from the reference alone
 (float64, CPU) the best and second-best entry of every row and column differ by more than 1e-4 in every case.
 

@@ -1,7 +1,8 @@
 """CPU: the backward of the otAspire distance without a GPU -- the C-ABI entry (declared, exported, signed), the argument checks of
 aspire_ot_backward_f32 and ops.ot_backward that are decided on the host, the fake kernels of the two new operators, and the
 yardstick of the GPU test: the float64 restatement with geomloss's detach pattern (tests/ot_backward_ref.py) against the closed
-formulas of include/aspire_hip.h."""
+formulas of include/aspire_hip.h -- on its own inputs and on every edge case of tests/ot_backward_cases.py, with the conditions on
+those cases that the reference alone decides."""
 import ctypes
 import os
 import re
@@ -9,6 +10,7 @@ import re
 import pytest
 import torch
 
+import ot_backward_cases as cases
 import ot_backward_ref as ref
 
 FAKE = 16            # a non-null, 16-byte aligned "device pointer" that no call of this file reaches
@@ -146,3 +148,84 @@ def test_float64_restatement_equals_the_closed_formulas():
         w = torch.exp(p['lb'][0, None, :5] + (p['g0'][0, None, :5] - p['c'][0] + p['f'][0, :, None]) / p['eps'])
         v = torch.exp(p['la'][0, :, None] + (p['f0'][0, :, None] - p['c'][0] + p['g'][0, None, :5]) / p['eps'])
         assert (w.sum(1) - 1).abs().max() < 1e-12 and (v.sum(0) - 1).abs().max() < 1e-12
+
+
+# ---- the edge cases of the GPU test (tests/ot_backward_cases.py): everything that the reference alone decides, before any GPU time
+@pytest.mark.parametrize('name', list(cases.CASES))
+def test_edge_case_yardstick_and_closed_formulas(name):
+    """Every edge case: the pick gaps exceed 1e-4 * (noise scale / 0.3) and the fp32 restatement stays within 1e-4 of float64 (both
+    asserted by cases.yardstick), the batch's diameter is more than 1e-5 (relative) from a jump of the schedule length, float64
+    autograd equals the formula sheet to 1e-12 under the case's settings and diameters, pad rows are exact zeros."""
+    inp, yard = cases.inputs(name), cases.yardstick(name)
+    assert yard.gap > 1.0 and yard.dev32 < 1e-4 and yard.tol == max(4.0 * yard.dev32, 1e-6)
+    if inp.group is None:       # the GPU side forms the batch's diameter itself: a few fp32 ulps must not change the schedule
+        assert cases.schedule_clearance(name) > 1e-5, cases.schedule_clearance(name)
+    cx, cy = cases.closed_form(inp)
+    dev = max((yard.gx - cx).abs().max().item(), (yard.gy - cy).abs().max().item())
+    print(f'OTBWD closed formulas vs float64 autograd ({name}): {dev:.3e}')
+    assert dev < 1e-12
+    assert torch.isfinite(yard.gx).all() and torch.isfinite(yard.gy).all() and max(yard.gx.abs().max(), yard.gy.abs().max()) > 1e-3
+    for b, (ql, cl) in enumerate(zip(inp.ql, inp.cl)):
+        assert torch.count_nonzero(yard.gx[b, ql:]) == 0 and torch.count_nonzero(yard.gy[b, cl:]) == 0
+        assert torch.count_nonzero(inp.x[b, ql:]) == 0 and torch.count_nonzero(inp.y[b, cl:]) == 0
+
+
+def test_edge_case_schedules_and_marginals():
+    """What the solver-setting cases are there for, from the reference alone: the schedule lengths (12, 655, 426 steps; 2 where the
+    diameter is below the blur, so that the kernel's n_mid has to clamp at 0), uniform marginals at temp 5000, and marginals that are
+    exactly 0.0 in fp32 on both sides at temp 0.02 over 3.0-scale rows (the -100000 rule of the log-weights) -- with none of them
+    denormal, so that whether a device's expf flushes denormals does not enter."""
+    assert cases.schedule_lengths('scaling0.5') == [12]
+    assert cases.schedule_lengths('scaling0.99') == [655]
+    assert cases.schedule_lengths('blur0.5scaling0.99') == [426]
+    inp = cases.inputs('blur_above_diam')
+    assert cases.schedule_lengths('blur_above_diam') == [2] and cases.orc.max_diameter(inp.x, inp.y) < inp.kw['blur']
+    a, b = cases.fp32_marginals('temp5000')
+    uniform_a = torch.cat([torch.full((n,), 1.0 / n) for n in cases.inputs('temp5000').ql])
+    uniform_b = torch.cat([torch.full((n,), 1.0 / n) for n in cases.inputs('temp5000').cl])
+    assert ((a - uniform_a).abs() < 1e-3 * uniform_a).all() and ((b - uniform_b).abs() < 1e-3 * uniform_b).all()
+    a, b = cases.fp32_marginals('zero_marginal')
+    tiny = torch.finfo(torch.float32).tiny
+    print(f'OTBWD zero marginals: {int((a == 0).sum())} of {a.numel()} in a, {int((b == 0).sum())} of {b.numel()} in b')
+    assert (a == 0).sum() >= 1 and (b == 0).sum() >= 1
+    assert not ((a > 0) & (a < tiny)).any() and not ((b > 0) & (b < tiny)).any()
+
+
+@pytest.mark.parametrize('name', ['groups2', 'groups1'])
+def test_edge_case_diameter_groups_are_told_apart(name):
+    """The diameters of 'groups2' differ by at least 20 % from one another; with one diameter read for every pair the float64
+    gradient leaves the yardstick by more than 10 x the bound, whichever diameter that is -- and in 'groups2' so does every single
+    group under either other group's diameter."""
+    inp, yard = cases.inputs(name), cases.yardstick(name)
+    assert len(inp.diams) == (3 if name == 'groups2' else 5)
+    if name == 'groups2':
+        d = sorted(float(v) for v in inp.diams)
+        assert all(hi >= 1.2 * lo for lo, hi in zip(d, d[1:])), d
+    whole, per_group = cases.wrong_group_margin(name)
+    print(f'OTBWD wrong diameter group ({name}): float64 gradient moves {whole:.3e} (a single group at least {per_group:.3e}), bound {yard.tol:.3e}')
+    assert whole > 10.0 * yard.tol
+    if name == 'groups2':
+        assert per_group > 10.0 * yard.tol
+
+
+def test_edge_case_schedule_steps_are_told_apart():
+    """The 33 diameters straddle at least 6 schedule lengths; across a discontinuity (diameters 2e-7 apart, one step more) the
+    float64 gradient moves by more than 10 x the bound, and the float64 distance by more than twice the 1e-4 that the forward's
+    own tests allow it (tests/test_gpu_edges.py): a forward or a backward one step off cannot pass."""
+    yard = cases.yardstick('schedule')
+    lens = cases.schedule_lengths('schedule')
+    assert len(lens) == 33 and len(set(lens)) >= 6, sorted(set(lens))
+    grad_step, value_step = cases.schedule_step_margin()
+    print(f'OTBWD one schedule step: float64 gradient moves {grad_step:.3e}, bound {yard.tol:.3e}; float64 distance moves {value_step:.3e}')
+    assert grad_step > 10.0 * yard.tol
+    assert value_step > 2.0 * cases.FORWARD_ATOL
+
+
+def test_edge_case_route_settings_are_told_apart():
+    """'route' (blur 0.1, scaling 0.5, temp 0.2): the float64 gradient with all three settings, or any one of them, at its default
+    leaves the yardstick by more than 10 x the bound -- a backward that lost a setting on its way from the forward cannot pass."""
+    yard = cases.yardstick('route')
+    assert set(cases.inputs('route').kw) == set(cases.DEFAULTS)
+    margin = cases.default_settings_margin()
+    print(f'OTBWD a setting at its default (route): float64 gradient moves at least {margin:.3e}, bound {yard.tol:.3e}')
+    assert margin > 10.0 * yard.tol
