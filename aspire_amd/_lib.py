@@ -83,7 +83,11 @@ SIGNATURES = {
                                                c_void_p, c_void_p, c_void_p, c_void_p]),
     'aspire_span_pool_ranges_f32': (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
                                             c_void_p, c_void_p, c_void_p, c_void_p]),
+    'aspire_span_mean_pool_backward_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64,
+                                                   c_void_p, c_void_p]),
     'aspire_cls_l2_f32': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_double, c_void_p, c_void_p]),
+    'aspire_cls_l2_backward_f32': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_double, c_void_p, c_void_p,
+                                           c_void_p, c_void_p]),
     'aspire_bert_planes_bytes': (c_size_t, [ctypes.POINTER(BertWeights)]),
     'aspire_bert_prepare_planes': (c_int, [ctypes.POINTER(BertWeights), c_void_p, c_size_t, c_void_p]),
     'aspire_bert_workspace_bytes': (c_size_t, [ctypes.POINTER(BertWeights), c_int64, c_int64]),

@@ -3,6 +3,8 @@
 // [B, L, 768] mask-multiply-sum pass per sentence slot.  Here every token row is read at most once:
 // one workgroup of 192 threads per (document, sentence slot); thread t owns the float4 at d = 4t, so a
 // token row is a single coalesced 3 KB read; the slot's rows are summed in index order.
+// The read-out's backward (what the reference's rank loss sends back to last_hidden_state): span_mean_pool_backward_kernel and
+// cls_l2_backward_kernel, each beside its forward.
 #include "common.h"
 
 namespace aspire {
@@ -48,6 +50,67 @@ __global__ void __launch_bounds__(192) span_mean_pool_kernel(const float* __rest
     const float cnt = (float)max(hi - lo, 1);
     acc.x /= cnt; acc.y /= cnt; acc.z /= cnt; acc.w /= cnt;
     *reinterpret_cast<float4*>(sent_reps + (size_t)orow * kD + d) = acc;
+}
+
+// The gradient of span_mean_pool_kernel with respect to hidden (aspire_span_mean_pool_backward_f32), as a GATHER: one 192-thread
+// workgroup per (document, tile of kBwdTile token rows) owns its rows of grad_hidden and is their only writer, so there are no atomics
+// and no zero fill in front, and the order of every row's sum is fixed by the walk below, not by the launch.  Thread t owns the
+// float4 at d = 4t of every row of the tile (the file's access pattern); the tile lives in LDS because the row a hit lands on is
+// only known at run time -- each thread reads and writes its own 16 bytes of each row, so the workgroup needs no barrier.
+// The walk: the document's slots in ascending order; a slot's positions 64 at a time, one per lane (every wave of the workgroup walks
+// the same list); the lanes whose position lies inside the tile are a ballot, its bits taken from the lowest up = ascending k, each
+// a wave-uniform branch.  On a slot's first hit the slot's gradient row is loaded and divided by max(count, 1), once.  A position
+// outside [0, L) lies in no tile and is never an address.  The CLS gradient is added last to row 0.  B = 32, L = 256 gives 1024
+// workgroups of 24 KB LDS: four per CU.
+constexpr int kBwdTile = 8;
+
+__global__ void __launch_bounds__(192) span_mean_pool_backward_kernel(const float* __restrict__ grad_sent,
+                                                                      const float* __restrict__ grad_cls, int64_t L, int64_t tiles,
+                                                                      const int32_t* __restrict__ tok_idx,
+                                                                      const int32_t* __restrict__ span_off, int64_t S,
+                                                                      float* __restrict__ grad_hidden) {
+    __shared__ float4 tile[kBwdTile][192];
+    const int64_t b = blockIdx.x / tiles;
+    const int64_t t0 = (blockIdx.x - b * tiles) * kBwdTile;       // the tile: token rows [t0, t0 + rows)
+    const int rows = (int)min((int64_t)kBwdTile, L - t0);
+    const int th = threadIdx.x, lane = threadIdx.x & 63;
+#pragma unroll
+    for (int r = 0; r < kBwdTile; ++r) tile[r][th] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (grad_sent != nullptr) {
+        for (int64_t s = 0; s < S; ++s) {
+            const int lo = span_off[b * S + s], hi = span_off[b * S + s + 1];
+            bool have = false;
+            float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int k0 = lo; k0 < hi; k0 += 64) {
+                const int k = k0 + lane;
+                const int64_t rel = k < hi ? (int64_t)tok_idx[k] - t0 : -1;
+                const bool hit = rel >= 0 && rel < rows;
+                unsigned long long todo = __ballot(hit);
+                while (todo != 0) {
+                    const int src = __ffsll(todo) - 1;
+                    todo &= todo - 1;
+                    const int r = __shfl((int)rel, src);
+                    if (!have) {
+                        have = true;
+                        g = *reinterpret_cast<const float4*>(grad_sent + (size_t)(b * S + s) * kD + th * 4);
+                        const float cnt = (float)max(hi - lo, 1);
+                        g.x /= cnt; g.y /= cnt; g.z /= cnt; g.w /= cnt;
+                    }
+                    float4 a = tile[r][th];
+                    a.x += g.x; a.y += g.y; a.z += g.z; a.w += g.w;
+                    tile[r][th] = a;
+                }
+            }
+        }
+    }
+    if (grad_cls != nullptr && t0 == 0) {
+        const float4 c = *reinterpret_cast<const float4*>(grad_cls + (size_t)b * kD + th * 4);
+        float4 a = tile[0][th];
+        a.x += c.x; a.y += c.y; a.z += c.z; a.w += c.w;
+        tile[0][th] = a;
+    }
+    float* dst = grad_hidden + ((size_t)b * L + (size_t)t0) * kD + th * 4;
+    for (int r = 0; r < rows; ++r) *reinterpret_cast<float4*>(dst + (size_t)r * kD) = tile[r][th];
 }
 
 // Ragged span pooling (aspire_span_pool_ranges_f32): every output row is a RANGE of token rows of one document, so the grid is over
@@ -173,6 +236,34 @@ __global__ void __launch_bounds__(256) cls_l2_kernel(const float* __restrict__ q
     if (lane == 0) out[pair] = sqrtf(acc);
 }
 
+// Its gradient for paired rows (aspire_cls_l2_backward_f32): one wave per pair, the distance formed again exactly as above (the same
+// differences, the same fma chain, the same wave sum), then grad_q = (q - c + eps) * (g / dist), grad_c = -grad_q: torch's rule for
+// the 2-norm, zeros where dist == 0.  Each lane writes the 12 coordinates it read.
+__global__ void __launch_bounds__(256) cls_l2_backward_kernel(const float* __restrict__ q_cls, const float* __restrict__ c_cls, int64_t P,
+                                                              float eps, const float* __restrict__ grad_dist, float* __restrict__ grad_q,
+                                                              float* __restrict__ grad_c) {
+    const int lane = threadIdx.x & 63;
+    const int64_t pair = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (pair >= P) return;
+    const size_t at = (size_t)pair * kD + lane * 4;
+    float4 d[3];
+    float acc = 0.f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float4 u = *reinterpret_cast<const float4*>(q_cls + at + 256 * k), v = *reinterpret_cast<const float4*>(c_cls + at + 256 * k);
+        d[k] = make_float4((u.x - v.x) + eps, (u.y - v.y) + eps, (u.z - v.z) + eps, (u.w - v.w) + eps);
+        acc = fmaf(d[k].w, d[k].w, fmaf(d[k].z, d[k].z, fmaf(d[k].y, d[k].y, fmaf(d[k].x, d[k].x, acc))));
+    }
+    const float dist = sqrtf(wave_sum(acc));
+    const float r = dist > 0.f ? grad_dist[pair] / dist : 0.f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float4 g = make_float4(d[k].x * r, d[k].y * r, d[k].z * r, d[k].w * r);
+        *reinterpret_cast<float4*>(grad_q + at + 256 * k) = g;
+        *reinterpret_cast<float4*>(grad_c + at + 256 * k) = make_float4(-g.x, -g.y, -g.z, -g.w);
+    }
+}
+
 }  // namespace
 }  // namespace aspire
 
@@ -189,6 +280,43 @@ extern "C" int aspire_cls_l2_f32(const float* q_cls, int64_t Q, const float* c_c
     ASPIRE_REQUIRE(q_cls && c_cls && dist, ASPIRE_ERR_INVALID_ARG, "null pointer");
     hipLaunchKernelGGL(cls_l2_kernel, dim3((unsigned)((P + 3) / 4)), dim3(256), 0, (hipStream_t)stream, q_cls, Q, c_cls, C,
                        pairing == ASPIRE_PAIR_PAIRED ? 1 : 0, (float)eps, dist);
+    ASPIRE_LAUNCH_OK();
+    return ASPIRE_OK;
+}
+
+extern "C" int aspire_cls_l2_backward_f32(const float* q_cls, int64_t Q, const float* c_cls, int64_t C, int64_t D, int pairing, double eps,
+                                          const float* grad_dist, float* grad_q, float* grad_c, void* stream) {
+    ASPIRE_REQUIRE(D == kD, ASPIRE_ERR_UNSUPPORTED, "encoding dim %lld unsupported (kernels are built for 768)", (long long)D);
+    ASPIRE_REQUIRE(pairing == ASPIRE_PAIR_CROSS || pairing == ASPIRE_PAIR_PAIRED, ASPIRE_ERR_INVALID_ARG, "bad pairing %d", pairing);
+    ASPIRE_REQUIRE(pairing == ASPIRE_PAIR_PAIRED, ASPIRE_ERR_UNSUPPORTED,
+                   "the backward is built for ASPIRE_PAIR_PAIRED only (ASPIRE_PAIR_CROSS needs an accumulation across pairs)");
+    ASPIRE_REQUIRE(Q >= 0 && Q == C, ASPIRE_ERR_INVALID_ARG, "paired distances need equal batch sizes (query %lld vs cand %lld)",
+                   (long long)Q, (long long)C);
+    if (C == 0) return ASPIRE_OK;
+    ASPIRE_REQUIRE(q_cls && c_cls && grad_dist && grad_q && grad_c, ASPIRE_ERR_INVALID_ARG, "null pointer");
+    ASPIRE_REQUIRE((((uintptr_t)q_cls | (uintptr_t)c_cls | (uintptr_t)grad_q | (uintptr_t)grad_c) & 15) == 0, ASPIRE_ERR_INVALID_ARG,
+                   "the CLS rows and their gradients must be 16-byte aligned");
+    hipLaunchKernelGGL(cls_l2_backward_kernel, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, (hipStream_t)stream, q_cls, c_cls, C,
+                       (float)eps, grad_dist, grad_q, grad_c);
+    ASPIRE_LAUNCH_OK();
+    return ASPIRE_OK;
+}
+
+extern "C" int aspire_span_mean_pool_backward_f32(const float* grad_sent, const float* grad_cls, int64_t B, int64_t L, int64_t D,
+                                                  const int32_t* tok_idx, const int32_t* span_off, int64_t S, float* grad_hidden,
+                                                  void* stream) {
+    ASPIRE_REQUIRE(D == kD, ASPIRE_ERR_UNSUPPORTED, "encoding dim %lld unsupported (kernels are built for 768)", (long long)D);
+    ASPIRE_REQUIRE(B >= 0 && L >= 0 && S > 0, ASPIRE_ERR_INVALID_ARG, "bad shape B=%lld L=%lld S=%lld", (long long)B, (long long)L,
+                   (long long)S);
+    if (B == 0 || L == 0) return ASPIRE_OK;
+    ASPIRE_REQUIRE(grad_hidden && (grad_sent == nullptr || span_off), ASPIRE_ERR_INVALID_ARG, "null pointer");
+    ASPIRE_REQUIRE((((uintptr_t)grad_sent | (uintptr_t)grad_cls | (uintptr_t)grad_hidden) & 15) == 0, ASPIRE_ERR_INVALID_ARG,
+                   "the gradients must be 16-byte aligned");
+    const int64_t tiles = (L + kBwdTile - 1) / kBwdTile;
+    ASPIRE_REQUIRE(B <= 0x7fffffffLL / tiles, ASPIRE_ERR_UNSUPPORTED, "%lld documents of %lld tokens in one call", (long long)B,
+                   (long long)L);
+    hipLaunchKernelGGL(span_mean_pool_backward_kernel, dim3((unsigned)(B * tiles)), dim3(192), 0, (hipStream_t)stream, grad_sent,
+                       grad_cls, L, tiles, tok_idx, span_off, S, grad_hidden);
     ASPIRE_LAUNCH_OK();
     return ASPIRE_OK;
 }

@@ -314,6 +314,39 @@ def cls_l2(q_cls, c_cls, pairing=_lib.PAIR_PAIRED, eps=1e-6):
     return out
 
 
+def cls_l2_backward(q_cls, c_cls, grad, eps=1e-6, out=None):
+    """The gradient of the PAIRED cls_l2 distances (aspire_cls_l2_backward_f32): grad [B] = dLoss / ddist -> (grad_q, grad_c) [B, 768],
+    grad_q = (q - c + eps) * grad / dist with the distance formed again as the forward forms it, grad_c = -grad_q.  out: the two
+    buffers to write into instead of new ones (every row is written)."""
+    _f32(q_cls, 'q_cls')
+    _f32(c_cls, 'c_cls')
+    assert q_cls.dim() == 2 and q_cls.shape == c_cls.shape, 'paired distances need equal batch sizes'
+    grad = _f32(grad, 'grad')
+    assert grad.numel() == q_cls.shape[0], 'grad: one entry per pair'
+    gq, gc = out if out is not None else (torch.empty_like(q_cls), torch.empty_like(c_cls))
+    assert _f32(gq, 'grad_q').shape == q_cls.shape and _f32(gc, 'grad_c').shape == c_cls.shape
+    check(lib.aspire_cls_l2_backward_f32(_ptr(q_cls), q_cls.shape[0], _ptr(c_cls), c_cls.shape[0], q_cls.shape[1], _lib.PAIR_PAIRED,
+                                         float(eps), _ptr(grad), _ptr(gq), _ptr(gc), _stream()))
+    return gq, gc
+
+
+def span_mean_pool_backward(grad_sent, grad_cls, tok_idx, span_off, B, L, max_sents, out=None):
+    """The gradient of span_mean_pool with respect to hidden (aspire_span_mean_pool_backward_f32): grad_sent [B, max_sents, 768] or
+    None, grad_cls [B, 768] or None (None: that output took no part in the loss) -> grad_hidden [B, L, 768] on the GPU, every element
+    written by the kernel (tokens of no span: exact zeros).  out: the buffer to write into instead of a new one."""
+    _i32(span_off, 'span_off')
+    assert span_off.numel() == B * max_sents + 1, 'span_off: one entry per (document, slot) and the end'
+    if grad_sent is not None:
+        assert _f32(grad_sent, 'grad_sent').shape == (B, max_sents, D)
+    if grad_cls is not None:
+        assert _f32(grad_cls, 'grad_cls').shape == (B, D)
+    grad_hidden = out if out is not None else torch.empty(B, L, D, device=span_off.device, dtype=torch.float32)
+    assert _f32(grad_hidden, 'grad_hidden').shape == (B, L, D)
+    check(lib.aspire_span_mean_pool_backward_f32(_ptr(grad_sent), _ptr(grad_cls), B, L, D, _ptr(_i32(tok_idx, 'tok_idx')), _ptr(span_off),
+                                                 max_sents, _ptr(grad_hidden), _stream()))
+    return grad_hidden
+
+
 def bert_pooler(cls, weight, bias):
     """HF BertPooler on CLS rows (aspire_bert_pooler_f32): tanh(cls @ weight.T + bias), cls [B, 768], weight [768, 768] (nn.Linear
     layout), bias [768] -> [B, 768] on the GPU."""

@@ -33,6 +33,11 @@ implementation so that shapes propagate under FakeTensor / torch.compile tracing
     torch.ops.aspire.l2sup_pair_scores(q, q_lens, c, c_lens, align, weighted) -> scores [B]        pair_distances.py:189-292
                                          (autograd registered; align int32 [B, 2]: the pre-aligned (query row, candidate row))
     torch.ops.aspire.l2sup_pair_backward(grad_scores, q, q_lens, c, c_lens, align, weighted) -> (grad_q, grad_c)
+  the read-out under autograd (span_mean_pool above has its autograd registered: the gradient with respect to hidden):
+    torch.ops.aspire.span_mean_pool_backward(grad_sent | None, grad_cls | None, tok_idx, span_off, B, L, max_sents) -> grad_hidden [B, L, 768]
+    torch.ops.aspire.cls_l2_pair(q_cls, c_cls, eps) -> dist [B]                                    disent_models.py:582, :634
+                                         (autograd registered; F.pairwise_distance on paired CLS rows, the bits of ops.cls_l2)
+    torch.ops.aspire.cls_l2_pair_backward(grad, q_cls, c_cls, eps) -> (grad_q, grad_c)
   resident CSR pools (rows + start + len, struct aspire_repset):
     torch.ops.aspire.l2max_scores_csr / ot_scores_csr(q_rows, q_start, q_len, q_max, c_rows, c_start, c_len, c_max, ...) -> [Q * C]
     torch.ops.aspire.ot_rank_batch(q_rows, q_start, q_len, q_max, c_rows, c_start, c_len, c_max, job_off, max_job, k, ...)
@@ -45,7 +50,7 @@ Padded inputs are [n, S, 768] fp32 with int32 lens [n] (the reference's RepLen a
 ``paired`` False scores every query against every candidate ([Q * C], query-major), True scores pair p (Q == C).
 """
 import ctypes
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -80,6 +85,35 @@ def span_mean_pool(hidden: Tensor, tok_idx: Tensor, span_off: Tensor, max_sents:
 def _(hidden, tok_idx, span_off, max_sents):
     b, _, d = hidden.shape
     return hidden.new_empty(b, d), hidden.new_empty(b, max_sents, d)
+
+
+# its gradient with respect to hidden (aspire_span_mean_pool_backward_f32); a gradient that is None is passed as NULL: that output
+# took no part in the loss
+@torch.library.custom_op('aspire::span_mean_pool_backward', mutates_args=(), device_types='cuda')
+def span_mean_pool_backward(grad_sent: Optional[Tensor], grad_cls: Optional[Tensor], tok_idx: Tensor, span_off: Tensor, B: int, L: int,
+                            max_sents: int) -> Tensor:
+    grad_sent, grad_cls = (None if g is None else g.to(torch.float32).contiguous() for g in (grad_sent, grad_cls))
+    return ops.span_mean_pool_backward(grad_sent, grad_cls, tok_idx, span_off, B, L, max_sents)
+
+
+@span_mean_pool_backward.register_fake
+def _(grad_sent, grad_cls, tok_idx, span_off, B, L, max_sents):
+    return span_off.new_empty(B, L, _D, dtype=torch.float32)
+
+
+def _span_mean_pool_setup(ctx, inputs, output):
+    hidden, tok_idx, span_off, max_sents = inputs
+    ctx.save_for_backward(tok_idx, span_off)
+    ctx.dims = (hidden.shape[0], hidden.shape[1], max_sents)
+    ctx.set_materialize_grads(False)        # an output the loss does not read arrives as None, not as a block of zeros
+
+
+def _span_mean_pool_grad(ctx, grad_cls, grad_sent):
+    tok_idx, span_off = ctx.saved_tensors
+    return torch.ops.aspire.span_mean_pool_backward(grad_sent, grad_cls, tok_idx, span_off, *ctx.dims), None, None, None
+
+
+span_mean_pool.register_autograd(_span_mean_pool_grad, setup_context=_span_mean_pool_setup)
 
 
 # ragged span pooling (aspire_span_pool_ranges_f32): row r = mean of hidden[row_doc[r], row_start[r] : row_start[r] + row_len[r]]
@@ -437,6 +471,43 @@ def l2sup_pair_backward(grad_scores: Tensor, q: Tensor, q_lens: Tensor, c: Tenso
 _register_pair_autograd(l2sup_pair_scores, l2sup_pair_backward)
 
 
+# The document-level distance of the rank loss's abstract term: functional.pairwise_distance(q_cls, c_cls, p=2, eps) on paired CLS rows
+# [B, 768] -> [B], the bits of ops.cls_l2; the backward aspire_cls_l2_backward_f32.  (Two row matrices and no lens: not the shape
+# _register_pair_autograd serves.)
+@torch.library.custom_op('aspire::cls_l2_pair', mutates_args=(), device_types='cuda')
+def cls_l2_pair(q_cls: Tensor, c_cls: Tensor, eps: float) -> Tensor:
+    return ops.cls_l2(q_cls.contiguous(), c_cls.contiguous(), pairing=_lib.PAIR_PAIRED, eps=eps)
+
+
+@torch.library.custom_op('aspire::cls_l2_pair_backward', mutates_args=(), device_types='cuda')
+def cls_l2_pair_backward(grad: Tensor, q_cls: Tensor, c_cls: Tensor, eps: float) -> Tuple[Tensor, Tensor]:
+    return ops.cls_l2_backward(q_cls.contiguous(), c_cls.contiguous(), grad.to(torch.float32).contiguous(), eps=eps)
+
+
+@cls_l2_pair.register_fake
+def _(q_cls, c_cls, eps):
+    return q_cls.new_empty(_npairs(q_cls.shape[0], c_cls.shape[0], True))
+
+
+@cls_l2_pair_backward.register_fake
+def _(grad, q_cls, c_cls, eps):
+    return q_cls.new_empty(q_cls.shape), c_cls.new_empty(c_cls.shape)
+
+
+def _cls_l2_pair_setup(ctx, inputs, output):
+    q_cls, c_cls, ctx.eps = inputs
+    ctx.save_for_backward(q_cls, c_cls)
+
+
+def _cls_l2_pair_grad(ctx, grad):
+    gq, gc = torch.ops.aspire.cls_l2_pair_backward(grad, *ctx.saved_tensors, ctx.eps)
+    return gq, gc, None
+
+
+cls_l2_pair.register_autograd(_cls_l2_pair_grad, setup_context=_cls_l2_pair_setup)
+
+
 OPS = ('span_mean_pool', 'span_pool_ranges', 'bert_encoder_forward', 'bert_cls_forward', 'bert_pooler', 'token_mean_pool', 'l2max_scores', 'jointsm_scores', 'ot_sinkhorn_scores', 'topk_desc', 'topk_keys', 'topk_merge',
        'l2max_scores_csr', 'ot_scores_csr', 'ot_rank_batch', 'dense_rank_batch', 'l2agg_pair_scores', 'l2agg_pair_backward',
-       'ot_pair_scores', 'ot_pair_backward', 'jointsm_pair_scores', 'jointsm_pair_backward', 'l2sup_pair_scores', 'l2sup_pair_backward')
+       'ot_pair_scores', 'ot_pair_backward', 'jointsm_pair_scores', 'jointsm_pair_backward', 'l2sup_pair_scores', 'l2sup_pair_backward',
+       'span_mean_pool_backward', 'cls_l2_pair', 'cls_l2_pair_backward')

@@ -83,6 +83,23 @@ int aspire_span_mean_pool_rows_f32(const float* hidden, int64_t B, int64_t L, in
 int aspire_span_pool_ranges_f32(const float* hidden, int64_t B, int64_t L, int64_t D,
                                 const int32_t* row_doc, const int32_t* row_start, const int32_t* row_len, int64_t R,
                                 const int32_t* out_row, float* rows, float* cls_reps, void* stream);
+/* The gradient of aspire_span_mean_pool_f32 with respect to `hidden` (the read-out of the reference's training step,
+ * disent_models.py:487-535 under autograd): what reaches last_hidden_state from the sentence rows and the CLS rows.
+ *   grad_sent   [B, S, D] or NULL  dLoss / dsent_reps       grad_cls  [B, D] or NULL  dLoss / dcls_reps     (NULL: the term is absent)
+ *   tok_idx, span_off, S           the forward's
+ *   grad_hidden [B, L, D]  out:  grad_hidden[b, t, :] = the sum, over the slots s of document b in ascending order and within a slot
+ *               over its positions k in ascending order with tok_idx[k] == t, of grad_sent[b, s, :] / max(count_s, 1) (a division,
+ *               formed once per slot, as torch's autograd of sum / count); then, last, + grad_cls[b, :] when t == 0.
+ * Every element of grad_hidden is written exactly once, tokens of no span (pads, the title, [SEP]) with exact zeros; with both
+ * gradients NULL all of it is zeros.  Any index list the forward takes: a position listed twice in a slot counts twice, a position of
+ * two slots gets both terms, position 0 may sit in a span beside grad_cls; an index outside [0, L) contributes nothing and is never
+ * used as an address.  The kernel is a gather (a tile of token rows looks for its slots; one writer per row): no atomics, no zero
+ * fill in front, the same bits on every run and for every launch geometry.
+ * D != 768 -> ASPIRE_ERR_UNSUPPORTED; B < 0, L < 0, S <= 0, grad_hidden NULL, span_off NULL beside grad_sent, or a gradient pointer
+ * not 16-byte aligned -> ASPIRE_ERR_INVALID_ARG; B == 0 or L == 0 -> ASPIRE_OK without a launch.  All of it before any launch. */
+int aspire_span_mean_pool_backward_f32(const float* grad_sent /* [B,S,D] or NULL */, const float* grad_cls /* [B,D] or NULL */,
+                                       int64_t B, int64_t L, int64_t D, const int32_t* tok_idx, const int32_t* span_off, int64_t S,
+                                       float* grad_hidden /* [B,L,D] out */, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * A1  BERT-base encoder forward.  Replaces `self.bert_encoder(tokid_tt, token_type_ids=seg_tt,
@@ -230,6 +247,14 @@ int aspire_token_mean_pool_f32(const float* hidden, const int64_t* attn_mask, in
  * ------------------------------------------------------------------------------------------- */
 int aspire_cls_l2_f32(const float* q_cls, int64_t Q, const float* c_cls, int64_t C, int64_t D, int pairing, double eps,
                       float* dist, void* stream);
+/* Its gradient for ASPIRE_PAIR_PAIRED (the abstract term of the reference's rank loss, nn.TripletMarginLoss(p=2) over the CLS rows,
+ * disent_models.py:582, :634): dist_p is formed again with the forward's arithmetic, then
+ *   grad_q[p, :] = (q[p] - c[p] + eps) * (grad_dist[p] / dist_p)      grad_c[p, :] = -grad_q[p, :]      (zeros where dist_p == 0)
+ * one wave per pair, every output row written once.  ASPIRE_PAIR_CROSS -> ASPIRE_ERR_UNSUPPORTED (a row would need an
+ * accumulation across pairs); D != 768 -> ASPIRE_ERR_UNSUPPORTED; Q != C or a NULL pointer with pairs to do ->
+ * ASPIRE_ERR_INVALID_ARG; no pairs -> ASPIRE_OK without a launch. */
+int aspire_cls_l2_backward_f32(const float* q_cls, int64_t Q, const float* c_cls, int64_t C, int64_t D, int pairing, double eps,
+                               const float* grad_dist, float* grad_q, float* grad_c, void* stream);
 
 /* cdist formula selection, mirroring torch.cdist's default compute mode (used at
  * pair_distances.py:49 and :167): rows <= 25 on both sides -> direct sqrt(sum (x-y)^2),
