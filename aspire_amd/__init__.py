@@ -9,6 +9,7 @@ from .batch_prep import prepare_abstracts, prepare_bert_sentences  # noqa: F401
 from .pair_distances import (AllPairMaskedWasserstein, AllPairMaskedAttention, allpair_masked_dist_l2max,  # noqa: F401
                              allpair_masked_dist_l2topk, allpair_joint_sm_negscore, rep_len_tup)
 from .rank_loss import RankLoss, sent_reps_from_hidden  # noqa: F401
+from .train_encoder import HipBertTrainEncoder  # noqa: F401
 from .consent import AspireConSent  # noqa: F401
 from .contextner import AspireConSenContextual, AspireContextNER, AspireNER  # noqa: F401
 from .polyenc import WordSentAlignPolyEnc, TrainedScoringModel  # noqa: F401

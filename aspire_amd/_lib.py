@@ -63,6 +63,16 @@ class BertWeights(ctypes.Structure):
                 ('max_pos', c_int32), ('n_types', c_int32), ('ln_eps', ctypes.c_float), ('planes', c_void_p)]
 
 
+class BertLayerGrads(ctypes.Structure):
+    """struct aspire_bert_layer_grads"""
+    _fields_ = list(BertLayer._fields_)
+
+
+class BertGrads(ctypes.Structure):
+    """struct aspire_bert_grads"""
+    _fields_ = [('emb_ln_g', c_void_p), ('emb_ln_b', c_void_p), ('layers', ctypes.POINTER(BertLayerGrads))]
+
+
 class BertExtras(ctypes.Structure):
     """struct aspire_bert_extras"""
     _fields_ = [('pos_ids', c_void_p), ('rel_bias', c_void_p), ('rel_span', c_int32)]
@@ -95,6 +105,12 @@ SIGNATURES = {
                                         c_void_p, c_void_p, c_size_t, c_void_p]),
     'aspire_bert_forward_var_f32': (c_int, [ctypes.POINTER(BertWeights), ctypes.POINTER(BertExtras), c_void_p, c_void_p, c_void_p,
                                             c_int64, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'aspire_bert_tape_bytes': (c_size_t, [ctypes.POINTER(BertWeights), c_int64, c_int64]),
+    'aspire_bert_train_workspace_bytes': (c_size_t, [ctypes.POINTER(BertWeights), c_int64, c_int64]),
+    'aspire_bert_layers_forward_train_f32': (c_int, [ctypes.POINTER(BertWeights), c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
+                                                     c_size_t, c_void_p, c_size_t, c_void_p]),
+    'aspire_bert_layers_backward_f32': (c_int, [ctypes.POINTER(BertWeights), c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_size_t,
+                                                c_void_p, ctypes.POINTER(BertGrads), c_void_p, c_size_t, c_void_p]),
     'aspire_token_mean_pool_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p]),
     'aspire_bert_status': (c_int, [ctypes.POINTER(ctypes.c_int32), c_void_p]),
     'aspire_bert_cls_workspace_bytes': (c_size_t, [ctypes.POINTER(BertWeights), c_int64, c_int64]),

@@ -9,14 +9,20 @@
 //                            conflict-free ds_read_b32, register-staged double buffering.
 //   gemm_bf16x3_kernel       the same for nn.Linear shapes on the bf16 matrix pipe: three bf16 planes per operand, split when a tile is
 //                            staged, six products per term
-// Launch rule: launch_gemm (tile and form by shape and the ASPIRE_HIP_GEMM / ASPIRE_HIP_GEMM_TILE pins).
+//                            A_KM: the TN form, C[M, N] = sum_r A[r, M] . B[r, N] -- both operands row-major with the contraction over
+//                            their rows (the encoder backward's dW = dY^T . X, dV = P^T . dO, dK = dS^T . Q); new instantiations of the
+//                            same kernel, the existing ones compile to the code they had
+// Launch rules: launch_gemm (tile and form by shape and the ASPIRE_HIP_GEMM / ASPIRE_HIP_GEMM_TILE pins), launch_gemm_tn.
 #include "enc_types.h"
 #include "tuning.h"
 
 namespace aspire {
 namespace {
 
-template <int BM, int BN, int kBK, bool B_KN, int WAVES_N = 2>
+// A_KM (the TN form, launch_gemm_tn): A is [K, M] m-contiguous as well -- C[M, N] = sum_r A[r, M] . B[r, N], both operands row-major with
+// the contraction over their rows (dW = dY^T . X, dV = P^T . dO, dK = dS^T . Q).  A row of either operand IS a row of its k-major LDS
+// tile: float4 loads along m / n, float4 LDS stores, no transposing scatter -- B_KN's staging on both sides.
+template <int BM, int BN, int kBK, bool B_KN, int WAVES_N = 2, bool A_KM = false>
 __global__ void __launch_bounds__(256) gemm_f32_kernel(GemmArgs g) {
     constexpr int LDA = BM + 4, LDB = BN + 4;  // k-major LDS rows; +4 keeps float4 alignment and staggers banks
     constexpr int WAVES_M = 4 / WAVES_N;
@@ -53,10 +59,18 @@ __global__ void __launch_bounds__(256) gemm_f32_kernel(GemmArgs g) {
     auto load_tiles = [&](int k0) {
 #pragma unroll
         for (int p = 0; p < A_F4; ++p) {
-            const int idx = tid + 256 * p, row = idx / (kBK / 4), k4 = idx % (kBK / 4);
-            const int m = m0 + row, k = k0 + 4 * k4;
-            ra[p] = (m < g.M && k < g.K) ? *reinterpret_cast<const float4*>(A + (size_t)m * g.lda + k)
-                                         : make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (A_KM) {
+                constexpr int M4 = BM / 4;
+                const int idx = tid + 256 * p, kr = idx / M4, m4 = idx % M4;
+                const int k = k0 + kr, m = m0 + 4 * m4;
+                ra[p] = (k < g.K && m < g.M) ? *reinterpret_cast<const float4*>(A + (size_t)k * g.lda + m)
+                                             : make_float4(0.f, 0.f, 0.f, 0.f);
+            } else {
+                const int idx = tid + 256 * p, row = idx / (kBK / 4), k4 = idx % (kBK / 4);
+                const int m = m0 + row, k = k0 + 4 * k4;
+                ra[p] = (m < g.M && k < g.K) ? *reinterpret_cast<const float4*>(A + (size_t)m * g.lda + k)
+                                             : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
         }
 #pragma unroll
         for (int p = 0; p < B_F4; ++p) {
@@ -78,11 +92,17 @@ __global__ void __launch_bounds__(256) gemm_f32_kernel(GemmArgs g) {
     auto store_tiles = [&](int buf) {
 #pragma unroll
         for (int p = 0; p < A_F4; ++p) {
-            const int idx = tid + 256 * p, row = idx / (kBK / 4), k4 = idx % (kBK / 4);
-            As[buf][4 * k4 + 0][row] = ra[p].x;
-            As[buf][4 * k4 + 1][row] = ra[p].y;
-            As[buf][4 * k4 + 2][row] = ra[p].z;
-            As[buf][4 * k4 + 3][row] = ra[p].w;
+            if constexpr (A_KM) {
+                constexpr int M4 = BM / 4;
+                const int idx = tid + 256 * p, kr = idx / M4, m4 = idx % M4;
+                *reinterpret_cast<float4*>(&As[buf][kr][4 * m4]) = ra[p];
+            } else {
+                const int idx = tid + 256 * p, row = idx / (kBK / 4), k4 = idx % (kBK / 4);
+                As[buf][4 * k4 + 0][row] = ra[p].x;
+                As[buf][4 * k4 + 1][row] = ra[p].y;
+                As[buf][4 * k4 + 2][row] = ra[p].z;
+                As[buf][4 * k4 + 3][row] = ra[p].w;
+            }
         }
 #pragma unroll
         for (int p = 0; p < B_F4; ++p) {
@@ -386,6 +406,22 @@ int launch_gemm_bkn(const GemmArgs& g, int batch, hipStream_t st) {
 
 int launch_gemm(const GemmArgs& g, int batch, bool b_kn, hipStream_t st) {
     return b_kn ? launch_gemm_bkn<true>(g, batch, st) : launch_gemm_bkn<false>(g, batch, st);
+}
+
+// The TN form (the encoder backward's weight gradients and dV / dK): A [K, M] and B [K, N], both row-major, M and N multiples of 4
+// (float4 along m / n).  Tiles by the same rule as the fp32 forms above.
+int launch_gemm_tn(const GemmArgs& g, int batch, hipStream_t st) {
+    const long long b128 = (long long)((g.M + 127) / 128) * ((g.N + 127) / 128) * batch;
+    const long long b12864 = (long long)((g.M + 127) / 128) * ((g.N + 63) / 64) * batch;
+    if (b128 >= 512 && g.N >= 128) {
+        hipLaunchKernelGGL((gemm_f32_kernel<128, 128, 16, true, 2, true>), dim3((g.N + 127) / 128, (g.M + 127) / 128, batch), dim3(256), 0, st, g);
+    } else if (b12864 >= 512) {
+        hipLaunchKernelGGL((gemm_f32_kernel<128, 64, 16, true, 2, true>), dim3((g.N + 63) / 64, (g.M + 127) / 128, batch), dim3(256), 0, st, g);
+    } else {
+        hipLaunchKernelGGL((gemm_f32_kernel<64, 64, 16, true, 2, true>), dim3((g.N + 63) / 64, (g.M + 63) / 64, batch), dim3(256), 0, st, g);
+    }
+    ASPIRE_LAUNCH_OK();
+    return ASPIRE_OK;
 }
 
 }  // namespace aspire

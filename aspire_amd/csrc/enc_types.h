@@ -72,6 +72,9 @@ __device__ __forceinline__ float gelu_erf(float x) {
 
 // enc_gemm.hip: C = alpha A.B^T (+bias)(+GELU)(+residual) on fp32 operands, batched; b_kn: B is [K, N] n-contiguous (V of attention)
 int launch_gemm(const GemmArgs& g, int batch, bool b_kn, hipStream_t st);
+// the TN form on the fp32-input matrix cores: C[M, N] = alpha sum_r A[r, M] . B[r, N] (+ the same epilogues); g.A is [batch][K][lda],
+// g.B [batch][K][ldb], both row-major with the contraction over their rows; M, N, lda, ldb multiples of 4 (encoder_bwd.hip)
+int launch_gemm_tn(const GemmArgs& g, int batch, hipStream_t st);
 
 // enc_gemm_p.hip: the GEMMs on pre-split fp16 planes (enc_planes.h) and the split of an fp32 matrix into them (weight: the B side,
 // scaled by kPWeightScale; too_big: optional device flag).  swap: the GELU -> P-layout epilogue.  The unit also owns the encoder's
@@ -102,6 +105,23 @@ int launch_embed_layernorm(const int64_t* tok, const int64_t* typ, const int64_t
                            void* yp, hipStream_t st);
 int launch_cls_tap(const float* x, const void* xp, int64_t rows, int64_t L, int64_t B, float wt, int mode, float* cls_out, float* layer_cls,
                    float* gather, hipStream_t st);
+
+// enc_bwd.hip: the row kernels of the encoder's backward (encoder_bwd.hip runs them).  No atomics: every output element has one writer,
+// column sums go through per-row-block partials (`partial`) and a fixed-order second stage.
+//   gelu_forward:        a = GELU(u), n elements (the training forward's own GELU pass: the pre-GELU value stays on the tape)
+//   gelu_backward:       du = dy . GELU'(u), n elements; du may be dy
+//   softmax_backward:    ds[row][j] = scale . p[row][j] (dp[row][j] - sum_j dp p), j < L; zeros in [L, ld); in place (ds = dp)
+//   layernorm_backward:  x the saved pre-norm rows; dy (+ dy_res when not NULL) the gradient of the LayerNorm's output; dx out;
+//                        dgamma / dbeta [768] out through partial (layernorm_backward_partial_floats(rows))
+//   colsum:              out[n] = sum_m x[m][n], x [rows, N] contiguous, through partial (colsum_partial_floats(rows, N))
+int launch_gelu_forward(const float* u, float* a, int64_t n, hipStream_t st);
+int launch_gelu_backward(const float* dy, const float* u, float* du, int64_t n, hipStream_t st);
+int launch_softmax_backward(float* dp, const float* p, int64_t rows, int L, int ld, float scale, hipStream_t st);
+size_t layernorm_backward_partial_floats(int64_t rows);
+int launch_layernorm_backward(const float* x, const float* gamma, float eps, const float* dy, const float* dy_res, float* dx, float* dgamma,
+                              float* dbeta, int64_t rows, float* partial, hipStream_t st);
+size_t colsum_partial_floats(int64_t rows, int N);
+int launch_colsum(const float* x, int64_t rows, int N, float* out, float* partial, hipStream_t st);
 
 // enc_pooler.hip: pooled = tanh(cls . w_pool^T + b_pool) on [B, 768] rows (HF BertPooler)
 int launch_pooler(const float* cls, int64_t B, const float* w_pool, const float* b_pool, float* pooled, hipStream_t st);

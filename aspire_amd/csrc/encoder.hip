@@ -29,6 +29,8 @@
 //   enc_rows.hip     layernorm_kernel, embed_layernorm_kernel, cls_tap_kernel                                launch_layernorm, launch_embed_layernorm, launch_cls_tap
 //   enc_pooler.hip   bert_pooler_kernel: tanh(cls . W^T + b) behind the CLS forward (aspire_bert_pooler_f32)   launch_pooler
 //   enc_planes.h     the fp16-plane layout: constants and device helpers
+// The layer stack under training (the tape-keeping forward over this file's fp32-operand launches, and the backward) has a host file of
+// its own, encoder_bwd.hip, with its row kernels in enc_bwd.hip and the TN GEMM form in enc_gemm.hip (launch_gemm_tn).
 #include <math.h>
 
 #include "enc_planes.h"

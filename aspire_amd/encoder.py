@@ -80,6 +80,26 @@ def pack_weights(weights, n_heads, ln_eps):
     return bw
 
 
+def pack_layer_stack(weights, n_heads, ln_eps):
+    """struct aspire_bert_weights of the training entry points (aspire_bert_layers_forward_train_f32 / _backward_f32), which start behind
+    the embedding lookup: fp32 GPU tensors [emb_ln_g, emb_ln_b] + the twelve per layer in pack_weights' order; the three tables stay
+    NULL.  The struct keeps the (contiguous) tensors and its layer array alive."""
+    assert (len(weights) - 2) % 12 == 0 and len(weights) >= 2, 'weights: emb_ln_g, emb_ln_b + 12 per layer'
+    w = [t.contiguous() for t in weights]
+    assert all(t.is_cuda and t.dtype == torch.float32 for t in w)
+    n_layers = (len(w) - 2) // 12
+    layers = (BertLayer * max(n_layers, 1))()
+    for i in range(n_layers):
+        for (f, _), t in zip(BertLayer._fields_, w[2 + 12 * i:14 + 12 * i]):
+            setattr(layers[i], f, ctypes.c_void_p(t.data_ptr()))
+    hidden_size = w[0].shape[0]
+    ffn = w[2 + 6].shape[0] if n_layers else 4 * hidden_size
+    bw = BertWeights(None, None, None, ctypes.c_void_p(w[0].data_ptr()), ctypes.c_void_p(w[1].data_ptr()), layers, n_layers, n_heads,
+                     hidden_size, ffn, 0, 0, 0, float(ln_eps), None)
+    bw._keep = (layers, w)
+    return bw
+
+
 def run_checked(run, outputs_finite, who, status):
     """The encoder's fall-back rule around run() (a forward and whatever reads it out), each re-run at most once, in this order:
       * status() non-zero: a LayerNorm-epilogue GEMM gave up waiting for its row block (enc_gemm_p.hip: gemm_p_ln_kernel's bounded

@@ -6,9 +6,12 @@ WordSentAbsAlignBiEnc.forward_rank (disent_models.py:587-660), differentiable do
         -> dist_function of aspire_amd.pair_distances over (query, positive) and (query, negative)    (backward: their HIP kernels)
         -> clamp_min(d(q, p) - d(q, n) + 1, 0).sum()        [+ the same hinge over torch.ops.aspire.cls_l2_pair of the CLS rows]
 
-The hinge and the sum are torch ops on [B] tensors.  The encoder's own backward is whatever the caller's encoder brings (torch's, for
-a HuggingFace model): no encoder backward, optimizer, batcher or DDP is built here.  Not built either: the `sentsup` term of
-WordSentAbsSupAlignBiEnc, the two L1 regularisers (cd_l1_prop, cd_svalue_l1_prop), double backward.
+The hinge and the sum are torch ops on [B] tensors.  The encoder's own backward is whatever the caller's encoder brings: with
+aspire_amd.HipBertTrainEncoder(bert_model) as the `encoder` argument (an instance takes the reference's batch dict as it stands) the
+twelve layers and the embedding LayerNorm run forward and backward on this project's kernels (encoder_bwd.hip) and only the embedding
+table lookup is torch's; a HuggingFace model called under torch autograd brings torch's.  No dropout, optimizer, batcher or DDP is built
+here.  Not built either: the `sentsup` term of WordSentAbsSupAlignBiEnc, the two L1 regularisers (cd_l1_prop, cd_svalue_l1_prop), double
+backward.
 """
 import torch
 

@@ -38,6 +38,10 @@ implementation so that shapes propagate under FakeTensor / torch.compile tracing
     torch.ops.aspire.cls_l2_pair(q_cls, c_cls, eps) -> dist [B]                                    disent_models.py:582, :634
                                          (autograd registered; F.pairwise_distance on paired CLS rows, the bits of ops.cls_l2)
     torch.ops.aspire.cls_l2_pair_backward(grad, q_cls, c_cls, eps) -> (grad_q, grad_c)
+  the encoder under autograd (behind the embedding lookup; weights = [emb_ln_g, emb_ln_b] + the twelve tensors per layer below):
+    torch.ops.aspire.bert_layers_train(emb_sum, mask, weights, n_heads, ln_eps) -> (hidden [B, L, 768], tape uint8)      A1t
+                                         (autograd registered: the gradient with respect to emb_sum and every tensor of weights)
+    torch.ops.aspire.bert_layers_backward(grad_hidden, tape, mask, weights, n_heads, ln_eps) -> (grad_emb_sum, grads)    its formula
   resident CSR pools (rows + start + len, struct aspire_repset):
     torch.ops.aspire.l2max_scores_csr / ot_scores_csr(q_rows, q_start, q_len, q_max, c_rows, c_start, c_len, c_max, ...) -> [Q * C]
     torch.ops.aspire.ot_rank_batch(q_rows, q_start, q_len, q_max, c_rows, c_start, c_len, c_max, job_off, max_job, k, ...)
@@ -56,7 +60,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import lib, check
-from .encoder import pack_weights
+from .encoder import pack_layer_stack, pack_weights
 
 Tensor = torch.Tensor
 _D = 768
@@ -507,7 +511,84 @@ def _cls_l2_pair_grad(ctx, grad):
 cls_l2_pair.register_autograd(_cls_l2_pair_grad, setup_context=_cls_l2_pair_setup)
 
 
+# ---- the encoder under autograd (aspire_bert_layers_forward_train_f32 / aspire_bert_layers_backward_f32) -------------------------------
+# emb_sum [B, L, 768]: word + position + type rows before the embedding LayerNorm; weights: [emb_ln_g, emb_ln_b] + per layer the twelve
+# tensors of bert_encoder_forward's list.  tape: what the backward reads (opaque bytes, aspire_bert_tape_bytes).
+def _train_workspace(bw, b, l, device):
+    return torch.empty(max(lib.aspire_bert_train_workspace_bytes(ctypes.byref(bw), b, l), 16), device=device, dtype=torch.uint8)
+
+
+@torch.library.custom_op('aspire::bert_layers_train', mutates_args=(), device_types='cuda')
+def bert_layers_train(emb_sum: Tensor, mask: Tensor, weights: List[Tensor], n_heads: int, ln_eps: float) -> Tuple[Tensor, Tensor]:
+    bw = pack_layer_stack(weights, n_heads, ln_eps)
+    emb_sum = emb_sum.to(torch.float32).contiguous()
+    b, l, _ = emb_sum.shape
+    mask = mask.to(torch.int64).contiguous()
+    out = torch.empty_like(emb_sum)
+    tape = torch.empty(max(lib.aspire_bert_tape_bytes(ctypes.byref(bw), b, l), 16), device=emb_sum.device, dtype=torch.uint8)
+    ws = _train_workspace(bw, b, l, emb_sum.device)
+    check(lib.aspire_bert_layers_forward_train_f32(ctypes.byref(bw), ops._ptr(emb_sum), ops._ptr(mask), b, l, ops._ptr(out), ops._ptr(tape),
+                                                   tape.numel(), ops._ptr(ws), ws.numel(), ops._stream()))
+    return out, tape
+
+
+@torch.library.custom_op('aspire::bert_layers_backward', mutates_args=(), device_types='cuda')
+def bert_layers_backward(grad_hidden: Tensor, tape: Tensor, mask: Tensor, weights: List[Tensor], n_heads: int,
+                         ln_eps: float) -> Tuple[Tensor, List[Tensor]]:
+    bw = pack_layer_stack(weights, n_heads, ln_eps)
+    grad_hidden = grad_hidden.to(torch.float32).contiguous()
+    b, l, _ = grad_hidden.shape
+    mask = mask.to(torch.int64).contiguous()
+    grads = [torch.empty_like(t, memory_format=torch.contiguous_format) for t in weights]
+    grad_emb = torch.empty_like(grad_hidden)
+    n_layers = (len(grads) - 2) // 12
+    layers = (_lib.BertLayerGrads * max(n_layers, 1))()
+    for i in range(n_layers):
+        for (f, _), t in zip(_lib.BertLayerGrads._fields_, grads[2 + 12 * i:14 + 12 * i]):
+            setattr(layers[i], f, ctypes.c_void_p(t.data_ptr()))
+    bg = _lib.BertGrads(ctypes.c_void_p(grads[0].data_ptr()), ctypes.c_void_p(grads[1].data_ptr()), layers)
+    ws = _train_workspace(bw, b, l, grad_hidden.device)
+    check(lib.aspire_bert_layers_backward_f32(ctypes.byref(bw), ops._ptr(mask), b, l, ops._ptr(grad_hidden), ops._ptr(tape), tape.numel(),
+                                              ops._ptr(grad_emb), ctypes.byref(bg), ops._ptr(ws), ws.numel(), ops._stream()))
+    return grad_emb, grads
+
+
+@bert_layers_train.register_fake
+def _(emb_sum, mask, weights, n_heads, ln_eps):
+    # (the tape's size is the library's to say: one byte per element of an unbacked length would need a GPU-free query of the struct;
+    # shapes downstream never depend on it)
+    return emb_sum.new_empty(emb_sum.shape, dtype=torch.float32), emb_sum.new_empty(_fake_tape_bytes(emb_sum, weights, n_heads, ln_eps),
+                                                                                     dtype=torch.uint8)
+
+
+def _fake_tape_bytes(emb_sum, weights, n_heads, ln_eps):
+    """aspire_bert_tape_bytes from shapes alone (a host-only query: it reads the struct's geometry, no pointer)."""
+    n_layers = (len(weights) - 2) // 12
+    bw = _lib.BertWeights(None, None, None, None, None, None, n_layers, n_heads, emb_sum.shape[2],
+                          weights[2 + 6].shape[0] if n_layers else 4 * emb_sum.shape[2], 0, 0, 0, float(ln_eps), None)
+    return max(lib.aspire_bert_tape_bytes(ctypes.byref(bw), emb_sum.shape[0], emb_sum.shape[1]), 16)
+
+
+@bert_layers_backward.register_fake
+def _(grad_hidden, tape, mask, weights, n_heads, ln_eps):
+    return grad_hidden.new_empty(grad_hidden.shape, dtype=torch.float32), [t.new_empty(t.shape) for t in weights]
+
+
+def _bert_layers_train_setup(ctx, inputs, output):
+    emb_sum, mask, weights, ctx.n_heads, ctx.ln_eps = inputs
+    ctx.save_for_backward(output[1], mask, *weights)
+
+
+def _bert_layers_train_grad(ctx, grad_hidden, grad_tape):
+    tape, mask, *weights = ctx.saved_tensors
+    grad_emb, grads = torch.ops.aspire.bert_layers_backward(grad_hidden, tape, mask, weights, ctx.n_heads, ctx.ln_eps)
+    return grad_emb, None, grads, None, None
+
+
+bert_layers_train.register_autograd(_bert_layers_train_grad, setup_context=_bert_layers_train_setup)
+
+
 OPS = ('span_mean_pool', 'span_pool_ranges', 'bert_encoder_forward', 'bert_cls_forward', 'bert_pooler', 'token_mean_pool', 'l2max_scores', 'jointsm_scores', 'ot_sinkhorn_scores', 'topk_desc', 'topk_keys', 'topk_merge',
        'l2max_scores_csr', 'ot_scores_csr', 'ot_rank_batch', 'dense_rank_batch', 'l2agg_pair_scores', 'l2agg_pair_backward',
        'ot_pair_scores', 'ot_pair_backward', 'jointsm_pair_scores', 'jointsm_pair_backward', 'l2sup_pair_scores', 'l2sup_pair_backward',
-       'span_mean_pool_backward', 'cls_l2_pair', 'cls_l2_pair_backward')
+       'span_mean_pool_backward', 'cls_l2_pair', 'cls_l2_pair_backward', 'bert_layers_train', 'bert_layers_backward')

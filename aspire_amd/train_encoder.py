@@ -1,0 +1,86 @@
+"""A1t: the BERT encoder under training -- a HuggingFace ``BertModel`` whose layer stack runs forward AND backward on this library's
+kernels (aspire_bert_layers_forward_train_f32 / aspire_bert_layers_backward_f32 behind torch.ops.aspire.bert_layers_train).
+
+``HipBertTrainEncoder(bert_model)`` is an ``nn.Module`` around the model; the parameters stay the model's own, so
+``torch.optim.Adam(enc.parameters())`` trains them, ``state_dict()`` / ``load_state_dict()`` speak HuggingFace's names, and what was
+trained loads straight into ``HipBertEncoder.from_state_dict`` / ``AspireConSent``.  Per forward, torch does the plumbing only: the
+embedding sum (word + token-type + position rows: the tables' scatter gradient stays torch's) and the ``torch.cat`` of the query / key /
+value weights and biases (autograd splits their gradient back); everything from the embedding LayerNorm to ``last_hidden_state``, and its
+gradient down to every parameter, is the library's.
+
+Dropout is not built: the encoder trains as ``BertModel`` does with ``hidden_dropout_prob = attention_probs_dropout_prob = 0``.
+"""
+import warnings
+
+import torch
+
+from . import ops
+from .encoder import _LAYER_KEYS
+
+
+class HipBertTrainEncoder(torch.nn.Module):
+    def __init__(self, bert_model):
+        super().__init__()
+        dev = ops.require_gpu()
+        cfg = bert_model.config
+        if getattr(cfg, 'model_type', 'bert') in ('roberta', 'mpnet') or not hasattr(bert_model.embeddings, 'token_type_embeddings'):
+            raise NotImplementedError(f'{type(bert_model).__name__}: the training encoder is built for BertModel (the position ids and the '
+                                      'relative-position bias of aspire_bert_extras have no backward)')
+        if cfg.hidden_size != 768 or cfg.num_attention_heads != 12 or cfg.intermediate_size % 64:
+            raise NotImplementedError('only BERT-base geometry (hidden 768, 12 heads, intermediate_size % 64 == 0) is built')
+        if cfg.hidden_act != 'gelu':
+            raise NotImplementedError(f'hidden_act {cfg.hidden_act!r}: only erf-GELU is built')
+        if getattr(cfg, 'position_embedding_type', 'absolute') != 'absolute':
+            raise NotImplementedError('only absolute position embeddings are built')
+        if cfg.hidden_dropout_prob > 0 or cfg.attention_probs_dropout_prob > 0:
+            warnings.warn(f'HipBertTrainEncoder: dropout is not built -- the model trains as with hidden_dropout_prob = '
+                          f'attention_probs_dropout_prob = 0 (the config has {cfg.hidden_dropout_prob} / {cfg.attention_probs_dropout_prob})',
+                          UserWarning)
+        self.bert = bert_model.to(device=dev, dtype=torch.float32)      # (moved in place: the parameters stay the model's own)
+        self.config = cfg
+
+    # HuggingFace's names, not 'bert.'-prefixed ones: what is saved here is a BertModel's state dict
+    def state_dict(self, *args, **kwargs):
+        return self.bert.state_dict(*args, **kwargs)
+
+    def load_state_dict(self, state_dict, *args, **kwargs):
+        return self.bert.load_state_dict(state_dict, *args, **kwargs)
+
+    def layer_weights(self):
+        """[emb_ln_g, emb_ln_b] + per layer the twelve tensors of struct aspire_bert_layer (pack_weights' order), on the autograd graph of
+        the model's parameters."""
+        emb = self.bert.embeddings
+        w = [emb.LayerNorm.weight, emb.LayerNorm.bias]
+        for layer in self.bert.encoder.layer:
+            att = layer.attention.self
+            w.append(torch.cat([att.query.weight, att.key.weight, att.value.weight], 0))
+            w.append(torch.cat([att.query.bias, att.key.bias, att.value.bias], 0))
+            named = dict(layer.named_parameters())
+            w += [named[k] for k in _LAYER_KEYS]
+        return w
+
+    def forward(self, tokid_tt, token_type_ids=None, attention_mask=None):
+        """int64 [B, L] tensors (any device), or the reference's batch dict (tokid_tt, seg_tt, attnmask_tt) -> last_hidden_state
+        [B, L, 768] fp32 on the GPU.  In train() mode with grad enabled the layer stack runs the training forward and keeps its tape for
+        the backward; under torch.no_grad() or in eval() it is the plain inference forward (no tape, not differentiable)."""
+        from . import torch_ops  # noqa: F401  (registers the operators)
+        if isinstance(tokid_tt, dict):
+            tokid_tt, token_type_ids, attention_mask = tokid_tt['tokid_tt'], tokid_tt.get('seg_tt'), tokid_tt.get('attnmask_tt')
+        emb = self.bert.embeddings
+        dev = emb.word_embeddings.weight.device
+        tok = tokid_tt.to(device=dev, dtype=torch.int64)
+        typ = token_type_ids.to(device=dev, dtype=torch.int64) if token_type_ids is not None else torch.zeros_like(tok)
+        msk = attention_mask.to(device=dev, dtype=torch.int64) if attention_mask is not None else torch.ones_like(tok)
+        cfg = self.config
+        if not (self.training and torch.is_grad_enabled()):
+            with torch.no_grad():
+                tables = [emb.word_embeddings.weight, emb.position_embeddings.weight, emb.token_type_embeddings.weight]
+                return torch.ops.aspire.bert_encoder_forward(tok, typ, msk, tables + self.layer_weights(), cfg.num_attention_heads,
+                                                             cfg.layer_norm_eps)
+        seq_len = tok.shape[1]
+        if seq_len > cfg.max_position_embeddings:
+            raise IndexError(f'{seq_len} tokens: beyond max_position_embeddings={cfg.max_position_embeddings}')
+        # BertEmbeddings' order: (word + token type) + position
+        emb_sum = (emb.word_embeddings(tok) + emb.token_type_embeddings(typ)) + emb.position_embeddings.weight[:seq_len]
+        hidden, _tape = torch.ops.aspire.bert_layers_train(emb_sum, msk, self.layer_weights(), cfg.num_attention_heads, cfg.layer_norm_eps)
+        return hidden

@@ -240,6 +240,52 @@ int aspire_token_mean_pool_f32(const float* hidden, const int64_t* attn_mask, in
                                int normalize, float* out /* [B, D] */, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * A1t  The BERT layer stack under training (fine_tune: true in the reference's configs: the encoder call of
+ * disent_models.py:470-485 under autograd).  HuggingFace BertModel from the embedding sum to last_hidden_state -- the embedding
+ * LayerNorm, then n_layers x [QKV, masked soft-max attention, output projection + residual + LayerNorm, GELU(erf) FFN + residual +
+ * LayerNorm] -- with both dropout probabilities 0, and its backward to every parameter of that stack and to the embedding sum.
+ * The table lookup (word + position + type rows) and its scatter gradient stay the caller's.  fp32 accuracy throughout.
+ *
+ * The forward runs the kernels aspire_bert_forward_f32 takes on fp32 operands (operands split into bf16 planes on the fly / the
+ * fp32-input matrix cores, the three-kernel attention, LayerNorm as its own pass: no kernel waits on another workgroup, so
+ * aspire_bert_status is not involved) and keeps on the caller's `tape`, per layer: the layer input, qkv, the soft-max probabilities
+ * [B, heads, L, Lp = L rounded up to 4], the attention context, both pre-LayerNorm sums, the LN1 output and the PRE-GELU FFN1 output
+ * (GELU is a pass of its own here; the backward forms GELU(u) again), and in front of layer 0 the embedding sum.  At B x L = 5 x 512,
+ * 12 layers, ffn 3072: 94 MB of activations + 63 MB of probabilities per layer.
+ *   emb_sum      [B, L, 768]  word + position + type embedding rows BEFORE the embedding LayerNorm
+ *   w            emb_ln_g / emb_ln_b, layers, n_layers, n_heads, hidden, ffn_dim, ln_eps are read; word_emb / pos_emb / type_emb /
+ *                vocab / max_pos / n_types / planes are not
+ *   attn_mask    int64 [B, L], any 0/1 pattern; an all-zero row attends uniformly (as the forward above)
+ *   hidden_out   [B, L, 768]  the bits of the fp32-operand forward (aspire_debug_set("GEMM", "bf16x3") + ("ATTN", "gemm"))
+ *   tape         device, aspire_bert_tape_bytes(w, B, L) bytes; opaque; valid for backward calls until it is overwritten
+ *   ws           device scratch, aspire_bert_train_workspace_bytes(w, B, L) bytes (one size serves both calls)
+ * The backward: grad_hidden [B, L, 768] -> grad_emb_sum [B, L, 768] (may be NULL) and every pointer of `grads`, each shaped like the
+ * weight of the same name.  Every gradient buffer is WRITTEN, not accumulated.  No atomics: column sums (bias and LayerNorm
+ * gradients) go through per-row-block partials added in a fixed order, so two calls on one tape give the same bits.  attn_mask
+ * must be the forward's (the masked keys' zeros are on the tape: it is checked, not read).
+ * Checked before the first launch: a NULL pointer, L outside (0, 512], a tape or workspace smaller than the query functions say
+ * -> ASPIRE_ERR_INVALID_ARG; hidden != 768, n_heads != 12, ffn_dim % 64 != 0 -> ASPIRE_ERR_UNSUPPORTED; B == 0 -> ASPIRE_OK
+ * without a launch; n_layers == 0 is legal (the embedding LayerNorm alone).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {
+    float *w_qkv, *b_qkv, *w_o, *b_o, *ln1_g, *ln1_b, *w_ffn1, *b_ffn1, *w_ffn2, *b_ffn2, *ln2_g, *ln2_b;
+} aspire_bert_layer_grads;
+
+typedef struct {
+    float *emb_ln_g, *emb_ln_b;
+    aspire_bert_layer_grads* layers;            /* HOST array of n_layers entries (device pointers inside) */
+} aspire_bert_grads;
+
+size_t aspire_bert_tape_bytes(const aspire_bert_weights* w, int64_t B, int64_t L);
+size_t aspire_bert_train_workspace_bytes(const aspire_bert_weights* w, int64_t B, int64_t L);
+int aspire_bert_layers_forward_train_f32(const aspire_bert_weights* w, const float* emb_sum, const int64_t* attn_mask, int64_t B,
+                                         int64_t L, float* hidden_out, void* tape, size_t tape_bytes, void* ws, size_t ws_bytes,
+                                         void* stream);
+int aspire_bert_layers_backward_f32(const aspire_bert_weights* w, const int64_t* attn_mask, int64_t B, int64_t L,
+                                    const float* grad_hidden, const void* tape, size_t tape_bytes, float* grad_emb_sum,
+                                    const aspire_bert_grads* grads, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * caching_score's document-level term (src/learning/facetid_models/disent_models.py:305-307, taken when
  * abs_loss_prop > 0): functional.pairwise_distance(query_cls_reps, cand_cls_reps, p=2.0) = ||q - c + eps||_2 with torch's
  * eps = 1e-6 added to every coordinate of the difference.  (The caller negates and scales it.)
