@@ -1,6 +1,8 @@
-// What the encoder's units share: the argument structs the GEMM kernels take by value (the forward in encoder.hip fills them), the
-// two device-side names that kernels of more than one unit use, and the host launchers each kernel family's unit offers to the
-// forward in encoder.hip (one comment line names the unit).  The fp16-plane layout has a header of its own, enc_planes.h.
+// What the encoder's units share: the argument structs the GEMM kernels take by value (GemmArgs: filled by enc_host.h's builders and
+// encoder_bwd.hip's two gradient forms; PGemmArgs: by run_layer in encoder.hip), the two device-side names that kernels of more than
+// one unit use, and the host launchers each kernel family's unit offers to the two host files, encoder.hip and encoder_bwd.hip (one
+// comment line names the unit).  What those two share on the host side is enc_host.h; the fp16-plane layout has a header of its own,
+// enc_planes.h.
 #pragma once
 #include "common.h"
 

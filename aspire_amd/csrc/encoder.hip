@@ -18,7 +18,8 @@
 // row of every token from a table (aspire_bert_extras::pos_ids) and adds MPNet's relative-position bias to the attention scores
 // (::rel_bias); without either it is aspire_bert_forward_f32 launch for launch.  The masked-mean read-out behind it is pool.hip's.
 //
-// This file is host only: the workspace, the forward's plan (plan_forward), one layer of it (run_layer), the CLS forward's tail and the C entry
+// This file is host only: the workspace, the forward's plan (plan_forward), one layer of it (run_layer: the plane path here, otherwise the
+// fp32-operand body of enc_host.h), the CLS forward and the C entry
 // points (aspire_bert_status and the clock build's aspire_debug_gemm_buffer sit with their device globals in enc_gemm_p.hip).  The kernels and their launch rules, one unit per family, each
 // kernel launched from one host function of its unit (enc_types.h declares them):
 //   enc_gemm.hip     gemm_f32_kernel, gemm_bf16x3_kernel: GEMMs on fp32 operands                              launch_gemm
@@ -29,18 +30,18 @@
 //   enc_rows.hip     layernorm_kernel, embed_layernorm_kernel, cls_tap_kernel                                launch_layernorm, launch_embed_layernorm, launch_cls_tap
 //   enc_pooler.hip   bert_pooler_kernel: tanh(cls . W^T + b) behind the CLS forward (aspire_bert_pooler_f32)   launch_pooler
 //   enc_planes.h     the fp16-plane layout: constants and device helpers
-// The layer stack under training (the tape-keeping forward over this file's fp32-operand launches, and the backward) has a host file of
+//   enc_host.h       host only, shared with encoder_bwd.hip: the buffer carver, the GemmArgs builders (linear, head_gemm), the three-kernel
+//                    attention (attention_gemm), the fp32-operand layer tail (layer_tail), the geometry and null-pointer checks
+// The layer stack under training (the tape-keeping forward over the same enc_host.h launches, and the backward) has a host file of
 // its own, encoder_bwd.hip, with its row kernels in enc_bwd.hip and the TN GEMM form in enc_gemm.hip (launch_gemm_tn).
 #include <math.h>
 
+#include "enc_host.h"
 #include "enc_planes.h"
-#include "enc_types.h"
 #include "tuning.h"
 
 namespace aspire {
 namespace {
-
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct Workspace {
     float *x, *qkv, *scores, *ctx, *tmp, *ffn;
@@ -54,33 +55,22 @@ struct Workspace {
 
 Workspace carve(void* base, int64_t B, int64_t L, int heads, int ffn_dim, int n_layers) {
     const size_t M = (size_t)B * L, Lp = (size_t)(L + 3) / 4 * 4;
-    char* p = (char*)base;
+    Carver c(base);
     Workspace w;
-    size_t off = 0;
-    auto take = [&](size_t nfloats) {
-        float* r = (float*)(p + off);
-        off += align_up(nfloats * sizeof(float));
-        return r;
-    };
-    w.x = take(M * kD);
-    w.qkv = take(M * 3 * kD);
-    w.scores = take((size_t)B * heads * L * Lp);
-    w.ctx = take(M * kD);
-    w.tmp = take(M * kD);
-    w.ffn = take(M * ffn_dim);
-    auto take_p = [&](int64_t K) {
-        void* r = p + off;
-        off += align_up(p_bytes((int64_t)M, K));
-        return r;
-    };
-    w.actp = take_p(kD);
-    w.ctxp = take_p(kD);
-    w.ffnp = take_p(ffn_dim);
-    w.ln_stats = reinterpret_cast<float2*>(take(M * 24));
+    w.x = c.floats(M * kD);
+    w.qkv = c.floats(M * 3 * kD);
+    w.scores = c.floats((size_t)B * heads * L * Lp);
+    w.ctx = c.floats(M * kD);
+    w.tmp = c.floats(M * kD);
+    w.ffn = c.floats(M * ffn_dim);
+    w.actp = c.bytes(p_bytes((int64_t)M, kD));
+    w.ctxp = c.bytes(p_bytes((int64_t)M, kD));
+    w.ffnp = c.bytes(p_bytes((int64_t)M, ffn_dim));
+    w.ln_stats = reinterpret_cast<float2*>(c.floats(M * 24));
     w.ln_count_bytes = (size_t)2 * (n_layers > 0 ? n_layers : 0) * ((M + 127) / 128) * sizeof(int);
-    w.ln_count = reinterpret_cast<int*>(take(w.ln_count_bytes / sizeof(float) + 1));
-    w.qkvp = reinterpret_cast<unsigned char*>(take(M * 3 * kD));                     // 2 planes x [Q | K | V] x M x 768 fp16 = the bytes of the fp32 qkv
-    w.total = off;
+    w.ln_count = reinterpret_cast<int*>(c.floats(w.ln_count_bytes / sizeof(float) + 1));
+    w.qkvp = reinterpret_cast<unsigned char*>(c.floats(M * 3 * kD));                 // 2 planes x [Q | K | V] x M x 768 fp16 = the bytes of the fp32 qkv
+    w.total = c.off;
     return w;
 }
 
@@ -90,12 +80,12 @@ struct PlaneOffsets {
 };
 PlaneOffsets plane_offsets(int ffn_dim) {
     PlaneOffsets o{};
-    size_t off = 0;
-    o.qkv = off; off += align_up(p_bytes(3 * kD, kD));
-    o.o = off; off += align_up(p_bytes(kD, kD));
-    o.ffn1 = off; off += align_up(p_bytes(ffn_dim, kD));
-    o.ffn2 = off; off += align_up(p_bytes(kD, ffn_dim));
-    o.per_layer = off;
+    Carver c(nullptr);
+    o.qkv = c.off; c.bytes(p_bytes(3 * kD, kD));
+    o.o = c.off; c.bytes(p_bytes(kD, kD));
+    o.ffn1 = c.off; c.bytes(p_bytes(ffn_dim, kD));
+    o.ffn2 = c.off; c.bytes(p_bytes(kD, ffn_dim));
+    o.per_layer = c.off;
     return o;
 }
 
@@ -121,11 +111,8 @@ struct Fwd {
 // the forwards' argument checks: all of them before the first launch
 int check_forward_args(const aspire_bert_weights* w, const int64_t* tok_ids, const int64_t* attn_mask, const float* out, int64_t B, int64_t L) {
     ASPIRE_REQUIRE(w && tok_ids && attn_mask && out, ASPIRE_ERR_INVALID_ARG, "null pointer");
-    ASPIRE_REQUIRE(w->hidden == kD && w->n_heads == 12 && w->ffn_dim % 64 == 0 && w->ffn_dim > 0, ASPIRE_ERR_UNSUPPORTED,
-                   "only BERT-base geometry is built (hidden 768, 12 heads); got hidden %d heads %d", w->hidden, w->n_heads);
-    ASPIRE_REQUIRE(B >= 0 && L > 0 && L <= 512 && L <= w->max_pos, ASPIRE_ERR_INVALID_ARG,
-                   "sequence length %lld outside (0, min(512, max_position_embeddings=%d)]", (long long)L, w->max_pos);
-    ASPIRE_REQUIRE(w->n_layers >= 0 && (w->n_layers == 0 || w->layers), ASPIRE_ERR_INVALID_ARG, "bad layer table");
+    if (int rc = check_bert_shape(w, B, L)) return rc;
+    ASPIRE_REQUIRE(L <= w->max_pos, ASPIRE_ERR_INVALID_ARG, "sequence length %lld beyond max_position_embeddings=%d", (long long)L, w->max_pos);
     return ASPIRE_OK;
 }
 
@@ -188,7 +175,6 @@ int run_layer(const Fwd& f, int l, const float* x, float* out, bool last, bool q
     hipStream_t st = f.st;
     const aspire_bert_layer& ly = w->layers[l];
     const char* lp = (const char*)w->planes + (size_t)l * po.per_layer;
-    GemmArgs g{};
     PGemmArgs pg{};
     // 1. fused QKV projection: qkv [M, 2304] = x . Wqkv^T + bqkv
     if (attn_p) {
@@ -200,10 +186,7 @@ int run_layer(const Fwd& f, int l, const float* x, float* out, bool last, bool q
         pg = PGemmArgs{ws.actp, lp + po.qkv, ws.qkv, nullptr, ly.b_qkv, nullptr, (int)M, 3 * kD, kD, 3 * kD, 0, 0};
         if (int rc = launch_gemm_p(pg, false, st)) return rc;
     } else {
-        g = GemmArgs{};
-        g.A = x; g.B = ly.w_qkv; g.C = ws.qkv; g.bias = ly.b_qkv;
-        g.M = (int)M; g.N = 3 * kD; g.K = kD; g.lda = kD; g.ldb = kD; g.ldc = 3 * kD; g.nz2 = 1; g.alpha = 1.f;
-        if (int rc = launch_gemm(g, 1, false, st)) return rc;
+        if (int rc = launch_gemm(linear(x, ly.w_qkv, ws.qkv, ly.b_qkv, nullptr, M, 3 * kD, kD), 1, false, st)) return rc;
     }
     if (qkv_only) return ASPIRE_OK;
     // 2-4. attention.  Fused kernel (scores never leave the chip) unless ASPIRE_HIP_ATTN=gemm pins the
@@ -216,25 +199,11 @@ int run_layer(const Fwd& f, int l, const float* x, float* out, bool last, bool q
                                        f.rel_span, st))
             return rc;
     } else {
-        // 2. scores[b,h] = Q_bh . K_bh^T   (scale and mask are applied by the softmax kernel)
-        g = GemmArgs{};
-        g.A = ws.qkv; g.B = ws.qkv + kD; g.C = ws.scores;
-        g.M = (int)L; g.N = (int)L; g.K = dh; g.lda = 3 * kD; g.ldb = 3 * kD; g.ldc = Lp; g.nz2 = H; g.alpha = 1.f;
-        g.sa1 = (long long)L * 3 * kD; g.sa2 = dh; g.sb1 = g.sa1; g.sb2 = dh;
-        g.sc1 = (long long)H * L * Lp; g.sc2 = (long long)L * Lp;
-        if (int rc = launch_gemm(g, (int)(B * H), false, st)) return rc;
-        // 3. masked softmax over keys
-        const int64_t srows = B * H * L;
-        if (int rc = launch_softmax_mask(ws.scores, attn_mask, srows, (int)L, Lp, (int)(H * L), 1.0f / sqrtf((float)dh), f.rel_bias, f.rel_span, st))
-            return rc;
-        // 4. ctx[b, :, h*64:(h+1)*64] = P_bh . V_bh        (V is [K = L keys, N = 64] n-contiguous)
-        g = GemmArgs{};
-        g.A = ws.scores; g.B = ws.qkv + 2 * kD; g.C = ws.ctx;
-        g.M = (int)L; g.N = dh; g.K = (int)L; g.lda = Lp; g.ldb = 3 * kD; g.ldc = kD; g.nz2 = H; g.alpha = 1.f;
-        g.sa1 = (long long)H * L * Lp; g.sa2 = (long long)L * Lp; g.sb1 = (long long)L * 3 * kD; g.sb2 = dh;
-        g.sc1 = (long long)L * kD; g.sc2 = dh;
-        if (int rc = launch_gemm(g, (int)(B * H), true, st)) return rc;
+        if (int rc = attention_gemm(ws.qkv, ws.scores, ws.ctx, attn_mask, B, L, Lp, H, dh, f.rel_bias, f.rel_span, st)) return rc;
     }
+    // 5-6 on fp32 operands: the shared body.  h = LN1(.) goes where the context was read from, both pre-norm sums to ws.tmp
+    if (!pp) return layer_tail(w, ly, ws.ctx, x, TailSlots{ws.tmp, ws.ctx, nullptr, ws.ffn, ws.tmp}, out, M, st);
+    // ... and on the planes:
     // 5. attention output projection + residual, LayerNorm
     if (ln_fused) {
         // x lives in actp (written by the embedding LayerNorm / the previous layer's FFN2 epilogue, read by the QKV GEMM): read as the
@@ -244,44 +213,24 @@ int run_layer(const Fwd& f, int l, const float* x, float* out, bool last, bool q
         pg.gamma = ly.ln1_g; pg.beta = ly.ln1_b; pg.eps = w->ln_eps;
         pg.ln_stats = ws.ln_stats; pg.ln_count = ws.ln_count + (size_t)(2 * l) * row_tiles;
         if (int rc = launch_gemm_p_ln(pg, st)) return rc;
-    } else if (pp) {
+    } else {
         pg = PGemmArgs{ws.ctxp, lp + po.o, ws.tmp, nullptr, ly.b_o, x, (int)M, kD, kD, kD, kD, 0};
         if (int rc = launch_gemm_p(pg, false, st)) return rc;
-    } else {
-        g = GemmArgs{};
-        g.A = ws.ctx; g.B = ly.w_o; g.C = ws.tmp; g.bias = ly.b_o; g.res = x; g.ldr = kD;
-        g.M = (int)M; g.N = kD; g.K = kD; g.lda = kD; g.ldb = kD; g.ldc = kD; g.nz2 = 1; g.alpha = 1.f;
-        if (int rc = launch_gemm(g, 1, false, st)) return rc;
+        if (int rc = launch_layernorm(ws.tmp, ly.ln1_g, ly.ln1_b, w->ln_eps, ws.ctx, M, ws.actp, st)) return rc;
     }
-    if (!ln_fused)
-        if (int rc = launch_layernorm(ws.tmp, ly.ln1_g, ly.ln1_b, w->ln_eps, ws.ctx, M, pp ? ws.actp : nullptr, st)) return rc;
     // 6. FFN: GELU(h . W1^T + b1) . W2^T + b2 + h, LayerNorm          (h = ws.ctx)
-    if (pp) {
-        pg = PGemmArgs{ws.actp, lp + po.ffn1, nullptr, ws.ffnp, ly.b_ffn1, nullptr, (int)M, w->ffn_dim, kD, 0, 0, 0};
-        if (int rc = launch_gemm_p(pg, true, st)) return rc;
-        if (ln_fused) {
-            pg = PGemmArgs{ws.ffnp, lp + po.ffn2, last ? out : nullptr, last ? nullptr : ws.actp, ly.b_ffn2, nullptr, (int)M, kD, w->ffn_dim, kD, kD, 0};
-            pg.resp = ws.actp;
-            pg.gamma = ly.ln2_g; pg.beta = ly.ln2_b; pg.eps = w->ln_eps;
-            pg.ln_stats = ws.ln_stats; pg.ln_count = ws.ln_count + (size_t)(2 * l + 1) * row_tiles;
-            if (int rc = launch_gemm_p_ln(pg, st)) return rc;
-        } else {
-            pg = PGemmArgs{ws.ffnp, lp + po.ffn2, ws.tmp, nullptr, ly.b_ffn2, ws.ctx, (int)M, kD, w->ffn_dim, kD, kD, 0};
-            if (int rc = launch_gemm_p(pg, false, st)) return rc;
-        }
-    } else {
-        g = GemmArgs{};
-        g.A = ws.ctx; g.B = ly.w_ffn1; g.C = ws.ffn; g.bias = ly.b_ffn1; g.gelu = 1;
-        g.M = (int)M; g.N = w->ffn_dim; g.K = kD; g.lda = kD; g.ldb = kD; g.ldc = w->ffn_dim; g.nz2 = 1; g.alpha = 1.f;
-        if (int rc = launch_gemm(g, 1, false, st)) return rc;
-        g = GemmArgs{};
-        g.A = ws.ffn; g.B = ly.w_ffn2; g.C = ws.tmp; g.bias = ly.b_ffn2; g.res = ws.ctx; g.ldr = kD;
-        g.M = (int)M; g.N = kD; g.K = w->ffn_dim; g.lda = w->ffn_dim; g.ldb = w->ffn_dim; g.ldc = kD; g.nz2 = 1; g.alpha = 1.f;
-        if (int rc = launch_gemm(g, 1, false, st)) return rc;
+    pg = PGemmArgs{ws.actp, lp + po.ffn1, nullptr, ws.ffnp, ly.b_ffn1, nullptr, (int)M, w->ffn_dim, kD, 0, 0, 0};
+    if (int rc = launch_gemm_p(pg, true, st)) return rc;
+    if (ln_fused) {
+        pg = PGemmArgs{ws.ffnp, lp + po.ffn2, last ? out : nullptr, last ? nullptr : ws.actp, ly.b_ffn2, nullptr, (int)M, kD, w->ffn_dim, kD, kD, 0};
+        pg.resp = ws.actp;
+        pg.gamma = ly.ln2_g; pg.beta = ly.ln2_b; pg.eps = w->ln_eps;
+        pg.ln_stats = ws.ln_stats; pg.ln_count = ws.ln_count + (size_t)(2 * l + 1) * row_tiles;
+        return launch_gemm_p_ln(pg, st);
     }
-    if (!ln_fused)
-        if (int rc = launch_layernorm(ws.tmp, ly.ln2_g, ly.ln2_b, w->ln_eps, out, M, pp && !last ? ws.actp : nullptr, st)) return rc;
-    return ASPIRE_OK;
+    pg = PGemmArgs{ws.ffnp, lp + po.ffn2, ws.tmp, nullptr, ly.b_ffn2, ws.ctx, (int)M, kD, w->ffn_dim, kD, kD, 0};
+    if (int rc = launch_gemm_p(pg, false, st)) return rc;
+    return launch_layernorm(ws.tmp, ly.ln2_g, ly.ln2_b, w->ln_eps, out, M, last ? nullptr : ws.actp, st);
 }
 
 // The CLS forward's own workspace, behind the forward's (carve): the B gathered rows of the last layer
@@ -290,21 +239,15 @@ struct ClsWorkspace {
     size_t total;
 };
 ClsWorkspace carve_cls(void* base, int64_t B, int ffn_dim) {
-    char* p = (char*)base;
+    Carver cv(base);
     ClsWorkspace c;
-    size_t off = 0;
-    auto take = [&](size_t nfloats) {
-        float* r = (float*)(p + off);
-        off += align_up(nfloats * sizeof(float));
-        return r;
-    };
-    c.gin = take((size_t)B * kD);
-    c.ctx = take((size_t)B * kD);
-    c.tmp = take((size_t)B * kD);
-    c.h = take((size_t)B * kD);
-    c.y = take((size_t)B * kD);
-    c.ffn = take((size_t)B * ffn_dim);
-    c.total = off;
+    c.gin = cv.floats((size_t)B * kD);
+    c.ctx = cv.floats((size_t)B * kD);
+    c.tmp = cv.floats((size_t)B * kD);
+    c.h = cv.floats((size_t)B * kD);
+    c.y = cv.floats((size_t)B * kD);
+    c.ffn = cv.floats((size_t)B * ffn_dim);
+    c.total = cv.off;
     return c;
 }
 
@@ -402,20 +345,7 @@ extern "C" int aspire_bert_forward_cls_f32(const aspire_bert_weights* w, const i
     if (int rc = launch_cls_attn(f.attn_p ? nullptr : f.ws.qkv, f.attn_p ? f.ws.qkvp : nullptr, attn_mask, cw.ctx, B, (int)L, f.H, f.M, f.st))
         return rc;
     // ... then the rest of the layer on the B context rows: out-proj + residual, LN1, GELU(FFN1), FFN2 + residual, LN2
-    GemmArgs g{};
-    g.A = cw.ctx; g.B = ly.w_o; g.C = cw.tmp; g.bias = ly.b_o; g.res = cw.gin; g.ldr = kD;
-    g.M = (int)B; g.N = kD; g.K = kD; g.lda = kD; g.ldb = kD; g.ldc = kD; g.nz2 = 1; g.alpha = 1.f;
-    if (int rc = launch_gemm(g, 1, false, f.st)) return rc;
-    if (int rc = launch_layernorm(cw.tmp, ly.ln1_g, ly.ln1_b, w->ln_eps, cw.h, B, nullptr, f.st)) return rc;
-    g = GemmArgs{};
-    g.A = cw.h; g.B = ly.w_ffn1; g.C = cw.ffn; g.bias = ly.b_ffn1; g.gelu = 1;
-    g.M = (int)B; g.N = w->ffn_dim; g.K = kD; g.lda = kD; g.ldb = kD; g.ldc = w->ffn_dim; g.nz2 = 1; g.alpha = 1.f;
-    if (int rc = launch_gemm(g, 1, false, f.st)) return rc;
-    g = GemmArgs{};
-    g.A = cw.ffn; g.B = ly.w_ffn2; g.C = cw.tmp; g.bias = ly.b_ffn2; g.res = cw.h; g.ldr = kD;
-    g.M = (int)B; g.N = kD; g.K = w->ffn_dim; g.lda = w->ffn_dim; g.ldb = w->ffn_dim; g.ldc = kD; g.nz2 = 1; g.alpha = 1.f;
-    if (int rc = launch_gemm(g, 1, false, f.st)) return rc;
-    if (int rc = launch_layernorm(cw.tmp, ly.ln2_g, ly.ln2_b, w->ln_eps, cw.y, B, nullptr, f.st)) return rc;
+    if (int rc = layer_tail(w, ly, cw.ctx, cw.gin, TailSlots{cw.tmp, cw.h, nullptr, cw.ffn, cw.tmp}, cw.y, B, f.st)) return rc;
     return tap(n, cw.y, nullptr, B, 1);
 }
 
@@ -496,12 +426,5 @@ extern "C" int aspire_debug_gemm_planes(const void* Ap, const void* Bp, float* C
 // dispatch, for tools/gemmbench.py.  A [M,K], B [N,K], C [M,N], all row-major fp32 device pointers.
 extern "C" int aspire_debug_gemm_f32(const float* A, const float* B, float* C, const float* bias, int M, int N, int K,
                                      void* stream) {
-    GemmArgs g{};
-    g.A = A; g.B = B; g.C = C; g.bias = bias; g.res = nullptr;
-    g.M = M; g.N = N; g.K = K;
-    g.lda = K; g.ldb = K; g.ldc = N; g.ldr = 0;
-    g.nz2 = 1;
-    g.alpha = 1.0f;
-    g.gelu = 0;
-    return launch_gemm(g, 1, false, (hipStream_t)stream);
+    return launch_gemm(linear(A, B, C, bias, nullptr, M, N, K), 1, false, (hipStream_t)stream);
 }

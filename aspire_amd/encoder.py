@@ -60,24 +60,41 @@ def relative_bias_table(weight, span=REL_SPAN, num_buckets=32, max_distance=128)
     return weight.detach().to(device='cpu', dtype=torch.float32)[bucket].t().contiguous()
 
 
+def fill_layers(struct_type, tensors):
+    """A ctypes array of struct_type (BertLayer, BertLayerGrads: the same twelve pointer fields) over twelve tensors per layer, in the
+    fields' order.  At least one element, so that the array is never empty; the caller keeps the tensors alive."""
+    n_layers = len(tensors) // 12
+    layers = (struct_type * max(n_layers, 1))()
+    for i in range(n_layers):
+        for (f, _), t in zip(struct_type._fields_, tensors[12 * i:12 * i + 12]):
+            setattr(layers[i], f, ctypes.c_void_p(t.data_ptr()))
+    return layers
+
+
+def _pack(weights, n_tables, n_heads, ln_eps):
+    """struct aspire_bert_weights over [the n_tables (3 or 0) embedding tables] + [emb_ln_g, emb_ln_b] + 12 per layer; tables that are
+    not given stay NULL with 0 rows.  The geometry comes from the tensors' shapes."""
+    w = [t.contiguous() for t in weights]
+    assert all(t.is_cuda and t.dtype == torch.float32 for t in w)
+    tables, stack = w[:n_tables], w[n_tables:]
+    n_layers = (len(stack) - 2) // 12
+    layers = fill_layers(BertLayer, stack[2:])
+    hidden_size = stack[0].shape[0]
+    ffn = stack[2 + 6].shape[0] if n_layers else 4 * hidden_size
+    table_ptrs = [ctypes.c_void_p(t.data_ptr()) for t in tables] or [None] * 3
+    table_rows = [t.shape[0] for t in tables] or [0] * 3
+    bw = BertWeights(*table_ptrs, ctypes.c_void_p(stack[0].data_ptr()), ctypes.c_void_p(stack[1].data_ptr()), layers, n_layers, n_heads,
+                     hidden_size, ffn, *table_rows, float(ln_eps), None)
+    bw._keep = (layers, w)
+    return bw
+
+
 def pack_weights(weights, n_heads, ln_eps):
     """struct aspire_bert_weights over fp32 GPU tensors [word_emb, pos_emb, type_emb, emb_ln_g, emb_ln_b] + per layer [w_qkv, b_qkv,
     w_o, b_o, ln1_g, ln1_b, w_ffn1, b_ffn1, w_ffn2, b_ffn2, ln2_g, ln2_b] (struct aspire_bert_layer, nn.Linear layout); the geometry
     comes from the tensors' shapes.  The struct keeps the (contiguous) tensors and its layer array alive."""
     assert (len(weights) - 5) % 12 == 0 and len(weights) >= 5, 'weights: 5 embedding tensors + 12 per layer'
-    w = [t.contiguous() for t in weights]
-    assert all(t.is_cuda and t.dtype == torch.float32 for t in w)
-    n_layers = (len(w) - 5) // 12
-    layers = (BertLayer * max(n_layers, 1))()
-    for i in range(n_layers):
-        for (f, _), t in zip(BertLayer._fields_, w[5 + 12 * i:17 + 12 * i]):
-            setattr(layers[i], f, ctypes.c_void_p(t.data_ptr()))
-    hidden_size = w[0].shape[1]
-    ffn = w[5 + 6].shape[0] if n_layers else 4 * hidden_size
-    bw = BertWeights(*(ctypes.c_void_p(t.data_ptr()) for t in w[:5]), layers, n_layers, n_heads, hidden_size, ffn,
-                     w[0].shape[0], w[1].shape[0], w[2].shape[0], float(ln_eps), None)
-    bw._keep = (layers, w)
-    return bw
+    return _pack(weights, 3, n_heads, ln_eps)
 
 
 def pack_layer_stack(weights, n_heads, ln_eps):
@@ -85,19 +102,19 @@ def pack_layer_stack(weights, n_heads, ln_eps):
     the embedding lookup: fp32 GPU tensors [emb_ln_g, emb_ln_b] + the twelve per layer in pack_weights' order; the three tables stay
     NULL.  The struct keeps the (contiguous) tensors and its layer array alive."""
     assert (len(weights) - 2) % 12 == 0 and len(weights) >= 2, 'weights: emb_ln_g, emb_ln_b + 12 per layer'
-    w = [t.contiguous() for t in weights]
-    assert all(t.is_cuda and t.dtype == torch.float32 for t in w)
-    n_layers = (len(w) - 2) // 12
-    layers = (BertLayer * max(n_layers, 1))()
-    for i in range(n_layers):
-        for (f, _), t in zip(BertLayer._fields_, w[2 + 12 * i:14 + 12 * i]):
-            setattr(layers[i], f, ctypes.c_void_p(t.data_ptr()))
-    hidden_size = w[0].shape[0]
-    ffn = w[2 + 6].shape[0] if n_layers else 4 * hidden_size
-    bw = BertWeights(None, None, None, ctypes.c_void_p(w[0].data_ptr()), ctypes.c_void_p(w[1].data_ptr()), layers, n_layers, n_heads,
-                     hidden_size, ffn, 0, 0, 0, float(ln_eps), None)
-    bw._keep = (layers, w)
-    return bw
+    return _pack(weights, 0, n_heads, ln_eps)
+
+
+def require_bert_base(cfg, ffn_multiple, who):
+    """NotImplementedError unless cfg describes what the kernels are built for: BERT-base geometry with intermediate_size a multiple of
+    ffn_multiple, erf-GELU, absolute position embeddings."""
+    if cfg.hidden_size != 768 or cfg.num_attention_heads != 12 or cfg.intermediate_size % ffn_multiple:
+        ffn = f', intermediate_size % {ffn_multiple} == 0' if ffn_multiple > 1 else ''
+        raise NotImplementedError(f'{who}: only BERT-base geometry (hidden 768, 12 heads{ffn}) is built')
+    if cfg.hidden_act != 'gelu':
+        raise NotImplementedError(f'{who}: hidden_act {cfg.hidden_act!r}: only erf-GELU is built')
+    if getattr(cfg, 'position_embedding_type', 'absolute') != 'absolute':
+        raise NotImplementedError(f'{who}: only absolute position embeddings are built')
 
 
 def run_checked(run, outputs_finite, who, status):
@@ -124,12 +141,7 @@ class HipBertEncoder:
     def __init__(self, bert_model):
         dev = ops.require_gpu()
         cfg = bert_model.config
-        if cfg.hidden_size != 768 or cfg.num_attention_heads != 12:
-            raise NotImplementedError('only BERT-base geometry (hidden 768, 12 heads) is built')
-        if cfg.hidden_act != 'gelu':
-            raise NotImplementedError(f'hidden_act {cfg.hidden_act!r}: only erf-GELU is built')
-        if getattr(cfg, 'position_embedding_type', 'absolute') != 'absolute':
-            raise NotImplementedError('only absolute position embeddings are built')
+        require_bert_base(cfg, 1, 'HipBertEncoder')          # (any intermediate_size: the library checks it per call)
         sd = {k: v.detach() for k, v in bert_model.state_dict().items()}
         self.config = cfg
         self.device = dev

@@ -60,7 +60,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import lib, check
-from .encoder import pack_layer_stack, pack_weights
+from .encoder import fill_layers, pack_layer_stack, pack_weights
 
 Tensor = torch.Tensor
 _D = 768
@@ -76,6 +76,15 @@ def _padded_repset(t, lens):
 
 def _csr_repset(rows, start, lens, max_len):
     return ops.DeviceRepSet(rows, start, lens, ext=0, max_len=max_len)
+
+
+def _scratch(query, bw, b, l, device):
+    """uint8 [what the library's size query asks for, at least 16]: a call's workspace or tape"""
+    return torch.empty(max(query(ctypes.byref(bw), b, l), 16), device=device, dtype=torch.uint8)
+
+
+def _int64(*tensors):
+    return [t.to(torch.int64).contiguous() for t in tensors]
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -140,14 +149,12 @@ def _(hidden, row_doc, row_start, row_len):
 @torch.library.custom_op('aspire::bert_encoder_forward', mutates_args=(), device_types='cuda')
 def bert_encoder_forward(ids: Tensor, type_ids: Tensor, mask: Tensor, weights: List[Tensor], n_heads: int, ln_eps: float) -> Tensor:
     bw = pack_weights(weights, n_heads, ln_eps)
-    ids = ids.to(torch.int64).contiguous()
+    ids, type_ids, mask = _int64(ids, type_ids, mask)
     b, l = ids.shape
     out = torch.empty(b, l, bw.hidden, device=ids.device, dtype=torch.float32)
-    need = lib.aspire_bert_workspace_bytes(ctypes.byref(bw), b, l)
-    ws = torch.empty(max(need, 16), device=ids.device, dtype=torch.uint8)
-    check(lib.aspire_bert_forward_f32(ctypes.byref(bw), ops._ptr(ids), ops._ptr(type_ids.to(torch.int64).contiguous()),
-                                      ops._ptr(mask.to(torch.int64).contiguous()), b, l, ops._ptr(out), ops._ptr(ws), ws.numel(),
-                                      ops._stream()))
+    ws = _scratch(lib.aspire_bert_workspace_bytes, bw, b, l, ids.device)
+    check(lib.aspire_bert_forward_f32(ctypes.byref(bw), ops._ptr(ids), ops._ptr(type_ids), ops._ptr(mask), b, l, ops._ptr(out), ops._ptr(ws),
+                                      ws.numel(), ops._stream()))
     return out
 
 
@@ -163,15 +170,13 @@ def bert_cls_forward(ids: Tensor, type_ids: Tensor, mask: Tensor, weights: List[
                      layer_mix: List[float]) -> Tensor:
     bw = pack_weights(weights, n_heads, ln_eps)
     assert len(layer_mix) in (0, bw.n_layers + 1), 'layer_mix: n_layers + 1 weights, or none'
-    ids = ids.to(torch.int64).contiguous()
+    ids, type_ids, mask = _int64(ids, type_ids, mask)
     b, l = ids.shape
     out = torch.empty(b, bw.hidden, device=ids.device, dtype=torch.float32)
     mix = ctypes.cast((ctypes.c_float * len(layer_mix))(*layer_mix), ctypes.c_void_p) if layer_mix else None
-    need = lib.aspire_bert_cls_workspace_bytes(ctypes.byref(bw), b, l)
-    ws = torch.empty(max(need, 16), device=ids.device, dtype=torch.uint8)
-    check(lib.aspire_bert_forward_cls_f32(ctypes.byref(bw), ops._ptr(ids), ops._ptr(type_ids.to(torch.int64).contiguous()),
-                                          ops._ptr(mask.to(torch.int64).contiguous()), b, l, mix, ops._ptr(out), None, ops._ptr(ws),
-                                          ws.numel(), ops._stream()))
+    ws = _scratch(lib.aspire_bert_cls_workspace_bytes, bw, b, l, ids.device)
+    check(lib.aspire_bert_forward_cls_f32(ctypes.byref(bw), ops._ptr(ids), ops._ptr(type_ids), ops._ptr(mask), b, l, mix, ops._ptr(out), None,
+                                          ops._ptr(ws), ws.numel(), ops._stream()))
     return out
 
 
@@ -515,7 +520,7 @@ cls_l2_pair.register_autograd(_cls_l2_pair_grad, setup_context=_cls_l2_pair_setu
 # emb_sum [B, L, 768]: word + position + type rows before the embedding LayerNorm; weights: [emb_ln_g, emb_ln_b] + per layer the twelve
 # tensors of bert_encoder_forward's list.  tape: what the backward reads (opaque bytes, aspire_bert_tape_bytes).
 def _train_workspace(bw, b, l, device):
-    return torch.empty(max(lib.aspire_bert_train_workspace_bytes(ctypes.byref(bw), b, l), 16), device=device, dtype=torch.uint8)
+    return _scratch(lib.aspire_bert_train_workspace_bytes, bw, b, l, device)
 
 
 @torch.library.custom_op('aspire::bert_layers_train', mutates_args=(), device_types='cuda')
@@ -523,9 +528,9 @@ def bert_layers_train(emb_sum: Tensor, mask: Tensor, weights: List[Tensor], n_he
     bw = pack_layer_stack(weights, n_heads, ln_eps)
     emb_sum = emb_sum.to(torch.float32).contiguous()
     b, l, _ = emb_sum.shape
-    mask = mask.to(torch.int64).contiguous()
+    mask, = _int64(mask)
     out = torch.empty_like(emb_sum)
-    tape = torch.empty(max(lib.aspire_bert_tape_bytes(ctypes.byref(bw), b, l), 16), device=emb_sum.device, dtype=torch.uint8)
+    tape = _scratch(lib.aspire_bert_tape_bytes, bw, b, l, emb_sum.device)
     ws = _train_workspace(bw, b, l, emb_sum.device)
     check(lib.aspire_bert_layers_forward_train_f32(ctypes.byref(bw), ops._ptr(emb_sum), ops._ptr(mask), b, l, ops._ptr(out), ops._ptr(tape),
                                                    tape.numel(), ops._ptr(ws), ws.numel(), ops._stream()))
@@ -538,14 +543,10 @@ def bert_layers_backward(grad_hidden: Tensor, tape: Tensor, mask: Tensor, weight
     bw = pack_layer_stack(weights, n_heads, ln_eps)
     grad_hidden = grad_hidden.to(torch.float32).contiguous()
     b, l, _ = grad_hidden.shape
-    mask = mask.to(torch.int64).contiguous()
+    mask, = _int64(mask)
     grads = [torch.empty_like(t, memory_format=torch.contiguous_format) for t in weights]
     grad_emb = torch.empty_like(grad_hidden)
-    n_layers = (len(grads) - 2) // 12
-    layers = (_lib.BertLayerGrads * max(n_layers, 1))()
-    for i in range(n_layers):
-        for (f, _), t in zip(_lib.BertLayerGrads._fields_, grads[2 + 12 * i:14 + 12 * i]):
-            setattr(layers[i], f, ctypes.c_void_p(t.data_ptr()))
+    layers = fill_layers(_lib.BertLayerGrads, grads[2:])
     bg = _lib.BertGrads(ctypes.c_void_p(grads[0].data_ptr()), ctypes.c_void_p(grads[1].data_ptr()), layers)
     ws = _train_workspace(bw, b, l, grad_hidden.device)
     check(lib.aspire_bert_layers_backward_f32(ctypes.byref(bw), ops._ptr(mask), b, l, ops._ptr(grad_hidden), ops._ptr(tape), tape.numel(),

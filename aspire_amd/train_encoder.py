@@ -15,7 +15,7 @@ import warnings
 import torch
 
 from . import ops
-from .encoder import _LAYER_KEYS
+from .encoder import _LAYER_KEYS, require_bert_base
 
 
 class HipBertTrainEncoder(torch.nn.Module):
@@ -26,12 +26,7 @@ class HipBertTrainEncoder(torch.nn.Module):
         if getattr(cfg, 'model_type', 'bert') in ('roberta', 'mpnet') or not hasattr(bert_model.embeddings, 'token_type_embeddings'):
             raise NotImplementedError(f'{type(bert_model).__name__}: the training encoder is built for BertModel (the position ids and the '
                                       'relative-position bias of aspire_bert_extras have no backward)')
-        if cfg.hidden_size != 768 or cfg.num_attention_heads != 12 or cfg.intermediate_size % 64:
-            raise NotImplementedError('only BERT-base geometry (hidden 768, 12 heads, intermediate_size % 64 == 0) is built')
-        if cfg.hidden_act != 'gelu':
-            raise NotImplementedError(f'hidden_act {cfg.hidden_act!r}: only erf-GELU is built')
-        if getattr(cfg, 'position_embedding_type', 'absolute') != 'absolute':
-            raise NotImplementedError('only absolute position embeddings are built')
+        require_bert_base(cfg, 64, 'HipBertTrainEncoder')
         if cfg.hidden_dropout_prob > 0 or cfg.attention_probs_dropout_prob > 0:
             warnings.warn(f'HipBertTrainEncoder: dropout is not built -- the model trains as with hidden_dropout_prob = '
                           f'attention_probs_dropout_prob = 0 (the config has {cfg.hidden_dropout_prob} / {cfg.attention_probs_dropout_prob})',
