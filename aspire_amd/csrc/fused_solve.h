@@ -232,9 +232,153 @@ __device__ __forceinline__ void solve_step(Solve& s, float r2, float h) {
     s.g = __builtin_elementwise_fma(f2_t{-h, -h}, lc, s.g);
 }
 
-// up to `n` more annealing steps (all of the rest with n < 0)
-template <int W>
-__device__ __forceinline__ void solve_steps_w(Solve& s, const ScoreArgs& a, int n) {
+// ---------------------------------------------------------------------------------------------------------------------
+// Solve16: the same solve with FOUR lanes per pair, sixteen pairs per wave.  Lane l of a pair's quad takes the place of li:
+// it owns rows 2 l, 2 l + 1 and all eight columns (column pair j = the entries lane (li, j) holds in the 16-lane layout).
+// Every sum is paired as the 16-lane layout pairs it, so a pair's bits do not depend on the layout:
+//   * row side (sum_lj): ((e0 + e1) + (e2 + e3)) + ((e4 + e5) + (e6 + e7)) in every lane -- formed in-lane here (sum_row8);
+//   * column side (sum_li): row_ror:4 then row_ror:8 give lane li (v_li + v_li-1) + (v_li-2 + v_li-3): two bit-variants by the
+//     parity of li, each lane keeping its own -- the quad rotations by one and by two (sum_q) give lane l the same variant.
+// The products that the compiler contracts in the 16-lane code (read from its assembly) are explicit fmas here and nothing
+// else is contracted.  That ties this code to what the compiler makes of Solve today: the sixteen-lane code is built with
+// contraction on, and a toolchain that contracts solve_begin / solve_step / solve_safe otherwise changes ITS bits, not these, and
+// the two forms part -- tests/test_gpu_fused_solve16.py (torch.equal between the forms) fails then, and the fix is to read the
+// new assembly and restate it here (or to write Solve with explicit fmas under contract(off) too, at the price of its bits).
+// As compiled: 102 issue slots per epsilon step for sixteen pairs as compiled (26 transcendental) against 4 x 31 (4 x 8).
+// ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float sum_q(float v) {        // all-reduce over a quad, paired as sum_li pairs the four li
+    v += dpp_mov<0x93>(v, v);                            // quad_perm:[3,0,1,2]: lane l reads lane l - 1
+    return v + dpp_mov<0x4E>(v, v);                      // quad_perm:[2,3,0,1]
+}
+__device__ __forceinline__ float max_q(float v) {
+    v = fmaxf(v, dpp_mov<0x93>(v, v));
+    return fmaxf(v, dpp_mov<0x4E>(v, v));
+}
+__device__ __forceinline__ float sum_row8(float p0, float p1, float p2, float p3) { return (p0 + p1) + (p2 + p3); }   // p_j = e_2j + e_2j+1
+
+struct Solve16 {
+    f2_t mc[2][4], neg[2][4];   // [x][j]: entries (2 l + x, 2 j), (2 l + x, 2 j + 1); masked as in Solve
+    f2_t wb[4], g[4];           // all eight columns (g: this lane's bit-variant of the column potentials)
+    f2_t wa, f;                 // the lane's two rows
+    float diam, r2, h;
+    int n_mid, k, max_steps, n_mid_lo;      // max_steps / n_mid_lo over the wave's sixteen schedules
+    unsigned valid;             // bit x: row 2 l + x valid, bit 2 + c: column c valid, bit 10: a document longer than the tile (poison)
+    int64_t out;
+};
+
+__device__ __forceinline__ void solve16_begin(Solve16& s, const ScoreArgs& a, const f2_t (&cost)[2][4], const f2_t (&neg)[2][4],
+                                              int q_len, int c_len, float diam) {
+#pragma clang fp contract(off)
+    const int l = threadIdx.x & 3;
+    bool rv[2], cv[8];
+#pragma unroll
+    for (int x = 0; x < 2; ++x) rv[x] = 2 * l + x < q_len;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) cv[c] = c < c_len;
+    s.diam = diam;
+    const float temp = (float)a.temp;
+    {
+        float qm[2], cm[8];
+#pragma unroll
+        for (int x = 0; x < 2; ++x) {
+            float m = (rv[x] && cv[0]) ? neg[x][0][0] : kNegBig;
+#pragma unroll
+            for (int c = 1; c < 8; ++c) m = fmaxf(m, (rv[x] && cv[c]) ? neg[x][c >> 1][c & 1] : kNegBig);
+            qm[x] = m / temp;
+        }
+#pragma unroll
+        for (int c = 0; c < 8; ++c)
+            cm[c] = max_q(fmaxf((rv[0] && cv[c]) ? neg[0][c >> 1][c & 1] : kNegBig, (rv[1] && cv[c]) ? neg[1][c >> 1][c & 1] : kNegBig)) / temp;
+        const float mq = max_q(fmaxf(rv[0] ? qm[0] : kNegBig, rv[1] ? qm[1] : kNegBig));
+        float mc = cv[0] ? cm[0] : kNegBig;
+#pragma unroll
+        for (int c = 1; c < 8; ++c) mc = fmaxf(mc, cv[c] ? cm[c] : kNegBig);
+        const float sq = (rv[0] ? fast_exp(qm[0] - mq) : 0.f) + (rv[1] ? fast_exp(qm[1] - mq) : 0.f);
+        float sc[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            sc[j] = (cv[2 * j] ? fast_exp(cm[2 * j] - mc) : 0.f) + (cv[2 * j + 1] ? fast_exp(cm[2 * j + 1] - mc) : 0.f);
+        // log_softmax: (q - max) - ln2 log2(sum), the product contracted into the subtraction
+        const float l2q = __builtin_amdgcn_logf(sum_q(sq)), l2c = __builtin_amdgcn_logf(sum_row8(sc[0], sc[1], sc[2], sc[3]));
+#pragma unroll
+        for (int t = 0; t < 2; ++t) s.wa[t] = rv[t] ? fast_exp(fmaf(-kLn2, l2q, qm[t] - mq)) : 0.f;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) s.wb[c >> 1][c & 1] = cv[c] ? fast_exp(fmaf(-kLn2, l2c, cm[c] - mc)) : 0.f;
+    }
+    s.valid = (rv[0] ? 1u : 0u) | (rv[1] ? 2u : 0u);
+#pragma unroll
+    for (int c = 0; c < 8; ++c) s.valid |= cv[c] ? 4u << c : 0u;
+    float ldf;
+    s.n_mid = schedule_mid_steps(a, diam, ldf);
+    int ms = s.n_mid, ml = s.n_mid;
+#pragma unroll
+    for (int m = 4; m < 64; m <<= 1) {
+        ms = max(ms, __shfl_xor(ms, m));
+        ml = min(ml, __shfl_xor(ml, m));
+    }
+    s.max_steps = __builtin_amdgcn_readfirstlane(ms) + 3;
+    s.n_mid_lo = __builtin_amdgcn_readfirstlane(ml);
+    s.k = 0;
+    const float r2_first = kLog2e * rcp_refined(diam), h_first = 0.5f * kLn2 * diam;
+    s.r2 = r2_first;
+    s.h = h_first;
+#pragma unroll
+    for (int x = 0; x < 2; ++x)
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            s.mc[x][c >> 1][c & 1] = (rv[x] && cv[c]) ? cost[x][c >> 1][c & 1] : 0.f;
+            s.neg[x][c >> 1][c & 1] = (rv[x] && cv[c]) ? neg[x][c >> 1][c & 1] : 0.f;
+        }
+    float rp[2][4], cs[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) cs[c] = 0.f;
+#pragma unroll
+    for (int x = 0; x < 2; ++x)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            rp[x][j] = 0.f;
+#pragma unroll
+            for (int y = 0; y < 2; ++y) {
+                const float k0 = __builtin_amdgcn_exp2f(-s.mc[x][j][y] * r2_first);
+                rp[x][j] = fmaf(s.wb[j][y], k0, rp[x][j]);
+                cs[2 * j + y] = fmaf(s.wa[x], k0, cs[2 * j + y]);
+            }
+        }
+#pragma unroll
+    for (int t = 0; t < 2; ++t) s.f[t] = -2.f * h_first * __builtin_amdgcn_logf(sum_row8(rp[t][0], rp[t][1], rp[t][2], rp[t][3]));
+#pragma unroll
+    for (int c = 0; c < 8; ++c) s.g[c >> 1][c & 1] = -2.f * h_first * __builtin_amdgcn_logf(sum_q(cs[c]));
+}
+
+// solve_step on the four-lane layout: the exponent is fma(C, -r2, fma(g, r2, f r2)) as the 16-lane step's compiled form has it
+template <int W = 1>
+__device__ __forceinline__ void solve_step(Solve16& s, float r2, float h) {
+#pragma clang fp contract(off)
+    const f2_t fr = s.f * r2, rr = {r2, r2}, nr = {-r2, -r2}, nh = {-h, -h};
+    float rp[2][4];
+    f2_t lc[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const f2_t a0 = __builtin_elementwise_fma(s.mc[0][j], nr, __builtin_elementwise_fma(s.g[j], rr, f2_t{fr.x, fr.x}));
+        const f2_t a1 = __builtin_elementwise_fma(s.mc[1][j], nr, __builtin_elementwise_fma(s.g[j], rr, f2_t{fr.y, fr.y}));
+        const f2_t k0 = {__builtin_amdgcn_exp2f(a0.x), __builtin_amdgcn_exp2f(a0.y)};
+        const f2_t k1 = {__builtin_amdgcn_exp2f(a1.x), __builtin_amdgcn_exp2f(a1.y)};
+        const f2_t t0 = k0 * s.wb[j], t1 = k1 * s.wb[j];
+        rp[0][j] = t0.x + t0.y;
+        rp[1][j] = t1.x + t1.y;
+        const f2_t cs = __builtin_elementwise_fma(k1, f2_t{s.wa.y, s.wa.y}, k0 * f2_t{s.wa.x, s.wa.x});
+        lc[j] = f2_t{__builtin_amdgcn_logf(sum_q(cs.x)), __builtin_amdgcn_logf(sum_q(cs.y))};
+    }
+    const f2_t lr = {__builtin_amdgcn_logf(sum_row8(rp[0][0], rp[0][1], rp[0][2], rp[0][3])),
+                     __builtin_amdgcn_logf(sum_row8(rp[1][0], rp[1][1], rp[1][2], rp[1][3]))};
+    s.f = __builtin_elementwise_fma(nh, lr, s.f);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s.g[j] = __builtin_elementwise_fma(nh, lc[j], s.g[j]);
+}
+
+// up to `n` more annealing steps (all of the rest with n < 0); S: Solve, or Solve16 with its own solve_step (W = 1)
+template <int W, class S>
+__device__ __forceinline__ void solve_steps_w(S& s, const ScoreArgs& a, int n) {
     const float scal = (float)a.scaling, inv_scal = (float)(1.0 / a.scaling);
     const float eb = (float)a.blur;
     const float r2_blur = kLog2e * rcp_refined(eb), h_blur = 0.5f * kLn2 * eb;
@@ -390,13 +534,133 @@ __device__ __forceinline__ void solve_finish(Solve& s, const ScoreArgs& a) {
     // finite (seen with a sentence shared by query and candidate on large vectors)
     bool bad = !(fabsf(score) < 1e30f);
     if (a.want != ASPIRE_OT_PLAN_SIM && (a.want == ASPIRE_OT_SIMILARITY ? score : -score) > 1e-2f) bad = true;
-    if (__any(bad && !(s.valid & 16u))) {
+    if (!a.no_repair && __any(bad && !(s.valid & 16u))) {
         const float again = solve_safe<XG>(s, a);
         if (bad) score = again;
     }
     // a document longer than the tile is never truncated silently: NaN, for the kernels queued behind this one (hybrid forms)
     if (s.valid & 16u) score = __builtin_nanf("");
     if (s.out >= 0 && (threadIdx.x & 15) == 0) a.scores[s.out] = score;
+}
+
+// ---- Solve16: score, safe re-solve, finish.  The score that is stored is the quad's lane 0, which sums what lane lp = 0 of the
+// 16-lane layout sums: its own rows' and all columns' terms, then the other lanes' row terms through the rotations ----
+__device__ __forceinline__ float solve16_output(const Solve16& s, const ScoreArgs& a, const f2_t f, const f2_t (&g)[4]) {
+#pragma clang fp contract(off)
+    const int l = threadIdx.x & 3;
+    const bool rv[2] = {(s.valid & 1u) != 0, (s.valid & 2u) != 0};
+    float b[4];         // what lane (l, j) of the 16-lane layout accumulates
+    if (a.want != ASPIRE_OT_PLAN_SIM) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float acc = 0.f;
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                acc += (j == 0 && rv[t]) ? s.wa[t] * f[t] : 0.f;
+                acc += (l == 0 && (s.valid & (4u << (2 * j + t)))) ? s.wb[j][t] * g[j][t] : 0.f;
+            }
+            b[j] = acc;
+        }
+    } else {
+        const float eb = (float)a.blur, rb = rcp_refined(eb);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float acc = 0.f;
+#pragma unroll
+            for (int x = 0; x < 2; ++x)
+#pragma unroll
+                for (int y = 0; y < 2; ++y) {
+                    const bool valid = rv[x] && (s.valid & (4u << (2 * j + y)));
+                    const float outer = valid ? f[x] + g[j][y] : 0.f;
+                    acc += fast_exp(div_r(outer + s.neg[x][j][y], eb, rb)) * (s.wa[x] * s.wb[j][y]) * s.neg[x][j][y];
+                }
+            b[j] = acc;
+        }
+    }
+    float score = sum_q(sum_row8(b[0], b[1], b[2], b[3]));
+    if (a.want == ASPIRE_OT_SIMILARITY) score = -score;
+    return score;
+}
+
+__device__ __forceinline__ float solve16_safe(Solve16& s, const ScoreArgs& a) {
+#pragma clang fp contract(off)
+    const bool rv[2] = {(s.valid & 1u) != 0, (s.valid & 2u) != 0};
+    float la[2], lb[8], f[2], g[8];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        la[t] = (rv[t] && s.wa[t] > 0.f) ? logf(s.wa[t]) : -100000.f;
+        f[t] = 0.f;
+    }
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const float w = s.wb[c >> 1][c & 1];
+        lb[c] = ((s.valid & (4u << c)) && w > 0.f) ? logf(w) : -100000.f;
+        g[c] = 0.f;
+    }
+    auto softmins = [&](float eps, const float (&fi)[2], const float (&gi)[8], float (&ft)[2], float (&gt)[8]) {
+#pragma clang fp contract(off)
+        const float re = 1.0f / eps;
+        float ar[2][8], ac[2][8];
+#pragma unroll
+        for (int x = 0; x < 2; ++x)
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                ar[x][c] = fmaf(gi[c] - s.mc[x][c >> 1][c & 1], re, lb[c]);
+                ac[x][c] = fmaf(fi[x] - s.mc[x][c >> 1][c & 1], re, la[x]);
+            }
+#pragma unroll
+        for (int x = 0; x < 2; ++x) {
+            float m = ar[x][0];
+#pragma unroll
+            for (int c = 1; c < 8; ++c) m = fmaxf(m, ar[x][c]);
+            float p[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) p[j] = expf(ar[x][2 * j] - m) + expf(ar[x][2 * j + 1] - m);
+            ft[x] = -eps * (m + logf(sum_row8(p[0], p[1], p[2], p[3])));
+        }
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            const float m = max_q(fmaxf(ac[0][c], ac[1][c]));
+            const float e = sum_q(expf(ac[0][c] - m) + expf(ac[1][c] - m));
+            gt[c] = -eps * (m + logf(e));
+        }
+    };
+    int n_max = s.n_mid;
+#pragma unroll
+    for (int m = 4; m < 64; m <<= 1) n_max = max(n_max, __shfl_xor(n_max, m));
+    n_max = __builtin_amdgcn_readfirstlane(n_max);
+    const float eb = (float)a.blur, scal = (float)a.scaling;
+    float ft[2], gt[8];
+    float eps = s.diam;
+    // one loop for the initialisation (k = -1: potentials taken over), the averaged steps and the last extrapolation
+    // (k = n_max + 2: both from the previous pair, kept apart in ft / gt): one copy of the softmins in the code
+#pragma unroll 1
+    for (int k = -1; k <= n_max + 2; ++k) {
+        const bool mine = k <= s.n_mid + 1;
+        const float e = (k > s.n_mid || k > n_max + 1) ? eb : eps;
+        softmins(e, f, g, ft, gt);
+        if (k > n_max + 1) break;
+#pragma unroll
+        for (int t = 0; t < 2; ++t) f[t] = k < 0 ? ft[t] : mine ? 0.5f * (f[t] + ft[t]) : f[t];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) g[c] = k < 0 ? gt[c] : mine ? 0.5f * (g[c] + gt[c]) : g[c];
+        if (k >= 1) eps *= scal;
+    }
+    const f2_t go[4] = {f2_t{gt[0], gt[1]}, f2_t{gt[2], gt[3]}, f2_t{gt[4], gt[5]}, f2_t{gt[6], gt[7]}};
+    return solve16_output(s, a, f2_t{ft[0], ft[1]}, go);
+}
+
+__device__ __forceinline__ void solve16_finish(Solve16& s, const ScoreArgs& a) {
+    solve_steps_w<1>(s, a, -1);
+    float score = solve16_output(s, a, s.f, s.g);
+    bool bad = !(fabsf(score) < 1e30f);        // as solve_finish
+    if (a.want != ASPIRE_OT_PLAN_SIM && (a.want == ASPIRE_OT_SIMILARITY ? score : -score) > 1e-2f) bad = true;
+    if (!a.no_repair && __any(bad && !(s.valid & 1024u))) {
+        const float again = solve16_safe(s, a);
+        if (bad) score = again;
+    }
+    if (s.valid & 1024u) score = __builtin_nanf("");
+    if (s.out >= 0 && (threadIdx.x & 3) == 0) a.scores[s.out] = score;
 }
 
 }  // namespace

@@ -58,6 +58,12 @@ bool apply_tuning(Tuning& t, const char* key, const char* v) {
         t.fused_nosolve = unset ? 0 : atoi(v);
     } else if (!strcmp(key, "FUSED_NOSELF")) {
         t.fused_noself = unset ? 0 : atoi(v);
+    } else if (!strcmp(key, "FUSED_SOLVE16")) {
+        const int f = unset ? -1 : atoi(v);
+        if (f < -1 || f > 1 || (!unset && strcmp(v, "0") && strcmp(v, "1"))) return false;
+        t.fused_solve16 = f;
+    } else if (!strcmp(key, "FUSED_NOREPAIR")) {
+        t.fused_norepair = unset ? 0 : atoi(v);
     } else if (!strcmp(key, "FUSED_WAVES")) {
         t.fused_waves = unset ? 0 : atoi(v);
     } else if (!strcmp(key, "FUSED_SPLIT")) {
@@ -106,6 +112,12 @@ bool render_tuning(const Tuning& t, const char* key, char* buf, size_t len) {
     else if (!strcmp(key, "FUSED_VALU")) v = number(t.fused_valu);
     else if (!strcmp(key, "FUSED_NOSOLVE")) v = number(t.fused_nosolve);
     else if (!strcmp(key, "FUSED_NOSELF")) v = number(t.fused_noself);
+    else if (!strcmp(key, "FUSED_SOLVE16")) v = t.fused_solve16 < 0 ? "" : t.fused_solve16 ? "1" : "0";
+    else if (!strcmp(key, "FUSED_NOREPAIR")) v = number(t.fused_norepair);
+    else if (!strcmp(key, "FUSED_SOLVE16_LAUNCHES")) {      // read-only
+        snprintf(num, sizeof(num), "%lld", solve16_launches());
+        v = num;
+    }
     else if (!strcmp(key, "FUSED_WAVES")) v = number(t.fused_waves);
     else if (!strcmp(key, "FUSED_SPLIT")) v = number(t.fused_split);
     else if (!strcmp(key, "SPLIT_PRIO")) v = number(t.split_prio);
@@ -119,7 +131,7 @@ bool render_tuning(const Tuning& t, const char* key, char* buf, size_t len) {
 }
 
 void tuning_from_env() {
-    static const char* keys[] = {"SINKHORN", "COST_PATH", "COST1_BLOCKS", "ATTN", "GEMM_TILE", "GEMM_RING", "GEMM_LN", "GEMM_PROBE", "GEMM", "OT_FORM", "FUSED_VALU", "FUSED_NOSOLVE", "FUSED_WAVES", "FUSED_SPLIT", "SPLIT_PRIO", "FUSED_NOSELF", "GRAM_TILE", "GRAM_RING", "GRAM_PP"};
+    static const char* keys[] = {"SINKHORN", "COST_PATH", "COST1_BLOCKS", "ATTN", "GEMM_TILE", "GEMM_RING", "GEMM_LN", "GEMM_PROBE", "GEMM", "OT_FORM", "FUSED_VALU", "FUSED_NOSOLVE", "FUSED_SOLVE16", "FUSED_NOREPAIR", "FUSED_WAVES", "FUSED_SPLIT", "SPLIT_PRIO", "FUSED_NOSELF", "GRAM_TILE", "GRAM_RING", "GRAM_PP"};
     for (const char* k : keys) {
         char name[64];
         snprintf(name, sizeof(name), "ASPIRE_HIP_%s", k);

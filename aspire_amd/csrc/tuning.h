@@ -27,12 +27,16 @@ struct Tuning {
     int gram_tile = 0;       // ASPIRE_HIP_GRAM_TILE=128128 | 128256 | 256256: candidate x query rows per tile of the fp16-plane cost tiles (0: by shape)
     int gram_pp = 0;         // ASPIRE_HIP_GRAM_PP=1: the 256 x 256 tiles in the ping-pong form (two wave groups a segment apart)
     int gram_ring = 0;       // ASPIRE_HIP_GRAM_RING=4: four-stage ring for the 256 x 256 tiles (default 3)
+    int fused_solve16 = -1;  // ASPIRE_HIP_FUSED_SOLVE16: the SELF form's solve: 0 sixteen lanes per pair, sliced through the next item's stages; 1 four lanes per pair, sixteen pairs per wave behind a super-item of sixteen candidates (Solve16); unset (-1): 1 for a launch on another stream than the previous one (calls in flight), else 0 (fused.hip: solve16_wanted)
+    int fused_norepair = 0;  // ASPIRE_HIP_FUSED_NOREPAIR=1: the fused kernel skips the in-wave re-solve of poisoned pairs (tests: which pairs reach it; invalid scores)
     int fused_waves = 0;     // ASPIRE_HIP_FUSED_WAVES: cap on the fused kernel's resident waves (0 = default; grid experiments)
     int fused_split = 0;     // ASPIRE_HIP_FUSED_SPLIT: 0 / 2 the fused kernel, 1 the role-split kernel where it applies -- ONLY in the experiment build (tools/experiments/split/build.sh: -DASPIRE_EXPERIMENT_SPLIT); ignored by the product library
     int split_prio = 0;      // ASPIRE_HIP_SPLIT_PRIO: the role-split kernel's solver mode: 0 solve, 3 skip the solves (timing probe: wrong scores)
 };
 
 const Tuning& tuning();
+// launches of the fused kernel's Solve16 form so far in this process (aspire_debug_get("FUSED_SOLVE16_LAUNCHES"): tests of the form rule)
+long long solve16_launches();
 // key = the environment variable's name without the ASPIRE_HIP_ prefix (e.g. "SINKHORN"), value as in the environment;
 // value NULL or "" restores the default.  Returns false on an unknown key / value.
 bool tuning_set(const char* key, const char* value);
