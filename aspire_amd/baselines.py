@@ -16,9 +16,9 @@ evaluate.score(..., method='l2max') for BertMLM / BertNER and method='cosine' fo
 import numpy as np
 import torch
 
-from .batch_prep import (MAX_NUM_TOKS, _with_special_tokens, _word_pieces, pad_sentences, prepare_eval_ner_seqs, prepare_eval_seqs,
-                         sentence_buckets)
+from .batch_prep import MAX_NUM_TOKS, _with_special_tokens, _word_pieces, prepare_eval_ner_seqs, prepare_eval_seqs
 from .encoder import HipBertEncoder
+from .model_front import EncoderFront, add_to_store, check_pid_count, encode_bucketed, load_hf, per_paper
 
 
 def neg_euclidean(x, y):
@@ -30,7 +30,7 @@ def neg_euclidean(x, y):
     return -float(np.linalg.norm(x - y))
 
 
-class BertMLM:
+class BertMLM(EncoderFront):
     """'specter' (models.py:237-320)."""
     MODEL_PATHS = {
         'specter': 'allenai/specter',
@@ -48,19 +48,10 @@ class BertMLM:
         """
         self.name = name
         self.bert_max_seq_len = MAX_NUM_TOKS
-        if bert_model is None or tokenizer is None:
-            full_name = hf_model_name if hf_model_name is not None else self.MODEL_PATHS[name]
-            if bert_model is None:
-                from transformers import AutoModel
-                bert_model = AutoModel.from_pretrained(full_name)
-            if tokenizer is None:
-                from transformers import AutoTokenizer
-                tokenizer = AutoTokenizer.from_pretrained(full_name)
-        self.tokenizer = tokenizer
+        if hf_model_name is None and (bert_model is None or tokenizer is None):
+            hf_model_name = self.MODEL_PATHS[name]
+        bert_model, self.tokenizer = load_hf(hf_model_name, bert_model, tokenizer)
         self.bert_encoder = HipBertEncoder(bert_model)
-
-    def eval(self):
-        return self
 
     def _bert_batch(self, batch_papers):
         """_pre_process_input_batch + _prepare_batch (models.py:259-298)."""
@@ -72,9 +63,8 @@ class BertMLM:
             return torch.zeros(0, 768)
         bb = self._bert_batch(batch_papers)
         enc = self.bert_encoder
-        tok, typ, msk = enc.device_inputs(bb['tokid_tt'], bb['seg_tt'], bb['attnmask_tt'])
-        return enc.checked(lambda: enc.forward_cls(tok, typ, msk, check_ids=False)[0], lambda out: bool(torch.isfinite(out).all()),
-                           type(self).__name__).cpu()
+        return self._checked_read(lambda tok, typ, msk: enc.forward_cls(tok, typ, msk, check_ids=False)[0], lambda out: out,
+                                  bb['tokid_tt'], bb['seg_tt'], bb['attnmask_tt']).cpu()
 
     @staticmethod
     def get_similarity(x, y):
@@ -90,16 +80,15 @@ class BertMLM:
         """Every paper encoded (`batch_size` at a time: SimilarityModel's batch_size, models.py:34) into one [1, 768] block under
         pids[j].  Returns the RepStore (new, or `store` with the reps added): evaluate.score(..., method='l2max') then ranks a pool
         by -cdist of the 1 x 1 pair = -euclidean, this class's get_similarity (the route AspireBiEnc.encode_to_store documents)."""
-        from .repstore import RepStore
         papers, pids = list(papers), list(pids)
-        if len(papers) != len(pids):
-            raise ValueError(f'{len(pids)} pids for {len(papers)} papers')
-        store = RepStore() if store is None else store
-        for lo in range(0, len(papers), batch_size):
-            reps = self.encode(papers[lo:lo + batch_size]).numpy()
-            for i in range(reps.shape[0]):
-                store.add(pids[lo + i], reps[i:i + 1])
-        return store
+        check_pid_count(pids, len(papers))
+
+        def blocks():
+            for lo in range(0, len(papers), batch_size):
+                reps = self.encode(papers[lo:lo + batch_size]).numpy()
+                for i in range(reps.shape[0]):
+                    yield reps[i:i + 1]
+        return add_to_store(store, pids, blocks())
 
 
 class BertNER(BertMLM):
@@ -129,9 +118,8 @@ class SimCSE(BertMLM):
         """int64 [B, L] -> pooler_output [B, 768] on the GPU, under the encoder's fall-back rule (encoder.run_checked) -- which
         judges the CLS rows: tanh maps an overflowed activation to +-1, the pooled rows of a broken forward can all be finite."""
         enc = self.bert_encoder
-        tok, typ, msk = enc.device_inputs(tokid_tt, token_type_ids, attention_mask)
-        return enc.checked(lambda: enc.forward_pooled(tok, typ, msk, check_ids=False), lambda r: bool(torch.isfinite(r[0]).all()),
-                           'SimCSE')[1]
+        return self._checked_read(lambda tok, typ, msk: enc.forward_pooled(tok, typ, msk, check_ids=False), lambda r: r[0],
+                                  tokid_tt, token_type_ids, attention_mask, 'SimCSE')[1]
 
     def _encode_sentences(self, sents, max_tokens=16384):
         """pooler_output of every string, float32 [N, 768] (numpy) in input order.  _prepare_batch's tokenisation (models.py:259-293:
@@ -139,25 +127,16 @@ class SimCSE(BertMLM):
         vocabularies pad with id 0), so instead of one batch of all sentences padded to the longest, everything is tokenised once,
         sorted by length and cut into encoder calls of at most `max_tokens` padded token rows (batch_prep.sentence_buckets), as
         AspireSentEnc.encode does."""
-        dev = self.bert_encoder.device
-        out = torch.empty(len(sents), 768, device=dev, dtype=torch.float32)
         ids = [_with_special_tokens(self.tokenizer, piece_ids[:self.bert_max_seq_len])
                for _, piece_ids in _word_pieces(self.tokenizer, list(sents), want_text=False)]
         types = [[0] * len(x) for x in ids]
-        for run in sentence_buckets([len(x) for x in ids], max_tokens):
-            out[torch.from_numpy(run).to(dev)] = self._pooled_checked(*pad_sentences(ids, types, run, self.tokenizer.pad_token_id))
-        return out.cpu().numpy()
+        return encode_bucketed(self._pooled_checked, ids, types, self.tokenizer.pad_token_id, max_tokens,
+                               self.bert_encoder.device).cpu().numpy()
 
     def encode(self, batch_papers):
         """SimCSE.encode (models.py:326-357): the ABSTRACT sentences of all papers encoded, split back per paper with np.split
         semantics -> list of float32 [n_sents, 768] (a paper without sentences: [0, 768])."""
-        batch, splits, cur = [], [], 0
-        for paper in batch_papers:
-            batch += list(paper['ABSTRACT'])
-            cur += len(paper['ABSTRACT'])
-            splits.append(cur)
-        reps = self._encode_sentences(batch) if batch else np.zeros((0, 768), np.float32)
-        return np.split(reps, splits[:-1])
+        return per_paper(batch_papers, self._encode_sentences)
 
     @staticmethod
     def get_similarity(x, y):
@@ -173,11 +152,6 @@ class SimCSE(BertMLM):
         """Every paper's ABSTRACT sentences encoded (one encode call for the lot), one [n_sents, 768] row block per paper under
         pids[j] (what write_wholeabs_reps stores).  Returns the RepStore (new, or `store` with the reps added), ready for
         evaluate.score(..., method='cosine')."""
-        from .repstore import RepStore
         papers, pids = list(papers), list(pids)
-        if len(papers) != len(pids):
-            raise ValueError(f'{len(pids)} pids for {len(papers)} papers')
-        store = RepStore() if store is None else store
-        for pid, reps in zip(pids, self.encode(papers)):
-            store.add(pid, reps)
-        return store
+        check_pid_count(pids, len(papers))
+        return add_to_store(store, pids, self.encode(papers))

@@ -18,27 +18,21 @@ import torch
 from . import ops
 from .batch_prep import batch_tensors
 from .encoder import HipBertEncoder
+from .model_front import EncoderFront, add_to_store, load_hf, refuse_keys, strip_prefix
 
 
 def split_state_dict(sd):
     """The reference's state dict (AspireBiEnc / MySPECTER) -> (the BertModel's own state dict, layer weights [1, n + 1] or None).
     Keys: ``bert_encoder.<BertModel key>`` and ``bert_layer_weights.weight``; anything else is an error."""
-    enc, mix, other = {}, None, []
-    for k, v in sd.items():
-        if k.startswith('bert_encoder.'):
-            enc[k[len('bert_encoder.'):]] = v
-        elif k == 'bert_layer_weights.weight':
-            mix = v
-        else:
-            other.append(k)
-    if other:
-        raise KeyError(f'unexpected keys in the bi-encoder state dict: {other}')
+    enc, other = strip_prefix(sd, 'bert_encoder.')
+    refuse_keys([k for k in other if k != 'bert_layer_weights.weight'], 'bi-encoder')
+    mix = sd.get('bert_layer_weights.weight')
     if mix is not None and (mix.dim() != 2 or mix.shape[0] != 1):
         raise ValueError(f'bert_layer_weights.weight: expected [1, n_layers + 1], got {tuple(mix.shape)}')
     return enc, mix
 
 
-class AspireBiEnc:
+class AspireBiEnc(EncoderFront):
     def __init__(self, model_hparams=None, bert_model=None, layer_weights=None):
         """
         :param model_hparams: dict with 'base-pt-layer' (the HF model the reference loads, ex_aspire_bienc.py:40).
@@ -46,17 +40,12 @@ class AspireBiEnc:
         :param layer_weights: the SoftmaxMixLayers weight [1, n_layers + 1] (before the softmax), or None: last_hidden_state[:, 0].
         """
         self.bert_encoding_dim = 768
-        if bert_model is None:
-            from transformers import AutoModel
-            bert_model = AutoModel.from_pretrained(model_hparams['base-pt-layer'])
-        self.bert_encoder = HipBertEncoder(bert_model)
+        name = model_hparams['base-pt-layer'] if bert_model is None else None
+        self.bert_encoder = HipBertEncoder(load_hf(name, bert_model, want_tokenizer=False)[0])
         self.bert_layer_count = self.bert_encoder.config.num_hidden_layers + 1   # plus 1 for the bottom most layer
         self.layer_weights = None
         if layer_weights is not None:
             self.set_layer_weights(layer_weights)
-
-    def eval(self):
-        return self
 
     def set_layer_weights(self, w):
         w = torch.as_tensor(w).detach().to('cpu', torch.float32).reshape(1, -1)
@@ -85,20 +74,14 @@ class AspireBiEnc:
     def forward_device(self, tokid_tt, token_type_ids=None, attention_mask=None, want_layers=False):
         """int64 [B, L] tensors (any device) -> (cls reps [B, 768], the CLS rows of every hidden state [n_layers + 1, B, 768] or None),
         on the GPU, under the encoder's fall-back rule (encoder.run_checked)."""
-        enc = self.bert_encoder
-        tok, typ, msk = enc.device_inputs(tokid_tt, token_type_ids, attention_mask)
-        mix = self.layer_mix()
-        return enc.checked(lambda: enc.forward_cls(tok, typ, msk, mix, want_layers, check_ids=False),
-                           lambda r: bool(torch.isfinite(r[0]).all()) and (r[1] is None or bool(torch.isfinite(r[1]).all())),
-                           'AspireBiEnc')
+        enc, mix = self.bert_encoder, self.layer_mix()
+        return self._checked_read(lambda tok, typ, msk: enc.forward_cls(tok, typ, msk, mix, want_layers, check_ids=False),
+                                  lambda r: r, tokid_tt, token_type_ids, attention_mask, 'AspireBiEnc')      # both outputs judged
 
     def forward(self, bert_batch):
         """AspireBiEnc.forward (ex_aspire_bienc.py:46-58): [B, 768] CLS reps, on the device of the input ids."""
         tok, typ, msk = batch_tensors(bert_batch)
         return self.forward_device(tok, typ, msk)[0].to(tok.device)
-
-    def __call__(self, bert_batch):
-        return self.forward(bert_batch)
 
     def partial_forward(self, bert_batch):
         """MySPECTER.partial_forward (disent_models.py:164-176): [B, 768] on the GPU (a 1-document batch stays [1, 768])."""
@@ -130,15 +113,9 @@ class AspireBiEnc:
         """Every bert_batch of `batches` (prepare_abstract_seqs / prepare_eval_seqs / an HF tokenizer dict) encoded; document j
         overall gets pid pids[j] with a [1, 768] rep.  Returns the RepStore (new, or `store` with the reps added): evaluate.score(...,
         method='l2max') then ranks a pool by -cdist of the 1 x 1 pair = -euclidean, TrainedAbstractModel.get_similarity (models.py:565)."""
-        from .repstore import RepStore
-        store = RepStore() if store is None else store
-        pids = list(pids)
-        j = 0
-        for bb in batches:
-            reps = self.partial_forward(bb).cpu().numpy()
-            for i in range(reps.shape[0]):
-                store.add(pids[j], reps[i:i + 1])
-                j += 1
-        if j != len(pids):
-            raise ValueError(f'{len(pids)} pids for {j} documents')
-        return store
+        def blocks():
+            for bb in batches:
+                reps = self.partial_forward(bb).cpu().numpy()
+                for i in range(reps.shape[0]):
+                    yield reps[i:i + 1]
+        return add_to_store(store, pids, blocks(), 'documents')

@@ -25,9 +25,10 @@ import torch
 from . import ops
 from .batch_prep import spans_to_csr
 from .encoder import HipBertEncoder
+from .model_front import EncoderFront, all_finite, check_token_ids, finish_pool, load_hf, pool_layout
 
 
-class AspireConSent:
+class AspireConSent(EncoderFront):
     def __init__(self, hf_model_name=None, bert_model=None):
         """
         :param hf_model_name: HuggingFace model name or path, loaded like the reference does (:33).
@@ -35,16 +36,7 @@ class AspireConSent:
         """
         self.bert_encoding_dim = 768
         self.bert_layer_count = 12 + 1  # plus 1 for the bottom most layer.
-        if bert_model is None:
-            from transformers import AutoModel
-            bert_model = AutoModel.from_pretrained(hf_model_name)
-        self.bert_encoder = HipBertEncoder(bert_model)
-
-    def eval(self):
-        return self
-
-    def __call__(self, *args, **kwargs):
-        return self.forward(*args, **kwargs)
+        self.bert_encoder = HipBertEncoder(load_hf(hf_model_name, bert_model, want_tokenizer=False)[0])
 
     def forward(self, bert_batch, abs_lens, sent_tok_idxs):
         """
@@ -77,8 +69,7 @@ class AspireConSent:
         def run():
             return ops.span_mean_pool(enc.forward_hidden(tok, typ, msk, check_ids=False), tok_idx, span_off, max_sents)
         # (the CLS token belongs to no sentence span: both outputs are checked)
-        doc_cls_reps, sent_reps = enc.checked(run, lambda r: bool(torch.isfinite(r[1]).all() & torch.isfinite(r[0]).all()),
-                                              'AspireConSent')
+        doc_cls_reps, sent_reps = enc.checked(run, lambda r: all_finite(*r), 'AspireConSent')
         # the reference squeezes and re-unsqueezes (:76, :46-49): shapes are [B,768] and [B,S,768] for every B.
         return doc_cls_reps.to(out_dev), sent_reps.to(out_dev)
 
@@ -223,22 +214,11 @@ class AspireConSent:
         The finished store goes through the encoder's fall-back rule (encoder.run_checked) once: one status read and one range check
         for the whole corpus; a re-run encodes everything again and its events replace the first run's.
         Returns a scorer.CandidatePool (and the [N, 768] CLS reps on the GPU with want_cls)."""
-        from .scorer import CandidatePool
         dev = ops.require_gpu()
         batches = list(batches)
         all_lens = [int(n) for _, abs_lens, _ in batches for n in abs_lens]       # corpus order
-        n_docs, total = len(all_lens), int(sum(all_lens))
-        lens_t = torch.tensor(all_lens, dtype=torch.int32)
-        start_t = (torch.cumsum(lens_t, 0) - lens_t).to(torch.int32)
-        # token ids of every batch validated with ONE device round trip (nn.Embedding raises IndexError on the reference path);
-        # per batch that check is a host sync in front of every encoder call
-        if batches:
-            # (64 batches' ids flattened into one tensor per reduction: per batch it was two tiny kernels each, ~1000 launches in
-            # front of the first encoder call of a 16 384-document corpus)
-            lo_hi = torch.stack([torch.stack(torch.aminmax(torch.cat([bb['tokid_tt'].reshape(-1) for bb, _, _ in batches[i:i + 64]]))).to(dev)
-                                 for i in range(0, len(batches), 64)])
-            if int(lo_hi[:, 0].min()) < 0 or int(lo_hi[:, 1].max()) >= self.bert_encoder.config.vocab_size:
-                raise IndexError('token id out of range')
+        lens_t, start_t, total = pool_layout(all_lens)
+        check_token_ids((bb['tokid_tt'] for bb, _, _ in batches), self.bert_encoder.config.vocab_size, dev)
         n_events = len(stage_events) if stage_events is not None else 0
 
         def fill():
@@ -246,17 +226,8 @@ class AspireConSent:
                 del stage_events[n_events:]
             return self._fill_store(batches, start_t.numpy(), total, want_cls, docs_per_forward, sort_by_length, rows_per_forward,
                                     streams, stage_events)
-        if total:
-            rows, cls_all = self.bert_encoder.checked(
-                fill, lambda r: bool(torch.isfinite(r[0]).all() & (torch.isfinite(r[1]).all() if want_cls else True)),
-                'AspireConSent.encode_to_pool')
-        else:
-            rows, cls_all = fill()
-        repset = ops.DeviceRepSet(rows, start_t.to(dev), lens_t.to(dev), ext=0, max_len=max(all_lens) if all_lens else 0,
-                                  lens_host=all_lens)
-        pool = CandidatePool.from_repset(repset, pids=pids)
-        if planes and total:
-            pool.prepare_planes()
+        rows, cls_all = self._checked_fill(fill, total, 'AspireConSent.encode_to_pool')       # (cls_all: None without want_cls)
+        pool = finish_pool(rows, lens_t, start_t, all_lens, pids, planes)
         return (pool, cls_all) if want_cls else pool
 
     def _fill_store(self, batches, start_np, total, want_cls, docs_per_forward, sort_by_length, rows_per_forward, streams,

@@ -25,16 +25,17 @@ from . import ops
 from .batch_prep import append_entities, prepare_abstracts_entities, span_range_tables
 from .consent import AspireConSent
 from .encoder import HipBertEncoder
+from .model_front import (EncoderFront, add_to_store, all_finite, check_pid_count, check_token_ids, facet_sentence_ids, finish_pool,
+                          load_hf, ot_similarity, pool_layout)
 
 
 # ---- the 'sentence-entity' facet filter (host side, integers only) ---------------------------------------------------------
 def facet_row_ids(facet_labels, entities, facet):
     """SimilarityModel.get_faceted_encoding for encoding type 'sentence-entity' (models.py:127-163) as row numbers: the sentences
-    labelled `<facet>_label` ('objective_label' counts as background), then the entity rows of those sentences, entity rows being
+    labelled `<facet>_label` (model_front.facet_sentence_ids), then the entity rows of those sentences, entity rows being
     counted from len(facet_labels) in sentence order.  entities: per sentence the list of its entities (only its length is used)."""
-    labels = ['background' if lab == 'objective_label' else lab[:-len('_label')] for lab in facet_labels]
-    sent_ids = [i for i, k in enumerate(labels) if facet == k]
-    ner_cur_id = len(labels)
+    sent_ids = facet_sentence_ids(facet_labels, facet)
+    ner_cur_id = len(facet_labels)
     ner_ids = []
     for i, sent_ners in enumerate(entities):
         if i in sent_ids:
@@ -68,7 +69,7 @@ def _pooling_tables(sent_tok_idxs, ner_tok_idxs, max_seq_len, dev, row_base=None
     return (flat[0], flat[1], flat[2], flat[3] if out_row is not None else None), n_entities
 
 
-class AspireConSenContextual:
+class AspireConSenContextual(EncoderFront):
     """Drop-in for the class of the same name (models.py:413-508): contextual sentence reps and contextual entity reps from one
     BERT forward."""
 
@@ -79,16 +80,7 @@ class AspireConSenContextual:
         """
         self.bert_encoding_dim = 768
         self.bert_layer_count = 12 + 1  # plus 1 for the bottom most layer.
-        if bert_model is None:
-            from transformers import AutoModel
-            bert_model = AutoModel.from_pretrained(hf_model_name)
-        self.bert_encoder = HipBertEncoder(bert_model)
-
-    def eval(self):
-        return self
-
-    def __call__(self, *args, **kwargs):
-        return self.forward(*args, **kwargs)
+        self.bert_encoder = HipBertEncoder(load_hf(hf_model_name, bert_model, want_tokenizer=False)[0])
 
     def forward(self, bert_batch, abs_lens, sent_tok_idxs, ner_tok_idxs):
         """
@@ -132,8 +124,7 @@ class AspireConSenContextual:
             ops.span_pool_ranges(enc.forward_hidden(tok, typ, msk, check_ids=False), doc, start, length, rows=rows, out_row=out_row,
                                  cls=cls)
             return cls, rows
-        doc_cls_reps, rows = enc.checked(run, lambda r: bool(torch.isfinite(r[1]).all() & torch.isfinite(r[0]).all()),
-                                         'AspireConSenContextual')
+        doc_cls_reps, rows = enc.checked(run, lambda r: all_finite(*r), 'AspireConSenContextual')
         sent_reps = rows[:n_sent_rows].view(batch_size, max_sents, 768).to(out_dev)
         ner_rows = rows[n_sent_rows:].to(out_dev)
         ner_reps, e = [], 0
@@ -152,12 +143,7 @@ class AspireConSenContextual:
 class _SentenceEntityModel:
     """What the two 'sentence-entity' models share: otAspire as the similarity and the base facet filter."""
     encoding_type = 'sentence-entity'
-
-    @staticmethod
-    def get_similarity(x, y):
-        """AspireModel.get_similarity (models.py:190-197): the negative Wasserstein distance of two [n, 768] rep matrices."""
-        from .scorer import get_similarity
-        return get_similarity(x, y)
+    get_similarity = staticmethod(ot_similarity)
 
     def get_faceted_encoding(self, unfaceted_encoding, facet, input_data):
         """SimilarityModel.get_faceted_encoding (models.py:127-163): the rows of the facet's sentences and of their entities."""
@@ -169,11 +155,8 @@ class AspireNER(_SentenceEntityModel):
 
     def __init__(self, hf_model_name=None, bert_model=None, tokenizer=None, name='aspire_ner_compsci'):
         self.name = name
-        if tokenizer is None and hf_model_name is not None:
-            from transformers import AutoTokenizer
-            tokenizer = AutoTokenizer.from_pretrained(hf_model_name)
-        self.tokenizer = tokenizer
-        self.model = AspireConSent(hf_model_name=hf_model_name, bert_model=bert_model)
+        bert_model, self.tokenizer = load_hf(hf_model_name, bert_model, tokenizer)
+        self.model = AspireConSent(bert_model=bert_model)
 
     def encode(self, batch_papers, tokenizer=None):
         """:return: per paper [n_kept_sentences (abstract sentences, then entity strings), 768]"""
@@ -192,11 +175,8 @@ class AspireContextNER(_SentenceEntityModel):
         :param tokenizer: default AutoTokenizer.from_pretrained(hf_model_name).
         """
         self.name = name
-        if tokenizer is None and hf_model_name is not None:
-            from transformers import AutoTokenizer
-            tokenizer = AutoTokenizer.from_pretrained(hf_model_name)
-        self.tokenizer = tokenizer
-        self.model = AspireConSenContextual(hf_model_name=hf_model_name, bert_model=bert_model)
+        bert_model, self.tokenizer = load_hf(hf_model_name, bert_model, tokenizer)
+        self.model = AspireConSenContextual(bert_model=bert_model)
 
     def _preprocess_input(self, input_data):
         return prepare_abstracts_entities(input_data, self.tokenizer)
@@ -212,12 +192,12 @@ class AspireContextNER(_SentenceEntityModel):
         """models.py:620-639: papers -> per paper [n_sents + n_valid_entities, 768] (sentence rows, then the rows of the entities
         that have token positions, in order), on the CPU like the reference's."""
         bert_batch, abs_lens, sent_idxs, ner_idxs = self._preprocess_input(input_data)
-        enc = self.model.bert_encoder
-        tok, typ, msk = enc.device_inputs(bert_batch['tokid_tt'], bert_batch['seg_tt'], bert_batch['attnmask_tt'])
-        (doc, start, length, _), n_entities = _pooling_tables(sent_idxs, ner_idxs, tok.shape[1], enc.device)
-        rows = enc.checked(lambda: ops.span_pool_ranges(enc.forward_hidden(tok, typ, msk, check_ids=False), doc, start, length),
-                           lambda r: bool(torch.isfinite(r).all()), 'AspireContextNER')
-        rows = rows.to(bert_batch['tokid_tt'].device)
+        enc, tokid_tt = self.model.bert_encoder, bert_batch['tokid_tt']
+        (doc, start, length, _), n_entities = _pooling_tables(sent_idxs, ner_idxs, tokid_tt.shape[1], enc.device)
+        rows = self.model._checked_read(
+            lambda tok, typ, msk: ops.span_pool_ranges(enc.forward_hidden(tok, typ, msk, check_ids=False), doc, start, length),
+            lambda r: r, tokid_tt, bert_batch['seg_tt'], bert_batch['attnmask_tt'], 'AspireContextNER')
+        rows = rows.to(tokid_tt.device)
         return list(torch.split(rows, [n + e for n, e in zip(abs_lens, n_entities)]))
 
     def get_faceted_encoding(self, unfaceted_encoding, facet, input_data):
@@ -240,7 +220,6 @@ class AspireContextNER(_SentenceEntityModel):
         planes: also keep the rows as fp16 planes (CandidatePool.prepare_planes).
         Returns (scorer.CandidatePool, layout): layout[j] = (n_sents, valid entity count per sentence, or None) of paper j.
         A paper of more than aspire_max_sents() rows is encoded; scoring it raises NotImplementedError."""
-        from .scorer import CandidatePool
         dev = ops.require_gpu()
         batches = [tuple(b) for b in batches]
         layout, all_lens = [], []
@@ -255,14 +234,9 @@ class AspireContextNER(_SentenceEntityModel):
                     per_sent = [sum(next(flags) for _ in range(k)) for k in paper_ents]
                 layout.append((int(n), per_sent))
                 all_lens.append(int(n) + n_valid)
-        total = int(sum(all_lens))
-        lens_t = torch.tensor(all_lens, dtype=torch.int32)
-        start_t = (torch.cumsum(lens_t, 0) - lens_t).to(torch.int32)
+        lens_t, start_t, total = pool_layout(all_lens)
         enc = self.model.bert_encoder
-        if batches:
-            lo, hi = (int(v) for v in torch.aminmax(torch.cat([item[0]['tokid_tt'].reshape(-1) for item in batches])))
-            if lo < 0 or hi >= enc.config.vocab_size:
-                raise IndexError('token id out of range')       # nn.Embedding raises IndexError on the reference path
+        check_token_ids((item[0]['tokid_tt'] for item in batches), enc.config.vocab_size, dev)
         # (a paper's sentence and entity index lists travel through _merge_batches as one pair)
         triples = [(item[0], item[1], list(zip(item[2], item[3]))) for item in batches]
         forwards = AspireConSent._merge_batches(triples, docs_per_forward) if docs_per_forward else triples
@@ -286,13 +260,8 @@ class AspireContextNER(_SentenceEntityModel):
                                             attention_mask=bert_batch['attnmask_tt'], check_ids=False)
                 ops.span_pool_ranges(hidden, flat[0, r0:r1], flat[1, r0:r1], flat[2, r0:r1], rows=rows, out_row=flat[3, r0:r1])
             return rows
-        rows = enc.checked(fill, lambda r: bool(torch.isfinite(r).all()), 'AspireContextNER.encode_to_pool') if total else fill()
-        repset = ops.DeviceRepSet(rows, start_t.to(dev), lens_t.to(dev), ext=0, max_len=max(all_lens) if all_lens else 0,
-                                  lens_host=all_lens)
-        pool = CandidatePool.from_repset(repset, pids=pids)
-        if planes and total:
-            pool.prepare_planes()
-        return pool, layout
+        rows = self.model._checked_fill(fill, total, 'AspireContextNER.encode_to_pool')
+        return finish_pool(rows, lens_t, start_t, all_lens, pids, planes), layout
 
     def encode_to_store(self, papers, pids, store=None, batch_size=32, docs_per_forward=64):
         """Every paper encoded through encode_to_pool (papers prepared batch_size at a time), ONE download of the finished row
@@ -300,21 +269,20 @@ class AspireContextNER(_SentenceEntityModel):
         (RepStore.add's `layout`: the sentence count and, per sentence, the entity rows the reference's facet filter counts for it --
         filter_valid_entities), so that evaluate.score(..., facet=...) filters a query the way get_faceted_encoding does.
         Returns the RepStore (new, or `store` with the papers added), ready for evaluate.score."""
-        from .repstore import RepStore
         papers, pids = list(papers), list(pids)
-        if len(papers) != len(pids):
-            raise ValueError(f'{len(pids)} pids for {len(papers)} papers')
-        store = RepStore() if store is None else store
+        check_pid_count(pids, len(papers))
         batches = [self.prepare(papers[i:i + batch_size]) for i in range(0, len(papers), batch_size)]
         pool, layout = self.encode_to_pool(batches, pids=pids, docs_per_forward=docs_per_forward)
         rows = pool.repset.rows.cpu().numpy()
         ner_idxs = [x for item in batches for x in item[3]]
-        r0 = 0
-        for pid, paper, (n_sents, _), paper_ners, n_rows in zip(pids, papers, layout, ner_idxs, pool.repset.lens_host):
-            try:
-                counts = [len(x) for x in filter_valid_entities(paper['ENTITIES'], [len(x) > 0 for x in paper_ners])]
-            except IndexError:          # the reference's filter raises on this paper: so does RepStore.faceted
-                counts = None
-            store.add(pid, rows[r0:r0 + n_rows], layout=(n_sents, counts))
-            r0 += n_rows
-        return store
+
+        def blocks():
+            r0 = 0
+            for paper, (n_sents, _), paper_ners, n_rows in zip(papers, layout, ner_idxs, pool.repset.lens_host):
+                try:
+                    counts = [len(x) for x in filter_valid_entities(paper['ENTITIES'], [len(x) > 0 for x in paper_ners])]
+                except IndexError:          # the reference's filter raises on this paper: so does RepStore.faceted
+                    counts = None
+                yield rows[r0:r0 + n_rows], (n_sents, counts)
+                r0 += n_rows
+        return add_to_store(store, pids, blocks())

@@ -6,14 +6,13 @@
 
 MODEL_TABLE says which class stands for which of the reference's model names.
 """
-import codecs
-import json
 import os
 
 from .baselines import BertMLM, BertNER, SimCSE
 from .bienc import AspireBiEnc
 from .consent import AspireConSent
 from .contextner import AspireContextNER, AspireNER
+from .model_front import load_hf, ot_similarity, read_hparams, sentence_facet_rows
 from .sentenc import AspireSentEnc
 
 ASPIRE_MODEL_PATHS = {          # AspireModel.MODEL_PATHS, models.py:175-178
@@ -31,27 +30,15 @@ class AspireModel:
         self.name = name
         if hf_model_name is None and (bert_model is None or tokenizer is None):
             hf_model_name = ASPIRE_MODEL_PATHS[name.split('_')[-1]]
-        if tokenizer is None:
-            from transformers import AutoTokenizer
-            tokenizer = AutoTokenizer.from_pretrained(hf_model_name)
-        self.tokenizer = tokenizer
-        self.model = AspireConSent(hf_model_name=hf_model_name, bert_model=bert_model)
+        bert_model, self.tokenizer = load_hf(hf_model_name, bert_model, tokenizer)
+        self.model = AspireConSent(bert_model=bert_model)
 
     def encode(self, batch_papers):
         """:return: per paper [n_kept_sentences, 768]"""
         return self.model.encode(batch_papers, self.tokenizer)
 
-    @staticmethod
-    def get_similarity(x, y):
-        """AspireModel.get_similarity (models.py:190-197): the negative Wasserstein distance of two [n, 768] rep matrices."""
-        from .scorer import get_similarity
-        return get_similarity(x, y)
-
-    @staticmethod
-    def get_faceted_encoding(unfaceted_encoding, facet, input_data):
-        """SimilarityModel.get_faceted_encoding for encoding_type 'sentence' (models.py:147-153): the facet's sentence rows."""
-        labels = ['background' if lab == 'objective_label' else lab[:-len('_label')] for lab in input_data['FACETS']]
-        return unfaceted_encoding[[i for i, k in enumerate(labels) if facet == k]]
+    get_similarity = staticmethod(ot_similarity)
+    get_faceted_encoding = staticmethod(sentence_facet_rows)
 
 
 MODEL_TABLE = {
@@ -94,14 +81,12 @@ def get_model(model_name, trained_model_path=None, **kw):
     if cls is AspireBiEnc:
         tokenizer = kw.pop('tokenizer', None)
         if trained_model_path is not None:
-            with codecs.open(os.path.join(trained_model_path, 'run_info.json'), 'r', 'utf-8') as fp:
-                kw.setdefault('model_hparams', json.load(fp)['all_hparams'])
+            kw.setdefault('model_hparams', read_hparams(trained_model_path))
         model = cls(**kw)
         if trained_model_path is not None:
             model.load_state_dict(torch.load(os.path.join(trained_model_path, 'model_cur_best.pt'), map_location='cpu'))
         if tokenizer is None and kw.get('model_hparams'):
-            from transformers import AutoTokenizer
-            tokenizer = AutoTokenizer.from_pretrained(kw['model_hparams']['base-pt-layer'])
+            tokenizer = load_hf(kw['model_hparams']['base-pt-layer'], model=model)[1]       # (the model is built: the tokenizer only)
         model.tokenizer = tokenizer         # TrainedAbstractModel.tokenizer (models.py:555): prepare_eval_seqs' second argument
         return model
     model = cls(**_default_hf_name(kw, 'allenai/scibert_scivocab_uncased'))

@@ -13,8 +13,6 @@ score is aspire_jointsm_scores_f32 (include/aspire_hip.h, A14).  The model's dis
 pair_distances.allpair_joint_sm_negscore, is differentiable with respect to the sentence reps (aspire_jointsm_backward_f32), so its
 triplet loss can be written; forward_rank and a trainer are still not built.
 """
-import codecs
-import json
 import os
 
 import numpy as np
@@ -22,6 +20,7 @@ import torch
 
 from . import _lib, ops
 from .consent import AspireConSent
+from .model_front import read_hparams, strip_prefix
 
 
 class WordSentAlignPolyEnc(AspireConSent):
@@ -41,10 +40,8 @@ class WordSentAlignPolyEnc(AspireConSent):
     def load_state_dict(self, sd):
         """model_cur_best.pt: the encoder is rebuilt from its bert_encoder.* keys (the class has no other parameters)."""
         from .encoder import HipBertEncoder
-        other = [k for k in sd if not k.startswith('bert_encoder.')]
-        if other:
-            raise KeyError(f'unexpected keys in the WordSentAlignPolyEnc state dict: {other}')
-        self.bert_encoder = HipBertEncoder.from_state_dict(self.bert_encoder.config, {k[len('bert_encoder.'):]: v for k, v in sd.items()})
+        enc, _ = strip_prefix(sd, 'bert_encoder.', who='WordSentAlignPolyEnc')
+        self.bert_encoder = HipBertEncoder.from_state_dict(self.bert_encoder.config, enc)
         return self
 
     @staticmethod
@@ -79,9 +76,7 @@ class TrainedScoringModel:
         if model_name not in {'miswordpolyenc'}:
             raise ValueError(f'Unknown model: {model_name}')
         if model is None and trained_model_path is not None:
-            with codecs.open(os.path.join(trained_model_path, 'run_info.json'), 'r', 'utf-8') as fp:
-                all_hparams = json.load(fp)['all_hparams']
-            model = WordSentAlignPolyEnc(model_hparams=all_hparams)
+            model = WordSentAlignPolyEnc(model_hparams=read_hparams(trained_model_path))
             model.load_state_dict(torch.load(os.path.join(trained_model_path, 'model_{:s}.pt'.format(model_version)), map_location='cpu'))
         self.model_name = model_name
         self.model = model

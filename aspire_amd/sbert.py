@@ -16,10 +16,9 @@ import json
 import os
 
 import numpy as np
-import torch
 
-from .batch_prep import pad_sentences, sentence_buckets
 from .encoder import HipBertEncoder
+from .model_front import EncoderFront, add_to_store, check_pid_count, encode_bucketed, load_hf, per_paper, sentence_facet_rows
 
 
 def _read_json(path):
@@ -27,7 +26,7 @@ def _read_json(path):
         return json.load(fp)
 
 
-class SentenceModel:
+class SentenceModel(EncoderFront):
     """'sbtinybertsota' / 'sbrobertanli' / 'sbmpnet1B' (models.py:379-410).
 
     max_seq_length and normalize default per name to DEFAULTS below.  Those values are RECALLED from the models' published
@@ -63,15 +62,9 @@ class SentenceModel:
             seq_file, norm_file = self.read_local_settings(hf_model_name)
             seq_default = seq_file if seq_file is not None else seq_default
             norm_default = norm_file if norm_file is not None else norm_default
-        if model is None:
-            from transformers import AutoModel
-            model = AutoModel.from_pretrained(full_name)
-        if tokenizer is None:
-            from transformers import AutoTokenizer
-            tokenizer = AutoTokenizer.from_pretrained(full_name)
+        model, self.tokenizer = load_hf(full_name, model, tokenizer)
         self.max_seq_length = int(max_seq_length if max_seq_length is not None else seq_default or 512)
         self.normalize = bool(normalize if normalize is not None else norm_default)
-        self.tokenizer = tokenizer
         self.bert_encoder = HipBertEncoder(model)
 
     @classmethod
@@ -93,15 +86,11 @@ class SentenceModel:
             norm = any(str(m.get('type', '')).endswith('Normalize') for m in _read_json(p))
         return seq, norm
 
-    def eval(self):
-        return self
-
     def _mean_checked(self, tokid_tt, token_type_ids, attention_mask):
         """int64 [B, L] -> the sentence reps [B, 768] on the GPU, under the encoder's fall-back rule (encoder.run_checked)."""
         enc = self.bert_encoder
-        tok, typ, msk = enc.device_inputs(tokid_tt, token_type_ids, attention_mask)
-        return enc.checked(lambda: enc.forward_mean(tok, typ, msk, normalize=self.normalize, check_ids=False),
-                           lambda out: bool(torch.isfinite(out).all()), 'SentenceModel')
+        return self._checked_read(lambda tok, typ, msk: enc.forward_mean(tok, typ, msk, normalize=self.normalize, check_ids=False),
+                                  lambda out: out, tokid_tt, token_type_ids, attention_mask, 'SentenceModel')
 
     def _encode_sentences(self, sents, max_tokens=16384):
         """The rep of every string, float32 [N, 768] (numpy) in input order: SentenceTransformer.encode's text.strip() and
@@ -109,24 +98,15 @@ class SentenceModel:
         rep does not depend on its batch mates (padding is masked out of the attention and of the mean), so instead of batches of 32
         in input order everything is tokenised once, sorted by length and cut into encoder calls of at most `max_tokens` padded
         token rows (batch_prep.sentence_buckets), padded with the tokenizer's pad id."""
-        dev = self.bert_encoder.device
-        out = torch.empty(len(sents), 768, device=dev, dtype=torch.float32)
         ids = [list(self.tokenizer(str(s).strip(), truncation=True, max_length=self.max_seq_length)['input_ids']) for s in sents]
         types = [[0] * len(x) for x in ids]
-        for run in sentence_buckets([len(x) for x in ids], max_tokens):
-            out[torch.from_numpy(run).to(dev)] = self._mean_checked(*pad_sentences(ids, types, run, self.tokenizer.pad_token_id))
-        return out.cpu().numpy()
+        return encode_bucketed(self._mean_checked, ids, types, self.tokenizer.pad_token_id, max_tokens,
+                               self.bert_encoder.device).cpu().numpy()
 
     def encode(self, batch_papers):
         """SentenceModel.encode (models.py:392-406): the ABSTRACT sentences of all papers encoded, split back per paper with
         np.split semantics -> list of float32 [n_sents, 768] (a paper without sentences: [0, 768])."""
-        batch, splits, cur = [], [], 0
-        for paper in batch_papers:
-            batch += list(paper['ABSTRACT'])
-            cur += len(paper['ABSTRACT'])
-            splits.append(cur)
-        reps = self._encode_sentences(batch) if batch else np.zeros((0, 768), np.float32)
-        return np.split(reps, splits[:-1])
+        return per_paper(batch_papers, self._encode_sentences)
 
     @staticmethod
     def get_similarity(x, y):
@@ -140,20 +120,11 @@ class SentenceModel:
             return a / nrm[:, None]
         return float(np.max(unit(x) @ unit(y).T))
 
-    @staticmethod
-    def get_faceted_encoding(unfaceted_encoding, facet, input_data):
-        """SimilarityModel.get_faceted_encoding for encoding_type 'sentence' (models.py:147-153): the facet's sentence rows."""
-        labels = ['background' if lab == 'objective_label' else lab[:-len('_label')] for lab in input_data['FACETS']]
-        return unfaceted_encoding[[i for i, k in enumerate(labels) if facet == k]]
+    get_faceted_encoding = staticmethod(sentence_facet_rows)
 
     def encode_to_store(self, papers, pids, store=None):
         """Every paper's ABSTRACT sentences encoded (one encode call for the lot), one [n_sents, 768] row block per paper under
         pids[j].  Returns the RepStore (new, or `store` with the reps added), ready for evaluate.score(..., method='cosine')."""
-        from .repstore import RepStore
         papers, pids = list(papers), list(pids)
-        if len(papers) != len(pids):
-            raise ValueError(f'{len(pids)} pids for {len(papers)} papers')
-        store = RepStore() if store is None else store
-        for pid, reps in zip(pids, self.encode(papers)):
-            store.add(pid, reps)
-        return store
+        check_pid_count(pids, len(papers))
+        return add_to_store(store, pids, self.encode(papers))

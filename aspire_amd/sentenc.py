@@ -12,11 +12,11 @@ encoder is HipBertEncoder.forward_cls with no layer mix (AspireBiEnc's read-out)
 aspire_dotmax_rank_batch_f32 (include/aspire_hip.h, A13).
 """
 import numpy as np
-import torch
 
 from . import _lib, ops
-from .batch_prep import batch_tensors, pad_sentences, sentence_buckets, tokenize_sentences
+from .batch_prep import batch_tensors, tokenize_sentences
 from .encoder import HipBertEncoder
+from .model_front import EncoderFront, add_to_store, check_pid_count, encode_bucketed, load_hf, per_paper, refuse_keys, strip_prefix
 
 
 def split_state_dict(sd):
@@ -26,22 +26,12 @@ def split_state_dict(sd):
         context tower of its training loss) is dropped: the evaluation encodes with the sentence tower only.
     Any other key is a KeyError."""
     if any(k.startswith(('sent_encoder.', 'context_encoder.')) for k in sd):
-        enc, other = {}, []
-        for k, v in sd.items():
-            if k.startswith('sent_encoder.'):
-                enc[k[len('sent_encoder.'):]] = v
-            elif not k.startswith('context_encoder.'):
-                other.append(k)
-        if other:
-            raise KeyError(f'unexpected keys in the sentence-encoder state dict: {other}')
-        return enc
-    bad = [k for k in sd if not k.startswith(('embeddings.', 'encoder.', 'pooler.'))]
-    if bad:
-        raise KeyError(f'unexpected keys in the sentence-encoder state dict: {bad}')
+        return strip_prefix(sd, 'sent_encoder.', drop=('context_encoder.',), who='sentence-encoder')[0]
+    refuse_keys([k for k in sd if not k.startswith(('embeddings.', 'encoder.', 'pooler.'))], 'sentence-encoder')
     return dict(sd)
 
 
-class AspireSentEnc:
+class AspireSentEnc(EncoderFront):
     def __init__(self, hf_model_name=None, bert_model=None, max_seq_length=512, tokenizer=None):
         """
         :param hf_model_name: the HF model (and tokenizer) to load, e.g. 'allenai/aspire-sentence-embedder' or, as
@@ -52,17 +42,8 @@ class AspireSentEnc:
         """
         self.bert_encoding_dim = 768
         self.max_seq_length = int(max_seq_length)
-        if bert_model is None:
-            from transformers import AutoModel
-            bert_model = AutoModel.from_pretrained(hf_model_name)
-        if tokenizer is None and hf_model_name is not None:
-            from transformers import AutoTokenizer
-            tokenizer = AutoTokenizer.from_pretrained(hf_model_name)
-        self.tokenizer = tokenizer
+        bert_model, self.tokenizer = load_hf(hf_model_name, bert_model, tokenizer)
         self.bert_encoder = HipBertEncoder(bert_model)
-
-    def eval(self):
-        return self
 
     def load_state_dict(self, sd):
         """sent_encoder_cur_best.pt (a BertModel state dict) or a SentBERTWrapper / ICTBERTWrapper one (split_state_dict)."""
@@ -73,9 +54,8 @@ class AspireSentEnc:
     def forward_device(self, tokid_tt, token_type_ids=None, attention_mask=None):
         """int64 [B, L] -> last_hidden_state[:, 0] [B, 768] on the GPU, under the encoder's fall-back rule (encoder.run_checked)."""
         enc = self.bert_encoder
-        tok, typ, msk = enc.device_inputs(tokid_tt, token_type_ids, attention_mask)
-        return enc.checked(lambda: enc.forward_cls(tok, typ, msk, check_ids=False)[0], lambda out: bool(torch.isfinite(out).all()),
-                           'AspireSentEnc')
+        return self._checked_read(lambda tok, typ, msk: enc.forward_cls(tok, typ, msk, check_ids=False)[0], lambda out: out,
+                                  tokid_tt, token_type_ids, attention_mask, 'AspireSentEnc')
 
     @staticmethod
     def sent_reps_bert(bert_batch, model=None):
@@ -96,15 +76,13 @@ class AspireSentEnc:
         single = isinstance(sentences, str)
         sents = [sentences] if single else list(sentences)
         dev = ops.require_gpu()
-        out = torch.empty(len(sents), 768, device=dev, dtype=torch.float32)
+        ids, types, pad = [], [], None
         if sents:
             if self.tokenizer is None:
                 raise ValueError('encode() needs a tokenizer: pass hf_model_name or tokenizer=')
             ids, types = tokenize_sentences(sents, self.tokenizer, self.max_seq_length)
             pad = self.tokenizer.pad_token_id
-            for run in sentence_buckets([len(x) for x in ids], max_tokens):
-                tok, typ, msk = pad_sentences(ids, types, run, pad)
-                out[torch.from_numpy(run).to(dev)] = self.forward_device(tok, typ, msk)
+        out = encode_bucketed(self.forward_device, ids, types, pad, max_tokens, dev)
         if single:
             out = out[0]
         return out.cpu().numpy() if convert_to_numpy else out
@@ -113,13 +91,7 @@ class AspireSentEnc:
     def encode_papers(self, batch_papers, **kw):
         """TrainedSentModel.encode (models.py:584-600): the ABSTRACT sentences of every paper, encoded, split back per paper with
         np.split semantics -> list of float32 [n_sents, 768]."""
-        batch, splits, cur = [], [], 0
-        for paper in batch_papers:
-            batch += list(paper['ABSTRACT'])
-            cur += len(paper['ABSTRACT'])
-            splits.append(cur)
-        reps = self.encode(batch, **kw) if batch else np.zeros((0, 768), np.float32)
-        return np.split(reps, splits[:-1])
+        return per_paper(batch_papers, lambda batch: self.encode(batch, **kw))
 
     @staticmethod
     def get_similarity(x, y):
@@ -135,11 +107,6 @@ class AspireSentEnc:
         """Every paper's ABSTRACT sentences encoded (one encode call for the lot), one [n_sents, 768] row block per paper under
         pids[j] (pre_proc_buildreps.py:332-360 writes the same reps).  Returns the RepStore (new, or `store` with the reps added),
         ready for evaluate.score(..., method='cosine')."""
-        from .repstore import RepStore
         papers, pids = list(papers), list(pids)
-        if len(papers) != len(pids):
-            raise ValueError(f'{len(pids)} pids for {len(papers)} papers')
-        store = RepStore() if store is None else store
-        for pid, reps in zip(pids, self.encode_papers(papers, **kw)):
-            store.add(pid, reps)
-        return store
+        check_pid_count(pids, len(papers))
+        return add_to_store(store, pids, self.encode_papers(papers, **kw))
