@@ -11,7 +11,8 @@
 //                            staged, six products per term
 //                            A_KM: the TN form, C[M, N] = sum_r A[r, M] . B[r, N] -- both operands row-major with the contraction over
 //                            their rows (the encoder backward's dW = dY^T . X, dV = P^T . dO, dK = dS^T . Q); new instantiations of the
-//                            same kernel, the existing ones compile to the code they had
+//                            same kernel, the existing ones keep their arithmetic.  The contraction is over token rows, so this
+//                            form alone sums in two levels: the accumulators are folded into a second set every 256 rows
 // Launch rules: launch_gemm (tile and form by shape and the ASPIRE_HIP_GEMM / ASPIRE_HIP_GEMM_TILE pins), launch_gemm_tn.
 #include "enc_types.h"
 #include "tuning.h"
@@ -136,7 +137,7 @@ __global__ void __launch_bounds__(256) gemm_f32_kernel(GemmArgs g) {
     store_tiles(0);
     __syncthreads();
     const int lr = lane & 31, lk = lane >> 5;
-    for (int t = 0; t < nk; ++t) {
+    auto mma_tile = [&](int t) {
         const int buf = t & 1;
         if (t + 1 < nk) load_tiles((t + 1) * kBK);  // in flight under the MFMAs below
 #pragma unroll
@@ -157,6 +158,40 @@ __global__ void __launch_bounds__(256) gemm_f32_kernel(GemmArgs g) {
         }
         if (t + 1 < nk) store_tiles(buf ^ 1);
         __syncthreads();
+    };
+    if constexpr (A_KM) {
+        // The contraction runs over token rows -- thousands under training, where one fp32 accumulator summed in k order drifts by
+        // the roundings of an ever larger running sum (a weight gradient over 5 599 rows was 6 - 9 x further from float64 than an
+        // fp32 CPU GEMM).  So two levels: after every kFold k tiles (256 rows) the accumulators are added to `tot` and start again
+        // from zero -- in a loop of its own around the tile loop, so that the tile loop stays what it was (a fold predicated inside
+        // it is if-converted: every tile then drains the MFMAs to read the accumulators).  Up to 256 rows: the bits of one level.
+        constexpr int kFold = 16;
+        f32x16 tot[TM][TN];
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) tot[i][j][r] = 0.f;
+        for (int t0 = 0; t0 < nk; t0 += kFold) {
+            const int t1 = min(t0 + kFold, nk);
+            for (int t = t0; t < t1; ++t) mma_tile(t);
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        tot[i][j][r] += acc[i][j][r];
+                        acc[i][j][r] = 0.f;
+                    }
+        }
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j) acc[i][j] = tot[i][j];
+    } else {
+        for (int t = 0; t < nk; ++t) mma_tile(t);
     }
 
     // epilogue: C/D layout of 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)

@@ -53,12 +53,12 @@ pytestmark = pytest.mark.gpu
 VOCAB = 50
 
 
-def _bert(n_layers, seed=0, dropout=0.0):
+def _bert(n_layers, seed=0, dropout=0.0, intermediate_size=128):
     from transformers import BertConfig, BertModel
     torch.manual_seed(seed)
-    cfg = BertConfig(vocab_size=VOCAB, hidden_size=768, num_hidden_layers=n_layers, num_attention_heads=12, intermediate_size=128,
-                     max_position_embeddings=512, layer_norm_eps=1e-12, hidden_dropout_prob=dropout, attention_probs_dropout_prob=dropout,
-                     attn_implementation='eager')
+    cfg = BertConfig(vocab_size=VOCAB, hidden_size=768, num_hidden_layers=n_layers, num_attention_heads=12,
+                     intermediate_size=intermediate_size, max_position_embeddings=512, layer_norm_eps=1e-12, hidden_dropout_prob=dropout,
+                     attention_probs_dropout_prob=dropout, attn_implementation='eager')
     m = BertModel(cfg, add_pooling_layer=False).eval()
     with torch.no_grad():
         for n, p in m.named_parameters():
