@@ -129,7 +129,8 @@ bool fused_path_ok(const aspire_repset* q, const aspire_repset* c) {
 // tsAspire (max-sim) of every (query, candidate) pair, CROSS, documents of <= 8 rows: the fused kernel's streaming phase
 // self (batched jobs, <= 64 of them): no tables in front of the launch -- the waves derive an item's job from job_off (SELF)
 int launch_pair_fused_l2max(const ScoreArgs& a, int64_t groups_bound, hipStream_t stream, bool self) {
-    const int64_t waves = groups_bound < 256 * 8 ? groups_bound : 256 * 8;
+    const int64_t cap = tuning().fused_waves > 0 ? tuning().fused_waves : 256 * 8;
+    const int64_t waves = groups_bound < cap ? groups_bound : cap;
     const dim3 grid((unsigned)((waves + 3) / 4));
     if (self)
         hipLaunchKernelGGL((pair_fused_kernel<true, false, true, true>), grid, dim3(256), 4 * kWaveLds * sizeof(float), stream, a,
