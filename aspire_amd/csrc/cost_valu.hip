@@ -1185,7 +1185,8 @@ int launch_cost_stage(const ScoreArgs& a, int T_rt, const aspire_repset* q, cons
                 // wave (measured 4.7 TB/s algorithmic at 1 x 20 000 against 1.8 TB/s for the accumulate-then-reduce kernel)
                 if (!a.diameter && first_chunk && a.pairing != kPairMapped)     // per-coordinate boxes of the queries, once per call
                     if (int rc = launch_doc_box(a.q, qbox, stream)) return rc;
-                const int64_t waves = groups4 < 256 * 8 ? groups4 : 256 * 8;
+                const int64_t wave_cap = tuning().tile_waves > 0 ? tuning().tile_waves : 256 * 8;      // TILE_WAVES: tests with several items per wave
+                const int64_t waves = groups4 < wave_cap ? groups4 : wave_cap;
                 hipLaunchKernelGGL((pair_tile_kernel<2, 1>), dim3((unsigned)((waves + 3) / 4)), dim3(256),
                                    4 * TileCfg<2>::kLdsFloats * sizeof(float), stream, a, ws1, qbox);
             } else {

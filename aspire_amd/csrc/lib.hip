@@ -66,6 +66,8 @@ bool apply_tuning(Tuning& t, const char* key, const char* v) {
         t.fused_norepair = unset ? 0 : atoi(v);
     } else if (!strcmp(key, "FUSED_WAVES")) {
         t.fused_waves = unset ? 0 : atoi(v);
+    } else if (!strcmp(key, "TILE_WAVES")) {
+        t.tile_waves = unset ? 0 : atoi(v);
     } else if (!strcmp(key, "FUSED_SPLIT")) {
         t.fused_split = unset ? 0 : atoi(v);
     } else if (!strcmp(key, "SPLIT_PRIO")) {
@@ -119,6 +121,7 @@ bool render_tuning(const Tuning& t, const char* key, char* buf, size_t len) {
         v = num;
     }
     else if (!strcmp(key, "FUSED_WAVES")) v = number(t.fused_waves);
+    else if (!strcmp(key, "TILE_WAVES")) v = number(t.tile_waves);
     else if (!strcmp(key, "FUSED_SPLIT")) v = number(t.fused_split);
     else if (!strcmp(key, "SPLIT_PRIO")) v = number(t.split_prio);
     else if (!strcmp(key, "GRAM_TILE")) v = number(t.gram_tile);
@@ -131,7 +134,7 @@ bool render_tuning(const Tuning& t, const char* key, char* buf, size_t len) {
 }
 
 void tuning_from_env() {
-    static const char* keys[] = {"SINKHORN", "COST_PATH", "COST1_BLOCKS", "ATTN", "GEMM_TILE", "GEMM_RING", "GEMM_LN", "GEMM_PROBE", "GEMM", "OT_FORM", "FUSED_VALU", "FUSED_NOSOLVE", "FUSED_SOLVE16", "FUSED_NOREPAIR", "FUSED_WAVES", "FUSED_SPLIT", "SPLIT_PRIO", "FUSED_NOSELF", "GRAM_TILE", "GRAM_RING", "GRAM_PP"};
+    static const char* keys[] = {"SINKHORN", "COST_PATH", "COST1_BLOCKS", "ATTN", "GEMM_TILE", "GEMM_RING", "GEMM_LN", "GEMM_PROBE", "GEMM", "OT_FORM", "FUSED_VALU", "FUSED_NOSOLVE", "FUSED_SOLVE16", "FUSED_NOREPAIR", "FUSED_WAVES", "TILE_WAVES", "FUSED_SPLIT", "SPLIT_PRIO", "FUSED_NOSELF", "GRAM_TILE", "GRAM_RING", "GRAM_PP"};
     for (const char* k : keys) {
         char name[64];
         snprintf(name, sizeof(name), "ASPIRE_HIP_%s", k);

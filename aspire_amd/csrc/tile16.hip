@@ -398,11 +398,14 @@ bool tile16_path_ok(const aspire_repset* q, const aspire_repset* c, int pairing)
     return mq > 0 && mc > 0 && mq <= 16 && mc <= 16 && (mq > 8 || mc > 8);
 }
 
+// the launches' waves: 256 * 8 resident ones unless TILE_WAVES pins fewer (tests: several items per wave)
+static int64_t tile_wave_cap() { return tuning().tile_waves > 0 ? tuning().tile_waves : 256 * 8; }
+
 // items_bound: upper bound of the launch's items (pairs of candidates x queries)
 int launch_pair_tile16(const ScoreArgs& a, float* cost, float* neg, float* diam2, int64_t items_bound, const float* qbox,
                        hipStream_t stream) {
     PairWs<2> ws{cost, neg, diam2};
-    const int64_t waves = items_bound < 256 * 8 ? items_bound : 256 * 8;
+    const int64_t waves = items_bound < tile_wave_cap() ? items_bound : tile_wave_cap();
     hipLaunchKernelGGL((pair_tile16_kernel<false>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 4 * kWaveLds * sizeof(float), stream, a, ws,
                        qbox);
     ASPIRE_LAUNCH_OK();
@@ -412,7 +415,7 @@ int launch_pair_tile16(const ScoreArgs& a, float* cost, float* neg, float* diam2
 // tsAspire (max-sim) of every (query, candidate) pair, CROSS
 int launch_pair_tile16_l2max(const ScoreArgs& a, int64_t items_bound, hipStream_t stream) {
     PairWs<2> ws{nullptr, nullptr, nullptr};
-    const int64_t waves = items_bound < 256 * 8 ? items_bound : 256 * 8;
+    const int64_t waves = items_bound < tile_wave_cap() ? items_bound : tile_wave_cap();
     hipLaunchKernelGGL((pair_tile16_kernel<true>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 4 * kWaveLds * sizeof(float), stream, a, ws,
                        (const float*)nullptr);
     ASPIRE_LAUNCH_OK();
@@ -422,7 +425,7 @@ int launch_pair_tile16_l2max(const ScoreArgs& a, int64_t items_bound, hipStream_
 // REC items (chunk16_prep_kernel's records in a.grp_rec, their count in a.grp_off[0]); T = the workspace slots' tile width (3, 4)
 int launch_pair_tile16_rec(const ScoreArgs& a, int T, float* cost, float* neg, float* diam2, int64_t items_bound, const float* qbox,
                            hipStream_t stream) {
-    const int64_t waves = items_bound < 256 * 8 ? items_bound : 256 * 8;
+    const int64_t waves = items_bound < tile_wave_cap() ? items_bound : tile_wave_cap();
     const dim3 grid((unsigned)((waves + 3) / 4));
     if (T == 3) {
         PairWs<3> ws{cost, neg, diam2};
@@ -436,7 +439,7 @@ int launch_pair_tile16_rec(const ScoreArgs& a, int T, float* cost, float* neg, f
 }
 int launch_pair_tile16_rec_l2max(const ScoreArgs& a, int64_t items_bound, hipStream_t stream) {
     PairWs<4> ws{nullptr, nullptr, nullptr};
-    const int64_t waves = items_bound < 256 * 8 ? items_bound : 256 * 8;
+    const int64_t waves = items_bound < tile_wave_cap() ? items_bound : tile_wave_cap();
     hipLaunchKernelGGL((pair_tile16_kernel<true, 4, true>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 4 * kWaveLds * sizeof(float), stream,
                        a, ws, (const float*)nullptr);
     ASPIRE_LAUNCH_OK();

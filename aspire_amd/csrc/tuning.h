@@ -30,6 +30,7 @@ struct Tuning {
     int fused_solve16 = -1;  // ASPIRE_HIP_FUSED_SOLVE16: the SELF form's solve: 0 sixteen lanes per pair, sliced through the next item's stages; 1 four lanes per pair, sixteen pairs per wave behind a super-item of sixteen candidates (Solve16); unset (-1): 1 for a launch on another stream than the previous one (calls in flight), else 0 (fused.hip: solve16_wanted)
     int fused_norepair = 0;  // ASPIRE_HIP_FUSED_NOREPAIR=1: the fused kernel skips the in-wave re-solve of poisoned pairs (tests: which pairs reach it; invalid scores)
     int fused_waves = 0;     // ASPIRE_HIP_FUSED_WAVES: cap on the fused kernel's resident waves (0 = default; grid experiments)
+    int tile_waves = 0;      // ASPIRE_HIP_TILE_WAVES: cap on the waves of the streaming cost / max-sim launches of tile16.hip and of cost_valu.hip's pair_tile_kernel (0 = default 2048; tests: several items per wave)
     int fused_split = 0;     // ASPIRE_HIP_FUSED_SPLIT: 0 / 2 the fused kernel, 1 the role-split kernel where it applies -- ONLY in the experiment build (tools/experiments/split/build.sh: -DASPIRE_EXPERIMENT_SPLIT); ignored by the product library
     int split_prio = 0;      // ASPIRE_HIP_SPLIT_PRIO: the role-split kernel's solver mode: 0 solve, 3 skip the solves (timing probe: wrong scores)
 };

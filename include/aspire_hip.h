@@ -845,6 +845,8 @@ int aspire_topk_merge_keys(const uint64_t* keys, int64_t R, int64_t Q, int64_t k
  *                      (mfma | valu), "OT_FORM" (small | tile | fused), "COST1_BLOCKS" (n), "ATTN" (gemm), "GEMM" (f32 | bf16x3 | planes), "GEMM_TILE" (96 | 128 | 64), "GEMM_RING" (2 | 3), "GEMM_LN" (on | off: LayerNorm in / behind the N = 768 GEMMs),
  *                      "FUSED_VALU" (1),
  *                      "FUSED_NOSELF" (1), "FUSED_WAVES" (n: cap on the waves of a fused launch (max-sim launches too)), "FUSED_NOSOLVE" (1 | 2: timing only, invalid scores),
+ *                      "TILE_WAVES" (n: cap on the waves of the 16-row streaming launches (tile16.hip, record items and max-sim too) and of the tiled cost
+ *                      kernel for documents of <= 8 rows (OT_FORM tile); tests: several items per wave, the same bits),
  *                      "FUSED_SOLVE16" (0 | 1: the batched fused kernel's solve on sixteen / four lanes per pair; unset: four where
  *                      consecutive calls come on different streams; the same bits either way), "FUSED_NOREPAIR" (1: poisoned
  *                      pairs keep the fast solve's score -- invalid; tests); aspire_debug_get("FUSED_SOLVE16_LAUNCHES") counts the

@@ -80,6 +80,9 @@ def test_diagnostic_switches_without_gpu():
             assert current(b'OT_FORM') == b'fused'
         assert current(b'OT_FORM') == b'small' and current(b'FUSED_WAVES') == b'1024'
     assert current(b'OT_FORM') == b'' and current(b'FUSED_WAVES') == b''
+    with _lib.pinned(TILE_WAVES=12):
+        assert current(b'TILE_WAVES') == b'12'
+    assert current(b'TILE_WAVES') == b''
     assert _lib.lib.aspire_debug_get(b'NO_SUCH_SWITCH', buf, len(buf)) == _lib.ASPIRE_ERR_INVALID_ARG
 
 
