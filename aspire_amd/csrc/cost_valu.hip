@@ -19,6 +19,7 @@
 #include "tuning.h"
 #include "score_types.h"
 #include "score_device.h"
+#include "exact_d2.h"
 
 namespace aspire {
 namespace {
@@ -254,20 +255,11 @@ __global__ void __launch_bounds__(kBlock, 3) l2max_kernel(ScoreArgs a) {
                         }
                         const float sqv = fmaf(-2.f, g, xx) + yy, ns = xx + yy;
                         d2 = fmaxf(sqv, 0.f);
-                        // (round 6: where the expansion cancels the entry comes from the exact sum under this formula too -- one rule in every kernel family:
-                        // include/aspire_hip.h, SHARED SENTENCES.  Rare: the lane walks the two rows itself)
-                        if (i < q_len && j < c_len && sqv < 1e-4f * ns * ns) {
+                        // (under this formula too -- the rule: exact_d2.h.  Rare: the lane walks the two rows itself, form C)
+                        if (i < q_len && j < c_len && expansion_cancels(sqv, ns)) {
                             const float* xr = qdoc + (size_t)i * kD;
                             const float* yr = cdoc + (size_t)j * kD;
-                            float s0 = 0.f, s1 = 0.f;
-                            for (int d = 0; d < kD; d += 8) {
-                                const float4 u0 = ld4(xr + d), v0 = ld4(yr + d), u1 = ld4(xr + d + 4), v1 = ld4(yr + d + 4);
-                                const float a0 = u0.x - v0.x, a1 = u0.y - v0.y, a2 = u0.z - v0.z, a3 = u0.w - v0.w;
-                                const float b0 = u1.x - v1.x, b1 = u1.y - v1.y, b2 = u1.z - v1.z, b3 = u1.w - v1.w;
-                                s0 = fmaf(a3, a3, fmaf(a2, a2, fmaf(a1, a1, fmaf(a0, a0, s0))));
-                                s1 = fmaf(b3, b3, fmaf(b2, b2, fmaf(b1, b1, fmaf(b0, b0, s1))));
-                            }
-                            d2 = s0 + s1;
+                            d2 = lane_d2([=](int d) { return ld4(xr + d); }, [=](int d) { return ld4(yr + d); });
                         }
                     } else {
                         d2 = 0.f;
@@ -378,31 +370,24 @@ __device__ __forceinline__ void finish_pair(const float* lds, bool mm, bool want
         const int64_t o = slot * (64 * T * T) + (ta * 8 + li) * (8 * T) + tb * 8 + lj;
         // geomloss's cost: its expansion -- except where that cancels (the test the streaming kernels use), where the exact sum
         // stands in: what the reference's own formula gives in float64 (in fp32 it returns the square root of rounding noise there)
-        float costv = sqrtf(fmaxf(sq, 1e-8f));
+        float costv = cost_of_d2(sq);
         if constexpr (DIRECT) {
             const float ns = xx + yy;
-            const bool cancels = sq < 1e-4f * ns * ns;
-            if (cancels) costv = sqrtf(fmaxf(d2, 1e-8f));
+            const bool cancels = expansion_cancels(sq, ns);
+            if (cancels) costv = cost_of_d2(d2);
             ws.cost[o] = costv;
-            ws.neg[o] = (mm && !cancels) ? -sqrtf(fmaxf(sq, 0.f)) : -sqrtf(d2);      // (round 6: a cancelling entry from the exact sum under either formula)
+            ws.neg[o] = (mm && !cancels) ? neg_of_expansion(sq) : -sqrtf(d2);      // (a cancelling entry from the exact sum under either formula: exact_d2.h)
         } else {
             // only x.y was accumulated (see pair_cost1_kernel): -cdist from the expansion, except where it cancels
             const int i = ta * 8 + li, j = tb * 8 + lj;
             const float ns = xx + yy;
-            float negv = -sqrtf(fmaxf(sq, 0.f));
-            if (i < q_len && j < c_len && sq < 1e-4f * ns * ns) {   // rare: this thread walks the two rows itself
+            float negv = neg_of_expansion(sq);
+            if (i < q_len && j < c_len && expansion_cancels(sq, ns)) {   // rare: this thread walks the two rows itself (exact_d2.h, form C)
                 const float* xr = qdoc + (size_t)i * kD;
                 const float* yr = cdoc + (size_t)j * kD;
-                float s0 = 0.f, s1 = 0.f;
-                for (int d = 0; d < kD; d += 8) {
-                    const float4 u0 = ld4(xr + d), v0 = ld4(yr + d), u1 = ld4(xr + d + 4), v1 = ld4(yr + d + 4);
-                    const float a0 = u0.x - v0.x, a1 = u0.y - v0.y, a2 = u0.z - v0.z, a3 = u0.w - v0.w;
-                    const float b0 = u1.x - v1.x, b1 = u1.y - v1.y, b2 = u1.z - v1.z, b3 = u1.w - v1.w;
-                    s0 = fmaf(a3, a3, fmaf(a2, a2, fmaf(a1, a1, fmaf(a0, a0, s0))));
-                    s1 = fmaf(b3, b3, fmaf(b2, b2, fmaf(b1, b1, fmaf(b0, b0, s1))));
-                }
-                negv = -sqrtf(s0 + s1);
-                costv = sqrtf(fmaxf(s0 + s1, 1e-8f));
+                const float d2x = lane_d2([=](int d) { return ld4(xr + d); }, [=](int d) { return ld4(yr + d); });
+                negv = -sqrtf(d2x);
+                costv = cost_of_d2(d2x);
             }
             ws.cost[o] = costv;
             ws.neg[o] = negv;
@@ -625,13 +610,12 @@ __device__ __forceinline__ void pair_cost1_body(const ScoreArgs& a, const PairWs
             }
             const float sq = fmaf(-2.f, gsum, xx) + yy;
             const float ns = xx + yy;
-            // (round 6: a cancelling entry is redone from the exact sum whatever formula torch.cdist would pick -- also beyond 25 rows: include/aspire_hip.h, SHARED SENTENCES)
             const int gi = 8 * ta + li, gj = 8 * tb + lj;                  // entry of the pair's 8T x 8T slot
-            const bool redo = gi < q_len && gj < c_len && sq < 1e-4f * ns * ns;
+            const bool redo = gi < q_len && gj < c_len && expansion_cancels(sq, ns);       // (the rule and the exact sum: exact_d2.h)
             const int64_t o = slot * n_ent + gi * ld_e + gj;
             if (!redo) {
-                ws.cost[o] = sqrtf(fmaxf(sq, 1e-8f));
-                ws.neg[o] = -sqrtf(fmaxf(sq, 0.f));
+                ws.cost[o] = cost_of_d2(sq);
+                ws.neg[o] = neg_of_expansion(sq);
             }
             const unsigned long long m = __ballot(redo);
             if (lane == 0) {
@@ -662,23 +646,10 @@ __device__ __forceinline__ void pair_cost1_body(const ScoreArgs& a, const PairWs
                     const int gi = 8 * ta + (e >> 3), gj = 8 * tb + (e & 7);
                     const float* xr = qdoc + (size_t)gi * kD + 4 * l16;
                     const float* yr = cdoc + (size_t)gj * kD + 4 * l16;
-                    float p0 = 0.f, p1 = 0.f;
-#pragma unroll
-                    for (int c = 0; c < 12; c += 2) {
-                        const float4 u0 = ld4(xr + 64 * c), v0 = ld4(yr + 64 * c), u1 = ld4(xr + 64 * c + 64), v1 = ld4(yr + 64 * c + 64);
-                        const float a0 = u0.x - v0.x, a1 = u0.y - v0.y, a2 = u0.z - v0.z, a3 = u0.w - v0.w;
-                        const float b0 = u1.x - v1.x, b1 = u1.y - v1.y, b2 = u1.z - v1.z, b3 = u1.w - v1.w;
-                        p0 = fmaf(a3, a3, fmaf(a2, a2, fmaf(a1, a1, fmaf(a0, a0, p0))));
-                        p1 = fmaf(b3, b3, fmaf(b2, b2, fmaf(b1, b1, fmaf(b0, b0, p1))));
-                    }
-                    float part = p0 + p1;
-                    part += lane_xor<1>(part);
-                    part += lane_xor<2>(part);
-                    part += lane_xor<4>(part);
-                    part += lane_xor<8>(part);
-                    if (live && l16 == 0) {       // geomloss's cost from the same exact sum (kCostFloor2: its clamp_min)
+                    const float part = row16_d2([=](int d) { return ld4(xr + d); }, [=](int d) { return ld4(yr + d); });
+                    if (live && l16 == 0) {       // geomloss's cost from the same exact sum
                         ws.neg[slot * n_ent + gi * ld_e + gj] = -sqrtf(part);
-                        ws.cost[slot * n_ent + gi * ld_e + gj] = sqrtf(fmaxf(part, 1e-8f));
+                        ws.cost[slot * n_ent + gi * ld_e + gj] = cost_of_d2(part);
                     }
                 }
             }
@@ -724,26 +695,24 @@ pair_cost1_sub_kernel(ScoreArgs a, PairWs<1> ws, uint32_t T_rt) {
 // a lane OWNS R x R entries (i,j) of a pair and walks all 768 coordinates itself, so its accumulators are finished
 // sums and nothing is reduced across lanes.  The sentence rows are staged through LDS 16-byte chunk by chunk
 // (coalesced global_load_dwordx4 -> ds_write_b128; row stride padded so the operand reads are conflict free) and
-// re-read as ds_read_b128 broadcasts.  One wave handles NC = R*R candidates against one query:
-//   R = 1: 1 candidate, lane (li,lj) = (l>>3, l&7) owns entry (li,lj); stages of 128 coordinates (lanes 0-31 stage
-//          the query rows, lanes 32-63 the candidate rows)                                   -- lowest latency
-//   R = 2: 4 candidates, 16 lanes each, lane owns the 2x2 block (2li+a, 2lj+b); stages of 64 coordinates (the 16
-//          lanes of candidate p stage its 8 rows and query rows 2p, 2p+1)                    -- 3x fewer LDS reads
+// re-read as ds_read_b128 broadcasts.  One wave handles NC = R*R = 4 candidates against one query, 16 lanes each: a
+// lane owns the 2x2 block (2li+a, 2lj+b); stages of 64 coordinates (the 16 lanes of candidate p stage its 8 rows and
+// query rows 2p, 2p+1).  Every wave of the 4-wave workgroup takes its own items.
 // While staging, the lane that holds all 8 rows of a candidate for one chunk also forms that chunk's bounding-box
 // term (geomloss diameter) and the row norms, so those cost no extra pass either.
 // ---------------------------------------------------------------------------------------------
-template <int R>
 struct TileCfg {
-    static constexpr int kNC = R * R;              // candidates per wave
+    static constexpr int kR = 2;                   // a lane's block of entries is kR x kR
+    static constexpr int kNC = kR * kR;            // candidates per wave
     static constexpr int kLanesPerCand = 64 / kNC;
-    static constexpr int kGroups = R == 1 ? 2 : 4; // staging lane groups
+    static constexpr int kGroups = 4;              // staging lane groups
     static constexpr int kCh = 64 / kGroups;       // 16-byte chunks per row per stage
     static constexpr int kStages = 192 / kCh;
     static constexpr int kRowStride = 4 * kCh + 4; // floats; (kRowStride / 4) is odd -> rows land on distinct bank slots
     static constexpr int kRows = 8 + 8 * kNC;      // staged rows: 8 query + 8 per candidate
     static constexpr int kNormLd = 68;
     static constexpr int kLdsFloats = kRows * kRowStride + 16 * kNormLd;   // + norm / box scratch
-    static constexpr int kXRows = R == 1 ? 8 : 2;  // query rows staged by one lane
+    static constexpr int kXRows = 2;               // query rows staged by one lane
 };
 
 // per-coordinate bounding box of each query's valid rows: qbox[q][0][768] = min, qbox[q][1][768] = max
@@ -770,18 +739,14 @@ __global__ void __launch_bounds__(256) long_pair_census_kernel(ScoreArgs a, int3
     if ((threadIdx.x & 63) == 0 && n) atomicAdd(gate, n);
 }
 
-// DS = 1: every wave of the 4-wave workgroup takes its own items (throughput form).  DS > 1: the DS waves of a
-// workgroup share one item and each walks every DS-th stage, then wave 0 adds the partial results (latency form
-// for small grids).
-template <int R, int DS>
 __global__ void __launch_bounds__(256) pair_tile_kernel(ScoreArgs a, PairWs<1> ws, const float* __restrict__ qbox) {
-    using C = TileCfg<R>;
-    constexpr int kAcc = 2 * R * R;
+    using C = TileCfg;
+    constexpr int R = C::kR;
     extern __shared__ __attribute__((aligned(16))) float lds_all[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     float* lds = lds_all + wave * C::kLdsFloats;
-    float* nscr = lds + C::kRows * C::kRowStride;       // [16][kNormLd]: norm partials, then (DS = 4) accumulators
+    float* nscr = lds + C::kRows * C::kRowStride;       // [16][kNormLd]: norm partials
     const bool paired = a.pairing == ASPIRE_PAIR_PAIRED;
     const bool mapped = a.pairing == kPairMapped;                // batched jobs: items are the groups of four of jobs [job0, job1)
     const bool own_diam = a.diameter == nullptr;
@@ -790,18 +755,14 @@ __global__ void __launch_bounds__(256) pair_tile_kernel(ScoreArgs a, PairWs<1> w
     const uint32_t ngroups = (ncand + C::kNC - 1) / C::kNC;
     const uint32_t item_lo = mapped ? (uint32_t)a.grp_off[a.job0] : 0u;
     const uint32_t n_items = mapped ? (uint32_t)a.grp_off[a.job1] : ngroups * nq;   // item = (candidate group, query), group-major
-    const uint32_t first = item_lo + (DS == 1 ? blockIdx.x * 4 + wave : blockIdx.x);
-    const uint32_t stride = DS == 1 ? gridDim.x * 4 : gridDim.x;
+    const uint32_t first = item_lo + blockIdx.x * 4 + wave;
+    const uint32_t stride = gridDim.x * 4;
 
     // lane roles ------------------------------------------------------------------------------------------
-    const int p = lane / C::kLanesPerCand;                       // candidate of this lane (compute AND staging, R = 2)
+    const int p = lane / C::kLanesPerCand;                       // candidate of this lane (compute AND staging)
     const int lp = lane % C::kLanesPerCand;
     const int li = lp / (8 / R), lj = lp % (8 / R);
-    const int sg = lane / C::kCh, sc = lane % C::kCh;            // staging group, staging chunk
-    // what this lane stages: R = 1: group 0 -> the 8 query rows, group 1 -> the 8 candidate rows;
-    //                        R = 2: group g -> the 8 rows of candidate g and query rows 2g, 2g+1.
-    const bool stages_y = R == 2 || sg == 1;
-    const bool stages_x = R == 2 || sg == 0;
+    const int sg = lane / C::kCh, sc = lane % C::kCh;            // staging group, staging chunk: group g stages the 8 rows of candidate g and query rows 2g, 2g+1
 
     for (uint32_t item = first; item < n_items; item += stride) {
         const uint32_t cg = nq == 1 ? item : item / nq;
@@ -813,14 +774,14 @@ __global__ void __launch_bounds__(256) pair_tile_kernel(ScoreArgs a, PairWs<1> w
             c_loc0 = (uint32_t)a.job_off[q_loc] + (item - (uint32_t)a.grp_off[q_loc]) * C::kNC;
             c_end = (uint32_t)a.job_off[q_loc + 1];
         }
-        const uint32_t my_c_loc = min(c_loc0 + (R == 1 ? 0u : (uint32_t)p), c_end - 1);   // tail groups: clamp (duplicate work, not stored)
-        const bool my_c_real = c_loc0 + (R == 1 ? 0u : (uint32_t)p) < c_end;
+        const uint32_t my_c_loc = min(c_loc0 + (uint32_t)p, c_end - 1);   // tail groups: clamp (duplicate work, not stored)
+        const bool my_c_real = c_loc0 + (uint32_t)p < c_end;
         const int64_t c_idx = a.cand0 + my_c_loc;
         const int64_t q_idx = paired ? c_idx : (int64_t)q_loc;
         const int c_len = a.c.len[c_idx], q_len = a.q.len[q_idx];
         const float* qdoc = a.q.rows + (size_t)a.q.start[q_idx] * kD;
         // staging source of this lane (pad rows clamp to the last valid row: masked downstream, box-neutral)
-        const int64_t sy_idx = a.cand0 + (R == 1 ? my_c_loc : min(c_loc0 + (uint32_t)sg, c_end - 1));
+        const int64_t sy_idx = a.cand0 + min(c_loc0 + (uint32_t)sg, c_end - 1);
         const int sy_len = a.c.len[sy_idx];
         const float* sy_doc = a.c.rows + (size_t)a.c.start[sy_idx] * kD;
 
@@ -840,53 +801,42 @@ __global__ void __launch_bounds__(256) pair_tile_kernel(ScoreArgs a, PairWs<1> w
         const int qb_hi = own_diam ? kD : 0;
         auto issue_loads = [&](int st) {
             const int dofs = (st * C::kCh + sc) * 4;
-            if (stages_y) {
 #pragma unroll
-                for (int j = 0; j < 8; ++j) vy[j] = ld4_stream(sy_doc + (size_t)min(j, sy_len - 1) * kD + dofs);
-                // UNCONDITIONAL (with caller-supplied diameters the candidate's first row stands in and the box term
-                // is unused): a branch around these two loads made the compiler wait for the row loads just issued
-                // at the join -- every stage's HBM latency in series with its arithmetic (see fused.hip)
-                qmn = ld4(qb + dofs);
-                qmx = ld4(qb + qb_hi + dofs);
-            }
-            if (stages_x) {
+            for (int j = 0; j < 8; ++j) vy[j] = ld4_stream(sy_doc + (size_t)min(j, sy_len - 1) * kD + dofs);
+            // UNCONDITIONAL (with caller-supplied diameters the candidate's first row stands in and the box term
+            // is unused): a branch around these two loads made the compiler wait for the row loads just issued
+            // at the join -- every stage's HBM latency in series with its arithmetic (see fused.hip)
+            qmn = ld4(qb + dofs);
+            qmx = ld4(qb + qb_hi + dofs);
 #pragma unroll
-                for (int k = 0; k < C::kXRows; ++k)
-                    vx[k] = ld4(qdoc + (size_t)min(R == 1 ? k : 2 * sg + k, q_len - 1) * kD + dofs);
-            }
+            for (int k = 0; k < C::kXRows; ++k) vx[k] = ld4(qdoc + (size_t)min(2 * sg + k, q_len - 1) * kD + dofs);
         };
-        const int st0 = DS == 1 ? 0 : wave;
-        if (st0 < C::kStages) issue_loads(st0);
+        issue_loads(0);
 #pragma unroll 1
-        for (int st = st0; st < C::kStages; st += DS) {
+        for (int st = 0; st < C::kStages; ++st) {
             // ---- stage: registers -> LDS, with box / norm side products; then the NEXT stage's loads go out so
             // that they fly under this stage's arithmetic (no extra registers: the rows were just consumed) ----
-            if (stages_y) {
-                float4 mn = vy[0], mx = vy[0];
+            float4 mn = vy[0], mx = vy[0];
 #pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    ny[j] += sq4(vy[j]);
-                    if (j > 0) {
-                        mn.x = fminf(mn.x, vy[j].x); mn.y = fminf(mn.y, vy[j].y); mn.z = fminf(mn.z, vy[j].z); mn.w = fminf(mn.w, vy[j].w);
-                        mx.x = fmaxf(mx.x, vy[j].x); mx.y = fmaxf(mx.y, vy[j].y); mx.z = fmaxf(mx.z, vy[j].z); mx.w = fmaxf(mx.w, vy[j].w);
-                    }
-                    const int row = 8 + (R == 1 ? 0 : sg) * 8 + j;
-                    *reinterpret_cast<float4*>(lds + row * C::kRowStride + sc * 4) = vy[j];
+            for (int j = 0; j < 8; ++j) {
+                ny[j] += sq4(vy[j]);
+                if (j > 0) {
+                    mn.x = fminf(mn.x, vy[j].x); mn.y = fminf(mn.y, vy[j].y); mn.z = fminf(mn.z, vy[j].z); mn.w = fminf(mn.w, vy[j].w);
+                    mx.x = fmaxf(mx.x, vy[j].x); mx.y = fmaxf(mx.y, vy[j].y); mx.z = fmaxf(mx.z, vy[j].z); mx.w = fmaxf(mx.w, vy[j].w);
                 }
-                if (own_diam) {
-                    const float dx = fmaxf(mx.x, qmx.x) - fminf(mn.x, qmn.x), dy = fmaxf(mx.y, qmx.y) - fminf(mn.y, qmn.y);
-                    const float dz = fmaxf(mx.z, qmx.z) - fminf(mn.z, qmn.z), dw = fmaxf(mx.w, qmx.w) - fminf(mn.w, qmn.w);
-                    dsq += fmaf(dw, dw, fmaf(dz, dz, fmaf(dy, dy, dx * dx)));
-                }
+                *reinterpret_cast<float4*>(lds + (8 + sg * 8 + j) * C::kRowStride + sc * 4) = vy[j];
             }
-            if (stages_x) {
+            if (own_diam) {
+                const float dx = fmaxf(mx.x, qmx.x) - fminf(mn.x, qmn.x), dy = fmaxf(mx.y, qmx.y) - fminf(mn.y, qmn.y);
+                const float dz = fmaxf(mx.z, qmx.z) - fminf(mn.z, qmn.z), dw = fmaxf(mx.w, qmx.w) - fminf(mn.w, qmn.w);
+                dsq += fmaf(dw, dw, fmaf(dz, dz, fmaf(dy, dy, dx * dx)));
+            }
 #pragma unroll
-                for (int k = 0; k < C::kXRows; ++k) {
-                    nx[k] += sq4(vx[k]);
-                    *reinterpret_cast<float4*>(lds + (R == 1 ? k : 2 * sg + k) * C::kRowStride + sc * 4) = vx[k];
-                }
+            for (int k = 0; k < C::kXRows; ++k) {
+                nx[k] += sq4(vx[k]);
+                *reinterpret_cast<float4*>(lds + (2 * sg + k) * C::kRowStride + sc * 4) = vx[k];
             }
-            if (st + DS < C::kStages) issue_loads(st + DS);
+            if (st + 1 < C::kStages) issue_loads(st + 1);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -918,79 +868,38 @@ __global__ void __launch_bounds__(256) pair_tile_kernel(ScoreArgs a, PairWs<1> w
         // ---- norms and box: sum the staging lanes' partials through the scratch table nscr[value][lane] --------
         // value 0..7: |y_j|^2 partials of the lane's staged candidate; 8..8+kXRows-1: |x|^2 partials of its query rows
 #pragma unroll
-        for (int k = 0; k < 8; ++k) nscr[k * C::kNormLd + lane] = stages_y ? ny[k] : 0.f;
+        for (int k = 0; k < 8; ++k) nscr[k * C::kNormLd + lane] = ny[k];
 #pragma unroll
-        for (int k = 0; k < C::kXRows; ++k) nscr[(8 + k) * C::kNormLd + lane] = stages_x ? nx[k] : 0.f;
-        if constexpr (DS == 1) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        } else {
-            // the other waves' accumulators and box terms travel through their stage buffers (free by now)
-#pragma unroll
-            for (int x = 0; x < R; ++x)
-#pragma unroll
-                for (int y = 0; y < R; ++y) {
-                    lds[((x * R + y) * 2 + 0) * 64 + lane] = accg[x][y];
-                }
-            lds[kAcc * 64 + lane] = dsq;
-            __syncthreads();
-            if (wave != 0) {
-                __syncthreads();   // matches the end-of-item barrier below
-                continue;
-            }
-#pragma unroll
-            for (int w = 1; w < DS; ++w) {
-                const float* o = lds_all + w * C::kLdsFloats;
-#pragma unroll
-                for (int x = 0; x < R; ++x)
-#pragma unroll
-                    for (int y = 0; y < R; ++y) {
-                        accg[x][y] += o[((x * R + y) * 2 + 0) * 64 + lane];
-                    }
-                dsq += o[kAcc * 64 + lane];
-            }
-        }
+        for (int k = 0; k < C::kXRows; ++k) nscr[(8 + k) * C::kNormLd + lane] = nx[k];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         auto table_sum = [&](int value, int lane0, int nlanes) {
             float t = 0.f;
-#pragma unroll
-            for (int w = 0; w < DS; ++w) {
-                const float4* src = reinterpret_cast<const float4*>(lds_all + (DS == 1 ? wave : w) * C::kLdsFloats +
-                                                                    C::kRows * C::kRowStride + value * C::kNormLd + lane0);
-                for (int m = 0; m < nlanes / 4; ++m) {
-                    const float4 u = src[m];
-                    t += (u.x + u.y) + (u.z + u.w);
-                }
+            const float4* src = reinterpret_cast<const float4*>(lds_all + wave * C::kLdsFloats + C::kRows * C::kRowStride + value * C::kNormLd + lane0);
+            for (int m = 0; m < nlanes / 4; ++m) {
+                const float4 u = src[m];
+                t += (u.x + u.y) + (u.z + u.w);
             }
             return t;
         };
         float xx[R], yy[R];
-        if constexpr (R == 1) {
-            // x partials live in lanes 0..31 (staging group 0), y partials in lanes 32..63
-            yy[0] = table_sum(lj, 32, 32);
-            xx[0] = table_sum(8 + li, 0, 32);
-        } else {
 #pragma unroll
-            for (int y = 0; y < R; ++y) yy[y] = table_sum(R * lj + y, p * 16, 16);
+        for (int y = 0; y < R; ++y) yy[y] = table_sum(R * lj + y, p * 16, 16);
 #pragma unroll
-            for (int x = 0; x < R; ++x) xx[x] = table_sum(8 + ((R * li + x) & 1), ((R * li + x) >> 1) * 16, 16);
-        }
+        for (int x = 0; x < R; ++x) xx[x] = table_sum(8 + ((R * li + x) & 1), ((R * li + x) >> 1) * 16, 16);
         float diam2 = 0.f;
         if (own_diam) {
             // box terms were formed by the lanes that staged candidate rows: sum them over that candidate's lanes
-            if constexpr (R == 1) {
-                diam2 = wave_sum(stages_y ? dsq : 0.f);
-            } else {
-                float t = dsq;                       // 16 staging lanes of candidate sg == this lane's p (same grouping)
-                t += lane_xor<1>(t); t += lane_xor<2>(t); t += lane_xor<4>(t); t += lane_xor<8>(t);
-                diam2 = t;
-            }
+            float t = dsq;                       // 16 staging lanes of candidate sg == this lane's p (same grouping)
+            t += lane_xor<1>(t); t += lane_xor<2>(t); t += lane_xor<4>(t); t += lane_xor<8>(t);
+            diam2 = t;
         }
 
         // ---- finish the entries and hand them to the Sinkhorn kernel -----------------------------------------
         // Only x.y was accumulated: -cdist comes from the same expansion as the cost, and the entries where it cancels
         // (torch.cdist's direct formula differs there) are redone below.  See pair_cost1_kernel.
-        // (round 6: a cancelling entry is redone from the exact sum whatever formula torch.cdist would pick -- also beyond 25 rows: include/aspire_hip.h, SHARED SENTENCES)
+        // (the rule and the exact sum: exact_d2.h)
         const int64_t slot = (paired || mapped) ? (int64_t)my_c_loc : (int64_t)q_loc * ncand + my_c_loc;
         bool redo[R][R];
 #pragma unroll
@@ -1000,16 +909,16 @@ __global__ void __launch_bounds__(256) pair_tile_kernel(ScoreArgs a, PairWs<1> w
                 const int i = R * li + x, j = R * lj + y;
                 const float sq = fmaf(-2.f, accg[x][y], xx[x]) + yy[y];
                 const float ns = xx[x] + yy[y];
-                redo[x][y] = my_c_real && i < q_len && j < c_len && sq < 1e-4f * ns * ns;
+                redo[x][y] = my_c_real && i < q_len && j < c_len && expansion_cancels(sq, ns);
                 if (my_c_real && !redo[x][y]) {
-                    ws.cost[slot * 64 + i * 8 + j] = sqrtf(fmaxf(sq, 1e-8f));
-                    ws.neg[slot * 64 + i * 8 + j] = -sqrtf(fmaxf(sq, 0.f));
+                    ws.cost[slot * 64 + i * 8 + j] = cost_of_d2(sq);
+                    ws.neg[slot * 64 + i * 8 + j] = neg_of_expansion(sq);
                 }
             }
         if (my_c_real && own_diam && lp == 0) ws.diam2[slot] = diam2;
-        if constexpr (R == 2 && DS == 1) {
-            // direct-formula redo, the whole wave on one entry (12 coordinates per lane), four entries per memory round trip
-            // (see pair_fused_kernel: one entry per trip makes a wave with a duplicate document fall behind by 8 trips)
+        {
+            // direct-formula redo, the whole wave on one entry, four entries per memory round trip: this kernel's own text of
+            // exact_d2.h's redo_wave4 (through the helper it takes 212 registers instead of 210: NOTES.md)
             const int c_start_v = a.c.start[c_idx];
 #pragma unroll
             for (int x = 0; x < R; ++x)
@@ -1039,48 +948,21 @@ __global__ void __launch_bounds__(256) pair_tile_kernel(ScoreArgs a, PairWs<1> w
                         }
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            float part = 0.f;
-#pragma unroll
-                            for (int t = 0; t < 3; ++t) {
-                                const float d0 = u[e][t].x - v[e][t].x, d1 = u[e][t].y - v[e][t].y, d2 = u[e][t].z - v[e][t].z, d3 = u[e][t].w - v[e][t].w;
-                                part = fmaf(d3, d3, fmaf(d2, d2, fmaf(d1, d1, fmaf(d0, d0, part))));
-                            }
+                            const float part = wave_d2_part(u[e], v[e]);
                             if (owner[e] >= 0) {
                                 const float tot = wave_sum(part);
                                 const int ol = owner[e] & 15, i = R * (ol >> 2) + x, j = R * (ol & 3) + y;
                                 if (lane == owner[e]) {
                                     ws.neg[slot * 64 + i * 8 + j] = -sqrtf(tot);
-                                    ws.cost[slot * 64 + i * 8 + j] = sqrtf(fmaxf(tot, 1e-8f));      // geomloss's cost from the same exact sum
+                                    ws.cost[slot * 64 + i * 8 + j] = cost_of_d2(tot);      // geomloss's cost from the same exact sum
                                 }
                             }
                         }
                     }
                 }
-        } else {
-#pragma unroll
-            for (int x = 0; x < R; ++x)
-#pragma unroll
-                for (int y = 0; y < R; ++y)
-                    if (redo[x][y]) {   // other layouts (not instantiated for production): lane-local direct sum
-                        const int i = R * li + x, j = R * lj + y;
-                        const float* xr = qdoc + (size_t)i * kD;
-                        const float* yr = a.c.rows + ((size_t)a.c.start[c_idx] + j) * kD;
-                        float d2s = 0.f;
-                        for (int d = 0; d < kD; d += 4) {
-                            const float4 u = ld4(xr + d), v = ld4(yr + d);
-                            const float d0 = u.x - v.x, d1 = u.y - v.y, d2 = u.z - v.z, d3 = u.w - v.w;
-                            d2s = fmaf(d3, d3, fmaf(d2, d2, fmaf(d1, d1, fmaf(d0, d0, d2s))));
-                        }
-                        ws.neg[slot * 64 + i * 8 + j] = -sqrtf(d2s);
-                        ws.cost[slot * 64 + i * 8 + j] = sqrtf(fmaxf(d2s, 1e-8f));
-                    }
         }
-        if constexpr (DS == 1) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // scratch and stage buffers are reused by the next item
-            __builtin_amdgcn_wave_barrier();
-        } else {
-            __syncthreads();
-        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // scratch and stage buffers are reused by the next item
+        __builtin_amdgcn_wave_barrier();
     }
 }
 
@@ -1187,8 +1069,8 @@ int launch_cost_stage(const ScoreArgs& a, int T_rt, const aspire_repset* q, cons
                     if (int rc = launch_doc_box(a.q, qbox, stream)) return rc;
                 const int64_t wave_cap = tuning().tile_waves > 0 ? tuning().tile_waves : 256 * 8;      // TILE_WAVES: tests with several items per wave
                 const int64_t waves = groups4 < wave_cap ? groups4 : wave_cap;
-                hipLaunchKernelGGL((pair_tile_kernel<2, 1>), dim3((unsigned)((waves + 3) / 4)), dim3(256),
-                                   4 * TileCfg<2>::kLdsFloats * sizeof(float), stream, a, ws1, qbox);
+                hipLaunchKernelGGL(pair_tile_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256),
+                                   4 * TileCfg::kLdsFloats * sizeof(float), stream, a, ws1, qbox);
             } else {
                 // small grids are latency bound: three waves per pair (a third of the coordinates each), persistent and
                 // software pipelined (measured 15.6 us per launch at 50-250 pairs against 20-23 us for the tiled form with its

@@ -44,6 +44,7 @@
 #include "common.h"
 #include "score_device.h"
 #include "score_types.h"
+#include "exact_d2.h"
 #include "fused_solve.h"
 #include "tuning.h"
 

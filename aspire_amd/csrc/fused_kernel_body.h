@@ -413,7 +413,7 @@
 
         // ---- finish the entries.  Only x.y was accumulated: -cdist comes from the same expansion as geomloss's cost, and
         // the entries where it cancels (torch.cdist's direct formula differs there) are redone below ----------------------
-        // (round 6: a cancelling entry is redone from the exact sum whatever formula torch.cdist would pick -- also beyond 25 rows: include/aspire_hip.h, SHARED SENTENCES)
+        // (the rule and the exact sum: exact_d2.h)
         float cost[2][2], neg[2][2];
         bool redo[2][2];
 #pragma unroll
@@ -423,66 +423,26 @@
                 const int i = 2 * li + x, j = row0 + 2 * lj + y;
                 const float sq = fmaf(-2.f, accg[x][y], xx[x]) + yy[y];
                 const float ns = xx[x] + yy[y];
-                redo[x][y] = i < q_len && j < c_len && sq < 1e-4f * ns * ns;
-                cost[x][y] = sqrtf(fmaxf(sq, 1e-8f));
-                neg[x][y] = -sqrtf(fmaxf(sq, 0.f));
+                redo[x][y] = i < q_len && j < c_len && expansion_cancels(sq, ns);
+                cost[x][y] = cost_of_d2(sq);
+                neg[x][y] = neg_of_expansion(sq);
             }
-        {
-            // direct-formula redo, the whole wave on one entry (12 coordinates per lane), FOUR entries per memory round trip:
-            // under a saturated HBM stream a dependent round trip is ~5 us, and a wave that falls behind by n of them
-            // finishes the launch n x 5 us late (one duplicate document = 8 entries in a 20 000-pair call, one entry per
-            // round trip: 145 instead of 101 us)
+        // direct-formula redo, the whole wave on one entry, four entries per memory round trip (exact_d2.h, form A)
 #pragma unroll
-            for (int x = 0; x < 2; ++x)
+        for (int x = 0; x < 2; ++x)
 #pragma unroll
-                for (int y = 0; y < 2; ++y) {
-                    unsigned long long wm = __ballot(redo[x][y]);
-                    while (wm != 0) {
-                        int owner[4];
-                        float part[4];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            owner[e] = wm != 0 ? (int)__builtin_ctzll(wm) : -1;
-                            wm = wm != 0 ? wm & (wm - 1) : 0;
-                        }
-                        // all 24 loads go out before the first is consumed: no branch around them (an empty slot
-                        // repeats the first entry's rows)
-                        float4 u[4][3], v[4][3];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const int o = owner[e] >= 0 ? owner[e] : owner[0];
-                            const int ol = o & 15, i = 2 * (ol >> 2) + x;
-                            const int j = (CHUNK ? __builtin_amdgcn_readlane(row0, o) : 0) + 2 * (ol & 3) + y;
-                            const int cs_e = __builtin_amdgcn_readlane(c_start, o);
-                            const float* qrow = qdoc + (size_t)i * kD + 4 * lane;
-                            const float* crow = a.c.rows + ((size_t)cs_e + j) * kD + 4 * lane;
-#pragma unroll
-                            for (int t = 0; t < 3; ++t) {
-                                u[e][t] = ld4(qrow + 256 * t);
-                                v[e][t] = ld4(crow + 256 * t);
-                            }
-                        }
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            part[e] = 0.f;
-#pragma unroll
-                            for (int t = 0; t < 3; ++t) {
-                                const float d0 = u[e][t].x - v[e][t].x, d1 = u[e][t].y - v[e][t].y, d2 = u[e][t].z - v[e][t].z, d3 = u[e][t].w - v[e][t].w;
-                                part[e] = fmaf(d3, d3, fmaf(d2, d2, fmaf(d1, d1, fmaf(d0, d0, part[e]))));
-                            }
-                        }
-#pragma unroll
-                        for (int e = 0; e < 4; ++e)
-                            if (owner[e] >= 0) {
-                                const float tot = wave_sum(part[e]);
-                                if (lane == owner[e]) {
-                                    neg[x][y] = -sqrtf(tot);
-                                    cost[x][y] = sqrtf(fmaxf(tot, 1e-8f));      // geomloss's cost from the same exact sum (see the header of this block)
-                                }
-                            }
-                    }
-                }
-        }
+            for (int y = 0; y < 2; ++y)
+                redo_wave4(__ballot(redo[x][y]), lane,
+                           [&](int o) {
+                               const int ol = o & 15, i = 2 * (ol >> 2) + x;
+                               const int j = (CHUNK ? __builtin_amdgcn_readlane(row0, o) : 0) + 2 * (ol & 3) + y;
+                               const int cs_e = __builtin_amdgcn_readlane(c_start, o);
+                               return RowPair{qdoc + (size_t)i * kD, a.c.rows + ((size_t)cs_e + j) * kD};
+                           },
+                           [&](int, float tot) {
+                               neg[x][y] = -sqrtf(tot);
+                               cost[x][y] = cost_of_d2(tot);      // geomloss's cost from the same exact sum
+                           });
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // the scratch table is rewritten by the next item
         __builtin_amdgcn_wave_barrier();
         cached_q = q_idx;

@@ -14,6 +14,7 @@
 
 #include "common.h"
 #include "score_device.h"
+#include "exact_d2.h"
 #include "score_types.h"
 
 namespace aspire {
@@ -112,19 +113,16 @@ __device__ __forceinline__ void pair_generic_body(const ScoreArgs& a, int mode, 
             const float4 u0 = ld4(x + d), v0 = ld4(y + d), u1 = ld4(x + d + 4), v1 = ld4(y + d + 4);
             g0 += dot4(u0, v0);
             g1 += dot4(u1, v1);
-            const float a0 = u0.x - v0.x, a1 = u0.y - v0.y, a2 = u0.z - v0.z, a3 = u0.w - v0.w;
-            const float b0 = u1.x - v1.x, b1 = u1.y - v1.y, b2 = u1.z - v1.z, b3 = u1.w - v1.w;
-            d0 = fmaf(a3, a3, fmaf(a2, a2, fmaf(a1, a1, fmaf(a0, a0, d0))));
-            d1 = fmaf(b3, b3, fmaf(b2, b2, fmaf(b1, b1, fmaf(b0, b0, d1))));
+            d2_step2(u0, v0, u1, v1, d0, d1);
         }
         const float sq = fmaf(-2.f, g0 + g1, lds[L.xx + i]) + lds[L.yy + j];
         const float ns = lds[L.xx + i] + lds[L.yy + j];
         // (where the expansion cancels -- the streaming kernels' test -- geomloss's cost comes from the exact sum too: what its own
         // formula gives in float64; in fp32 the reference returns the square root of rounding noise there)
-        // (round 6: ... and so does -cdist, also under torch.cdist's matmul formula: one rule for a cancelling entry in every kernel family)
-        const bool cancels = sq < 1e-4f * ns * ns;
-        cost[i * ld + j] = sqrtf(fmaxf(cancels ? d0 + d1 : sq, 1e-8f));
-        neg[i * ld + j] = (mm && !cancels) ? -sqrtf(fmaxf(sq, 0.f)) : -sqrtf(d0 + d1);
+        // (... and so does -cdist, also under torch.cdist's matmul formula: the rule is exact_d2.h's)
+        const bool cancels = expansion_cancels(sq, ns);
+        cost[i * ld + j] = cost_of_d2(cancels ? d0 + d1 : sq);
+        neg[i * ld + j] = (mm && !cancels) ? neg_of_expansion(sq) : -sqrtf(d0 + d1);
     }
     __syncthreads();
 

@@ -30,6 +30,7 @@
 #include "tuning.h"
 #include "score_types.h"
 #include "score_device.h"
+#include "exact_d2.h"
 
 namespace aspire {
 namespace {
@@ -39,7 +40,6 @@ typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 
 constexpr int kBM = 128;   // candidate rows per tile
 constexpr int kBK = 16;    // coordinates per LDS stage
-constexpr float kDirectTau = 1e-4f;   // recompute (x-y)^2 directly when d^2 < tau * (|x|^2 + |y|^2)^2
 
 struct GramArgs {
     RepSet q, c;
@@ -92,19 +92,9 @@ __device__ __forceinline__ float ldg1(unsigned long long addr, int ofs) {
 #endif
 }
 
-__device__ __forceinline__ float sq4f(const float4& a) { return fmaf(a.w, a.w, fmaf(a.z, a.z, fmaf(a.y, a.y, a.x * a.x))); }
-
 // sum_d (x_d - y_d)^2 over the 768 coordinates (rare path: near-coincident sentences)
 __device__ __noinline__ float direct_d2(unsigned long long x, unsigned long long y) {
-    float s0 = 0.f, s1 = 0.f;
-    for (int k = 0; k < kD; k += 8) {
-        const float4 a = ldg4(x, k), b = ldg4(y, k), c = ldg4(x, k + 4), d = ldg4(y, k + 4);
-        const float e0 = a.x - b.x, e1 = a.y - b.y, e2 = a.z - b.z, e3 = a.w - b.w;
-        const float f0 = c.x - d.x, f1 = c.y - d.y, f2 = c.z - d.z, f3 = c.w - d.w;
-        s0 = fmaf(e3, e3, fmaf(e2, e2, fmaf(e1, e1, fmaf(e0, e0, s0))));
-        s1 = fmaf(f3, f3, fmaf(f2, f2, fmaf(f1, f1, fmaf(f0, f0, s1))));
-    }
-    return s0 + s1;
+    return lane_d2([=](int k) { return ldg4(x, k); }, [=](int k) { return ldg4(y, k); });      // exact_d2.h, form C
 }
 
 // Three workgroups per CU for the 32/64-column tiles costs 80-144 B of scratch per lane (epilogue values) against
@@ -238,13 +228,13 @@ __global__ void __launch_bounds__(256, 2) pair_gram_kernel(GramArgs g) {
         for (int p = 0; p < A_F4; ++p) {
             const float4 v = sub4(ra[S][p], rm[S]);
             split_store(As3[buf][0], As3[buf][1], As3[buf][2], lrow + 64 * p, v);
-            na[p] = fmaf(count, sq4f(v), na[p]);
+            na[p] = fmaf(count, sq4(v), na[p]);
         }
 #pragma unroll
         for (int p = 0; p < B_F4; ++p) {
             const float4 v = sub4(rb[S][p], rm[S]);
             split_store(Bs3[buf][0], Bs3[buf][1], Bs3[buf][2], lrow + 64 * p, v);
-            nb[p] = fmaf(count, sq4f(v), nb[p]);
+            nb[p] = fmaf(count, sq4(v), nb[p]);
         }
     };
     auto store_piece = [&](auto setc, int piece, int buf) {
@@ -256,7 +246,7 @@ __global__ void __launch_bounds__(256, 2) pair_gram_kernel(GramArgs g) {
             As[buf][4 * lk4 + 1][row] = v.y;
             As[buf][4 * lk4 + 2][row] = v.z;
             As[buf][4 * lk4 + 3][row] = v.w;
-            na[p] += sq4f(v);
+            na[p] += sq4(v);
         } else if (piece < A_F4 + B_F4) {
             const int p = piece - A_F4;
             if (B_ALL || lrow < BN) {
@@ -266,7 +256,7 @@ __global__ void __launch_bounds__(256, 2) pair_gram_kernel(GramArgs g) {
                 Bs[buf][4 * lk4 + 1][row] = v.y;
                 Bs[buf][4 * lk4 + 2][row] = v.z;
                 Bs[buf][4 * lk4 + 3][row] = v.w;
-                nb[p] += sq4f(v);
+                nb[p] += sq4(v);
             }
         }
     };
@@ -486,7 +476,7 @@ __global__ void __launch_bounds__(256, 2) pair_gram_kernel(GramArgs g) {
                 const int m0 = wr * WM + 32 * i + 8 * g4 + 4 * lk;
                 const long long co = c_off[m0];
                 if (qo < 0 || co < 0) continue;
-                // (round 6: a cancelling entry is redone from the exact sum whatever formula torch.cdist would pick -- also beyond 25 rows: include/aspire_hip.h, SHARED SENTENCES)
+                // (the rule and the exact sums: exact_d2.h)
                 const float4 yy4 = *reinterpret_cast<const float4*>(&c_nrm[m0]);
                 const float yy[4] = {yy4.x, yy4.y, yy4.z, yy4.w};
                 float cost[4], neg[4];
@@ -495,17 +485,17 @@ __global__ void __launch_bounds__(256, 2) pair_gram_kernel(GramArgs g) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const float sq = fmaf(-2.f, acc[i][j][4 * g4 + k], xx) + yy[k];
-                    cost[k] = sqrtf(fmaxf(sq, 1e-8f));
-                    neg[k] = -sqrtf(fmaxf(sq, 0.f));
+                    cost[k] = cost_of_d2(sq);
+                    neg[k] = neg_of_expansion(sq);
                     const float ns = xx + yy[k];
-                    redo[k] = sq < kDirectTau * ns * ns && qp != zrow && c_ptr[m0 + k] != zrow;
+                    redo[k] = expansion_cancels(sq, ns) && qp != zrow && c_ptr[m0 + k] != zrow;
                     if (redo[k]) {
                         const uint32_t slot = atomicAdd(&wl_count, 1u);
                         if (slot < (uint32_t)kCap) wlist[slot] = ((uint32_t)(m0 + k) << 16) | (uint32_t)n;
                         else {   // list full: lane-local
                             const float d2 = direct_d2(qp, c_ptr[m0 + k]);
                             neg[k] = -sqrtf(d2);
-                            cost[k] = sqrtf(fmaxf(d2, 1e-8f));
+                            cost[k] = cost_of_d2(d2);
                             redo[k] = false;
                         }
                     }
@@ -534,7 +524,7 @@ __global__ void __launch_bounds__(256, 2) pair_gram_kernel(GramArgs g) {
         }
     __syncthreads();
     {
-        // 16 lanes (one DPP row) per entry, 48 coordinates per lane: 16 entries per workgroup in flight, 24
+        // 16 lanes (one DPP row) per entry, 48 coordinates per lane (exact_d2.h, form B): 16 entries per workgroup in flight, 24
         // independent 16-byte loads per lane, and a 4-step in-row reduction
         const uint32_t n_redo = min(wl_count, (uint32_t)kCap);
         const int grp = tid >> 4, l16 = tid & 15;
@@ -544,27 +534,13 @@ __global__ void __launch_bounds__(256, 2) pair_gram_kernel(GramArgs g) {
             const uint32_t mn = wlist[live ? e : 0];
             const int m = (int)(mn >> 16), n = (int)(mn & 0xFFFFu);
             const unsigned long long xp = q_ptr[n], yp = c_ptr[m];
-            float p0 = 0.f, p1 = 0.f;
-#pragma unroll
-            for (int c = 0; c < 12; c += 2) {
-                const float4 u0 = ldg4(xp, 4 * l16 + 64 * c), v0 = ldg4(yp, 4 * l16 + 64 * c);
-                const float4 u1 = ldg4(xp, 4 * l16 + 64 * c + 64), v1 = ldg4(yp, 4 * l16 + 64 * c + 64);
-                const float a0 = u0.x - v0.x, a1 = u0.y - v0.y, a2 = u0.z - v0.z, a3 = u0.w - v0.w;
-                const float b0 = u1.x - v1.x, b1 = u1.y - v1.y, b2 = u1.z - v1.z, b3 = u1.w - v1.w;
-                p0 = fmaf(a3, a3, fmaf(a2, a2, fmaf(a1, a1, fmaf(a0, a0, p0))));
-                p1 = fmaf(b3, b3, fmaf(b2, b2, fmaf(b1, b1, fmaf(b0, b0, p1))));
-            }
-            float part = p0 + p1;
-            part += lane_xor<1>(part);
-            part += lane_xor<2>(part);
-            part += lane_xor<4>(part);
-            part += lane_xor<8>(part);
+            const float part = row16_d2([=](int d) { return ldg4(xp, 4 * l16 + d); }, [=](int d) { return ldg4(yp, 4 * l16 + d); });
             const float negd = -sqrtf(part);
             if (live && l16 == 0) {
                 if constexpr (L2MAX) atomicMax(&pairmax[(int)c_off[m] * 16 + (int)q_off[n]], order_key(negd));
                 else {
                     g.neg[q_off[n] + c_off[m]] = negd;
-                    if (g.cost) g.cost[q_off[n] + c_off[m]] = sqrtf(fmaxf(part, 1e-8f));
+                    if (g.cost) g.cost[q_off[n] + c_off[m]] = cost_of_d2(part);
                 }
             }
         }

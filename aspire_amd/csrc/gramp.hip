@@ -31,6 +31,7 @@
 #include "tuning.h"
 #include "score_types.h"
 #include "score_device.h"
+#include "exact_d2.h"
 
 namespace aspire {
 namespace {
@@ -40,7 +41,6 @@ typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 
 constexpr int kKBlocks = kD / 16;          // 48
 constexpr int kRowB = 64;                  // one row of one k block: 2 planes x 2 k halves x 16 bytes
-constexpr float kDirectTau = 1e-4f;        // as gram.hip: redo (x-y)^2 directly when d^2 < tau * (|x|^2 + |y|^2)^2
 constexpr int kMuSample = 4096;
 #ifndef GRAMP_SPREAD
 #define GRAMP_SPREAD 1   // 1: the LDS-DMA pieces of a stage go out one at a time between runs of MFMAs, 0: together behind the barrier
@@ -444,7 +444,7 @@ __global__ void __launch_bounds__(2 * BM, (BM == 128 && BN == 128) ? 3 : (BM == 
                     for (int k = 0; k < 4; ++k) {
                         const float ns = xx + yy[k];
                         const float sq = fmaf(acc[i][j][4 * g4 + k], qis2 * cis[k], ns);       // the scales are powers of two: exact
-                        const bool redo = sq < kDirectTau * ns * ns;
+                        const bool redo = expansion_cancels(sq, ns);       // (the rule and the exact sums: exact_d2.h)
                         if (__builtin_expect(redo, 0)) {
                             const uint32_t slot = atomicAdd(&wl_count, 1u);
                             if (slot < (uint32_t)kCap) {
@@ -495,13 +495,13 @@ __global__ void __launch_bounds__(2 * BM, (BM == 128 && BN == 128) ? 3 : (BM == 
                         const float dot = acc[i][j][4 * g4 + k] * qis * cis[k];       // powers of two: exact
                         const float sq = fmaf(-2.f, dot, xx) + yy[k];
                         const float d = sqrtf(fmaxf(sq, 0.f));
-                        cost[k] = fmaxf(d, __builtin_sqrtf(1e-8f));                   // = sqrt(max(sq, 1e-8)): geomloss's clamp
+                        cost[k] = cost_of_dist(d);                                    // = sqrt(max(sq, 1e-8)): geomloss's clamp
                         neg[k] = -d;
                         const float ns = xx + yy[k];
                         // (otAspire: ALSO under torch.cdist's matmul formula -- a side beyond 25 rows -- where the reference's own -cdist is the expansion: geomloss's
                         // cost of the entry is derived from this tile (cost_from_neg), and the rule for a cancelling entry is the exact sum for both:
-                        // include/aspire_hip.h, SHARED SENTENCES; round 6, tools/fuzz_parity.py 24 412 planes)
-                        redo[k] = sq < kDirectTau * ns * ns && qrow >= 0 && c_row[m0 + k] >= 0;
+                        // exact_d2.h; tools/fuzz_parity.py 24 412 planes)
+                        redo[k] = expansion_cancels(sq, ns) && qrow >= 0 && c_row[m0 + k] >= 0;
                         if (redo[k]) {
                             const uint32_t slot = atomicAdd(&wl_count, 1u);
                             if (slot < (uint32_t)kCap) {
@@ -515,7 +515,7 @@ __global__ void __launch_bounds__(2 * BM, (BM == 128 && BN == 128) ? 3 : (BM == 
                                     s0 = fmaf(df, df, s0);
                                 }
                                 neg[k] = -sqrtf(s0);
-                                cost[k] = sqrtf(fmaxf(s0, 1e-8f));
+                                cost[k] = cost_of_d2(s0);
                                 redo[k] = false;
                             }
                         }
@@ -538,7 +538,7 @@ __global__ void __launch_bounds__(2 * BM, (BM == 128 && BN == 128) ? 3 : (BM == 
     }
     __syncthreads();
     {
-        // 16 lanes (one DPP row) per flagged entry, 48 coordinates per lane, from the fp32 rows
+        // 16 lanes (one DPP row) per flagged entry, 48 coordinates per lane, from the fp32 rows (exact_d2.h, form B)
         const uint32_t n_redo = min(wl_count, (uint32_t)kCap);
         const int grp = tid >> 4, l16 = tid & 15;
         for (uint32_t e0 = 0; e0 < n_redo; e0 += NT / 16) {
@@ -547,21 +547,8 @@ __global__ void __launch_bounds__(2 * BM, (BM == 128 && BN == 128) ? 3 : (BM == 
             const uint32_t mn = wlist[live ? e : 0];
             const int m = (int)(mn >> 16), n = (int)(mn & 0xFFFFu);
             const int32_t xr = q_row[n], yr = c_row[m];
-            float p0 = 0.f, p1 = 0.f;
-#pragma unroll
-            for (int c = 0; c < 12; c += 2) {
-                const float4 u0 = ldrow4(g.q.rows, xr, 4 * l16 + 64 * c), v0 = ldrow4(g.c.rows, yr, 4 * l16 + 64 * c);
-                const float4 u1 = ldrow4(g.q.rows, xr, 4 * l16 + 64 * c + 64), v1 = ldrow4(g.c.rows, yr, 4 * l16 + 64 * c + 64);
-                const float a0 = u0.x - v0.x, a1 = u0.y - v0.y, a2 = u0.z - v0.z, a3 = u0.w - v0.w;
-                const float b0 = u1.x - v1.x, b1 = u1.y - v1.y, b2 = u1.z - v1.z, b3 = u1.w - v1.w;
-                p0 = fmaf(a3, a3, fmaf(a2, a2, fmaf(a1, a1, fmaf(a0, a0, p0))));
-                p1 = fmaf(b3, b3, fmaf(b2, b2, fmaf(b1, b1, fmaf(b0, b0, p1))));
-            }
-            float part = p0 + p1;
-            part += lane_xor<1>(part);
-            part += lane_xor<2>(part);
-            part += lane_xor<4>(part);
-            part += lane_xor<8>(part);
+            const float part = row16_d2([rows = g.q.rows, xr, l16](int d) { return ldrow4(rows, xr, 4 * l16 + d); },
+                                        [rows = g.c.rows, yr, l16](int d) { return ldrow4(rows, yr, 4 * l16 + d); });
             if (live && l16 == 0) {
                 const int32_t cdi = c_di[m], qdi = q_di[n];
                 if constexpr (L2MAX) {
@@ -571,7 +558,7 @@ __global__ void __launch_bounds__(2 * BM, (BM == 128 && BN == 128) ? 3 : (BM == 
                     const long long qo = ((long long)(qt * g.dpt_q + (qdi & 255)) * g.ncand) * g.E + (long long)((qdi >> 8) & 255) * g.ld;
                     const long long co = (long long)(ct * g.dpt_c + (cdi & 255)) * g.E + ((cdi >> 8) & 255);
                     g.neg[qo + co] = negd;
-                    if (put_cost) g.cost[qo + co] = sqrtf(fmaxf(part, 1e-8f));
+                    if (put_cost) g.cost[qo + co] = cost_of_d2(part);
                 }
             }
         }

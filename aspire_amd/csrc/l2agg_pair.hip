@@ -37,6 +37,7 @@
 #include "common.h"
 #include "batch_host.h"
 #include "pair_fwd.h"
+#include "exact_d2.h"
 
 namespace aspire {
 namespace {
@@ -48,14 +49,8 @@ struct L2aggArgs : PairArgs {
 // sum_d (x_d - y_d)^2 over the 768 coordinates (rare path: a candidate row that (nearly) equals a query row)
 __device__ __noinline__ float exact_d2(const float* __restrict__ x, const float* __restrict__ y) {
     float s0 = 0.f, s1 = 0.f;
-#pragma unroll 1
-    for (int k = 0; k < kD; k += 8) {
-        const f32x4 a = ld4(x + k), b = ld4(y + k), c = ld4(x + k + 4), d = ld4(y + k + 4);
-        const float e0 = a.x - b.x, e1 = a.y - b.y, e2 = a.z - b.z, e3 = a.w - b.w;
-        const float f0 = c.x - d.x, f1 = c.y - d.y, f2 = c.z - d.z, f3 = c.w - d.w;
-        s0 = fmaf(e3, e3, fmaf(e2, e2, fmaf(e1, e1, fmaf(e0, e0, s0))));
-        s1 = fmaf(f3, f3, fmaf(f2, f2, fmaf(f1, f1, fmaf(f0, f0, s1))));
-    }
+#pragma unroll 1           // exact_d2.h's form C, rolled: lane_d2 leaves the unrolling to the compiler, and this function's registers count in the kernel's
+    for (int k = 0; k < kD; k += 8) d2_step2(ld4(x + k), ld4(y + k), ld4(x + k + 4), ld4(y + k + 4), s0, s1);
     return s0 + s1;
 }
 
@@ -118,9 +113,9 @@ __global__ void __launch_bounds__(256) l2agg_pair_kernel(L2aggArgs a, int64_t P)
                 valid[v] = entry_valid(w, c0, v, vb);
                 const float ns = qn + cn[v];
                 float d2 = fmaf(-2.0f, dot[v], ns);
-                if (valid[v] && d2 < 1e-4f * ns * ns)
+                if (valid[v] && expansion_cancels(d2, ns))       // (the rule: exact_d2.h)
                     d2 = exact_d2(qdoc + (int64_t)(q0 + r) * kD, cdoc + (int64_t)(c0 + 4 * g + v) * kD);
-                s[v] = -sqrtf(fmaxf(d2, 0.0f));
+                s[v] = neg_of_expansion(d2);
             }
             if constexpr (AGG == ASPIRE_AGG_TOP2) {
 #pragma unroll

@@ -20,6 +20,7 @@
 #include "tuning.h"
 #include "score_types.h"
 #include "score_device.h"
+#include "exact_d2.h"
 
 namespace aspire {
 namespace {
@@ -100,7 +101,7 @@ __device__ __forceinline__ void load_pair(PairState<T>& s, const PairWs<T>& ws, 
             const int64_t o = slot * (64 * T * T) + (ta * 8 + li) * (8 * T) + tb * 8 + lj;
             s.neg[ta][tb] = ws.neg[o];
             // (the matrix-pipe cost tiles store -cdist only: sqrt(max(sq, 1e-8)) = max(sqrt(max(sq, 0)), sqrt(1e-8)) bit for bit)
-            s.cost[ta][tb] = cost_from_neg ? fmaxf(-s.neg[ta][tb], __builtin_sqrtf(1e-8f)) : ws.cost[o];
+            s.cost[ta][tb] = cost_from_neg ? cost_of_dist(-s.neg[ta][tb]) : ws.cost[o];
         }
 }
 
@@ -596,26 +597,24 @@ __global__ void __launch_bounds__(256) pair_one_kernel(ScoreArgs a, int64_t n_sl
     const float xx = __shfl(nsum, 4 * li), yy = __shfl(nsum, 32 + 4 * lj);
     const float sq = fmaf(-2.f, dot, xx) + yy, ns = xx + yy;
     PairState<1> st;
-    st.cost[0][0] = sqrtf(fmaxf(sq, 1e-8f));
-    st.neg[0][0] = -sqrtf(fmaxf(sq, 0.f));
-    // (round 6: a cancelling entry is redone from the exact sum whatever formula torch.cdist would pick -- also beyond 25 rows: include/aspire_hip.h, SHARED SENTENCES)
-    unsigned long long todo = __ballot(li < q_len && lj < c_len && sq < 1e-4f * ns * ns);
-    while (todo != 0) {        // rare: the whole wave on one entry, from the rows as they are in memory (a common shift drops out)
+    st.cost[0][0] = cost_of_d2(sq);
+    st.neg[0][0] = neg_of_expansion(sq);
+    unsigned long long todo = __ballot(li < q_len && lj < c_len && expansion_cancels(sq, ns));       // (the rule and the exact sum: exact_d2.h)
+    while (todo != 0) {        // rare: the whole wave on one entry (form A), from the rows as they are in memory (a common shift drops out)
         const int o = (int)__builtin_ctzll(todo);
         todo &= todo - 1;
         int oi, oj;
         lane_ij<1>(o, oi, oj);
-        float part = 0.f;
+        float4 u[3], v[3];
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
-            const float4 u = ld4(qdoc + (size_t)oi * kD + 4 * lane + 256 * t), v = ld4(cdoc + (size_t)oj * kD + 4 * lane + 256 * t);
-            const float d0 = u.x - v.x, d1 = u.y - v.y, d2 = u.z - v.z, d3 = u.w - v.w;
-            part = fmaf(d3, d3, fmaf(d2, d2, fmaf(d1, d1, fmaf(d0, d0, part))));
+            u[t] = ld4(qdoc + (size_t)oi * kD + 4 * lane + 256 * t);
+            v[t] = ld4(cdoc + (size_t)oj * kD + 4 * lane + 256 * t);
         }
-        const float tot = wave_sum(part);
+        const float tot = wave_sum(wave_d2_part(u, v));
         if (lane == o) {
             st.neg[0][0] = -sqrtf(tot);
-            st.cost[0][0] = sqrtf(fmaxf(tot, 1e-8f));
+            st.cost[0][0] = cost_of_d2(tot);
         }
     }
     const float diam = a.diameter == nullptr ? fmaxf(sqrtf(diam2), kMinDiameter) : group_diameter_of(a, ix);
@@ -790,7 +789,7 @@ __global__ void __launch_bounds__(256) sinkhorn_block_kernel(ScoreArgs a, PairWs
 #pragma unroll
         for (int x = 0; x < R; ++x)
 #pragma unroll
-            for (int y = 0; y < R; ++y) cost[x][y] = (rv[x] && cv[y]) ? fmaxf(-cost[x][y], __builtin_sqrtf(1e-8f)) : 0.f;
+            for (int y = 0; y < R; ++y) cost[x][y] = (rv[x] && cv[y]) ? cost_of_dist(-cost[x][y]) : 0.f;
     } else {
         load_block(ws.cost, cost);
     }

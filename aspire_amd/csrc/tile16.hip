@@ -21,6 +21,7 @@
 #include "common.h"
 #include "score_device.h"
 #include "score_types.h"
+#include "exact_d2.h"
 #include "tuning.h"
 
 namespace aspire {
@@ -294,7 +295,7 @@ __global__ void __launch_bounds__(256, 2) pair_tile16_kernel(ScoreArgs a, PairWs
         __builtin_amdgcn_wave_barrier();
 
         // ---- the pair's entries (i = 8 s + 4 iq + r, j = 8 hp + 4 jq + t) ---------------------------------------------
-        // (round 6: a cancelling entry is redone from the exact sum whatever formula torch.cdist would pick -- also beyond 25 rows: include/aspire_hip.h, SHARED SENTENCES)
+        // (the rule and the exact sum: exact_d2.h)
         const int j = crow0 + 8 * hp + 4 * mjq + mt;
         bool redo[2][4];
         float negv[2][4];
@@ -306,65 +307,32 @@ __global__ void __launch_bounds__(256, 2) pair_tile16_kernel(ScoreArgs a, PairWs
                 const float dot = macc[s][0][r] + macc[s][1][r];
                 const float sq = fmaf(-2.f, dot, xx[s][r]) + yy;
                 const float ns = xx[s][r] + yy;
-                redo[s][r] = my_c_real && i < q_len && j < c_len && sq < 1e-4f * ns * ns;
-                negv[s][r] = -sqrtf(fmaxf(sq, 0.f));
+                redo[s][r] = my_c_real && i < q_len && j < c_len && expansion_cancels(sq, ns);
+                negv[s][r] = neg_of_expansion(sq);
                 if constexpr (!L2MAX)
-                    if (my_c_real && (!REC || (i < LDW && j < LDW))) ws.cost[slot * EW + i * LDW + j] = sqrtf(fmaxf(sq, 1e-8f));
+                    if (my_c_real && (!REC || (i < LDW && j < LDW))) ws.cost[slot * EW + i * LDW + j] = cost_of_d2(sq);
             }
         if constexpr (!L2MAX)
             if (my_c_real && own_diam && lp == 0 && hp == 0 && qrow0 == 0 && crow0 == 0) ws.diam2[slot] = diam2;
-        // direct-formula redo, the whole wave on one entry (12 coordinates per lane), four entries per memory round trip
+        // direct-formula redo, the whole wave on one entry, four entries per memory round trip (exact_d2.h, form A)
 #pragma unroll
         for (int s = 0; s < 2; ++s)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                unsigned long long wm = __ballot(redo[s][r]);
-                while (wm != 0) {
-                    int owner[4];
-                    float4 u[4][3], v[4][3];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        owner[e] = wm != 0 ? (int)__builtin_ctzll(wm) : -1;
-                        wm = wm != 0 ? wm & (wm - 1) : 0;
-                    }
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {            // all 24 loads go out before the first is consumed
-                        const int o = owner[e] >= 0 ? owner[e] : owner[0];
-                        const int ob = o >> 2, oi = qrow0 + 8 * s + 4 * ((ob >> 1) & 1) + r;
-                        const int oj = (REC ? __builtin_amdgcn_readlane(crow0, o) : 0) + 8 * ((ob >> 2) & 1) + 4 * (ob & 1) + (o & 3);
-                        const int cs_e = __builtin_amdgcn_readlane(c_start, o);
-                        const float* qrow = qdoc + (size_t)oi * kD + 4 * lane;
-                        const float* crow = a.c.rows + ((size_t)cs_e + oj) * kD + 4 * lane;
-#pragma unroll
-                        for (int t = 0; t < 3; ++t) {
-                            u[e][t] = ld4(qrow + 256 * t);
-                            v[e][t] = ld4(crow + 256 * t);
-                        }
-                    }
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float part = 0.f;
-#pragma unroll
-                        for (int t = 0; t < 3; ++t) {
-                            const float d0 = u[e][t].x - v[e][t].x, d1 = u[e][t].y - v[e][t].y, d2 = u[e][t].z - v[e][t].z, d3 = u[e][t].w - v[e][t].w;
-                            part = fmaf(d3, d3, fmaf(d2, d2, fmaf(d1, d1, fmaf(d0, d0, part))));
-                        }
-                        if (owner[e] >= 0) {
-                            const float tot = wave_sum(part);
-                            const int o = owner[e], ob = o >> 2;
-                            const int oi = 8 * s + 4 * ((ob >> 1) & 1) + r, oj = 8 * ((ob >> 2) & 1) + 4 * (ob & 1) + (o & 3);
-                            (void)oi; (void)oj;
-                            if (lane == o) {
-                                negv[s][r] = -sqrtf(tot);
-                                if constexpr (!L2MAX) {      // geomloss's cost from the same exact sum (this lane wrote the expansion's value above)
-                                    const int i = qrow0 + 8 * s + 4 * miq + r;
-                                    if (!REC || (i < LDW && j < LDW)) ws.cost[slot * EW + i * LDW + j] = sqrtf(fmaxf(tot, 1e-8f));
-                                }
-                            }
-                        }
-                    }
-                }
-            }
+            for (int r = 0; r < 4; ++r)
+                redo_wave4(__ballot(redo[s][r]), lane,
+                           [&](int o) {
+                               const int ob = o >> 2, oi = qrow0 + 8 * s + 4 * ((ob >> 1) & 1) + r;
+                               const int oj = (REC ? __builtin_amdgcn_readlane(crow0, o) : 0) + 8 * ((ob >> 2) & 1) + 4 * (ob & 1) + (o & 3);
+                               const int cs_e = __builtin_amdgcn_readlane(c_start, o);
+                               return RowPair{qdoc + (size_t)oi * kD, a.c.rows + ((size_t)cs_e + oj) * kD};
+                           },
+                           [=, &negv](int, float tot) {      // by value: with j, s, r by reference the !L2MAX forms lose their packed adds
+                               negv[s][r] = -sqrtf(tot);
+                               if constexpr (!L2MAX) {      // geomloss's cost from the same exact sum (this lane wrote the expansion's value above)
+                                   const int i = qrow0 + 8 * s + 4 * miq + r;
+                                   if (!REC || (i < LDW && j < LDW)) ws.cost[slot * EW + i * LDW + j] = cost_of_d2(tot);
+                               }
+                           });
         if constexpr (L2MAX) {
             float m = kNegBig;
 #pragma unroll

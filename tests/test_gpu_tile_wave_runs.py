@@ -1,5 +1,5 @@
 """The 16-row streaming kernels (tile16.hip: pair_tile16_kernel, CROSS / MAPPED / REC, otAspire and max-sim) and the tiled cost kernel
-for documents of <= 8 rows (cost_valu.hip: pair_tile_kernel<2, 1>) with SEVERAL items per wave.  A wave of these kernels is persistent:
+for documents of <= 8 rows (cost_valu.hip: pair_tile_kernel) with SEVERAL items per wave.  A wave of these kernels is persistent:
 `for (item = first; item < n_items; item += n_waves)` with the next item's context fetched one item ahead, accumulators zeroed per
 item, a per-wave stage buffer that doubles as the norm table between items, the hybrid form's `continue` past items the fused kernel
 has scored, and (REC) the roles wide / crow0 / qrow0 changing from item to item.  The launches take min(items bound, 2048) waves, so
