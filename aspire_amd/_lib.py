@@ -73,6 +73,11 @@ class BertGrads(ctypes.Structure):
     _fields_ = [('emb_ln_g', c_void_p), ('emb_ln_b', c_void_p), ('layers', ctypes.POINTER(BertLayerGrads))]
 
 
+class BertDropout(ctypes.Structure):
+    """struct aspire_bert_dropout"""
+    _fields_ = [('p_hidden', ctypes.c_float), ('p_attn', ctypes.c_float), ('seed', ctypes.c_uint64), ('step', ctypes.c_uint32)]
+
+
 class BertExtras(ctypes.Structure):
     """struct aspire_bert_extras"""
     _fields_ = [('pos_ids', c_void_p), ('rel_bias', c_void_p), ('rel_span', c_int32)]
@@ -111,6 +116,13 @@ SIGNATURES = {
                                                      c_size_t, c_void_p, c_size_t, c_void_p]),
     'aspire_bert_layers_backward_f32': (c_int, [ctypes.POINTER(BertWeights), c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_size_t,
                                                 c_void_p, ctypes.POINTER(BertGrads), c_void_p, c_size_t, c_void_p]),
+    'aspire_bert_layers_forward_train_dropout_f32': (c_int, [ctypes.POINTER(BertWeights), c_void_p, c_void_p, c_int64, c_int64, c_void_p,
+                                                             c_void_p, c_size_t, c_void_p, c_size_t, ctypes.POINTER(BertDropout), c_void_p]),
+    'aspire_bert_layers_backward_dropout_f32': (c_int, [ctypes.POINTER(BertWeights), c_void_p, c_int64, c_int64, c_void_p, c_void_p,
+                                                        c_size_t, c_void_p, ctypes.POINTER(BertGrads), c_void_p, c_size_t,
+                                                        ctypes.POINTER(BertDropout), c_void_p]),
+    'aspire_bert_dropout_mask_u8': (c_int, [ctypes.c_uint64, ctypes.c_uint32, c_int32, ctypes.c_float, c_int64, c_int64, c_void_p,
+                                            c_void_p]),
     'aspire_token_mean_pool_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p]),
     'aspire_bert_status': (c_int, [ctypes.POINTER(ctypes.c_int32), c_void_p]),
     'aspire_bert_cls_workspace_bytes': (c_size_t, [ctypes.POINTER(BertWeights), c_int64, c_int64]),

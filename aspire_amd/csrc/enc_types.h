@@ -5,6 +5,7 @@
 // enc_planes.h.
 #pragma once
 #include "common.h"
+#include "dropout_rng.h"
 
 namespace aspire {
 
@@ -124,6 +125,15 @@ int launch_layernorm_backward(const float* x, const float* gamma, float eps, con
                               float* dbeta, int64_t rows, float* partial, hipStream_t st);
 size_t colsum_partial_floats(int64_t rows, int N);
 int launch_colsum(const float* x, int64_t rows, int N, float* out, float* partial, hipStream_t st);
+
+// enc_dropout.hip: the dropout passes of the encoder under training; d names the site and its mask (dropout_rng.h), which every pass
+// forms again from the element's logical index.  No atomics, every output element has one writer; out may be the first operand.
+//   dropout_flat:   out = keep . scale . (a (+ a2)) (+ res), n % 4 == 0 contiguous elements whose logical index is their offset
+//   dropout_probs:  out [rows][ld] = keep . scale . p [rows][ld] with logical index row L + j, j < L; zeros in [L, ld)
+//   dropout_mask:   keep[i] = 1 iff element first + i of the site is kept
+int launch_dropout_flat(const float* a, const float* a2, const float* res, float* out, int64_t n, const DropSite& d, hipStream_t st);
+int launch_dropout_probs(const float* p, float* out, int64_t rows, int L, int ld, const DropSite& d, hipStream_t st);
+int launch_dropout_mask(unsigned char* keep, uint64_t first, int64_t n, const DropSite& d, hipStream_t st);
 
 // enc_pooler.hip: pooled = tanh(cls . w_pool^T + b_pool) on [B, 768] rows (HF BertPooler)
 int launch_pooler(const float* cls, int64_t B, const float* w_pool, const float* b_pool, float* pooled, hipStream_t st);

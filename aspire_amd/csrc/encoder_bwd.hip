@@ -1,6 +1,6 @@
 // A1t: the BERT layer stack under training -- a forward that keeps what the backward needs on a caller-owned tape, and the backward from
-// the gradient of last_hidden_state to every encoder parameter and to the embedding sum (HuggingFace BertModel with both dropout
-// probabilities 0; the table lookup in front of it stays the caller's).  fp32 accuracy throughout.
+// the gradient of last_hidden_state to every encoder parameter and to the embedding sum (HuggingFace BertModel, with its dropout
+// when asked for; the table lookup in front of it stays the caller's).  fp32 accuracy throughout.
 //
 // Forward = the fp32-operand body that inference runs without planes, by the same functions (enc_host.h: linear, attention_gemm,
 // layer_tail): launch_gemm with its bias / residual epilogues, the three-kernel attention (QK^T GEMM, softmax_mask_kernel, PV GEMM) and
@@ -21,6 +21,13 @@
 //                         dQ = dS . K (B_KN); dK = dS^T . Q (TN)
 //   dbqkv = colsum(dqkv); dWqkv = dqkv^T . x (TN); dx = dqkv . Wqkv (B_KN), and ds1 is the residual branch's gradient of the layer below
 // and at the bottom the embedding LayerNorm's backward.  Every gradient buffer is written, none accumulated; no atomics.
+//
+// Dropout (the _dropout_ entry points; dropout_rng.h: the contract; enc_dropout.hip: the passes): s1 = drop(ctx Wo^T + bo) + x and
+// s2 = drop(GELU(u) W2^T + b2) + h as a pass behind a GEMM without its residual epilogue, ctx = drop(P) V with the dropped P in the
+// workspace's dprobs (the tape keeps P), x0 = drop(LN(emb)).  The backward forms each mask again: dz2 = keep . scale . ds2 -> d2 feeds
+// db2 / dW2 / da, dz1 = keep . scale . ds1 -> d1 feeds dbo / dWo / dctx (ds2, ds1 themselves go down the residual), the dropped P is
+// formed again in dprobs for dV, dP = keep . scale . (dctx V^T) in place, and keep . scale . (dy + dy_res) -> d1 stands in front of the
+// embedding LayerNorm's backward.  A probability of 0 (or a NULL struct) launches none of this: the calls without dropout, bit for bit.
 //
 // This file is host only (the tape's and the workspace's carve, the two layer loops, the C entry points); the kernels: enc_bwd.hip (rows),
 // enc_gemm.hip (launch_gemm, launch_gemm_tn), enc_attn.hip (launch_softmax_mask), enc_rows.hip (launch_layernorm).
@@ -139,31 +146,68 @@ GemmArgs grad_weight(const float* dY, const float* X, float* dW, int64_t M, int 
     return g;
 }
 
-int forward_layer(const aspire_bert_weights* w, const Geometry& q, int l, const TapeLayer& t, const int64_t* mask, float* act, float* out,
-                  hipStream_t st) {
+// The dropout of one call (dropout_rng.h).  A probability of 0 switches its sites off: they run exactly the launches of a call without
+// dropout.
+struct Dropout {
+    float p_hidden = 0.f, p_attn = 0.f;
+    uint64_t seed = 0;
+    uint32_t step = 0;
+    bool hidden() const { return p_hidden > 0.f; }
+    bool attn() const { return p_attn > 0.f; }
+    DropSite emb() const { return drop_site(seed, step, 0, p_hidden); }
+    DropSite probs(int l) const { return drop_site(seed, step, 1 + 3 * (uint32_t)l, p_attn); }
+    DropSite proj(int l) const { return drop_site(seed, step, 2 + 3 * (uint32_t)l, p_hidden); }
+    DropSite ffn2(int l) const { return drop_site(seed, step, 3 + 3 * (uint32_t)l, p_hidden); }
+};
+
+int check_probability(float p, const char* name) {
+    ASPIRE_REQUIRE(p >= 0.f && p < 1.f, ASPIRE_ERR_INVALID_ARG, "dropout probability %s = %g outside [0, 1)", name, (double)p);     // (NaN fails too)
+    return ASPIRE_OK;
+}
+int read_dropout(const aspire_bert_dropout* d, Dropout* out) {
+    if (!d) return ASPIRE_OK;
+    if (int rc = check_probability(d->p_hidden, "p_hidden")) return rc;
+    if (int rc = check_probability(d->p_attn, "p_attn")) return rc;
+    *out = Dropout{d->p_hidden, d->p_attn, d->seed, d->step};
+    return ASPIRE_OK;
+}
+
+int forward_layer(const aspire_bert_weights* w, const Geometry& q, int l, const TapeLayer& t, const int64_t* mask, const TrainWorkspace& ws,
+                  float* out, const Dropout& dr, hipStream_t st) {
     const aspire_bert_layer& ly = w->layers[l];
+    float* act = ws.act;
+    const DropSite probs = dr.probs(l), tail[2] = {dr.proj(l), dr.ffn2(l)};
     // 1. qkv = x . Wqkv^T + bqkv
     if (int rc = launch_gemm(linear(t.x, ly.w_qkv, t.qkv, ly.b_qkv, nullptr, q.M, 3 * kD, kD), 1, false, st)) return rc;
     // 2-4. the three-kernel attention; the masked soft-max runs in place: the tape's P
-    if (int rc = attention_gemm(t.qkv, t.probs, t.ctx, mask, q.B, q.L, q.Lp, q.H, q.dh, nullptr, 0, st)) return rc;
+    // (with dropout the tape keeps the undropped P; the dropped copy the P.V product reads goes to the workspace's dprobs, free here)
+    if (int rc = attention_gemm(t.qkv, t.probs, t.ctx, mask, q.B, q.L, q.Lp, q.H, q.dh, nullptr, 0, st, dr.attn() ? &probs : nullptr, ws.dprobs))
+        return rc;
     // 5. s1 = ctx . Wo^T + bo + x; h = LN1(s1)
     // 6. u = h . W1^T + b1 (GELU epilogue off); a = GELU(u); s2 = a . W2^T + b2 + h; out = LN2(s2)
-    return layer_tail(w, ly, t.ctx, t.x, TailSlots{t.s1, t.h, t.u, act, t.s2}, out, q.M, st);
+    return layer_tail(w, ly, t.ctx, t.x, TailSlots{t.s1, t.h, t.u, act, t.s2}, out, q.M, st, dr.hidden() ? tail : nullptr);
 }
 
 // dy (+ dy_res) = the gradient of layer l's output -> ws.d2 (+ ws.d3) = the gradient of its input, the layer's parameter gradients
 int backward_layer(const aspire_bert_weights* w, const Geometry& q, int l, const TapeLayer& t, const aspire_bert_layer_grads& gr,
-                   const float* dy, const float* dy_res, const TrainWorkspace& ws, hipStream_t st) {
+                   const float* dy, const float* dy_res, const TrainWorkspace& ws, const Dropout& dr, hipStream_t st) {
     const aspire_bert_layer& ly = w->layers[l];
     const int64_t M = q.M, L = q.L, B = q.B;
     const int H = q.H, dh = q.dh, Lp = q.Lp, ffn = q.ffn;
     const int batch = (int)(B * H);
     // LN2, FFN2
     if (int rc = launch_layernorm_backward(t.s2, ly.ln2_g, w->ln_eps, dy, dy_res, ws.d1, gr.ln2_g, gr.ln2_b, M, ws.partial, st)) return rc;
-    if (int rc = launch_colsum(ws.d1, M, kD, gr.b_ffn2, ws.partial, st)) return rc;
+    // dropout: the FFN2 branch reads dz2 = keep . scale . ds2 (into d2: dy and dy_res, d2 / d3 below the top layer, are dead by now);
+    // ds2 itself goes down the residual
+    const float* dz2 = ws.d1;
+    if (dr.hidden()) {
+        if (int rc = launch_dropout_flat(ws.d1, nullptr, nullptr, ws.d2, M * kD, dr.ffn2(l), st)) return rc;
+        dz2 = ws.d2;
+    }
+    if (int rc = launch_colsum(dz2, M, kD, gr.b_ffn2, ws.partial, st)) return rc;
     if (int rc = launch_gelu_forward(t.u, ws.act, M * ffn, st)) return rc;
-    if (int rc = launch_gemm_tn(grad_weight(ws.d1, ws.act, gr.w_ffn2, M, kD, ffn), 1, st)) return rc;
-    if (int rc = launch_gemm(grad_input(ws.d1, ly.w_ffn2, ws.big, M, kD, ffn), 1, true, st)) return rc;
+    if (int rc = launch_gemm_tn(grad_weight(dz2, ws.act, gr.w_ffn2, M, kD, ffn), 1, st)) return rc;
+    if (int rc = launch_gemm(grad_input(dz2, ly.w_ffn2, ws.big, M, kD, ffn), 1, true, st)) return rc;
     // GELU, FFN1
     if (int rc = launch_gelu_backward(ws.big, t.u, ws.big, M * ffn, st)) return rc;
     if (int rc = launch_colsum(ws.big, M, ffn, gr.b_ffn1, ws.partial, st)) return rc;
@@ -171,17 +215,30 @@ int backward_layer(const aspire_bert_weights* w, const Geometry& q, int l, const
     if (int rc = launch_gemm(grad_input(ws.big, ly.w_ffn1, ws.d2, M, ffn, kD), 1, true, st)) return rc;
     // LN1 (dh = the FFN branch's gradient + ds2 down the residual), the output projection
     if (int rc = launch_layernorm_backward(t.s1, ly.ln1_g, w->ln_eps, ws.d2, ws.d1, ws.d3, gr.ln1_g, gr.ln1_b, M, ws.partial, st)) return rc;
-    if (int rc = launch_colsum(ws.d3, M, kD, gr.b_o, ws.partial, st)) return rc;
-    if (int rc = launch_gemm_tn(grad_weight(ws.d3, t.ctx, gr.w_o, M, kD, kD), 1, st)) return rc;
-    if (int rc = launch_gemm(grad_input(ws.d3, ly.w_o, ws.d2, M, kD, kD), 1, true, st)) return rc;         // dctx
+    // dropout: the projection reads dz1 = keep . scale . ds1 (into d1: ds2 is dead once LN1's backward has read it); ds1 stays in d3,
+    // the residual branch's gradient for the layer below
+    const float* dz1 = ws.d3;
+    if (dr.hidden()) {
+        if (int rc = launch_dropout_flat(ws.d3, nullptr, nullptr, ws.d1, M * kD, dr.proj(l), st)) return rc;
+        dz1 = ws.d1;
+    }
+    if (int rc = launch_colsum(dz1, M, kD, gr.b_o, ws.partial, st)) return rc;
+    if (int rc = launch_gemm_tn(grad_weight(dz1, t.ctx, gr.w_o, M, kD, kD), 1, st)) return rc;
+    if (int rc = launch_gemm(grad_input(dz1, ly.w_o, ws.d2, M, kD, kD), 1, true, st)) return rc;         // dctx
     // attention, per (document, head); dqkv = [dQ | dK | dV] in qkv's layout
-    const auto P = prob_heads(t.probs, H, L, Lp), dP = prob_heads(ws.dprobs, H, L, Lp), dctx = ctx_heads(ws.d2, L, dh);
+    const auto dP = prob_heads(ws.dprobs, H, L, Lp), dctx = ctx_heads(ws.d2, L, dh);
     const auto Q = qkv_heads(t.qkv, L, dh), K = qkv_heads(t.qkv + kD, L, dh), V = qkv_heads(t.qkv + 2 * kD, L, dh);
     const auto dQ = qkv_heads(ws.dqkv, L, dh), dK = qkv_heads(ws.dqkv + kD, L, dh), dV = qkv_heads(ws.dqkv + 2 * kD, L, dh);
-    // dV_bh [keys, 64] = P_bh^T . dctx_bh
+    // dV_bh [keys, 64] = P_bh^T . dctx_bh; dropout: of the dropped P, formed again in dprobs (free until dP lands there)
+    const DropSite drop_p = dr.probs(l);
+    if (dr.attn())
+        if (int rc = launch_dropout_probs(t.probs, ws.dprobs, B * H * L, (int)L, Lp, drop_p, st)) return rc;
+    const auto P = prob_heads(dr.attn() ? ws.dprobs : t.probs, H, L, Lp);
     if (int rc = launch_gemm_tn(head_gemm(P, dctx, dV, L, dh, L, H), batch, st)) return rc;
-    // dP_bh [queries, keys] = dctx_bh . V_bh^T
+    // dP_bh [queries, keys] = dctx_bh . V_bh^T; dropout: that is the dropped P's gradient, the soft-max's is keep . scale . of it
     if (int rc = launch_gemm(head_gemm(dctx, V, dP, L, L, dh, H), batch, false, st)) return rc;
+    if (dr.attn())
+        if (int rc = launch_dropout_probs(ws.dprobs, ws.dprobs, B * H * L, (int)L, Lp, drop_p, st)) return rc;
     if (int rc = launch_softmax_backward(ws.dprobs, t.probs, B * H * L, (int)L, Lp, 1.0f / sqrtf((float)dh), st)) return rc;
     // dQ_bh = dS_bh . K_bh
     if (int rc = launch_gemm(head_gemm(dP, K, dQ, L, dh, L, H), batch, true, st)) return rc;
@@ -208,10 +265,12 @@ extern "C" size_t aspire_bert_train_workspace_bytes(const aspire_bert_weights* w
     return carve_train(nullptr, geometry(w, B, L)).total;
 }
 
-extern "C" int aspire_bert_layers_forward_train_f32(const aspire_bert_weights* w, const float* emb_sum, const int64_t* attn_mask, int64_t B,
-                                                    int64_t L, float* hidden_out, void* tape, size_t tape_bytes, void* ws, size_t ws_bytes,
-                                                    void* stream) {
+extern "C" int aspire_bert_layers_forward_train_dropout_f32(const aspire_bert_weights* w, const float* emb_sum, const int64_t* attn_mask,
+                                                            int64_t B, int64_t L, float* hidden_out, void* tape, size_t tape_bytes, void* ws,
+                                                            size_t ws_bytes, const aspire_bert_dropout* dropout, void* stream) {
     ASPIRE_REQUIRE(w && emb_sum && attn_mask && hidden_out, ASPIRE_ERR_INVALID_ARG, "null pointer");
+    Dropout dr;
+    if (int rc = read_dropout(dropout, &dr)) return rc;
     if (int rc = check_train_args(w, B, L)) return rc;
     if (B == 0) return ASPIRE_OK;
     const Geometry q = geometry(w, B, L);
@@ -221,16 +280,28 @@ extern "C" int aspire_bert_layers_forward_train_f32(const aspire_bert_weights* w
     const TrainWorkspace tw = carve_train(ws, q);
     ASPIRE_HIP_OK(hipMemcpyAsync(t.emb(), emb_sum, (size_t)q.M * kD * sizeof(float), hipMemcpyDeviceToDevice, st));
     const int n = q.n_layers;
-    if (int rc = launch_layernorm(t.emb(), w->emb_ln_g, w->emb_ln_b, w->ln_eps, n == 0 ? hidden_out : t.layer(0).x, q.M, nullptr, st)) return rc;
+    float* x0 = n == 0 ? hidden_out : t.layer(0).x;
+    if (int rc = launch_layernorm(t.emb(), w->emb_ln_g, w->emb_ln_b, w->ln_eps, x0, q.M, nullptr, st)) return rc;
+    if (dr.hidden())
+        if (int rc = launch_dropout_flat(x0, nullptr, nullptr, x0, q.M * kD, dr.emb(), st)) return rc;
     for (int l = 0; l < n; ++l)
-        if (int rc = forward_layer(w, q, l, t.layer(l), attn_mask, tw.act, l == n - 1 ? hidden_out : t.layer(l + 1).x, st)) return rc;
+        if (int rc = forward_layer(w, q, l, t.layer(l), attn_mask, tw, l == n - 1 ? hidden_out : t.layer(l + 1).x, dr, st)) return rc;
     return ASPIRE_OK;
 }
 
-extern "C" int aspire_bert_layers_backward_f32(const aspire_bert_weights* w, const int64_t* attn_mask, int64_t B, int64_t L,
-                                               const float* grad_hidden, const void* tape, size_t tape_bytes, float* grad_emb_sum,
-                                               const aspire_bert_grads* grads, void* ws, size_t ws_bytes, void* stream) {
+extern "C" int aspire_bert_layers_forward_train_f32(const aspire_bert_weights* w, const float* emb_sum, const int64_t* attn_mask, int64_t B,
+                                                    int64_t L, float* hidden_out, void* tape, size_t tape_bytes, void* ws, size_t ws_bytes,
+                                                    void* stream) {
+    return aspire_bert_layers_forward_train_dropout_f32(w, emb_sum, attn_mask, B, L, hidden_out, tape, tape_bytes, ws, ws_bytes, nullptr, stream);
+}
+
+extern "C" int aspire_bert_layers_backward_dropout_f32(const aspire_bert_weights* w, const int64_t* attn_mask, int64_t B, int64_t L,
+                                                       const float* grad_hidden, const void* tape, size_t tape_bytes, float* grad_emb_sum,
+                                                       const aspire_bert_grads* grads, void* ws, size_t ws_bytes,
+                                                       const aspire_bert_dropout* dropout, void* stream) {
     ASPIRE_REQUIRE(w && attn_mask && grad_hidden && grads, ASPIRE_ERR_INVALID_ARG, "null pointer");
+    Dropout dr;
+    if (int rc = read_dropout(dropout, &dr)) return rc;
     if (int rc = check_train_args(w, B, L)) return rc;
     ASPIRE_REQUIRE(grads->emb_ln_g && grads->emb_ln_b && (w->n_layers == 0 || grads->layers), ASPIRE_ERR_INVALID_ARG,
                    "null pointer in the gradient table");
@@ -243,11 +314,35 @@ extern "C" int aspire_bert_layers_backward_f32(const aspire_bert_weights* w, con
     const TrainWorkspace tw = carve_train(ws, q);
     const float *dy = grad_hidden, *dy_res = nullptr;
     for (int l = q.n_layers - 1; l >= 0; --l) {
-        if (int rc = backward_layer(w, q, l, t.layer(l), grads->layers[l], dy, dy_res, tw, st)) return rc;
+        if (int rc = backward_layer(w, q, l, t.layer(l), grads->layers[l], dy, dy_res, tw, dr, st)) return rc;
         dy = tw.d2;         // the attention branch's gradient of the layer's input ...
         dy_res = tw.d3;     // ... and ds1 down the residual: summed by the LayerNorm backward that reads them
     }
     // the embedding LayerNorm (grad_emb_sum NULL: its input gradient goes to scratch, the parameter gradients are still wanted)
-    return launch_layernorm_backward(t.emb(), w->emb_ln_g, w->ln_eps, dy, dy_res, grad_emb_sum ? grad_emb_sum : tw.d1, grads->emb_ln_g,
+    float* scratch = tw.d1;
+    if (dr.hidden()) {
+        // its output's gradient is keep . scale . (dy + dy_res), into d1; d2 is dead after that pass and takes the scratch's place
+        if (int rc = launch_dropout_flat(dy, dy_res, nullptr, tw.d1, q.M * kD, dr.emb(), st)) return rc;
+        dy = tw.d1; dy_res = nullptr; scratch = tw.d2;
+    }
+    return launch_layernorm_backward(t.emb(), w->emb_ln_g, w->ln_eps, dy, dy_res, grad_emb_sum ? grad_emb_sum : scratch, grads->emb_ln_g,
                                      grads->emb_ln_b, q.M, tw.partial, st);
+}
+
+extern "C" int aspire_bert_layers_backward_f32(const aspire_bert_weights* w, const int64_t* attn_mask, int64_t B, int64_t L,
+                                               const float* grad_hidden, const void* tape, size_t tape_bytes, float* grad_emb_sum,
+                                               const aspire_bert_grads* grads, void* ws, size_t ws_bytes, void* stream) {
+    return aspire_bert_layers_backward_dropout_f32(w, attn_mask, B, L, grad_hidden, tape, tape_bytes, grad_emb_sum, grads, ws, ws_bytes, nullptr,
+                                                   stream);
+}
+
+extern "C" int aspire_bert_dropout_mask_u8(uint64_t seed, uint32_t step, int32_t site, float p, int64_t first, int64_t n,
+                                           unsigned char* keep_out, void* stream) {
+    if (int rc = check_probability(p, "p")) return rc;
+    ASPIRE_REQUIRE(site >= 0 && first >= 0 && n >= 0, ASPIRE_ERR_INVALID_ARG, "negative site, first or n (%d, %lld, %lld)", (int)site,
+                   (long long)first, (long long)n);
+    ASPIRE_REQUIRE(keep_out, ASPIRE_ERR_INVALID_ARG, "null pointer (keep_out)");
+    if (n == 0) return ASPIRE_OK;
+    ASPIRE_REQUIRE(n < ((int64_t)1 << 39), ASPIRE_ERR_UNSUPPORTED, "%lld mask bytes in one call: the grid is 2^31 workgroups of 256", (long long)n);
+    return launch_dropout_mask(keep_out, (uint64_t)first, n, drop_site(seed, step, (uint32_t)site, p), (hipStream_t)stream);
 }

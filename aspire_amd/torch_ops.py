@@ -42,6 +42,9 @@ implementation so that shapes propagate under FakeTensor / torch.compile tracing
     torch.ops.aspire.bert_layers_train(emb_sum, mask, weights, n_heads, ln_eps) -> (hidden [B, L, 768], tape uint8)      A1t
                                          (autograd registered: the gradient with respect to emb_sum and every tensor of weights)
     torch.ops.aspire.bert_layers_backward(grad_hidden, tape, mask, weights, n_heads, ln_eps) -> (grad_emb_sum, grads)    its formula
+    torch.ops.aspire.bert_layers_train_dropout(emb_sum, mask, weights, n_heads, ln_eps, p_hidden, p_attn, seed, step)     A1t with dropout
+    torch.ops.aspire.bert_layers_backward_dropout(grad_hidden, tape, mask, weights, n_heads, ln_eps, p_hidden, p_attn, seed, step)
+    torch.ops.aspire.bert_dropout_mask(seed, step, site, p, first, n) -> uint8 [n]                          a site's keep mask
   resident CSR pools (rows + start + len, struct aspire_repset):
     torch.ops.aspire.l2max_scores_csr / ot_scores_csr(q_rows, q_start, q_len, q_max, c_rows, c_start, c_len, c_max, ...) -> [Q * C]
     torch.ops.aspire.ot_rank_batch(q_rows, q_start, q_len, q_max, c_rows, c_start, c_len, c_max, job_off, max_job, k, ...)
@@ -523,8 +526,8 @@ def _train_workspace(bw, b, l, device):
     return _scratch(lib.aspire_bert_train_workspace_bytes, bw, b, l, device)
 
 
-@torch.library.custom_op('aspire::bert_layers_train', mutates_args=(), device_types='cuda')
-def bert_layers_train(emb_sum: Tensor, mask: Tensor, weights: List[Tensor], n_heads: int, ln_eps: float) -> Tuple[Tensor, Tensor]:
+# drop: a _lib.BertDropout for the _dropout_ entry points, None for the plain ones (the body of both operator pairs)
+def _layers_forward(emb_sum, mask, weights, n_heads, ln_eps, drop=None):
     bw = pack_layer_stack(weights, n_heads, ln_eps)
     emb_sum = emb_sum.to(torch.float32).contiguous()
     b, l, _ = emb_sum.shape
@@ -532,14 +535,15 @@ def bert_layers_train(emb_sum: Tensor, mask: Tensor, weights: List[Tensor], n_he
     out = torch.empty_like(emb_sum)
     tape = _scratch(lib.aspire_bert_tape_bytes, bw, b, l, emb_sum.device)
     ws = _train_workspace(bw, b, l, emb_sum.device)
-    check(lib.aspire_bert_layers_forward_train_f32(ctypes.byref(bw), ops._ptr(emb_sum), ops._ptr(mask), b, l, ops._ptr(out), ops._ptr(tape),
-                                                   tape.numel(), ops._ptr(ws), ws.numel(), ops._stream()))
+    args = (ctypes.byref(bw), ops._ptr(emb_sum), ops._ptr(mask), b, l, ops._ptr(out), ops._ptr(tape), tape.numel(), ops._ptr(ws), ws.numel())
+    if drop is None:
+        check(lib.aspire_bert_layers_forward_train_f32(*args, ops._stream()))
+    else:
+        check(lib.aspire_bert_layers_forward_train_dropout_f32(*args, ctypes.byref(drop), ops._stream()))
     return out, tape
 
 
-@torch.library.custom_op('aspire::bert_layers_backward', mutates_args=(), device_types='cuda')
-def bert_layers_backward(grad_hidden: Tensor, tape: Tensor, mask: Tensor, weights: List[Tensor], n_heads: int,
-                         ln_eps: float) -> Tuple[Tensor, List[Tensor]]:
+def _layers_backward(grad_hidden, tape, mask, weights, n_heads, ln_eps, drop=None):
     bw = pack_layer_stack(weights, n_heads, ln_eps)
     grad_hidden = grad_hidden.to(torch.float32).contiguous()
     b, l, _ = grad_hidden.shape
@@ -549,9 +553,24 @@ def bert_layers_backward(grad_hidden: Tensor, tape: Tensor, mask: Tensor, weight
     layers = fill_layers(_lib.BertLayerGrads, grads[2:])
     bg = _lib.BertGrads(ctypes.c_void_p(grads[0].data_ptr()), ctypes.c_void_p(grads[1].data_ptr()), layers)
     ws = _train_workspace(bw, b, l, grad_hidden.device)
-    check(lib.aspire_bert_layers_backward_f32(ctypes.byref(bw), ops._ptr(mask), b, l, ops._ptr(grad_hidden), ops._ptr(tape), tape.numel(),
-                                              ops._ptr(grad_emb), ctypes.byref(bg), ops._ptr(ws), ws.numel(), ops._stream()))
+    args = (ctypes.byref(bw), ops._ptr(mask), b, l, ops._ptr(grad_hidden), ops._ptr(tape), tape.numel(), ops._ptr(grad_emb), ctypes.byref(bg),
+            ops._ptr(ws), ws.numel())
+    if drop is None:
+        check(lib.aspire_bert_layers_backward_f32(*args, ops._stream()))
+    else:
+        check(lib.aspire_bert_layers_backward_dropout_f32(*args, ctypes.byref(drop), ops._stream()))
     return grad_emb, grads
+
+
+@torch.library.custom_op('aspire::bert_layers_train', mutates_args=(), device_types='cuda')
+def bert_layers_train(emb_sum: Tensor, mask: Tensor, weights: List[Tensor], n_heads: int, ln_eps: float) -> Tuple[Tensor, Tensor]:
+    return _layers_forward(emb_sum, mask, weights, n_heads, ln_eps)
+
+
+@torch.library.custom_op('aspire::bert_layers_backward', mutates_args=(), device_types='cuda')
+def bert_layers_backward(grad_hidden: Tensor, tape: Tensor, mask: Tensor, weights: List[Tensor], n_heads: int,
+                         ln_eps: float) -> Tuple[Tensor, List[Tensor]]:
+    return _layers_backward(grad_hidden, tape, mask, weights, n_heads, ln_eps)
 
 
 @bert_layers_train.register_fake
@@ -589,7 +608,67 @@ def _bert_layers_train_grad(ctx, grad_hidden, grad_tape):
 bert_layers_train.register_autograd(_bert_layers_train_grad, setup_context=_bert_layers_train_setup)
 
 
+# ---- the same with dropout (aspire_bert_layers_forward_train_dropout_f32 / aspire_bert_layers_backward_dropout_f32) ----------------------
+# p_hidden, p_attn: BertConfig's hidden_dropout_prob / attention_probs_dropout_prob; (seed, step): the masks' key (include/aspire_hip.h:
+# the generator, the sites, the keep rule).  seed is taken modulo 2^64 and step modulo 2^32 (an operator's int is signed).  The backward
+# forms the forward's masks again from the same four numbers; no mask is saved.
+def _dropout(p_hidden, p_attn, seed, step):
+    return _lib.BertDropout(p_hidden, p_attn, seed & 0xFFFFFFFFFFFFFFFF, step & 0xFFFFFFFF)
+
+
+@torch.library.custom_op('aspire::bert_layers_train_dropout', mutates_args=(), device_types='cuda')
+def bert_layers_train_dropout(emb_sum: Tensor, mask: Tensor, weights: List[Tensor], n_heads: int, ln_eps: float, p_hidden: float,
+                              p_attn: float, seed: int, step: int) -> Tuple[Tensor, Tensor]:
+    return _layers_forward(emb_sum, mask, weights, n_heads, ln_eps, _dropout(p_hidden, p_attn, seed, step))
+
+
+@torch.library.custom_op('aspire::bert_layers_backward_dropout', mutates_args=(), device_types='cuda')
+def bert_layers_backward_dropout(grad_hidden: Tensor, tape: Tensor, mask: Tensor, weights: List[Tensor], n_heads: int, ln_eps: float,
+                                 p_hidden: float, p_attn: float, seed: int, step: int) -> Tuple[Tensor, List[Tensor]]:
+    return _layers_backward(grad_hidden, tape, mask, weights, n_heads, ln_eps, _dropout(p_hidden, p_attn, seed, step))
+
+
+@bert_layers_train_dropout.register_fake
+def _(emb_sum, mask, weights, n_heads, ln_eps, p_hidden, p_attn, seed, step):
+    return emb_sum.new_empty(emb_sum.shape, dtype=torch.float32), emb_sum.new_empty(_fake_tape_bytes(emb_sum, weights, n_heads, ln_eps),
+                                                                                     dtype=torch.uint8)
+
+
+@bert_layers_backward_dropout.register_fake
+def _(grad_hidden, tape, mask, weights, n_heads, ln_eps, p_hidden, p_attn, seed, step):
+    return grad_hidden.new_empty(grad_hidden.shape, dtype=torch.float32), [t.new_empty(t.shape) for t in weights]
+
+
+def _bert_layers_train_dropout_setup(ctx, inputs, output):
+    emb_sum, mask, weights, ctx.n_heads, ctx.ln_eps, *ctx.dropout = inputs
+    ctx.save_for_backward(output[1], mask, *weights)
+
+
+def _bert_layers_train_dropout_grad(ctx, grad_hidden, grad_tape):
+    tape, mask, *weights = ctx.saved_tensors
+    grad_emb, grads = torch.ops.aspire.bert_layers_backward_dropout(grad_hidden, tape, mask, weights, ctx.n_heads, ctx.ln_eps, *ctx.dropout)
+    return grad_emb, None, grads, None, None, None, None, None, None
+
+
+bert_layers_train_dropout.register_autograd(_bert_layers_train_dropout_grad, setup_context=_bert_layers_train_dropout_setup)
+
+
+# keep bytes (0 / 1) of elements first .. first + n - 1 of one site's mask, by the device function the training kernels use
+@torch.library.custom_op('aspire::bert_dropout_mask', mutates_args=(), device_types=None)
+def bert_dropout_mask(seed: int, step: int, site: int, p: float, first: int, n: int) -> Tensor:
+    keep = torch.empty(max(n, 0), device=ops.require_gpu(), dtype=torch.uint8)
+    if n != 0:
+        check(lib.aspire_bert_dropout_mask_u8(seed & 0xFFFFFFFFFFFFFFFF, step & 0xFFFFFFFF, site, p, first, n, ops._ptr(keep), ops._stream()))
+    return keep
+
+
+@bert_dropout_mask.register_fake
+def _(seed, step, site, p, first, n):
+    return torch.empty(n, device='cuda', dtype=torch.uint8)
+
+
 OPS = ('span_mean_pool', 'span_pool_ranges', 'bert_encoder_forward', 'bert_cls_forward', 'bert_pooler', 'token_mean_pool', 'l2max_scores', 'jointsm_scores', 'ot_sinkhorn_scores', 'topk_desc', 'topk_keys', 'topk_merge',
        'l2max_scores_csr', 'ot_scores_csr', 'ot_rank_batch', 'dense_rank_batch', 'l2agg_pair_scores', 'l2agg_pair_backward',
        'ot_pair_scores', 'ot_pair_backward', 'jointsm_pair_scores', 'jointsm_pair_backward', 'l2sup_pair_scores', 'l2sup_pair_backward',
-       'span_mean_pool_backward', 'cls_l2_pair', 'cls_l2_pair_backward', 'bert_layers_train', 'bert_layers_backward')
+       'span_mean_pool_backward', 'cls_l2_pair', 'cls_l2_pair_backward', 'bert_layers_train', 'bert_layers_backward',
+       'bert_layers_train_dropout', 'bert_layers_backward_dropout', 'bert_dropout_mask')

@@ -8,7 +8,15 @@ embedding sum (word + token-type + position rows: the tables' scatter gradient s
 value weights and biases (autograd splits their gradient back); everything from the embedding LayerNorm to ``last_hidden_state``, and its
 gradient down to every parameter, is the library's.
 
-Dropout is not built: the encoder trains as ``BertModel`` does with ``hidden_dropout_prob = attention_probs_dropout_prob = 0``.
+Dropout is opt-in.  ``HipBertTrainEncoder(bert_model)`` trains as ``BertModel`` does with ``hidden_dropout_prob =
+attention_probs_dropout_prob = 0`` (and says so once when the config asks for more).  ``HipBertTrainEncoder(bert_model, dropout=True)``
+applies the config's two probabilities at HuggingFace's four sites per layer stack, inside the library
+(torch.ops.aspire.bert_layers_train_dropout): the masks are Philox4x32-10 words keyed by ``(seed, step, site, element)``
+(include/aspire_hip.h states the contract), never stored, formed again by the backward.  ``seed`` defaults to ``torch.initial_seed()``;
+``step`` is a uint32 counter that advances once per training forward, so a run is reproduced by its seed alone and resumed through
+``dropout_state()`` / ``set_dropout_state(seed, step)``.  ``eval()`` and ``torch.no_grad()`` run the inference forward: no dropout, and
+the counter does not move.  Not supported: activation checkpointing around this module -- the recomputed forward would draw the next
+step's masks, not the first forward's.
 """
 import warnings
 
@@ -19,7 +27,7 @@ from .encoder import _LAYER_KEYS, require_bert_base
 
 
 class HipBertTrainEncoder(torch.nn.Module):
-    def __init__(self, bert_model):
+    def __init__(self, bert_model, dropout=False, seed=None):
         super().__init__()
         dev = ops.require_gpu()
         cfg = bert_model.config
@@ -27,7 +35,15 @@ class HipBertTrainEncoder(torch.nn.Module):
             raise NotImplementedError(f'{type(bert_model).__name__}: the training encoder is built for BertModel (the position ids and the '
                                       'relative-position bias of aspire_bert_extras have no backward)')
         require_bert_base(cfg, 64, 'HipBertTrainEncoder')
-        if cfg.hidden_dropout_prob > 0 or cfg.attention_probs_dropout_prob > 0:
+        self.p_hidden, self.p_attn = (float(cfg.hidden_dropout_prob), float(cfg.attention_probs_dropout_prob)) if dropout else (0.0, 0.0)
+        for name, p in (('hidden_dropout_prob', self.p_hidden), ('attention_probs_dropout_prob', self.p_attn)):
+            if not 0.0 <= p < 1.0:
+                raise ValueError(f'HipBertTrainEncoder: {name} = {p} outside [0, 1)')
+        self.dropout = bool(dropout)
+        self._seed = (torch.initial_seed() if seed is None else int(seed)) % 2 ** 64
+        self._step = 0
+        if not dropout and (cfg.hidden_dropout_prob > 0 or cfg.attention_probs_dropout_prob > 0):
+            # (the text is pinned by a test; "not built" here reads: not in this instance -- dropout=True applies it)
             warnings.warn(f'HipBertTrainEncoder: dropout is not built -- the model trains as with hidden_dropout_prob = '
                           f'attention_probs_dropout_prob = 0 (the config has {cfg.hidden_dropout_prob} / {cfg.attention_probs_dropout_prob})',
                           UserWarning)
@@ -40,6 +56,13 @@ class HipBertTrainEncoder(torch.nn.Module):
 
     def load_state_dict(self, state_dict, *args, **kwargs):
         return self.bert.load_state_dict(state_dict, *args, **kwargs)
+
+    def dropout_state(self):
+        """(seed, step): the key of the NEXT training forward's masks"""
+        return self._seed, self._step
+
+    def set_dropout_state(self, seed, step):
+        self._seed, self._step = int(seed) % 2 ** 64, int(step) % 2 ** 32
 
     def layer_weights(self):
         """[emb_ln_g, emb_ln_b] + per layer the twelve tensors of struct aspire_bert_layer (pack_weights' order), on the autograd graph of
@@ -77,5 +100,12 @@ class HipBertTrainEncoder(torch.nn.Module):
             raise IndexError(f'{seq_len} tokens: beyond max_position_embeddings={cfg.max_position_embeddings}')
         # BertEmbeddings' order: (word + token type) + position
         emb_sum = (emb.word_embeddings(tok) + emb.token_type_embeddings(typ)) + emb.position_embeddings.weight[:seq_len]
-        hidden, _tape = torch.ops.aspire.bert_layers_train(emb_sum, msk, self.layer_weights(), cfg.num_attention_heads, cfg.layer_norm_eps)
+        if not self.dropout:
+            hidden, _tape = torch.ops.aspire.bert_layers_train(emb_sum, msk, self.layer_weights(), cfg.num_attention_heads, cfg.layer_norm_eps)
+            return hidden
+        seed, step = self._seed, self._step
+        self._step = (step + 1) % 2 ** 32
+        # (an operator's int is a signed 64-bit one: the seed goes through as its two's complement)
+        hidden, _tape = torch.ops.aspire.bert_layers_train_dropout(emb_sum, msk, self.layer_weights(), cfg.num_attention_heads, cfg.layer_norm_eps,
+                                                                   self.p_hidden, self.p_attn, seed - 2 ** 64 if seed >= 2 ** 63 else seed, step)
         return hidden

@@ -286,6 +286,47 @@ int aspire_bert_layers_backward_f32(const aspire_bert_weights* w, const int64_t*
                                     const aspire_bert_grads* grads, void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * A1t with dropout: BertModel.train() with hidden_dropout_prob / attention_probs_dropout_prob > 0.  The two calls above plus a
+ * `dropout` argument; NULL, or a probability of 0, switches the sites of that probability off, and they then run exactly the
+ * launches -- and give exactly the bits -- of the calls above.  Tape and workspace sizes are the same.
+ *
+ * No mask is stored: a mask is a function of (seed, step, site, element) that the forward and the backward each evaluate.
+ *   generator  Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85)
+ *   key        (low word of seed, high word of seed); counter (block low, block high, site, step); block = e >> 2, and element e
+ *              takes output word e & 3; e = the element's flat index in the tensor HuggingFace drops: [B, L, 768] at the hidden
+ *              sites, [B, heads, L, L] for the probabilities (not the tape's padded rows)
+ *   sites      0 after the embedding LayerNorm (p_hidden); layer l: 1 + 3 l the soft-max probabilities (p_attn), 2 + 3 l the
+ *              output projection before the residual (p_hidden), 3 + 3 l the FFN2 output before the residual (p_hidden):
+ *              HuggingFace's call order
+ *   keep rule  keep iff word >= (uint32) floor((double) p * 2^32); kept elements are multiplied by 1.0f / (1.0f - p), dropped ones
+ *              are 0.0f
+ * The backward must be given the forward's struct.  Advance `step` once per training forward; the same (seed, step) gives the
+ * same bits on every run.  A forward run again for the same step (activation checkpointing) must pass that step again: the
+ * library keeps no counter.  p outside [0, 1) or NaN -> ASPIRE_ERR_INVALID_ARG (the value is in aspire_last_error()), checked
+ * with the other arguments before the device is touched.
+ *
+ * aspire_bert_dropout_mask_u8 writes keep_out[i] = 1 if element first + i of `site` is kept, else 0, for i < n, with the device
+ * function the training kernels use.  site < 0, first < 0, n < 0, keep_out NULL, p outside [0, 1) -> ASPIRE_ERR_INVALID_ARG;
+ * n == 0 -> ASPIRE_OK without a launch.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {
+    float    p_hidden;        /* hidden_dropout_prob: sites 0, 2 + 3 l, 3 + 3 l */
+    float    p_attn;          /* attention_probs_dropout_prob: sites 1 + 3 l */
+    uint64_t seed;
+    uint32_t step;
+} aspire_bert_dropout;
+
+int aspire_bert_layers_forward_train_dropout_f32(const aspire_bert_weights* w, const float* emb_sum, const int64_t* attn_mask,
+                                                 int64_t B, int64_t L, float* hidden_out, void* tape, size_t tape_bytes, void* ws,
+                                                 size_t ws_bytes, const aspire_bert_dropout* dropout, void* stream);
+int aspire_bert_layers_backward_dropout_f32(const aspire_bert_weights* w, const int64_t* attn_mask, int64_t B, int64_t L,
+                                            const float* grad_hidden, const void* tape, size_t tape_bytes, float* grad_emb_sum,
+                                            const aspire_bert_grads* grads, void* ws, size_t ws_bytes,
+                                            const aspire_bert_dropout* dropout, void* stream);
+int aspire_bert_dropout_mask_u8(uint64_t seed, uint32_t step, int32_t site, float p, int64_t first, int64_t n,
+                                unsigned char* keep_out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * caching_score's document-level term (src/learning/facetid_models/disent_models.py:305-307, taken when
  * abs_loss_prop > 0): functional.pairwise_distance(query_cls_reps, cand_cls_reps, p=2.0) = ||q - c + eps||_2 with torch's
  * eps = 1e-6 added to every coordinate of the difference.  (The caller negates and scales it.)

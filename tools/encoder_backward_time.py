@@ -1,4 +1,4 @@
-"""One training step of the encoder -- forward + backward of a 12-layer BERT-base (ffn 3072), fp32, dropout 0 -- on this library's
+"""One training step of the encoder -- forward + backward of a 12-layer BERT-base (ffn 3072), fp32, dropout 0 or --dropout P -- on this library's
 kernels next to HuggingFace BertModel under torch autograd on the same card: what a RankLoss caller runs with
 aspire_amd.HipBertTrainEncoder, and what it ran before that class existed.
 
@@ -9,7 +9,10 @@ Both sides share one set of random-init weights, are warmed up, then timed with 
 sides alternating, five windows each; the median and the spread of the per-step times are printed as one JSON line per shape.  The
 parameter gradients are compared first.  Needs a GPU; there is no CPU path.
 
-    python tools/encoder_backward_time.py [--shapes 3x512,10x256] [--layers 12]
+    python tools/encoder_backward_time.py [--shapes 3x512,10x256] [--layers 12] [--dropout P]
+
+--dropout P sets both of the config's probabilities on both sides: ours is HipBertTrainEncoder(model, dropout=True), torch's is
+BertModel.train() with the same config.  The two sides then draw different masks, so the gradients are not compared.
 
 The kernels' own times: the same command under rocprofv3 --kernel-trace --stats with --side ours --windows 1 --window-s 0.02
 (tools/statsum.py sums the CSV by kernel).
@@ -42,15 +45,16 @@ def main():
     ap.add_argument('--windows', type=int, default=5)
     ap.add_argument('--window-s', type=float, default=0.2, help='seconds of steps per timed window (small under a profiler)')
     ap.add_argument('--side', choices=['both', 'ours', 'torch'], default='both')
+    ap.add_argument('--dropout', type=float, default=0.0, help='hidden_dropout_prob = attention_probs_dropout_prob, both sides')
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'needs a GPU'
     from transformers import BertConfig, BertModel
     from aspire_amd import HipBertTrainEncoder
     torch.manual_seed(0)
     cfg = BertConfig(vocab_size=3000, hidden_size=768, num_hidden_layers=a.layers, num_attention_heads=12, intermediate_size=3072,
-                     max_position_embeddings=512, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0)
+                     max_position_embeddings=512, hidden_dropout_prob=a.dropout, attention_probs_dropout_prob=a.dropout)
     hf = BertModel(cfg, add_pooling_layer=False).cuda().train()
-    enc = HipBertTrainEncoder(copy.deepcopy(hf)).train()
+    enc = HipBertTrainEncoder(copy.deepcopy(hf), dropout=a.dropout > 0).train()
     for shape in a.shapes.split(','):
         b, l = (int(x) for x in shape.split('x'))
         g = torch.Generator().manual_seed(b * 1000 + l)
@@ -70,8 +74,8 @@ def main():
             (hf(tok, token_type_ids=typ, attention_mask=mask).last_hidden_state * G).sum().backward()
 
         sides = [s for s in (('ours', ours), ('torch', theirs)) if a.side in ('both', s[0])]
-        res = dict(B=b, L=l, layers=a.layers)
-        if a.side == 'both':
+        res = dict(B=b, L=l, layers=a.layers, dropout=a.dropout)
+        if a.side == 'both' and a.dropout == 0:
             ours()
             theirs()
             dev = 0.0
