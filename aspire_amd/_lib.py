@@ -83,6 +83,12 @@ class BertExtras(ctypes.Structure):
     _fields_ = [('pos_ids', c_void_p), ('rel_bias', c_void_p), ('rel_span', c_int32)]
 
 
+class OptimTensor(ctypes.Structure):
+    """struct aspire_optim_tensor"""
+    _fields_ = [('param', c_void_p), ('grad', c_void_p), ('state1', c_void_p), ('state2', c_void_p), ('n', c_int64),
+                ('step', c_int64), ('lr', c_double)]
+
+
 class AspireHipError(RuntimeError):
     pass
 
@@ -103,6 +109,9 @@ SIGNATURES = {
     'aspire_cls_l2_f32': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_double, c_void_p, c_void_p]),
     'aspire_cls_l2_backward_f32': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_double, c_void_p, c_void_p,
                                            c_void_p, c_void_p]),
+    'aspire_optim_workspace_bytes': (c_size_t, [c_int64]),
+    'aspire_adam_step_f32': (c_int, [ctypes.POINTER(OptimTensor), c_int64, c_double, c_double, c_double, c_void_p, c_size_t, c_void_p]),
+    'aspire_adagrad_step_f32': (c_int, [ctypes.POINTER(OptimTensor), c_int64, c_double, c_double, c_void_p, c_size_t, c_void_p]),
     'aspire_bert_planes_bytes': (c_size_t, [ctypes.POINTER(BertWeights)]),
     'aspire_bert_prepare_planes': (c_int, [ctypes.POINTER(BertWeights), c_void_p, c_size_t, c_void_p]),
     'aspire_bert_workspace_bytes': (c_size_t, [ctypes.POINTER(BertWeights), c_int64, c_int64]),

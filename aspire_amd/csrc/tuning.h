@@ -5,6 +5,12 @@
 
 namespace aspire {
 
+// optim.hip: elements of one work item of the multi-tensor optimizer step.  A 256-lane workgroup takes a chunk as four 16-byte
+// slots per lane and array (16 loads in flight per lane for Adam's four arrays); a multiple of 4, so that a chunk's start keeps its
+// tensor's 16-byte alignment.  A constant, not a switch: tests/test_gpu_optim.py sizes its tensors around it.
+constexpr int kOptimChunk = 4096;
+constexpr int kOptimMaxGrid = 256 * 8;      // workgroups of a step: 8 per CU, grid-striding over the chunk list
+
 struct Tuning {
     int sinkhorn_form = 0;   // ASPIRE_HIP_SINKHORN: 0 by grid size, 1 wave, 3 block, 4 block-norepair, 5 block16, 6 block-dense, 7 block-wide (lanes per pair of the block form)
     int cost_path = 0;       // ASPIRE_HIP_COST_PATH: 0 by shape, 1 mfma (Gram kernel), 2 valu

@@ -2,6 +2,7 @@
 computation happens in libaspire_hip.so.  All tensors given here must already live on the GPU."""
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -748,6 +749,82 @@ def topk_merge_keys(keys, k):
     top_i = torch.empty(qn, k, device=keys.device, dtype=torch.int64)
     check(lib.aspire_topk_merge_keys(_ptr(keys), r, qn, k_in, k, _ptr(top_s), _ptr(top_i), _stream()))
     return top_s, top_i
+
+
+def optim_tensor_check(t, name):
+    """What the optimizer kernels take: a dense, contiguous fp32 tensor on the GPU (a contiguous view at any storage offset is fine)."""
+    if t.is_sparse:
+        raise RuntimeError(f'{name}: sparse tensors are not supported')
+    if not t.is_cuda:
+        raise RuntimeError(f'{name}: need a GPU tensor (there is no CPU fallback)')
+    if t.dtype != torch.float32:
+        raise TypeError(f'{name}: need fp32, got {t.dtype}')
+    if not t.is_contiguous():
+        raise ValueError(f'{name}: need a contiguous tensor')
+    return t
+
+
+OPTIM_TABLE = np.dtype([('param', 'u8'), ('grad', 'u8'), ('state1', 'u8'), ('state2', 'u8'), ('n', 'i8'), ('step', 'i8'), ('lr', 'f8')])
+assert OPTIM_TABLE.itemsize == ctypes.sizeof(_lib.OptimTensor)
+_OPTIM_ENTRY = {'adam': lib.aspire_adam_step_f32, 'adagrad': lib.aspire_adagrad_step_f32}
+_OPTIM_WS = {}      # (device index, stream handle) -> the device table of that stream's steps
+
+
+def optim_launch(rule, table, scalars, dev):
+    """One aspire_adam_step_f32 ('adam', scalars = (beta1, beta2, eps)) / aspire_adagrad_step_f32 ('adagrad', (lr_decay, eps)) call on
+    dev's current stream over `table`, a numpy array of OPTIM_TABLE records (struct aspire_optim_tensor: device addresses, element
+    counts, per-tensor step and lr).  The caller vouches for the addresses: adam_step / adagrad_step build a table from checked
+    tensors, HipAdam / HipAdagrad keep one per set of parameters that have a gradient."""
+    assert table.dtype == OPTIM_TABLE and table.flags.c_contiguous and table.ndim == 1
+    n = len(table)
+    if n == 0:
+        return
+    require_gpu()
+    with torch.cuda.device(dev):
+        handle = torch.cuda.current_stream().cuda_stream
+        key = (dev.index, handle)
+        ws = _OPTIM_WS.get(key)
+        if ws is None or ws.numel() < lib.aspire_optim_workspace_bytes(n):
+            ws = _OPTIM_WS[key] = torch.empty(max(lib.aspire_optim_workspace_bytes(n), 16384), device=dev, dtype=torch.uint8)
+        check(_OPTIM_ENTRY[rule](ctypes.cast(table.ctypes.data, ctypes.POINTER(_lib.OptimTensor)), n, *scalars, ws.data_ptr(), ws.numel(),
+                                 handle))
+
+
+def _optim_step(rule, scalars, params, grads, state1, state2, steps, lrs):
+    n = len(params)
+    assert len(grads) == len(state1) == len(steps) == len(lrs) == n and (state2 is None or len(state2) == n), 'one entry per tensor'
+    if n == 0:
+        return
+    dev = params[0].device
+    for i, (p, g) in enumerate(zip(params, grads)):
+        s1, s2 = state1[i], state2[i] if state2 is not None else None
+        for t, name in ((p, 'param'), (g, 'grad'), (s1, 'state'), (s2, 'state')):
+            if t is not None:
+                optim_tensor_check(t, f'{name} {i}')
+        if not (g.device == dev == s1.device and p.device == dev and g.numel() == p.numel() == s1.numel()
+                and (s2 is None or (s2.device == dev and s2.numel() == p.numel()))):
+            raise ValueError(f'tensor {i}: param, grad and state must have one size and live on one device')
+    table = np.empty(n, dtype=OPTIM_TABLE)
+    table['param'] = [t.data_ptr() for t in params]
+    table['grad'] = [t.data_ptr() for t in grads]
+    table['state1'] = [t.data_ptr() for t in state1]
+    table['state2'] = [t.data_ptr() for t in state2] if state2 is not None else 0
+    table['n'] = [t.numel() for t in params]
+    table['step'] = steps
+    table['lr'] = lrs
+    optim_launch(rule, table, scalars, dev)
+
+
+def adam_step(params, grads, exp_avgs, exp_avg_sqs, steps, lrs, beta1=0.9, beta2=0.999, eps=1e-8):
+    """torch.optim.Adam's update of every listed tensor in one launch (aspire_adam_step_f32), in place, on the current stream:
+    params / grads / exp_avgs / exp_avg_sqs are lists of dense contiguous fp32 GPU tensors on one device (anything else raises, see
+    optim_tensor_check), steps the per-tensor step numbers (>= 1, this update's), lrs the per-tensor learning rates."""
+    _optim_step('adam', (float(beta1), float(beta2), float(eps)), params, grads, exp_avgs, exp_avg_sqs, steps, lrs)
+
+
+def adagrad_step(params, grads, sums, steps, lrs, lr_decay=0.0, eps=1e-10):
+    """torch.optim.Adagrad's update of every listed tensor in one launch (aspire_adagrad_step_f32); arguments as adam_step's."""
+    _optim_step('adagrad', (float(lr_decay), float(eps)), params, grads, sums, None, steps, lrs)
 
 
 def selftest_xlane():

@@ -9,8 +9,9 @@ WordSentAbsAlignBiEnc.forward_rank (disent_models.py:587-660), differentiable do
 The hinge and the sum are torch ops on [B] tensors.  The encoder's own backward is whatever the caller's encoder brings: with
 aspire_amd.HipBertTrainEncoder(bert_model) as the `encoder` argument (an instance takes the reference's batch dict as it stands) the
 twelve layers and the embedding LayerNorm run forward and backward on this project's kernels (encoder_bwd.hip) and only the embedding
-table lookup is torch's; a HuggingFace model called under torch autograd brings torch's.  No dropout, optimizer, batcher or DDP is built
-here.  Not built either: the `sentsup` term of WordSentAbsSupAlignBiEnc, the two L1 regularisers (cd_l1_prop, cd_svalue_l1_prop), double
+table lookup is torch's; a HuggingFace model called under torch autograd brings torch's.  Dropout is that encoder's (dropout=True), the
+parameter update aspire_amd.HipAdam / HipAdagrad, the loop around all three aspire_amd.RankTrainer; no batcher or DDP is built.  Not
+built either: the `sentsup` term of WordSentAbsSupAlignBiEnc, the two L1 regularisers (cd_l1_prop, cd_svalue_l1_prop), double
 backward.
 """
 import torch

@@ -1,0 +1,188 @@
+"""The reference's training loop (``GenericTrainer.__init__`` / ``.train()``, src/learning/trainer.py:100-359) restated over this
+project's pieces: a caller's encoder (``HipBertTrainEncoder`` is the intended one), ``RankLoss.forward_rank`` as the objective and
+``HipAdam`` / ``HipAdagrad`` as the update, plus a checkpoint that resumes a run, which the reference lacks.
+
+    trainer = RankTrainer(HipBertTrainEncoder(bert, dropout=True), model_hparams, train_hparams, model_path, train_batches, dev_batches)
+    trainer.train()
+
+``train_batches(epoch)`` / ``dev_batches()`` return iterables of the reference's ``batch_rank`` dicts (the jsonl batchers stay the
+caller's).  ``train_hparams`` has the reference's keys and rules, quirks included:
+
+  update_rule             'adam' -> HipAdam, 'adagrad' -> HipAdagrad, at ``learning_rate``; anything else raises ValueError
+  train_size, batch_size, num_epochs
+                          num_batches = ceil(train_size / batch_size) (1 when train_size <= batch_size); total_iters = num_epochs *
+                          num_batches -- what the warm-up schedules are told, not a cap: an epoch runs every batch it is given
+  lr_decay_method         'exponential' (ExponentialLR(gamma=decay_lr_by)), 'warmuplin' / 'warmupcosine'
+                          (transformers.get_*_schedule_with_warmup(num_warmup_steps, num_training_steps=total_iters))
+  decay_lr_every          scheduler.step() fires only when iteration > 0 and iteration % decay_lr_every == 0 -- so a warm-up schedule
+                          with decay_lr_every > 1 advances slower than its num_training_steps assumes, as in the reference
+  accumulated_batch_size  absent or <= 0: off.  Otherwise it must exceed batch_size and be a multiple of it (the reference's assertion);
+                          gradients then accumulate in .grad un-averaged, step() + zero_grad() fire when (iteration + 1) %
+                          update_params_every == 0, and a trailing partial group is never applied
+  es_check_every          when iteration % es_check_every == 0, iteration != 0 and early_stop: in eval() under no_grad the loss is summed
+                          over dev_batches(); the score is its negative; an improvement saves model_cur_best.pt
+
+The loss is recorded every 5 iterations (``loss_history`` / ``loss_checked_iters``) and again at a dev check.  ``model_final.pt`` is
+written when train() runs to its end.  Both files hold ``encoder.state_dict()``: HuggingFace's names with ``HipBertTrainEncoder``.
+
+``save_checkpoint(path)`` / ``load_checkpoint(path)`` carry the encoder's, the optimizer's and the scheduler's state dicts, the
+iteration, the epoch and the position within it, the best dev score, the histories and ``encoder.dropout_state()`` where the encoder
+has one; ``train()`` of a trainer that loaded one continues there, skipping the batches the interrupted epoch had consumed (so
+``train_batches(epoch)`` must give an epoch's batches in the same order again).  ``train(max_iterations=n)`` returns after n more
+iterations without writing model_final.pt: the place to checkpoint.  With gradient accumulation a checkpoint can only be taken at an
+update boundary: half-accumulated gradients are not saved.
+
+``loss_fn(batch, encoder) -> scalar`` and ``optimizer`` replace the two GPU pieces, which makes the host logic testable without one.
+"""
+import logging
+import math
+import os
+from collections import defaultdict
+
+import torch
+
+LOG_EVERY = 5       # trainer.py:187
+
+
+class RankTrainer:
+    def __init__(self, encoder, model_hparams, train_hparams, model_path, train_batches, dev_batches=None, early_stop=True,
+                 optimizer=None, loss_fn=None):
+        self.encoder = encoder
+        self.model_path = model_path
+        self.train_batches, self.dev_batches = train_batches, dev_batches
+        self.early_stop = bool(early_stop) and dev_batches is not None
+        self.es_check_every = train_hparams['es_check_every']
+        self.num_train, self.batch_size = train_hparams['train_size'], train_hparams['batch_size']
+        self.num_epochs = train_hparams['num_epochs']
+        self.accumulated_batch_size = train_hparams.get('accumulated_batch_size', 0)
+        self.accumulate_gradients = self.accumulated_batch_size > 0
+        if self.accumulate_gradients:
+            # It should be bigger and an exact multiple of the batch size.
+            assert self.accumulated_batch_size > self.batch_size and self.accumulated_batch_size % self.batch_size == 0
+            self.update_params_every = self.accumulated_batch_size // self.batch_size
+        self.num_batches = int(math.ceil(float(self.num_train) / self.batch_size)) if self.num_train > self.batch_size else 1
+        self.total_iters = self.num_epochs * self.num_batches
+
+        self.update_rule, self.learning_rate = train_hparams['update_rule'], train_hparams['learning_rate']
+        if self.update_rule not in ('adam', 'adagrad'):
+            raise ValueError('Unknown upate rule: {:}'.format(self.update_rule))
+        self.lr_decay_method, self.decay_lr_every = train_hparams['lr_decay_method'], train_hparams['decay_lr_every']
+        if self.lr_decay_method not in ('exponential', 'warmuplin', 'warmupcosine'):
+            raise ValueError('Unknown lr_decay_method: {:}'.format(self.lr_decay_method))
+        if optimizer is None:
+            from .optim import HipAdam, HipAdagrad
+            optimizer = (HipAdam if self.update_rule == 'adam' else HipAdagrad)(encoder.parameters(), lr=self.learning_rate)
+        self.optimizer = optimizer
+        if self.lr_decay_method == 'exponential':
+            self.scheduler = torch.optim.lr_scheduler.ExponentialLR(optimizer=optimizer, gamma=train_hparams['decay_lr_by'])
+        else:
+            import transformers
+            make = (transformers.get_linear_schedule_with_warmup if self.lr_decay_method == 'warmuplin'
+                    else transformers.get_cosine_schedule_with_warmup)
+            self.scheduler = make(optimizer=optimizer, num_warmup_steps=train_hparams['num_warmup_steps'],
+                                  num_training_steps=self.total_iters)
+        if loss_fn is None:
+            from .rank_loss import RankLoss
+            loss_fn = RankLoss(model_hparams).forward_rank
+        self.loss_fn = loss_fn
+
+        self.iteration, self.epoch, self.batch_in_epoch = 0, 0, 0
+        self.best_dev_score, self.best_iter = -math.inf, 0
+        self.loss_history = defaultdict(list)
+        self.loss_checked_iters = []
+        self.dev_score_history, self.dev_checked_iters = [], []
+
+    # ---- the files the reference writes
+    def _save_model(self, suffix):
+        os.makedirs(self.model_path, exist_ok=True)
+        fname = os.path.join(self.model_path, f'model_{suffix}.pt')
+        torch.save(self.encoder.state_dict(), fname)
+        logging.info('Wrote: %s', fname)
+
+    def dev_loss(self):
+        """the loss summed over dev_batches(), in eval() under no_grad (predict_utils.batched_loss); the encoder is left in eval(), as the
+        reference leaves it until the next iteration's train()"""
+        self.encoder.eval()
+        total = 0.0
+        with torch.no_grad():
+            for batch in self.dev_batches():
+                total += float(self.loss_fn(batch, self.encoder))
+        return total
+
+    def _record_loss(self, objective):
+        self.loss_history['loss'].append(float(objective.detach()))
+        self.loss_checked_iters.append(self.iteration)
+
+    def _iterate(self, batch):
+        self.encoder.train()
+        if self.accumulate_gradients:
+            objective = self.loss_fn(batch, self.encoder)
+            objective.backward()
+            if (self.iteration + 1) % self.update_params_every == 0:
+                self.optimizer.step()
+                self.optimizer.zero_grad()
+        else:
+            self.optimizer.zero_grad()
+            objective = self.loss_fn(batch, self.encoder)
+            objective.backward()
+            self.optimizer.step()
+        if self.iteration % LOG_EVERY == 0:
+            self._record_loss(objective)
+        # The decay_lr_every doesnt need to be a multiple of self.log_every
+        if self.iteration > 0 and self.iteration % self.decay_lr_every == 0:
+            self.scheduler.step()
+        if self.iteration % self.es_check_every == 0 and self.iteration != 0 and self.early_stop:
+            self._record_loss(objective)
+            dev_score = -1.0 * self.dev_loss()
+            self.dev_score_history.append(dev_score)
+            self.dev_checked_iters.append(self.iteration)
+            if dev_score > self.best_dev_score:
+                self.best_dev_score, self.best_iter = dev_score, self.iteration
+                self._save_model('cur_best')
+        self.iteration += 1
+
+    def train(self, max_iterations=None):
+        """Run from where the trainer stands (the start, or a loaded checkpoint) to the end of the last epoch and write model_final.pt;
+        with max_iterations, return after that many further iterations instead (nothing is written).  Returns True when training ended."""
+        budget = math.inf if max_iterations is None else int(max_iterations)
+        while self.epoch < self.num_epochs:
+            consumed = self.batch_in_epoch
+            for i, batch in enumerate(self.train_batches(self.epoch)):
+                if i < consumed:
+                    continue
+                if budget <= 0:
+                    return False
+                self._iterate(batch)
+                self.batch_in_epoch = i + 1
+                budget -= 1
+            self.epoch, self.batch_in_epoch = self.epoch + 1, 0
+        self._save_model('final')
+        logging.info('Best model; Iteration %d; Dev loss: %.4f', self.best_iter, self.best_dev_score)
+        return True
+
+    # ---- resume (beyond the reference)
+    def save_checkpoint(self, path):
+        if self.accumulate_gradients and self.iteration % self.update_params_every != 0:
+            raise ValueError(f'iteration {self.iteration} is inside a group of {self.update_params_every} accumulated batches: '
+                             'half-accumulated gradients are not part of a checkpoint')
+        state = {'encoder': self.encoder.state_dict(), 'optimizer': self.optimizer.state_dict(), 'scheduler': self.scheduler.state_dict(),
+                 'iteration': self.iteration, 'epoch': self.epoch, 'batch_in_epoch': self.batch_in_epoch,
+                 'best_dev_score': self.best_dev_score, 'best_iter': self.best_iter,
+                 'loss_history': dict(self.loss_history), 'loss_checked_iters': list(self.loss_checked_iters),
+                 'dev_score_history': list(self.dev_score_history), 'dev_checked_iters': list(self.dev_checked_iters),
+                 'dropout_state': tuple(self.encoder.dropout_state()) if hasattr(self.encoder, 'dropout_state') else None}
+        torch.save(state, path)
+
+    def load_checkpoint(self, path):
+        state = torch.load(path, map_location='cpu', weights_only=True)
+        self.encoder.load_state_dict(state['encoder'])
+        self.optimizer.load_state_dict(state['optimizer'])
+        self.scheduler.load_state_dict(state['scheduler'])
+        self.iteration, self.epoch, self.batch_in_epoch = state['iteration'], state['epoch'], state['batch_in_epoch']
+        self.best_dev_score, self.best_iter = state['best_dev_score'], state['best_iter']
+        self.loss_history = defaultdict(list, {k: list(v) for k, v in state['loss_history'].items()})
+        self.loss_checked_iters = list(state['loss_checked_iters'])
+        self.dev_score_history, self.dev_checked_iters = list(state['dev_score_history']), list(state['dev_checked_iters'])
+        if state['dropout_state'] is not None:
+            self.encoder.set_dropout_state(*state['dropout_state'])
+        self.optimizer.zero_grad()

@@ -327,6 +327,44 @@ int aspire_bert_dropout_mask_u8(uint64_t seed, uint32_t step, int32_t site, floa
                                 unsigned char* keep_out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The trainer's parameter update (src/learning/trainer.py:178-181: optim.Adam / optim.Adagrad at torch's defaults): one launch over
+ * every tensor of a parameter set, torch's single-tensor formulas in fp32 (division and square root correctly rounded), in place.
+ *   tensors[i]   param, grad, state1, state2: n fp32 elements each, on the device, 4-byte aligned (16-byte aligned tensors take
+ *                16-byte accesses); step = this update's number for THIS tensor, >= 1 (torch's state['step'] after its increment: a
+ *                parameter without a gradient at some steps lags behind the others); lr = the tensor's param group's learning rate
+ *   Adam         state1 = exp_avg m, state2 = exp_avg_sq v:
+ *                m += (g - m) (1 - beta1);  v = v beta2 + g g (1 - beta2);  p -= step_size (m / (sqrt(v) / bc2_sqrt + eps))
+ *                step_size = lr / (1 - beta1^step), bc2_sqrt = sqrt(1 - beta2^step), formed in double per tensor, passed as floats
+ *   Adagrad      state1 = sum s, state2 unused (may be NULL):
+ *                s += g g;  p -= clr (g / (sqrt(s) + eps));  clr = lr / (1 + (step - 1) lr_decay)
+ * No weight decay, amsgrad or maximize.  Non-finite gradients propagate as the formulas say.  Every element has one writer, no
+ * atomics, the same bits on every run, and nothing outside [ptr, ptr + n) of a tensor is touched.
+ *   workspace    device memory of at least aspire_optim_workspace_bytes(n_tensors) bytes (a multiple of 16, growing with
+ *                n_tensors), 16-byte aligned: the library copies the table there on `stream` from pinned staging of its own, so
+ *                `tensors` need not outlive the call and the call does not wait for the stream.  The workspace must stay untouched
+ *                until the step has run; two steps in flight on different streams need two workspaces.  Not capturable into a graph.
+ * Errors, all before the device is touched, the offending value in aspire_last_error(): ASPIRE_ERR_INVALID_ARG for n_tensors < 0;
+ * a NULL table with n_tensors > 0; a tensor with n < 0, step < 1, lr negative or not finite, a NULL param / grad / state pointer with
+ * n > 0 or a pointer that is not 4-byte aligned; eps / lr_decay negative or not finite; a beta outside [0, 1); a workspace that is
+ * NULL, too small or not 16-byte aligned.  n_tensors == 0, or every n == 0 -> ASPIRE_OK without a launch.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {
+    float*       param;
+    const float* grad;
+    float*       state1;
+    float*       state2;
+    int64_t      n;
+    int64_t      step;
+    double       lr;
+} aspire_optim_tensor;
+
+size_t aspire_optim_workspace_bytes(int64_t n_tensors);
+int aspire_adam_step_f32(const aspire_optim_tensor* tensors, int64_t n_tensors, double beta1, double beta2, double eps,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int aspire_adagrad_step_f32(const aspire_optim_tensor* tensors, int64_t n_tensors, double lr_decay, double eps, void* workspace,
+                            size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * caching_score's document-level term (src/learning/facetid_models/disent_models.py:305-307, taken when
  * abs_loss_prop > 0): functional.pairwise_distance(query_cls_reps, cand_cls_reps, p=2.0) = ||q - c + eps||_2 with torch's
  * eps = 1e-6 added to every coordinate of the difference.  (The caller negates and scales it.)
