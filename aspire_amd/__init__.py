@@ -10,6 +10,7 @@ from .pair_distances import (AllPairMaskedWasserstein, AllPairMaskedAttention, a
                              allpair_masked_dist_l2topk, allpair_joint_sm_negscore, rep_len_tup)
 from .rank_loss import RankLoss, sent_reps_from_hidden  # noqa: F401
 from .train_encoder import HipBertTrainEncoder  # noqa: F401
+from .cls_train import BiEncTrain, ClsTripletLoss, IctEncTrain, IctLoss, SentEncTrain  # noqa: F401
 from .optim import HipAdam, HipAdagrad  # noqa: F401
 from .trainer import RankTrainer  # noqa: F401
 from .consent import AspireConSent  # noqa: F401

@@ -132,6 +132,13 @@ SIGNATURES = {
                                                         ctypes.POINTER(BertDropout), c_void_p]),
     'aspire_bert_dropout_mask_u8': (c_int, [ctypes.c_uint64, ctypes.c_uint32, c_int32, ctypes.c_float, c_int64, c_int64, c_void_p,
                                             c_void_p]),
+    'aspire_bert_cls_mix_train_f32': (c_int, [ctypes.POINTER(BertWeights), c_int64, c_int64, c_void_p, c_size_t, c_void_p, c_void_p,
+                                              c_void_p, c_void_p, c_void_p]),
+    'aspire_bert_layers_backward_cls_f32': (c_int, [ctypes.POINTER(BertWeights), c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                                    c_void_p, c_void_p, c_size_t, c_void_p, ctypes.POINTER(BertGrads), c_void_p, c_void_p,
+                                                    c_size_t, ctypes.POINTER(BertDropout), c_void_p]),
+    'aspire_inbatch_xent_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    'aspire_inbatch_xent_backward_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'aspire_token_mean_pool_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p]),
     'aspire_bert_status': (c_int, [ctypes.POINTER(ctypes.c_int32), c_void_p]),
     'aspire_bert_cls_workspace_bytes': (c_size_t, [ctypes.POINTER(BertWeights), c_int64, c_int64]),

@@ -135,6 +135,30 @@ int launch_dropout_flat(const float* a, const float* a2, const float* res, float
 int launch_dropout_probs(const float* p, float* out, int64_t rows, int L, int ld, const DropSite& d, hipStream_t st);
 int launch_dropout_mask(unsigned char* keep, uint64_t first, int64_t n, const DropSite& d, hipStream_t st);
 
+// enc_cls_train.hip: the CLS read-out of a training forward, its gradient source, and the in-batch cross-entropy of two towers' CLS
+// rows.  No atomics, every output element has one writer.
+//   ClsStates:       where the n_layers + 1 hidden states of a training forward lie: state l < n_layers at x0 + l * layer_stride bytes
+//                    (the tape's layer inputs), state n_layers at top (hidden_out); [B, L, 768] each
+//   cls_mix_tap:     layer_cls [n_layers + 1, B, 768] (when not NULL) = the states' CLS rows; cls_out [B, 768] = sum_l mix[l] . row_l,
+//                    l ascending (mix NULL: the top state's rows, copied)
+//   cls_inject:      grad[b, 0, :] += (mix ? mix[l] : 1) . grad_cls[b, :] on a [B, L, 768] gradient
+//   cls_grad_mix:    grad_mix[l] = sum_b <grad_cls[b], layer_cls[l, b]>, l < n_states (summed in double, rounded once)
+//   inbatch_xent:    row_lse[i] = logsumexp_j <q_i, c_j>, loss[0] = sum_i (row_lse[i] - <q_i, c_i>); B <= kXentMaxRows rows of 768
+//   inbatch_xent_backward: grad_q[i] = sum_j W_ij c_j, grad_c[j] = sum_i W_ij q_i, W_ij = grad_loss[0] (softmax_j(s_i.)_j - [i == j]),
+//                    the soft-max formed again from the same products (nothing is read from the forward)
+constexpr int kXentMaxRows = 128;
+struct ClsStates {
+    const char* x0;
+    size_t layer_stride;
+    const float* top;
+    int n_layers;
+};
+int launch_cls_mix_tap(const ClsStates& s, int64_t B, int64_t L, const float* mix, float* cls_out, float* layer_cls, hipStream_t st);
+int launch_cls_inject(float* grad, int64_t B, int64_t L, const float* grad_cls, const float* mix, int l, hipStream_t st);
+int launch_cls_grad_mix(const float* grad_cls, const float* layer_cls, int64_t B, int n_states, float* grad_mix, hipStream_t st);
+int launch_inbatch_xent(const float* q, const float* c, int B, float* loss, float* row_lse, hipStream_t st);
+int launch_inbatch_xent_backward(const float* q, const float* c, int B, const float* grad_loss, float* grad_q, float* grad_c, hipStream_t st);
+
 // enc_pooler.hip: pooled = tanh(cls . w_pool^T + b_pool) on [B, 768] rows (HF BertPooler)
 int launch_pooler(const float* cls, int64_t B, const float* w_pool, const float* b_pool, float* pooled, hipStream_t st);
 

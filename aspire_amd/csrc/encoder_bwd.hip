@@ -29,6 +29,12 @@
 // formed again in dprobs for dV, dP = keep . scale . (dctx V^T) in place, and keep . scale . (dy + dy_res) -> d1 stands in front of the
 // embedding LayerNorm's backward.  A probability of 0 (or a NULL struct) launches none of this: the calls without dropout, bit for bit.
 //
+// The CLS read-out (aspire_bert_cls_mix_train_f32, aspire_bert_layers_backward_cls_f32; the bi-encoders' and sentence encoders' models):
+// the CLS rows of the n_layers + 1 hidden states come off the tape's layer inputs and hidden_out, and their [B, 768] gradient is one more
+// source of backward_stack -- mix[l] . grad_cls onto row (b, 0) of state l's gradient: the top gradient formed in d2, below it a B-row
+// update of d3 behind backward_layer(l).  The in-batch cross-entropy of two towers' CLS rows has its entry points here as well; the
+// kernels of both: enc_cls_train.hip.
+//
 // This file is host only (the tape's and the workspace's carve, the two layer loops, the C entry points); the kernels: enc_bwd.hip (rows),
 // enc_gemm.hip (launch_gemm, launch_gemm_tn), enc_attn.hip (launch_softmax_mask), enc_rows.hip (launch_layernorm).
 #include <math.h>
@@ -250,6 +256,83 @@ int backward_layer(const aspire_bert_weights* w, const Geometry& q, int l, const
     return launch_gemm(grad_input(ws.dqkv, ly.w_qkv, ws.d2, M, 3 * kD, kD), 1, true, st);
 }
 
+// The CLS read-out's gradient source (aspire_bert_layers_backward_cls_f32): row (b, 0) of hidden state l's gradient takes
+// mix[l] . grad_cls[b, :] for every l, or with mix NULL the top state's alone, with factor 1
+struct ClsSource {
+    const float *grad_cls, *mix, *layer_cls;
+    float* grad_mix;
+};
+
+// From the gradient of the top hidden state (grad_hidden, and / or the CLS rows of `cls`) to every parameter gradient and the embedding
+// sum's.  cls NULL: the launches of the backward without a read-out source, none more.
+int backward_stack(const aspire_bert_weights* w, const Geometry& q, const Tape& t, const TrainWorkspace& tw, const float* grad_hidden,
+                   const ClsSource* cls, float* grad_emb_sum, const aspire_bert_grads* grads, const Dropout& dr, hipStream_t st) {
+    const float *dy = grad_hidden, *dy_res = nullptr;
+    if (cls) {
+        // the top gradient = grad_hidden (or zeros) + the CLS rows, formed in d2: backward_layer writes d2 only after LN2's backward has
+        // read dy, and the layers below hand their dy over in d2 as well
+        const size_t bytes = (size_t)q.M * kD * sizeof(float);
+        if (grad_hidden)
+            ASPIRE_HIP_OK(hipMemcpyAsync(tw.d2, grad_hidden, bytes, hipMemcpyDeviceToDevice, st));
+        else
+            ASPIRE_HIP_OK(hipMemsetAsync(tw.d2, 0, bytes, st));
+        if (int rc = launch_cls_inject(tw.d2, q.B, q.L, cls->grad_cls, cls->mix, q.n_layers, st)) return rc;
+        dy = tw.d2;
+        if (cls->grad_mix)
+            if (int rc = launch_cls_grad_mix(cls->grad_cls, cls->layer_cls, q.B, q.n_layers + 1, cls->grad_mix, st)) return rc;
+    }
+    for (int l = q.n_layers - 1; l >= 0; --l) {
+        if (int rc = backward_layer(w, q, l, t.layer(l), grads->layers[l], dy, dy_res, tw, dr, st)) return rc;
+        dy = tw.d2;         // the attention branch's gradient of the layer's input ...
+        dy_res = tw.d3;     // ... and ds1 down the residual: summed by the LayerNorm backward that reads them
+        // hidden state l is this layer's input: its CLS rows' share of the mix lands on the residual branch's gradient, before the
+        // LayerNorm backward below (or, for state 0, the backward of site 0's dropout) adds the two branches
+        if (cls && cls->mix)
+            if (int rc = launch_cls_inject(tw.d3, q.B, q.L, cls->grad_cls, cls->mix, l, st)) return rc;
+    }
+    // the embedding LayerNorm (grad_emb_sum NULL: its input gradient goes to scratch, the parameter gradients are still wanted)
+    float* scratch = tw.d1;
+    if (dr.hidden()) {
+        // its output's gradient is keep . scale . (dy + dy_res), into d1; d2 is dead after that pass and takes the scratch's place
+        if (int rc = launch_dropout_flat(dy, dy_res, nullptr, tw.d1, q.M * kD, dr.emb(), st)) return rc;
+        dy = tw.d1; dy_res = nullptr; scratch = tw.d2;
+    }
+    return launch_layernorm_backward(t.emb(), w->emb_ln_g, w->ln_eps, dy, dy_res, grad_emb_sum ? grad_emb_sum : scratch, grads->emb_ln_g,
+                                     grads->emb_ln_b, q.M, tw.partial, st);
+}
+
+// what the backward entry points share behind their own null checks: the dropout, geometry, gradient-table, tape and workspace checks,
+// then the stack
+int backward_entry(const aspire_bert_weights* w, int64_t B, int64_t L, const float* grad_hidden, const ClsSource* cls, const void* tape,
+                   size_t tape_bytes, float* grad_emb_sum, const aspire_bert_grads* grads, void* ws, size_t ws_bytes,
+                   const aspire_bert_dropout* dropout, void* stream) {
+    Dropout dr;
+    if (int rc = read_dropout(dropout, &dr)) return rc;
+    if (int rc = check_train_args(w, B, L)) return rc;
+    ASPIRE_REQUIRE(grads->emb_ln_g && grads->emb_ln_b && (w->n_layers == 0 || grads->layers), ASPIRE_ERR_INVALID_ARG,
+                   "null pointer in the gradient table");
+    if (int rc = check_layer_pointers(grads->layers, w->n_layers, "gradients")) return rc;
+    if (B == 0) return ASPIRE_OK;
+    const Geometry q = geometry(w, B, L);
+    if (int rc = check_train_buffers(q, tape, tape_bytes, ws, ws_bytes)) return rc;
+    return backward_stack(w, q, carve_tape(tape, q), carve_train(ws, q), grad_hidden, cls, grad_emb_sum, grads, dr, (hipStream_t)stream);
+}
+
+// the rows of the in-batch cross-entropy: both calls' checks
+int check_xent_args(bool pointers, int64_t B, int64_t D) {
+    ASPIRE_REQUIRE(B >= 0, ASPIRE_ERR_INVALID_ARG, "negative batch size %lld", (long long)B);
+    ASPIRE_REQUIRE(D == kD, ASPIRE_ERR_UNSUPPORTED, "encoding dim %lld unsupported (kernels are built for 768)", (long long)D);
+    ASPIRE_REQUIRE(B <= kXentMaxRows, ASPIRE_ERR_UNSUPPORTED, "%lld rows in one batch: the in-batch cross-entropy is built for at most %d",
+                   (long long)B, kXentMaxRows);
+    ASPIRE_REQUIRE(pointers, ASPIRE_ERR_INVALID_ARG, "null pointer");
+    return ASPIRE_OK;
+}
+int check_xent_rows(const void* a, const void* b, const void* c = nullptr, const void* d = nullptr) {
+    ASPIRE_REQUIRE((((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 15) == 0, ASPIRE_ERR_INVALID_ARG,
+                   "rows must be 16-byte aligned");
+    return ASPIRE_OK;
+}
+
 }  // namespace
 }  // namespace aspire
 
@@ -300,33 +383,7 @@ extern "C" int aspire_bert_layers_backward_dropout_f32(const aspire_bert_weights
                                                        const aspire_bert_grads* grads, void* ws, size_t ws_bytes,
                                                        const aspire_bert_dropout* dropout, void* stream) {
     ASPIRE_REQUIRE(w && attn_mask && grad_hidden && grads, ASPIRE_ERR_INVALID_ARG, "null pointer");
-    Dropout dr;
-    if (int rc = read_dropout(dropout, &dr)) return rc;
-    if (int rc = check_train_args(w, B, L)) return rc;
-    ASPIRE_REQUIRE(grads->emb_ln_g && grads->emb_ln_b && (w->n_layers == 0 || grads->layers), ASPIRE_ERR_INVALID_ARG,
-                   "null pointer in the gradient table");
-    if (int rc = check_layer_pointers(grads->layers, w->n_layers, "gradients")) return rc;
-    if (B == 0) return ASPIRE_OK;
-    const Geometry q = geometry(w, B, L);
-    if (int rc = check_train_buffers(q, tape, tape_bytes, ws, ws_bytes)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const Tape t = carve_tape(tape, q);
-    const TrainWorkspace tw = carve_train(ws, q);
-    const float *dy = grad_hidden, *dy_res = nullptr;
-    for (int l = q.n_layers - 1; l >= 0; --l) {
-        if (int rc = backward_layer(w, q, l, t.layer(l), grads->layers[l], dy, dy_res, tw, dr, st)) return rc;
-        dy = tw.d2;         // the attention branch's gradient of the layer's input ...
-        dy_res = tw.d3;     // ... and ds1 down the residual: summed by the LayerNorm backward that reads them
-    }
-    // the embedding LayerNorm (grad_emb_sum NULL: its input gradient goes to scratch, the parameter gradients are still wanted)
-    float* scratch = tw.d1;
-    if (dr.hidden()) {
-        // its output's gradient is keep . scale . (dy + dy_res), into d1; d2 is dead after that pass and takes the scratch's place
-        if (int rc = launch_dropout_flat(dy, dy_res, nullptr, tw.d1, q.M * kD, dr.emb(), st)) return rc;
-        dy = tw.d1; dy_res = nullptr; scratch = tw.d2;
-    }
-    return launch_layernorm_backward(t.emb(), w->emb_ln_g, w->ln_eps, dy, dy_res, grad_emb_sum ? grad_emb_sum : scratch, grads->emb_ln_g,
-                                     grads->emb_ln_b, q.M, tw.partial, st);
+    return backward_entry(w, B, L, grad_hidden, nullptr, tape, tape_bytes, grad_emb_sum, grads, ws, ws_bytes, dropout, stream);
 }
 
 extern "C" int aspire_bert_layers_backward_f32(const aspire_bert_weights* w, const int64_t* attn_mask, int64_t B, int64_t L,
@@ -345,4 +402,45 @@ extern "C" int aspire_bert_dropout_mask_u8(uint64_t seed, uint32_t step, int32_t
     if (n == 0) return ASPIRE_OK;
     ASPIRE_REQUIRE(n < ((int64_t)1 << 39), ASPIRE_ERR_UNSUPPORTED, "%lld mask bytes in one call: the grid is 2^31 workgroups of 256", (long long)n);
     return launch_dropout_mask(keep_out, (uint64_t)first, n, drop_site(seed, step, (uint32_t)site, p), (hipStream_t)stream);
+}
+
+extern "C" int aspire_bert_cls_mix_train_f32(const aspire_bert_weights* w, int64_t B, int64_t L, const void* tape, size_t tape_bytes,
+                                             const float* hidden_out, const float* mix, float* cls_out, float* layer_cls, void* stream) {
+    ASPIRE_REQUIRE(w && hidden_out && cls_out, ASPIRE_ERR_INVALID_ARG, "null pointer (w / hidden_out / cls_out)");
+    ASPIRE_REQUIRE(!mix || layer_cls, ASPIRE_ERR_INVALID_ARG, "null pointer (layer_cls with a mix)");
+    if (int rc = check_bert_shape(w, B, L)) return rc;
+    if (B == 0) return ASPIRE_OK;
+    const Geometry q = geometry(w, B, L);
+    const Tape t = carve_tape(tape, q);
+    ASPIRE_REQUIRE(tape && tape_bytes >= t.total, ASPIRE_ERR_INVALID_ARG, "tape too small: need %zu bytes (aspire_bert_tape_bytes)", t.total);
+    const ClsStates s{t.base + t.emb_bytes, t.per_layer, hidden_out, q.n_layers};
+    return launch_cls_mix_tap(s, B, L, mix, cls_out, layer_cls, (hipStream_t)stream);
+}
+
+extern "C" int aspire_bert_layers_backward_cls_f32(const aspire_bert_weights* w, const int64_t* attn_mask, int64_t B, int64_t L,
+                                                   const float* grad_hidden, const float* grad_cls, const float* mix, const float* layer_cls,
+                                                   const void* tape, size_t tape_bytes, float* grad_emb_sum, const aspire_bert_grads* grads,
+                                                   float* grad_mix, void* ws, size_t ws_bytes, const aspire_bert_dropout* dropout,
+                                                   void* stream) {
+    ASPIRE_REQUIRE(w && attn_mask && grads, ASPIRE_ERR_INVALID_ARG, "null pointer");
+    ASPIRE_REQUIRE(grad_hidden || grad_cls, ASPIRE_ERR_INVALID_ARG, "null pointer (grad_hidden and grad_cls: no gradient source)");
+    ASPIRE_REQUIRE(!grad_mix || (layer_cls && mix && grad_cls), ASPIRE_ERR_INVALID_ARG,
+                   "grad_mix needs grad_cls, mix and layer_cls (null pointer)");
+    const ClsSource cls{grad_cls, mix, layer_cls, grad_mix};
+    return backward_entry(w, B, L, grad_hidden, grad_cls ? &cls : nullptr, tape, tape_bytes, grad_emb_sum, grads, ws, ws_bytes, dropout, stream);
+}
+
+extern "C" int aspire_inbatch_xent_f32(const float* q, const float* c, int64_t B, int64_t D, float* loss, float* row_lse, void* stream) {
+    if (int rc = check_xent_args(q && c && loss && row_lse, B, D)) return rc;
+    if (B == 0) return ASPIRE_OK;
+    if (int rc = check_xent_rows(q, c)) return rc;
+    return launch_inbatch_xent(q, c, (int)B, loss, row_lse, (hipStream_t)stream);
+}
+
+extern "C" int aspire_inbatch_xent_backward_f32(const float* q, const float* c, int64_t B, int64_t D, const float* row_lse,
+                                                const float* grad_loss, float* grad_q, float* grad_c, void* stream) {
+    if (int rc = check_xent_args(q && c && row_lse && grad_loss && grad_q && grad_c, B, D)) return rc;
+    if (B == 0) return ASPIRE_OK;
+    if (int rc = check_xent_rows(q, c, grad_q, grad_c)) return rc;
+    return launch_inbatch_xent_backward(q, c, (int)B, grad_loss, grad_q, grad_c, (hipStream_t)stream);
 }

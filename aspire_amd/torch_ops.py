@@ -45,6 +45,14 @@ implementation so that shapes propagate under FakeTensor / torch.compile tracing
     torch.ops.aspire.bert_layers_train_dropout(emb_sum, mask, weights, n_heads, ln_eps, p_hidden, p_attn, seed, step)     A1t with dropout
     torch.ops.aspire.bert_layers_backward_dropout(grad_hidden, tape, mask, weights, n_heads, ln_eps, p_hidden, p_attn, seed, step)
     torch.ops.aspire.bert_dropout_mask(seed, step, site, p, first, n) -> uint8 [n]                          a site's keep mask
+    torch.ops.aspire.bert_layers_train_cls(emb_sum, mask, weights, mix | None, n_heads, ln_eps, p_hidden, p_attn, seed, step)
+                                         -> (cls [B, 768], layer_cls, tape)      disent_models.py:178-205, sentsim_models.py:62-78
+                                         (autograd registered: emb_sum, every tensor of weights and mix, from the gradient of cls)
+    torch.ops.aspire.bert_layers_backward_cls(grad_cls, layer_cls, tape, mask, weights, mix | None, n_heads, ln_eps, p_hidden, p_attn,
+                                         seed, step) -> (grad_emb_sum, grads, grad_mix)                                 its formula
+    torch.ops.aspire.inbatch_xent(q, c) -> (loss [1], row_lse [B])                                 sentsim_models.py:81-126
+                                         (autograd registered: the gradient of loss with respect to q and c)
+    torch.ops.aspire.inbatch_xent_backward(grad_loss, q, c, row_lse) -> (grad_q, grad_c)
   resident CSR pools (rows + start + len, struct aspire_repset):
     torch.ops.aspire.l2max_scores_csr / ot_scores_csr(q_rows, q_start, q_len, q_max, c_rows, c_start, c_len, c_max, ...) -> [Q * C]
     torch.ops.aspire.ot_rank_batch(q_rows, q_start, q_len, q_max, c_rows, c_start, c_len, c_max, job_off, max_job, k, ...)
@@ -653,6 +661,134 @@ def _bert_layers_train_dropout_grad(ctx, grad_hidden, grad_tape):
 bert_layers_train_dropout.register_autograd(_bert_layers_train_dropout_grad, setup_context=_bert_layers_train_dropout_setup)
 
 
+# ---- the CLS read-out under autograd (aspire_bert_cls_mix_train_f32 / aspire_bert_layers_backward_cls_f32) --------------------------------
+# The training forward with the CLS rows of the (optionally mix-weighted) hidden states as its differentiable output: MySPECTER's
+# doc_reps_bert (disent_models.py:178-205) and SentBERTWrapper.sent_reps_bert (sentsim_models.py:62-78).  mix: post-soft-max weights
+# [n_layers + 1] on the device, or None (the last hidden state's rows); both probabilities 0: the launches without dropout.  layer_cls
+# [n_layers + 1, B, 768] (with a mix; else [0]) and the tape are what the backward reads; neither is differentiable.  No [B, L, 768]
+# gradient crosses the operator: the backward forms the top gradient in its workspace.
+def _drop_or_none(p_hidden, p_attn, seed, step):
+    return _dropout(p_hidden, p_attn, seed, step) if (p_hidden > 0 or p_attn > 0) else None
+
+
+@torch.library.custom_op('aspire::bert_layers_train_cls', mutates_args=(), device_types='cuda')
+def bert_layers_train_cls(emb_sum: Tensor, mask: Tensor, weights: List[Tensor], mix: Optional[Tensor], n_heads: int, ln_eps: float,
+                          p_hidden: float, p_attn: float, seed: int, step: int) -> Tuple[Tensor, Tensor, Tensor]:
+    hidden, tape = _layers_forward(emb_sum, mask, weights, n_heads, ln_eps, _drop_or_none(p_hidden, p_attn, seed, step))
+    bw = pack_layer_stack(weights, n_heads, ln_eps)
+    b, l, d = hidden.shape
+    cls = hidden.new_empty(b, d)
+    layer_cls = hidden.new_empty(((len(weights) - 2) // 12 + 1, b, d) if mix is not None else (0,))
+    if mix is not None:
+        mix = mix.to(torch.float32).contiguous()
+    check(lib.aspire_bert_cls_mix_train_f32(ctypes.byref(bw), b, l, ops._ptr(tape), tape.numel(), ops._ptr(hidden), ops._ptr(mix),
+                                            ops._ptr(cls), ops._ptr(layer_cls if mix is not None else None), ops._stream()))
+    return cls, layer_cls, tape
+
+
+@torch.library.custom_op('aspire::bert_layers_backward_cls', mutates_args=(), device_types='cuda')
+def bert_layers_backward_cls(grad_cls: Tensor, layer_cls: Tensor, tape: Tensor, mask: Tensor, weights: List[Tensor], mix: Optional[Tensor],
+                             n_heads: int, ln_eps: float, p_hidden: float, p_attn: float, seed: int,
+                             step: int) -> Tuple[Tensor, List[Tensor], Tensor]:
+    bw = pack_layer_stack(weights, n_heads, ln_eps)
+    grad_cls = grad_cls.to(torch.float32).contiguous()
+    mask, = _int64(mask)
+    b, l = mask.shape
+    grads = [torch.empty_like(t, memory_format=torch.contiguous_format) for t in weights]
+    grad_emb = grad_cls.new_empty(b, l, grad_cls.shape[1])
+    grad_mix = grad_cls.new_empty(mix.numel() if mix is not None else 0)
+    if mix is not None:
+        mix = mix.to(torch.float32).contiguous()
+    layers = fill_layers(_lib.BertLayerGrads, grads[2:])
+    bg = _lib.BertGrads(ctypes.c_void_p(grads[0].data_ptr()), ctypes.c_void_p(grads[1].data_ptr()), layers)
+    ws = _train_workspace(bw, b, l, grad_cls.device)
+    drop = _drop_or_none(p_hidden, p_attn, seed, step)
+    with_mix = mix is not None
+    check(lib.aspire_bert_layers_backward_cls_f32(ctypes.byref(bw), ops._ptr(mask), b, l, None, ops._ptr(grad_cls), ops._ptr(mix),
+                                                  ops._ptr(layer_cls.contiguous() if with_mix else None), ops._ptr(tape), tape.numel(),
+                                                  ops._ptr(grad_emb), ctypes.byref(bg), ops._ptr(grad_mix if with_mix else None),
+                                                  ops._ptr(ws), ws.numel(), ctypes.byref(drop) if drop is not None else None,
+                                                  ops._stream()))
+    return grad_emb, grads, grad_mix
+
+
+@bert_layers_train_cls.register_fake
+def _(emb_sum, mask, weights, mix, n_heads, ln_eps, p_hidden, p_attn, seed, step):
+    b, _, d = emb_sum.shape
+    return (emb_sum.new_empty((b, d), dtype=torch.float32),
+            emb_sum.new_empty(((len(weights) - 2) // 12 + 1, b, d) if mix is not None else (0,), dtype=torch.float32),
+            emb_sum.new_empty(_fake_tape_bytes(emb_sum, weights, n_heads, ln_eps), dtype=torch.uint8))
+
+
+@bert_layers_backward_cls.register_fake
+def _(grad_cls, layer_cls, tape, mask, weights, mix, n_heads, ln_eps, p_hidden, p_attn, seed, step):
+    b, l = mask.shape
+    return (grad_cls.new_empty((b, l, grad_cls.shape[1]), dtype=torch.float32), [t.new_empty(t.shape) for t in weights],
+            grad_cls.new_empty(mix.numel() if mix is not None else 0, dtype=torch.float32))
+
+
+def _bert_layers_train_cls_setup(ctx, inputs, output):
+    emb_sum, mask, weights, mix, ctx.n_heads, ctx.ln_eps, *ctx.dropout = inputs
+    ctx.with_mix = mix is not None
+    ctx.save_for_backward(output[1], output[2], mask, *([mix] if ctx.with_mix else []), *weights)
+    ctx.mark_non_differentiable(output[1])          # (the tape's bytes are no floating-point tensor: not differentiable as they are)
+
+
+def _bert_layers_train_cls_grad(ctx, grad_cls, grad_layer_cls, grad_tape):
+    layer_cls, tape, mask, *rest = ctx.saved_tensors
+    mix, weights = (rest[0], rest[1:]) if ctx.with_mix else (None, rest)
+    grad_emb, grads, grad_mix = torch.ops.aspire.bert_layers_backward_cls(grad_cls, layer_cls, tape, mask, weights, mix, ctx.n_heads,
+                                                                          ctx.ln_eps, *ctx.dropout)
+    return grad_emb, None, grads, grad_mix if ctx.with_mix else None, None, None, None, None, None, None
+
+
+bert_layers_train_cls.register_autograd(_bert_layers_train_cls_grad, setup_context=_bert_layers_train_cls_setup)
+
+
+# ---- the in-batch cross-entropy (aspire_inbatch_xent_f32 / aspire_inbatch_xent_backward_f32) -----------------------------------------------
+# ICTBERTWrapper.forward_rank's loss (sentsim_models.py:81-126) over two towers' CLS rows q, c [B, 768], B <= 128: loss [1] and the
+# rows' logsumexp [B], which the backward reads.
+@torch.library.custom_op('aspire::inbatch_xent', mutates_args=(), device_types='cuda')
+def inbatch_xent(q: Tensor, c: Tensor) -> Tuple[Tensor, Tensor]:
+    q, c = q.to(torch.float32).contiguous(), c.to(torch.float32).contiguous()
+    assert q.dim() == 2 and q.shape == c.shape, 'q and c must be [B, 768] alike'
+    loss, row_lse = q.new_zeros(1), q.new_empty(q.shape[0])
+    check(lib.aspire_inbatch_xent_f32(ops._ptr(q), ops._ptr(c), q.shape[0], q.shape[1], ops._ptr(loss), ops._ptr(row_lse), ops._stream()))
+    return loss, row_lse
+
+
+@torch.library.custom_op('aspire::inbatch_xent_backward', mutates_args=(), device_types='cuda')
+def inbatch_xent_backward(grad_loss: Tensor, q: Tensor, c: Tensor, row_lse: Tensor) -> Tuple[Tensor, Tensor]:
+    q, c = q.to(torch.float32).contiguous(), c.to(torch.float32).contiguous()
+    grad_loss = grad_loss.to(torch.float32).reshape(1).contiguous()
+    grad_q, grad_c = torch.empty_like(q), torch.empty_like(c)
+    check(lib.aspire_inbatch_xent_backward_f32(ops._ptr(q), ops._ptr(c), q.shape[0], q.shape[1], ops._ptr(row_lse.contiguous()),
+                                               ops._ptr(grad_loss), ops._ptr(grad_q), ops._ptr(grad_c), ops._stream()))
+    return grad_q, grad_c
+
+
+@inbatch_xent.register_fake
+def _(q, c):
+    return q.new_empty(1, dtype=torch.float32), q.new_empty(q.shape[0], dtype=torch.float32)
+
+
+@inbatch_xent_backward.register_fake
+def _(grad_loss, q, c, row_lse):
+    return q.new_empty(q.shape, dtype=torch.float32), c.new_empty(c.shape, dtype=torch.float32)
+
+
+def _inbatch_xent_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs, output[1])
+    ctx.mark_non_differentiable(output[1])
+
+
+def _inbatch_xent_grad(ctx, grad_loss, grad_lse):
+    return torch.ops.aspire.inbatch_xent_backward(grad_loss, *ctx.saved_tensors)
+
+
+inbatch_xent.register_autograd(_inbatch_xent_grad, setup_context=_inbatch_xent_setup)
+
+
 # keep bytes (0 / 1) of elements first .. first + n - 1 of one site's mask, by the device function the training kernels use
 @torch.library.custom_op('aspire::bert_dropout_mask', mutates_args=(), device_types=None)
 def bert_dropout_mask(seed: int, step: int, site: int, p: float, first: int, n: int) -> Tensor:
@@ -671,4 +807,5 @@ OPS = ('span_mean_pool', 'span_pool_ranges', 'bert_encoder_forward', 'bert_cls_f
        'l2max_scores_csr', 'ot_scores_csr', 'ot_rank_batch', 'dense_rank_batch', 'l2agg_pair_scores', 'l2agg_pair_backward',
        'ot_pair_scores', 'ot_pair_backward', 'jointsm_pair_scores', 'jointsm_pair_backward', 'l2sup_pair_scores', 'l2sup_pair_backward',
        'span_mean_pool_backward', 'cls_l2_pair', 'cls_l2_pair_backward', 'bert_layers_train', 'bert_layers_backward',
-       'bert_layers_train_dropout', 'bert_layers_backward_dropout', 'bert_dropout_mask')
+       'bert_layers_train_dropout', 'bert_layers_backward_dropout', 'bert_dropout_mask', 'bert_layers_train_cls', 'bert_layers_backward_cls',
+       'inbatch_xent', 'inbatch_xent_backward')

@@ -8,6 +8,10 @@ embedding sum (word + token-type + position rows: the tables' scatter gradient s
 value weights and biases (autograd splits their gradient back); everything from the embedding LayerNorm to ``last_hidden_state``, and its
 gradient down to every parameter, is the library's.
 
+``forward_cls(batch, mix=None)`` is the read-out of the models whose reps are CLS rows (aspire_amd/cls_train.py): the same plumbing, then
+torch.ops.aspire.bert_layers_train_cls -- the CLS rows of last_hidden_state, or of a mix of all hidden states, whose backward starts
+from the [B, 768] gradient (no [B, L, 768] gradient is built in torch).
+
 Dropout is opt-in.  ``HipBertTrainEncoder(bert_model)`` trains as ``BertModel`` does with ``hidden_dropout_prob =
 attention_probs_dropout_prob = 0`` (and says so once when the config asks for more).  ``HipBertTrainEncoder(bert_model, dropout=True)``
 applies the config's two probabilities at HuggingFace's four sites per layer stack, inside the library
@@ -76,6 +80,46 @@ class HipBertTrainEncoder(torch.nn.Module):
             named = dict(layer.named_parameters())
             w += [named[k] for k in _LAYER_KEYS]
         return w
+
+    def forward_cls(self, batch, mix=None):
+        """The CLS read-out of the bi-encoders and the sentence encoders (MySPECTER.doc_reps_bert, SentBERTWrapper.sent_reps_bert):
+        batch -- the reference's batch dict (tokid_tt, seg_tt, attnmask_tt) or an (ids, type ids, mask) tuple of int64 [B, L] tensors --
+        -> [B, 768] fp32 on the GPU: the CLS rows of last_hidden_state, or with mix (post-soft-max weights [n_layers + 1], a device
+        tensor that may carry a graph) of the mix-weighted sum of all n_layers + 1 hidden states.  In train() mode with grad enabled
+        one operator (torch.ops.aspire.bert_layers_train_cls) runs the training forward, the read-out and, on backward, the layer stack's
+        gradient from the [B, 768] gradient alone; the dropout counter advances once per call, as in forward.  In eval() or under
+        torch.no_grad() it is the inference forward's read-out (no tape, no dropout, the counter stays)."""
+        from . import torch_ops  # noqa: F401  (registers the operators)
+        if isinstance(batch, dict):
+            tokid_tt, token_type_ids, attention_mask = batch['tokid_tt'], batch.get('seg_tt'), batch.get('attnmask_tt')
+        else:
+            tokid_tt, token_type_ids, attention_mask = (tuple(batch) + (None, None))[:3] if isinstance(batch, (tuple, list)) else (batch, None, None)
+        emb = self.bert.embeddings
+        dev = emb.word_embeddings.weight.device
+        tok = tokid_tt.to(device=dev, dtype=torch.int64)
+        typ = token_type_ids.to(device=dev, dtype=torch.int64) if token_type_ids is not None else torch.zeros_like(tok)
+        msk = attention_mask.to(device=dev, dtype=torch.int64) if attention_mask is not None else torch.ones_like(tok)
+        cfg = self.config
+        if mix is not None:
+            mix = mix.to(device=dev, dtype=torch.float32).reshape(-1)
+            if mix.numel() != cfg.num_hidden_layers + 1:
+                raise ValueError(f'mix: expected {cfg.num_hidden_layers + 1} weights, got {mix.numel()}')
+        if not (self.training and torch.is_grad_enabled()):
+            with torch.no_grad():
+                tables = [emb.word_embeddings.weight, emb.position_embeddings.weight, emb.token_type_embeddings.weight]
+                return torch.ops.aspire.bert_cls_forward(tok, typ, msk, tables + self.layer_weights(), cfg.num_attention_heads,
+                                                         cfg.layer_norm_eps, mix.cpu().tolist() if mix is not None else [])
+        seq_len = tok.shape[1]
+        if seq_len > cfg.max_position_embeddings:
+            raise IndexError(f'{seq_len} tokens: beyond max_position_embeddings={cfg.max_position_embeddings}')
+        emb_sum = (emb.word_embeddings(tok) + emb.token_type_embeddings(typ)) + emb.position_embeddings.weight[:seq_len]
+        seed, step = self._seed, self._step
+        if self.dropout:
+            self._step = (step + 1) % 2 ** 32
+        cls, _layer_cls, _tape = torch.ops.aspire.bert_layers_train_cls(
+            emb_sum, msk, self.layer_weights(), mix, cfg.num_attention_heads, cfg.layer_norm_eps, self.p_hidden, self.p_attn,
+            seed - 2 ** 64 if seed >= 2 ** 63 else seed, step)
+        return cls
 
     def forward(self, tokid_tt, token_type_ids=None, attention_mask=None):
         """int64 [B, L] tensors (any device), or the reference's batch dict (tokid_tt, seg_tt, attnmask_tt) -> last_hidden_state

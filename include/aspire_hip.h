@@ -327,6 +327,52 @@ int aspire_bert_dropout_mask_u8(uint64_t seed, uint32_t step, int32_t site, floa
                                 unsigned char* keep_out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * A1t for the CLS-row models: the read-out of MySPECTER (cospecter; disent_models.py:178-205: torch.stack of hidden_states,
+ * SoftmaxMixLayers, [:, 0, :]) and of SentBERTWrapper / ICTBERTWrapper (cosentbert / ictsentbert; sentsim_models.py:62-78:
+ * last_hidden_state[:, 0, :]) under training, and its gradient as one more source of the backward above.
+ *
+ * aspire_bert_cls_mix_train_f32: call it after aspire_bert_layers_forward_train[_dropout]_f32, on that call's tape and hidden_out.
+ * Hidden state l < n_layers is the tape's layer-l input (under dropout state 0 is the embedding LayerNorm output AFTER site 0's
+ * dropout: HuggingFace's hidden_states[0]); state n_layers is hidden_out.  The tape stays opaque: only this entry knows where the
+ * layer inputs lie.
+ *   mix        device [n_layers + 1] post-soft-max weights, or NULL
+ *   layer_cls  [n_layers + 1, B, 768]: the CLS rows of every state; may be NULL when mix is NULL
+ *   cls_out    [B, 768] = sum_l mix[l] * state_l[b, 0, :], l ascending in fp32; mix NULL: the top state's CLS rows, bit for bit
+ *
+ * aspire_bert_layers_backward_cls_f32: aspire_bert_layers_backward_dropout_f32 with one more gradient source.  Row (b, 0) of the
+ * gradient of hidden state l additionally receives mix[l] * grad_cls[b, :] for every l in 0 .. n_layers (mix NULL: the top state
+ * alone, factor 1): below the top a B x 768 row update on the residual branch's gradient between a layer's backward and the LayerNorm
+ * backward that adds the two branches; for state 0 before the backward of site 0's dropout.  grad_hidden may be NULL: the top
+ * gradient is then zeros plus the CLS rows, formed in the workspace (no [B, L, 768] gradient crosses the interface).
+ *   grad_mix   device [n_layers + 1] or NULL: grad_mix[l] = sum_b <grad_cls[b], layer_cls[l, b]>, one workgroup per l, fixed order
+ *   dropout    NULL or the forward's struct, as above
+ * Tape and workspace sizes are unchanged.  No atomics, one writer per element: two calls on one tape give the same bits.  Checked
+ * before the first launch, beyond the checks above: grad_cls and grad_hidden both NULL, grad_mix with layer_cls / mix / grad_cls
+ * NULL -> ASPIRE_ERR_INVALID_ARG; B == 0 -> ASPIRE_OK without a launch.
+ *
+ * aspire_inbatch_xent_f32 / _backward_f32: ICTBERTWrapper.forward_rank's loss (sentsim_models.py:81-126: torch.matmul(q, c.T) into
+ * nn.CrossEntropyLoss(reduction='sum') against targets arange(B)) over q, c [B, 768], 16-byte aligned.
+ *   s = Q C^T (exact fp32 products on the matrix cores, as aspire_dotmax_scores_f32);  row_lse[i] = max-shifted logsumexp_j s_ij
+ *   loss[0] = sum_i (row_lse[i] - s_ii), a fixed order;  B == 1 gives exactly 0
+ *   backward: W_ij = grad_loss[0] * (exp(s_ij - row_lse[i]) - [i == j]), grad_q[i] = sum_j W_ij c_j, grad_c[j] = sum_i W_ij q_i; the
+ *   dot products are formed again on the matrix cores, and with them every row's maximum m_i and normaliser z_i, kept apart:
+ *   W_ij = grad_loss[0] * (exp(s_ij - m_i) / z_i - [i == j]), so a row of weights sums to 0 to a rounding at any |s| (m_i + log z_i
+ *   rounded to one float loses log z_i's low bits at |s| of several hundred, where one ulp is 6e-5).  row_lse is therefore checked
+ *   for NULL but not read.  Every row is written once by the workgroup that owns it; no atomics, the same bits on every run
+ * B in [1, 128] (the document-row limit); B > 128 or D != 768 -> ASPIRE_ERR_UNSUPPORTED (the value is in aspire_last_error()); a NULL
+ * pointer -> ASPIRE_ERR_INVALID_ARG; B == 0 -> ASPIRE_OK without a launch.
+ * ------------------------------------------------------------------------------------------- */
+int aspire_bert_cls_mix_train_f32(const aspire_bert_weights* w, int64_t B, int64_t L, const void* tape, size_t tape_bytes,
+                                  const float* hidden_out, const float* mix, float* cls_out, float* layer_cls, void* stream);
+int aspire_bert_layers_backward_cls_f32(const aspire_bert_weights* w, const int64_t* attn_mask, int64_t B, int64_t L,
+                                        const float* grad_hidden, const float* grad_cls, const float* mix, const float* layer_cls,
+                                        const void* tape, size_t tape_bytes, float* grad_emb_sum, const aspire_bert_grads* grads,
+                                        float* grad_mix, void* ws, size_t ws_bytes, const aspire_bert_dropout* dropout, void* stream);
+int aspire_inbatch_xent_f32(const float* q, const float* c, int64_t B, int64_t D, float* loss, float* row_lse, void* stream);
+int aspire_inbatch_xent_backward_f32(const float* q, const float* c, int64_t B, int64_t D, const float* row_lse,
+                                     const float* grad_loss, float* grad_q, float* grad_c, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The trainer's parameter update (src/learning/trainer.py:178-181: optim.Adam / optim.Adagrad at torch's defaults): one launch over
  * every tensor of a parameter set, torch's single-tensor formulas in fp32 (division and square root correctly rounded), in place.
  *   tensors[i]   param, grad, state1, state2: n fp32 elements each, on the device, 4-byte aligned (16-byte aligned tensors take
