@@ -139,6 +139,11 @@ SIGNATURES = {
                                                     c_size_t, ctypes.POINTER(BertDropout), c_void_p]),
     'aspire_inbatch_xent_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     'aspire_inbatch_xent_backward_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'aspire_bert_embed_sum_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64,
+                                          c_void_p, c_void_p]),
+    'aspire_bert_embed_workspace_bytes': (c_size_t, [c_int64, c_int64]),
+    'aspire_bert_embed_backward_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64,
+                                               c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     'aspire_token_mean_pool_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p]),
     'aspire_bert_status': (c_int, [ctypes.POINTER(ctypes.c_int32), c_void_p]),
     'aspire_bert_cls_workspace_bytes': (c_size_t, [ctypes.POINTER(BertWeights), c_int64, c_int64]),

@@ -751,6 +751,60 @@ def topk_merge_keys(keys, k):
     return top_s, top_i
 
 
+def _i64_ids(t, name, shape=None):
+    assert t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.dim() == 2, f'{name}: need contiguous int64 [B, L] on the GPU'
+    assert shape is None or t.shape == shape, f'{name}: shape {tuple(t.shape)}, expected {tuple(shape)}'
+    return t
+
+
+def bert_embed_sum(tok, typ, word, pos, type_emb, out=None):
+    """BertEmbeddings' sum (aspire_bert_embed_sum_f32): tok int64 [B, L], typ the same or None (all type 0), the three tables
+    [rows, 768] fp32 -> emb_sum [B, L, 768] = (word[tok] + type_emb[typ]) + pos[:L], torch's bits.  A row whose id or type lies
+    outside its table is NaN (never read).  out: the buffer to write into instead of a new one."""
+    _i64_ids(tok, 'tok')
+    if typ is not None:
+        _i64_ids(typ, 'typ', tok.shape)
+    for t, name in ((word, 'word'), (pos, 'pos'), (type_emb, 'type_emb')):
+        assert _f32(t, name).dim() == 2 and t.shape[1] == D, f'{name}: need [rows, {D}]'
+    b, l = tok.shape
+    out = out if out is not None else torch.empty(b, l, D, device=tok.device, dtype=torch.float32)
+    assert _f32(out, 'out').shape == (b, l, D)
+    check(lib.aspire_bert_embed_sum_f32(_ptr(word), _ptr(pos), _ptr(type_emb), _ptr(tok), _ptr(typ), b, l, word.shape[0], pos.shape[0],
+                                        type_emb.shape[0], _ptr(out), _stream()))
+    return out
+
+
+def bert_embed_backward(grad, tok, typ, vocab, max_pos, n_types, padding_idx=-1, want=(True, True, True), out=None):
+    """The three tables' gradients (aspire_bert_embed_backward_f32): grad [B, L, 768] fp32, tok / typ as bert_embed_sum ->
+    (grad_word [vocab, 768], grad_pos [max_pos, 768], grad_type [n_types, 768]), None where want says the table is not wanted
+    (nothing is launched for it).  Every row of a wanted table is written by the kernels, in the fixed orders the header states: the
+    same bits on every run.  out: three buffers (or None) to write into instead of new ones."""
+    _i64_ids(tok, 'tok')
+    if typ is not None:
+        _i64_ids(typ, 'typ', tok.shape)
+    b, l = tok.shape
+    assert _f32(grad, 'grad').shape == (b, l, D)
+    rows = (vocab, max_pos, n_types)
+    outs = []
+    for i, n in enumerate(rows):
+        given = out[i] if out is not None else None
+        if not want[i]:
+            outs.append(None)
+        elif given is not None:
+            assert _f32(given, 'out').shape == (n, D)
+            outs.append(given)
+        else:
+            outs.append(torch.empty(n, D, device=grad.device, dtype=torch.float32))
+    if all(o is None for o in outs):
+        return tuple(outs)
+    ws = None
+    if outs[0] is not None:
+        ws = torch.empty(lib.aspire_bert_embed_workspace_bytes(b * l, vocab), device=grad.device, dtype=torch.uint8)
+    check(lib.aspire_bert_embed_backward_f32(_ptr(grad), _ptr(tok), _ptr(typ), b, l, vocab, max_pos, n_types, padding_idx, _ptr(outs[0]),
+                                             _ptr(outs[1]), _ptr(outs[2]), _ptr(ws), ws.numel() if ws is not None else 0, _stream()))
+    return tuple(outs)
+
+
 def optim_tensor_check(t, name):
     """What the optimizer kernels take: a dense, contiguous fp32 tensor on the GPU (a contiguous view at any storage offset is fine)."""
     if t.is_sparse:

@@ -53,6 +53,11 @@ implementation so that shapes propagate under FakeTensor / torch.compile tracing
     torch.ops.aspire.inbatch_xent(q, c) -> (loss [1], row_lse [B])                                 sentsim_models.py:81-126
                                          (autograd registered: the gradient of loss with respect to q and c)
     torch.ops.aspire.inbatch_xent_backward(grad_loss, q, c, row_lse) -> (grad_q, grad_c)
+  the embedding lookup in front of the encoder (HipBertTrainEncoder(hip_embeddings=True)):
+    torch.ops.aspire.bert_embed_sum(tok, typ | None, word, pos, type_emb, padding_idx) -> emb_sum [B, L, 768]     BertEmbeddings' sum
+                                         (autograd registered: the three tables' gradients, written in a fixed order, no atomics)
+    torch.ops.aspire.bert_embed_backward(grad, tok, typ | None, vocab, max_pos, n_types, padding_idx, want_word, want_pos, want_type)
+                                         -> (grad_word, grad_pos, grad_type), an empty tensor for a table that is not wanted
   resident CSR pools (rows + start + len, struct aspire_repset):
     torch.ops.aspire.l2max_scores_csr / ot_scores_csr(q_rows, q_start, q_len, q_max, c_rows, c_start, c_len, c_max, ...) -> [Q * C]
     torch.ops.aspire.ot_rank_batch(q_rows, q_start, q_len, q_max, c_rows, c_start, c_len, c_max, job_off, max_job, k, ...)
@@ -789,6 +794,58 @@ def _inbatch_xent_grad(ctx, grad_loss, grad_lse):
 inbatch_xent.register_autograd(_inbatch_xent_grad, setup_context=_inbatch_xent_setup)
 
 
+# ---- the embedding lookup under autograd (aspire_bert_embed_sum_f32 / aspire_bert_embed_backward_f32) ------------------------------------
+# BertEmbeddings' sum (word[tok] + type_emb[typ]) + pos[:L] with torch's bits; typ None: every token of type 0.  padding_idx: the word
+# table's row without a gradient (nn.Embedding's padding_idx), -1 for none; the forward does not read it.  The backward writes every row
+# of every wanted table in a fixed order without atomics; a table that is not wanted comes back as an empty tensor and the autograd
+# formula hands None on (the want flags are the forward's needs_input_grad).
+@torch.library.custom_op('aspire::bert_embed_sum', mutates_args=(), device_types='cuda')
+def bert_embed_sum(tok: Tensor, typ: Optional[Tensor], word: Tensor, pos: Tensor, type_emb: Tensor, padding_idx: int) -> Tensor:
+    tok, = _int64(tok)
+    if typ is not None:
+        typ, = _int64(typ)
+    return ops.bert_embed_sum(tok, typ, *(t.to(torch.float32).contiguous() for t in (word, pos, type_emb)))
+
+
+@torch.library.custom_op('aspire::bert_embed_backward', mutates_args=(), device_types='cuda')
+def bert_embed_backward(grad: Tensor, tok: Tensor, typ: Optional[Tensor], vocab: int, max_pos: int, n_types: int, padding_idx: int,
+                        want_word: bool, want_pos: bool, want_type: bool) -> Tuple[Tensor, Tensor, Tensor]:
+    tok, = _int64(tok)
+    if typ is not None:
+        typ, = _int64(typ)
+    grads = ops.bert_embed_backward(grad.to(torch.float32).contiguous(), tok, typ, vocab, max_pos, n_types, padding_idx,
+                                    want=(want_word, want_pos, want_type))
+    return tuple(g if g is not None else grad.new_empty(0, dtype=torch.float32) for g in grads)
+
+
+@bert_embed_sum.register_fake
+def _(tok, typ, word, pos, type_emb, padding_idx):
+    return word.new_empty((tok.shape[0], tok.shape[1], word.shape[1]), dtype=torch.float32)
+
+
+@bert_embed_backward.register_fake
+def _(grad, tok, typ, vocab, max_pos, n_types, padding_idx, want_word, want_pos, want_type):
+    return tuple(grad.new_empty((n, grad.shape[2]) if want else (0,), dtype=torch.float32)
+                 for n, want in ((vocab, want_word), (max_pos, want_pos), (n_types, want_type)))
+
+
+def _bert_embed_sum_setup(ctx, inputs, output):
+    tok, typ, word, pos, type_emb, ctx.padding_idx = inputs
+    ctx.with_typ = typ is not None
+    ctx.save_for_backward(tok, *([typ] if ctx.with_typ else []))
+    ctx.rows = (word.shape[0], pos.shape[0], type_emb.shape[0])
+
+
+def _bert_embed_sum_grad(ctx, grad):
+    tok, *rest = ctx.saved_tensors
+    want = tuple(ctx.needs_input_grad[2:5])
+    gw, gp, gt = torch.ops.aspire.bert_embed_backward(grad, tok, rest[0] if ctx.with_typ else None, *ctx.rows, ctx.padding_idx, *want)
+    return None, None, gw if want[0] else None, gp if want[1] else None, gt if want[2] else None, None
+
+
+bert_embed_sum.register_autograd(_bert_embed_sum_grad, setup_context=_bert_embed_sum_setup)
+
+
 # keep bytes (0 / 1) of elements first .. first + n - 1 of one site's mask, by the device function the training kernels use
 @torch.library.custom_op('aspire::bert_dropout_mask', mutates_args=(), device_types=None)
 def bert_dropout_mask(seed: int, step: int, site: int, p: float, first: int, n: int) -> Tensor:
@@ -808,4 +865,4 @@ OPS = ('span_mean_pool', 'span_pool_ranges', 'bert_encoder_forward', 'bert_cls_f
        'ot_pair_scores', 'ot_pair_backward', 'jointsm_pair_scores', 'jointsm_pair_backward', 'l2sup_pair_scores', 'l2sup_pair_backward',
        'span_mean_pool_backward', 'cls_l2_pair', 'cls_l2_pair_backward', 'bert_layers_train', 'bert_layers_backward',
        'bert_layers_train_dropout', 'bert_layers_backward_dropout', 'bert_dropout_mask', 'bert_layers_train_cls', 'bert_layers_backward_cls',
-       'inbatch_xent', 'inbatch_xent_backward')
+       'inbatch_xent', 'inbatch_xent_backward', 'bert_embed_sum', 'bert_embed_backward')

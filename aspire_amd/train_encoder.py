@@ -19,8 +19,18 @@ applies the config's two probabilities at HuggingFace's four sites per layer sta
 (include/aspire_hip.h states the contract), never stored, formed again by the backward.  ``seed`` defaults to ``torch.initial_seed()``;
 ``step`` is a uint32 counter that advances once per training forward, so a run is reproduced by its seed alone and resumed through
 ``dropout_state()`` / ``set_dropout_state(seed, step)``.  ``eval()`` and ``torch.no_grad()`` run the inference forward: no dropout, and
-the counter does not move.  Not supported: activation checkpointing around this module -- the recomputed forward would draw the next
-step's masks, not the first forward's.
+the counter does not move.
+
+The embedding lookup is opt-in too.  ``HipBertTrainEncoder(bert_model, hip_embeddings=True)`` forms the embedding sum with
+torch.ops.aspire.bert_embed_sum (the same bits as torch's expression) and the three tables' gradients with its backward: every row
+written once, every sum in a fixed order, no atomics -- with it a run's gradients are the same bits on every run with the tables
+trained, which torch's scatter backward (atomics) does not promise.  ``padding_idx`` is the word table's (its row gets no gradient, as
+in torch).  ``check_ids=True`` (the default) looks at the ids and type ids first and raises IndexError for one out of range, at one
+host sync per forward; ``check_ids=False`` says the caller has validated them (an id out of range is then never read: its row of the
+sum is NaN).  The default ``hip_embeddings=False`` is the graph described above.
+
+Not supported: activation checkpointing around this module -- the recomputed forward would draw the next step's masks, not the first
+forward's.
 """
 import warnings
 
@@ -31,9 +41,10 @@ from .encoder import _LAYER_KEYS, require_bert_base
 
 
 class HipBertTrainEncoder(torch.nn.Module):
-    def __init__(self, bert_model, dropout=False, seed=None):
+    def __init__(self, bert_model, dropout=False, seed=None, hip_embeddings=False, check_ids=True):
         super().__init__()
         dev = ops.require_gpu()
+        self.hip_embeddings, self.check_ids = bool(hip_embeddings), bool(check_ids)
         cfg = bert_model.config
         if getattr(cfg, 'model_type', 'bert') in ('roberta', 'mpnet') or not hasattr(bert_model.embeddings, 'token_type_embeddings'):
             raise NotImplementedError(f'{type(bert_model).__name__}: the training encoder is built for BertModel (the position ids and the '
@@ -81,6 +92,24 @@ class HipBertTrainEncoder(torch.nn.Module):
             w += [named[k] for k in _LAYER_KEYS]
         return w
 
+    def _emb_sum(self, tok, typ, seq_len):
+        """BertEmbeddings' sum in its order, (word + token type) + position, [B, L, 768]: torch's lookups (the tables' gradients are then
+        torch's scatter), or with hip_embeddings the library's operator, whose backward writes the three tables' gradients in a fixed
+        order.  The two give the same bits forward."""
+        emb = self.bert.embeddings
+        if not self.hip_embeddings:
+            return (emb.word_embeddings(tok) + emb.token_type_embeddings(typ)) + emb.position_embeddings.weight[:seq_len]
+        word, types = emb.word_embeddings, emb.token_type_embeddings.weight
+        if self.check_ids and tok.numel():
+            # one host sync for the four extremes (nn.Embedding raises IndexError on the reference path)
+            lo_t, hi_t, lo_y, hi_y = torch.stack([tok.min(), tok.max(), typ.min(), typ.max()]).tolist()
+            if lo_t < 0 or hi_t >= word.weight.shape[0]:
+                raise IndexError('token id out of range')
+            if lo_y < 0 or hi_y >= types.shape[0]:
+                raise IndexError('token type id out of range')
+        return torch.ops.aspire.bert_embed_sum(tok, typ, word.weight, emb.position_embeddings.weight, types,
+                                               -1 if word.padding_idx is None else int(word.padding_idx))
+
     def forward_cls(self, batch, mix=None):
         """The CLS read-out of the bi-encoders and the sentence encoders (MySPECTER.doc_reps_bert, SentBERTWrapper.sent_reps_bert):
         batch -- the reference's batch dict (tokid_tt, seg_tt, attnmask_tt) or an (ids, type ids, mask) tuple of int64 [B, L] tensors --
@@ -112,7 +141,7 @@ class HipBertTrainEncoder(torch.nn.Module):
         seq_len = tok.shape[1]
         if seq_len > cfg.max_position_embeddings:
             raise IndexError(f'{seq_len} tokens: beyond max_position_embeddings={cfg.max_position_embeddings}')
-        emb_sum = (emb.word_embeddings(tok) + emb.token_type_embeddings(typ)) + emb.position_embeddings.weight[:seq_len]
+        emb_sum = self._emb_sum(tok, typ, seq_len)
         seed, step = self._seed, self._step
         if self.dropout:
             self._step = (step + 1) % 2 ** 32
@@ -142,8 +171,7 @@ class HipBertTrainEncoder(torch.nn.Module):
         seq_len = tok.shape[1]
         if seq_len > cfg.max_position_embeddings:
             raise IndexError(f'{seq_len} tokens: beyond max_position_embeddings={cfg.max_position_embeddings}')
-        # BertEmbeddings' order: (word + token type) + position
-        emb_sum = (emb.word_embeddings(tok) + emb.token_type_embeddings(typ)) + emb.position_embeddings.weight[:seq_len]
+        emb_sum = self._emb_sum(tok, typ, seq_len)
         if not self.dropout:
             hidden, _tape = torch.ops.aspire.bert_layers_train(emb_sum, msk, self.layer_weights(), cfg.num_attention_heads, cfg.layer_norm_eps)
             return hidden

@@ -373,6 +373,46 @@ int aspire_inbatch_xent_backward_f32(const float* q, const float* c, int64_t B, 
                                      const float* grad_loss, float* grad_q, float* grad_c, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The embedding lookup under training: BertEmbeddings' sum in front of aspire_bert_layers_forward_train_f32 and the three tables'
+ * gradients behind aspire_bert_layers_backward_f32 (what nn.Embedding's forward and scatter backward do on the reference path).
+ * Hidden size 768.  Token rows m = b L + l, M = B L.  word [vocab, 768], pos [max_pos, 768], type [n_types, 768]; tok, typ int64
+ * [B, L] on the device, typ may be NULL (every token of type 0).  Tables, out and the gradients are 16-byte aligned.
+ *
+ * aspire_bert_embed_sum_f32:  out[b, l, :] = (word[tok[b, l]] + type[typ[b, l]]) + pos[l], plain fp32 adds in BertEmbeddings'
+ *   order (torch's bits).  One wave per token row.  A row whose id lies outside [0, vocab) or whose type lies outside [0, n_types)
+ *   is never turned into an address: that row of out is NaN.
+ *
+ * aspire_bert_embed_backward_f32:  grad_emb_sum [B, L, 768] -> grad_word [vocab, 768], grad_pos [max_pos, 768], grad_type
+ *   [n_types, 768].  Each output pointer may be NULL: that table is not wanted and nothing is launched for it.  Every row of every
+ *   wanted table is WRITTEN (the buffers need no zero-fill; rows that no token names are exact zeros), every element by one writer,
+ *   no atomics: the same bits on every run.  All sums are plain fp32 adds in these orders:
+ *     grad_word[v]   the rows grad_emb_sum[m] with tok[m] == v, added one after the other in ascending m, starting from the first
+ *                    row; zeros for v == padding_idx (nn.Embedding's padding row has no gradient; padding_idx = -1: there is no such
+ *                    row) and for an id no token has.  A token whose id lies outside [0, vocab) contributes to no row.
+ *     grad_pos[l]    grad_emb_sum[0, l] + grad_emb_sum[1, l] + ... in ascending b, for l < L; zeros for l >= L.
+ *     grad_type[t]   two stages whose order depends on M alone.  R = ceil(M / 64) rows per block; partial_j, j = 0 .. 63, starts at
+ *                    0 and adds, in ascending m, the rows m in [j R, min((j + 1) R, M)) with typ[m] == t (a block without such a
+ *                    row, or beyond M, stays 0); grad_type[t] starts at 0 and adds partial_0 .. partial_63 in ascending j.  A
+ *                    type outside [0, n_types) contributes to no row.
+ *   The word table: the keys (tok[m], m) are ranked by counting -- every token counts the keys below its own, M^2 integer compares,
+ *   no data-dependent exchange -- and m goes to order[rank]; then one wave per table row finds its run of the sorted ids with a
+ *   binary search and adds the run's gradient rows.  A row that one id fills is a serial chain of M adds on one wave.
+ *   workspace   device memory of at least aspire_bert_embed_workspace_bytes(M, vocab) bytes (a multiple of 16, growing with M),
+ *               16-byte aligned; read and written only when grad_word is wanted.
+ *   The rank pass serves at most 65 536 token rows: grad_word wanted with M above that -> ASPIRE_ERR_UNSUPPORTED.
+ * Errors, all before the device is touched, the offending value in aspire_last_error(): ASPIRE_ERR_INVALID_ARG for a NULL word / pos /
+ * type / tok / out (forward), a NULL grad_emb_sum with a wanted table, a NULL tok with grad_word wanted, B < 0, L outside
+ * (0, max_pos], vocab, max_pos or n_types <= 0, padding_idx outside [-1, vocab), a pointer that is not 16-byte aligned, a workspace
+ * that is NULL or too small when grad_word is wanted.  B == 0, or all three outputs NULL -> ASPIRE_OK without a launch.
+ * ------------------------------------------------------------------------------------------- */
+int aspire_bert_embed_sum_f32(const float* word, const float* pos, const float* type, const int64_t* tok, const int64_t* typ, int64_t B,
+                              int64_t L, int64_t vocab, int64_t max_pos, int64_t n_types, float* out, void* stream);
+size_t aspire_bert_embed_workspace_bytes(int64_t M, int64_t vocab);
+int aspire_bert_embed_backward_f32(const float* grad_emb_sum, const int64_t* tok, const int64_t* typ, int64_t B, int64_t L, int64_t vocab,
+                                   int64_t max_pos, int64_t n_types, int64_t padding_idx, float* grad_word, float* grad_pos,
+                                   float* grad_type, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The trainer's parameter update (src/learning/trainer.py:178-181: optim.Adam / optim.Adagrad at torch's defaults): one launch over
  * every tensor of a parameter set, torch's single-tensor formulas in fp32 (division and square root correctly rounded), in place.
  *   tensors[i]   param, grad, state1, state2: n fp32 elements each, on the device, 4-byte aligned (16-byte aligned tensors take
