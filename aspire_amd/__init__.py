@@ -8,7 +8,7 @@ from . import _lib  # noqa: F401  (fails loudly when the HIP library has not bee
 from .batch_prep import prepare_abstracts, prepare_bert_sentences  # noqa: F401
 from .pair_distances import (AllPairMaskedWasserstein, AllPairMaskedAttention, allpair_masked_dist_l2max,  # noqa: F401
                              allpair_masked_dist_l2topk, allpair_joint_sm_negscore, rep_len_tup)
-from .rank_loss import RankLoss, sent_reps_from_hidden  # noqa: F401
+from .rank_loss import RankLoss, SupAlignRankLoss, cross_doc_l1, sent_reps_from_hidden  # noqa: F401
 from .train_encoder import HipBertTrainEncoder  # noqa: F401
 from .cls_train import BiEncTrain, ClsTripletLoss, IctEncTrain, IctLoss, SentEncTrain  # noqa: F401
 from .optim import HipAdam, HipAdagrad  # noqa: F401

@@ -203,6 +203,9 @@ SIGNATURES = {
     'aspire_l2sup_scores_f32': (c_int, [ctypes.POINTER(RepSet), ctypes.POINTER(RepSet), c_int64, c_void_p, c_int, c_void_p, c_void_p]),
     'aspire_l2sup_backward_f32': (c_int, [ctypes.POINTER(RepSet), ctypes.POINTER(RepSet), c_int64, c_void_p, c_int, c_void_p, c_void_p,
                                           c_void_p, c_void_p]),
+    'aspire_sent_cdist_f32': (c_int, [ctypes.POINTER(RepSet), ctypes.POINTER(RepSet), c_int64, c_void_p, c_void_p]),
+    'aspire_sent_cdist_backward_f32': (c_int, [ctypes.POINTER(RepSet), ctypes.POINTER(RepSet), c_int64, c_void_p, c_void_p, c_void_p,
+                                               c_void_p]),
     'aspire_dense_rank_batch_workspace_bytes': (c_size_t, [c_int64, c_int64, c_int64, c_int64]),
     'aspire_dense_rank_batch_f32': (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int,
                                             c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -109,6 +109,46 @@ def prepare_abstracts(batch_abs, pt_lm_tokenizer):
     return bert_batch, abs_lens, sent_token_idxs
 
 
+ALIGN_TYPES = ('cc_align', 'abs_align')     # AbsSentTokBatcherPreAlign.align_type (batchers.py:639-640)
+
+
+def _prepare_abstracts_align(batch_abs, pt_lm_tokenizer, align_type):
+    """AbsSentTokBatcherPreAlign.prepare_abstracts (batchers.py:710-746): prepare_abstracts and the examples' pre-computed
+    alignments [query sentence, candidate sentence] (copies), None when no example carries `align_type`."""
+    align = []
+    for ex_abs in batch_abs:
+        if align_type in ex_abs:
+            assert (len(ex_abs[align_type]) == 2)   # batchers.py:729
+            align.append(list(ex_abs[align_type]))
+    bert_batch, abs_lens, sent_token_idxs = prepare_abstracts(batch_abs, pt_lm_tokenizer)
+    if align:
+        assert (len(align) == len(abs_lens))   # batchers.py:743: every example carries the key, or none
+    return bert_batch, abs_lens, sent_token_idxs, align or None
+
+
+def make_batch(raw_feed, pt_lm_tokenizer, align_type='cc_align'):
+    """AbsSentTokBatcher.make_batch and AbsSentTokBatcherPreAlign.make_batch (batchers.py:462-523, :642-746) in one: the batch dict
+    of RankLoss / SupAlignRankLoss.forward_rank from a raw feed of example dicts ('TITLE', 'ABSTRACT' and, pre-aligned, `align_type`).
+      'query_texts', 'pos_texts' and 'neg_texts' (the dev set): query_ / pos_ / neg_ + bert_batch, abs_lens, senttok_idxs
+      'query_texts' and 'pos_texts' (training with in-batch negatives): query_ / pos_
+      'query_texts' alone (encoding): bert_batch, abs_lens, senttok_idxs
+    'pos_align_idxs' / 'neg_align_idxs' are present exactly when every example of that side carries `align_type` ('cc_align' or
+    'abs_align'); when only some do, the reference's assertion fires.  The alignment lists are copies of the examples'."""
+    if align_type not in ALIGN_TYPES:
+        raise ValueError(f'Unknown align_type: {align_type}')
+    qbert_batch, qabs_len, qabs_senttok_idxs = prepare_abstracts(raw_feed['query_texts'], pt_lm_tokenizer)
+    if 'pos_texts' not in raw_feed:     # Happens when the function is called from other scripts to encode text.
+        return {'bert_batch': qbert_batch, 'abs_lens': qabs_len, 'senttok_idxs': qabs_senttok_idxs}
+    batch_dict = {'query_bert_batch': qbert_batch, 'query_abs_lens': qabs_len, 'query_senttok_idxs': qabs_senttok_idxs}
+    sides = ('neg', 'pos') if 'neg_texts' in raw_feed else ('pos',)      # (the reference's order: negatives first in the dev set)
+    for side in sides:
+        bert_batch, abs_len, senttok_idxs, align = _prepare_abstracts_align(raw_feed[side + '_texts'], pt_lm_tokenizer, align_type)
+        batch_dict.update({side + '_bert_batch': bert_batch, side + '_abs_lens': abs_len, side + '_senttok_idxs': senttok_idxs})
+        if align is not None:
+            batch_dict[side + '_align_idxs'] = align
+    return batch_dict
+
+
 def spans_to_csr(batch_senttok_idxs, max_sents):
     """Ragged [B][<=S][tokens] position lists -> (tok_idx int32 [N], span_off int32 [B*S+1]) on the host.
     Slots beyond a document's sentence count are empty (they pool to exact zeros)."""

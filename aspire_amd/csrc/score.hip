@@ -5,7 +5,8 @@
 //
 // Top to bottom: argument checks and ScoreArgs fills (check_repsets, check_backward_sets, fill_set_args, fill_ot_args); the max-sim
 // entry points and the backward of their aggregations (aspire_l2agg_backward_f32: checks here, the kernel in l2agg_bwd.hip), the checks of
-// aspire_jointsm_backward_f32 (jointsm_bwd.hip) and of the supervised-alignment pair aspire_l2sup_scores_f32 / _backward_f32 (l2sup.hip); the
+// aspire_jointsm_backward_f32 (jointsm_bwd.hip), of the supervised-alignment pair aspire_l2sup_scores_f32 / _backward_f32 (l2sup.hip) and
+// of the padded blocks' distance matrix aspire_sent_cdist_f32 / _backward_f32 (cdist_pair.hip); the
 // host helpers of the batched / CHUNK / REC forms -- form rules (chunk_size_ok, one_wave_form_ok, sinkhorn_form_honours_gate),
 // workspace layouts (batch_layout, l2_batch_layout, batch_tables), launch_fused_form; otAspire per call (ot_run_tiles, ot_run)
 // and its backward (aspire_ot_backward_f32: checks here, the kernel in ot_bwd.hip);
@@ -212,6 +213,26 @@ extern "C" int aspire_l2sup_backward_f32(const aspire_repset* q, const aspire_re
                    "align, grad_scores, grad_q_rows or grad_c_rows is null");
     return launch_l2sup_backward(to_dev(q), to_dev(c), align, weighted != 0, grad_scores, grad_q_rows, grad_c_rows, rows_q, rows_c,
                                  (hipStream_t)stream);
+}
+
+// The cross-document distance matrix of the padded blocks and its backward (kernels in cdist_pair.hip): PAIRED only, padded sets only
+extern "C" int aspire_sent_cdist_f32(const aspire_repset* q, const aspire_repset* c, int64_t D, float* dist, void* stream) {
+    int rows_q, rows_c;
+    if (int rc = check_backward_sets(q, c, D, ASPIRE_PAIR_PAIRED, rows_q, rows_c)) return rc;
+    ASPIRE_REQUIRE(q->ext > 0 && c->ext > 0, ASPIRE_ERR_INVALID_ARG, "the distance matrix needs padded extents (ext > 0)");
+    if (q->n == 0) return ASPIRE_OK;
+    ASPIRE_REQUIRE(dist, ASPIRE_ERR_INVALID_ARG, "dist is null");
+    return launch_sent_cdist(to_dev(q), to_dev(c), dist, rows_q, rows_c, (hipStream_t)stream);
+}
+
+extern "C" int aspire_sent_cdist_backward_f32(const aspire_repset* q, const aspire_repset* c, int64_t D, const float* grad_dist,
+                                              float* grad_q_rows, float* grad_c_rows, void* stream) {
+    int rows_q, rows_c;
+    if (int rc = check_backward_sets(q, c, D, ASPIRE_PAIR_PAIRED, rows_q, rows_c)) return rc;
+    ASPIRE_REQUIRE(q->ext > 0 && c->ext > 0, ASPIRE_ERR_INVALID_ARG, "the distance matrix needs padded extents (ext > 0)");
+    if (q->n == 0) return ASPIRE_OK;
+    ASPIRE_REQUIRE(grad_dist && grad_q_rows && grad_c_rows, ASPIRE_ERR_INVALID_ARG, "grad_dist, grad_q_rows or grad_c_rows is null");
+    return launch_sent_cdist_backward(to_dev(q), to_dev(c), grad_dist, grad_q_rows, grad_c_rows, rows_q, rows_c, (hipStream_t)stream);
 }
 
 namespace {

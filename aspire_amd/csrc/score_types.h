@@ -209,6 +209,11 @@ int launch_l2sup_scores(const RepSet& q, const RepSet& c, const int32_t* align, 
 int launch_l2sup_backward(const RepSet& q, const RepSet& c, const int32_t* align, int weighted, const float* grad_scores, float* grad_q,
                           float* grad_c, int rows_q, int rows_c, hipStream_t stream);
 
+// cdist_pair.hip: the distance matrix of a PAIRED pair's zero-padded blocks [P, q.ext, c.ext] and its gradient (padded sets; pair_bwd.h's frame)
+int launch_sent_cdist(const RepSet& q, const RepSet& c, float* dist, int rows_q, int rows_c, hipStream_t stream);
+int launch_sent_cdist_backward(const RepSet& q, const RepSet& c, const float* grad_dist, float* grad_q, float* grad_c, int rows_q,
+                               int rows_c, hipStream_t stream);
+
 // fused.hip: cost + Sinkhorn solve in one launch for documents of <= 8 rows (CSR inputs, CROSS or MAPPED pairing)
 bool fused_self_ok(int64_t jobs, const aspire_ot_params* prm);
 bool fused_inbox_ok(const aspire_repset* q, const float* diameter);

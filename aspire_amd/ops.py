@@ -666,6 +666,31 @@ def l2sup_backward(q, c, align, grad_scores, weighted=False, out=None):
     return gq, gc
 
 
+def sent_cdist(q, c):
+    """disent_models.py:655 / :829 without the sign: dist [P, q.ext, c.ext] = ||q_i - c_j|| over the PAIRED pairs' whole zero-padded
+    blocks (padded rep sets; a row at or beyond its document's length counts as zeros and is not read) -- include/aspire_hip.h:
+    aspire_sent_cdist_f32."""
+    assert q.n == c.n, 'paired scoring needs equal batch sizes'
+    assert q.ext > 0 and c.ext > 0, 'the distance matrix needs padded rep sets'
+    dist = torch.empty(q.n, q.ext, c.ext, device=q.rows.device, dtype=torch.float32)
+    qs, cs = q.struct(), c.struct()
+    check(lib.aspire_sent_cdist_f32(ctypes.byref(qs), ctypes.byref(cs), D, _ptr(dist), _stream()))
+    return dist
+
+
+def sent_cdist_backward(q, c, grad_dist, out=None):
+    """The gradient of sent_cdist with respect to the sentence rows (aspire_sent_cdist_backward_f32): grad_dist [P, q.ext, c.ext] =
+    dLoss / ddist; the distances are formed again from the rows.  Returns and `out` as jointsm_backward."""
+    assert q.n == c.n, 'paired scoring needs equal batch sizes'
+    assert q.ext > 0 and c.ext > 0, 'the distance matrix needs padded rep sets'
+    assert _f32(grad_dist, 'grad_dist').shape == (q.n, q.ext, c.ext), 'grad_dist: [P, q.ext, c.ext]'
+    gq, gc = out if out is not None else (torch.zeros_like(q.rows), torch.zeros_like(c.rows))
+    assert _f32(gq, 'grad_q_rows').shape == q.rows.shape and _f32(gc, 'grad_c_rows').shape == c.rows.shape
+    qs, cs = q.struct(), c.struct()
+    check(lib.aspire_sent_cdist_backward_f32(ctypes.byref(qs), ctypes.byref(cs), D, _ptr(grad_dist), _ptr(gq), _ptr(gc), _stream()))
+    return gq, gc
+
+
 def jointsm_rank_batch(q, c, job_off, max_job, k, out=None, workspace=None, job_base=None, key_form=False):
     """The joint soft-max alignment score over J independent (query, pool) jobs in ONE call (include/aspire_hip.h:
     aspire_jointsm_rank_batch_f32); arguments and returns as l2max_rank_batch."""

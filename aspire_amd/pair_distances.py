@@ -18,7 +18,8 @@ not detached (include/aspire_hip.h, aspire_ot_backward_f32) -- since geomloss it
 ``return_pair_sims=True`` its outputs stay detached (the reference marks that branch "only used at test time").  Differentiable too are
 allpair_joint_sm_negscore, the dist_function of WordSentAlignPolyEnc (aspire_jointsm_backward_f32; ``pair_sm`` stays detached), and the
 supervised-alignment distances allpair_masked_dist_l2sup / allpair_masked_dist_l2sup_weighted, the criterion_sentsup of
-WordSentAbsSupAlignBiEnc (aspire_l2sup_backward_f32).  The cosine and dot scores have no backward: the reference does not train with
+WordSentAbsSupAlignBiEnc (aspire_l2sup_backward_f32), and ``sent_cdist``, the cross-document distance matrix of the zero-padded
+blocks that the reference's L1 regularisers read (aspire_sent_cdist_backward_f32).  The cosine and dot scores have no backward: the reference does not train with
 them.  For the L2 aggregations and jointsm, with ``return_pair_sims=True`` and a rep requiring grad the forward runs
 twice -- once for the (detached) pair matrices, once through the differentiable operator for ``sims`` -- and the inputs are copied to
 the GPU for each: correct and the same bits, twice the work; the train-time branch (``return_pair_sims=False``) runs it once.
@@ -51,7 +52,8 @@ def _wants_grad(query, cand):
 def _differentiable_sims(query, cand, op):
     """sims [batch_size] of the pairs, attached to the graph of query.embed / cand.embed: op(q, q_lens, c, c_lens) -> sims, one of
     the differentiable torch.ops.aspire.*_pair_scores operators (the same bits as the plain scoring calls give), on the GPU between
-    differentiable moves and permutes."""
+    differentiable moves and permutes.  (sent_cdist sends torch.ops.aspire.sent_cdist through it: then the result is that operator's
+    [batch_size, q_max_sents, c_max_sents] matrix.)"""
     from . import torch_ops  # noqa: F401  (registers the operators)
     dev = ops.require_gpu()
     assert (query.embed.size(0) == cand.embed.size(0))   # pair_distances.py:46
@@ -218,3 +220,11 @@ def allpair_masked_dist_l2sup_weighted(query, cand):
     """pair_distances.py:238-292: allpair_masked_dist_l2sup divided by the number of entries q_len * c_len of the pair's cross-document
     block ("for use in multi tasking with the OT loss")."""
     return _l2sup_dist(query, cand, True)
+
+
+def sent_cdist(query, cand):
+    """disent_models.py:655 / :829 without the sign: torch.cdist(query.embed.permute(0, 2, 1), cand.embed.permute(0, 2, 1)) over the
+    whole zero-padded blocks -> [batch_size, q_max_sents, c_max_sents], with a row at or beyond its document's abs_lens entry taken as
+    zeros (what the read-out leaves there).  Distances from direct differences; attached to the graph when an embed requires grad
+    (torch.ops.aspire.sent_cdist, aspire_sent_cdist_backward_f32)."""
+    return _differentiable_sims(query, cand, lambda q, ql, c, cl: torch.ops.aspire.sent_cdist(q, ql, c, cl))

@@ -33,6 +33,9 @@ implementation so that shapes propagate under FakeTensor / torch.compile tracing
     torch.ops.aspire.l2sup_pair_scores(q, q_lens, c, c_lens, align, weighted) -> scores [B]        pair_distances.py:189-292
                                          (autograd registered; align int32 [B, 2]: the pre-aligned (query row, candidate row))
     torch.ops.aspire.l2sup_pair_backward(grad_scores, q, q_lens, c, c_lens, align, weighted) -> (grad_q, grad_c)
+    torch.ops.aspire.sent_cdist(q, q_lens, c, c_lens) -> dist [B, Sq, Sc]                          disent_models.py:655, :829
+                                         (autograd registered; ||q_i - c_j|| over the whole zero-padded blocks, pad rows as zeros)
+    torch.ops.aspire.sent_cdist_backward(grad_dist, q, q_lens, c, c_lens) -> (grad_q, grad_c)      torch.cdist's rule
   the read-out under autograd (span_mean_pool above has its autograd registered: the gradient with respect to hidden):
     torch.ops.aspire.span_mean_pool_backward(grad_sent | None, grad_cls | None, tok_idx, span_off, B, L, max_sents) -> grad_hidden [B, L, 768]
     torch.ops.aspire.cls_l2_pair(q_cls, c_cls, eps) -> dist [B]                                    disent_models.py:582, :634
@@ -398,10 +401,10 @@ def _pair_backward_fake(grad_scores, q, q_lens, c, c_lens, *rest):
     return q.new_empty(q.shape), c.new_empty(c.shape)
 
 
-def _register_pair_autograd(forward_op, backward_op):
+def _register_pair_autograd(forward_op, backward_op, forward_fake=_pair_scores_fake):
     """The two operators' fakes and the forward's autograd: the tensor inputs (they lead in every schema) are saved, the others kept
     on ctx; backward_op gives the gradients of q (position 0) and c (position 2), no other input has one."""
-    forward_op.register_fake(_pair_scores_fake)
+    forward_op.register_fake(forward_fake)
     backward_op.register_fake(_pair_backward_fake)
 
     def setup(ctx, inputs, output):
@@ -494,6 +497,23 @@ def l2sup_pair_backward(grad_scores: Tensor, q: Tensor, q_lens: Tensor, c: Tenso
 
 
 _register_pair_autograd(l2sup_pair_scores, l2sup_pair_backward)
+
+
+# The distance matrix of the pairs' whole zero-padded blocks, [B, Sq, Sc] instead of a score per pair (aspire_sent_cdist_f32): what the
+# reference's L1 regularisers take the norm / the singular values of.  q_lens / c_lens say which rows are pads: those count as zeros
+# and are not read.  The backward (aspire_sent_cdist_backward_f32) forms the distances again from the rows.
+@torch.library.custom_op('aspire::sent_cdist', mutates_args=(), device_types='cuda')
+def sent_cdist(q: Tensor, q_lens: Tensor, c: Tensor, c_lens: Tensor) -> Tensor:
+    return ops.sent_cdist(_padded_repset(q, q_lens), _padded_repset(c, c_lens))
+
+
+@torch.library.custom_op('aspire::sent_cdist_backward', mutates_args=(), device_types='cuda')
+def sent_cdist_backward(grad_dist: Tensor, q: Tensor, q_lens: Tensor, c: Tensor, c_lens: Tensor) -> Tuple[Tensor, Tensor]:
+    return _pair_backward(lambda qs, cs, g, out: ops.sent_cdist_backward(qs, cs, g, out=out), grad_dist, q, q_lens, c, c_lens)
+
+
+_register_pair_autograd(sent_cdist, sent_cdist_backward,
+                        forward_fake=lambda q, q_lens, c, c_lens: q.new_empty(_npairs(q.shape[0], c.shape[0], True), q.shape[1], c.shape[1]))
 
 
 # The document-level distance of the rank loss's abstract term: functional.pairwise_distance(q_cls, c_cls, p=2, eps) on paired CLS rows
@@ -863,6 +883,6 @@ def _(seed, step, site, p, first, n):
 OPS = ('span_mean_pool', 'span_pool_ranges', 'bert_encoder_forward', 'bert_cls_forward', 'bert_pooler', 'token_mean_pool', 'l2max_scores', 'jointsm_scores', 'ot_sinkhorn_scores', 'topk_desc', 'topk_keys', 'topk_merge',
        'l2max_scores_csr', 'ot_scores_csr', 'ot_rank_batch', 'dense_rank_batch', 'l2agg_pair_scores', 'l2agg_pair_backward',
        'ot_pair_scores', 'ot_pair_backward', 'jointsm_pair_scores', 'jointsm_pair_backward', 'l2sup_pair_scores', 'l2sup_pair_backward',
-       'span_mean_pool_backward', 'cls_l2_pair', 'cls_l2_pair_backward', 'bert_layers_train', 'bert_layers_backward',
+       'sent_cdist', 'sent_cdist_backward', 'span_mean_pool_backward', 'cls_l2_pair', 'cls_l2_pair_backward', 'bert_layers_train', 'bert_layers_backward',
        'bert_layers_train_dropout', 'bert_layers_backward_dropout', 'bert_dropout_mask', 'bert_layers_train_cls', 'bert_layers_backward_cls',
        'inbatch_xent', 'inbatch_xent_backward', 'bert_embed_sum', 'bert_embed_backward')

@@ -1,5 +1,6 @@
 """The reference's training loop (``GenericTrainer.__init__`` / ``.train()``, src/learning/trainer.py:100-359) restated over this
-project's pieces: a caller's encoder (``HipBertTrainEncoder`` is the intended one), ``RankLoss.forward_rank`` as the objective and
+project's pieces: a caller's encoder (``HipBertTrainEncoder`` is the intended one), ``RankLoss.forward_rank`` as the objective
+(``SupAlignRankLoss.forward_rank`` when ``model_hparams['model_name'] == 'sbalisentbienc'``) and
 ``HipAdam`` / ``HipAdagrad`` as the update, plus a checkpoint that resumes a run, which the reference lacks.
 
     trainer = RankTrainer(HipBertTrainEncoder(bert, dropout=True), model_hparams, train_hparams, model_path, train_batches, dev_batches)
@@ -26,8 +27,9 @@ The loss is recorded every 5 iterations (``loss_history`` / ``loss_checked_iters
 written when train() runs to its end.  Both files hold ``encoder.state_dict()``: HuggingFace's names with ``HipBertTrainEncoder``.
 
 ``save_checkpoint(path)`` / ``load_checkpoint(path)`` carry the encoder's, the optimizer's and the scheduler's state dicts, the
-iteration, the epoch and the position within it, the best dev score, the histories and ``encoder.dropout_state()`` where the encoder
-has one; ``train()`` of a trainer that loaded one continues there, skipping the batches the interrupted epoch had consumed (so
+iteration, the epoch and the position within it, the best dev score, the histories, ``encoder.dropout_state()`` where the encoder
+has one and the state of torch's global CPU generator (``torch.get_rng_state()``: the reference draws its in-batch negatives with
+``torch.randperm`` from it, so a resumed run draws the permutations the uninterrupted one would; ``load_checkpoint`` sets it); ``train()`` of a trainer that loaded one continues there, skipping the batches the interrupted epoch had consumed (so
 ``train_batches(epoch)`` must give an epoch's batches in the same order again).  ``train(max_iterations=n)`` returns after n more
 iterations without writing model_final.pt: the place to checkpoint.  With gradient accumulation a checkpoint can only be taken at an
 update boundary: half-accumulated gradients are not saved.
@@ -82,8 +84,10 @@ class RankTrainer:
             self.scheduler = make(optimizer=optimizer, num_warmup_steps=train_hparams['num_warmup_steps'],
                                   num_training_steps=self.total_iters)
         if loss_fn is None:
-            from .rank_loss import RankLoss
-            loss_fn = RankLoss(model_hparams).forward_rank
+            from .rank_loss import RankLoss, SupAlignRankLoss
+            # the reference's model_name (main_fsim.py): 'sbalisentbienc' is WordSentAbsSupAlignBiEnc, its loss SupAlignRankLoss
+            loss_cls = SupAlignRankLoss if model_hparams.get('model_name') == 'sbalisentbienc' else RankLoss
+            loss_fn = loss_cls(model_hparams).forward_rank
         self.loss_fn = loss_fn
 
         self.iteration, self.epoch, self.batch_in_epoch = 0, 0, 0
@@ -170,7 +174,8 @@ class RankTrainer:
                  'best_dev_score': self.best_dev_score, 'best_iter': self.best_iter,
                  'loss_history': dict(self.loss_history), 'loss_checked_iters': list(self.loss_checked_iters),
                  'dev_score_history': list(self.dev_score_history), 'dev_checked_iters': list(self.dev_checked_iters),
-                 'dropout_state': tuple(self.encoder.dropout_state()) if hasattr(self.encoder, 'dropout_state') else None}
+                 'dropout_state': tuple(self.encoder.dropout_state()) if hasattr(self.encoder, 'dropout_state') else None,
+                 'torch_rng_state': torch.get_rng_state()}
         torch.save(state, path)
 
     def load_checkpoint(self, path):
@@ -185,4 +190,6 @@ class RankTrainer:
         self.dev_score_history, self.dev_checked_iters = list(state['dev_score_history']), list(state['dev_checked_iters'])
         if state['dropout_state'] is not None:
             self.encoder.set_dropout_state(*state['dropout_state'])
+        if state.get('torch_rng_state') is not None:        # (absent in a checkpoint written before it was carried)
+            torch.set_rng_state(state['torch_rng_state'])
         self.optimizer.zero_grad()

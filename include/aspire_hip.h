@@ -949,6 +949,32 @@ int aspire_l2sup_backward_f32(const aspire_repset* q, const aspire_repset* c, in
                               float* grad_q_rows, float* grad_c_rows, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The cross-document distance matrix of the zero-padded sentence blocks, forward and backward: the
+ *   pair_sims = -1 * torch.cdist(q_sent_reps.permute(0, 2, 1), p_sent_reps.permute(0, 2, 1))
+ * of the two L1 regularisers, cd_l1_prop of WordSentAbsAlignBiEnc.forward_rank (disent_models.py:653-659) and cd_svalue_l1_prop of
+ * WordSentAbsSupAlignBiEnc.forward_rank (:826-835), without the sign, and what autograd sends back through it.  PAIRED only (pair p =
+ * query p with candidate p, q->n == c->n; no pairing argument) and padded sets only (ext > 0 on both, else ASPIRE_ERR_INVALID_ARG).
+ *   dist         [P, q.ext, c.ext] out: d_ij = ||q_i - c_j|| from the direct difference for EVERY i < q.ext, j < c.ext.  A row at
+ *                or beyond its document's length counts as the zero vector and is never read ("Pad values will be zeros", :654,
+ *                :828): a real row against a pad row gives the real row's norm, pad against pad exactly 0.0f.
+ *   grad_dist    [P, q.ext, c.ext] in: dLoss / dd.  torch.cdist's rule, A_ij = grad_dist_ij / d_ij and A_ij = 0 where d_ij == 0:
+ *                  grad_q_i = sum_j A_ij (q_i - c_j)    j ascending over all c.ext columns, pad columns (c_j = 0) included
+ *                  grad_c_j = sum_i A_ij (c_j - q_i)    i ascending over all q.ext rows
+ *                for the valid rows; pad rows (len <= r < ext) get exact zeros.  The backward forms d_ij again from the rows by the
+ *                forward's own loop (the same bits); it does not read the forward's output, so nothing has to be kept for it.
+ *   grad_q_rows, grad_c_rows, the alignment of the buffers and the error codes as aspire_l2sup_backward_f32: every row of every
+ *   document is written once with 16-byte stores, no atomics, no zero fill in front, the same bits on every run.  Documents of up
+ *   to aspire_max_sents() rows (the backward keeps the pair's 128 x 128 weights in 64 KiB of LDS).  A document longer than its
+ *   extent: NaN over the pair's whole dist block, NaN gradient rows, for that pair only.  One launch on `stream` each, one
+ *   workgroup per pair, no workspace.
+ * ------------------------------------------------------------------------------------------- */
+int aspire_sent_cdist_f32(const aspire_repset* q, const aspire_repset* c, int64_t D,
+                          float* dist /* [P, q.ext, c.ext] */, void* stream);
+int aspire_sent_cdist_backward_f32(const aspire_repset* q, const aspire_repset* c, int64_t D,
+                                   const float* grad_dist /* [P, q.ext, c.ext] */,
+                                   float* grad_q_rows, float* grad_c_rows, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * A15  precomputed-embedding rankers.  Replaces the per-query body of src/pre_process/pp_gen_nearest.py rank_pool (:683-717) and
  * rank_pool_faceted (:1166-1191): `all_doc_reps[pool_idxs, :]`, sklearn.neighbors.NearestNeighbors(algorithm='brute').fit on it and
  * kneighbors of the query row -- for J (query, pool) jobs in ONE call over ONE resident [N, 768] matrix of whole-document reps.
