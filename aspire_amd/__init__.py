@@ -13,6 +13,7 @@ from .train_encoder import HipBertTrainEncoder  # noqa: F401
 from .cls_train import BiEncTrain, ClsTripletLoss, IctEncTrain, IctLoss, SentEncTrain  # noqa: F401
 from .optim import HipAdam, HipAdagrad  # noqa: F401
 from .trainer import RankTrainer  # noqa: F401
+from .ddp import GradReducer, RankTrainerDDP, broadcast_parameters  # noqa: F401
 from .consent import AspireConSent  # noqa: F401
 from .contextner import AspireConSenContextual, AspireContextNER, AspireNER  # noqa: F401
 from .polyenc import WordSentAlignPolyEnc, TrainedScoringModel  # noqa: F401

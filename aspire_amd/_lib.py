@@ -89,6 +89,11 @@ class OptimTensor(ctypes.Structure):
                 ('step', c_int64), ('lr', c_double)]
 
 
+class GradTensor(ctypes.Structure):
+    """struct aspire_grad_tensor"""
+    _fields_ = [('grad', c_void_p), ('n', c_int64)]
+
+
 class AspireHipError(RuntimeError):
     pass
 
@@ -112,6 +117,10 @@ SIGNATURES = {
     'aspire_optim_workspace_bytes': (c_size_t, [c_int64]),
     'aspire_adam_step_f32': (c_int, [ctypes.POINTER(OptimTensor), c_int64, c_double, c_double, c_double, c_void_p, c_size_t, c_void_p]),
     'aspire_adagrad_step_f32': (c_int, [ctypes.POINTER(OptimTensor), c_int64, c_double, c_double, c_void_p, c_size_t, c_void_p]),
+    'aspire_grad_bucket_elems': (c_int64, [ctypes.POINTER(c_int64), c_int64, ctypes.POINTER(c_int64)]),
+    'aspire_grad_bucket_workspace_bytes': (c_size_t, [c_int64]),
+    'aspire_grad_bucket_pack_f32': (c_int, [ctypes.POINTER(GradTensor), c_int64, c_double, c_void_p, c_int64, c_void_p, c_size_t,
+                                            c_void_p]),
     'aspire_bert_planes_bytes': (c_size_t, [ctypes.POINTER(BertWeights)]),
     'aspire_bert_prepare_planes': (c_int, [ctypes.POINTER(BertWeights), c_void_p, c_size_t, c_void_p]),
     'aspire_bert_workspace_bytes': (c_size_t, [ctypes.POINTER(BertWeights), c_int64, c_int64]),

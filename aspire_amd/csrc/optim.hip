@@ -10,7 +10,8 @@
 // grid-stride over the global chunk list.  A workgroup finds its (tensor, offset) with a binary search over the prefix sum of chunk
 // counts -- wave-uniform, so scalar loads -- and nothing is looked up per element.  The table (one 64-byte record per tensor + the
 // prefix sums) lives in the caller's workspace: the host fills a pinned staging slot of the library and copies it there on the call's
-// stream, so the caller's descriptor array is dead when the call returns and the call does not wait for the stream.
+// stream, so the caller's descriptor array is dead when the call returns and the call does not wait for the stream.  The chunk list
+// and the staging ring are multi_tensor.h's, shared with grad_bucket.hip.
 //
 // Memory access.  A tensor whose four pointers are 16-byte aligned goes through 16-byte loads and stores (a chunk starts at a multiple
 // of 4 elements, so the alignment carries), its last 1-3 elements through a scalar tail; any other tensor (a view at an odd storage
@@ -18,10 +19,7 @@
 // same bits on every run.  Non-finite gradients propagate as the formulas say.
 #include <math.h>
 
-#include <mutex>
-
-#include "common.h"
-#include "tuning.h"
+#include "multi_tensor.h"
 
 namespace aspire {
 namespace {
@@ -78,13 +76,7 @@ __global__ void __launch_bounds__(256) optim_step_kernel(const OptimRec* __restr
                                                          int n_tensors, int total_chunks, OptimCoef k) {
     const int tid = threadIdx.x;
     for (int c = blockIdx.x; c < total_chunks; c += gridDim.x) {
-        // the tensor of chunk c: the last t with prefix[t] <= c (a tensor of no elements has no chunk and is never found)
-        int lo = 0, hi = n_tensors;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (prefix[mid] > c) hi = mid; else lo = mid + 1;
-        }
-        const int t = lo - 1;       // prefix[0] == 0 <= c: lo >= 1
+        const int t = chunk_tensor(prefix, n_tensors, c);
         const OptimRec r = recs[t];
         const int64_t off = (int64_t)(c - prefix[t]) * kOptimChunk;
         const int64_t left = r.n - off;
@@ -149,23 +141,6 @@ __global__ void __launch_bounds__(256) optim_step_kernel(const OptimRec* __restr
     }
 }
 
-// Pinned staging for the table: a ring of slots per device, each guarded by an event recorded behind its copy, so that a call neither
-// waits for its stream (a copy from pageable memory would) nor overwrites a table whose copy is still queued.  A slot is waited for
-// only when kRing steps are in flight at once.
-constexpr int kRing = 8, kMaxDevices = 64;
-struct Slot {
-    void* host = nullptr;
-    size_t cap = 0;
-    hipEvent_t done = nullptr;
-    bool pending = false;
-};
-struct Ring {
-    Slot slot[kRing];
-    unsigned next = 0;
-};
-Ring g_rings[kMaxDevices];
-std::mutex g_ring_mu;
-
 bool finite_nonneg(double x) { return isfinite(x) && x >= 0.0; }
 
 int optim_step(int rule, const char* who, const aspire_optim_tensor* tensors, int64_t n_tensors, double beta1, double beta2, double eps,
@@ -192,7 +167,7 @@ int optim_step(int rule, const char* who, const aspire_optim_tensor* tensors, in
                        "%s: tensor %lld has a null param / grad / state pointer with n = %lld", who, (long long)i, (long long)t.n);
         ASPIRE_REQUIRE((((uintptr_t)t.param | (uintptr_t)t.grad | (uintptr_t)t.state1 | (rule == kAdam ? (uintptr_t)t.state2 : 0)) & 3) == 0,
                        ASPIRE_ERR_INVALID_ARG, "%s: tensor %lld has a pointer that is not 4-byte aligned", who, (long long)i);
-        chunks += (t.n + kOptimChunk - 1) / kOptimChunk;
+        chunks += chunks_of(t.n);
         ASPIRE_REQUIRE(chunks < ((int64_t)1 << 31), ASPIRE_ERR_UNSUPPORTED, "%s: more than 2^31 chunks of %d elements", who, kOptimChunk);
     }
     const size_t need = table_bytes(n_tensors);
@@ -203,29 +178,10 @@ int optim_step(int rule, const char* who, const aspire_optim_tensor* tensors, in
     if (chunks == 0) return ASPIRE_OK;
 
     hipStream_t st = static_cast<hipStream_t>(stream);
-    int dev = 0;
-    ASPIRE_HIP_OK(hipGetDevice(&dev));
-    ASPIRE_REQUIRE(dev >= 0 && dev < kMaxDevices, ASPIRE_ERR_UNSUPPORTED, "%s: device %d beyond the %d staging rings", who, dev, kMaxDevices);
-    std::lock_guard<std::mutex> lock(g_ring_mu);
-    Ring& ring = g_rings[dev];
-    Slot& s = ring.slot[ring.next];
-    ring.next = (ring.next + 1) % kRing;
-    if (s.pending) {
-        ASPIRE_HIP_OK(hipEventSynchronize(s.done));
-        s.pending = false;
-    }
-    if (s.cap < need) {
-        if (s.host) ASPIRE_HIP_OK(hipHostFree(s.host));
-        s.host = nullptr;
-        s.cap = 0;
-        size_t cap = 16384;
-        while (cap < need) cap *= 2;
-        ASPIRE_HIP_OK(hipHostMalloc(&s.host, cap, hipHostMallocDefault));
-        s.cap = cap;
-    }
-    if (!s.done) ASPIRE_HIP_OK(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+    Staging staging;        // (multi_tensor.h: the pinned ring shared with the gradient bucket)
+    if (const int rc = staging.acquire(who, need)) return rc;
 
-    OptimRec* recs = static_cast<OptimRec*>(s.host);
+    OptimRec* recs = static_cast<OptimRec*>(staging.host());
     int32_t* prefix = reinterpret_cast<int32_t*>(recs + n_tensors);
     int32_t at = 0;
     for (int64_t i = 0; i < n_tensors; ++i) {
@@ -247,12 +203,10 @@ int optim_step(int rule, const char* who, const aspire_optim_tensor* tensors, in
         r.vec = (((uintptr_t)t.param | (uintptr_t)t.grad | (uintptr_t)t.state1 | (uintptr_t)r.s2) & 15) == 0;
         recs[i] = r;
         prefix[i] = at;
-        at += (int32_t)((t.n + kOptimChunk - 1) / kOptimChunk);
+        at += (int32_t)chunks_of(t.n);
     }
     prefix[n_tensors] = at;
-    ASPIRE_HIP_OK(hipMemcpyAsync(ws, s.host, need, hipMemcpyHostToDevice, st));
-    ASPIRE_HIP_OK(hipEventRecord(s.done, st));
-    s.pending = true;
+    if (const int rc = staging.commit(ws, st)) return rc;
 
     const OptimRec* d_recs = static_cast<const OptimRec*>(ws);
     const int32_t* d_prefix = reinterpret_cast<const int32_t*>(d_recs + n_tensors);

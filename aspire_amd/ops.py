@@ -906,6 +906,60 @@ def adagrad_step(params, grads, sums, steps, lrs, lr_decay=0.0, eps=1e-10):
     _optim_step('adagrad', (float(lr_decay), float(eps)), params, grads, sums, None, steps, lrs)
 
 
+GRAD_TABLE = np.dtype([('grad', 'u8'), ('n', 'i8')])
+assert GRAD_TABLE.itemsize == ctypes.sizeof(_lib.GradTensor)
+_GRAD_WS = {}       # (device index, stream handle) -> the device table of that stream's packs
+
+
+def grad_bucket_layout(numels):
+    """The gradient bucket's layout for tensors of `numels` elements (aspire_grad_bucket_elems; no device is touched) ->
+    (offsets, tail, total): tensor i takes [offsets[i], offsets[i] + numels[i]), every offset a multiple of 4; the tail of
+    round_up(len(numels), 4) floats starts at `tail`; `total` is the bucket's length."""
+    n = len(numels)
+    sizes = (ctypes.c_int64 * max(n, 1))(*[int(x) for x in numels])
+    offsets = (ctypes.c_int64 * max(n, 1))()
+    total = lib.aspire_grad_bucket_elems(sizes, n, offsets)
+    if total < 0:
+        raise ValueError(f'grad_bucket_layout: a negative element count in {list(numels)}')
+    return list(offsets[:n]), total - (n + 3) // 4 * 4, total
+
+
+def grad_bucket_pack(grads, flat, scale, numels=None):
+    """One aspire_grad_bucket_pack_f32 call on flat's device's current stream: grads[i] * scale into its region of `flat`, zeros for
+    a `None`, zeros in the pads, 1 / 0 per tensor in the tail (include/aspire_hip.h).  grads: dense contiguous fp32 GPU tensors on
+    flat's device (optim_tensor_check) or None; numels: every tensor's element count -- needed when a gradient is None, whose region
+    keeps its size; flat: a contiguous fp32 GPU tensor of grad_bucket_layout(numels)[2] elements."""
+    if numels is None:
+        if any(g is None for g in grads):
+            raise ValueError('grad_bucket_pack: an absent gradient keeps its region: pass numels')
+        numels = [g.numel() for g in grads]
+    optim_tensor_check(flat, 'flat')
+    n = len(grads)
+    if len(numels) != n:
+        raise ValueError(f'grad_bucket_pack: {len(numels)} element counts for {n} tensors')
+    for i, g in enumerate(grads):
+        if g is not None:
+            optim_tensor_check(g, f'grad {i}')
+            if g.device != flat.device or g.numel() != numels[i]:
+                raise ValueError(f'grad {i}: {g.numel()} elements on {g.device}, expected {numels[i]} on {flat.device}')
+    table = np.zeros(n, dtype=GRAD_TABLE)
+    table['n'] = [int(x) for x in numels]
+    dev = flat.device
+    with torch.cuda.device(dev):
+        handle = torch.cuda.current_stream().cuda_stream
+        key = (dev.index, handle)
+        ws = _GRAD_WS.get(key)
+        need = lib.aspire_grad_bucket_workspace_bytes(n)
+        if ws is None or ws.numel() < need:
+            ws = _GRAD_WS[key] = torch.empty(max(need, 16384), device=dev, dtype=torch.uint8)
+        # a tensor of no elements has no storage and a null data_ptr(): where the library wants an address that is never read -- a
+        # gradient of no elements that IS present, a bucket of no elements -- it gets the workspace's
+        table['grad'] = [0 if g is None else (g.data_ptr() or ws.data_ptr()) for g in grads]
+        check(lib.aspire_grad_bucket_pack_f32(ctypes.cast(table.ctypes.data, ctypes.POINTER(_lib.GradTensor)), n, float(scale),
+                                              flat.data_ptr() or ws.data_ptr(), flat.numel(), ws.data_ptr(), ws.numel(), handle))
+    return flat
+
+
 def selftest_xlane():
     require_gpu()
     n = (ctypes.c_int * 16)()

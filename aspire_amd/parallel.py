@@ -56,6 +56,18 @@ def all_gather_flat(out, inp, group=None):
     return out
 
 
+def all_reduce_flat(t, group=None):
+    """dist.all_reduce(t, SUM) in place, on either backend (_through_host): RCCL sums a GPU tensor where it lies; under gloo a GPU
+    tensor goes to the host, is summed there and comes back.  Returns t."""
+    if _through_host(t, group):
+        host = t.cpu()
+        dist.all_reduce(host, op=dist.ReduceOp.SUM, group=group)
+        t.copy_(host)
+    else:
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    return t
+
+
 def merge_topk(scores, idx, k):
     """scores/idx [Q, M] candidates from all shards (idx = global ids, -1 = padding) ->
     (top scores [Q, k], top idx [Q, k]) descending, ties by ascending global index.

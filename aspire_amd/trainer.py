@@ -34,6 +34,9 @@ has one and the state of torch's global CPU generator (``torch.get_rng_state()``
 iterations without writing model_final.pt: the place to checkpoint.  With gradient accumulation a checkpoint can only be taken at an
 update boundary: half-accumulated gradients are not saved.
 
+Data-parallel training (the reference's ``GenericTrainerDDP``) is ``aspire_amd.ddp.RankTrainerDDP``, a subclass: it overrides ``_step``
+(reduce the gradients over the ranks, then update), ``_dev_check`` / ``_record_loss`` / ``_save_model`` (rank 0 only) and ``train``.
+
 ``loss_fn(batch, encoder) -> scalar`` and ``optimizer`` replace the two GPU pieces, which makes the host logic testable without one.
 """
 import logging
@@ -117,32 +120,39 @@ class RankTrainer:
         self.loss_history['loss'].append(float(objective.detach()))
         self.loss_checked_iters.append(self.iteration)
 
+    def _step(self):
+        """the update from the gradients in .grad (RankTrainerDDP reduces them over the ranks first)"""
+        self.optimizer.step()
+
+    def _dev_check(self, objective):
+        self._record_loss(objective)
+        dev_score = -1.0 * self.dev_loss()
+        self.dev_score_history.append(dev_score)
+        self.dev_checked_iters.append(self.iteration)
+        if dev_score > self.best_dev_score:
+            self.best_dev_score, self.best_iter = dev_score, self.iteration
+            self._save_model('cur_best')
+
     def _iterate(self, batch):
         self.encoder.train()
         if self.accumulate_gradients:
             objective = self.loss_fn(batch, self.encoder)
             objective.backward()
             if (self.iteration + 1) % self.update_params_every == 0:
-                self.optimizer.step()
+                self._step()
                 self.optimizer.zero_grad()
         else:
             self.optimizer.zero_grad()
             objective = self.loss_fn(batch, self.encoder)
             objective.backward()
-            self.optimizer.step()
+            self._step()
         if self.iteration % LOG_EVERY == 0:
             self._record_loss(objective)
         # The decay_lr_every doesnt need to be a multiple of self.log_every
         if self.iteration > 0 and self.iteration % self.decay_lr_every == 0:
             self.scheduler.step()
         if self.iteration % self.es_check_every == 0 and self.iteration != 0 and self.early_stop:
-            self._record_loss(objective)
-            dev_score = -1.0 * self.dev_loss()
-            self.dev_score_history.append(dev_score)
-            self.dev_checked_iters.append(self.iteration)
-            if dev_score > self.best_dev_score:
-                self.best_dev_score, self.best_iter = dev_score, self.iteration
-                self._save_model('cur_best')
+            self._dev_check(objective)
         self.iteration += 1
 
     def train(self, max_iterations=None):

@@ -451,6 +451,43 @@ int aspire_adagrad_step_f32(const aspire_optim_tensor* tensors, int64_t n_tensor
                             size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The gradient bucket of data-parallel training (the reference trains through DistributedDataParallel, main_fsim.py ddp_train_model):
+ * every gradient of a step packed and scaled into ONE flat fp32 buffer in one launch, so that one all-reduce sums it across the ranks
+ * and the optimizer step above reads the reduced gradients where they lie.
+ *   Layout       the library's, the same for every caller: tensor i takes [offsets[i], offsets[i] + n_i) with offsets[0] = 0 and
+ *                offsets[i + 1] = offsets[i] + round_up(n_i, 4), so every offset is a multiple of 4 elements; behind the last region
+ *                comes a tail of round_up(n_tensors, 4) floats.  aspire_grad_bucket_elems returns the total (the tail starts at
+ *                total - round_up(n_tensors, 4)) and fills offsets[n_tensors] when it is not NULL; -1 for n_tensors < 0, a negative
+ *                n, or n NULL with n_tensors > 0.  No device is touched.
+ *   pack         flat[offsets[i] + j] = grad_i[j] * (float)scale -- ONE fp32 multiply, never contracted: torch's reducer arithmetic
+ *                mul_out(bucket_view, grad, 1 / world) -- zeros where grad_i == NULL (no gradient on this rank), zeros in every pad
+ *                element; flat[tail + i] = grad_i ? 1.0f : 0.0f, unscaled, zeros in the tail's pad: summed over the ranks, the
+ *                tail holds the number of ranks that had a gradient for each tensor.  Every element of [flat, flat + flat_elems)
+ *                has exactly one writer, nothing outside it is touched, no atomics, no zero fill in front, the same bits on every
+ *                run and wherever a gradient's storage starts.  Non-finite gradients propagate as the multiply says.
+ *   tensors[i]   grad: n fp32 elements on the device, 4-byte aligned (16-byte aligned ones are read with 16-byte loads), or NULL
+ *   flat         flat_elems fp32 elements on the device, 16-byte aligned; flat_elems must equal aspire_grad_bucket_elems
+ *   workspace    device memory of at least aspire_grad_bucket_workspace_bytes(n_tensors) bytes, 16-byte aligned; the rules of the
+ *                optimizer step's workspace apply (the table is copied there on `stream` from pinned staging of the library; the
+ *                call does not wait for the stream; not capturable into a graph)
+ * Errors, all before the device is touched, the offending value in aspire_last_error(): ASPIRE_ERR_INVALID_ARG for n_tensors < 0; a
+ * NULL table with n_tensors > 0; a scale that is not finite (as a float); flat NULL or not 16-byte aligned; a tensor with n < 0 or a
+ * gradient pointer that is not 4-byte aligned; flat_elems other than aspire_grad_bucket_elems; a gradient that overlaps
+ * [flat, flat + flat_elems) (a gradient that already lives in the bucket: the reduction ran twice on the same gradients); a
+ * workspace that is NULL, too small or not 16-byte aligned.  ASPIRE_ERR_UNSUPPORTED beyond 2^30 chunks of 4096 elements.
+ * n_tensors == 0 (flat_elems == 0) -> ASPIRE_OK without a launch.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {
+    const float* grad;   /* NULL: no gradient on this rank */
+    int64_t      n;
+} aspire_grad_tensor;
+
+int64_t aspire_grad_bucket_elems(const int64_t* n, int64_t n_tensors, int64_t* offsets);
+size_t aspire_grad_bucket_workspace_bytes(int64_t n_tensors);
+int aspire_grad_bucket_pack_f32(const aspire_grad_tensor* tensors, int64_t n_tensors, double scale, float* flat, int64_t flat_elems,
+                                void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * caching_score's document-level term (src/learning/facetid_models/disent_models.py:305-307, taken when
  * abs_loss_prop > 0): functional.pairwise_distance(query_cls_reps, cand_cls_reps, p=2.0) = ||q - c + eps||_2 with torch's
  * eps = 1e-6 added to every coordinate of the difference.  (The caller negates and scales it.)
