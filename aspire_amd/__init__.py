@@ -14,6 +14,9 @@ from .cls_train import BiEncTrain, ClsTripletLoss, IctEncTrain, IctLoss, SentEnc
 from .optim import HipAdam, HipAdagrad  # noqa: F401
 from .trainer import RankTrainer  # noqa: F401
 from .ddp import GradReducer, RankTrainerDDP, broadcast_parameters  # noqa: F401
+from .batchers import JsonlRankBatches, rank_batch_sources, write_shuffled_copies  # noqa: F401
+from .align import (align_cocited, alignment_encoder, context_set, random_neg_sampler,  # noqa: F401
+                    write_aligned_examples)
 from .consent import AspireConSent  # noqa: F401
 from .contextner import AspireConSenContextual, AspireContextNER, AspireNER  # noqa: F401
 from .polyenc import WordSentAlignPolyEnc, TrainedScoringModel  # noqa: F401

@@ -613,6 +613,26 @@ def dotmax_rank_batch(q, c, job_off, max_job, k, sim=_lib.SIM_COSINE, out=None, 
     return _rank_batch('dotmax', lambda: (sim,), q, c, job_off, max_job, k, out, workspace, job_base, key_form)
 
 
+def dot_argmax(q, c, want_best=True, out=None):
+    """A16 (pre_proc_cocits.py:487-494): for the PAIRED pairs, arg int32 [P, 2] = np.unravel_index(np.matmul(q, c.T).argmax(),
+    (q_len, c_len)) with numpy's rule in full (first maximum in row-major order, +-0.0 tie, the first NaN wins) and best [P] = the
+    dot product there, the bits of dotmax_scores(q, c, PAIR_PAIRED, SIM_DOT).  Non-finite rows are inside the contract; a document
+    without rows raises ValueError, as numpy's argmax of an empty block does.  want_best=False passes best = NULL and returns
+    (arg, None); out: the (arg, best) buffers to write into instead of new ones."""
+    if q.n != c.n:
+        raise AssertionError(f'paired arg-max needs equal batch sizes (query {q.n} vs cand {c.n})')
+    for s in (q, c):
+        if s.n and (min(s.lens_host) if s.lens_host is not None else int(s.len.min())) <= 0:
+            raise ValueError('attempt to get argmax of an empty sequence: a document without sentence rows')
+    dev = q.rows.device
+    arg, best = out if out is not None else (torch.empty(q.n, 2, device=dev, dtype=torch.int32),
+                                             torch.empty(q.n, device=dev, dtype=torch.float32) if want_best else None)
+    assert _i32(arg, 'arg').numel() >= 2 * q.n and (best is None or _f32(best, 'best').numel() >= q.n)
+    qs, cs = q.struct(), c.struct()
+    check(lib.aspire_dot_argmax_f32(ctypes.byref(qs), ctypes.byref(cs), D, _ptr(arg), _ptr(best), _stream()))
+    return arg, best
+
+
 def jointsm_scores(q, c, pairing=_lib.PAIR_CROSS, want_pair_softmax=False):
     """A14 (pair_distances.py:348-402 as WordSentAlignPolyEnc.score negates it back, disent_models.py:905-906): sims [P] =
     2 sum_ij p_ij <q_i, c_j> with p the soft-max of the scaled dot products over the pair's whole valid block.  With

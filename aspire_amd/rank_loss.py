@@ -11,7 +11,7 @@ aspire_amd.HipBertTrainEncoder(bert_model) as the `encoder` argument (an instanc
 twelve layers and the embedding LayerNorm run forward and backward on this project's kernels (encoder_bwd.hip) and only the embedding
 table lookup is torch's; a HuggingFace model called under torch autograd brings torch's.  Dropout is that encoder's (dropout=True), the
 parameter update aspire_amd.HipAdam / HipAdagrad, the loop around all three aspire_amd.RankTrainer; the batch dicts come from
-aspire_amd.batch_prep.make_batch, the jsonl streaming batchers are not built (data-parallel training: aspire_amd/ddp.py).
+aspire_amd.batch_prep.make_batch, streamed from the jsonl files by aspire_amd.batchers (data-parallel training: aspire_amd/ddp.py).
 
 SupAlignRankLoss is the same for WordSentAbsSupAlignBiEnc.forward_rank (disent_models.py:750-837, model_name 'sbalisentbienc'): the
 hinge over the supervised-alignment distance of the batch's pre-aligned sentences (torch.ops.aspire.l2sup_pair_scores) in front of the

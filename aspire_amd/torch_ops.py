@@ -65,6 +65,10 @@ implementation so that shapes propagate under FakeTensor / torch.compile tracing
     torch.ops.aspire.l2max_scores_csr / ot_scores_csr(q_rows, q_start, q_len, q_max, c_rows, c_start, c_len, c_max, ...) -> [Q * C]
     torch.ops.aspire.ot_rank_batch(q_rows, q_start, q_len, q_max, c_rows, c_start, c_len, c_max, job_off, max_job, k, ...)
                                          -> (scores [C], top_scores [J, k], top_idx [J, k])        evaluate.py:58-76, batched
+    torch.ops.aspire.dot_argmax(q_rows, q_start, q_len, c_rows, c_start, c_len, q_bound, c_bound)
+                                         -> (arg int32 [P, 2], best [P])                           A16  pre_proc_cocits.py:487-494
+                                         (a data-preparation op: it reads min(q_len) and min(c_len) back before the launch -- two
+                                         blocking device syncs -- to raise ValueError on a document without rows, as numpy does)
   one resident [N, 768] matrix of whole-document reps, jobs as row-index lists:
     torch.ops.aspire.dense_rank_batch(rows, q_idx, cand_idx, job_off, max_job, k, metric)
                                          -> (scores [C], top_scores [J, k], top_idx [J, k])        A15  pp_gen_nearest.py:683-717
@@ -366,6 +370,18 @@ def ot_rank_batch(q_rows: Tensor, q_start: Tensor, q_len: Tensor, q_max: int, c_
 def _(q_rows, q_start, q_len, q_max, c_rows, c_start, c_len, c_max, job_off, max_job, k, blur, scaling, temp, want):
     j = q_start.shape[0]
     return (q_rows.new_empty(c_start.shape[0]), q_rows.new_empty(j, k), q_rows.new_empty(j, k, dtype=torch.int64))
+
+
+@torch.library.custom_op('aspire::dot_argmax', mutates_args=(), device_types='cuda')
+def dot_argmax(q_rows: Tensor, q_start: Tensor, q_len: Tensor, c_rows: Tensor, c_start: Tensor, c_len: Tensor, q_bound: int,
+               c_bound: int) -> Tuple[Tensor, Tensor]:
+    return ops.dot_argmax(_csr_repset(q_rows, q_start, q_len, q_bound), _csr_repset(c_rows, c_start, c_len, c_bound))
+
+
+@dot_argmax.register_fake
+def _(q_rows, q_start, q_len, c_rows, c_start, c_len, q_bound, c_bound):
+    p = q_start.shape[0]
+    return q_rows.new_empty(p, 2, dtype=torch.int32), q_rows.new_empty(p)
 
 
 @torch.library.custom_op('aspire::dense_rank_batch', mutates_args=(), device_types='cuda')
@@ -881,7 +897,7 @@ def _(seed, step, site, p, first, n):
 
 
 OPS = ('span_mean_pool', 'span_pool_ranges', 'bert_encoder_forward', 'bert_cls_forward', 'bert_pooler', 'token_mean_pool', 'l2max_scores', 'jointsm_scores', 'ot_sinkhorn_scores', 'topk_desc', 'topk_keys', 'topk_merge',
-       'l2max_scores_csr', 'ot_scores_csr', 'ot_rank_batch', 'dense_rank_batch', 'l2agg_pair_scores', 'l2agg_pair_backward',
+       'l2max_scores_csr', 'ot_scores_csr', 'ot_rank_batch', 'dot_argmax', 'dense_rank_batch', 'l2agg_pair_scores', 'l2agg_pair_backward',
        'ot_pair_scores', 'ot_pair_backward', 'jointsm_pair_scores', 'jointsm_pair_backward', 'l2sup_pair_scores', 'l2sup_pair_backward',
        'sent_cdist', 'sent_cdist_backward', 'span_mean_pool_backward', 'cls_l2_pair', 'cls_l2_pair_backward', 'bert_layers_train', 'bert_layers_backward',
        'bert_layers_train_dropout', 'bert_layers_backward_dropout', 'bert_dropout_mask', 'bert_layers_train_cls', 'bert_layers_backward_cls',

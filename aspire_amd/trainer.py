@@ -6,8 +6,9 @@ project's pieces: a caller's encoder (``HipBertTrainEncoder`` is the intended on
     trainer = RankTrainer(HipBertTrainEncoder(bert, dropout=True), model_hparams, train_hparams, model_path, train_batches, dev_batches)
     trainer.train()
 
-``train_batches(epoch)`` / ``dev_batches()`` return iterables of the reference's ``batch_rank`` dicts (the jsonl batchers stay the
-caller's).  ``train_hparams`` has the reference's keys and rules, quirks included:
+``train_batches(epoch)`` / ``dev_batches()`` return iterables of the reference's ``batch_rank`` dicts
+(``aspire_amd.batchers.rank_batch_sources`` gives both over the jsonl files of 'miswordbienc' / 'miswordpolyenc' / 'sbalisentbienc'; the
+CLS-row models' batches stay the caller's).  ``train_hparams`` has the reference's keys and rules, quirks included:
 
   update_rule             'adam' -> HipAdam, 'adagrad' -> HipAdagrad, at ``learning_rate``; anything else raises ValueError
   train_size, batch_size, num_epochs

@@ -906,6 +906,24 @@ int aspire_dotmax_rank_batch_f32(const aspire_repset* q, const aspire_repset* c,
                                  size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * A16  the alignment step of the co-citation data path.  Replaces the np.matmul(...).argmax() calls of
+ * generate_examples_aligned_cocitabs_rand, src/pre_process/pre_proc_cocits.py:487-494 (three per training example), over
+ * documents that are (start, len) views into resident row matrices.
+ *   PAIRED only: P = q->n == c->n (else ASPIRE_ERR_INVALID_ARG).  For pair p with s_ij = <q_i, c_j>, i < q_len, j < c_len:
+ *   arg  [P, 2] out: (i, j) = np.unravel_index(np.matmul(q, c.T).argmax(), (q_len, c_len)) -- numpy's rule in full: the first
+ *                   maximum in row-major order of [q_len, c_len]; -0.0 and +0.0 tie; a NaN counts as the maximum and the first
+ *                   NaN wins; a block of all -inf gives (0, 0).
+ *   best [P] out, or NULL: s_ij at that entry -- the bits aspire_dotmax_scores_f32(..., ASPIRE_PAIR_PAIRED, ASPIRE_SIM_DOT) gives
+ *                   the pair on NaN-free input (the same products on v_mfma_f32_16x16x4_f32, four accumulators over k; where the
+ *                   maximum is a zero, the picked entry's sign).
+ *   A document longer than its host bound (ext, or max_len): arg = (-1, -1), best = NaN.  A pair with a document of no rows:
+ *   arg = (-1, -1), best = -inf.  D must be 768, rows 16-byte aligned, documents of up to aspire_max_sents() rows, as A13.  The
+ *   planes and doc_box fields are ignored.  One launch on `stream`, one wave per pair; no atomics: every output has one writer,
+ *   so every run gives the same bits.  P == 0: ASPIRE_OK, nothing is touched.
+ * ------------------------------------------------------------------------------------------- */
+int aspire_dot_argmax_f32(const aspire_repset* q, const aspire_repset* c, int64_t D, int32_t* arg, float* best, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * A14  miswordpolyenc joint soft-max alignment ('jointsm').  Replaces pair_distances.allpair_joint_sm_negscore,
  * src/learning/facetid_models/pair_distances.py:348-402 with the mask of models_common/activations.py:35-61, as
  * WordSentAlignPolyEnc.score calls it (disent_models.py:877-925) under TrainedScoringModel.predict and its ranking callers
