@@ -29,6 +29,8 @@ OT_DISTANCE, OT_PLAN_SIM, OT_SIMILARITY = 0, 1, 2
 AGG_MAX, AGG_TOP2, AGG_ATTENTION = 0, 1, 2
 SIM_COSINE, SIM_DOT = 0, 1
 DENSE_L2, DENSE_COSINE, DENSE_DOT = 0, 1, 2
+FORM_L2AGG, FORM_OT, FORM_OT_BATCH, FORM_L2MAX_BATCH = 0, 1, 2, 3      # aspire_debug_score_form: kind
+ASKED_PAIR_OUTPUTS, ASKED_DIAMETERS, ASKED_COST_ONLY, ASKED_PLAN_SIM, ASKED_AGG_OTHER, ASKED_ONE_FORM = 1, 2, 4, 8, 16, 32
 
 
 class RepPlanes(ctypes.Structure):
@@ -221,6 +223,8 @@ SIGNATURES = {
                                             c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     'aspire_debug_set': (c_int, [ctypes.c_char_p, ctypes.c_char_p]),
     'aspire_debug_get': (c_int, [ctypes.c_char_p, ctypes.c_char_p, c_size_t]),
+    'aspire_debug_score_form': (c_int, [c_int, ctypes.POINTER(RepSet), ctypes.POINTER(RepSet), c_int, ctypes.POINTER(OtParams), c_int,
+                                        c_size_t, ctypes.c_char_p, c_size_t]),
     'aspire_debug_ot_cost_stage_f32': (c_int, [ctypes.POINTER(RepSet), ctypes.POINTER(RepSet), c_int64, c_int,
                                                ctypes.POINTER(OtParams), c_void_p, c_void_p, c_size_t, c_void_p]),
     'aspire_debug_ot_rank_batch_stages_f32': (c_int, [ctypes.POINTER(RepSet), ctypes.POINTER(RepSet), c_int64, c_void_p, c_int64,

@@ -17,6 +17,7 @@
 
 #include "common.h"
 #include "tuning.h"
+#include "forms.h"
 #include "score_types.h"
 #include "score_device.h"
 #include "exact_d2.h"
@@ -1045,61 +1046,35 @@ int launch_doc_box(const RepSet& d, float* box, hipStream_t stream) {
 // (MAPPED pairing: the whole batch, or with `tile_blocks` > 0 the jobs [a.job0, a.job1) on the throughput kernel.)
 int launch_cost_stage(const ScoreArgs& a, int T_rt, const aspire_repset* q, const aspire_repset* c, float* cost, float* neg, float* diam2,
                       int64_t n_slots, int qchunks, bool gram, float* qbox, float* cbox, bool first_chunk, hipStream_t stream) {
-    const bool csr = q->ext == 0 && c->ext == 0;
-    if (gram) {
-        // many queries or long documents: Gram tiles on the matrix cores (gram.hip)
+    // which kernel: forms.hip
+    const CostChoice ch = cost_kernel_form(T_rt, q, c, a.pairing, gram, a.tile_form != 0, a.grp_off != nullptr, a.cand1 - a.cand0,
+                                           a.job1 - a.job0, a.max_job_groups, n_slots);
+    if (ch.kernel == CostKernel::Gram)
         return launch_pair_gram_ot(a, T_rt, q->max_len, c->max_len, cost, neg, a.diameter ? nullptr : diam2, qbox, cbox, stream);
-    }
+    // the streaming kernels take the per-coordinate boxes of the queries, once per call (MAPPED: the tables launch wrote them)
+    if ((ch.kernel == CostKernel::Tile || ch.kernel == CostKernel::Tile16) && !a.diameter && first_chunk && a.pairing != kPairMapped)
+        if (int rc = launch_doc_box(a.q, qbox, stream)) return rc;
+    if (ch.kernel == CostKernel::Tile16) return launch_pair_tile16(a, cost, neg, diam2, ch.items, qbox, stream);
     return dispatch_T(8 * T_rt, [&](auto tc) -> int {
         constexpr int T = decltype(tc)::value;
         const PairWs<T> ws{cost, neg, diam2};
-        if (T == 1 && csr) {
-            PairWs<1> ws1{ws.cost, ws.neg, ws.diam2};
-            const int64_t ncand = a.cand1 - a.cand0;
-            // groups of four candidates x queries (MAPPED: an upper bound; the kernel reads the exact range from grp_off)
-            const int64_t groups4 = a.pairing == kPairMapped ? (int64_t)(a.job1 - a.job0) * a.max_job_groups
-                                                             : (ncand + 3) / 4 * (a.pairing == ASPIRE_PAIR_CROSS ? q->n : 0);
-            const int form_t = tuning().ot_form;
-            const bool tile = a.pairing == kPairMapped ? a.tile_form
-                                                       : (a.pairing == ASPIRE_PAIR_CROSS && (form_t == 2 || (form_t != 1 && groups4 >= 2048)));
-            if (tile) {
-                // enough groups of 4 candidates to fill the chip: tiled form (lanes own finished (i,j) sums), one group per
-                // wave (measured 4.7 TB/s algorithmic at 1 x 20 000 against 1.8 TB/s for the accumulate-then-reduce kernel)
-                if (!a.diameter && first_chunk && a.pairing != kPairMapped)     // per-coordinate boxes of the queries, once per call
-                    if (int rc = launch_doc_box(a.q, qbox, stream)) return rc;
-                const int64_t wave_cap = tuning().tile_waves > 0 ? tuning().tile_waves : 256 * 8;      // TILE_WAVES: tests with several items per wave
-                const int64_t waves = groups4 < wave_cap ? groups4 : wave_cap;
-                hipLaunchKernelGGL(pair_tile_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256),
-                                   4 * TileCfg::kLdsFloats * sizeof(float), stream, a, ws1, qbox);
-            } else {
-                // small grids are latency bound: three waves per pair (a third of the coordinates each), persistent and
-                // software pipelined (measured 15.6 us per launch at 50-250 pairs against 20-23 us for the tiled form with its
-                // stages split over three or four waves).  One pair per workgroup up to 2048 pairs (at ~1000 pairs it beats
-                // 512 persistent workgroups with two each, alone and beside other launches); beyond, 512 persistent
-                // workgroups = what is resident at two per CU.
-                const int cap_t = tuning().cost1_blocks;
-                const int64_t cap = cap_t > 0 ? cap_t : (n_slots <= 2048 ? 2048 : 512);
-                const int64_t blocks = n_slots < cap ? n_slots : cap;
-                hipLaunchKernelGGL(pair_cost1_kernel, dim3((unsigned)blocks), dim3(kBlock), Lds<1>::kTotal * sizeof(float), stream, a,
-                                   ws1, 1u);
-            }
-        } else if (T == 2 && tile16_path_ok(q, c, a.pairing) && (a.pairing != kPairMapped || a.grp_off != nullptr) &&
-                   tuning().ot_form != 1 &&
-                   (tuning().ot_form == 2 || (a.pairing == kPairMapped ? 2 * (int64_t)(a.job1 - a.job0) * a.max_job_groups
-                                                                          : (a.cand1 - a.cand0 + 1) / 2 * q->n) >= 2048)) {
-            // documents of 9 .. 16 rows, enough pairs of candidates to fill the chip: the streaming kernel (tile16.hip)
-            if (!a.diameter && first_chunk && a.pairing != kPairMapped)     // per-coordinate boxes of the queries, once per call
-                if (int rc = launch_doc_box(a.q, qbox, stream)) return rc;
-            const int64_t items = a.pairing == kPairMapped ? 2 * (int64_t)(a.job1 - a.job0) * a.max_job_groups
-                                                           : (a.cand1 - a.cand0 + 1) / 2 * q->n;
-            return launch_pair_tile16(a, ws.cost, ws.neg, ws.diam2, items, qbox, stream);
-        } else if (csr && n_slots < 512) {
-            // CSR documents of more than 8 rows: every 8 x 8 sub-tile of every pair is an item of the small-pool kernel
-            // while the pairs alone would not fill the chip (1 x 125 x 20: 125 workgroups walking 9 tiles each -> 1024
-            // side by side, 54 -> 36 us; from ~1000 pairs the per-pair kernel is ahead again)
-            PairWs<1> ws1{ws.cost, ws.neg, ws.diam2};
-            const int64_t items = n_slots * T * T;
-            hipLaunchKernelGGL(pair_cost1_sub_kernel, dim3((unsigned)(items < 1024 ? items : 1024)), dim3(kBlock),
+        const PairWs<1> ws1{cost, neg, diam2};
+        const bool csr = q->ext == 0 && c->ext == 0;
+        if (ch.kernel == CostKernel::Tile) {
+            const int64_t wave_cap = tuning().tile_waves > 0 ? tuning().tile_waves : 256 * 8;      // TILE_WAVES: tests with several items per wave
+            const int64_t waves = ch.items < wave_cap ? ch.items : wave_cap;
+            hipLaunchKernelGGL(pair_tile_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256),
+                               4 * TileCfg::kLdsFloats * sizeof(float), stream, a, ws1, qbox);
+        } else if (ch.kernel == CostKernel::Cost1) {
+            // One pair per workgroup up to 2048 pairs (at ~1000 pairs it beats 512 persistent workgroups with two each, alone
+            // and beside other launches); beyond, 512 persistent workgroups = what is resident at two per CU.
+            const int cap_t = tuning().cost1_blocks;
+            const int64_t cap = cap_t > 0 ? cap_t : (n_slots <= 2048 ? 2048 : 512);
+            const int64_t blocks = n_slots < cap ? n_slots : cap;
+            hipLaunchKernelGGL(pair_cost1_kernel, dim3((unsigned)blocks), dim3(kBlock), Lds<1>::kTotal * sizeof(float), stream, a,
+                               ws1, 1u);
+        } else if (ch.kernel == CostKernel::Cost1Sub) {
+            hipLaunchKernelGGL(pair_cost1_sub_kernel, dim3((unsigned)(ch.items < 1024 ? ch.items : 1024)), dim3(kBlock),
                                Lds<1>::kTotal * sizeof(float), stream, a, ws1, (uint32_t)T);
         } else if (csr && a.center) {        // rows with a large common component: the same kernel on centred rows
             hipLaunchKernelGGL((pair_cost_kernel<T, false, true>), dim3((unsigned)(a.cand1 - a.cand0), (unsigned)qchunks, 1), dim3(kBlock),

@@ -111,22 +111,7 @@ __global__ void __launch_bounds__(256, ASPIRE_FUSED_MIN_WAVES) pair_solve16_kern
 
 }  // namespace
 
-// batched jobs: few enough jobs for the in-wave tables (one lane per job), and hyper-parameters at which overflowed sums (each
-// re-solved by the wave that finds it) stay the exception
-bool fused_self_ok(int64_t jobs, const aspire_ot_params* prm) {
-    return jobs <= 64 && prm->scaling >= 0.25 && tuning().fused_nosolve != 1 && !tuning().fused_valu && !tuning().fused_noself;
-}
-
-// one query against a pool with its own per-pair diameters: the box comes from the staged query rows (no box launch)
-bool fused_inbox_ok(const aspire_repset* q, const float* diameter) {
-    return q->n == 1 && diameter == nullptr && tuning().fused_nosolve != 1 && !tuning().fused_valu && !tuning().fused_noself;
-}
-
-bool fused_path_ok(const aspire_repset* q, const aspire_repset* c) {
-    const int mq = q->max_len, mc = c->max_len;
-    return q->ext == 0 && c->ext == 0 && mq > 0 && mc > 0 && mq <= 8 && mc <= 8;
-}
-
+// (when a call takes which form of the kernel: forms.hip -- fused_path_ok, fused_self_ok, fused_inbox_ok)
 // tsAspire (max-sim) of every (query, candidate) pair, CROSS, documents of <= 8 rows: the fused kernel's streaming phase
 // self (batched jobs, <= 64 of them): no tables in front of the launch -- the waves derive an item's job from job_off (SELF)
 int launch_pair_fused_l2max(const ScoreArgs& a, int64_t groups_bound, hipStream_t stream, bool self) {

@@ -28,6 +28,7 @@
 #include <type_traits>
 
 #include "tuning.h"
+#include "forms.h"
 #include "score_types.h"
 #include "score_device.h"
 #include "exact_d2.h"
@@ -680,10 +681,7 @@ int launch_pair_box(const float* qbox, const float* cbox, uint32_t nq, uint32_t 
     return ASPIRE_OK;
 }
 
-int slot_rows(int max_len) {
-    const int r = (max_len + 3) / 4 * 4;
-    return r < 8 ? 8 : r;
-}
+static_assert(kBM == kGramCandRows, "forms.hip counts candidate tiles of kBM rows");
 
 int fill_geometry(GramArgs& g, const ScoreArgs& a, int mr_q, int mr_c, int& bn) {
     g.q = a.q;
@@ -691,8 +689,8 @@ int fill_geometry(GramArgs& g, const ScoreArgs& a, int mr_q, int mr_c, int& bn) 
     g.cand0 = a.cand0;
     g.ncand = (uint32_t)(a.cand1 - a.cand0);
     g.nq = (uint32_t)a.q.n;
-    g.mr_q = slot_rows(mr_q);
-    g.mr_c = slot_rows(mr_c);
+    g.mr_q = gram_slot_rows(mr_q);
+    g.mr_c = gram_slot_rows(mr_c);
     const int64_t qrows = (int64_t)g.nq * g.mr_q;
     bn = qrows <= 32 ? 32 : qrows <= 64 ? 64 : 128;
     g.dpt_c = kBM / g.mr_c;
@@ -737,52 +735,7 @@ int launch_gram(const GramArgs& g, int bn, hipStream_t stream) {
 
 }  // namespace
 
-// The matrix-core form serves CSR inputs (no padded extents) scored all-against-all, once the query side fills
-// a useful part of an MFMA tile or documents are longer than the 8-row VALU tile.
-// Max-sim on the fp16-plane tiles whatever the number of queries: both rep sets carry planes around one centre, the pool fills the
-// chip (>= 128 candidate tiles), and it is not the one case the streaming kernel wins (ONE query of <= 8 rows against documents of
-// <= 8: the fused kernel's max-sim form reads each row once at 6 TB/s and has no wasted columns -- 81 against 95 us at 1 x 20 000 x 8)
-bool gram_planes_wanted_l2max(const aspire_repset* q, const aspire_repset* c, int pairing) {
-    if (pairing != ASPIRE_PAIR_CROSS || q->ext != 0 || c->ext != 0 || !q->planes || !c->planes) return false;
-    if (q->max_len <= 0 || c->max_len <= 0 || q->max_len > 32 || c->max_len > 32) return false;
-    if (tuning().cost_path == 2 || tuning().gemm_form == 1 || tuning().gemm_form == 2) return false;
-    if (q->planes->mu != c->planes->mu || !q->planes->planes || !c->planes->planes) return false;
-    const int64_t tiles = (c->n + kBM / slot_rows(c->max_len) - 1) / (kBM / slot_rows(c->max_len));
-    if (tiles < 128) return false;
-    return !(q->n == 1 && q->max_len <= 8 && c->max_len <= 8);
-}
-
-// otAspire's cost stage on the plane tiles with FEW queries too: as above, and the pairs' diameters must not cost a pass over every
-// candidate row -- the pool brings its documents' boxes along (aspire_repset.doc_box) or the caller its own diameters.  Two to eight
-// queries against 20 000 documents of 8 rows then take cost tiles (~90 us) + pair_box + the block Sinkhorn kernel instead of the
-// fused kernel re-staging every candidate group per query (Q = 4: 335 us, Q = 8: 626).  ONE query of <= 8 rows stays on the fused /
-// chunk kernels.
-bool gram_planes_wanted_ot(const aspire_repset* q, const aspire_repset* c, int pairing, bool caller_diameters) {
-    if (!gram_planes_wanted_l2max(q, c, pairing)) return false;
-    if (!c->doc_box && !caller_diameters) return false;
-    return !(q->n == 1 && q->max_len <= 8);
-}
-
-bool gram_path_wanted(const aspire_repset* q, const aspire_repset* c, int pairing) {
-    if (pairing != ASPIRE_PAIR_CROSS || q->ext != 0 || c->ext != 0) return false;
-    if (q->max_len <= 0 || c->max_len <= 0 || q->max_len > 32 || c->max_len > 32) return false;
-    // ASPIRE_HIP_COST_PATH=mfma|valu pins the choice (parity tests compare the two forms); default: by shape
-    if (tuning().cost_path == 1) return true;
-    if (tuning().cost_path == 2) return false;
-    const int max_rows = q->max_len > c->max_len ? q->max_len : c->max_len;
-    const int64_t qrows = q->n * (int64_t)slot_rows(q->max_len);
-    const int64_t tiles = (c->n + kBM / slot_rows(c->max_len) - 1) / (kBM / slot_rows(c->max_len));
-    if (max_rows > 8) {
-        // long documents: the VALU tile-loop kernel costs ~5 ns per (pair x 8x8 tile), the Gram kernel ~75 us of
-        // latency (48 dependent K stages) before its throughput counts: 1 x 3000 x 12 is 82 vs 88 us, 1 x 4000 x 20
-        // 194 vs 120 us
-        const int64_t T = (max_rows + 7) / 8;
-        return tiles >= 32 && q->n * c->n * T * T >= 16000;
-    }
-    if (tiles < 128) return false;          // small pools are latency bound: the per-pair kernels start faster
-    return qrows >= 24;
-}
-
+// (when the matrix-core form serves a call: forms.hip -- gram_path_wanted, gram_planes_wanted_*)
 size_t gram_extra_bytes_per_cand(void) { return (size_t)2 * kD * sizeof(float); }   // the candidate's box
 
 int launch_pair_gram_ot(const ScoreArgs& a, int T, int mr_q, int mr_c, float* cost, float* neg, float* diam2, float* qbox,

@@ -1,18 +1,18 @@
-// Host dispatch of the scoring entry points: which kernel family scores a pair.  No kernel is defined here; every launch goes
-// through the launcher of the unit that defines the kernel (score_types.h lists them by unit: cost_valu.hip, sinkhorn.hip,
-// batch_prep.hip, gram.hip, gramp.hip, generic.hip, fused.hip, tile16.hip; the rank: topk.hip).  Reference call structure:
+// The scoring entry points.  No kernel is defined here and no rule that picks one: every entry point reads argument checks, the
+// plan of its family (forms.h: one pure decision function per family, every rule and threshold in forms.hip), a `switch` over the
+// plan that carries it out through the launchers of the units that define the kernels (score_types.h lists them by unit:
+// cost_valu.hip, sinkhorn.hip, batch_prep.hip, gram.hip, gramp.hip, generic.hip, fused.hip, tile16.hip), and the rank (topk.hip).
+// Reference call structure:
 //   src/learning/facetid_models/pair_distances.py:21-92, :138-186; src/evaluation/evaluate.py:58-76 (allenai/aspire).
 //
 // Top to bottom: argument checks and ScoreArgs fills (check_repsets, check_backward_sets, fill_set_args, fill_ot_args); the max-sim
 // entry points and the backward of their aggregations (aspire_l2agg_backward_f32: checks here, the kernel in l2agg_bwd.hip), the checks of
 // aspire_jointsm_backward_f32 (jointsm_bwd.hip), of the supervised-alignment pair aspire_l2sup_scores_f32 / _backward_f32 (l2sup.hip) and
-// of the padded blocks' distance matrix aspire_sent_cdist_f32 / _backward_f32 (cdist_pair.hip); the
-// host helpers of the batched / CHUNK / REC forms -- form rules (chunk_size_ok, one_wave_form_ok, sinkhorn_form_honours_gate),
-// workspace layouts (batch_layout, l2_batch_layout, batch_tables), launch_fused_form; otAspire per call (ot_run_tiles, ot_run)
-// and its backward (aspire_ot_backward_f32: checks here, the kernel in ot_bwd.hip);
-// the batched entry points (ot_rank_batch, aspire_l2max_rank_batch_f32).  Which kernel family scores a pair decides the pair's
-// bits, so every rule that picks one is written once and asked by every entry point; the batched entry points share their
-// argument checks and their rank with dotmax.hip through batch_host.h (batch_preamble, BatchRank).
+// of the padded blocks' distance matrix aspire_sent_cdist_f32 / _backward_f32 (cdist_pair.hip); the workspace layouts of the batched
+// / CHUNK / REC forms (batch_layout, l2_batch_layout, batch_tables) and launch_fused_form; otAspire per call (ot_run_tiles, ot_run)
+// and its backward (aspire_ot_backward_f32: checks here, the kernel in ot_bwd.hip); the batched entry points (ot_rank_batch,
+// aspire_l2max_rank_batch_f32), which share their argument checks and their rank with dotmax.hip through batch_host.h
+// (batch_preamble, BatchRank); aspire_debug_score_form, which names the plan of a call without running it.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -20,7 +20,7 @@
 #include <type_traits>
 
 #include "common.h"
-#include "tuning.h"
+#include "forms.h"
 #include "score_types.h"
 #include "score_device.h"
 #include "topk_device.h"
@@ -28,11 +28,6 @@
 
 namespace aspire {
 namespace {
-
-// Groups of four candidates from which the fused streaming kernel (fused.hip) is ahead of the small-pool kernels, documents of
-// <= 8 rows (tools/otbatchcross.py: one query x one pool 750 groups 39 against 46 us, 2000 groups 59 / 94; batched jobs 500
-// groups 33 / 37, 1600 groups 45 / 79).  Below, a call is latency bound and the small-pool kernels' shorter chains win.
-constexpr int64_t kStreamMinGroups1 = 640, kStreamMinGroupsBatch = 512;
 
 int check_repsets(const aspire_repset* q, const aspire_repset* c, int64_t D, int pairing) {
     ASPIRE_REQUIRE(q && c, ASPIRE_ERR_INVALID_ARG, "null repset");
@@ -59,12 +54,6 @@ void fill_set_args(ScoreArgs& a, const aspire_repset* q, const aspire_repset* c,
     a.pairing = pairing;
 }
 
-int max_rows_of(const aspire_repset* q, const aspire_repset* c) {
-    const int mq = q->ext > 0 ? q->ext : q->max_len;
-    const int mc = c->ext > 0 ? c->ext : c->max_len;
-    return mq > mc ? mq : mc;
-}
-
 // What the backward entries (l2agg, jointsm, l2sup, ot) check first, alike: the sets, PAIRED only.  Yields the host-known bounds of
 // the documents' rows.  (An entry's own argument checks follow, then its null-pointer check once there is a pair to write for.)
 int check_backward_sets(const aspire_repset* q, const aspire_repset* c, int64_t D, int pairing, int& rows_q, int& rows_c) {
@@ -75,6 +64,16 @@ int check_backward_sets(const aspire_repset* q, const aspire_repset* c, int64_t 
     rows_q = q->ext > 0 ? q->ext : q->max_len;
     rows_c = c->ext > 0 ? c->ext : c->max_len;
     return ASPIRE_OK;
+}
+
+// the flags or'ed into the max-sim entry points' cdist_mode, taken off it
+struct CdistFlags {
+    bool one_form, center;
+};
+CdistFlags take_cdist_flags(int& cdist_mode) {
+    const CdistFlags f{(cdist_mode & ASPIRE_CDIST_ONE_FORM) != 0, (cdist_mode & ASPIRE_CDIST_CENTER) != 0};
+    cdist_mode &= ~(ASPIRE_CDIST_ONE_FORM | ASPIRE_CDIST_CENTER);
+    return f;
 }
 
 // Query chunking.  CROSS: grid.x = candidates, grid.y = query chunks; queries are split over grid.y only while
@@ -114,9 +113,8 @@ extern "C" int aspire_l2agg_scores_f32(const aspire_repset* q, const aspire_reps
     ASPIRE_REQUIRE(scores, ASPIRE_ERR_INVALID_ARG, "scores is null");
     ASPIRE_REQUIRE((!pair_sims && !pair_softmax) || (q->ext > 0 && c->ext > 0), ASPIRE_ERR_INVALID_ARG,
                    "pair outputs need padded extents (ext > 0)");
-    const bool one_form = (cdist_mode & ASPIRE_CDIST_ONE_FORM) != 0, center = (cdist_mode & ASPIRE_CDIST_CENTER) != 0;
-    cdist_mode &= ~(ASPIRE_CDIST_ONE_FORM | ASPIRE_CDIST_CENTER);
-    ASPIRE_REQUIRE(!one_form || agg == ASPIRE_AGG_MAX, ASPIRE_ERR_UNSUPPORTED, "ASPIRE_CDIST_ONE_FORM is built for the max-sim score only");
+    const CdistFlags flags = take_cdist_flags(cdist_mode);
+    ASPIRE_REQUIRE(!flags.one_form || agg == ASPIRE_AGG_MAX, ASPIRE_ERR_UNSUPPORTED, "ASPIRE_CDIST_ONE_FORM is built for the max-sim score only");
     ScoreArgs a{};
     fill_set_args(a, q, c, pairing);
     a.cdist_mode = cdist_mode;
@@ -125,45 +123,25 @@ extern "C" int aspire_l2agg_scores_f32(const aspire_repset* q, const aspire_reps
     a.scores = scores;
     a.out_pairsims = pair_sims;
     a.out_plan = pair_softmax;
-    a.center = center;
-    if (one_form)      // every pair through the long-form kernel, whatever the size of the call (include/aspire_hip.h)
-        return launch_pair_generic(a, 1, 0, q->ext > 0 ? q->ext : q->max_len, c->ext > 0 ? c->ext : c->max_len, (hipStream_t)stream);
-    // both sides carry fp16 planes: the matrix-pipe tiles (gramp.hip) whatever the number of queries
-    if (agg == ASPIRE_AGG_MAX && !pair_sims && gram_planes_wanted_l2max(q, c, pairing))
-        return launch_pair_gram_l2max(a, q->max_len, c->max_len, (hipStream_t)stream);
-    // ONE query against a big pool of 9 .. 16-row documents: the streaming kernel's max-sim form (tile16.hip)
-    if (agg == ASPIRE_AGG_MAX && !pair_sims && q->n == 1 && c->n >= 4096 && tile16_path_ok(q, c, pairing) &&
-        pairing == ASPIRE_PAIR_CROSS && tuning().cost_path != 1 && tuning().ot_form != 1) {
+    a.center = flags.center;
+    hipStream_t s = (hipStream_t)stream;
+    const int rows_q = q->ext > 0 ? q->ext : q->max_len, rows_c = c->ext > 0 ? c->ext : c->max_len;
+    const ScorePlan plan = plan_l2agg(q, c, pairing, agg, pair_sims != nullptr, flags.one_form);
+    switch (plan.form) {
+    case Form::Generic: return launch_pair_generic(a, 1, 0, rows_q, rows_c, s);
+    case Form::GramPlanes:
+    case Form::Gram: return launch_pair_gram_l2max(a, q->max_len, c->max_len, s);
+    case Form::Stream16:
+    case Form::FusedStream:
         a.cand0 = 0;
         a.cand1 = c->n;
-        return launch_pair_tile16_l2max(a, (c->n + 1) / 2, (hipStream_t)stream);
+        return plan.form == Form::Stream16 ? launch_pair_tile16_l2max(a, (c->n + 1) / 2, s)
+                                           : launch_pair_fused_l2max(a, (c->n + 3) / 4 * q->n, s);
+    default: break;      // Form::Tiles
     }
-    if (agg == ASPIRE_AGG_MAX && !pair_sims && gram_path_wanted(q, c, pairing))
-        return launch_pair_gram_l2max(a, q->max_len, c->max_len, (hipStream_t)stream);
-    // Few queries against a big pool of short documents (CSR): the fused kernel's streaming phase with a max epilogue --
-    // four candidates per wave, dot products on the matrix pipe (l2max_kernel<1> is one workgroup per candidate with VALU
-    // difference sums: 114 us at 1 x 20 000 against the stream's 88)
-    {
-        const int form_t = tuning().ot_form;
-        const int64_t groups4 = (c->n + 3) / 4 * q->n;
-        if (agg == ASPIRE_AGG_MAX && !pair_sims && pairing == ASPIRE_PAIR_CROSS && fused_path_ok(q, c) &&
-            (form_t == 3 || (form_t == 0 && groups4 >= (q->n == 1 ? kStreamMinGroups1 : 2048)))) {
-            a.cand0 = 0;
-            a.cand1 = c->n;
-            return launch_pair_fused_l2max(a, groups4, (hipStream_t)stream);
-        }
-    }
-    // Documents beyond the tile kernels' 32 rows (max-sim only): padded tensors that wide go through the one-workgroup-
-    // per-pair kernel for every pair; CSR pools run the tile kernel on 32-row tiles first (it covers every pair of short
-    // documents) and the long-document kernel then rewrites the pairs that hold a longer one.
-    const int rows_q = q->ext > 0 ? q->ext : q->max_len, rows_c = c->ext > 0 ? c->ext : c->max_len;
-    const bool long_docs = max_rows_of(q, c) > 8 * kMaxT;
-    if (long_docs && (q->ext > 0 || c->ext > 0)) return launch_pair_generic(a, 1, 0, rows_q, rows_c, (hipStream_t)stream);
     const int qchunks = query_chunks(a);
-    const int tile_rows = long_docs ? 8 * kMaxT : max_rows_of(q, c);
-    const int rc_tiles = launch_l2max_tiles(a, tile_rows, qchunks, (hipStream_t)stream);
-    if (rc_tiles || !long_docs) return rc_tiles;
-    return launch_pair_generic(a, 1, 8 * kMaxT, rows_q, rows_c, (hipStream_t)stream);
+    if (int rc = launch_l2max_tiles(a, plan.max_rows, qchunks, s)) return rc;
+    return plan.then_generic ? launch_pair_generic(a, 1, plan.max_rows, rows_q, rows_c, s) : (int)ASPIRE_OK;
 }
 
 extern "C" int aspire_l2max_scores_f32(const aspire_repset* q, const aspire_repset* c, int64_t D, int pairing,
@@ -241,7 +219,6 @@ size_t slot_bytes(int max_rows) {
     const int T = (max_rows + 7) / 8;
     return (size_t)(2 * 64 * T * T + 1) * sizeof(float);
 }
-size_t qbox_bytes(const aspire_repset* q) { return (size_t)q->n * 2 * kD * sizeof(float); }
 constexpr size_t kWsCap = (size_t)1 << 30;  // suggested workspace is capped at 1 GiB; larger jobs run in chunks
 constexpr size_t kWsSlack = 48;             // alignment of the box tables behind the pair slots
 size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
@@ -249,6 +226,10 @@ size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
 size_t per_cand_bytes(const aspire_repset* q, const aspire_repset* c, int pairing) {
     return slot_bytes(max_rows_of(q, c)) * (pairing == ASPIRE_PAIR_CROSS ? (size_t)q->n : 1) +
            (gram_path_wanted(q, c, pairing) ? gram_extra_bytes_per_cand() : 0);
+}
+// candidates per chunk of a per-call otAspire workspace of `workspace_bytes` (the queries' boxes sit at its tail)
+int64_t ot_cand_per_chunk(const aspire_repset* q, size_t workspace_bytes, size_t per_cand) {
+    return (int64_t)((((workspace_bytes - qbox_bytes(q)) & ~(size_t)15) - 32) / per_cand);
 }
 }  // namespace
 
@@ -304,13 +285,6 @@ void fill_ot_args(ScoreArgs& a, const aspire_repset* q, const aspire_repset* c, 
     a.center = (prm->flags & ASPIRE_OT_FLAG_CENTER) != 0;
 }
 
-// The hybrid forms (fused kernel in front of the 16-row kernels, ScoreArgs::gate) need a solve stage that leaves the short pairs'
-// scores alone: the block kernels and their repair kernel check the gate, the one-solve-per-wave kernel (SINKHORN=wave) does not.
-bool sinkhorn_form_honours_gate() {
-    const int f = tuning().sinkhorn_form;
-    return f == 0 || f == 3 || f == 5 || f == 6 || f == 7;
-}
-
 // the pair slots of `n_slots` pairs at `base` (cost tiles, -cdist tiles, squared diameters)
 template <int T>
 PairWs<T> pair_ws_at(void* base, int64_t n_slots) {
@@ -323,33 +297,10 @@ PairWs<T> pair_ws_at(void* base, int64_t n_slots) {
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
-// The batched / CHUNK / REC forms: form rules and workspace layouts (the preparation kernels and their launchers: batch_prep.hip)
+// The batched / CHUNK / REC forms: workspace layouts (the preparation kernels and their launchers: batch_prep.hip)
 // ---------------------------------------------------------------------------------------------
 namespace aspire {
 namespace {
-
-// smallest pool / batch (candidates) that takes the CHUNK / REC forms (below: the small-batch kernels; tools/csfbench.py sweeps)
-constexpr int64_t kChunkMinCands = 256;
-// the size rule of the CHUNK / REC forms: pinned (OT_FORM 4), or by default from kChunkMinCands candidates in the call
-bool chunk_size_ok(int64_t C) {
-    const int form_t = tuning().ot_form;
-    return form_t == 4 || (form_t == 0 && C >= kChunkMinCands);
-}
-// pairs of short documents per call that take pair_one_kernel (tools/experiments/singlejob.py sweeps)
-constexpr int64_t kOneMinPairs = 1, kOneMaxPairs = 8192;        // (ONE form for every small grid: a pair scored alone, in a subset or in a shard gets the same bits)
-// May a call of `pairs` pairs of documents of <= 8 rows take the one-launch form (pair_one_kernel: one wave per pair, costs and
-// solve)?  The single-pool and the batched entry points ask the same question, so that a pair gets the same kernel -- the same
-// bits -- whether it is scored in a call of its own or in a batch.
-//   plain_call: CSR sets, no Gram tiles, every stage of the call wanted.  Single-pool: ext == 0 on both sides && !gram &&
-//               !cost_only; batched: the full stage mask (batched sets are CSR and never take the Gram tiles).
-//   small_grid: the call stays below the throughput kernels.  The two callers' rules differ and stay their own: single-pool calls
-//               go by groups of four (CROSS pairing from 2048 groups: the tiled cost kernel's grid), batches by !a.tile_form
-//               (from kStreamMinGroupsBatch groups the fused kernel, which also carries the OT_FORM pins 2 and 3).
-bool one_wave_form_ok(int64_t pairs, bool plain_call, bool small_grid) {
-    const int form_t = tuning().ot_form;
-    return plain_call && small_grid && pairs >= kOneMinPairs && pairs <= kOneMaxPairs &&
-           (form_t == 5 || (form_t == 0 && tuning().sinkhorn_form == 0 && tuning().cost_path == 0 && tuning().cost1_blocks == 0));
-}
 
 // Workspace of a batched call (byte offsets): otAspire's pair slots, then the tables the preparation kernels write, the hybrid
 // forms' gate word and the rank scratch.
@@ -424,61 +375,29 @@ int launch_fused_form(const ScoreArgs& a, int64_t groups, bool own_box, bool who
 // ---------------------------------------------------------------------------------------------
 namespace {
 
-// The tile-kernel forms (documents of up to 32 rows) of a call that ot_run has checked and described in `a`: non-empty sets, sound
-// parameters, a.scores set.  q / c carry the row bound the kernels are to use (ot_run clamps max_len for pools with longer
-// documents).  Scores only: the rank is ot_run's.
-int ot_run_tiles(ScoreArgs a, const aspire_repset* q, const aspire_repset* c, const aspire_ot_params* prm, void* workspace,
-                 size_t workspace_bytes, hipStream_t stream, bool cost_only) {
+// The forms of documents of up to 32 rows of a call that ot_run has checked and described in `a` (a copy: what the forms set in it
+// stays theirs).  q / c carry the row bound the kernels are to use (ot_run clamps max_len for pools with longer documents).
+int ot_run_tiles(ScoreArgs a, const ScorePlan& plan, const aspire_repset* q, const aspire_repset* c, const aspire_ot_params* prm,
+                 void* workspace, size_t workspace_bytes, hipStream_t stream, bool cost_only) {
     const int pairing = a.pairing;
-    const float* diameter = a.diameter;
     const bool extra = a.out_qdistr || a.out_cdistr || a.out_pairsims || a.out_plan;
-    const int max_rows = max_rows_of(q, c);
     const size_t per_cand = per_cand_bytes(q, c, pairing);
-    // ONE query against a big pool of 9 .. 16-row documents: the streaming kernel (tile16.hip) beats the 32-column Gram tiles,
-    // whose 12 .. 16 real query rows fill a third to a half of the MFMA tile (1 x 20 000 x 12 otAspire: 247 vs 363 us; at two
-    // queries they tie, from three the Gram tiles win: 623 vs 565 us)
-    // both sides on fp16 planes, the pool's boxes cached: the plane tiles whatever the number of queries (gram.hip)
-    const bool planes_ot = !extra && gram_planes_wanted_ot(q, c, pairing, diameter != nullptr) && tuning().ot_form == 0;
-    const bool stream16 = !planes_ot && q->n == 1 && c->n >= 4096 && tile16_path_ok(q, c, pairing) && tuning().cost_path != 1 &&
-                          tuning().ot_form != 1;
-    const int form_t = tuning().ot_form;
-    // ONE short query (facet-selected rows) against a pool of abstracts of up to 32 rows: the fused kernel's CHUNK form, as in
-    // ot_rank_batch (1 x 20 000 x (3..20): 674 us on the Gram tiles + block Sinkhorn before) -- the item records and their counter
-    // take the (unused) front of the pair-slot workspace.  (From kChunkMinCands candidates even where the form is pinned: the
-    // call's workspace is sized for the pair slots.)
-    const bool chunk1 = pairing == ASPIRE_PAIR_CROSS && q->n == 1 && q->ext == 0 && c->ext == 0 && q->max_len <= 8 && c->max_len > 8 &&
-                        c->max_len <= 8 * kMaxT && c->n >= kChunkMinCands && c->n < ((int64_t)1 << 30) && !extra && !cost_only && !diameter &&
-                        chunk_size_ok(c->n) && prm->scaling >= 0.25 && !tuning().fused_nosolve && !tuning().fused_valu &&
-                        tuning().cost_path == 0 && workspace &&
-                        (size_t)(chunk_items_bound(1, c->n, c->n) + 2) * 64 + 256 + qbox_bytes(q) + 64 <= workspace_bytes;
-    const bool gram = (gram_path_wanted(q, c, pairing) || planes_ot) && !stream16 && !chunk1;
     ASPIRE_REQUIRE(workspace && workspace_bytes >= per_cand + qbox_bytes(q) + kWsSlack, ASPIRE_ERR_INVALID_ARG,
                    "workspace too small: %zu bytes given, at least %zu needed (aspire_ot_workspace_bytes suggests %zu)",
                    workspace_bytes, per_cand, aspire_ot_workspace_bytes(q, c, pairing));
-    // the matrix-pipe cost tiles derive -cdist and geomloss's cost from ONE distance: they store -cdist only and the solve stage takes
-    // cost = max(cdist, 1e-4) from it -- half the tile bytes written and read (the debug cost stage keeps both buffers)
-    a.cost_from_neg = gram && !cost_only;
-    const int qchunks = query_chunks(a);
-    const int64_t cand_per_chunk = (int64_t)((((workspace_bytes - qbox_bytes(q)) & ~(size_t)15) - 32) / per_cand);
-    const int64_t pairs_per_cand = pairing == ASPIRE_PAIR_PAIRED ? 1 : q->n;
+    a.cost_from_neg = plan.cost_from_neg;
     // query boxes sit at a fixed place (the tail of the workspace) so that every candidate chunk finds them
     float* qbox = (float*)((char*)workspace + ((workspace_bytes - qbox_bytes(q)) & ~(size_t)15));
-    // Few queries against a big pool of short documents: costs and solves in ONE launch, no workspace slots, no candidate
-    // chunks (fused.hip).
-    const int64_t groups4_all = (c->n + 3) / 4 * q->n;
-    const bool fused = pairing == ASPIRE_PAIR_CROSS && !extra && !gram && !cost_only && fused_path_ok(q, c) &&
-                       (form_t == 3 || (form_t == 0 && groups4_all >= (q->n == 1 ? kStreamMinGroups1 : 2048)));
-    if (fused) {
-        a.cand0 = 0;
-        a.cand1 = c->n;
-        const bool inbox = fused_inbox_ok(q, diameter);      // ONE query: the kernel forms its box itself
-        if (!diameter && !inbox)     // per-coordinate boxes of the queries (the kernel adds each candidate's rows)
+    const int qchunks = query_chunks(a);
+    a.cand0 = 0;
+    a.cand1 = c->n;
+    switch (plan.form) {
+    case Form::FusedInbox:
+    case Form::FusedQbox:      // costs and solves in ONE launch, no workspace slots, no candidate chunks (fused.hip)
+        if (plan.qbox_first)
             if (int rc = launch_doc_box(a.q, qbox, stream)) return rc;
-        return launch_fused_form(a, groups4_all, inbox, true, qbox, prm, stream);
-    }
-    if (chunk1) {
-        a.cand0 = 0;
-        a.cand1 = c->n;
+        return launch_fused_form(a, (c->n + 3) / 4 * q->n, plan.form == Form::FusedInbox, true, qbox, prm, stream);
+    case Form::Chunk: {
         // counter and records at the front of the workspace; no candidate -> job table (ONE query)
         const BatchTables t{nullptr, qbox, nullptr, nullptr, (int32_t*)workspace, (int32_t*)((char*)workspace + 256), nullptr, nullptr};
         a.grp_off = t.grp_off;
@@ -486,37 +405,31 @@ int ot_run_tiles(ScoreArgs a, const aspire_repset* q, const aspire_repset* c, co
         if (int rc = launch_chunk_prep(a, t, nullptr, 1, c->n, stream)) return rc;
         return launch_pair_fused_chunk(a, chunk_items_bound(1, c->n, c->n), qbox, stream);
     }
-    return dispatch_T(max_rows, [&](auto tc) -> int {
+    default: break;      // Form::Tiles: the cost stage and the solve stage on workspace slots, in chunks of candidates
+    }
+    const int64_t cand_per_chunk = ot_cand_per_chunk(q, workspace_bytes, per_cand);
+    const int64_t pairs_per_cand = pairing == ASPIRE_PAIR_PAIRED ? 1 : q->n;
+    return dispatch_T(plan.max_rows, [&](auto tc) -> int {
         constexpr int T = decltype(tc)::value;
         for (int64_t c0 = 0; c0 < c->n; c0 += cand_per_chunk) {
             a.cand0 = c0;
             a.cand1 = c0 + cand_per_chunk < c->n ? c0 + cand_per_chunk : c->n;
             const int64_t n_slots = (a.cand1 - a.cand0) * pairs_per_cand;
+            if (ot_chunk_one_wave(plan, q, c, pairing, a.cand1 - a.cand0, cost_only)) {
+                if (int rc = launch_pair_one(a, n_slots, stream)) return rc;
+                continue;
+            }
             const PairWs<T> ws = pair_ws_at<T>(workspace, n_slots);
             float* cbox = (float*)(((uintptr_t)(ws.diam2 + n_slots) + 15) & ~(uintptr_t)15);
-            if constexpr (T == 1) {
-                // a small pool of short documents (the per-query call of evaluate.py:58-76): one wave per pair, costs and solve in ONE
-                // launch (pair_one_kernel) instead of the cost launch + the Sinkhorn launch and the workspace between them
-                const int64_t groups4 = (a.cand1 - a.cand0 + 3) / 4 * (pairing == ASPIRE_PAIR_CROSS ? q->n : 1);
-                const bool small_grid = !(pairing == ASPIRE_PAIR_CROSS && groups4 >= 2048);        // (beyond: the tiled cost kernel's grid)
-                if (one_wave_form_ok(n_slots, q->ext == 0 && c->ext == 0 && !gram && !cost_only, small_grid)) {
-                    if (int rc = launch_pair_one(a, n_slots, stream)) return rc;
-                    continue;
-                }
-            }
-            if (int rc = launch_cost_stage(a, T, q, c, ws.cost, ws.neg, ws.diam2, n_slots, qchunks, gram, qbox, cbox, c0 == 0, stream)) return rc;
+            if (int rc = launch_cost_stage(a, T, q, c, ws.cost, ws.neg, ws.diam2, n_slots, qchunks, plan.gram, qbox, cbox, c0 == 0, stream)) return rc;
             if (cost_only) continue;
-            if (int rc = launch_sinkhorn_stage(a, T, ws.cost, ws.neg, ws.diam2, n_slots, max_rows, extra, 0, stream)) return rc;
+            if (int rc = launch_sinkhorn_stage(a, T, ws.cost, ws.neg, ws.diam2, n_slots, plan.max_rows, extra, 0, stream)) return rc;
         }
         return (int)ASPIRE_OK;
     });
 }
 
-// One otAspire call: the argument checks, the form by document length, the rank.
-// Documents beyond the tile kernels' 32 rows: padded tensors that wide go through the one-workgroup-per-pair kernel
-// (generic.hip) for every pair; CSR pools run the tile kernels with their documents' bound clamped to 32 rows (every pair
-// of short documents is scored there, a pair that holds a longer one gets NaN) and the long-document kernel then rewrites
-// exactly those pairs.  The rank follows.
+// One otAspire call: the argument checks, the plan (forms.hip: plan_ot), its launches, the rank.
 int ot_run(const aspire_repset* q, const aspire_repset* c, int64_t D, int pairing, const aspire_ot_params* prm,
            const float* diameter, int64_t diam_group, int want, float* scores, float* out_qdistr, float* out_cdistr,
            float* out_pairsims, float* out_plan, void* workspace, size_t workspace_bytes, void* stream, const RankReq& rank,
@@ -535,23 +448,17 @@ int ot_run(const aspire_repset* q, const aspire_repset* c, int64_t D, int pairin
     a.out_pairsims = out_pairsims;
     a.out_plan = out_plan;
     hipStream_t s = (hipStream_t)stream;
-    const int tile_max = 8 * kMaxT;
-    // ONE_FORM (include/aspire_hip.h): every pair through the long-form kernel, whatever the size of the call
-    const bool one_form = (prm->flags & ASPIRE_OT_FLAG_ONE_FORM) && !cost_only;
-    if (max_rows_of(q, c) <= tile_max && !one_form) {
-        if (int rc = ot_run_tiles(a, q, c, prm, workspace, workspace_bytes, s, cost_only)) return rc;
-    } else {
-        int skip = 0;
-        if (q->ext == 0 && c->ext == 0 && !one_form) {      // (CSR: no pair outputs, `a` serves the tile kernels as it is)
-            aspire_repset q32 = *q, c32 = *c;
-            q32.max_len = q->max_len < tile_max ? q->max_len : tile_max;
-            c32.max_len = c->max_len < tile_max ? c->max_len : tile_max;
-            if (int rc = ot_run_tiles(a, &q32, &c32, prm, workspace, workspace_bytes, s, cost_only)) return rc;
-            skip = tile_max;
-        }
-        if (cost_only) return ASPIRE_OK;
-        const int rows_q = q->ext > 0 ? q->ext : q->max_len, rows_c = c->ext > 0 ? c->ext : c->max_len;
-        if (int rc = launch_pair_generic(a, 0, skip, rows_q, rows_c, s)) return rc;
+    const ScorePlan plan = plan_ot(q, c, pairing, prm, OtAsked{extra, diameter != nullptr, cost_only, workspace != nullptr, workspace_bytes});
+    const int rows_q = q->ext > 0 ? q->ext : q->max_len, rows_c = c->ext > 0 ? c->ext : c->max_len;
+    if (plan.form == Form::Generic) {
+        if (int rc = launch_pair_generic(a, 0, 0, rows_q, rows_c, s)) return rc;
+    } else if (plan.form != Form::None) {
+        // (CSR pools with longer documents: the tile kernels see the bound the plan clamped)
+        const bool csr = q->ext == 0 && c->ext == 0;
+        const aspire_repset q32 = csr ? tile_bound_set(q) : *q, c32 = csr ? tile_bound_set(c) : *c;
+        if (int rc = ot_run_tiles(a, plan, &q32, &c32, prm, workspace, workspace_bytes, s, cost_only)) return rc;
+        if (plan.then_generic)      // ... and the long-document kernel rewrites exactly those pairs
+            if (int rc = launch_pair_generic(a, 0, kTileMaxRows, rows_q, rows_c, s)) return rc;
     }
     // the rank kernels follow the scores on the same stream (their scratch sits behind the OT workspace proper,
     // which aspire_ot_workspace_bytes keeps a multiple of 16 bytes)
@@ -621,7 +528,6 @@ extern "C" size_t aspire_ot_rank_batch_workspace_bytes(const aspire_repset* q, c
 }
 
 namespace {
-constexpr int kStagePrep = 1, kStageCost = 2, kStageSolve = 4, kStageRank = 8, kStageAll = 15;
 int ot_rank_batch(const aspire_repset* q, const aspire_repset* c, int64_t D, const int32_t* job_off, int64_t max_job,
                   const aspire_ot_params* prm, int want, float* scores, int64_t k, const int32_t* job_base, float* top_scores,
                   int64_t* top_idx, uint64_t* keys, void* workspace, size_t workspace_bytes, void* stream, int stages) {
@@ -632,14 +538,10 @@ int ot_rank_batch(const aspire_repset* q, const aspire_repset* c, int64_t D, con
     bool go_on;
     if (int rc = batch_preamble(q, c, scores, rank, go_on); !go_on) return rc;
     hipStream_t s0 = (hipStream_t)stream;
-    // Documents beyond the tile kernels' 32 rows (AspireNER's appended entity rows, models.py:224-233), as in ot_run: the tile
-    // kernels run with their documents' bound clamped to 32 rows (a pair that holds a longer document gets NaN there) and the
-    // long-document kernel (generic.hip) then rewrites exactly those pairs, in front of the rank.
     const int max_rows_all = max_rows_of(q, c);
     ASPIRE_REQUIRE(max_rows_all <= generic_max_rows(), ASPIRE_ERR_UNSUPPORTED,
                    "documents with more than %d sentence rows are not supported (got %d)", generic_max_rows(), max_rows_all);
-    const int max_rows = max_rows_all < 8 * kMaxT ? max_rows_all : 8 * kMaxT;
-    const BatchLayout L = batch_layout(J, C, max_rows, max_job, k);
+    const BatchLayout L = batch_layout(J, C, max_rows_all < kTileMaxRows ? max_rows_all : kTileMaxRows, max_job, k);
     if (int rc = place_scratch(rank, workspace, workspace_bytes, L.total, L.topk, "aspire_ot_rank_batch_workspace_bytes")) return rc;
     const BatchTables t = batch_tables(workspace, L);
     if (!(stages & kStageRank)) rank.k = 0;      // (a stage mask of the debug entry point without the rank: scores only)
@@ -647,45 +549,26 @@ int ot_rank_batch(const aspire_repset* q, const aspire_repset* c, int64_t D, con
     fill_ot_args(a, q, c, kPairMapped, prm, nullptr, 0, want, scores);
     a.q_per_block = 1;
     fill_mapped_args(a, t, job_off, J, C, max_job);
-    // Forms.  Small batches are latency bound and take the kernels the single-pool entry points use.  Once the batch fills
-    // the chip (documents of <= 8 rows): the fused kernel -- four candidates of a job per wave, costs and solves in one
-    // launch (fused.hip) -- or, pinned for A/B tests, the same cost kernel + the block Sinkhorn kernel as two launches.
-    // (Chunks of jobs on two streams, Sinkhorn of chunk i beside the cost kernel of chunk i + 1, were measured and dropped:
-    // 20 x 1000: 169 us on one stream, 213 / 266 / 403 us in 2 / 4 / 8 chunks -- cross-stream waits cost more than they hide.)
-    if (prm->flags & ASPIRE_OT_FLAG_ONE_FORM) {
-        // every pair through the long-form kernel (one workgroup per pair; it finds a candidate's job by searching job_off)
-        a.qmap = nullptr;
-        if (stages & kStageSolve)
-            if (int rc = launch_pair_generic(a, 0, 0, q->max_len, c->max_len, s0)) return rc;
-        return rank.rank(scores);
-    }
     const int64_t groups_bound = J * ((max_job + 3) / 4);
-    const int form_t = tuning().ot_form;
-    const bool big = max_rows <= 8 && groups_bound >= kStreamMinGroupsBatch;
-    const bool fused = max_rows <= 8 && (form_t == 3 || (form_t == 0 && big));
-    a.tile_form = max_rows <= 8 && (form_t == 2 || fused);
-    // Documents of up to 16 rows in a batch that fills the chip: usually pools of mostly short abstracts with a few longer
-    // ones.  The fused kernel is queued in front of the 16-row streaming kernel + block Sinkhorn, and a census of the long
-    // pairs, taken on the device, decides how they work (score_types.h: ScoreArgs::gate): few long pairs -- the fused kernel
-    // scores the short ones, the 16-row kernels only the long ones; many -- the fused kernel returns at once.  No host round
-    // trip, and ONE long document no longer moves 20 000 pairs onto kernels 2.5 x slower.
-    const bool hybrid = max_rows > 8 && max_rows <= 16 && form_t == 0 && groups_bound >= 2048 && C >= 6000 && stages == kStageAll &&
-                        prm->scaling >= 0.25 && want != ASPIRE_OT_PLAN_SIM && !tuning().fused_nosolve && !tuning().fused_valu &&
-                        sinkhorn_form_honours_gate();
-    // Short queries (facet-selected rows, models.py:127-163) against abstracts of up to 32 rows -- config 4's shape: the fused
-    // kernel's CHUNK form, costs and solves of every pair in one launch behind a launch that sorts the candidates into items.
-    const bool chunked = q->max_len <= 8 && max_rows > 8 && max_rows_all <= 8 * kMaxT && chunk_size_ok(C) && stages == kStageAll &&
-                         prm->scaling >= 0.25 && !tuning().fused_valu;
-    if (chunked) {
+    // Forms: forms.hip, plan_ot_batch.  (Chunks of jobs on two streams, Sinkhorn of chunk i beside the cost kernel of chunk i + 1,
+    // were measured and dropped: 20 x 1000: 169 us on one stream, 213 / 266 / 403 us in 2 / 4 / 8 chunks -- cross-stream waits cost
+    // more than they hide.)
+    const ScorePlan plan = plan_ot_batch(q, c, max_job, prm, want, stages);
+    const int max_rows = plan.max_rows;
+    a.tile_form = plan.tile_form;
+    if (plan.tables_first)
+        if (int rc = launch_batch_tables(a, t, job_off, J, max_job, s0)) return rc;
+    switch (plan.form) {
+    case Form::None: break;
+    case Form::Generic:      // (one workgroup per pair; the kernel finds a candidate's job by searching job_off)
+        a.qmap = nullptr;
+        if (int rc = launch_pair_generic(a, 0, 0, q->max_len, c->max_len, s0)) return rc;
+        break;
+    case Form::Chunk:
         if (int rc = launch_chunk_prep(a, t, job_off, J, max_job, s0)) return rc;
         if (int rc = launch_pair_fused_chunk(a, chunk_items_bound(J, C, max_job), t.qbox, s0)) return rc;
-        return rank.rank(scores);
-    }
-    // Whole abstracts on both sides, documents of 17 .. 32 rows among them (un-faceted queries: pp_settings.py:2-3): the 16-row
-    // streaming kernel on record items (a query half against two candidate halves) + the block Sinkhorn kernel on 24- / 32-row
-    // workspace slots.  (Before: the VALU tile loop, one workgroup per candidate.)
-    const bool rec16 = max_rows > 16 && max_rows_all <= 8 * kMaxT && chunk_size_ok(C) && stages == kStageAll && tuning().cost_path != 2;
-    if (rec16) {
+        break;
+    case Form::Rec16: {
         if (int rc = launch_rec_prep(a, t, job_off, J, max_job, s0)) return rc;
         const int rc_run = dispatch_T(max_rows, [&](auto tc) -> int {
             constexpr int T = decltype(tc)::value;
@@ -697,27 +580,22 @@ int ot_rank_batch(const aspire_repset* q, const aspire_repset* c, int64_t D, con
             return (int)ASPIRE_ERR_UNSUPPORTED;
         });
         if (rc_run) return rc_run;
-        return rank.rank(scores);
+        break;
     }
-    // batches of <= 64 jobs on the fused kernel need no tables launch: the kernel's waves derive them (fused.hip, SELF)
-    const bool self = fused && fused_self_ok(J, prm);
-    if ((stages & kStagePrep) && !self)
-        if (int rc = launch_batch_tables(a, t, job_off, J, max_job, s0)) return rc;
-    if (hybrid) {
+    case Form::FusedSelf:
+    case Form::FusedTables:
+        if (int rc = launch_fused_form(a, groups_bound, plan.form == Form::FusedSelf, stages == kStageAll, t.qbox, prm, s0)) return rc;
+        break;
+    case Form::OneWave:
+        if (int rc = launch_pair_one(a, C, s0)) return rc;
+        break;
+    case Form::Hybrid:
         if (int rc = arm_long_pair_gate(a, t.gate, C, s0)) return rc;
         if (int rc = launch_pair_fused(a, groups_bound, t.qbox, s0)) return rc;
-    }
-    if (fused) {
-        if (stages & (kStageCost | kStageSolve))
-            if (int rc = launch_fused_form(a, groups_bound, self, stages == kStageAll, t.qbox, prm, s0)) return rc;
-    } else {
+        [[fallthrough]];      // ... in front of the 16-row cost kernel + the block solver
+    default: {               // Form::Tiles
         const int rc_run = dispatch_T(max_rows, [&](auto tc) -> int {
             constexpr int T = decltype(tc)::value;
-            if constexpr (T == 1) {
-                // a small batch of short documents: the single-pool calls' one-launch form (pair_one_kernel: one wave per pair) -- the
-                // same kernel whether a pair is scored in a batch or in a call of its own: the same bits
-                if (one_wave_form_ok(C, stages == kStageAll, !a.tile_form)) return launch_pair_one(a, C, s0);
-            }
             const PairWs<T> ws = pair_ws_at<T>(t.slots, C);
             if (stages & kStageCost)
                 if (int rc = launch_cost_stage(a, T, q, c, ws.cost, ws.neg, ws.diam2, C, 1, false, t.qbox, nullptr, true, s0)) return rc;
@@ -726,8 +604,9 @@ int ot_rank_batch(const aspire_repset* q, const aspire_repset* c, int64_t D, con
             return (int)ASPIRE_OK;
         });
         if (rc_run) return rc_run;
-        if (max_rows_all > max_rows && (stages & kStageSolve))
+        if (plan.then_generic)      // documents beyond 32 rows: rewritten in front of the rank, as in ot_run
             if (int rc = launch_pair_generic(a, 0, max_rows, q->max_len, c->max_len, s0)) return rc;
+    }
     }
     return rank.rank(scores);
 }
@@ -742,11 +621,6 @@ extern "C" int aspire_ot_rank_batch_f32(const aspire_repset* q, const aspire_rep
 }
 
 // ---- tsAspire over batched jobs ------------------------------------------------------------------------------------------
-namespace {
-// groups of four candidates from which aspire_l2max_rank_batch_f32 takes the streaming kernels (measured, tools/l2batchbench.py)
-constexpr int64_t kL2StreamMinGroups = 384;
-}  // namespace
-
 extern "C" size_t aspire_l2max_rank_batch_workspace_bytes(const aspire_repset* q, const aspire_repset* c, int64_t max_job, int64_t k) {
     if (!q || !c || q->n <= 0 || c->n <= 0) return 0;
     return l2_batch_layout(q->n, c->n, max_job, k).total;
@@ -768,57 +642,40 @@ extern "C" int aspire_l2max_rank_batch_f32(const aspire_repset* q, const aspire_
     const BatchLayout L = l2_batch_layout(J, C, max_job, k);
     if (int rc = place_scratch(rank, workspace, workspace_bytes, L.total, L.topk, "aspire_l2max_rank_batch_workspace_bytes")) return rc;
     const BatchTables t = batch_tables(workspace, L);
-    const bool one_form = (cdist_mode & ASPIRE_CDIST_ONE_FORM) != 0, center = (cdist_mode & ASPIRE_CDIST_CENTER) != 0;
-    cdist_mode &= ~(ASPIRE_CDIST_ONE_FORM | ASPIRE_CDIST_CENTER);
+    const CdistFlags flags = take_cdist_flags(cdist_mode);
     ScoreArgs a{};
     fill_set_args(a, q, c, kPairMapped);
     a.cdist_mode = cdist_mode;
-    a.center = center;
+    a.center = flags.center;
     a.agg = ASPIRE_AGG_MAX;
     a.temp = 1.0;
     a.scores = scores;
     fill_mapped_args(a, t, job_off, J, C, max_job);
     const int64_t groups_bound = J * ((max_job + 3) / 4);
-    const int form_t = tuning().ot_form;
-    const bool big = groups_bound >= 2048 && C >= 6000 && form_t != 1;
-    // (small batches too: a wave walks an item's twelve stages in ~15 us, what a one-workgroup-per-pair launch takes anyway)
-    // short queries against abstracts of up to 32 rows (config 4's shape): the CHUNK items of ot_rank_batch, max epilogue
-    if (q->max_len <= 8 && max_rows > 8 && max_rows <= 8 * kMaxT && chunk_size_ok(C) && !one_form) {
-        if (int rc = launch_chunk_prep(a, t, job_off, J, max_job, s0)) return rc;
-        if (int rc = launch_pair_fused_chunk_l2max(a, chunk_items_bound(J, C, max_job), s0)) return rc;
-        return rank.rank(scores);
-    }
-    // whole abstracts of up to 32 rows against queries of 9 .. 16: the 16-row streaming kernel on record items, max epilogue (a
-    // query of more than 16 rows would need its two halves' maxima joined across items: the per-candidate kernel keeps those)
-    if (q->max_len <= 16 && max_rows > 16 && max_rows <= 8 * kMaxT && chunk_size_ok(C) && !one_form) {
-        if (int rc = launch_rec_prep(a, t, job_off, J, max_job, s0)) return rc;
-        if (int rc = launch_pair_tile16_rec_l2max(a, 2 * chunk_items_bound(J, C, max_job), s0)) return rc;
-        return rank.rank(scores);
-    }
-    // batches of <= 64 jobs of short documents: the streaming kernel's waves derive the tables themselves (fused.hip, SELF) --
-    // one launch in front of the rank, at any size (2 x 20: 19 us either way)
-    const bool self = form_t != 1 && max_rows <= 8 && J <= 64 && !tuning().fused_noself && !one_form;
-    const bool streaming = form_t != 1 && (self || big || form_t >= 2 || groups_bound >= kL2StreamMinGroups) && !one_form;
-    if (!self)
+    const ScorePlan plan = plan_l2max_batch(q, c, max_job, flags.one_form);      // forms.hip
+    if (plan.tables_first)
         if (int rc = launch_batch_tables(a, t, job_off, J, max_job, s0)) return rc;
-    // Forms: the streaming kernels once the batch fills the chip (documents of <= 8 rows: fused.hip's max-sim form, four
-    // candidates of a job per wave; 9 .. 16 rows: tile16.hip, two), else -- small batches, longer documents -- the
-    // one-workgroup-per-pair kernel (generic.hip).
-    if (streaming && max_rows <= 8) {
-        if (int rc = launch_pair_fused_l2max(a, groups_bound, s0, self)) return rc;
-    } else if (streaming && max_rows <= 16) {
-        // mostly short documents with a few of 9 .. 16 rows: the hybrid of ot_rank_batch (ScoreArgs::gate)
-        if (big && form_t == 0) {
-            if (int rc = arm_long_pair_gate(a, t.gate, C, s0)) return rc;
-            if (int rc = launch_pair_fused_l2max(a, groups_bound, s0)) return rc;
-        }
-        if (int rc = launch_pair_tile16_l2max(a, 2 * groups_bound, s0)) return rc;
-    } else if (max_rows <= 8 * kMaxT && !one_form) {
-        // one workgroup per candidate against its job's query (small batches, documents of 17 .. 32 rows)
-        if (int rc = launch_l2max_tiles(a, max_rows, 1, s0)) return rc;
-    } else {
-        if (int rc = launch_pair_generic(a, 1, 0, q->max_len, c->max_len, s0)) return rc;
+    int rc = ASPIRE_OK;
+    switch (plan.form) {
+    case Form::Chunk:
+        if ((rc = launch_chunk_prep(a, t, job_off, J, max_job, s0))) return rc;
+        rc = launch_pair_fused_chunk_l2max(a, chunk_items_bound(J, C, max_job), s0);
+        break;
+    case Form::Rec16:
+        if ((rc = launch_rec_prep(a, t, job_off, J, max_job, s0))) return rc;
+        rc = launch_pair_tile16_rec_l2max(a, 2 * chunk_items_bound(J, C, max_job), s0);
+        break;
+    case Form::FusedSelf:
+    case Form::FusedTables: rc = launch_pair_fused_l2max(a, groups_bound, s0, plan.form == Form::FusedSelf); break;
+    case Form::Hybrid:
+        if ((rc = arm_long_pair_gate(a, t.gate, C, s0))) return rc;
+        if ((rc = launch_pair_fused_l2max(a, groups_bound, s0))) return rc;
+        [[fallthrough]];
+    case Form::Stream16: rc = launch_pair_tile16_l2max(a, 2 * groups_bound, s0); break;
+    case Form::Tiles: rc = launch_l2max_tiles(a, plan.max_rows, 1, s0); break;
+    default: rc = launch_pair_generic(a, 1, 0, q->max_len, c->max_len, s0); break;      // Form::Generic
     }
+    if (rc) return rc;
     return rank.rank(scores);
 }
 
@@ -845,4 +702,72 @@ extern "C" int aspire_group_diameter_f32(const aspire_repset* q, const aspire_re
     const int64_t blocks = pairing == ASPIRE_PAIR_PAIRED ? ngroups : ngroups * q->n;     // (query, group) folded into grid.x
     ASPIRE_REQUIRE(blocks < ((int64_t)1 << 31), ASPIRE_ERR_UNSUPPORTED, "too many (query, group) boxes: %lld", (long long)blocks);
     return launch_group_diameter(a, group, ngroups, blocks, diameter, (hipStream_t)stream);
+}
+
+// Diagnostics: the family a call would take, as short text -- the plan of the entry family `kind` and, where the plan runs the
+// stages on workspace slots, their kernels for the call's first chunk.  Runs no kernel and needs no GPU; the only place that
+// renders a plan as text.  Batched kinds take the jobs as equal shares of the candidates (max_job = ceil(c->n / q->n)).
+extern "C" int aspire_debug_score_form(int kind, const aspire_repset* q, const aspire_repset* c, int pairing, const aspire_ot_params* prm,
+                                       int asked, size_t workspace_bytes, char* buf, size_t len) {
+    ASPIRE_REQUIRE(q && c && buf && len > 0, ASPIRE_ERR_INVALID_ARG, "null repset / buffer");
+    ASPIRE_REQUIRE(q->n > 0 && c->n > 0, ASPIRE_ERR_INVALID_ARG, "an empty call has no form");
+    const bool ot = kind == ASPIRE_FORM_OT || kind == ASPIRE_FORM_OT_BATCH;
+    ASPIRE_REQUIRE(!ot || prm, ASPIRE_ERR_INVALID_ARG, "null params");
+    const int stages = (asked >> 8) & kStageAll ? (asked >> 8) & kStageAll : kStageAll;
+    const bool extra = asked & ASPIRE_ASKED_PAIR_OUTPUTS, cost_only = asked & ASPIRE_ASKED_COST_ONLY;
+    const int64_t J = q->n, C = c->n, max_job = (C + J - 1) / J;
+    static const char* const form_names[] = {"none", "generic", "gram-planes", "gram", "stream16", "fused-stream", "fused-inbox", "fused-qbox",
+                                             "fused-self", "fused-tables", "chunk", "rec16", "one-wave", "tiles", "hybrid"};
+    static const char* const cost_names[] = {"gram", "tile", "cost1", "tile16", "cost1-sub", "cost"};
+    ScorePlan plan{};
+    char stage_text[64] = "";
+    auto render_stages = [&](const CostChoice* cost, const SolveChoice* solve) {
+        size_t n = 0;
+        if (cost) n += snprintf(stage_text + n, sizeof(stage_text) - n, " cost=%s", cost_names[(int)cost->kernel]);
+        if (solve && solve->kernel == Solver::Wave) snprintf(stage_text + n, sizeof(stage_text) - n, " solve=wave");
+        else if (solve) snprintf(stage_text + n, sizeof(stage_text) - n, " solve=block%dx%d%s", solve->lanes * solve->lanes, solve->per_lane,
+                                 solve->repair ? "+repair" : "");
+    };
+    if (kind == ASPIRE_FORM_L2AGG) {
+        plan = plan_l2agg(q, c, pairing, asked & ASPIRE_ASKED_AGG_OTHER ? ASPIRE_AGG_TOP2 : ASPIRE_AGG_MAX, extra, asked & ASPIRE_ASKED_ONE_FORM);
+    } else if (kind == ASPIRE_FORM_L2MAX_BATCH) {
+        plan = plan_l2max_batch(q, c, max_job, asked & ASPIRE_ASKED_ONE_FORM);
+    } else if (kind == ASPIRE_FORM_OT) {
+        const bool csr = q->ext == 0 && c->ext == 0;
+        const aspire_repset q32 = csr ? tile_bound_set(q) : *q, c32 = csr ? tile_bound_set(c) : *c;
+        if (!workspace_bytes) workspace_bytes = aspire_ot_workspace_bytes(&q32, &c32, pairing);
+        plan = plan_ot(q, c, pairing, prm, OtAsked{extra, (asked & ASPIRE_ASKED_DIAMETERS) != 0, cost_only, true, workspace_bytes});
+        if (plan.form == Form::Tiles) {
+            const size_t per_cand = per_cand_bytes(&q32, &c32, pairing);
+            ASPIRE_REQUIRE(workspace_bytes >= per_cand + qbox_bytes(q) + kWsSlack, ASPIRE_ERR_INVALID_ARG, "workspace too small");
+            const int64_t per_chunk = ot_cand_per_chunk(q, workspace_bytes, per_cand), cands = per_chunk < C ? per_chunk : C;
+            const int64_t n_slots = cands * (pairing == ASPIRE_PAIR_PAIRED ? 1 : J);
+            const int T = (plan.max_rows + 7) / 8;
+            if (ot_chunk_one_wave(plan, &q32, &c32, pairing, cands, cost_only)) {
+                plan.form = Form::OneWave;
+            } else {
+                const CostChoice cost = cost_kernel_form(T, &q32, &c32, pairing, plan.gram, false, false, cands, 0, 0, n_slots);
+                const SolveChoice solve = solver_form(T, n_slots, plan.max_rows, extra, 0);
+                render_stages(&cost, cost_only ? nullptr : &solve);
+            }
+        }
+    } else if (kind == ASPIRE_FORM_OT_BATCH) {
+        plan = plan_ot_batch(q, c, max_job, prm, asked & ASPIRE_ASKED_PLAN_SIM ? ASPIRE_OT_PLAN_SIM : ASPIRE_OT_SIMILARITY, stages);
+        const int T = (plan.max_rows + 7) / 8;
+        const SolveChoice solve = solver_form(T, C, plan.max_rows, false, plan.tile_form || plan.form == Form::Rec16 ? 3 : 0);
+        if (plan.form == Form::Rec16) {
+            render_stages(nullptr, &solve);
+        } else if (plan.form == Form::Tiles || plan.form == Form::Hybrid) {
+            const CostChoice cost = cost_kernel_form(T, q, c, kPairMapped, false, plan.tile_form, true, C, J, (max_job + 3) / 4, C);
+            render_stages(stages & kStageCost ? &cost : nullptr, stages & kStageSolve ? &solve : nullptr);
+        }
+    } else {
+        ASPIRE_REQUIRE(false, ASPIRE_ERR_INVALID_ARG, "bad form kind %d", kind);
+    }
+    char text[128];
+    const int n = snprintf(text, sizeof(text), "%s%s%s%s%s", plan.tables_first ? "tables+" : "", plan.qbox_first ? "qbox+" : "",
+                           form_names[(int)plan.form], plan.then_generic ? "+generic" : "", stage_text);
+    ASPIRE_REQUIRE((size_t)n + 1 <= len, ASPIRE_ERR_INVALID_ARG, "buffer too small");
+    memcpy(buf, text, (size_t)n + 1);
+    return ASPIRE_OK;
 }

@@ -1,5 +1,6 @@
 // What the scoring units share: the device-side argument structs of the kernels, the constants kernels and host agree on, and the
-// host launchers each kernel family's unit offers to the dispatch in score.hip (one comment line names the unit).
+// host launchers each kernel family's unit offers to the dispatch in score.hip (one comment line names the unit).  WHEN a family
+// runs is not here: forms.h / forms.hip hold every rule and threshold, the launchers below only carry a decision out.
 #pragma once
 #include <type_traits>
 
@@ -170,9 +171,6 @@ int launch_chunk_prep(ScoreArgs& a, const BatchTables& t, const int32_t* job_off
 int launch_rec_prep(const ScoreArgs& a, const BatchTables& t, const int32_t* job_off, int64_t J, int64_t max_job, hipStream_t stream);
 
 // gram.hip: matrix-core form of the pairwise-cost stage (host launchers; see the file header)
-bool gram_path_wanted(const aspire_repset* q, const aspire_repset* c, int pairing);
-bool gram_planes_wanted_l2max(const aspire_repset* q, const aspire_repset* c, int pairing);
-bool gram_planes_wanted_ot(const aspire_repset* q, const aspire_repset* c, int pairing, bool caller_diameters);
 size_t gram_extra_bytes_per_cand(void);
 int launch_pair_gram_ot(const ScoreArgs& a, int T, int mr_q, int mr_c, float* cost, float* neg, float* diam2, float* qbox,
                         float* cbox, hipStream_t stream);
@@ -215,9 +213,6 @@ int launch_sent_cdist_backward(const RepSet& q, const RepSet& c, const float* gr
                                int rows_c, hipStream_t stream);
 
 // fused.hip: cost + Sinkhorn solve in one launch for documents of <= 8 rows (CSR inputs, CROSS or MAPPED pairing)
-bool fused_self_ok(int64_t jobs, const aspire_ot_params* prm);
-bool fused_inbox_ok(const aspire_repset* q, const float* diameter);
-bool fused_path_ok(const aspire_repset* q, const aspire_repset* c);
 // (a pair whose shifted sums leave fp32 range is solved again in the max-shifted form by the wave that finds it: fused.hip, solve_safe)
 int launch_pair_fused(const ScoreArgs& a, int64_t groups_bound, const float* qbox, hipStream_t stream);
 // split.hip: the same work with streaming waves and solver waves as two roles of one workgroup (where the fused kernel's SELF / QBOX
@@ -230,7 +225,6 @@ int launch_pair_split(const ScoreArgs& a, hipStream_t stream);
 int launch_pair_fused_chunk(const ScoreArgs& a, int64_t items_bound, const float* qbox, hipStream_t stream);
 int launch_pair_fused_chunk_l2max(const ScoreArgs& a, int64_t items_bound, hipStream_t stream);
 int launch_pair_fused_l2max(const ScoreArgs& a, int64_t groups_bound, hipStream_t stream, bool self = false);
-bool tile16_path_ok(const aspire_repset* q, const aspire_repset* c, int pairing);
 int launch_pair_tile16_l2max(const ScoreArgs& a, int64_t items_bound, hipStream_t stream);
 int launch_pair_tile16(const ScoreArgs& a, float* cost, float* neg, float* diam2, int64_t items_bound, const float* qbox,
                        hipStream_t stream);

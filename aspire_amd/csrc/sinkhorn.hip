@@ -18,6 +18,7 @@
 
 #include "common.h"
 #include "tuning.h"
+#include "forms.h"
 #include "score_types.h"
 #include "score_device.h"
 #include "exact_d2.h"
@@ -986,48 +987,38 @@ __global__ void __launch_bounds__(256) sinkhorn_repair_kernel(ScoreArgs a, PairW
 // ---------------------------------------------------------------------------------------------
 // ---- stage 2: one Sinkhorn solve per workspace slot.  n_slots: the slots of this launch (MAPPED: an upper bound, the
 // kernels read the exact range of jobs [a.job0, a.job1) from job_off). --------------------------------------------------
-// One solve per wave has the lowest latency (15.4 vs 26.7 us per call at 50 pairs), the block forms several times the
-// throughput; measured crossovers (1 x N x 8, cost + solve, us): N = 5000: wave 58 / 16-lane block 64 / 4-lane block 68;
-// 8000: 88 / 83 / 89; 12000: 119 / 109 / 106.  S = 12 / 20: even at 2000 / ~2500, block ahead at 3000.
+// Which solver and how many lanes per pair: forms.hip (solver_form).
 int launch_sinkhorn_stage(const ScoreArgs& a, int T_rt, float* cost, float* neg, float* diam2, int64_t n_slots, int max_rows, bool extra,
                           int form_hint, hipStream_t stream) {
+    const SolveChoice ch = solver_form(T_rt, n_slots, max_rows, extra, form_hint);
     return dispatch_T(8 * T_rt, [&](auto tc) -> int {
         constexpr int T = decltype(tc)::value;
         const PairWs<T> ws{cost, neg, diam2};
-        const int pinned = tuning().sinkhorn_form;
-        const int form = pinned ? pinned : form_hint ? form_hint
-                         : T == 1 ? (n_slots < 7000 ? 1 : n_slots < 10000 ? 5 : 3)
-                                  : (n_slots >= 2500 ? 3 : 1);
-        if (form >= 3 && !extra) {
-            // lanes per pair side LD and entries per lane side R: the smallest block grid that covers max_rows
+        if (ch.kernel == Solver::Block) {
+            // the layouts that are built: LD lanes per pair side, R entries per lane side, LD * R rows within this T's last tile
             auto launch_block = [&](auto ldc, auto rc) {
                 constexpr int LD = decltype(ldc)::value, R = decltype(rc)::value, PPB = 4 * 64 / (LD * LD);
                 if constexpr (LD * R <= 8 * T && LD * R > 8 * (T - 1)) {
-                    hipLaunchKernelGGL((sinkhorn_block_kernel<T, LD, R>), dim3((unsigned)((n_slots + PPB - 1) / PPB)),
-                                       dim3(256), 0, stream, a, ws, n_slots);
+                    if (ch.lanes == LD && ch.per_lane == R)
+                        hipLaunchKernelGGL((sinkhorn_block_kernel<T, LD, R>), dim3((unsigned)((n_slots + PPB - 1) / PPB)),
+                                           dim3(256), 0, stream, a, ws, n_slots);
                 }
             };
             using I2 = std::integral_constant<int, 2>;
             using I4 = std::integral_constant<int, 4>;
-            const int r4 = (max_rows + 3) / 4;
-            // Lanes per pair.  The dense layouts (documents of <= 8 rows: ONE lane per pair, 8 x 8 entries, no cross-lane step at
-            // all; 9 .. 16 rows: 2 x 2 lanes of 6 x 6 / 8 x 8 entries) need a third fewer issue slots per pair than the wide ones
-            // (2 x 2 lanes of 4 x 4; 4 x 4 lanes of 3 x 3 / 4 x 4): 32 x 50 000 x 8 0.90 -> 0.74 ms per launch, 128 x 8192 x 12
-            // 1.10 -> 0.76, x 16 1.59 -> 1.27 -- but hold 64 / 16 pairs per wave, so only grids that still fill the chip take them.
-            const bool dense = form == 6 || (form != 7 && n_slots >= (T == 1 ? 196608 : 49152));
-            if (T == 1 && form == 5) launch_block(I4{}, I2{});
-            else if (T == 1 && dense) launch_block(std::integral_constant<int, 1>{}, std::integral_constant<int, 8>{});
-            else if (T == 1) launch_block(I2{}, I4{});
-            else if (r4 == 3 && dense) launch_block(I2{}, std::integral_constant<int, 6>{});
-            else if (r4 == 4 && dense) launch_block(I2{}, std::integral_constant<int, 8>{});
-            else if (r4 == 3) launch_block(I4{}, std::integral_constant<int, 3>{});
-            else if (r4 == 4) launch_block(I4{}, I4{});
-            else if (r4 == 5) launch_block(I4{}, std::integral_constant<int, 5>{});
-            else if (r4 == 6) launch_block(I4{}, std::integral_constant<int, 6>{});
-            else if (r4 == 7) launch_block(I4{}, std::integral_constant<int, 7>{});
-            else launch_block(I4{}, std::integral_constant<int, 8>{});
+            launch_block(std::integral_constant<int, 1>{}, std::integral_constant<int, 8>{});
+            launch_block(I2{}, I4{});
+            launch_block(I2{}, std::integral_constant<int, 6>{});
+            launch_block(I2{}, std::integral_constant<int, 8>{});
+            launch_block(I4{}, I2{});
+            launch_block(I4{}, std::integral_constant<int, 3>{});
+            launch_block(I4{}, I4{});
+            launch_block(I4{}, std::integral_constant<int, 5>{});
+            launch_block(I4{}, std::integral_constant<int, 6>{});
+            launch_block(I4{}, std::integral_constant<int, 7>{});
+            launch_block(I4{}, std::integral_constant<int, 8>{});
             ASPIRE_LAUNCH_OK();
-            if (form != 4)      // pairs whose sums left fp32 range (NaN score) are solved again with the max-shifted solver
+            if (ch.repair)
                 hipLaunchKernelGGL(sinkhorn_repair_kernel<T>, dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0, stream, a, ws,
                                    n_slots);
         } else {

@@ -359,13 +359,6 @@ __global__ void __launch_bounds__(256, 2) pair_tile16_kernel(ScoreArgs a, PairWs
 
 }  // namespace
 
-// Documents of 9 .. 16 rows (both sides), CSR, CROSS or MAPPED pairing with the job tables built.
-bool tile16_path_ok(const aspire_repset* q, const aspire_repset* c, int pairing) {
-    if (q->ext != 0 || c->ext != 0 || (pairing != ASPIRE_PAIR_CROSS && pairing != kPairMapped)) return false;
-    const int mq = q->max_len, mc = c->max_len;
-    return mq > 0 && mc > 0 && mq <= 16 && mc <= 16 && (mq > 8 || mc > 8);
-}
-
 // the launches' waves: 256 * 8 resident ones unless TILE_WAVES pins fewer (tests: several items per wave)
 static int64_t tile_wave_cap() { return tuning().tile_waves > 0 ? tuning().tile_waves : 256 * 8; }
 

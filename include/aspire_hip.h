@@ -1106,7 +1106,25 @@ int aspire_topk_merge_keys(const uint64_t* keys, int64_t R, int64_t Q, int64_t k
  *                      2 costs, 4 Sinkhorn solves (2 and 4 are ONE kernel in the fused form: either bit launches it),
  *                      8 rank (bench.py times the stages of a pass one by one this way, after a full call has filled
  *                      the workspace)
+ *   aspire_debug_score_form  the kernel family a call would take, as short text in buf[0 .. len) -- e.g. "fused-self",
+ *                      "tables+tiles cost=tile solve=block4x4+repair" -- without running it (no GPU needed).  kind: the entry family
+ *                      (ASPIRE_FORM_*); the decision reads the sets' n / ext / max_len / planes / doc_box alone; asked: ASPIRE_ASKED_*
+ *                      bits or'ed, for ASPIRE_FORM_OT_BATCH plus the debug entry's stage mask << 8 (0 = all stages); the otAspire
+ *                      kinds read ONE_FORM and the scaling from prm; workspace_bytes 0 = what aspire_ot_workspace_bytes suggests.
+ *                      Batched kinds take the jobs as equal shares of the candidates (max_job = ceil(c->n / q->n)).
  * ------------------------------------------------------------------------------------------- */
+#define ASPIRE_FORM_L2AGG 0       /* aspire_l2agg_scores_f32 / aspire_l2max_scores_f32 */
+#define ASPIRE_FORM_OT 1          /* aspire_ot_sinkhorn_f32 / aspire_ot_rank_f32 */
+#define ASPIRE_FORM_OT_BATCH 2    /* aspire_ot_rank_batch_f32 */
+#define ASPIRE_FORM_L2MAX_BATCH 3 /* aspire_l2max_rank_batch_f32 */
+#define ASPIRE_ASKED_PAIR_OUTPUTS 1 /* pair_sims / plan / distribution outputs */
+#define ASPIRE_ASKED_DIAMETERS 2    /* the caller's own diameters */
+#define ASPIRE_ASKED_COST_ONLY 4    /* aspire_debug_ot_cost_stage_f32 */
+#define ASPIRE_ASKED_PLAN_SIM 8     /* want == ASPIRE_OT_PLAN_SIM */
+#define ASPIRE_ASKED_AGG_OTHER 16   /* an aggregation other than ASPIRE_AGG_MAX */
+#define ASPIRE_ASKED_ONE_FORM 32    /* ASPIRE_CDIST_ONE_FORM (the max-sim kinds) */
+int aspire_debug_score_form(int kind, const aspire_repset* q, const aspire_repset* c, int pairing, const aspire_ot_params* prm,
+                            int asked, size_t workspace_bytes, char* buf, size_t len);
 int aspire_debug_set(const char* key, const char* value);
 /* the switch's current value as aspire_debug_set takes it ("" = default) into buf[0 .. len); for scoped pins that restore
  * what was set before them (an ASPIRE_HIP_* environment setting, an enclosing pin) */
