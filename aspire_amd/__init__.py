@@ -11,7 +11,7 @@ from .pair_distances import (AllPairMaskedWasserstein, AllPairMaskedAttention, a
 from .rank_loss import RankLoss, SupAlignRankLoss, cross_doc_l1, sent_reps_from_hidden  # noqa: F401
 from .train_encoder import HipBertTrainEncoder  # noqa: F401
 from .cls_train import BiEncTrain, ClsTripletLoss, IctEncTrain, IctLoss, SentEncTrain  # noqa: F401
-from .optim import HipAdam, HipAdagrad  # noqa: F401
+from .optim import HipAdam, HipAdamW, HipAdagrad, clip_grad_norm_, grad_norm  # noqa: F401
 from .trainer import RankTrainer  # noqa: F401
 from .ddp import GradReducer, RankTrainerDDP, broadcast_parameters  # noqa: F401
 from .batchers import JsonlRankBatches, rank_batch_sources, write_shuffled_copies  # noqa: F401

@@ -91,6 +91,11 @@ class OptimTensor(ctypes.Structure):
                 ('step', c_int64), ('lr', c_double)]
 
 
+class AdamWTensor(ctypes.Structure):
+    """struct aspire_adamw_tensor"""
+    _fields_ = OptimTensor._fields_ + [('weight_decay', c_double)]
+
+
 class GradTensor(ctypes.Structure):
     """struct aspire_grad_tensor"""
     _fields_ = [('grad', c_void_p), ('n', c_int64)]
@@ -119,10 +124,20 @@ SIGNATURES = {
     'aspire_optim_workspace_bytes': (c_size_t, [c_int64]),
     'aspire_adam_step_f32': (c_int, [ctypes.POINTER(OptimTensor), c_int64, c_double, c_double, c_double, c_void_p, c_size_t, c_void_p]),
     'aspire_adagrad_step_f32': (c_int, [ctypes.POINTER(OptimTensor), c_int64, c_double, c_double, c_void_p, c_size_t, c_void_p]),
+    'aspire_adam_step_scaled_f32': (c_int, [ctypes.POINTER(OptimTensor), c_int64, c_double, c_double, c_double, c_void_p, c_void_p, c_size_t,
+                                            c_void_p]),
+    'aspire_adagrad_step_scaled_f32': (c_int, [ctypes.POINTER(OptimTensor), c_int64, c_double, c_double, c_void_p, c_void_p, c_size_t,
+                                               c_void_p]),
+    'aspire_adamw_step_f32': (c_int, [ctypes.POINTER(AdamWTensor), c_int64, c_double, c_double, c_double, c_void_p, c_void_p, c_size_t,
+                                      c_void_p]),
     'aspire_grad_bucket_elems': (c_int64, [ctypes.POINTER(c_int64), c_int64, ctypes.POINTER(c_int64)]),
     'aspire_grad_bucket_workspace_bytes': (c_size_t, [c_int64]),
     'aspire_grad_bucket_pack_f32': (c_int, [ctypes.POINTER(GradTensor), c_int64, c_double, c_void_p, c_int64, c_void_p, c_size_t,
                                             c_void_p]),
+    'aspire_grad_norm_workspace_bytes': (c_size_t, [ctypes.POINTER(c_int64), c_int64]),
+    'aspire_grad_norm_f32': (c_int, [ctypes.POINTER(GradTensor), c_int64, c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'aspire_grad_scale_workspace_bytes': (c_size_t, [c_int64]),
+    'aspire_grad_scale_f32': (c_int, [ctypes.POINTER(GradTensor), c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     'aspire_bert_planes_bytes': (c_size_t, [ctypes.POINTER(BertWeights)]),
     'aspire_bert_prepare_planes': (c_int, [ctypes.POINTER(BertWeights), c_void_p, c_size_t, c_void_p]),
     'aspire_bert_workspace_bytes': (c_size_t, [ctypes.POINTER(BertWeights), c_int64, c_int64]),

@@ -28,6 +28,8 @@ every run.  Here the three pieces are
                                      on ANY rank keeps ``grad is None`` (torch DDP's rule for a parameter unused everywhere), so the pooler
                                      under ``RankLoss`` never gets an optimizer state or a step count, exactly as in one process; one
                                      without a gradient on THIS rank only gets the other ranks' mean contribution (zeros from here).
+  max_grad_norm                      the norm is taken AFTER the reduction, over the bucket views; every rank holds the same reduced bits
+                                     and forms the same clip coefficient, so clipping adds no collective
   gradient accumulation              the reduction happens ONCE per update group, on the accumulated sums -- not once per backward as
                                      torch DDP does in the reference.  Mathematically the same mean (the scaling and the sum over ranks
                                      are linear); the rounding order differs and the traffic is 1 / update_params_every of it.
@@ -221,7 +223,9 @@ class RankTrainerDDP(RankTrainer):
 
     def _step(self):
         self.reducer.reduce()
-        self.optimizer.step()
+        # with max_grad_norm the norm is taken here, over the bucket views: every rank holds the same reduced bits and forms the same
+        # coefficient, so no further collective is issued; a parameter without a gradient on any rank (grad None) stays out of it
+        self._update()
 
     def _iterate(self, batch):
         checked = self.iteration % self.es_check_every == 0 and self.iteration != 0 and self.early_stop

@@ -1,6 +1,7 @@
 """Torch-tensor front end of the C ABI: device memory and streams come from PyTorch-ROCm, every
 computation happens in libaspire_hip.so.  All tensors given here must already live on the GPU."""
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -865,16 +866,40 @@ def optim_tensor_check(t, name):
 
 OPTIM_TABLE = np.dtype([('param', 'u8'), ('grad', 'u8'), ('state1', 'u8'), ('state2', 'u8'), ('n', 'i8'), ('step', 'i8'), ('lr', 'f8')])
 assert OPTIM_TABLE.itemsize == ctypes.sizeof(_lib.OptimTensor)
+ADAMW_TABLE = np.dtype(OPTIM_TABLE.descr + [('weight_decay', 'f8')])
+assert ADAMW_TABLE.itemsize == ctypes.sizeof(_lib.AdamWTensor)
 _OPTIM_ENTRY = {'adam': lib.aspire_adam_step_f32, 'adagrad': lib.aspire_adagrad_step_f32}
+# rule -> (entry that takes a grad_scale pointer, its table's dtype and record type)
+_OPTIM_SCALED = {'adam': (lib.aspire_adam_step_scaled_f32, OPTIM_TABLE, _lib.OptimTensor),
+                 'adagrad': (lib.aspire_adagrad_step_scaled_f32, OPTIM_TABLE, _lib.OptimTensor),
+                 'adamw': (lib.aspire_adamw_step_f32, ADAMW_TABLE, _lib.AdamWTensor)}
 _OPTIM_WS = {}      # (device index, stream handle) -> the device table of that stream's steps
 
 
-def optim_launch(rule, table, scalars, dev):
+def grad_scale_check(grad_scale, dev):
+    """What the scaled steps read their coefficient from: a one-element fp32 tensor on the step's GPU (grad_norm()'s clip_coef)."""
+    if not isinstance(grad_scale, torch.Tensor) or grad_scale.numel() != 1:
+        raise ValueError('grad_scale: need a one-element tensor')
+    optim_tensor_check(grad_scale, 'grad_scale')
+    if grad_scale.device != dev:
+        raise ValueError(f'grad_scale: on {grad_scale.device}, the step runs on {dev}')
+    return grad_scale
+
+
+def optim_launch(rule, table, scalars, dev, grad_scale=None):
     """One aspire_adam_step_f32 ('adam', scalars = (beta1, beta2, eps)) / aspire_adagrad_step_f32 ('adagrad', (lr_decay, eps)) call on
     dev's current stream over `table`, a numpy array of OPTIM_TABLE records (struct aspire_optim_tensor: device addresses, element
     counts, per-tensor step and lr).  The caller vouches for the addresses: adam_step / adagrad_step build a table from checked
-    tensors, HipAdam / HipAdagrad keep one per set of parameters that have a gradient."""
-    assert table.dtype == OPTIM_TABLE and table.flags.c_contiguous and table.ndim == 1
+    tensors, HipAdam / HipAdagrad keep one per set of parameters that have a gradient.
+    'adamw' (scalars as 'adam'): aspire_adamw_step_f32 over ADAMW_TABLE records (struct aspire_adamw_tensor).  grad_scale: a
+    one-element fp32 tensor on dev -- the step runs on every gradient times it (aspire_*_step_scaled_f32); None: the plain entries."""
+    assert table.flags.c_contiguous and table.ndim == 1
+    if grad_scale is None and rule in _OPTIM_ENTRY:
+        entry, dtype, record, extra = _OPTIM_ENTRY[rule], OPTIM_TABLE, _lib.OptimTensor, ()
+    else:
+        entry, dtype, record = _OPTIM_SCALED[rule]
+        extra = (grad_scale_check(grad_scale, dev).data_ptr() if grad_scale is not None else None,)
+    assert table.dtype == dtype
     n = len(table)
     if n == 0:
         return
@@ -885,11 +910,10 @@ def optim_launch(rule, table, scalars, dev):
         ws = _OPTIM_WS.get(key)
         if ws is None or ws.numel() < lib.aspire_optim_workspace_bytes(n):
             ws = _OPTIM_WS[key] = torch.empty(max(lib.aspire_optim_workspace_bytes(n), 16384), device=dev, dtype=torch.uint8)
-        check(_OPTIM_ENTRY[rule](ctypes.cast(table.ctypes.data, ctypes.POINTER(_lib.OptimTensor)), n, *scalars, ws.data_ptr(), ws.numel(),
-                                 handle))
+        check(entry(ctypes.cast(table.ctypes.data, ctypes.POINTER(record)), n, *scalars, *extra, ws.data_ptr(), ws.numel(), handle))
 
 
-def _optim_step(rule, scalars, params, grads, state1, state2, steps, lrs):
+def _optim_step(rule, scalars, params, grads, state1, state2, steps, lrs, weight_decays=None, grad_scale=None):
     n = len(params)
     assert len(grads) == len(state1) == len(steps) == len(lrs) == n and (state2 is None or len(state2) == n), 'one entry per tensor'
     if n == 0:
@@ -903,7 +927,9 @@ def _optim_step(rule, scalars, params, grads, state1, state2, steps, lrs):
         if not (g.device == dev == s1.device and p.device == dev and g.numel() == p.numel() == s1.numel()
                 and (s2 is None or (s2.device == dev and s2.numel() == p.numel()))):
             raise ValueError(f'tensor {i}: param, grad and state must have one size and live on one device')
-    table = np.empty(n, dtype=OPTIM_TABLE)
+    table = np.empty(n, dtype=ADAMW_TABLE if rule == 'adamw' else OPTIM_TABLE)
+    if rule == 'adamw':
+        table['weight_decay'] = weight_decays
     table['param'] = [t.data_ptr() for t in params]
     table['grad'] = [t.data_ptr() for t in grads]
     table['state1'] = [t.data_ptr() for t in state1]
@@ -911,24 +937,104 @@ def _optim_step(rule, scalars, params, grads, state1, state2, steps, lrs):
     table['n'] = [t.numel() for t in params]
     table['step'] = steps
     table['lr'] = lrs
-    optim_launch(rule, table, scalars, dev)
+    if grad_scale is None:
+        optim_launch(rule, table, scalars, dev)
+    else:
+        optim_launch(rule, table, scalars, dev, grad_scale)
 
 
-def adam_step(params, grads, exp_avgs, exp_avg_sqs, steps, lrs, beta1=0.9, beta2=0.999, eps=1e-8):
+def adam_step(params, grads, exp_avgs, exp_avg_sqs, steps, lrs, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=None):
     """torch.optim.Adam's update of every listed tensor in one launch (aspire_adam_step_f32), in place, on the current stream:
     params / grads / exp_avgs / exp_avg_sqs are lists of dense contiguous fp32 GPU tensors on one device (anything else raises, see
-    optim_tensor_check), steps the per-tensor step numbers (>= 1, this update's), lrs the per-tensor learning rates."""
-    _optim_step('adam', (float(beta1), float(beta2), float(eps)), params, grads, exp_avgs, exp_avg_sqs, steps, lrs)
+    optim_tensor_check), steps the per-tensor step numbers (>= 1, this update's), lrs the per-tensor learning rates.  grad_scale: a
+    one-element fp32 GPU tensor; the update then runs on every gradient times it (aspire_adam_step_scaled_f32), the gradients in
+    memory untouched."""
+    _optim_step('adam', (float(beta1), float(beta2), float(eps)), params, grads, exp_avgs, exp_avg_sqs, steps, lrs, grad_scale=grad_scale)
 
 
-def adagrad_step(params, grads, sums, steps, lrs, lr_decay=0.0, eps=1e-10):
+def adagrad_step(params, grads, sums, steps, lrs, lr_decay=0.0, eps=1e-10, grad_scale=None):
     """torch.optim.Adagrad's update of every listed tensor in one launch (aspire_adagrad_step_f32); arguments as adam_step's."""
-    _optim_step('adagrad', (float(lr_decay), float(eps)), params, grads, sums, None, steps, lrs)
+    _optim_step('adagrad', (float(lr_decay), float(eps)), params, grads, sums, None, steps, lrs, grad_scale=grad_scale)
+
+
+def adamw_step(params, grads, exp_avgs, exp_avg_sqs, steps, lrs, weight_decays, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=None):
+    """torch.optim.AdamW's update (decoupled decay, per-tensor weight_decays) in one launch (aspire_adamw_step_f32); else as adam_step."""
+    _optim_step('adamw', (float(beta1), float(beta2), float(eps)), params, grads, exp_avgs, exp_avg_sqs, steps, lrs, weight_decays,
+                grad_scale)
 
 
 GRAD_TABLE = np.dtype([('grad', 'u8'), ('n', 'i8')])
 assert GRAD_TABLE.itemsize == ctypes.sizeof(_lib.GradTensor)
 _GRAD_WS = {}       # (device index, stream handle) -> the device table of that stream's packs
+
+
+_NORM_WS = {}       # (device index, stream handle) -> the table and the partial sums of that stream's norms
+
+
+def _grad_table(grads, dev, name):
+    grads = [g for g in grads if g is not None and g.numel()]
+    for i, g in enumerate(grads):
+        optim_tensor_check(g, f'{name}: gradient {i}')
+        if g.device != dev:
+            raise ValueError(f'{name}: gradient {i} is on {g.device}, expected {dev}')
+    table = np.zeros(len(grads), dtype=GRAD_TABLE)
+    table['grad'] = [g.data_ptr() for g in grads]
+    table['n'] = [g.numel() for g in grads]
+    return table
+
+
+def grad_norm(grads, max_norm, out=None):
+    """aspire_grad_norm_f32 on the current stream of the gradients' device: -> a two-element fp32 GPU tensor, [0] the L2 norm of all
+    of `grads` (dense contiguous fp32 GPU tensors on one device, optim_tensor_check; None entries stay out) viewed as one vector,
+    [1] torch's clip coefficient clamp(max_norm / (norm + 1e-6), max=1).  Nothing is read back to the host."""
+    grads = [g for g in grads if g is not None]
+    max_norm = float(max_norm)
+    if not (math.isfinite(max_norm) and max_norm > 0):
+        raise ValueError(f'grad_norm: max_norm = {max_norm} must be finite and above 0')
+    dev = out.device if out is not None else grads[0].device if grads else require_gpu()
+    table = _grad_table(grads, dev, 'grad_norm')
+    if out is None:
+        out = torch.empty(2, device=dev, dtype=torch.float32)
+    elif out.numel() != 2:
+        raise ValueError('grad_norm: out must have two elements')
+    optim_tensor_check(out, 'grad_norm: out')
+    n = len(table)
+    with torch.cuda.device(dev):
+        handle = torch.cuda.current_stream().cuda_stream
+        key = (dev.index, handle)
+        sizes = np.ascontiguousarray(table['n'])        # (a column of a record array is strided: the library gets a packed copy)
+        need = lib.aspire_grad_norm_workspace_bytes(sizes.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)) if n else None, n)
+        ws = _NORM_WS.get(key)
+        if ws is None or ws.numel() < need:
+            ws = _NORM_WS[key] = torch.empty(max(need, 1 << 18), device=dev, dtype=torch.uint8)
+        check(lib.aspire_grad_norm_f32(ctypes.cast(table.ctypes.data, ctypes.POINTER(_lib.GradTensor)), n, max_norm, out.data_ptr(),
+                                       ws.data_ptr(), ws.numel(), handle))
+    return out
+
+
+def grad_scale_(grads, scale):
+    """aspire_grad_scale_f32: every listed gradient times `scale` (a one-element fp32 GPU tensor), in place, in one launch."""
+    grads = [g for g in grads if g is not None]
+    if not grads:
+        return
+    dev = grads[0].device
+    grad_scale_check(scale, dev)
+    table = _grad_table(grads, dev, 'grad_scale_')
+    n = len(table)
+    if n == 0:
+        return
+    with torch.cuda.device(dev):
+        handle = torch.cuda.current_stream().cuda_stream
+        key = (dev.index, handle)
+        ws = _GRAD_WS.get(key)
+        need = lib.aspire_grad_scale_workspace_bytes(n)
+        if ws is None or ws.numel() < need:
+            ws = _GRAD_WS[key] = torch.empty(max(need, 16384), device=dev, dtype=torch.uint8)
+        check(lib.aspire_grad_scale_f32(ctypes.cast(table.ctypes.data, ctypes.POINTER(_lib.GradTensor)), n, scale.data_ptr(), ws.data_ptr(),
+                                        ws.numel(), handle))
+    for g in grads:
+        if not g.is_inference():
+            torch.autograd.graph.increment_version(g)
 
 
 def grad_bucket_layout(numels):

@@ -1,5 +1,6 @@
 """The reference trainer's two update rules (src/learning/trainer.py:178-181: ``optim.Adam`` / ``optim.Adagrad`` at torch's defaults) on
 this library's multi-tensor kernel (optim.hip): ONE launch per ``step()`` over every tensor, of every param group, that has a gradient.
+Beyond the reference: AdamW and clipping of the global gradient norm, inside the same launch.
 
 ``HipAdam`` / ``HipAdagrad`` are ``torch.optim.Optimizer`` subclasses: torch's and transformers' schedulers drive
 ``param_groups[...]['lr']`` as they drive torch's optimizers, and the state keeps torch's keys and layouts -- ``'step'`` a CPU float32
@@ -10,8 +11,15 @@ As in torch, the step count is per parameter: one with ``grad is None`` (or ``re
 advance, and its state is created when it first has a gradient.  The arithmetic is torch's single-tensor formulas in fp32
 (include/aspire_hip.h states them).
 
+``HipAdamW`` is ``torch.optim.AdamW`` on the same launch: decoupled decay, ``p *= 1 - lr * weight_decay`` in front of Adam's update, with
+``lr`` and ``weight_decay`` per tensor in the table, so param groups that differ in them alone (``decay_groups``) stay ONE launch.
+``step(closure=None, grad_scale=None)`` on all three: ``grad_scale`` is a one-element fp32 GPU tensor by which every gradient is
+multiplied as the kernel loads it (``.grad`` is left as it is) -- the clip coefficient of ``grad_norm(parameters, max_norm)``, which
+leaves the global L2 norm and torch's coefficient on the GPU without a host synchronisation (grad_norm.hip).  ``clip_grad_norm_`` is
+torch's in-place form: the norm, then one launch that multiplies every gradient.
+
 Failing loudly: a sparse gradient or a parameter / gradient that is not on the GPU raises RuntimeError, not fp32 TypeError, not contiguous
-ValueError; ``weight_decay != 0``, ``amsgrad``, ``maximize``, ``capturable``, ``differentiable``, a tensor ``lr`` and (Adagrad)
+ValueError; ``weight_decay != 0`` (coupled L2 decay: ``HipAdam`` / ``HipAdagrad``), ``amsgrad``, ``maximize``, ``capturable``, ``differentiable``, a tensor ``lr`` and (Adagrad)
 ``initial_accumulator_value != 0`` raise NotImplementedError -- at construction, and again at ``step()`` for values that arrived through
 ``load_state_dict`` or a param group edited by hand.  ``foreach`` / ``fused`` in a loaded group are torch's choice among ITS
 implementations and are ignored.  ``step(closure)`` evaluates the closure once, with grad enabled, before the update (torch's pattern).
@@ -33,6 +41,7 @@ _UNBUILT = ('amsgrad', 'maximize', 'capturable', 'differentiable')
 class _HipOptimizer(torch.optim.Optimizer):
     _torch_class = None
     _state_keys = ()
+    _decoupled_decay = False        # HipAdamW: weight_decay is built, as a per-tensor column of the table
 
     def __init__(self, params, **hyper):
         params = list(params)
@@ -50,8 +59,10 @@ class _HipOptimizer(torch.optim.Optimizer):
         name = type(self).__name__
         if isinstance(group['lr'], torch.Tensor):
             raise NotImplementedError(f'{name}: a tensor lr is not built (the kernel takes its scalars from the host)')
-        if group.get('weight_decay', 0) != 0:
-            raise NotImplementedError(f'{name}: weight_decay is not built (the reference trains without)')
+        if isinstance(group.get('weight_decay', 0), torch.Tensor):
+            raise NotImplementedError(f'{name}: a tensor weight_decay is not built')
+        if group.get('weight_decay', 0) != 0 and not self._decoupled_decay:
+            raise NotImplementedError(f'{name}: coupled (L2) weight_decay is not built; HipAdamW has the decoupled one')
         for key in _UNBUILT:
             if group.get(key, False):
                 raise NotImplementedError(f'{name}: {key} is not built')
@@ -113,7 +124,7 @@ class _HipOptimizer(torch.optim.Optimizer):
             launches.setdefault(key, []).append((p, gi, state))
         plan = []
         for (dev, scalars), items in launches.items():
-            table = np.zeros(len(items), dtype=ops.OPTIM_TABLE)
+            table = np.zeros(len(items), dtype=ops.ADAMW_TABLE if self._decoupled_decay else ops.OPTIM_TABLE)
             table['n'] = [p.numel() for p, _, _ in items]
             plan.append(dict(dev=dev, scalars=scalars, table=table, params=[p for p, _, _ in items],
                              slots=np.array([self._slot[p] for p, _, _ in items]),
@@ -123,7 +134,9 @@ class _HipOptimizer(torch.optim.Optimizer):
         return plan
 
     @torch.no_grad()
-    def step(self, closure=None):
+    def step(self, closure=None, grad_scale=None):
+        """grad_scale: a one-element fp32 GPU tensor (grad_norm()'s clip_coef): the update runs on every gradient times it, in the same
+        one launch; .grad is left as it is."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -150,6 +163,8 @@ class _HipOptimizer(torch.optim.Optimizer):
                 self._plans = {}
             plan = self._plans[sig] = self._plan(sig, entries)
         lr_of_group = np.array([float(group['lr']) for group in groups])
+        if self._decoupled_decay:
+            decay_of_group = np.array([float(group['weight_decay']) for group in groups])
         for launch in plan:
             params = launch['params']
             grads = [p.grad for p in params]
@@ -164,7 +179,12 @@ class _HipOptimizer(torch.optim.Optimizer):
             counts = self._step_base.numpy()       # (shares the tensor's memory: every state['step'] is a view of it)
             table['step'] = counts[launch['slots']] + 1.0
             table['lr'] = lr_of_group[launch['group']]
-            ops.optim_launch(self._rule, table, launch['scalars'], launch['dev'])
+            if self._decoupled_decay:
+                table['weight_decay'] = decay_of_group[launch['group']]
+            if grad_scale is None:
+                ops.optim_launch(self._rule, table, launch['scalars'], launch['dev'])
+            else:
+                ops.optim_launch(self._rule, table, launch['scalars'], launch['dev'], grad_scale)
             counts[launch['slots']] += 1.0          # (behind the call: an argument error leaves the counts alone)
         return loss
 
@@ -183,6 +203,21 @@ class HipAdam(_HipOptimizer):
         return float(group['betas'][0]), float(group['betas'][1]), float(group['eps'])
 
 
+class HipAdamW(_HipOptimizer):
+    """torch.optim.AdamW(params, lr, betas, eps, weight_decay) without amsgrad, one HIP launch per step(): decoupled decay
+    p *= 1 - lr * weight_decay in front of Adam's update, lr and weight_decay per tensor in the table -- param groups that differ in
+    them alone (decay_groups) share the launch.  torch's state keys; with weight_decay=0 the bits are HipAdam's."""
+    _torch_class = torch.optim.AdamW
+    _state_keys = ('exp_avg', 'exp_avg_sq')
+    _rule = 'adamw'
+    _decoupled_decay = True
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, **kw):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, **kw)
+
+    _call_scalars = staticmethod(HipAdam._call_scalars)
+
+
 class HipAdagrad(_HipOptimizer):
     """torch.optim.Adagrad(params, lr, lr_decay, eps) without weight decay / initial accumulator value, one HIP launch per step()."""
     _torch_class = torch.optim.Adagrad
@@ -196,3 +231,47 @@ class HipAdagrad(_HipOptimizer):
     @staticmethod
     def _call_scalars(group):
         return float(group['lr_decay']), float(group['eps'])
+
+
+# ---- the global gradient norm and its clip (grad_norm.hip) ----------------------------------------------------------------------------------
+def _grads_of(parameters):
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    return [p.grad for p in parameters if p.grad is not None]
+
+
+def grad_norm(parameters, max_norm):
+    """-> (total_norm, clip_coef): 0-dim views of ONE two-element fp32 GPU tensor -- the L2 norm of every ``p.grad`` viewed as one vector
+    and torch's coefficient clamp(max_norm / (total_norm + 1e-6), max=1), in two launches with no host synchronisation.  For the fused
+    route: ``optimizer.step(grad_scale=clip_coef)`` applies the clip as the step loads each gradient.  The sum of squares is formed in
+    double, so the norm stays finite where torch's fp32 sum overflows (include/aspire_hip.h)."""
+    out = ops.grad_norm(_grads_of(parameters), max_norm)
+    return out[0], out[1]
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None):
+    """torch.nn.utils.clip_grad_norm_ on this library's kernels: the norm (two launches) and ONE multi-tensor launch that multiplies
+    every gradient in place by the coefficient -- by 1.0 too, as torch does.  Returns the total norm as a GPU tensor.  Only the L2 norm
+    is built; the gradients must be what optim_tensor_check takes.  `foreach` is torch's choice among ITS implementations: ignored."""
+    if float(norm_type) != 2.0:
+        raise NotImplementedError(f'clip_grad_norm_: norm_type = {norm_type} is not built (only the L2 norm is)')
+    grads = _grads_of(parameters)
+    out = ops.grad_norm(grads, max_norm)
+    if error_if_nonfinite and not bool(torch.isfinite(out[0])):
+        raise RuntimeError('The total norm of order 2.0 for gradients from `parameters` is non-finite, so it cannot be clipped.')
+    ops.grad_scale_(grads, out[1:])
+    return out[0]
+
+
+def decay_groups(module, weight_decay):
+    """The usual two param groups of a BERT fine-tuning recipe: [{'params': ..., 'weight_decay': weight_decay}, {'params': ...,
+    'weight_decay': 0.0}] -- no decay for parameters whose name ends in 'bias' and for the weights of LayerNorm modules (a
+    torch.nn.LayerNorm, or HuggingFace's naming, '...LayerNorm.weight').  An empty group is left out."""
+    norm_weights = {id(p) for m in module.modules() if isinstance(m, torch.nn.LayerNorm) for p in m.parameters(recurse=False)}
+    decay, no_decay = [], []
+    for name, p in module.named_parameters():
+        plain = name.endswith('bias') or id(p) in norm_weights or 'LayerNorm' in name
+        (no_decay if plain else decay).append(p)
+    groups = [{'params': decay, 'weight_decay': float(weight_decay)}, {'params': no_decay, 'weight_decay': 0.0}]
+    return [g for g in groups if g['params']]

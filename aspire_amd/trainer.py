@@ -10,7 +10,14 @@ project's pieces: a caller's encoder (``HipBertTrainEncoder`` is the intended on
 (``aspire_amd.batchers.rank_batch_sources`` gives both over the jsonl files of 'miswordbienc' / 'miswordpolyenc' / 'sbalisentbienc'; the
 CLS-row models' batches stay the caller's).  ``train_hparams`` has the reference's keys and rules, quirks included:
 
-  update_rule             'adam' -> HipAdam, 'adagrad' -> HipAdagrad, at ``learning_rate``; anything else raises ValueError
+  update_rule             'adam' -> HipAdam, 'adagrad' -> HipAdagrad, at ``learning_rate``; anything else raises ValueError.  Beyond the
+                          reference: 'adamw' -> HipAdamW over ``optim.decay_groups(encoder, weight_decay)`` (no decay on biases and
+                          LayerNorm weights), ``weight_decay`` defaulting to 0.01
+  max_grad_norm           beyond the reference; absent, None or 0: off.  Otherwise every update is clipped to this global L2 norm
+                          (torch.nn.utils.clip_grad_norm_'s rule): ``optim.grad_norm`` over the gradients in .grad, its coefficient
+                          handed to ``optimizer.step(grad_scale=...)`` -- with accumulation once per update group, on the accumulated
+                          sums.  The norm stays on the GPU (``last_grad_norm``); it is read where the loss is, into
+                          ``loss_history['grad_norm']``
   train_size, batch_size, num_epochs
                           num_batches = ceil(train_size / batch_size) (1 when train_size <= batch_size); total_iters = num_epochs *
                           num_batches -- what the warm-up schedules are told, not a cap: an epoch runs every batch it is given
@@ -70,14 +77,21 @@ class RankTrainer:
         self.total_iters = self.num_epochs * self.num_batches
 
         self.update_rule, self.learning_rate = train_hparams['update_rule'], train_hparams['learning_rate']
-        if self.update_rule not in ('adam', 'adagrad'):
+        if self.update_rule not in ('adam', 'adagrad', 'adamw'):
             raise ValueError('Unknown upate rule: {:}'.format(self.update_rule))
+        self.max_grad_norm = float(train_hparams.get('max_grad_norm') or 0.0)
+        if self.max_grad_norm < 0.0 or not math.isfinite(self.max_grad_norm):
+            raise ValueError('max_grad_norm = {:} must be finite and >= 0'.format(self.max_grad_norm))
+        self.last_grad_norm = None      # the last update's total norm: a GPU tensor, or a float right after load_checkpoint
         self.lr_decay_method, self.decay_lr_every = train_hparams['lr_decay_method'], train_hparams['decay_lr_every']
         if self.lr_decay_method not in ('exponential', 'warmuplin', 'warmupcosine'):
             raise ValueError('Unknown lr_decay_method: {:}'.format(self.lr_decay_method))
         if optimizer is None:
-            from .optim import HipAdam, HipAdagrad
-            optimizer = (HipAdam if self.update_rule == 'adam' else HipAdagrad)(encoder.parameters(), lr=self.learning_rate)
+            from .optim import HipAdam, HipAdamW, HipAdagrad, decay_groups
+            if self.update_rule == 'adamw':
+                optimizer = HipAdamW(decay_groups(encoder, train_hparams.get('weight_decay', 0.01)), lr=self.learning_rate)
+            else:
+                optimizer = (HipAdam if self.update_rule == 'adam' else HipAdagrad)(encoder.parameters(), lr=self.learning_rate)
         self.optimizer = optimizer
         if self.lr_decay_method == 'exponential':
             self.scheduler = torch.optim.lr_scheduler.ExponentialLR(optimizer=optimizer, gamma=train_hparams['decay_lr_by'])
@@ -120,10 +134,23 @@ class RankTrainer:
     def _record_loss(self, objective):
         self.loss_history['loss'].append(float(objective.detach()))
         self.loss_checked_iters.append(self.iteration)
+        if self.last_grad_norm is not None:     # (the one place the norm is read to the host: where the loss just was)
+            self.loss_history['grad_norm'].append(float(self.last_grad_norm))
+
+    def _update(self):
+        """optimizer.step() on the gradients in .grad; with max_grad_norm, clipped: the norm of the gradients, then the step with the
+        coefficient as its grad_scale (nothing is read back to the host)"""
+        if not self.max_grad_norm:
+            self.optimizer.step()
+            return
+        from . import optim
+        params = [p for group in self.optimizer.param_groups for p in group['params']]
+        self.last_grad_norm, coef = optim.grad_norm(params, self.max_grad_norm)
+        self.optimizer.step(grad_scale=coef)
 
     def _step(self):
         """the update from the gradients in .grad (RankTrainerDDP reduces them over the ranks first)"""
-        self.optimizer.step()
+        self._update()
 
     def _dev_check(self, objective):
         self._record_loss(objective)
@@ -186,6 +213,7 @@ class RankTrainer:
                  'loss_history': dict(self.loss_history), 'loss_checked_iters': list(self.loss_checked_iters),
                  'dev_score_history': list(self.dev_score_history), 'dev_checked_iters': list(self.dev_checked_iters),
                  'dropout_state': tuple(self.encoder.dropout_state()) if hasattr(self.encoder, 'dropout_state') else None,
+                 'last_grad_norm': None if self.last_grad_norm is None else float(self.last_grad_norm),
                  'torch_rng_state': torch.get_rng_state()}
         torch.save(state, path)
 
@@ -201,6 +229,7 @@ class RankTrainer:
         self.dev_score_history, self.dev_checked_iters = list(state['dev_score_history']), list(state['dev_checked_iters'])
         if state['dropout_state'] is not None:
             self.encoder.set_dropout_state(*state['dropout_state'])
+        self.last_grad_norm = state.get('last_grad_norm')
         if state.get('torch_rng_state') is not None:        # (absent in a checkpoint written before it was carried)
             torch.set_rng_state(state['torch_rng_state'])
         self.optimizer.zero_grad()

@@ -451,6 +451,37 @@ int aspire_adagrad_step_f32(const aspire_optim_tensor* tensors, int64_t n_tensor
                             size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The two stabilisers of a BERT fine-tuning recipe inside the same one-launch step: a gradient scale read from the device (the clip
+ * coefficient of aspire_grad_norm_f32 below) and AdamW's decoupled weight decay.  Everything the step above states holds; the two
+ * entries above keep their kernels and their bits.
+ *   grad_scale   one float on the device, 4-byte aligned, read once per workgroup: every rule is applied to g * (*grad_scale) -- ONE
+ *                fp32 multiply, never contracted, in front of the formula: torch's grad.mul_(clip_coef) followed by the step.  The
+ *                gradients in memory are not modified.  NULL: the unscaled kernel (for Adam / Adagrad: the entries above).
+ *   AdamW        p = p * (float)(1 - lr * weight_decay) in front of Adam's update: ONE fp32 multiply, the factor formed in double
+ *                per tensor (torch.optim.AdamW: _single_tensor_adam with decoupled_weight_decay=True).  lr and weight_decay are per
+ *                tensor, so param groups that differ in them alone are one launch.  weight_decay == 0 gives Adam's bits.
+ *                Coupled L2 decay (torch.optim.Adam(weight_decay=...)) and amsgrad are not built.
+ * Errors: those of the step above; weight_decay negative or not finite; a grad_scale that is not 4-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {
+    float*       param;
+    const float* grad;
+    float*       state1;         /* exp_avg */
+    float*       state2;         /* exp_avg_sq */
+    int64_t      n;
+    int64_t      step;
+    double       lr;
+    double       weight_decay;
+} aspire_adamw_tensor;
+
+int aspire_adam_step_scaled_f32(const aspire_optim_tensor* tensors, int64_t n_tensors, double beta1, double beta2, double eps,
+                                const float* grad_scale, void* workspace, size_t workspace_bytes, void* stream);
+int aspire_adagrad_step_scaled_f32(const aspire_optim_tensor* tensors, int64_t n_tensors, double lr_decay, double eps,
+                                   const float* grad_scale, void* workspace, size_t workspace_bytes, void* stream);
+int aspire_adamw_step_f32(const aspire_adamw_tensor* tensors, int64_t n_tensors, double beta1, double beta2, double eps,
+                          const float* grad_scale, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The gradient bucket of data-parallel training (the reference trains through DistributedDataParallel, main_fsim.py ddp_train_model):
  * every gradient of a step packed and scaled into ONE flat fp32 buffer in one launch, so that one all-reduce sums it across the ranks
  * and the optimizer step above reads the reduced gradients where they lie.
@@ -486,6 +517,38 @@ int64_t aspire_grad_bucket_elems(const int64_t* n, int64_t n_tensors, int64_t* o
 size_t aspire_grad_bucket_workspace_bytes(int64_t n_tensors);
 int aspire_grad_bucket_pack_f32(const aspire_grad_tensor* tensors, int64_t n_tensors, double scale, float* flat, int64_t flat_elems,
                                 void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Clipping the global gradient norm (torch.nn.utils.clip_grad_norm_, L2): the norm of all listed gradients viewed as one vector and
+ * torch's clip coefficient, left on the device -- no host synchronisation anywhere -- for the scaled steps above to read.
+ *   out[0]       the L2 norm.  Every element is squared in double (an fp32 square is exact there); each chunk of 4096 elements of
+ *                a tensor gives one double partial (fixed lane ownership, fixed tree); a second launch of one workgroup adds the
+ *                partials in a fixed order, takes the square root in double and rounds once to fp32.  The double sum of at most 2^27
+ *                exact squares is off by at most 2^-26 relative: out[0] lies within 1 ulp of float(sqrt(exact sum of squares)).
+ *                A deliberate departure from torch: because the sum is in double, gradients of 1e20 give a finite norm where
+ *                torch's fp32 sum of squares overflows to inf.
+ *   out[1]       the coefficient, in fp32 exactly as torch.nn.utils.clip_grads_with_norm_ forms it:
+ *                clamp((1 / (out[0] + 1e-6f)) * (float)max_norm, max = 1) -- `max_norm / tensor` is tensor.reciprocal() * max_norm
+ *                in torch -- every operation rounded once.  A NaN norm gives NaN, an infinite norm 0.
+ *   tensors[i]   grad: n fp32 elements on the device, 4-byte aligned (16-byte aligned ones are read with 16-byte loads), or NULL:
+ *                no gradient, the tensor stays out of the norm, as does one with n == 0
+ *   One partial per chunk (not per workgroup), the same element-to-lane ownership on the 16-byte and the scalar path, no atomics,
+ *   one writer per word: the bits depend neither on the grid, nor on where a gradient's storage starts, nor on the run.  With no
+ *   element at all the norm is 0.  Nothing but out[0], out[1] and the workspace is written.
+ *   workspace    device memory of at least aspire_grad_norm_workspace_bytes(n, n_tensors) bytes (the table + one double per chunk;
+ *                0 for a negative count), 16-byte aligned; the rules of the optimizer step's workspace apply
+ * aspire_grad_scale_f32: grad_i[j] *= *scale in place for every listed gradient, ONE fp32 multiply per element in one launch (the
+ * second half of clip_grad_norm_; `scale` = out + 1).  Its workspace holds the table alone.
+ * Errors, all before the device is touched, the offending value in aspire_last_error(): ASPIRE_ERR_INVALID_ARG for a max_norm that
+ * is not a finite float above 0; out / scale NULL or not 4-byte aligned; n_tensors < 0; a NULL table with n_tensors > 0; a tensor
+ * with n < 0 or a gradient pointer that is not 4-byte aligned; a workspace that is NULL, too small or not 16-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+size_t aspire_grad_norm_workspace_bytes(const int64_t* n, int64_t n_tensors);
+int aspire_grad_norm_f32(const aspire_grad_tensor* tensors, int64_t n_tensors, double max_norm, float* out, void* workspace,
+                         size_t workspace_bytes, void* stream);
+size_t aspire_grad_scale_workspace_bytes(int64_t n_tensors);
+int aspire_grad_scale_f32(const aspire_grad_tensor* tensors, int64_t n_tensors, const float* scale, void* workspace,
+                          size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * caching_score's document-level term (src/learning/facetid_models/disent_models.py:305-307, taken when
