@@ -163,6 +163,14 @@ SIGNATURES = {
     'aspire_bert_layers_backward_cls_f32': (c_int, [ctypes.POINTER(BertWeights), c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
                                                     c_void_p, c_void_p, c_size_t, c_void_p, ctypes.POINTER(BertGrads), c_void_p, c_void_p,
                                                     c_size_t, ctypes.POINTER(BertDropout), c_void_p]),
+    'aspire_bert_layers_forward_train_prec_f32': (c_int, [ctypes.POINTER(BertWeights), c_void_p, c_void_p, c_int64, c_int64, c_void_p,
+                                                          c_void_p, c_size_t, c_void_p, c_size_t, ctypes.POINTER(BertDropout), c_int, c_void_p]),
+    'aspire_bert_layers_backward_prec_f32': (c_int, [ctypes.POINTER(BertWeights), c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                                     c_void_p, c_void_p, c_size_t, c_void_p, ctypes.POINTER(BertGrads), c_void_p, c_void_p,
+                                                     c_size_t, ctypes.POINTER(BertDropout), c_int, c_void_p]),
+    'aspire_debug_gemm_bf16_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int64,
+                                           c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, ctypes.c_float, c_void_p, c_void_p,
+                                           c_int64, c_int, c_void_p]),
     'aspire_inbatch_xent_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     'aspire_inbatch_xent_backward_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'aspire_bert_embed_sum_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64,

@@ -8,7 +8,23 @@
 #include "enc_types.h"
 
 namespace aspire {
+
+// The three operand forms of a product C [M, N] = A . B over K (GemmArgs): NT A [M, K] and B [N, K], both k-contiguous (launch_gemm);
+// B_KN B [K, N] n-contiguous (launch_gemm's b_kn); TN A [K, M] and B [K, N] (launch_gemm_tn).  The values are the C ABI's
+// (aspire_debug_gemm_bf16_f32's `form`).
+enum { kGemmNT = 0, kGemmBKN = 1, kGemmTN = 2 };
+
+// enc_gemm_bf16.hip: the same product with every operand element rounded to bf16 once, when its tile is staged, on the bf16 matrix
+// cores with fp32 accumulators and the fp32 epilogues of launch_gemm; any M, N, K, lda / ldb multiples of 4 (ASPIRE_MATMUL_BF16)
+int launch_gemm_bf16(const GemmArgs& g, int batch, int form, hipStream_t st);
+
 namespace {
+
+// A product of the layer stack in the caller's matmul mode: ASPIRE_MATMUL_FP32 launches what the stack always launched
+int launch_product(int matmul, const GemmArgs& g, int batch, int form, hipStream_t st) {
+    if (matmul == ASPIRE_MATMUL_BF16) return launch_gemm_bf16(g, batch, form, st);
+    return form == kGemmTN ? launch_gemm_tn(g, batch, st) : launch_gemm(g, batch, form == kGemmBKN, st);
+}
 
 size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -67,10 +83,12 @@ GemmArgs head_gemm(Heads<TA> A, Heads<TB> B, Heads<float> C, int64_t M, int64_t 
 // columns zero) -> ctx [B L, 768].  With `drop` (training, p_attn > 0): the probabilities stay undropped in `probs` (the soft-max
 // backward wants them), their dropped copy goes to `dropped` (same layout) and the P.V product reads that.
 int attention_gemm(const float* qkv, float* probs, float* ctx, const int64_t* mask, int64_t B, int64_t L, int Lp, int H, int dh,
-                   const float* rel_bias, int rel_span, hipStream_t st, const DropSite* drop = nullptr, float* dropped = nullptr) {
+                   const float* rel_bias, int rel_span, hipStream_t st, const DropSite* drop = nullptr, float* dropped = nullptr,
+                   int matmul = ASPIRE_MATMUL_FP32) {
     const int batch = (int)(B * H);
     // 2. scores[b,h] = Q_bh . K_bh^T   (scale and mask are applied by the softmax kernel)
-    if (int rc = launch_gemm(head_gemm(qkv_heads(qkv, L, dh), qkv_heads(qkv + kD, L, dh), prob_heads(probs, H, L, Lp), L, L, dh, H), batch, false, st))
+    if (int rc = launch_product(matmul, head_gemm(qkv_heads(qkv, L, dh), qkv_heads(qkv + kD, L, dh), prob_heads(probs, H, L, Lp), L, L, dh, H), batch,
+                                kGemmNT, st))
         return rc;
     // 3. masked softmax over keys, in place
     if (int rc = launch_softmax_mask(probs, mask, B * H * L, (int)L, Lp, (int)(H * L), 1.0f / sqrtf((float)dh), rel_bias, rel_span, st)) return rc;
@@ -79,7 +97,8 @@ int attention_gemm(const float* qkv, float* probs, float* ctx, const int64_t* ma
         probs = dropped;
     }
     // 4. ctx[b, :, h*64:(h+1)*64] = P_bh . V_bh        (V is [K = L keys, N = 64] n-contiguous)
-    return launch_gemm(head_gemm(prob_heads(probs, H, L, Lp), qkv_heads(qkv + 2 * kD, L, dh), ctx_heads(ctx, L, dh), L, dh, L, H), batch, true, st);
+    return launch_product(matmul, head_gemm(prob_heads(probs, H, L, Lp), qkv_heads(qkv + 2 * kD, L, dh), ctx_heads(ctx, L, dh), L, dh, L, H), batch,
+                          kGemmBKN, st);
 }
 
 // Where the layer tail leaves its intermediates, [rows, 768] each but u and act [rows, ffn_dim]
@@ -97,24 +116,25 @@ struct TailSlots {
 // (training); without, the epilogue writes act directly (inference).  Slots may share a buffer wherever the earlier one is dead by the
 // time the later one is written -- the launches are stream-ordered and none reads what it writes: s2 may be s1, out may be x, and h may
 // be ctx (the out-projection that reads ctx has finished before LN1 writes h: inference runs so).
+// `matmul` (ASPIRE_MATMUL_*, here and in attention_gemm): the mode of the products alone; every other launch is the same.
 // With `drop` (training, p_hidden > 0; drop[0]: the out-projection's site, drop[1]: FFN2's) the two GEMMs run with their bias and
 // WITHOUT the residual, and a pass of its own forms s = dropout(z) + residual in the same slot.
 int layer_tail(const aspire_bert_weights* w, const aspire_bert_layer& ly, const float* ctx, const float* x, const TailSlots& t, float* out,
-               int64_t rows, hipStream_t st, const DropSite* drop = nullptr) {
+               int64_t rows, hipStream_t st, const DropSite* drop = nullptr, int matmul = ASPIRE_MATMUL_FP32) {
     const int ffn = w->ffn_dim;
     // 5. attention output projection + residual, LayerNorm
-    if (int rc = launch_gemm(linear(ctx, ly.w_o, t.s1, ly.b_o, drop ? nullptr : x, rows, kD, kD), 1, false, st)) return rc;
+    if (int rc = launch_product(matmul, linear(ctx, ly.w_o, t.s1, ly.b_o, drop ? nullptr : x, rows, kD, kD), 1, kGemmNT, st)) return rc;
     if (drop)
         if (int rc = launch_dropout_flat(t.s1, nullptr, x, t.s1, rows * kD, drop[0], st)) return rc;
     if (int rc = launch_layernorm(t.s1, ly.ln1_g, ly.ln1_b, w->ln_eps, t.h, rows, nullptr, st)) return rc;
     // 6. FFN: GELU(h . W1^T + b1) . W2^T + b2 + h, LayerNorm
     if (t.u) {
-        if (int rc = launch_gemm(linear(t.h, ly.w_ffn1, t.u, ly.b_ffn1, nullptr, rows, ffn, kD), 1, false, st)) return rc;
+        if (int rc = launch_product(matmul, linear(t.h, ly.w_ffn1, t.u, ly.b_ffn1, nullptr, rows, ffn, kD), 1, kGemmNT, st)) return rc;
         if (int rc = launch_gelu_forward(t.u, t.act, rows * ffn, st)) return rc;
     } else {
-        if (int rc = launch_gemm(linear(t.h, ly.w_ffn1, t.act, ly.b_ffn1, nullptr, rows, ffn, kD, true), 1, false, st)) return rc;
+        if (int rc = launch_product(matmul, linear(t.h, ly.w_ffn1, t.act, ly.b_ffn1, nullptr, rows, ffn, kD, true), 1, kGemmNT, st)) return rc;
     }
-    if (int rc = launch_gemm(linear(t.act, ly.w_ffn2, t.s2, ly.b_ffn2, drop ? nullptr : t.h, rows, kD, ffn), 1, false, st)) return rc;
+    if (int rc = launch_product(matmul, linear(t.act, ly.w_ffn2, t.s2, ly.b_ffn2, drop ? nullptr : t.h, rows, kD, ffn), 1, kGemmNT, st)) return rc;
     if (drop)
         if (int rc = launch_dropout_flat(t.s2, nullptr, t.h, t.s2, rows * kD, drop[1], st)) return rc;
     return launch_layernorm(t.s2, ly.ln2_g, ly.ln2_b, w->ln_eps, out, rows, nullptr, st);

@@ -35,8 +35,14 @@
 // update of d3 behind backward_layer(l).  The in-batch cross-entropy of two towers' CLS rows has its entry points here as well; the
 // kernels of both: enc_cls_train.hip.
 //
+// The matmul mode (the _prec_ entry points; ASPIRE_MATMUL_*): in ASPIRE_MATMUL_BF16 every product of both layer bodies -- the four
+// projections, Q K^T and P V forward, the ten of the backward -- goes through launch_gemm_bf16 (enc_gemm_bf16.hip: operands rounded to
+// bf16 once when staged, fp32 accumulators and epilogues); every other launch, the tape and the workspace are the same, in fp32.  In
+// ASPIRE_MATMUL_FP32 launch_product (enc_host.h) launches what was launched before there was a mode.
+//
 // This file is host only (the tape's and the workspace's carve, the two layer loops, the C entry points); the kernels: enc_bwd.hip (rows),
-// enc_gemm.hip (launch_gemm, launch_gemm_tn), enc_attn.hip (launch_softmax_mask), enc_rows.hip (launch_layernorm).
+// enc_gemm.hip (launch_gemm, launch_gemm_tn), enc_gemm_bf16.hip (launch_gemm_bf16), enc_attn.hip (launch_softmax_mask), enc_rows.hip
+// (launch_layernorm).
 #include <math.h>
 
 #include "enc_host.h"
@@ -170,6 +176,12 @@ int check_probability(float p, const char* name) {
     ASPIRE_REQUIRE(p >= 0.f && p < 1.f, ASPIRE_ERR_INVALID_ARG, "dropout probability %s = %g outside [0, 1)", name, (double)p);     // (NaN fails too)
     return ASPIRE_OK;
 }
+// the matmul mode of the _prec_ entry points (include/aspire_hip.h: ASPIRE_MATMUL_*)
+int check_matmul(int matmul) {
+    ASPIRE_REQUIRE(matmul == ASPIRE_MATMUL_FP32 || matmul == ASPIRE_MATMUL_BF16, ASPIRE_ERR_INVALID_ARG,
+                   "matmul mode %d: ASPIRE_MATMUL_FP32 (0) or ASPIRE_MATMUL_BF16 (1)", matmul);
+    return ASPIRE_OK;
+}
 int read_dropout(const aspire_bert_dropout* d, Dropout* out) {
     if (!d) return ASPIRE_OK;
     if (int rc = check_probability(d->p_hidden, "p_hidden")) return rc;
@@ -179,24 +191,25 @@ int read_dropout(const aspire_bert_dropout* d, Dropout* out) {
 }
 
 int forward_layer(const aspire_bert_weights* w, const Geometry& q, int l, const TapeLayer& t, const int64_t* mask, const TrainWorkspace& ws,
-                  float* out, const Dropout& dr, hipStream_t st) {
+                  float* out, const Dropout& dr, int mm, hipStream_t st) {
     const aspire_bert_layer& ly = w->layers[l];
     float* act = ws.act;
     const DropSite probs = dr.probs(l), tail[2] = {dr.proj(l), dr.ffn2(l)};
     // 1. qkv = x . Wqkv^T + bqkv
-    if (int rc = launch_gemm(linear(t.x, ly.w_qkv, t.qkv, ly.b_qkv, nullptr, q.M, 3 * kD, kD), 1, false, st)) return rc;
+    if (int rc = launch_product(mm, linear(t.x, ly.w_qkv, t.qkv, ly.b_qkv, nullptr, q.M, 3 * kD, kD), 1, kGemmNT, st)) return rc;
     // 2-4. the three-kernel attention; the masked soft-max runs in place: the tape's P
     // (with dropout the tape keeps the undropped P; the dropped copy the P.V product reads goes to the workspace's dprobs, free here)
-    if (int rc = attention_gemm(t.qkv, t.probs, t.ctx, mask, q.B, q.L, q.Lp, q.H, q.dh, nullptr, 0, st, dr.attn() ? &probs : nullptr, ws.dprobs))
+    if (int rc = attention_gemm(t.qkv, t.probs, t.ctx, mask, q.B, q.L, q.Lp, q.H, q.dh, nullptr, 0, st, dr.attn() ? &probs : nullptr, ws.dprobs,
+                                mm))
         return rc;
     // 5. s1 = ctx . Wo^T + bo + x; h = LN1(s1)
     // 6. u = h . W1^T + b1 (GELU epilogue off); a = GELU(u); s2 = a . W2^T + b2 + h; out = LN2(s2)
-    return layer_tail(w, ly, t.ctx, t.x, TailSlots{t.s1, t.h, t.u, act, t.s2}, out, q.M, st, dr.hidden() ? tail : nullptr);
+    return layer_tail(w, ly, t.ctx, t.x, TailSlots{t.s1, t.h, t.u, act, t.s2}, out, q.M, st, dr.hidden() ? tail : nullptr, mm);
 }
 
 // dy (+ dy_res) = the gradient of layer l's output -> ws.d2 (+ ws.d3) = the gradient of its input, the layer's parameter gradients
 int backward_layer(const aspire_bert_weights* w, const Geometry& q, int l, const TapeLayer& t, const aspire_bert_layer_grads& gr,
-                   const float* dy, const float* dy_res, const TrainWorkspace& ws, const Dropout& dr, hipStream_t st) {
+                   const float* dy, const float* dy_res, const TrainWorkspace& ws, const Dropout& dr, int mm, hipStream_t st) {
     const aspire_bert_layer& ly = w->layers[l];
     const int64_t M = q.M, L = q.L, B = q.B;
     const int H = q.H, dh = q.dh, Lp = q.Lp, ffn = q.ffn;
@@ -212,13 +225,13 @@ int backward_layer(const aspire_bert_weights* w, const Geometry& q, int l, const
     }
     if (int rc = launch_colsum(dz2, M, kD, gr.b_ffn2, ws.partial, st)) return rc;
     if (int rc = launch_gelu_forward(t.u, ws.act, M * ffn, st)) return rc;
-    if (int rc = launch_gemm_tn(grad_weight(dz2, ws.act, gr.w_ffn2, M, kD, ffn), 1, st)) return rc;
-    if (int rc = launch_gemm(grad_input(dz2, ly.w_ffn2, ws.big, M, kD, ffn), 1, true, st)) return rc;
+    if (int rc = launch_product(mm, grad_weight(dz2, ws.act, gr.w_ffn2, M, kD, ffn), 1, kGemmTN, st)) return rc;
+    if (int rc = launch_product(mm, grad_input(dz2, ly.w_ffn2, ws.big, M, kD, ffn), 1, kGemmBKN, st)) return rc;
     // GELU, FFN1
     if (int rc = launch_gelu_backward(ws.big, t.u, ws.big, M * ffn, st)) return rc;
     if (int rc = launch_colsum(ws.big, M, ffn, gr.b_ffn1, ws.partial, st)) return rc;
-    if (int rc = launch_gemm_tn(grad_weight(ws.big, t.h, gr.w_ffn1, M, ffn, kD), 1, st)) return rc;
-    if (int rc = launch_gemm(grad_input(ws.big, ly.w_ffn1, ws.d2, M, ffn, kD), 1, true, st)) return rc;
+    if (int rc = launch_product(mm, grad_weight(ws.big, t.h, gr.w_ffn1, M, ffn, kD), 1, kGemmTN, st)) return rc;
+    if (int rc = launch_product(mm, grad_input(ws.big, ly.w_ffn1, ws.d2, M, ffn, kD), 1, kGemmBKN, st)) return rc;
     // LN1 (dh = the FFN branch's gradient + ds2 down the residual), the output projection
     if (int rc = launch_layernorm_backward(t.s1, ly.ln1_g, w->ln_eps, ws.d2, ws.d1, ws.d3, gr.ln1_g, gr.ln1_b, M, ws.partial, st)) return rc;
     // dropout: the projection reads dz1 = keep . scale . ds1 (into d1: ds2 is dead once LN1's backward has read it); ds1 stays in d3,
@@ -229,8 +242,8 @@ int backward_layer(const aspire_bert_weights* w, const Geometry& q, int l, const
         dz1 = ws.d1;
     }
     if (int rc = launch_colsum(dz1, M, kD, gr.b_o, ws.partial, st)) return rc;
-    if (int rc = launch_gemm_tn(grad_weight(dz1, t.ctx, gr.w_o, M, kD, kD), 1, st)) return rc;
-    if (int rc = launch_gemm(grad_input(dz1, ly.w_o, ws.d2, M, kD, kD), 1, true, st)) return rc;         // dctx
+    if (int rc = launch_product(mm, grad_weight(dz1, t.ctx, gr.w_o, M, kD, kD), 1, kGemmTN, st)) return rc;
+    if (int rc = launch_product(mm, grad_input(dz1, ly.w_o, ws.d2, M, kD, kD), 1, kGemmBKN, st)) return rc;         // dctx
     // attention, per (document, head); dqkv = [dQ | dK | dV] in qkv's layout
     const auto dP = prob_heads(ws.dprobs, H, L, Lp), dctx = ctx_heads(ws.d2, L, dh);
     const auto Q = qkv_heads(t.qkv, L, dh), K = qkv_heads(t.qkv + kD, L, dh), V = qkv_heads(t.qkv + 2 * kD, L, dh);
@@ -240,20 +253,20 @@ int backward_layer(const aspire_bert_weights* w, const Geometry& q, int l, const
     if (dr.attn())
         if (int rc = launch_dropout_probs(t.probs, ws.dprobs, B * H * L, (int)L, Lp, drop_p, st)) return rc;
     const auto P = prob_heads(dr.attn() ? ws.dprobs : t.probs, H, L, Lp);
-    if (int rc = launch_gemm_tn(head_gemm(P, dctx, dV, L, dh, L, H), batch, st)) return rc;
+    if (int rc = launch_product(mm, head_gemm(P, dctx, dV, L, dh, L, H), batch, kGemmTN, st)) return rc;
     // dP_bh [queries, keys] = dctx_bh . V_bh^T; dropout: that is the dropped P's gradient, the soft-max's is keep . scale . of it
-    if (int rc = launch_gemm(head_gemm(dctx, V, dP, L, L, dh, H), batch, false, st)) return rc;
+    if (int rc = launch_product(mm, head_gemm(dctx, V, dP, L, L, dh, H), batch, kGemmNT, st)) return rc;
     if (dr.attn())
         if (int rc = launch_dropout_probs(ws.dprobs, ws.dprobs, B * H * L, (int)L, Lp, drop_p, st)) return rc;
     if (int rc = launch_softmax_backward(ws.dprobs, t.probs, B * H * L, (int)L, Lp, 1.0f / sqrtf((float)dh), st)) return rc;
     // dQ_bh = dS_bh . K_bh
-    if (int rc = launch_gemm(head_gemm(dP, K, dQ, L, dh, L, H), batch, true, st)) return rc;
+    if (int rc = launch_product(mm, head_gemm(dP, K, dQ, L, dh, L, H), batch, kGemmBKN, st)) return rc;
     // dK_bh [keys, 64] = dS_bh^T . Q_bh
-    if (int rc = launch_gemm_tn(head_gemm(dP, Q, dK, L, dh, L, H), batch, st)) return rc;
+    if (int rc = launch_product(mm, head_gemm(dP, Q, dK, L, dh, L, H), batch, kGemmTN, st)) return rc;
     // the QKV projection
     if (int rc = launch_colsum(ws.dqkv, M, 3 * kD, gr.b_qkv, ws.partial, st)) return rc;
-    if (int rc = launch_gemm_tn(grad_weight(ws.dqkv, t.x, gr.w_qkv, M, 3 * kD, kD), 1, st)) return rc;
-    return launch_gemm(grad_input(ws.dqkv, ly.w_qkv, ws.d2, M, 3 * kD, kD), 1, true, st);
+    if (int rc = launch_product(mm, grad_weight(ws.dqkv, t.x, gr.w_qkv, M, 3 * kD, kD), 1, kGemmTN, st)) return rc;
+    return launch_product(mm, grad_input(ws.dqkv, ly.w_qkv, ws.d2, M, 3 * kD, kD), 1, kGemmBKN, st);
 }
 
 // The CLS read-out's gradient source (aspire_bert_layers_backward_cls_f32): row (b, 0) of hidden state l's gradient takes
@@ -266,7 +279,7 @@ struct ClsSource {
 // From the gradient of the top hidden state (grad_hidden, and / or the CLS rows of `cls`) to every parameter gradient and the embedding
 // sum's.  cls NULL: the launches of the backward without a read-out source, none more.
 int backward_stack(const aspire_bert_weights* w, const Geometry& q, const Tape& t, const TrainWorkspace& tw, const float* grad_hidden,
-                   const ClsSource* cls, float* grad_emb_sum, const aspire_bert_grads* grads, const Dropout& dr, hipStream_t st) {
+                   const ClsSource* cls, float* grad_emb_sum, const aspire_bert_grads* grads, const Dropout& dr, int mm, hipStream_t st) {
     const float *dy = grad_hidden, *dy_res = nullptr;
     if (cls) {
         // the top gradient = grad_hidden (or zeros) + the CLS rows, formed in d2: backward_layer writes d2 only after LN2's backward has
@@ -282,7 +295,7 @@ int backward_stack(const aspire_bert_weights* w, const Geometry& q, const Tape& 
             if (int rc = launch_cls_grad_mix(cls->grad_cls, cls->layer_cls, q.B, q.n_layers + 1, cls->grad_mix, st)) return rc;
     }
     for (int l = q.n_layers - 1; l >= 0; --l) {
-        if (int rc = backward_layer(w, q, l, t.layer(l), grads->layers[l], dy, dy_res, tw, dr, st)) return rc;
+        if (int rc = backward_layer(w, q, l, t.layer(l), grads->layers[l], dy, dy_res, tw, dr, mm, st)) return rc;
         dy = tw.d2;         // the attention branch's gradient of the layer's input ...
         dy_res = tw.d3;     // ... and ds1 down the residual: summed by the LayerNorm backward that reads them
         // hidden state l is this layer's input: its CLS rows' share of the mix lands on the residual branch's gradient, before the
@@ -305,7 +318,8 @@ int backward_stack(const aspire_bert_weights* w, const Geometry& q, const Tape& 
 // then the stack
 int backward_entry(const aspire_bert_weights* w, int64_t B, int64_t L, const float* grad_hidden, const ClsSource* cls, const void* tape,
                    size_t tape_bytes, float* grad_emb_sum, const aspire_bert_grads* grads, void* ws, size_t ws_bytes,
-                   const aspire_bert_dropout* dropout, void* stream) {
+                   const aspire_bert_dropout* dropout, int matmul, void* stream) {
+    if (int rc = check_matmul(matmul)) return rc;
     Dropout dr;
     if (int rc = read_dropout(dropout, &dr)) return rc;
     if (int rc = check_train_args(w, B, L)) return rc;
@@ -315,7 +329,7 @@ int backward_entry(const aspire_bert_weights* w, int64_t B, int64_t L, const flo
     if (B == 0) return ASPIRE_OK;
     const Geometry q = geometry(w, B, L);
     if (int rc = check_train_buffers(q, tape, tape_bytes, ws, ws_bytes)) return rc;
-    return backward_stack(w, q, carve_tape(tape, q), carve_train(ws, q), grad_hidden, cls, grad_emb_sum, grads, dr, (hipStream_t)stream);
+    return backward_stack(w, q, carve_tape(tape, q), carve_train(ws, q), grad_hidden, cls, grad_emb_sum, grads, dr, matmul, (hipStream_t)stream);
 }
 
 // the rows of the in-batch cross-entropy: both calls' checks
@@ -348,10 +362,11 @@ extern "C" size_t aspire_bert_train_workspace_bytes(const aspire_bert_weights* w
     return carve_train(nullptr, geometry(w, B, L)).total;
 }
 
-extern "C" int aspire_bert_layers_forward_train_dropout_f32(const aspire_bert_weights* w, const float* emb_sum, const int64_t* attn_mask,
-                                                            int64_t B, int64_t L, float* hidden_out, void* tape, size_t tape_bytes, void* ws,
-                                                            size_t ws_bytes, const aspire_bert_dropout* dropout, void* stream) {
+extern "C" int aspire_bert_layers_forward_train_prec_f32(const aspire_bert_weights* w, const float* emb_sum, const int64_t* attn_mask,
+                                                         int64_t B, int64_t L, float* hidden_out, void* tape, size_t tape_bytes, void* ws,
+                                                         size_t ws_bytes, const aspire_bert_dropout* dropout, int matmul, void* stream) {
     ASPIRE_REQUIRE(w && emb_sum && attn_mask && hidden_out, ASPIRE_ERR_INVALID_ARG, "null pointer");
+    if (int rc = check_matmul(matmul)) return rc;
     Dropout dr;
     if (int rc = read_dropout(dropout, &dr)) return rc;
     if (int rc = check_train_args(w, B, L)) return rc;
@@ -368,8 +383,16 @@ extern "C" int aspire_bert_layers_forward_train_dropout_f32(const aspire_bert_we
     if (dr.hidden())
         if (int rc = launch_dropout_flat(x0, nullptr, nullptr, x0, q.M * kD, dr.emb(), st)) return rc;
     for (int l = 0; l < n; ++l)
-        if (int rc = forward_layer(w, q, l, t.layer(l), attn_mask, tw, l == n - 1 ? hidden_out : t.layer(l + 1).x, dr, st)) return rc;
+        if (int rc = forward_layer(w, q, l, t.layer(l), attn_mask, tw, l == n - 1 ? hidden_out : t.layer(l + 1).x, dr, matmul, st))
+            return rc;
     return ASPIRE_OK;
+}
+
+extern "C" int aspire_bert_layers_forward_train_dropout_f32(const aspire_bert_weights* w, const float* emb_sum, const int64_t* attn_mask,
+                                                            int64_t B, int64_t L, float* hidden_out, void* tape, size_t tape_bytes, void* ws,
+                                                            size_t ws_bytes, const aspire_bert_dropout* dropout, void* stream) {
+    return aspire_bert_layers_forward_train_prec_f32(w, emb_sum, attn_mask, B, L, hidden_out, tape, tape_bytes, ws, ws_bytes, dropout,
+                                                     ASPIRE_MATMUL_FP32, stream);
 }
 
 extern "C" int aspire_bert_layers_forward_train_f32(const aspire_bert_weights* w, const float* emb_sum, const int64_t* attn_mask, int64_t B,
@@ -383,7 +406,7 @@ extern "C" int aspire_bert_layers_backward_dropout_f32(const aspire_bert_weights
                                                        const aspire_bert_grads* grads, void* ws, size_t ws_bytes,
                                                        const aspire_bert_dropout* dropout, void* stream) {
     ASPIRE_REQUIRE(w && attn_mask && grad_hidden && grads, ASPIRE_ERR_INVALID_ARG, "null pointer");
-    return backward_entry(w, B, L, grad_hidden, nullptr, tape, tape_bytes, grad_emb_sum, grads, ws, ws_bytes, dropout, stream);
+    return backward_entry(w, B, L, grad_hidden, nullptr, tape, tape_bytes, grad_emb_sum, grads, ws, ws_bytes, dropout, ASPIRE_MATMUL_FP32, stream);
 }
 
 extern "C" int aspire_bert_layers_backward_f32(const aspire_bert_weights* w, const int64_t* attn_mask, int64_t B, int64_t L,
@@ -417,17 +440,27 @@ extern "C" int aspire_bert_cls_mix_train_f32(const aspire_bert_weights* w, int64
     return launch_cls_mix_tap(s, B, L, mix, cls_out, layer_cls, (hipStream_t)stream);
 }
 
-extern "C" int aspire_bert_layers_backward_cls_f32(const aspire_bert_weights* w, const int64_t* attn_mask, int64_t B, int64_t L,
-                                                   const float* grad_hidden, const float* grad_cls, const float* mix, const float* layer_cls,
-                                                   const void* tape, size_t tape_bytes, float* grad_emb_sum, const aspire_bert_grads* grads,
-                                                   float* grad_mix, void* ws, size_t ws_bytes, const aspire_bert_dropout* dropout,
-                                                   void* stream) {
+extern "C" int aspire_bert_layers_backward_prec_f32(const aspire_bert_weights* w, const int64_t* attn_mask, int64_t B, int64_t L,
+                                                    const float* grad_hidden, const float* grad_cls, const float* mix, const float* layer_cls,
+                                                    const void* tape, size_t tape_bytes, float* grad_emb_sum, const aspire_bert_grads* grads,
+                                                    float* grad_mix, void* ws, size_t ws_bytes, const aspire_bert_dropout* dropout,
+                                                    int matmul, void* stream) {
     ASPIRE_REQUIRE(w && attn_mask && grads, ASPIRE_ERR_INVALID_ARG, "null pointer");
     ASPIRE_REQUIRE(grad_hidden || grad_cls, ASPIRE_ERR_INVALID_ARG, "null pointer (grad_hidden and grad_cls: no gradient source)");
     ASPIRE_REQUIRE(!grad_mix || (layer_cls && mix && grad_cls), ASPIRE_ERR_INVALID_ARG,
                    "grad_mix needs grad_cls, mix and layer_cls (null pointer)");
     const ClsSource cls{grad_cls, mix, layer_cls, grad_mix};
-    return backward_entry(w, B, L, grad_hidden, grad_cls ? &cls : nullptr, tape, tape_bytes, grad_emb_sum, grads, ws, ws_bytes, dropout, stream);
+    return backward_entry(w, B, L, grad_hidden, grad_cls ? &cls : nullptr, tape, tape_bytes, grad_emb_sum, grads, ws, ws_bytes, dropout, matmul,
+                          stream);
+}
+
+extern "C" int aspire_bert_layers_backward_cls_f32(const aspire_bert_weights* w, const int64_t* attn_mask, int64_t B, int64_t L,
+                                                   const float* grad_hidden, const float* grad_cls, const float* mix, const float* layer_cls,
+                                                   const void* tape, size_t tape_bytes, float* grad_emb_sum, const aspire_bert_grads* grads,
+                                                   float* grad_mix, void* ws, size_t ws_bytes, const aspire_bert_dropout* dropout,
+                                                   void* stream) {
+    return aspire_bert_layers_backward_prec_f32(w, attn_mask, B, L, grad_hidden, grad_cls, mix, layer_cls, tape, tape_bytes, grad_emb_sum, grads,
+                                                grad_mix, ws, ws_bytes, dropout, ASPIRE_MATMUL_FP32, stream);
 }
 
 extern "C" int aspire_inbatch_xent_f32(const float* q, const float* c, int64_t B, int64_t D, float* loss, float* row_lse, void* stream) {

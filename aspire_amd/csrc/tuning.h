@@ -44,6 +44,9 @@ struct Tuning {
 const Tuning& tuning();
 // launches of the fused kernel's Solve16 form so far in this process (aspire_debug_get("FUSED_SOLVE16_LAUNCHES"): tests of the form rule)
 long long solve16_launches();
+// the instantiation the bf16 GEMM's latest launch of this process took, 3 form + tile, or -1 (aspire_debug_get("GEMM_BF16_LAST"): tests
+// of enc_gemm_bf16.hip's tile rule)
+int gemm_bf16_last();
 // key = the environment variable's name without the ASPIRE_HIP_ prefix (e.g. "SINKHORN"), value as in the environment;
 // value NULL or "" restores the default.  Returns false on an unknown key / value.
 bool tuning_set(const char* key, const char* value);

@@ -53,6 +53,10 @@ implementation so that shapes propagate under FakeTensor / torch.compile tracing
                                          (autograd registered: emb_sum, every tensor of weights and mix, from the gradient of cls)
     torch.ops.aspire.bert_layers_backward_cls(grad_cls, layer_cls, tape, mask, weights, mix | None, n_heads, ln_eps, p_hidden, p_attn,
                                          seed, step) -> (grad_emb_sum, grads, grad_mix)                                 its formula
+    torch.ops.aspire.bert_layers_train_prec(..., p_hidden, p_attn, seed, step, matmul) / bert_layers_backward_prec(..., matmul)
+    torch.ops.aspire.bert_layers_train_cls_prec(..., seed, step, matmul) / bert_layers_backward_cls_prec(..., matmul)
+                                         the dropout pair and the CLS pair with the matmul mode (0 fp32, 1 bf16 matrix products:
+                                         HipBertTrainEncoder(matmul='bf16')); autograd registered like their siblings
     torch.ops.aspire.inbatch_xent(q, c) -> (loss [1], row_lse [B])                                 sentsim_models.py:81-126
                                          (autograd registered: the gradient of loss with respect to q and c)
     torch.ops.aspire.inbatch_xent_backward(grad_loss, q, c, row_lse) -> (grad_q, grad_c)
@@ -576,7 +580,8 @@ def _train_workspace(bw, b, l, device):
 
 
 # drop: a _lib.BertDropout for the _dropout_ entry points, None for the plain ones (the body of both operator pairs)
-def _layers_forward(emb_sum, mask, weights, n_heads, ln_eps, drop=None):
+# matmul: None for those entries, or ASPIRE_MATMUL_* for the _prec_ entry points (drop may then be None as well)
+def _layers_forward(emb_sum, mask, weights, n_heads, ln_eps, drop=None, matmul=None):
     bw = pack_layer_stack(weights, n_heads, ln_eps)
     emb_sum = emb_sum.to(torch.float32).contiguous()
     b, l, _ = emb_sum.shape
@@ -585,14 +590,16 @@ def _layers_forward(emb_sum, mask, weights, n_heads, ln_eps, drop=None):
     tape = _scratch(lib.aspire_bert_tape_bytes, bw, b, l, emb_sum.device)
     ws = _train_workspace(bw, b, l, emb_sum.device)
     args = (ctypes.byref(bw), ops._ptr(emb_sum), ops._ptr(mask), b, l, ops._ptr(out), ops._ptr(tape), tape.numel(), ops._ptr(ws), ws.numel())
-    if drop is None:
+    if matmul is not None:
+        check(lib.aspire_bert_layers_forward_train_prec_f32(*args, ctypes.byref(drop) if drop is not None else None, matmul, ops._stream()))
+    elif drop is None:
         check(lib.aspire_bert_layers_forward_train_f32(*args, ops._stream()))
     else:
         check(lib.aspire_bert_layers_forward_train_dropout_f32(*args, ctypes.byref(drop), ops._stream()))
     return out, tape
 
 
-def _layers_backward(grad_hidden, tape, mask, weights, n_heads, ln_eps, drop=None):
+def _layers_backward(grad_hidden, tape, mask, weights, n_heads, ln_eps, drop=None, matmul=None):
     bw = pack_layer_stack(weights, n_heads, ln_eps)
     grad_hidden = grad_hidden.to(torch.float32).contiguous()
     b, l, _ = grad_hidden.shape
@@ -604,7 +611,11 @@ def _layers_backward(grad_hidden, tape, mask, weights, n_heads, ln_eps, drop=Non
     ws = _train_workspace(bw, b, l, grad_hidden.device)
     args = (ctypes.byref(bw), ops._ptr(mask), b, l, ops._ptr(grad_hidden), ops._ptr(tape), tape.numel(), ops._ptr(grad_emb), ctypes.byref(bg),
             ops._ptr(ws), ws.numel())
-    if drop is None:
+    if matmul is not None:
+        head, tail = args[:5], args[5:]     # (the _prec_ backward is the CLS one: grad_cls, mix, layer_cls behind grad_hidden; grad_mix behind grads)
+        check(lib.aspire_bert_layers_backward_prec_f32(*head, None, None, None, *tail[:4], None, *tail[4:],
+                                                       ctypes.byref(drop) if drop is not None else None, matmul, ops._stream()))
+    elif drop is None:
         check(lib.aspire_bert_layers_backward_f32(*args, ops._stream()))
     else:
         check(lib.aspire_bert_layers_backward_dropout_f32(*args, ctypes.byref(drop), ops._stream()))
@@ -712,10 +723,9 @@ def _drop_or_none(p_hidden, p_attn, seed, step):
     return _dropout(p_hidden, p_attn, seed, step) if (p_hidden > 0 or p_attn > 0) else None
 
 
-@torch.library.custom_op('aspire::bert_layers_train_cls', mutates_args=(), device_types='cuda')
-def bert_layers_train_cls(emb_sum: Tensor, mask: Tensor, weights: List[Tensor], mix: Optional[Tensor], n_heads: int, ln_eps: float,
-                          p_hidden: float, p_attn: float, seed: int, step: int) -> Tuple[Tensor, Tensor, Tensor]:
-    hidden, tape = _layers_forward(emb_sum, mask, weights, n_heads, ln_eps, _drop_or_none(p_hidden, p_attn, seed, step))
+# matmul: None for the entries above, or ASPIRE_MATMUL_* for the _prec_ ones (the body of both operator pairs)
+def _train_cls(emb_sum, mask, weights, mix, n_heads, ln_eps, p_hidden, p_attn, seed, step, matmul=None):
+    hidden, tape = _layers_forward(emb_sum, mask, weights, n_heads, ln_eps, _drop_or_none(p_hidden, p_attn, seed, step), matmul)
     bw = pack_layer_stack(weights, n_heads, ln_eps)
     b, l, d = hidden.shape
     cls = hidden.new_empty(b, d)
@@ -727,10 +737,20 @@ def bert_layers_train_cls(emb_sum: Tensor, mask: Tensor, weights: List[Tensor], 
     return cls, layer_cls, tape
 
 
+@torch.library.custom_op('aspire::bert_layers_train_cls', mutates_args=(), device_types='cuda')
+def bert_layers_train_cls(emb_sum: Tensor, mask: Tensor, weights: List[Tensor], mix: Optional[Tensor], n_heads: int, ln_eps: float,
+                          p_hidden: float, p_attn: float, seed: int, step: int) -> Tuple[Tensor, Tensor, Tensor]:
+    return _train_cls(emb_sum, mask, weights, mix, n_heads, ln_eps, p_hidden, p_attn, seed, step)
+
+
 @torch.library.custom_op('aspire::bert_layers_backward_cls', mutates_args=(), device_types='cuda')
 def bert_layers_backward_cls(grad_cls: Tensor, layer_cls: Tensor, tape: Tensor, mask: Tensor, weights: List[Tensor], mix: Optional[Tensor],
                              n_heads: int, ln_eps: float, p_hidden: float, p_attn: float, seed: int,
                              step: int) -> Tuple[Tensor, List[Tensor], Tensor]:
+    return _backward_cls(grad_cls, layer_cls, tape, mask, weights, mix, n_heads, ln_eps, p_hidden, p_attn, seed, step)
+
+
+def _backward_cls(grad_cls, layer_cls, tape, mask, weights, mix, n_heads, ln_eps, p_hidden, p_attn, seed, step, matmul=None):
     bw = pack_layer_stack(weights, n_heads, ln_eps)
     grad_cls = grad_cls.to(torch.float32).contiguous()
     mask, = _int64(mask)
@@ -745,11 +765,13 @@ def bert_layers_backward_cls(grad_cls: Tensor, layer_cls: Tensor, tape: Tensor, 
     ws = _train_workspace(bw, b, l, grad_cls.device)
     drop = _drop_or_none(p_hidden, p_attn, seed, step)
     with_mix = mix is not None
-    check(lib.aspire_bert_layers_backward_cls_f32(ctypes.byref(bw), ops._ptr(mask), b, l, None, ops._ptr(grad_cls), ops._ptr(mix),
-                                                  ops._ptr(layer_cls.contiguous() if with_mix else None), ops._ptr(tape), tape.numel(),
-                                                  ops._ptr(grad_emb), ctypes.byref(bg), ops._ptr(grad_mix if with_mix else None),
-                                                  ops._ptr(ws), ws.numel(), ctypes.byref(drop) if drop is not None else None,
-                                                  ops._stream()))
+    args = (ctypes.byref(bw), ops._ptr(mask), b, l, None, ops._ptr(grad_cls), ops._ptr(mix),
+            ops._ptr(layer_cls.contiguous() if with_mix else None), ops._ptr(tape), tape.numel(), ops._ptr(grad_emb), ctypes.byref(bg),
+            ops._ptr(grad_mix if with_mix else None), ops._ptr(ws), ws.numel(), ctypes.byref(drop) if drop is not None else None)
+    if matmul is not None:
+        check(lib.aspire_bert_layers_backward_prec_f32(*args, matmul, ops._stream()))
+    else:
+        check(lib.aspire_bert_layers_backward_cls_f32(*args, ops._stream()))
     return grad_emb, grads, grad_mix
 
 
@@ -784,6 +806,94 @@ def _bert_layers_train_cls_grad(ctx, grad_cls, grad_layer_cls, grad_tape):
 
 
 bert_layers_train_cls.register_autograd(_bert_layers_train_cls_grad, setup_context=_bert_layers_train_cls_setup)
+
+
+# ---- the matmul mode (aspire_bert_layers_forward_train_prec_f32 / aspire_bert_layers_backward_prec_f32) -------------------------------------
+# The dropout pair and the CLS pair with a trailing matmul: int (include/aspire_hip.h: ASPIRE_MATMUL_FP32 0, ASPIRE_MATMUL_BF16 1 -- every
+# matrix product of the layer stack with both operands rounded to bf16 once, fp32 accumulators; everything else, the tape and every
+# gradient fp32).  HipBertTrainEncoder takes these only with matmul != 'fp32'; with 0 they give the bits of their siblings above.  Both
+# probabilities 0: the launches without dropout.
+@torch.library.custom_op('aspire::bert_layers_train_prec', mutates_args=(), device_types='cuda')
+def bert_layers_train_prec(emb_sum: Tensor, mask: Tensor, weights: List[Tensor], n_heads: int, ln_eps: float, p_hidden: float, p_attn: float,
+                           seed: int, step: int, matmul: int) -> Tuple[Tensor, Tensor]:
+    return _layers_forward(emb_sum, mask, weights, n_heads, ln_eps, _drop_or_none(p_hidden, p_attn, seed, step), matmul)
+
+
+@torch.library.custom_op('aspire::bert_layers_backward_prec', mutates_args=(), device_types='cuda')
+def bert_layers_backward_prec(grad_hidden: Tensor, tape: Tensor, mask: Tensor, weights: List[Tensor], n_heads: int, ln_eps: float,
+                              p_hidden: float, p_attn: float, seed: int, step: int, matmul: int) -> Tuple[Tensor, List[Tensor]]:
+    return _layers_backward(grad_hidden, tape, mask, weights, n_heads, ln_eps, _drop_or_none(p_hidden, p_attn, seed, step), matmul)
+
+
+@bert_layers_train_prec.register_fake
+def _(emb_sum, mask, weights, n_heads, ln_eps, p_hidden, p_attn, seed, step, matmul):
+    return emb_sum.new_empty(emb_sum.shape, dtype=torch.float32), emb_sum.new_empty(_fake_tape_bytes(emb_sum, weights, n_heads, ln_eps),
+                                                                                     dtype=torch.uint8)
+
+
+@bert_layers_backward_prec.register_fake
+def _(grad_hidden, tape, mask, weights, n_heads, ln_eps, p_hidden, p_attn, seed, step, matmul):
+    return grad_hidden.new_empty(grad_hidden.shape, dtype=torch.float32), [t.new_empty(t.shape) for t in weights]
+
+
+def _bert_layers_train_prec_setup(ctx, inputs, output):
+    emb_sum, mask, weights, ctx.n_heads, ctx.ln_eps, *ctx.mode = inputs         # mode: p_hidden, p_attn, seed, step, matmul
+    ctx.save_for_backward(output[1], mask, *weights)
+
+
+def _bert_layers_train_prec_grad(ctx, grad_hidden, grad_tape):
+    tape, mask, *weights = ctx.saved_tensors
+    grad_emb, grads = torch.ops.aspire.bert_layers_backward_prec(grad_hidden, tape, mask, weights, ctx.n_heads, ctx.ln_eps, *ctx.mode)
+    return grad_emb, None, grads, None, None, None, None, None, None, None
+
+
+bert_layers_train_prec.register_autograd(_bert_layers_train_prec_grad, setup_context=_bert_layers_train_prec_setup)
+
+
+@torch.library.custom_op('aspire::bert_layers_train_cls_prec', mutates_args=(), device_types='cuda')
+def bert_layers_train_cls_prec(emb_sum: Tensor, mask: Tensor, weights: List[Tensor], mix: Optional[Tensor], n_heads: int, ln_eps: float,
+                               p_hidden: float, p_attn: float, seed: int, step: int, matmul: int) -> Tuple[Tensor, Tensor, Tensor]:
+    return _train_cls(emb_sum, mask, weights, mix, n_heads, ln_eps, p_hidden, p_attn, seed, step, matmul)
+
+
+@torch.library.custom_op('aspire::bert_layers_backward_cls_prec', mutates_args=(), device_types='cuda')
+def bert_layers_backward_cls_prec(grad_cls: Tensor, layer_cls: Tensor, tape: Tensor, mask: Tensor, weights: List[Tensor],
+                                  mix: Optional[Tensor], n_heads: int, ln_eps: float, p_hidden: float, p_attn: float, seed: int, step: int,
+                                  matmul: int) -> Tuple[Tensor, List[Tensor], Tensor]:
+    return _backward_cls(grad_cls, layer_cls, tape, mask, weights, mix, n_heads, ln_eps, p_hidden, p_attn, seed, step, matmul)
+
+
+@bert_layers_train_cls_prec.register_fake
+def _(emb_sum, mask, weights, mix, n_heads, ln_eps, p_hidden, p_attn, seed, step, matmul):
+    b, _, d = emb_sum.shape
+    return (emb_sum.new_empty((b, d), dtype=torch.float32),
+            emb_sum.new_empty(((len(weights) - 2) // 12 + 1, b, d) if mix is not None else (0,), dtype=torch.float32),
+            emb_sum.new_empty(_fake_tape_bytes(emb_sum, weights, n_heads, ln_eps), dtype=torch.uint8))
+
+
+@bert_layers_backward_cls_prec.register_fake
+def _(grad_cls, layer_cls, tape, mask, weights, mix, n_heads, ln_eps, p_hidden, p_attn, seed, step, matmul):
+    b, l = mask.shape
+    return (grad_cls.new_empty((b, l, grad_cls.shape[1]), dtype=torch.float32), [t.new_empty(t.shape) for t in weights],
+            grad_cls.new_empty(mix.numel() if mix is not None else 0, dtype=torch.float32))
+
+
+def _bert_layers_train_cls_prec_setup(ctx, inputs, output):
+    emb_sum, mask, weights, mix, ctx.n_heads, ctx.ln_eps, *ctx.mode = inputs
+    ctx.with_mix = mix is not None
+    ctx.save_for_backward(output[1], output[2], mask, *([mix] if ctx.with_mix else []), *weights)
+    ctx.mark_non_differentiable(output[1])
+
+
+def _bert_layers_train_cls_prec_grad(ctx, grad_cls, grad_layer_cls, grad_tape):
+    layer_cls, tape, mask, *rest = ctx.saved_tensors
+    mix, weights = (rest[0], rest[1:]) if ctx.with_mix else (None, rest)
+    grad_emb, grads, grad_mix = torch.ops.aspire.bert_layers_backward_cls_prec(grad_cls, layer_cls, tape, mask, weights, mix, ctx.n_heads,
+                                                                               ctx.ln_eps, *ctx.mode)
+    return grad_emb, None, grads, grad_mix if ctx.with_mix else None, None, None, None, None, None, None, None
+
+
+bert_layers_train_cls_prec.register_autograd(_bert_layers_train_cls_prec_grad, setup_context=_bert_layers_train_cls_prec_setup)
 
 
 # ---- the in-batch cross-entropy (aspire_inbatch_xent_f32 / aspire_inbatch_xent_backward_f32) -----------------------------------------------
@@ -901,4 +1011,5 @@ OPS = ('span_mean_pool', 'span_pool_ranges', 'bert_encoder_forward', 'bert_cls_f
        'ot_pair_scores', 'ot_pair_backward', 'jointsm_pair_scores', 'jointsm_pair_backward', 'l2sup_pair_scores', 'l2sup_pair_backward',
        'sent_cdist', 'sent_cdist_backward', 'span_mean_pool_backward', 'cls_l2_pair', 'cls_l2_pair_backward', 'bert_layers_train', 'bert_layers_backward',
        'bert_layers_train_dropout', 'bert_layers_backward_dropout', 'bert_dropout_mask', 'bert_layers_train_cls', 'bert_layers_backward_cls',
+       'bert_layers_train_prec', 'bert_layers_backward_prec', 'bert_layers_train_cls_prec', 'bert_layers_backward_cls_prec',
        'inbatch_xent', 'inbatch_xent_backward', 'bert_embed_sum', 'bert_embed_backward')

@@ -29,6 +29,14 @@ in torch).  ``check_ids=True`` (the default) looks at the ids and type ids first
 host sync per forward; ``check_ids=False`` says the caller has validated them (an id out of range is then never read: its row of the
 sum is NaN).  The default ``hip_embeddings=False`` is the graph described above.
 
+The precision of the matrix products is opt-in as well.  ``HipBertTrainEncoder(bert_model, matmul='bf16')`` runs all 16 products of a
+layer (the four projections, Q K^T and P V forward; the ten of the backward) with both operands rounded to bf16 once, fp32
+accumulators and fp32 epilogues -- what ``torch.autocast(dtype=torch.bfloat16)`` asks of them (torch.ops.aspire.bert_layers_train_prec /
+bert_layers_train_cls_prec; include/aspire_hip.h states the arithmetic).  LayerNorm, soft-max, GELU, the dropout passes, the tape, the
+parameters and every gradient stay fp32, so optimizers, gradient buckets and clipping see what they always saw.  The default
+``matmul='fp32'`` goes through the operators described above, untouched.  ``eval()`` and ``torch.no_grad()`` forwards stay on the
+inference path in fp32 in either mode: the mode is a property of training steps.
+
 Not supported: activation checkpointing around this module -- the recomputed forward would draw the next step's masks, not the first
 forward's.
 """
@@ -41,8 +49,13 @@ from .encoder import _LAYER_KEYS, require_bert_base
 
 
 class HipBertTrainEncoder(torch.nn.Module):
-    def __init__(self, bert_model, dropout=False, seed=None, hip_embeddings=False, check_ids=True):
+    MATMUL_MODES = {'fp32': 0, 'bf16': 1}        # include/aspire_hip.h: ASPIRE_MATMUL_*
+
+    def __init__(self, bert_model, dropout=False, seed=None, hip_embeddings=False, check_ids=True, matmul='fp32'):
         super().__init__()
+        if matmul not in self.MATMUL_MODES:
+            raise ValueError(f"HipBertTrainEncoder: matmul={matmul!r}: 'fp32' or 'bf16'")
+        self.matmul = matmul
         dev = ops.require_gpu()
         self.hip_embeddings, self.check_ids = bool(hip_embeddings), bool(check_ids)
         cfg = bert_model.config
@@ -145,9 +158,11 @@ class HipBertTrainEncoder(torch.nn.Module):
         seed, step = self._seed, self._step
         if self.dropout:
             self._step = (step + 1) % 2 ** 32
-        cls, _layer_cls, _tape = torch.ops.aspire.bert_layers_train_cls(
-            emb_sum, msk, self.layer_weights(), mix, cfg.num_attention_heads, cfg.layer_norm_eps, self.p_hidden, self.p_attn,
-            seed - 2 ** 64 if seed >= 2 ** 63 else seed, step)
+        args = (emb_sum, msk, self.layer_weights(), mix, cfg.num_attention_heads, cfg.layer_norm_eps, self.p_hidden, self.p_attn,
+                seed - 2 ** 64 if seed >= 2 ** 63 else seed, step)
+        if self.matmul != 'fp32':
+            return torch.ops.aspire.bert_layers_train_cls_prec(*args, self.MATMUL_MODES[self.matmul])[0]
+        cls, _layer_cls, _tape = torch.ops.aspire.bert_layers_train_cls(*args)
         return cls
 
     def forward(self, tokid_tt, token_type_ids=None, attention_mask=None):
@@ -172,6 +187,15 @@ class HipBertTrainEncoder(torch.nn.Module):
         if seq_len > cfg.max_position_embeddings:
             raise IndexError(f'{seq_len} tokens: beyond max_position_embeddings={cfg.max_position_embeddings}')
         emb_sum = self._emb_sum(tok, typ, seq_len)
+        if self.matmul != 'fp32':
+            # one operator pair for the mode, with and without dropout (probabilities of 0 launch no dropout pass)
+            seed, step = self._seed, self._step
+            if self.dropout:
+                self._step = (step + 1) % 2 ** 32
+            hidden, _tape = torch.ops.aspire.bert_layers_train_prec(emb_sum, msk, self.layer_weights(), cfg.num_attention_heads, cfg.layer_norm_eps,
+                                                                    self.p_hidden, self.p_attn, seed - 2 ** 64 if seed >= 2 ** 63 else seed, step,
+                                                                    self.MATMUL_MODES[self.matmul])
+            return hidden
         if not self.dropout:
             hidden, _tape = torch.ops.aspire.bert_layers_train(emb_sum, msk, self.layer_weights(), cfg.num_attention_heads, cfg.layer_norm_eps)
             return hidden

@@ -213,12 +213,18 @@ class RankTrainer:
                  'loss_history': dict(self.loss_history), 'loss_checked_iters': list(self.loss_checked_iters),
                  'dev_score_history': list(self.dev_score_history), 'dev_checked_iters': list(self.dev_checked_iters),
                  'dropout_state': tuple(self.encoder.dropout_state()) if hasattr(self.encoder, 'dropout_state') else None,
+                 'matmul': getattr(self.encoder, 'matmul', 'fp32'),
                  'last_grad_norm': None if self.last_grad_norm is None else float(self.last_grad_norm),
                  'torch_rng_state': torch.get_rng_state()}
         torch.save(state, path)
 
     def load_checkpoint(self, path):
         state = torch.load(path, map_location='cpu', weights_only=True)
+        # the mode of the encoder's matrix products is part of what a run computes (a checkpoint from before the key: 'fp32')
+        saved, mine = state.get('matmul', 'fp32'), getattr(self.encoder, 'matmul', 'fp32')
+        if saved != mine:
+            raise ValueError(f"checkpoint written with matmul={saved!r}, this encoder runs matmul={mine!r}: resume with the mode the run was "
+                             'started in')
         self.encoder.load_state_dict(state['encoder'])
         self.optimizer.load_state_dict(state['optimizer'])
         self.scheduler.load_state_dict(state['scheduler'])

@@ -373,6 +373,58 @@ int aspire_inbatch_xent_backward_f32(const float* q, const float* c, int64_t B, 
                                      const float* grad_loss, float* grad_q, float* grad_c, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * A1t with the matrix products in bf16 (opt-in): "matrix products in bf16, everything else in fp32", what
+ * torch.autocast(dtype=torch.bfloat16) asks of a BertModel's linears and matmuls.
+ *
+ * aspire_bert_layers_forward_train_prec_f32 / aspire_bert_layers_backward_prec_f32 are
+ * aspire_bert_layers_forward_train_dropout_f32 / aspire_bert_layers_backward_cls_f32 plus `matmul`:
+ *   ASPIRE_MATMUL_FP32  those calls: the same launches, the same bits
+ *   ASPIRE_MATMUL_BF16  all 16 products of a layer (QKV, out, FFN1, FFN2 projections, Q K^T, P V forward; the ten of the backward)
+ *                       in the arithmetic below; LayerNorm, soft-max, GELU, column sums, dropout, the CLS mix and their backwards
+ *                       stay fp32 launches.  The tape stays fp32 in the same layout (the two size queries are unchanged), the
+ *                       weights stay fp32 and are rounded per use: no bf16 copy exists, nothing to refresh after an optimizer step
+ *   any other value     ASPIRE_ERR_INVALID_ARG before the device is touched, the value in aspire_last_error()
+ * The forward and the backward of one step take the same mode.
+ *
+ * The arithmetic of a bf16 product C = alpha A B (+ bias) (+ GELU) (+ residual), and nothing else:
+ *   - every element of A and B is rounded to bf16 ONCE, round to nearest even, when its tile is staged from the fp32 tensor: the
+ *     values of torch.Tensor.to(torch.bfloat16) -- +-0, ties and +-inf as torch gives them, NaN stays NaN, a magnitude that rounds past
+ *     bf16's largest finite becomes inf;
+ *   - a product of two bf16 values is exact in fp32;
+ *   - the sum over K is the matrix cores' fp32 accumulator in a fixed order, one level in all three forms;
+ *   - alpha, bias, GELU and the residual are fp32;
+ *   - no atomics, one writer per element of C: the same bits on every run.
+ *
+ * aspire_debug_gemm_bf16_f32: one such product, for tests and tools.  Per matrix C [M, N] (row stride ldc), by `form`:
+ *   ASPIRE_GEMM_NT    A [M, K] (lda), B [N, K] (ldb), both k-contiguous
+ *   ASPIRE_GEMM_BKN   A [M, K] (lda), B [K, N] (ldb)
+ *   ASPIRE_GEMM_TN    A [K, M] (lda), B [K, N] (ldb): C = A^T B
+ * `batch` matrices, matrix z = z1 * nz2 + z2 at offsets z1 * s?1 + z2 * s?2 floats of A, B and C (attention: z1 the document, z2
+ * the head); bias [N] or NULL; res [M, ldr] or NULL (not batched); gelu != 0 applies GELU before the residual.  Any M, N, K (tails
+ * are zero-filled when staged, nothing is read past an operand's rows); A and B 16-byte aligned, lda, ldb and their batch strides
+ * multiples of 4.  A NULL A / B / C, a negative size, an unknown form, nz2 < 1, a leading dimension shorter than its row or a
+ * misaligned operand -> ASPIRE_ERR_INVALID_ARG; M, N, K or batch == 0 -> ASPIRE_OK without a launch (C is not written).
+ * aspire_debug_get("GEMM_BF16_LAST") reads which kernel instantiation the latest bf16 product of this process launched, as
+ * 3 * form + tile (tile 0: 128 x 128, 1: 128 x 64, 2: 64 x 64; chosen by shape, aspire_debug_set("GEMM_TILE", "128" | "64") pins),
+ * -1 before the first.
+ * ------------------------------------------------------------------------------------------- */
+enum { ASPIRE_MATMUL_FP32 = 0, ASPIRE_MATMUL_BF16 = 1 };
+enum { ASPIRE_GEMM_NT = 0, ASPIRE_GEMM_BKN = 1, ASPIRE_GEMM_TN = 2 };
+
+int aspire_bert_layers_forward_train_prec_f32(const aspire_bert_weights* w, const float* emb_sum, const int64_t* attn_mask, int64_t B,
+                                              int64_t L, float* hidden_out, void* tape, size_t tape_bytes, void* ws, size_t ws_bytes,
+                                              const aspire_bert_dropout* dropout, int matmul, void* stream);
+int aspire_bert_layers_backward_prec_f32(const aspire_bert_weights* w, const int64_t* attn_mask, int64_t B, int64_t L,
+                                         const float* grad_hidden, const float* grad_cls, const float* mix, const float* layer_cls,
+                                         const void* tape, size_t tape_bytes, float* grad_emb_sum, const aspire_bert_grads* grads,
+                                         float* grad_mix, void* ws, size_t ws_bytes, const aspire_bert_dropout* dropout, int matmul,
+                                         void* stream);
+int aspire_debug_gemm_bf16_f32(const float* A, const float* B, float* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
+                               int64_t ldc, int form, int64_t batch, int64_t nz2, int64_t sa1, int64_t sa2, int64_t sb1, int64_t sb2,
+                               int64_t sc1, int64_t sc2, float alpha, const float* bias, const float* res, int64_t ldr, int gelu,
+                               void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The embedding lookup under training: BertEmbeddings' sum in front of aspire_bert_layers_forward_train_f32 and the three tables'
  * gradients behind aspire_bert_layers_backward_f32 (what nn.Embedding's forward and scatter backward do on the reference path).
  * Hidden size 768.  Token rows m = b L + l, M = B L.  word [vocab, 768], pos [max_pos, 768], type [n_types, 768]; tok, typ int64
