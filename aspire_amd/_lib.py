@@ -171,6 +171,9 @@ SIGNATURES = {
     'aspire_debug_gemm_bf16_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int64,
                                            c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, ctypes.c_float, c_void_p, c_void_p,
                                            c_int64, c_int, c_void_p]),
+    'aspire_debug_gemm_bf16x3_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int64,
+                                             c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, ctypes.c_float, c_void_p, c_void_p,
+                                             c_int64, c_int, c_void_p]),
     'aspire_inbatch_xent_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     'aspire_inbatch_xent_backward_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'aspire_bert_embed_sum_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64,

@@ -11,7 +11,7 @@
     AspireSentEnc(bert_model=...).load_state_dict(torch.load(...))          # the context tower is dropped there
 
 ``hip_embeddings`` / ``check_ids`` go to every tower's HipBertTrainEncoder (the embedding tables' gradients in HIP, in a fixed order),
-and so does ``matmul`` ('fp32' | 'bf16': the mode of the layer stack's matrix products; a module's ``matmul`` attribute is its towers').
+and so does ``matmul`` ('fp32' | 'bf16' | 'bf16x3': the mode of the layer stack's matrix products; a module's ``matmul`` attribute is its towers').
 A module's ``forward(bert_batch)`` gives the [B, 768] document (sentence) reps; ``state_dict()`` speaks the reference's key names, so
 ``model_final.pt`` / ``model_cur_best.pt`` load into ``AspireBiEnc`` / ``AspireSentEnc`` unchanged.  What runs where: the layer stack,
 the read-out (with MySPECTER's soft-max layer mix) and their backward are torch.ops.aspire.bert_layers_train_cls; the soft-max over

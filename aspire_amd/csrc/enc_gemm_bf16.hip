@@ -19,109 +19,20 @@
 // Any M, N, K: tails are zero-filled when a tile is staged (a partial float4 is read element by element, never past the operand's
 // valid extent); lda / ldb multiples of 4 and 16-byte aligned bases, as the fp32 forms ask.
 //
-// Staging.  The MFMA fragment is eight consecutive k of one row, so the LDS image of a tile is [k group of 8][row][8 bf16], 16 bytes
-// per row.  A k-contiguous operand stores its float4 (four k of one row) as one 8-byte half of such a row.  A K-MAJOR operand (a row
-// of global memory is a k-slice) is turned IN REGISTERS: a thread loads a 4 k x 4 row block as four float4 along the rows (coalesced:
-// eight lanes cover 128 contiguous bytes of a k-slice), and writes each of its four rows' four consecutive k as one 8-byte store into
-// the same image -- the scatter route; the fragment reads are then plain 16-byte reads, the same for all three forms.  (The other
-// route, storing k-major and reading through the LDS transpose read, needs no register turn but a second read path; NOTES.md.)
-// Rows are swizzled, row ^ ((row >> 3) & 3), the same in stores and reads: within an aligned group of four rows a permutation, so a
-// fragment read (16 lanes = 16 consecutive rows = 256 bytes) stays conflict free, and the four-row stride of the turned stores
-// (rows 4 m + i for eight lanes m) lands on eight distinct 16-byte slots of a 128-byte window instead of two.
+// Staging: StageRegs of enc_stage.h with one plane (the loads, the register turn of a k-major operand, the swizzled LDS image).
 //
 // Pipeline: 32 k per tile (two MFMA steps), LDS double buffered, the next tile's global loads in flight under this tile's MFMAs,
 // converted and stored behind them, one barrier per tile.  Tiles 128 x 128, 128 x 64 and 64 x 64, four waves as 2 x 2.
 #include <atomic>
 
 #include "enc_host.h"
+#include "enc_stage.h"
 #include "tuning.h"
 
 namespace aspire {
 namespace {
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-
-// two fp32 -> one dword of two bf16 (low half = the first), round to nearest even
-__device__ __forceinline__ uint32_t pack_bf16(float x, float y) {
-    typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    const f2 v = {x, y};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf2));
-}
-
-// p[0 .. 4) where n (<= 0: none) elements from p on are valid; the rest zero.  p is 16-byte aligned.
-__device__ __forceinline__ float4 load4_valid(const float* p, int n) {
-    if (n >= 4) return *reinterpret_cast<const float4*>(p);
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (n > 0) v.x = p[0];
-    if (n > 1) v.y = p[1];
-    if (n > 2) v.z = p[2];
-    return v;
-}
-
-__device__ __forceinline__ int swizzle_row(int r) { return r ^ ((r >> 3) & 3); }
-
 constexpr int kBf16BK = 32;      // k per tile: four groups of eight
-
-// One operand's tile, ROWS x 32 k, from global memory to registers and from registers to its LDS image.  K_MAJOR: the operand is
-// [K][ld] with the tile's rows along the contiguous dimension.  `rows` / `K`: the operand's valid extent; r0 / k0: the tile's origin.
-template <int ROWS, bool K_MAJOR>
-struct StageRegs {
-    static constexpr int kPlane = ROWS * 4 + 8;                                    // dwords of one k group: ROWS x 16 bytes + 32 bytes, so that the four groups' stores fall in different quarters of a 128-byte window
-    static constexpr int N4 = K_MAJOR ? 4 : ROWS * (kBf16BK / 4) / 256;           // float4 per thread
-    static constexpr int kUnits = (ROWS / 4) * (kBf16BK / 4);                      // K_MAJOR: 4 x 4 blocks of the tile (256 or 128)
-    float4 v[N4];
-
-    __device__ __forceinline__ void load(const float* X, int ld, int rows, int K, int r0, int k0, int tid) {
-        if constexpr (K_MAJOR) {
-            // (a 64-row tile has 128 blocks: the upper half of the workgroup stages nothing)
-            const bool active = kUnits >= 256 || tid < kUnits;
-            const int m4 = ((tid >> 4) % (ROWS / 32)) * 8 + (tid & 7), kq = ((tid >> 4) / (ROWS / 32)) * 2 + ((tid >> 3) & 1);
-            const int r = r0 + 4 * m4;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int k = k0 + 4 * kq + j;
-                v[j] = load4_valid(X + (size_t)k * ld + r, active && k < K ? rows - r : 0);
-            }
-        } else {
-#pragma unroll
-            for (int p = 0; p < N4; ++p) {
-                const int idx = tid + 256 * p, row = idx / (kBf16BK / 4), k4 = idx % (kBf16BK / 4);
-                const int r = r0 + row, k = k0 + 4 * k4;
-                v[p] = load4_valid(X + (size_t)r * ld + k, r < rows ? K - k : 0);
-            }
-        }
-    }
-    // S: the buffer's image [4][kPlane]
-    __device__ __forceinline__ void store(uint32_t (*S)[kPlane], int tid) const {
-        if constexpr (K_MAJOR) {
-            if (kUnits < 256 && tid >= kUnits) return;
-            const int m4 = ((tid >> 4) % (ROWS / 32)) * 8 + (tid & 7), kq = ((tid >> 4) / (ROWS / 32)) * 2 + ((tid >> 3) & 1);
-            uint32_t* base = &S[kq >> 1][2 * (kq & 1)];
-            // the turn: k-slice j gives (rows 0, 1) and (rows 2, 3) at k = j as two dwords, rounded where they lie; row i then takes its
-            // halves of the four slices' dwords (integer selects: no float leaves its float4)
-            uint32_t p01[4], p23[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                p01[q] = pack_bf16(v[q].x, v[q].y);
-                p23[q] = pack_bf16(v[q].z, v[q].w);
-            }
-            auto lo = [](uint32_t a, uint32_t b) { return (a & 0xffffu) | (b << 16); };
-            auto hi = [](uint32_t a, uint32_t b) { return (a >> 16) | (b & 0xffff0000u); };
-            *reinterpret_cast<uint2*>(base + 4 * swizzle_row(4 * m4 + 0)) = make_uint2(lo(p01[0], p01[1]), lo(p01[2], p01[3]));
-            *reinterpret_cast<uint2*>(base + 4 * swizzle_row(4 * m4 + 1)) = make_uint2(hi(p01[0], p01[1]), hi(p01[2], p01[3]));
-            *reinterpret_cast<uint2*>(base + 4 * swizzle_row(4 * m4 + 2)) = make_uint2(lo(p23[0], p23[1]), lo(p23[2], p23[3]));
-            *reinterpret_cast<uint2*>(base + 4 * swizzle_row(4 * m4 + 3)) = make_uint2(hi(p23[0], p23[1]), hi(p23[2], p23[3]));
-        } else {
-#pragma unroll
-            for (int p = 0; p < N4; ++p) {
-                const int idx = tid + 256 * p, row = idx / (kBf16BK / 4), k4 = idx % (kBf16BK / 4);
-                *reinterpret_cast<uint2*>(&S[k4 >> 1][4 * swizzle_row(row) + 2 * (k4 & 1)]) =
-                    make_uint2(pack_bf16(v[p].x, v[p].y), pack_bf16(v[p].z, v[p].w));
-            }
-        }
-    }
-};
 
 template <int BM, int BN, int FORM>
 __global__ void __launch_bounds__(256) gemm_bf16_kernel(GemmArgs g) {
@@ -129,10 +40,10 @@ __global__ void __launch_bounds__(256) gemm_bf16_kernel(GemmArgs g) {
     constexpr int WAVES_N = 2;
     constexpr int WM = BM / 2, WN = BN / 2, TM = WM / 32, TN = WN / 32;
     static_assert(WM % 32 == 0 && WN % 32 == 0, "tile / wave layout");
-    using StageA = StageRegs<BM, A_KM>;
-    using StageB = StageRegs<BN, B_KM>;
-    __shared__ __attribute__((aligned(16))) uint32_t As[2][4][StageA::kPlane];
-    __shared__ __attribute__((aligned(16))) uint32_t Bs[2][4][StageB::kPlane];
+    using StageA = StageRegs<BM, A_KM, kBf16BK, 1>;
+    using StageB = StageRegs<BN, B_KM, kBf16BK, 1>;
+    __shared__ __attribute__((aligned(16))) uint32_t As[2][1][4][StageA::kPlane];
+    __shared__ __attribute__((aligned(16))) uint32_t Bs[2][1][4][StageB::kPlane];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wr = wave / WAVES_N, wc = wave % WAVES_N;
@@ -182,10 +93,10 @@ __global__ void __launch_bounds__(256) gemm_bf16_kernel(GemmArgs g) {
             bf16x8_t af[TM], bfr[TN];
 #pragma unroll
             for (int i = 0; i < TM; ++i)
-                af[i] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(&As[buf][2 * s + lk][4 * swizzle_row(wr * WM + 32 * i + lr)]));
+                af[i] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(&As[buf][0][2 * s + lk][4 * swizzle_row(wr * WM + 32 * i + lr)]));
 #pragma unroll
             for (int j = 0; j < TN; ++j)
-                bfr[j] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(&Bs[buf][2 * s + lk][4 * swizzle_row(wc * WN + 32 * j + lr)]));
+                bfr[j] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(&Bs[buf][0][2 * s + lk][4 * swizzle_row(wc * WN + 32 * j + lr)]));
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -263,27 +174,11 @@ extern "C" int aspire_debug_gemm_bf16_f32(const float* A, const float* B, float*
                                           int64_t ldc, int form, int64_t batch, int64_t nz2, int64_t sa1, int64_t sa2, int64_t sb1, int64_t sb2,
                                           int64_t sc1, int64_t sc2, float alpha, const float* bias, const float* res, int64_t ldr, int gelu,
                                           void* stream) {
-    ASPIRE_REQUIRE(A && B && C, ASPIRE_ERR_INVALID_ARG, "null pointer (A / B / C)");
-    ASPIRE_REQUIRE(M >= 0 && N >= 0 && K >= 0 && batch >= 0, ASPIRE_ERR_INVALID_ARG, "negative size (M %lld N %lld K %lld batch %lld)",
-                   (long long)M, (long long)N, (long long)K, (long long)batch);
-    ASPIRE_REQUIRE(form == kGemmNT || form == kGemmBKN || form == kGemmTN, ASPIRE_ERR_INVALID_ARG, "unknown GEMM form %d (0 NT, 1 B_KN, 2 TN)",
-                   form);
-    ASPIRE_REQUIRE(nz2 >= 1, ASPIRE_ERR_INVALID_ARG, "nz2 = %lld: the inner batch count is at least 1", (long long)nz2);
-    // what each operand's rows must span, and the float4 rule of the fp32 forms
-    const int64_t a_cols = form == kGemmTN ? M : K, b_cols = form == kGemmNT ? K : N;
-    ASPIRE_REQUIRE(lda >= a_cols && ldb >= b_cols && ldc >= N && (!res || ldr >= N), ASPIRE_ERR_INVALID_ARG,
-                   "a leading dimension is shorter than its row (lda %lld ldb %lld ldc %lld ldr %lld)", (long long)lda, (long long)ldb,
-                   (long long)ldc, (long long)ldr);
-    ASPIRE_REQUIRE(lda % 4 == 0 && ldb % 4 == 0 && (sa1 | sa2 | sb1 | sb2) % 4 == 0 && (((uintptr_t)A | (uintptr_t)B) & 15) == 0,
-                   ASPIRE_ERR_INVALID_ARG, "A and B are read as float4: 16-byte aligned bases, lda / ldb / batch strides multiples of 4");
-    ASPIRE_REQUIRE(M < (1 << 30) && N < (1 << 30) && K < (1 << 30) && lda < (1 << 30) && ldb < (1 << 30) && ldc < (1 << 30) && ldr < (1 << 30) &&
-                       batch <= 65535,
-                   ASPIRE_ERR_UNSUPPORTED, "a size beyond the kernel's 32-bit indices (or more than 65535 matrices)");
-    if (M == 0 || N == 0 || K == 0 || batch == 0) return ASPIRE_OK;
-    GemmArgs g{};
-    g.A = A; g.B = B; g.C = C; g.bias = bias; g.res = res;
-    g.M = (int)M; g.N = (int)N; g.K = (int)K; g.lda = (int)lda; g.ldb = (int)ldb; g.ldc = (int)ldc; g.ldr = (int)ldr;
-    g.nz2 = (int)nz2; g.sa1 = sa1; g.sa2 = sa2; g.sb1 = sb1; g.sb2 = sb2; g.sc1 = sc1; g.sc2 = sc2;
-    g.alpha = alpha; g.gelu = gelu ? 1 : 0;
+    GemmArgs g;
+    bool launch;
+    if (int rc = debug_gemm_args(A, B, C, M, N, K, lda, ldb, ldc, form, batch, nz2, sa1, sa2, sb1, sb2, sc1, sc2, alpha, bias, res, ldr, gelu, &g,
+                                 &launch))
+        return rc;
+    if (!launch) return ASPIRE_OK;
     return launch_gemm_bf16(g, (int)batch, form, (hipStream_t)stream);
 }

@@ -18,12 +18,52 @@ enum { kGemmNT = 0, kGemmBKN = 1, kGemmTN = 2 };
 // cores with fp32 accumulators and the fp32 epilogues of launch_gemm; any M, N, K, lda / ldb multiples of 4 (ASPIRE_MATMUL_BF16)
 int launch_gemm_bf16(const GemmArgs& g, int batch, int form, hipStream_t st);
 
+// enc_gemm_bf16x3.hip: the B_KN and TN forms at fp32 accuracy on the bf16 matrix cores -- every operand element split into three bf16
+// planes when its tile is staged, six products per term, fp32 accumulators (the TN form in two levels) and the same epilogues; any
+// M, N, K, lda / ldb multiples of 4.  The NT form goes to launch_gemm, which is that arithmetic already wherever K % 16 == 0
+// (ASPIRE_MATMUL_BF16X3)
+int launch_gemm_bf16x3(const GemmArgs& g, int batch, int form, hipStream_t st);
+
 namespace {
 
 // A product of the layer stack in the caller's matmul mode: ASPIRE_MATMUL_FP32 launches what the stack always launched
 int launch_product(int matmul, const GemmArgs& g, int batch, int form, hipStream_t st) {
     if (matmul == ASPIRE_MATMUL_BF16) return launch_gemm_bf16(g, batch, form, st);
+    if (matmul == ASPIRE_MATMUL_BF16X3) return launch_gemm_bf16x3(g, batch, form, st);
     return form == kGemmTN ? launch_gemm_tn(g, batch, st) : launch_gemm(g, batch, form == kGemmBKN, st);
+}
+
+// The argument checks of the aspire_debug_gemm_*_f32 entries (include/aspire_hip.h) and the GemmArgs they launch.  *launch = false: a
+// zero size, nothing to do.
+int debug_gemm_args(const float* A, const float* B, float* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int form,
+                    int64_t batch, int64_t nz2, int64_t sa1, int64_t sa2, int64_t sb1, int64_t sb2, int64_t sc1, int64_t sc2, float alpha,
+                    const float* bias, const float* res, int64_t ldr, int gelu, GemmArgs* out, bool* launch) {
+    *launch = false;
+    ASPIRE_REQUIRE(A && B && C, ASPIRE_ERR_INVALID_ARG, "null pointer (A / B / C)");
+    ASPIRE_REQUIRE(M >= 0 && N >= 0 && K >= 0 && batch >= 0, ASPIRE_ERR_INVALID_ARG, "negative size (M %lld N %lld K %lld batch %lld)",
+                   (long long)M, (long long)N, (long long)K, (long long)batch);
+    ASPIRE_REQUIRE(form == kGemmNT || form == kGemmBKN || form == kGemmTN, ASPIRE_ERR_INVALID_ARG, "unknown GEMM form %d (0 NT, 1 B_KN, 2 TN)",
+                   form);
+    ASPIRE_REQUIRE(nz2 >= 1, ASPIRE_ERR_INVALID_ARG, "nz2 = %lld: the inner batch count is at least 1", (long long)nz2);
+    // what each operand's rows must span, and the float4 rule of the fp32 forms
+    const int64_t a_cols = form == kGemmTN ? M : K, b_cols = form == kGemmNT ? K : N;
+    ASPIRE_REQUIRE(lda >= a_cols && ldb >= b_cols && ldc >= N && (!res || ldr >= N), ASPIRE_ERR_INVALID_ARG,
+                   "a leading dimension is shorter than its row (lda %lld ldb %lld ldc %lld ldr %lld)", (long long)lda, (long long)ldb,
+                   (long long)ldc, (long long)ldr);
+    ASPIRE_REQUIRE(lda % 4 == 0 && ldb % 4 == 0 && (sa1 | sa2 | sb1 | sb2) % 4 == 0 && (((uintptr_t)A | (uintptr_t)B) & 15) == 0,
+                   ASPIRE_ERR_INVALID_ARG, "A and B are read as float4: 16-byte aligned bases, lda / ldb / batch strides multiples of 4");
+    ASPIRE_REQUIRE(M < (1 << 30) && N < (1 << 30) && K < (1 << 30) && lda < (1 << 30) && ldb < (1 << 30) && ldc < (1 << 30) && ldr < (1 << 30) &&
+                       batch <= 65535,
+                   ASPIRE_ERR_UNSUPPORTED, "a size beyond the kernel's 32-bit indices (or more than 65535 matrices)");
+    if (M == 0 || N == 0 || K == 0 || batch == 0) return ASPIRE_OK;
+    GemmArgs g{};
+    g.A = A; g.B = B; g.C = C; g.bias = bias; g.res = res;
+    g.M = (int)M; g.N = (int)N; g.K = (int)K; g.lda = (int)lda; g.ldb = (int)ldb; g.ldc = (int)ldc; g.ldr = (int)ldr;
+    g.nz2 = (int)nz2; g.sa1 = sa1; g.sa2 = sa2; g.sb1 = sb1; g.sb2 = sb2; g.sc1 = sc1; g.sc2 = sc2;
+    g.alpha = alpha; g.gelu = gelu ? 1 : 0;
+    *out = g;
+    *launch = true;
+    return ASPIRE_OK;
 }
 
 size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }

@@ -38,10 +38,13 @@
 // The matmul mode (the _prec_ entry points; ASPIRE_MATMUL_*): in ASPIRE_MATMUL_BF16 every product of both layer bodies -- the four
 // projections, Q K^T and P V forward, the ten of the backward -- goes through launch_gemm_bf16 (enc_gemm_bf16.hip: operands rounded to
 // bf16 once when staged, fp32 accumulators and epilogues); every other launch, the tape and the workspace are the same, in fp32.  In
-// ASPIRE_MATMUL_FP32 launch_product (enc_host.h) launches what was launched before there was a mode.
+// ASPIRE_MATMUL_FP32 launch_product (enc_host.h) launches what was launched before there was a mode.  In ASPIRE_MATMUL_BF16X3 the NT
+// products are those same launches (gemm_bf16x3_kernel already), and the B_KN and TN products -- P V forward; da, dh, dctx, dx, dQ and
+// every dW, dV, dK of the backward -- go through launch_gemm_bf16x3 (enc_gemm_bf16x3.hip: operands split into three bf16 planes when
+// staged, six products per term, fp32 accumulators): fp32 accuracy on the bf16 matrix pipe.
 //
 // This file is host only (the tape's and the workspace's carve, the two layer loops, the C entry points); the kernels: enc_bwd.hip (rows),
-// enc_gemm.hip (launch_gemm, launch_gemm_tn), enc_gemm_bf16.hip (launch_gemm_bf16), enc_attn.hip (launch_softmax_mask), enc_rows.hip
+// enc_gemm.hip (launch_gemm, launch_gemm_tn), enc_gemm_bf16.hip (launch_gemm_bf16), enc_gemm_bf16x3.hip (launch_gemm_bf16x3), enc_attn.hip (launch_softmax_mask), enc_rows.hip
 // (launch_layernorm).
 #include <math.h>
 
@@ -178,8 +181,8 @@ int check_probability(float p, const char* name) {
 }
 // the matmul mode of the _prec_ entry points (include/aspire_hip.h: ASPIRE_MATMUL_*)
 int check_matmul(int matmul) {
-    ASPIRE_REQUIRE(matmul == ASPIRE_MATMUL_FP32 || matmul == ASPIRE_MATMUL_BF16, ASPIRE_ERR_INVALID_ARG,
-                   "matmul mode %d: ASPIRE_MATMUL_FP32 (0) or ASPIRE_MATMUL_BF16 (1)", matmul);
+    ASPIRE_REQUIRE(matmul == ASPIRE_MATMUL_FP32 || matmul == ASPIRE_MATMUL_BF16 || matmul == ASPIRE_MATMUL_BF16X3, ASPIRE_ERR_INVALID_ARG,
+                   "matmul mode %d: ASPIRE_MATMUL_FP32 (0), ASPIRE_MATMUL_BF16 (1) or ASPIRE_MATMUL_BF16X3 (3)", matmul);
     return ASPIRE_OK;
 }
 int read_dropout(const aspire_bert_dropout* d, Dropout* out) {

@@ -124,6 +124,10 @@ bool render_tuning(const Tuning& t, const char* key, char* buf, size_t len) {
         snprintf(num, sizeof(num), "%d", gemm_bf16_last());
         v = num;
     }
+    else if (!strcmp(key, "GEMM_BF16X3_LAST")) {            // read-only
+        snprintf(num, sizeof(num), "%d", gemm_bf16x3_last());
+        v = num;
+    }
     else if (!strcmp(key, "FUSED_WAVES")) v = number(t.fused_waves);
     else if (!strcmp(key, "TILE_WAVES")) v = number(t.tile_waves);
     else if (!strcmp(key, "FUSED_SPLIT")) v = number(t.fused_split);

@@ -47,6 +47,9 @@ long long solve16_launches();
 // the instantiation the bf16 GEMM's latest launch of this process took, 3 form + tile, or -1 (aspire_debug_get("GEMM_BF16_LAST"): tests
 // of enc_gemm_bf16.hip's tile rule)
 int gemm_bf16_last();
+// the same for the k-major bf16x3 GEMM (aspire_debug_get("GEMM_BF16X3_LAST"): enc_gemm_bf16x3.hip's tile rule, and whether a step took
+// the mode at all)
+int gemm_bf16x3_last();
 // key = the environment variable's name without the ASPIRE_HIP_ prefix (e.g. "SINKHORN"), value as in the environment;
 // value NULL or "" restores the default.  Returns false on an unknown key / value.
 bool tuning_set(const char* key, const char* value);

@@ -55,8 +55,8 @@ implementation so that shapes propagate under FakeTensor / torch.compile tracing
                                          seed, step) -> (grad_emb_sum, grads, grad_mix)                                 its formula
     torch.ops.aspire.bert_layers_train_prec(..., p_hidden, p_attn, seed, step, matmul) / bert_layers_backward_prec(..., matmul)
     torch.ops.aspire.bert_layers_train_cls_prec(..., seed, step, matmul) / bert_layers_backward_cls_prec(..., matmul)
-                                         the dropout pair and the CLS pair with the matmul mode (0 fp32, 1 bf16 matrix products:
-                                         HipBertTrainEncoder(matmul='bf16')); autograd registered like their siblings
+                                         the dropout pair and the CLS pair with the matmul mode (0 fp32, 1 bf16 matrix products, 3 bf16x3:
+                                         HipBertTrainEncoder(matmul='bf16' | 'bf16x3')); autograd registered like their siblings
     torch.ops.aspire.inbatch_xent(q, c) -> (loss [1], row_lse [B])                                 sentsim_models.py:81-126
                                          (autograd registered: the gradient of loss with respect to q and c)
     torch.ops.aspire.inbatch_xent_backward(grad_loss, q, c, row_lse) -> (grad_q, grad_c)
@@ -810,8 +810,9 @@ bert_layers_train_cls.register_autograd(_bert_layers_train_cls_grad, setup_conte
 
 # ---- the matmul mode (aspire_bert_layers_forward_train_prec_f32 / aspire_bert_layers_backward_prec_f32) -------------------------------------
 # The dropout pair and the CLS pair with a trailing matmul: int (include/aspire_hip.h: ASPIRE_MATMUL_FP32 0, ASPIRE_MATMUL_BF16 1 -- every
-# matrix product of the layer stack with both operands rounded to bf16 once, fp32 accumulators; everything else, the tape and every
-# gradient fp32).  HipBertTrainEncoder takes these only with matmul != 'fp32'; with 0 they give the bits of their siblings above.  Both
+# matrix product of the layer stack with both operands rounded to bf16 once, fp32 accumulators; ASPIRE_MATMUL_BF16X3 3 -- the products
+# with a k-major operand on the bf16 matrix cores at fp32 accuracy, the others as in mode 0; everything else, the tape and every
+# gradient fp32; any other integer, 2 among them, is refused).  HipBertTrainEncoder takes these only with matmul != 'fp32'; with 0 they give the bits of their siblings above.  Both
 # probabilities 0: the launches without dropout.
 @torch.library.custom_op('aspire::bert_layers_train_prec', mutates_args=(), device_types='cuda')
 def bert_layers_train_prec(emb_sum: Tensor, mask: Tensor, weights: List[Tensor], n_heads: int, ln_eps: float, p_hidden: float, p_attn: float,

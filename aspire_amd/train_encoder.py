@@ -33,9 +33,13 @@ The precision of the matrix products is opt-in as well.  ``HipBertTrainEncoder(b
 layer (the four projections, Q K^T and P V forward; the ten of the backward) with both operands rounded to bf16 once, fp32
 accumulators and fp32 epilogues -- what ``torch.autocast(dtype=torch.bfloat16)`` asks of them (torch.ops.aspire.bert_layers_train_prec /
 bert_layers_train_cls_prec; include/aspire_hip.h states the arithmetic).  LayerNorm, soft-max, GELU, the dropout passes, the tape, the
-parameters and every gradient stay fp32, so optimizers, gradient buckets and clipping see what they always saw.  The default
+parameters and every gradient stay fp32, so optimizers, gradient buckets and clipping see what they always saw.
+``HipBertTrainEncoder(bert_model, matmul='bf16x3')`` keeps fp32 accuracy and moves the products that ``'fp32'`` still runs on the
+fp32-input matrix cores -- P V forward; the five dX-like and six dW-like products of the backward, whose operands are k-major -- onto
+the bf16 matrix cores: each operand split into three bf16 values, six products per term, fp32 accumulators.  The other products are
+``'fp32'``'s own launches, which are that arithmetic already; the mode's results sit inside the fp32 mode's error bound.  The default
 ``matmul='fp32'`` goes through the operators described above, untouched.  ``eval()`` and ``torch.no_grad()`` forwards stay on the
-inference path in fp32 in either mode: the mode is a property of training steps.
+inference path in fp32 in every mode: the mode is a property of training steps.
 
 Not supported: activation checkpointing around this module -- the recomputed forward would draw the next step's masks, not the first
 forward's.
@@ -49,12 +53,12 @@ from .encoder import _LAYER_KEYS, require_bert_base
 
 
 class HipBertTrainEncoder(torch.nn.Module):
-    MATMUL_MODES = {'fp32': 0, 'bf16': 1}        # include/aspire_hip.h: ASPIRE_MATMUL_*
+    MATMUL_MODES = {'fp32': 0, 'bf16': 1, 'bf16x3': 3}        # include/aspire_hip.h: ASPIRE_MATMUL_* (2 is not a mode)
 
     def __init__(self, bert_model, dropout=False, seed=None, hip_embeddings=False, check_ids=True, matmul='fp32'):
         super().__init__()
         if matmul not in self.MATMUL_MODES:
-            raise ValueError(f"HipBertTrainEncoder: matmul={matmul!r}: 'fp32' or 'bf16'")
+            raise ValueError(f"HipBertTrainEncoder: matmul={matmul!r}: 'fp32', 'bf16' or 'bf16x3'")
         self.matmul = matmul
         dev = ops.require_gpu()
         self.hip_embeddings, self.check_ids = bool(hip_embeddings), bool(check_ids)

@@ -383,8 +383,30 @@ int aspire_inbatch_xent_backward_f32(const float* q, const float* c, int64_t B, 
  *                       in the arithmetic below; LayerNorm, soft-max, GELU, column sums, dropout, the CLS mix and their backwards
  *                       stay fp32 launches.  The tape stays fp32 in the same layout (the two size queries are unchanged), the
  *                       weights stay fp32 and are rounded per use: no bf16 copy exists, nothing to refresh after an optimizer step
- *   any other value     ASPIRE_ERR_INVALID_ARG before the device is touched, the value in aspire_last_error()
+ *   ASPIRE_MATMUL_BF16X3  fp32 accuracy on the bf16 matrix cores (opt-in as well).  The NT products (the four projections, Q K^T, dP)
+ *                       are ASPIRE_MATMUL_FP32's launches -- already that arithmetic wherever K % 16 == 0, which every NT product of
+ *                       the layer stack is -- so the forward differs from ASPIRE_MATMUL_FP32 in P V alone; the B_KN products (P V,
+ *                       da, dh, dctx, dx, dQ) and the TN products (every dW, dV, dK) leave the fp32-input matrix cores for the
+ *                       bf16x3 arithmetic below.  Everything else as in ASPIRE_MATMUL_BF16: the same fp32 launches, tape and weights
+ *   any other value     ASPIRE_ERR_INVALID_ARG before the device is touched, the value in aspire_last_error().  2 among them: the
+ *                       value was a rejected mode before ASPIRE_MATMUL_BF16X3 existed and callers and tests rely on that, so the
+ *                       enum skips it
  * The forward and the backward of one step take the same mode.
+ *
+ * The arithmetic of a bf16x3 product C = alpha A B (+ bias) (+ GELU) (+ residual), and nothing else:
+ *   - every element of A and B is split ONCE, when its tile is staged from the fp32 tensor, into three bf16 values x = x1 + x2 + x3:
+ *     x1 = bf16(x), x2 = bf16(x - x1), x3 = bf16(x - x1 - x2), each round to nearest even, both subtractions exact (24 mantissa bits);
+ *   - a product a b is the six terms a3 b1, a1 b3, a2 b2, a2 b1, a1 b2, a1 b1, each exact in fp32, added in that order (smallest
+ *     first); the three dropped terms a2 b3 + a3 b2 + a3 b3 are below 2^-23 |a| |b| (|a2| <= 2^-8 |a|, |a3| <= 2^-16 |a|):
+ *     of the order of fp32's own rounding;
+ *   - the sums over K are the matrix cores' fp32 accumulators in a fixed order.  In the B_KN and TN forms a1 b1 has an accumulator of
+ *     its own and the five correction terms share a second one, added once at the end (the matrix cores cut addends far below the
+ *     running sum toward minus infinity; kept apart, the small terms are not cut).  One level in the B_KN form; the TN form, which
+ *     contracts over token rows, adds both to a further set every 256 k (the fp32 TN form's two levels);
+ *   - alpha, bias, GELU and the residual are fp32;
+ *   - no atomics, one writer per element of C: the same bits on every run;
+ *   - a non-finite element of A or B (or one that rounds past bf16's largest finite) splits into a NaN plane (inf - inf): its output
+ *     row or column is NaN, as in the NT form of the fp32 mode.
  *
  * The arithmetic of a bf16 product C = alpha A B (+ bias) (+ GELU) (+ residual), and nothing else:
  *   - every element of A and B is rounded to bf16 ONCE, round to nearest even, when its tile is staged from the fp32 tensor: the
@@ -407,8 +429,14 @@ int aspire_inbatch_xent_backward_f32(const float* q, const float* c, int64_t B, 
  * aspire_debug_get("GEMM_BF16_LAST") reads which kernel instantiation the latest bf16 product of this process launched, as
  * 3 * form + tile (tile 0: 128 x 128, 1: 128 x 64, 2: 64 x 64; chosen by shape, aspire_debug_set("GEMM_TILE", "128" | "64") pins),
  * -1 before the first.
+ *
+ * aspire_debug_gemm_bf16x3_f32: one bf16x3 product, the same arguments and checks.  ASPIRE_GEMM_BKN and ASPIRE_GEMM_TN run the
+ * arithmetic above for any M, N, K; ASPIRE_GEMM_NT is what the mode launches for an NT product, the fp32 mode's GEMM (bf16x3 where
+ * K % 16 == 0, else the fp32-input matrix cores), and asks K % 4 == 0 as that GEMM does.  aspire_debug_get("GEMM_BF16X3_LAST"): the
+ * instantiation of the latest B_KN or TN launch of this process as 3 * form + tile (3 .. 8; the tiles and the pin as above), -1
+ * before the first; an NT product does not change it.
  * ------------------------------------------------------------------------------------------- */
-enum { ASPIRE_MATMUL_FP32 = 0, ASPIRE_MATMUL_BF16 = 1 };
+enum { ASPIRE_MATMUL_FP32 = 0, ASPIRE_MATMUL_BF16 = 1, ASPIRE_MATMUL_BF16X3 = 3 };       /* 2 is not a mode (above) */
 enum { ASPIRE_GEMM_NT = 0, ASPIRE_GEMM_BKN = 1, ASPIRE_GEMM_TN = 2 };
 
 int aspire_bert_layers_forward_train_prec_f32(const aspire_bert_weights* w, const float* emb_sum, const int64_t* attn_mask, int64_t B,
@@ -423,6 +451,10 @@ int aspire_debug_gemm_bf16_f32(const float* A, const float* B, float* C, int64_t
                                int64_t ldc, int form, int64_t batch, int64_t nz2, int64_t sa1, int64_t sa2, int64_t sb1, int64_t sb2,
                                int64_t sc1, int64_t sc2, float alpha, const float* bias, const float* res, int64_t ldr, int gelu,
                                void* stream);
+int aspire_debug_gemm_bf16x3_f32(const float* A, const float* B, float* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
+                                 int64_t ldc, int form, int64_t batch, int64_t nz2, int64_t sa1, int64_t sa2, int64_t sb1, int64_t sb2,
+                                 int64_t sc1, int64_t sc2, float alpha, const float* bias, const float* res, int64_t ldr, int gelu,
+                                 void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The embedding lookup under training: BertEmbeddings' sum in front of aspire_bert_layers_forward_train_f32 and the three tables'

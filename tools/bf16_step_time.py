@@ -1,4 +1,4 @@
-"""One training step of the encoder -- forward + backward of a 12-layer BERT-base (ffn 3072), dropout 0 -- in the two matmul modes of
+"""One training step of the encoder -- forward + backward of a 12-layer BERT-base (ffn 3072), dropout 0 -- in the three matmul modes of
 aspire_amd.HipBertTrainEncoder, next to HuggingFace BertModel under torch autograd in fp32 and under
 torch.autocast('cuda', dtype=torch.bfloat16), on the same card ("bf16 matrix products").
 
@@ -7,13 +7,14 @@ is several runs of this tool in one session on one card:
 
     python tools/bf16_step_time.py --side fp32          HipBertTrainEncoder(model)                 (also runs on a tree without the mode)
     python tools/bf16_step_time.py --side bf16          HipBertTrainEncoder(model, matmul='bf16')
+    python tools/bf16_step_time.py --side bf16x3        HipBertTrainEncoder(model, matmul='bf16x3')
     python tools/bf16_step_time.py --side hf            BertModel, fp32
     python tools/bf16_step_time.py --side hf-autocast   BertModel under torch.autocast('cuda', dtype=torch.bfloat16)
 
 Every side: the same random-init weights and inputs, (hidden * G).sum().backward(), three warm-up steps, then device events over
 windows of about 0.2 s, five windows; the median and the range of the per-step times, one JSON line per shape.  Needs a GPU.
 
-The kernels' own times: the bf16 side under rocprofv3 --kernel-trace --stats with --windows 1 --window-s 0.02 (tools/statsum.py sums
+The kernels' own times: the bf16 or bf16x3 side under rocprofv3 --kernel-trace --stats with --windows 1 --window-s 0.02 (tools/statsum.py sums
 the CSV by kernel).
 """
 import argparse
@@ -38,7 +39,7 @@ def window(fn, calls):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--side', choices=['fp32', 'bf16', 'hf', 'hf-autocast'], required=True)
+    ap.add_argument('--side', choices=['fp32', 'bf16', 'bf16x3', 'hf', 'hf-autocast'], required=True)
     ap.add_argument('--shapes', default='3x512,10x256')
     ap.add_argument('--layers', type=int, default=12)
     ap.add_argument('--windows', type=int, default=5)
@@ -50,9 +51,10 @@ def main():
     cfg = BertConfig(vocab_size=3000, hidden_size=768, num_hidden_layers=a.layers, num_attention_heads=12, intermediate_size=3072,
                      max_position_embeddings=512, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0)
     model = BertModel(cfg, add_pooling_layer=False).cuda().train()
-    if a.side in ('fp32', 'bf16'):
+    ours = a.side in ('fp32', 'bf16', 'bf16x3')
+    if ours:
         from aspire_amd import HipBertTrainEncoder
-        model = (HipBertTrainEncoder(model, matmul='bf16') if a.side == 'bf16' else HipBertTrainEncoder(model)).train()
+        model = (HipBertTrainEncoder(model) if a.side == 'fp32' else HipBertTrainEncoder(model, matmul=a.side)).train()
     for shape in a.shapes.split(','):
         b, l = (int(x) for x in shape.split('x'))
         g = torch.Generator().manual_seed(b * 1000 + l)
@@ -65,7 +67,7 @@ def main():
 
         def step():
             model.zero_grad(set_to_none=True)
-            if a.side in ('fp32', 'bf16'):
+            if ours:
                 hidden = model(tok, token_type_ids=typ, attention_mask=mask)
             elif a.side == 'hf':
                 hidden = model(tok, token_type_ids=typ, attention_mask=mask).last_hidden_state
