@@ -20,6 +20,7 @@ c_void_p, c_int, c_int32, c_int64, c_double, c_size_t = (ctypes.c_void_p, ctypes
 
 ASPIRE_OK, ASPIRE_ERR_INVALID_ARG, ASPIRE_ERR_UNSUPPORTED, ASPIRE_ERR_HIP = 0, 1, 2, 3
 CDIST_AUTO, CDIST_DIRECT, CDIST_MM = 0, 1, 2
+ATTENTION_GEMM, ATTENTION_FLASH = 0, 1      # ASPIRE_ATTENTION_*: the _attn_ entry points of the training encoder
 CDIST_ONE_FORM = 0x100       # or'ed into cdist_mode of the max-sim entry points: one kernel form whatever the call's size
 OT_FLAG_ONE_FORM = 1         # aspire_ot_params.flags: the same for otAspire
 CDIST_CENTER = 0x200         # rows with a large common component: subtract the query's mean row before the expansion (max-sim entries)
@@ -168,6 +169,20 @@ SIGNATURES = {
     'aspire_bert_layers_backward_prec_f32': (c_int, [ctypes.POINTER(BertWeights), c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
                                                      c_void_p, c_void_p, c_size_t, c_void_p, ctypes.POINTER(BertGrads), c_void_p, c_void_p,
                                                      c_size_t, ctypes.POINTER(BertDropout), c_int, c_void_p]),
+    'aspire_bert_tape_bytes_attn': (c_size_t, [ctypes.POINTER(BertWeights), c_int64, c_int64, c_int]),
+    'aspire_bert_train_workspace_bytes_attn': (c_size_t, [ctypes.POINTER(BertWeights), c_int64, c_int64, c_int]),
+    'aspire_bert_layers_forward_train_attn_f32': (c_int, [ctypes.POINTER(BertWeights), c_void_p, c_void_p, c_int64, c_int64, c_void_p,
+                                                          c_void_p, c_size_t, c_void_p, c_size_t, ctypes.POINTER(BertDropout), c_int, c_int,
+                                                          c_void_p]),
+    'aspire_bert_layers_backward_attn_f32': (c_int, [ctypes.POINTER(BertWeights), c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                                     c_void_p, c_void_p, c_size_t, c_void_p, ctypes.POINTER(BertGrads), c_void_p, c_void_p,
+                                                     c_size_t, ctypes.POINTER(BertDropout), c_int, c_int, c_void_p]),
+    'aspire_bert_cls_mix_train_attn_f32': (c_int, [ctypes.POINTER(BertWeights), c_int64, c_int64, c_void_p, c_size_t, c_void_p, c_void_p,
+                                                   c_void_p, c_void_p, c_int, c_void_p]),
+    'aspire_debug_flash_attn_train_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int64, ctypes.POINTER(BertDropout), c_void_p, c_void_p,
+                                                  c_void_p]),
+    'aspire_debug_flash_attn_train_backward_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                                           ctypes.POINTER(BertDropout), c_int, c_void_p, c_void_p, c_void_p]),
     'aspire_debug_gemm_bf16_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int64,
                                            c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, ctypes.c_float, c_void_p, c_void_p,
                                            c_int64, c_int, c_void_p]),

@@ -100,6 +100,15 @@ int launch_flash_attn_p(const unsigned char* qkvp, const int64_t* mask, float* c
 int launch_cls_attn(const float* qkv, const unsigned char* qkvp, const int64_t* mask, float* ctx, int64_t B, int L, int H, int64_t rows,
                     hipStream_t st);
 
+// enc_attn_train.hip: the fused attention of the training encoder (ASPIRE_ATTENTION_FLASH; bf16 operands, fp32 everywhere else).
+// Forward: qkv [B L, 2304] -> ctx [B L, 768] and stats [B, H, L, 2] = per query the row maximum (log2 units) and the undropped row sum.
+// Backward: D [B, H, L] (scratch) = rowsum(dctx . ctx), then dqkv [B L, 2304] = [dQ | dK | dV], every element written once.
+// drop: the layer's attention site or NULL (no generator in the kernels).  H = 12, L in 1 .. 512.
+int launch_flash_attn_train(const float* qkv, const int64_t* mask, float* ctx, float* stats, int64_t B, int L, int H, const DropSite* drop,
+                            hipStream_t st);
+int launch_flash_attn_train_backward(const float* qkv, const int64_t* mask, const float* ctx, const float* stats, const float* dctx, float* D,
+                                     float* dqkv, int64_t B, int L, int H, const DropSite* drop, hipStream_t st);
+
 // enc_rows.hip: one wave per row of 768 -- LayerNorm, embeddings + LayerNorm (pos_ids [rows] or NULL: the row of pos each token takes,
 // NULL = its index in the document), the CLS rows of a hidden state
 int launch_layernorm(const float* x, const float* gamma, const float* beta, float eps, float* y, int64_t rows, void* yp, hipStream_t st);

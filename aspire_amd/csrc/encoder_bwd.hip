@@ -43,8 +43,14 @@
 // every dW, dV, dK of the backward -- go through launch_gemm_bf16x3 (enc_gemm_bf16x3.hip: operands split into three bf16 planes when
 // staged, six products per term, fp32 accumulators): fp32 accuracy on the bf16 matrix pipe.
 //
+// The attention form (the _attn_ entry points; ASPIRE_ATTENTION_*): with ASPIRE_ATTENTION_FLASH, which ASPIRE_MATMUL_BF16 alone takes,
+// steps 2 - 4 of the forward are one launch (launch_flash_attn_train) that leaves the rows' (m, l) [B, H, L, 2] in the tape's P slot, and
+// the backward's launches between dctx and the QKV projection's are launch_flash_attn_train_backward (D [B, H, L] in the workspace's dP
+// slot): neither buffer has an L^2 term, so carve_tape and carve_train take the mode with the geometry and the _attn size queries
+// answer for it.  ASPIRE_ATTENTION_GEMM: everything above, unchanged.
+//
 // This file is host only (the tape's and the workspace's carve, the two layer loops, the C entry points); the kernels: enc_bwd.hip (rows),
-// enc_gemm.hip (launch_gemm, launch_gemm_tn), enc_gemm_bf16.hip (launch_gemm_bf16), enc_gemm_bf16x3.hip (launch_gemm_bf16x3), enc_attn.hip (launch_softmax_mask), enc_rows.hip
+// enc_gemm.hip (launch_gemm, launch_gemm_tn), enc_gemm_bf16.hip (launch_gemm_bf16), enc_gemm_bf16x3.hip (launch_gemm_bf16x3), enc_attn.hip (launch_softmax_mask), enc_attn_train.hip (the fused training attention), enc_rows.hip
 // (launch_layernorm).
 #include <math.h>
 
@@ -56,14 +62,19 @@ namespace {
 struct Geometry {
     int64_t B, L, M;
     int Lp, H, dh, ffn, n_layers;
-    size_t probs;     // floats of one layer's P
+    size_t probs;     // floats of one layer's P; ASPIRE_ATTENTION_FLASH: of its row statistics (m, l) [B, H, L, 2]
+    size_t dprobs;    // floats of the workspace's dP / dS; ASPIRE_ATTENTION_FLASH: of D [B, H, L]
+    int attention;
 };
-Geometry geometry(const aspire_bert_weights* w, int64_t B, int64_t L) {
+Geometry geometry(const aspire_bert_weights* w, int64_t B, int64_t L, int attention = ASPIRE_ATTENTION_GEMM) {
     Geometry g;
     g.B = B; g.L = L; g.M = B * L;
     g.Lp = (int)((L + 3) / 4 * 4);
     g.H = w->n_heads; g.dh = g.H > 0 ? kD / g.H : 0; g.ffn = w->ffn_dim; g.n_layers = w->n_layers > 0 ? w->n_layers : 0;
-    g.probs = (size_t)B * g.H * L * g.Lp;
+    g.attention = attention;
+    const bool flash = attention == ASPIRE_ATTENTION_FLASH;
+    g.probs = flash ? (size_t)B * g.H * L * 2 : (size_t)B * g.H * L * g.Lp;
+    g.dprobs = flash ? (size_t)B * g.H * L : g.probs;
     return g;
 }
 
@@ -115,7 +126,7 @@ TrainWorkspace carve_train(void* base, const Geometry& g) {
     w.d2 = c.floats(M * kD);
     w.d3 = c.floats(M * kD);
     w.dqkv = c.floats(M * 3 * kD);
-    w.dprobs = c.floats(g.probs);
+    w.dprobs = c.floats(g.dprobs);
     size_t part = layernorm_backward_partial_floats(g.M);
     const size_t c1 = colsum_partial_floats(g.M, 3 * kD), c2 = colsum_partial_floats(g.M, g.ffn > 0 ? g.ffn : 0);
     part = part > c1 ? part : c1;
@@ -185,6 +196,15 @@ int check_matmul(int matmul) {
                    "matmul mode %d: ASPIRE_MATMUL_FP32 (0), ASPIRE_MATMUL_BF16 (1) or ASPIRE_MATMUL_BF16X3 (3)", matmul);
     return ASPIRE_OK;
 }
+// the attention form of the _attn_ entry points (include/aspire_hip.h: ASPIRE_ATTENTION_*): the fused form exists in bf16 alone
+int check_attention(int attention, int matmul) {
+    ASPIRE_REQUIRE(attention == ASPIRE_ATTENTION_GEMM || attention == ASPIRE_ATTENTION_FLASH, ASPIRE_ERR_INVALID_ARG,
+                   "attention mode %d: ASPIRE_ATTENTION_GEMM (0) or ASPIRE_ATTENTION_FLASH (1)", attention);
+    ASPIRE_REQUIRE(attention == ASPIRE_ATTENTION_GEMM || matmul == ASPIRE_MATMUL_BF16, ASPIRE_ERR_UNSUPPORTED,
+                   "ASPIRE_ATTENTION_FLASH is built for ASPIRE_MATMUL_BF16 alone (matmul mode %d): a fused attention at fp32 accuracy does not exist",
+                   matmul);
+    return ASPIRE_OK;
+}
 int read_dropout(const aspire_bert_dropout* d, Dropout* out) {
     if (!d) return ASPIRE_OK;
     if (int rc = check_probability(d->p_hidden, "p_hidden")) return rc;
@@ -202,17 +222,31 @@ int forward_layer(const aspire_bert_weights* w, const Geometry& q, int l, const 
     if (int rc = launch_product(mm, linear(t.x, ly.w_qkv, t.qkv, ly.b_qkv, nullptr, q.M, 3 * kD, kD), 1, kGemmNT, st)) return rc;
     // 2-4. the three-kernel attention; the masked soft-max runs in place: the tape's P
     // (with dropout the tape keeps the undropped P; the dropped copy the P.V product reads goes to the workspace's dprobs, free here)
-    if (int rc = attention_gemm(t.qkv, t.probs, t.ctx, mask, q.B, q.L, q.Lp, q.H, q.dh, nullptr, 0, st, dr.attn() ? &probs : nullptr, ws.dprobs,
-                                mm))
+    // (ASPIRE_ATTENTION_FLASH: one fused launch; the tape's slot keeps the rows' (m, l) instead of P)
+    if (q.attention == ASPIRE_ATTENTION_FLASH) {
+        if (int rc = launch_flash_attn_train(t.qkv, mask, t.ctx, t.probs, q.B, (int)q.L, q.H, dr.attn() ? &probs : nullptr, st)) return rc;
+    } else if (int rc = attention_gemm(t.qkv, t.probs, t.ctx, mask, q.B, q.L, q.Lp, q.H, q.dh, nullptr, 0, st, dr.attn() ? &probs : nullptr,
+                                       ws.dprobs, mm))
         return rc;
     // 5. s1 = ctx . Wo^T + bo + x; h = LN1(s1)
     // 6. u = h . W1^T + b1 (GELU epilogue off); a = GELU(u); s2 = a . W2^T + b2 + h; out = LN2(s2)
     return layer_tail(w, ly, t.ctx, t.x, TailSlots{t.s1, t.h, t.u, act, t.s2}, out, q.M, st, dr.hidden() ? tail : nullptr, mm);
 }
 
+// the QKV projection's backward: ws.dqkv -> dbqkv, dWqkv and the gradient of the layer's input in ws.d2
+int backward_qkv(const aspire_bert_weights* w, const Geometry& q, int l, const TapeLayer& t, const aspire_bert_layer_grads& gr,
+                 const TrainWorkspace& ws, int mm, hipStream_t st) {
+    const aspire_bert_layer& ly = w->layers[l];
+    const int64_t M = q.M;
+    if (int rc = launch_colsum(ws.dqkv, M, 3 * kD, gr.b_qkv, ws.partial, st)) return rc;
+    if (int rc = launch_product(mm, grad_weight(ws.dqkv, t.x, gr.w_qkv, M, 3 * kD, kD), 1, kGemmTN, st)) return rc;
+    return launch_product(mm, grad_input(ws.dqkv, ly.w_qkv, ws.d2, M, 3 * kD, kD), 1, kGemmBKN, st);
+}
+
 // dy (+ dy_res) = the gradient of layer l's output -> ws.d2 (+ ws.d3) = the gradient of its input, the layer's parameter gradients
 int backward_layer(const aspire_bert_weights* w, const Geometry& q, int l, const TapeLayer& t, const aspire_bert_layer_grads& gr,
-                   const float* dy, const float* dy_res, const TrainWorkspace& ws, const Dropout& dr, int mm, hipStream_t st) {
+                   const float* dy, const float* dy_res, const TrainWorkspace& ws, const int64_t* mask, const Dropout& dr, int mm,
+                   hipStream_t st) {
     const aspire_bert_layer& ly = w->layers[l];
     const int64_t M = q.M, L = q.L, B = q.B;
     const int H = q.H, dh = q.dh, Lp = q.Lp, ffn = q.ffn;
@@ -248,6 +282,14 @@ int backward_layer(const aspire_bert_weights* w, const Geometry& q, int l, const
     if (int rc = launch_product(mm, grad_weight(dz1, t.ctx, gr.w_o, M, kD, kD), 1, kGemmTN, st)) return rc;
     if (int rc = launch_product(mm, grad_input(dz1, ly.w_o, ws.d2, M, kD, kD), 1, kGemmBKN, st)) return rc;         // dctx
     // attention, per (document, head); dqkv = [dQ | dK | dV] in qkv's layout
+    if (q.attention == ASPIRE_ATTENTION_FLASH) {
+        // D = rowsum(dctx . ctx) into the workspace, then the key-block and the query-block kernels: every element of dqkv once
+        const DropSite site = dr.probs(l);
+        if (int rc = launch_flash_attn_train_backward(t.qkv, mask, t.ctx, t.probs, ws.d2, ws.dprobs, ws.dqkv, B, (int)L, H,
+                                                      dr.attn() ? &site : nullptr, st))
+            return rc;
+        return backward_qkv(w, q, l, t, gr, ws, mm, st);
+    }
     const auto dP = prob_heads(ws.dprobs, H, L, Lp), dctx = ctx_heads(ws.d2, L, dh);
     const auto Q = qkv_heads(t.qkv, L, dh), K = qkv_heads(t.qkv + kD, L, dh), V = qkv_heads(t.qkv + 2 * kD, L, dh);
     const auto dQ = qkv_heads(ws.dqkv, L, dh), dK = qkv_heads(ws.dqkv + kD, L, dh), dV = qkv_heads(ws.dqkv + 2 * kD, L, dh);
@@ -266,10 +308,7 @@ int backward_layer(const aspire_bert_weights* w, const Geometry& q, int l, const
     if (int rc = launch_product(mm, head_gemm(dP, K, dQ, L, dh, L, H), batch, kGemmBKN, st)) return rc;
     // dK_bh [keys, 64] = dS_bh^T . Q_bh
     if (int rc = launch_product(mm, head_gemm(dP, Q, dK, L, dh, L, H), batch, kGemmTN, st)) return rc;
-    // the QKV projection
-    if (int rc = launch_colsum(ws.dqkv, M, 3 * kD, gr.b_qkv, ws.partial, st)) return rc;
-    if (int rc = launch_product(mm, grad_weight(ws.dqkv, t.x, gr.w_qkv, M, 3 * kD, kD), 1, kGemmTN, st)) return rc;
-    return launch_product(mm, grad_input(ws.dqkv, ly.w_qkv, ws.d2, M, 3 * kD, kD), 1, kGemmBKN, st);
+    return backward_qkv(w, q, l, t, gr, ws, mm, st);
 }
 
 // The CLS read-out's gradient source (aspire_bert_layers_backward_cls_f32): row (b, 0) of hidden state l's gradient takes
@@ -281,8 +320,8 @@ struct ClsSource {
 
 // From the gradient of the top hidden state (grad_hidden, and / or the CLS rows of `cls`) to every parameter gradient and the embedding
 // sum's.  cls NULL: the launches of the backward without a read-out source, none more.
-int backward_stack(const aspire_bert_weights* w, const Geometry& q, const Tape& t, const TrainWorkspace& tw, const float* grad_hidden,
-                   const ClsSource* cls, float* grad_emb_sum, const aspire_bert_grads* grads, const Dropout& dr, int mm, hipStream_t st) {
+int backward_stack(const aspire_bert_weights* w, const Geometry& q, const Tape& t, const TrainWorkspace& tw, const int64_t* mask,
+                   const float* grad_hidden, const ClsSource* cls, float* grad_emb_sum, const aspire_bert_grads* grads, const Dropout& dr, int mm, hipStream_t st) {
     const float *dy = grad_hidden, *dy_res = nullptr;
     if (cls) {
         // the top gradient = grad_hidden (or zeros) + the CLS rows, formed in d2: backward_layer writes d2 only after LN2's backward has
@@ -298,7 +337,7 @@ int backward_stack(const aspire_bert_weights* w, const Geometry& q, const Tape& 
             if (int rc = launch_cls_grad_mix(cls->grad_cls, cls->layer_cls, q.B, q.n_layers + 1, cls->grad_mix, st)) return rc;
     }
     for (int l = q.n_layers - 1; l >= 0; --l) {
-        if (int rc = backward_layer(w, q, l, t.layer(l), grads->layers[l], dy, dy_res, tw, dr, mm, st)) return rc;
+        if (int rc = backward_layer(w, q, l, t.layer(l), grads->layers[l], dy, dy_res, tw, mask, dr, mm, st)) return rc;
         dy = tw.d2;         // the attention branch's gradient of the layer's input ...
         dy_res = tw.d3;     // ... and ds1 down the residual: summed by the LayerNorm backward that reads them
         // hidden state l is this layer's input: its CLS rows' share of the mix lands on the residual branch's gradient, before the
@@ -319,10 +358,11 @@ int backward_stack(const aspire_bert_weights* w, const Geometry& q, const Tape& 
 
 // what the backward entry points share behind their own null checks: the dropout, geometry, gradient-table, tape and workspace checks,
 // then the stack
-int backward_entry(const aspire_bert_weights* w, int64_t B, int64_t L, const float* grad_hidden, const ClsSource* cls, const void* tape,
+int backward_entry(const aspire_bert_weights* w, const int64_t* mask, int64_t B, int64_t L, const float* grad_hidden, const ClsSource* cls, const void* tape,
                    size_t tape_bytes, float* grad_emb_sum, const aspire_bert_grads* grads, void* ws, size_t ws_bytes,
-                   const aspire_bert_dropout* dropout, int matmul, void* stream) {
+                   const aspire_bert_dropout* dropout, int matmul, int attention, void* stream) {
     if (int rc = check_matmul(matmul)) return rc;
+    if (int rc = check_attention(attention, matmul)) return rc;
     Dropout dr;
     if (int rc = read_dropout(dropout, &dr)) return rc;
     if (int rc = check_train_args(w, B, L)) return rc;
@@ -330,9 +370,9 @@ int backward_entry(const aspire_bert_weights* w, int64_t B, int64_t L, const flo
                    "null pointer in the gradient table");
     if (int rc = check_layer_pointers(grads->layers, w->n_layers, "gradients")) return rc;
     if (B == 0) return ASPIRE_OK;
-    const Geometry q = geometry(w, B, L);
+    const Geometry q = geometry(w, B, L, attention);
     if (int rc = check_train_buffers(q, tape, tape_bytes, ws, ws_bytes)) return rc;
-    return backward_stack(w, q, carve_tape(tape, q), carve_train(ws, q), grad_hidden, cls, grad_emb_sum, grads, dr, matmul, (hipStream_t)stream);
+    return backward_stack(w, q, carve_tape(tape, q), carve_train(ws, q), mask, grad_hidden, cls, grad_emb_sum, grads, dr, matmul, (hipStream_t)stream);
 }
 
 // the rows of the in-batch cross-entropy: both calls' checks
@@ -365,16 +405,35 @@ extern "C" size_t aspire_bert_train_workspace_bytes(const aspire_bert_weights* w
     return carve_train(nullptr, geometry(w, B, L)).total;
 }
 
+extern "C" size_t aspire_bert_tape_bytes_attn(const aspire_bert_weights* w, int64_t B, int64_t L, int attention) {
+    if (!w || B <= 0 || L <= 0 || (attention != ASPIRE_ATTENTION_GEMM && attention != ASPIRE_ATTENTION_FLASH)) return 0;
+    return carve_tape(nullptr, geometry(w, B, L, attention)).total;
+}
+
+extern "C" size_t aspire_bert_train_workspace_bytes_attn(const aspire_bert_weights* w, int64_t B, int64_t L, int attention) {
+    if (!w || B <= 0 || L <= 0 || (attention != ASPIRE_ATTENTION_GEMM && attention != ASPIRE_ATTENTION_FLASH)) return 0;
+    return carve_train(nullptr, geometry(w, B, L, attention)).total;
+}
+
 extern "C" int aspire_bert_layers_forward_train_prec_f32(const aspire_bert_weights* w, const float* emb_sum, const int64_t* attn_mask,
                                                          int64_t B, int64_t L, float* hidden_out, void* tape, size_t tape_bytes, void* ws,
                                                          size_t ws_bytes, const aspire_bert_dropout* dropout, int matmul, void* stream) {
+    return aspire_bert_layers_forward_train_attn_f32(w, emb_sum, attn_mask, B, L, hidden_out, tape, tape_bytes, ws, ws_bytes, dropout, matmul,
+                                                     ASPIRE_ATTENTION_GEMM, stream);
+}
+
+extern "C" int aspire_bert_layers_forward_train_attn_f32(const aspire_bert_weights* w, const float* emb_sum, const int64_t* attn_mask,
+                                                         int64_t B, int64_t L, float* hidden_out, void* tape, size_t tape_bytes, void* ws,
+                                                         size_t ws_bytes, const aspire_bert_dropout* dropout, int matmul, int attention,
+                                                         void* stream) {
     ASPIRE_REQUIRE(w && emb_sum && attn_mask && hidden_out, ASPIRE_ERR_INVALID_ARG, "null pointer");
     if (int rc = check_matmul(matmul)) return rc;
+    if (int rc = check_attention(attention, matmul)) return rc;
     Dropout dr;
     if (int rc = read_dropout(dropout, &dr)) return rc;
     if (int rc = check_train_args(w, B, L)) return rc;
     if (B == 0) return ASPIRE_OK;
-    const Geometry q = geometry(w, B, L);
+    const Geometry q = geometry(w, B, L, attention);
     if (int rc = check_train_buffers(q, tape, tape_bytes, ws, ws_bytes)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const Tape t = carve_tape(tape, q);
@@ -409,7 +468,8 @@ extern "C" int aspire_bert_layers_backward_dropout_f32(const aspire_bert_weights
                                                        const aspire_bert_grads* grads, void* ws, size_t ws_bytes,
                                                        const aspire_bert_dropout* dropout, void* stream) {
     ASPIRE_REQUIRE(w && attn_mask && grad_hidden && grads, ASPIRE_ERR_INVALID_ARG, "null pointer");
-    return backward_entry(w, B, L, grad_hidden, nullptr, tape, tape_bytes, grad_emb_sum, grads, ws, ws_bytes, dropout, ASPIRE_MATMUL_FP32, stream);
+    return backward_entry(w, attn_mask, B, L, grad_hidden, nullptr, tape, tape_bytes, grad_emb_sum, grads, ws, ws_bytes, dropout, ASPIRE_MATMUL_FP32,
+                          ASPIRE_ATTENTION_GEMM, stream);
 }
 
 extern "C" int aspire_bert_layers_backward_f32(const aspire_bert_weights* w, const int64_t* attn_mask, int64_t B, int64_t L,
@@ -432,11 +492,19 @@ extern "C" int aspire_bert_dropout_mask_u8(uint64_t seed, uint32_t step, int32_t
 
 extern "C" int aspire_bert_cls_mix_train_f32(const aspire_bert_weights* w, int64_t B, int64_t L, const void* tape, size_t tape_bytes,
                                              const float* hidden_out, const float* mix, float* cls_out, float* layer_cls, void* stream) {
+    return aspire_bert_cls_mix_train_attn_f32(w, B, L, tape, tape_bytes, hidden_out, mix, cls_out, layer_cls, ASPIRE_ATTENTION_GEMM, stream);
+}
+
+extern "C" int aspire_bert_cls_mix_train_attn_f32(const aspire_bert_weights* w, int64_t B, int64_t L, const void* tape, size_t tape_bytes,
+                                                  const float* hidden_out, const float* mix, float* cls_out, float* layer_cls, int attention,
+                                                  void* stream) {
     ASPIRE_REQUIRE(w && hidden_out && cls_out, ASPIRE_ERR_INVALID_ARG, "null pointer (w / hidden_out / cls_out)");
     ASPIRE_REQUIRE(!mix || layer_cls, ASPIRE_ERR_INVALID_ARG, "null pointer (layer_cls with a mix)");
+    ASPIRE_REQUIRE(attention == ASPIRE_ATTENTION_GEMM || attention == ASPIRE_ATTENTION_FLASH, ASPIRE_ERR_INVALID_ARG,
+                   "attention mode %d: ASPIRE_ATTENTION_GEMM (0) or ASPIRE_ATTENTION_FLASH (1)", attention);
     if (int rc = check_bert_shape(w, B, L)) return rc;
     if (B == 0) return ASPIRE_OK;
-    const Geometry q = geometry(w, B, L);
+    const Geometry q = geometry(w, B, L, attention);
     const Tape t = carve_tape(tape, q);
     ASPIRE_REQUIRE(tape && tape_bytes >= t.total, ASPIRE_ERR_INVALID_ARG, "tape too small: need %zu bytes (aspire_bert_tape_bytes)", t.total);
     const ClsStates s{t.base + t.emb_bytes, t.per_layer, hidden_out, q.n_layers};
@@ -448,13 +516,22 @@ extern "C" int aspire_bert_layers_backward_prec_f32(const aspire_bert_weights* w
                                                     const void* tape, size_t tape_bytes, float* grad_emb_sum, const aspire_bert_grads* grads,
                                                     float* grad_mix, void* ws, size_t ws_bytes, const aspire_bert_dropout* dropout,
                                                     int matmul, void* stream) {
+    return aspire_bert_layers_backward_attn_f32(w, attn_mask, B, L, grad_hidden, grad_cls, mix, layer_cls, tape, tape_bytes, grad_emb_sum, grads,
+                                                grad_mix, ws, ws_bytes, dropout, matmul, ASPIRE_ATTENTION_GEMM, stream);
+}
+
+extern "C" int aspire_bert_layers_backward_attn_f32(const aspire_bert_weights* w, const int64_t* attn_mask, int64_t B, int64_t L,
+                                                    const float* grad_hidden, const float* grad_cls, const float* mix, const float* layer_cls,
+                                                    const void* tape, size_t tape_bytes, float* grad_emb_sum, const aspire_bert_grads* grads,
+                                                    float* grad_mix, void* ws, size_t ws_bytes, const aspire_bert_dropout* dropout,
+                                                    int matmul, int attention, void* stream) {
     ASPIRE_REQUIRE(w && attn_mask && grads, ASPIRE_ERR_INVALID_ARG, "null pointer");
     ASPIRE_REQUIRE(grad_hidden || grad_cls, ASPIRE_ERR_INVALID_ARG, "null pointer (grad_hidden and grad_cls: no gradient source)");
     ASPIRE_REQUIRE(!grad_mix || (layer_cls && mix && grad_cls), ASPIRE_ERR_INVALID_ARG,
                    "grad_mix needs grad_cls, mix and layer_cls (null pointer)");
     const ClsSource cls{grad_cls, mix, layer_cls, grad_mix};
-    return backward_entry(w, B, L, grad_hidden, grad_cls ? &cls : nullptr, tape, tape_bytes, grad_emb_sum, grads, ws, ws_bytes, dropout, matmul,
-                          stream);
+    return backward_entry(w, attn_mask, B, L, grad_hidden, grad_cls ? &cls : nullptr, tape, tape_bytes, grad_emb_sum, grads, ws, ws_bytes, dropout,
+                          matmul, attention, stream);
 }
 
 extern "C" int aspire_bert_layers_backward_cls_f32(const aspire_bert_weights* w, const int64_t* attn_mask, int64_t B, int64_t L,

@@ -57,6 +57,9 @@ implementation so that shapes propagate under FakeTensor / torch.compile tracing
     torch.ops.aspire.bert_layers_train_cls_prec(..., seed, step, matmul) / bert_layers_backward_cls_prec(..., matmul)
                                          the dropout pair and the CLS pair with the matmul mode (0 fp32, 1 bf16 matrix products, 3 bf16x3:
                                          HipBertTrainEncoder(matmul='bf16' | 'bf16x3')); autograd registered like their siblings
+    torch.ops.aspire.bert_layers_train_attn(..., matmul, attention) / bert_layers_backward_attn / bert_layers_train_cls_attn /
+    bert_layers_backward_cls_attn        the _prec operators with the attention mode (0 the three-kernel form, 1 the fused training
+                                         attention, with matmul 1 alone: HipBertTrainEncoder(matmul='bf16', attention='flash'))
     torch.ops.aspire.inbatch_xent(q, c) -> (loss [1], row_lse [B])                                 sentsim_models.py:81-126
                                          (autograd registered: the gradient of loss with respect to q and c)
     torch.ops.aspire.inbatch_xent_backward(grad_loss, q, c, row_lse) -> (grad_q, grad_c)
@@ -575,22 +578,41 @@ cls_l2_pair.register_autograd(_cls_l2_pair_grad, setup_context=_cls_l2_pair_setu
 # ---- the encoder under autograd (aspire_bert_layers_forward_train_f32 / aspire_bert_layers_backward_f32) -------------------------------
 # emb_sum [B, L, 768]: word + position + type rows before the embedding LayerNorm; weights: [emb_ln_g, emb_ln_b] + per layer the twelve
 # tensors of bert_encoder_forward's list.  tape: what the backward reads (opaque bytes, aspire_bert_tape_bytes).
-def _train_workspace(bw, b, l, device):
+def _train_workspace(bw, b, l, device, attention=None):
+    if attention is not None:
+        return _scratch(lambda w, b_, l_: lib.aspire_bert_train_workspace_bytes_attn(w, b_, l_, attention), bw, b, l, device)
     return _scratch(lib.aspire_bert_train_workspace_bytes, bw, b, l, device)
+
+
+def _check_attention(matmul, attention):
+    """the _attn operators' modes, before a size query could answer 0 for them (the C entries refuse the same)"""
+    if attention not in (_lib.ATTENTION_GEMM, _lib.ATTENTION_FLASH):
+        raise AssertionError(f'attention mode {attention}: ASPIRE_ATTENTION_GEMM (0) or ASPIRE_ATTENTION_FLASH (1)')
+    if attention == _lib.ATTENTION_FLASH and matmul != 1:
+        raise NotImplementedError(f'ASPIRE_ATTENTION_FLASH is built for ASPIRE_MATMUL_BF16 alone (matmul mode {matmul})')
 
 
 # drop: a _lib.BertDropout for the _dropout_ entry points, None for the plain ones (the body of both operator pairs)
 # matmul: None for those entries, or ASPIRE_MATMUL_* for the _prec_ entry points (drop may then be None as well)
-def _layers_forward(emb_sum, mask, weights, n_heads, ln_eps, drop=None, matmul=None):
+# attention: None for those, or ASPIRE_ATTENTION_* for the _attn_ entry points (with a matmul mode), whose tape and workspace have sizes of their own
+def _layers_forward(emb_sum, mask, weights, n_heads, ln_eps, drop=None, matmul=None, attention=None):
+    if attention is not None:
+        _check_attention(matmul, attention)
     bw = pack_layer_stack(weights, n_heads, ln_eps)
     emb_sum = emb_sum.to(torch.float32).contiguous()
     b, l, _ = emb_sum.shape
     mask, = _int64(mask)
     out = torch.empty_like(emb_sum)
-    tape = _scratch(lib.aspire_bert_tape_bytes, bw, b, l, emb_sum.device)
-    ws = _train_workspace(bw, b, l, emb_sum.device)
+    if attention is not None:
+        tape = _scratch(lambda w, b_, l_: lib.aspire_bert_tape_bytes_attn(w, b_, l_, attention), bw, b, l, emb_sum.device)
+    else:
+        tape = _scratch(lib.aspire_bert_tape_bytes, bw, b, l, emb_sum.device)
+    ws = _train_workspace(bw, b, l, emb_sum.device, attention)
     args = (ctypes.byref(bw), ops._ptr(emb_sum), ops._ptr(mask), b, l, ops._ptr(out), ops._ptr(tape), tape.numel(), ops._ptr(ws), ws.numel())
-    if matmul is not None:
+    if attention is not None:
+        check(lib.aspire_bert_layers_forward_train_attn_f32(*args, ctypes.byref(drop) if drop is not None else None, matmul, attention,
+                                                            ops._stream()))
+    elif matmul is not None:
         check(lib.aspire_bert_layers_forward_train_prec_f32(*args, ctypes.byref(drop) if drop is not None else None, matmul, ops._stream()))
     elif drop is None:
         check(lib.aspire_bert_layers_forward_train_f32(*args, ops._stream()))
@@ -599,7 +621,9 @@ def _layers_forward(emb_sum, mask, weights, n_heads, ln_eps, drop=None, matmul=N
     return out, tape
 
 
-def _layers_backward(grad_hidden, tape, mask, weights, n_heads, ln_eps, drop=None, matmul=None):
+def _layers_backward(grad_hidden, tape, mask, weights, n_heads, ln_eps, drop=None, matmul=None, attention=None):
+    if attention is not None:
+        _check_attention(matmul, attention)
     bw = pack_layer_stack(weights, n_heads, ln_eps)
     grad_hidden = grad_hidden.to(torch.float32).contiguous()
     b, l, _ = grad_hidden.shape
@@ -608,11 +632,15 @@ def _layers_backward(grad_hidden, tape, mask, weights, n_heads, ln_eps, drop=Non
     grad_emb = torch.empty_like(grad_hidden)
     layers = fill_layers(_lib.BertLayerGrads, grads[2:])
     bg = _lib.BertGrads(ctypes.c_void_p(grads[0].data_ptr()), ctypes.c_void_p(grads[1].data_ptr()), layers)
-    ws = _train_workspace(bw, b, l, grad_hidden.device)
+    ws = _train_workspace(bw, b, l, grad_hidden.device, attention)
     args = (ctypes.byref(bw), ops._ptr(mask), b, l, ops._ptr(grad_hidden), ops._ptr(tape), tape.numel(), ops._ptr(grad_emb), ctypes.byref(bg),
             ops._ptr(ws), ws.numel())
     if matmul is not None:
         head, tail = args[:5], args[5:]     # (the _prec_ backward is the CLS one: grad_cls, mix, layer_cls behind grad_hidden; grad_mix behind grads)
+        if attention is not None:
+            check(lib.aspire_bert_layers_backward_attn_f32(*head, None, None, None, *tail[:4], None, *tail[4:],
+                                                           ctypes.byref(drop) if drop is not None else None, matmul, attention, ops._stream()))
+            return grad_emb, grads
         check(lib.aspire_bert_layers_backward_prec_f32(*head, None, None, None, *tail[:4], None, *tail[4:],
                                                        ctypes.byref(drop) if drop is not None else None, matmul, ops._stream()))
     elif drop is None:
@@ -641,12 +669,12 @@ def _(emb_sum, mask, weights, n_heads, ln_eps):
                                                                                      dtype=torch.uint8)
 
 
-def _fake_tape_bytes(emb_sum, weights, n_heads, ln_eps):
-    """aspire_bert_tape_bytes from shapes alone (a host-only query: it reads the struct's geometry, no pointer)."""
+def _fake_tape_bytes(emb_sum, weights, n_heads, ln_eps, attention=0):
+    """aspire_bert_tape_bytes(_attn) from shapes alone (a host-only query: it reads the struct's geometry, no pointer)."""
     n_layers = (len(weights) - 2) // 12
     bw = _lib.BertWeights(None, None, None, None, None, None, n_layers, n_heads, emb_sum.shape[2],
                           weights[2 + 6].shape[0] if n_layers else 4 * emb_sum.shape[2], 0, 0, 0, float(ln_eps), None)
-    return max(lib.aspire_bert_tape_bytes(ctypes.byref(bw), emb_sum.shape[0], emb_sum.shape[1]), 16)
+    return max(lib.aspire_bert_tape_bytes_attn(ctypes.byref(bw), emb_sum.shape[0], emb_sum.shape[1], attention), 16)
 
 
 @bert_layers_backward.register_fake
@@ -724,16 +752,20 @@ def _drop_or_none(p_hidden, p_attn, seed, step):
 
 
 # matmul: None for the entries above, or ASPIRE_MATMUL_* for the _prec_ ones (the body of both operator pairs)
-def _train_cls(emb_sum, mask, weights, mix, n_heads, ln_eps, p_hidden, p_attn, seed, step, matmul=None):
-    hidden, tape = _layers_forward(emb_sum, mask, weights, n_heads, ln_eps, _drop_or_none(p_hidden, p_attn, seed, step), matmul)
+def _train_cls(emb_sum, mask, weights, mix, n_heads, ln_eps, p_hidden, p_attn, seed, step, matmul=None, attention=None):
+    hidden, tape = _layers_forward(emb_sum, mask, weights, n_heads, ln_eps, _drop_or_none(p_hidden, p_attn, seed, step), matmul, attention)
     bw = pack_layer_stack(weights, n_heads, ln_eps)
     b, l, d = hidden.shape
     cls = hidden.new_empty(b, d)
     layer_cls = hidden.new_empty(((len(weights) - 2) // 12 + 1, b, d) if mix is not None else (0,))
     if mix is not None:
         mix = mix.to(torch.float32).contiguous()
-    check(lib.aspire_bert_cls_mix_train_f32(ctypes.byref(bw), b, l, ops._ptr(tape), tape.numel(), ops._ptr(hidden), ops._ptr(mix),
-                                            ops._ptr(cls), ops._ptr(layer_cls if mix is not None else None), ops._stream()))
+    cls_args = (ctypes.byref(bw), b, l, ops._ptr(tape), tape.numel(), ops._ptr(hidden), ops._ptr(mix), ops._ptr(cls),
+                ops._ptr(layer_cls if mix is not None else None))
+    if attention is not None:       # (a tape of that mode: the layer inputs sit at other offsets)
+        check(lib.aspire_bert_cls_mix_train_attn_f32(*cls_args, attention, ops._stream()))
+    else:
+        check(lib.aspire_bert_cls_mix_train_f32(*cls_args, ops._stream()))
     return cls, layer_cls, tape
 
 
@@ -750,7 +782,9 @@ def bert_layers_backward_cls(grad_cls: Tensor, layer_cls: Tensor, tape: Tensor, 
     return _backward_cls(grad_cls, layer_cls, tape, mask, weights, mix, n_heads, ln_eps, p_hidden, p_attn, seed, step)
 
 
-def _backward_cls(grad_cls, layer_cls, tape, mask, weights, mix, n_heads, ln_eps, p_hidden, p_attn, seed, step, matmul=None):
+def _backward_cls(grad_cls, layer_cls, tape, mask, weights, mix, n_heads, ln_eps, p_hidden, p_attn, seed, step, matmul=None, attention=None):
+    if attention is not None:
+        _check_attention(matmul, attention)
     bw = pack_layer_stack(weights, n_heads, ln_eps)
     grad_cls = grad_cls.to(torch.float32).contiguous()
     mask, = _int64(mask)
@@ -762,13 +796,15 @@ def _backward_cls(grad_cls, layer_cls, tape, mask, weights, mix, n_heads, ln_eps
         mix = mix.to(torch.float32).contiguous()
     layers = fill_layers(_lib.BertLayerGrads, grads[2:])
     bg = _lib.BertGrads(ctypes.c_void_p(grads[0].data_ptr()), ctypes.c_void_p(grads[1].data_ptr()), layers)
-    ws = _train_workspace(bw, b, l, grad_cls.device)
+    ws = _train_workspace(bw, b, l, grad_cls.device, attention)
     drop = _drop_or_none(p_hidden, p_attn, seed, step)
     with_mix = mix is not None
     args = (ctypes.byref(bw), ops._ptr(mask), b, l, None, ops._ptr(grad_cls), ops._ptr(mix),
             ops._ptr(layer_cls.contiguous() if with_mix else None), ops._ptr(tape), tape.numel(), ops._ptr(grad_emb), ctypes.byref(bg),
             ops._ptr(grad_mix if with_mix else None), ops._ptr(ws), ws.numel(), ctypes.byref(drop) if drop is not None else None)
-    if matmul is not None:
+    if attention is not None:
+        check(lib.aspire_bert_layers_backward_attn_f32(*args, matmul, attention, ops._stream()))
+    elif matmul is not None:
         check(lib.aspire_bert_layers_backward_prec_f32(*args, matmul, ops._stream()))
     else:
         check(lib.aspire_bert_layers_backward_cls_f32(*args, ops._stream()))
@@ -897,6 +933,96 @@ def _bert_layers_train_cls_prec_grad(ctx, grad_cls, grad_layer_cls, grad_tape):
 bert_layers_train_cls_prec.register_autograd(_bert_layers_train_cls_prec_grad, setup_context=_bert_layers_train_cls_prec_setup)
 
 
+# ---- the attention mode (aspire_bert_layers_forward_train_attn_f32 / aspire_bert_layers_backward_attn_f32) ---------------------------------
+# The _prec operators with a trailing attention: int (include/aspire_hip.h: ASPIRE_ATTENTION_GEMM 0 -- the _prec operators' launches and
+# bits; ASPIRE_ATTENTION_FLASH 1 -- the fused attention, with matmul = 1 alone: any other matmul mode raises NotImplementedError; any
+# other integer is refused).  The tape is the mode's own (aspire_bert_tape_bytes_attn): with 1 it holds two statistics per (document,
+# head, query) where the probabilities were.  HipBertTrainEncoder takes these only with attention != 'gemm'.
+@torch.library.custom_op('aspire::bert_layers_train_attn', mutates_args=(), device_types='cuda')
+def bert_layers_train_attn(emb_sum: Tensor, mask: Tensor, weights: List[Tensor], n_heads: int, ln_eps: float, p_hidden: float, p_attn: float,
+                           seed: int, step: int, matmul: int, attention: int) -> Tuple[Tensor, Tensor]:
+    return _layers_forward(emb_sum, mask, weights, n_heads, ln_eps, _drop_or_none(p_hidden, p_attn, seed, step), matmul, attention)
+
+
+@torch.library.custom_op('aspire::bert_layers_backward_attn', mutates_args=(), device_types='cuda')
+def bert_layers_backward_attn(grad_hidden: Tensor, tape: Tensor, mask: Tensor, weights: List[Tensor], n_heads: int, ln_eps: float,
+                              p_hidden: float, p_attn: float, seed: int, step: int, matmul: int,
+                              attention: int) -> Tuple[Tensor, List[Tensor]]:
+    return _layers_backward(grad_hidden, tape, mask, weights, n_heads, ln_eps, _drop_or_none(p_hidden, p_attn, seed, step), matmul, attention)
+
+
+@bert_layers_train_attn.register_fake
+def _(emb_sum, mask, weights, n_heads, ln_eps, p_hidden, p_attn, seed, step, matmul, attention):
+    return emb_sum.new_empty(emb_sum.shape, dtype=torch.float32), emb_sum.new_empty(
+        _fake_tape_bytes(emb_sum, weights, n_heads, ln_eps, attention), dtype=torch.uint8)
+
+
+@bert_layers_backward_attn.register_fake
+def _(grad_hidden, tape, mask, weights, n_heads, ln_eps, p_hidden, p_attn, seed, step, matmul, attention):
+    return grad_hidden.new_empty(grad_hidden.shape, dtype=torch.float32), [t.new_empty(t.shape) for t in weights]
+
+
+def _bert_layers_train_attn_setup(ctx, inputs, output):
+    emb_sum, mask, weights, ctx.n_heads, ctx.ln_eps, *ctx.mode = inputs         # mode: p_hidden, p_attn, seed, step, matmul, attention
+    ctx.save_for_backward(output[1], mask, *weights)
+
+
+def _bert_layers_train_attn_grad(ctx, grad_hidden, grad_tape):
+    tape, mask, *weights = ctx.saved_tensors
+    grad_emb, grads = torch.ops.aspire.bert_layers_backward_attn(grad_hidden, tape, mask, weights, ctx.n_heads, ctx.ln_eps, *ctx.mode)
+    return grad_emb, None, grads, None, None, None, None, None, None, None, None
+
+
+bert_layers_train_attn.register_autograd(_bert_layers_train_attn_grad, setup_context=_bert_layers_train_attn_setup)
+
+
+@torch.library.custom_op('aspire::bert_layers_train_cls_attn', mutates_args=(), device_types='cuda')
+def bert_layers_train_cls_attn(emb_sum: Tensor, mask: Tensor, weights: List[Tensor], mix: Optional[Tensor], n_heads: int, ln_eps: float,
+                               p_hidden: float, p_attn: float, seed: int, step: int, matmul: int,
+                               attention: int) -> Tuple[Tensor, Tensor, Tensor]:
+    return _train_cls(emb_sum, mask, weights, mix, n_heads, ln_eps, p_hidden, p_attn, seed, step, matmul, attention)
+
+
+@torch.library.custom_op('aspire::bert_layers_backward_cls_attn', mutates_args=(), device_types='cuda')
+def bert_layers_backward_cls_attn(grad_cls: Tensor, layer_cls: Tensor, tape: Tensor, mask: Tensor, weights: List[Tensor],
+                                  mix: Optional[Tensor], n_heads: int, ln_eps: float, p_hidden: float, p_attn: float, seed: int, step: int,
+                                  matmul: int, attention: int) -> Tuple[Tensor, List[Tensor], Tensor]:
+    return _backward_cls(grad_cls, layer_cls, tape, mask, weights, mix, n_heads, ln_eps, p_hidden, p_attn, seed, step, matmul, attention)
+
+
+@bert_layers_train_cls_attn.register_fake
+def _(emb_sum, mask, weights, mix, n_heads, ln_eps, p_hidden, p_attn, seed, step, matmul, attention):
+    b, _, d = emb_sum.shape
+    return (emb_sum.new_empty((b, d), dtype=torch.float32),
+            emb_sum.new_empty(((len(weights) - 2) // 12 + 1, b, d) if mix is not None else (0,), dtype=torch.float32),
+            emb_sum.new_empty(_fake_tape_bytes(emb_sum, weights, n_heads, ln_eps, attention), dtype=torch.uint8))
+
+
+@bert_layers_backward_cls_attn.register_fake
+def _(grad_cls, layer_cls, tape, mask, weights, mix, n_heads, ln_eps, p_hidden, p_attn, seed, step, matmul, attention):
+    b, l = mask.shape
+    return (grad_cls.new_empty((b, l, grad_cls.shape[1]), dtype=torch.float32), [t.new_empty(t.shape) for t in weights],
+            grad_cls.new_empty(mix.numel() if mix is not None else 0, dtype=torch.float32))
+
+
+def _bert_layers_train_cls_attn_setup(ctx, inputs, output):
+    emb_sum, mask, weights, mix, ctx.n_heads, ctx.ln_eps, *ctx.mode = inputs
+    ctx.with_mix = mix is not None
+    ctx.save_for_backward(output[1], output[2], mask, *([mix] if ctx.with_mix else []), *weights)
+    ctx.mark_non_differentiable(output[1])
+
+
+def _bert_layers_train_cls_attn_grad(ctx, grad_cls, grad_layer_cls, grad_tape):
+    layer_cls, tape, mask, *rest = ctx.saved_tensors
+    mix, weights = (rest[0], rest[1:]) if ctx.with_mix else (None, rest)
+    grad_emb, grads, grad_mix = torch.ops.aspire.bert_layers_backward_cls_attn(grad_cls, layer_cls, tape, mask, weights, mix, ctx.n_heads,
+                                                                               ctx.ln_eps, *ctx.mode)
+    return grad_emb, None, grads, grad_mix if ctx.with_mix else None, None, None, None, None, None, None, None, None
+
+
+bert_layers_train_cls_attn.register_autograd(_bert_layers_train_cls_attn_grad, setup_context=_bert_layers_train_cls_attn_setup)
+
+
 # ---- the in-batch cross-entropy (aspire_inbatch_xent_f32 / aspire_inbatch_xent_backward_f32) -----------------------------------------------
 # ICTBERTWrapper.forward_rank's loss (sentsim_models.py:81-126) over two towers' CLS rows q, c [B, 768], B <= 128: loss [1] and the
 # rows' logsumexp [B], which the backward reads.
@@ -1013,4 +1139,5 @@ OPS = ('span_mean_pool', 'span_pool_ranges', 'bert_encoder_forward', 'bert_cls_f
        'sent_cdist', 'sent_cdist_backward', 'span_mean_pool_backward', 'cls_l2_pair', 'cls_l2_pair_backward', 'bert_layers_train', 'bert_layers_backward',
        'bert_layers_train_dropout', 'bert_layers_backward_dropout', 'bert_dropout_mask', 'bert_layers_train_cls', 'bert_layers_backward_cls',
        'bert_layers_train_prec', 'bert_layers_backward_prec', 'bert_layers_train_cls_prec', 'bert_layers_backward_cls_prec',
+       'bert_layers_train_attn', 'bert_layers_backward_attn', 'bert_layers_train_cls_attn', 'bert_layers_backward_cls_attn',
        'inbatch_xent', 'inbatch_xent_backward', 'bert_embed_sum', 'bert_embed_backward')

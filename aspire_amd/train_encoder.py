@@ -41,6 +41,14 @@ the bf16 matrix cores: each operand split into three bf16 values, six products p
 ``matmul='fp32'`` goes through the operators described above, untouched.  ``eval()`` and ``torch.no_grad()`` forwards stay on the
 inference path in fp32 in every mode: the mode is a property of training steps.
 
+The attention form is opt-in too, with ``matmul='bf16'`` alone.  ``HipBertTrainEncoder(bert_model, matmul='bf16', attention='flash')``
+runs each layer's attention as one fused forward kernel and three backward kernels (torch.ops.aspire.bert_layers_train_attn /
+bert_layers_train_cls_attn; aspire_amd/csrc/enc_attn_train.hip): the tape keeps two fp32 statistics per (document, head, query)
+instead of the [L, L] probabilities, so it grows linearly in L, and the backward forms the probabilities and the dropout masks again.
+Its operands (Q, K, V, the probabilities, dctx, dS) are rounded to bf16 once each, as the mode's other products are; the masks are the
+ones ``attention='gemm'`` draws.  With ``matmul='fp32'`` or ``'bf16x3'`` it raises NotImplementedError (a fused attention at fp32
+accuracy does not exist).  The default ``attention='gemm'`` is the launches and bits described above.
+
 Not supported: activation checkpointing around this module -- the recomputed forward would draw the next step's masks, not the first
 forward's.
 """
@@ -54,12 +62,18 @@ from .encoder import _LAYER_KEYS, require_bert_base
 
 class HipBertTrainEncoder(torch.nn.Module):
     MATMUL_MODES = {'fp32': 0, 'bf16': 1, 'bf16x3': 3}        # include/aspire_hip.h: ASPIRE_MATMUL_* (2 is not a mode)
+    ATTENTION_MODES = {'gemm': 0, 'flash': 1}                 # include/aspire_hip.h: ASPIRE_ATTENTION_*
 
-    def __init__(self, bert_model, dropout=False, seed=None, hip_embeddings=False, check_ids=True, matmul='fp32'):
+    def __init__(self, bert_model, dropout=False, seed=None, hip_embeddings=False, check_ids=True, matmul='fp32', attention='gemm'):
         super().__init__()
         if matmul not in self.MATMUL_MODES:
             raise ValueError(f"HipBertTrainEncoder: matmul={matmul!r}: 'fp32', 'bf16' or 'bf16x3'")
-        self.matmul = matmul
+        if attention not in self.ATTENTION_MODES:
+            raise ValueError(f"HipBertTrainEncoder: attention={attention!r}: 'gemm' or 'flash'")
+        if attention == 'flash' and matmul != 'bf16':
+            raise NotImplementedError(f"HipBertTrainEncoder: attention='flash' is built for matmul='bf16' alone (got matmul={matmul!r}): "
+                                      'a fused attention at fp32 accuracy does not exist')
+        self.matmul, self.attention = matmul, attention
         dev = ops.require_gpu()
         self.hip_embeddings, self.check_ids = bool(hip_embeddings), bool(check_ids)
         cfg = bert_model.config
@@ -164,6 +178,8 @@ class HipBertTrainEncoder(torch.nn.Module):
             self._step = (step + 1) % 2 ** 32
         args = (emb_sum, msk, self.layer_weights(), mix, cfg.num_attention_heads, cfg.layer_norm_eps, self.p_hidden, self.p_attn,
                 seed - 2 ** 64 if seed >= 2 ** 63 else seed, step)
+        if self.attention != 'gemm':
+            return torch.ops.aspire.bert_layers_train_cls_attn(*args, self.MATMUL_MODES[self.matmul], self.ATTENTION_MODES[self.attention])[0]
         if self.matmul != 'fp32':
             return torch.ops.aspire.bert_layers_train_cls_prec(*args, self.MATMUL_MODES[self.matmul])[0]
         cls, _layer_cls, _tape = torch.ops.aspire.bert_layers_train_cls(*args)
@@ -196,9 +212,11 @@ class HipBertTrainEncoder(torch.nn.Module):
             seed, step = self._seed, self._step
             if self.dropout:
                 self._step = (step + 1) % 2 ** 32
-            hidden, _tape = torch.ops.aspire.bert_layers_train_prec(emb_sum, msk, self.layer_weights(), cfg.num_attention_heads, cfg.layer_norm_eps,
-                                                                    self.p_hidden, self.p_attn, seed - 2 ** 64 if seed >= 2 ** 63 else seed, step,
-                                                                    self.MATMUL_MODES[self.matmul])
+            args = (emb_sum, msk, self.layer_weights(), cfg.num_attention_heads, cfg.layer_norm_eps, self.p_hidden, self.p_attn,
+                    seed - 2 ** 64 if seed >= 2 ** 63 else seed, step, self.MATMUL_MODES[self.matmul])
+            if self.attention != 'gemm':
+                return torch.ops.aspire.bert_layers_train_attn(*args, self.ATTENTION_MODES[self.attention])[0]
+            hidden, _tape = torch.ops.aspire.bert_layers_train_prec(*args)
             return hidden
         if not self.dropout:
             hidden, _tape = torch.ops.aspire.bert_layers_train(emb_sum, msk, self.layer_weights(), cfg.num_attention_heads, cfg.layer_norm_eps)

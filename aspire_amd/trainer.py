@@ -214,6 +214,7 @@ class RankTrainer:
                  'dev_score_history': list(self.dev_score_history), 'dev_checked_iters': list(self.dev_checked_iters),
                  'dropout_state': tuple(self.encoder.dropout_state()) if hasattr(self.encoder, 'dropout_state') else None,
                  'matmul': getattr(self.encoder, 'matmul', 'fp32'),
+                 'attention': getattr(self.encoder, 'attention', 'gemm'),
                  'last_grad_norm': None if self.last_grad_norm is None else float(self.last_grad_norm),
                  'torch_rng_state': torch.get_rng_state()}
         torch.save(state, path)
@@ -225,6 +226,11 @@ class RankTrainer:
         if saved != mine:
             raise ValueError(f"checkpoint written with matmul={saved!r}, this encoder runs matmul={mine!r}: resume with the mode the run was "
                              'started in')
+        # ... and so is the attention form (a checkpoint from before the key: 'gemm')
+        saved, mine = state.get('attention', 'gemm'), getattr(self.encoder, 'attention', 'gemm')
+        if saved != mine:
+            raise ValueError(f"checkpoint written with attention={saved!r}, this encoder runs attention={mine!r}: resume with the mode the run "
+                             'was started in')
         self.encoder.load_state_dict(state['encoder'])
         self.optimizer.load_state_dict(state['optimizer'])
         self.scheduler.load_state_dict(state['scheduler'])

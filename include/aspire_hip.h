@@ -457,6 +457,60 @@ int aspire_debug_gemm_bf16x3_f32(const float* A, const float* B, float* C, int64
                                  void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * A1t with a fused attention (opt-in, with ASPIRE_MATMUL_BF16 only): no [L, L] tensor on the tape or in the workspace.
+ *
+ * aspire_bert_layers_forward_train_attn_f32 / aspire_bert_layers_backward_attn_f32 are the _prec_ entries plus `attention`:
+ *   ASPIRE_ATTENTION_GEMM   those calls (the _prec_ entries forward here with it): the same launches, the same bits
+ *   ASPIRE_ATTENTION_FLASH  per layer, the forward's Q K^T, soft-max, dropout and P V launches become ONE kernel that writes ctx and, per
+ *                           (document, head, query), two fp32 statistics -- the row maximum m of the scaled, masked scores in log2
+ *                           units and the row sum l of exp2(s - m) over the UNdropped probabilities -- in the tape slot that held P;
+ *                           the backward's launches over [B, 12, L, L] become three kernels: D = rowsum(bf16(dctx) . ctx), a key-block
+ *                           kernel (dK, dV) and a query-block kernel (dQ), which form P = exp2(s - m) / l and the dropout mask again.
+ *                           Valid with ASPIRE_MATMUL_BF16 alone: any other matmul mode -> ASPIRE_ERR_UNSUPPORTED
+ *   any other value         ASPIRE_ERR_INVALID_ARG before the device is touched
+ * The forward and the backward of one step take the same modes, and a tape and a workspace of the _attn size queries
+ * (aspire_bert_tape_bytes_attn, aspire_bert_train_workspace_bytes_attn: host only; with ASPIRE_ATTENTION_GEMM the values of
+ * aspire_bert_tape_bytes / aspire_bert_train_workspace_bytes, with ASPIRE_ATTENTION_FLASH linear in L; 0 for an unknown mode).
+ * aspire_bert_cls_mix_train_attn_f32 is aspire_bert_cls_mix_train_f32 on a tape of that mode (the layer inputs sit at other offsets).
+ *
+ * The arithmetic of the fused attention, and nothing else: Q, K, V and dctx are rounded to bf16 once (round to nearest even) as their
+ * tiles are staged; scores, the online exp2 soft-max, m, l and D are fp32; HuggingFace's mask semantics as in every other form (a
+ * masked key adds the finite -FLT_MAX; a document without a real key attends uniformly -- which is why m and l are two values:
+ * -FLT_MAX + log2(L) rounds back to -FLT_MAX); the forward rounds the UNNORMALISED probability exp2(s - m_running), times keep . scale
+ * where the site drops, to bf16 on its way into the product with V and divides by l in fp32; the backward rounds
+ * P_drop = keep scale exp2(s - m) / l and dS = P (keep scale (dctx V^T) - D) to bf16 as they enter dV = P_drop^T dctx,
+ * dK = dS^T Q / 8 and dQ = dS K / 8 (the 1 / 8 in fp32).  Dropout: site 1 + 3 layer on the logical index ((b 12 + h) L + i) L + j
+ * (aspire_bert_dropout_mask_u8's masks).  No atomics, one writer per element, fixed summation orders: the same bits on every run.
+ *
+ * aspire_debug_flash_attn_train_f32 / aspire_debug_flash_attn_train_backward_f32: the bare kernels, for tests and tools.  qkv
+ * [B L, 2304] fp32, mask int64 [B, L], ctx / dctx [B L, 768], stats [B, 12, L, 2] = (m, l), dqkv [B L, 2304] = [dQ | dK | dV]; 12 heads
+ * of 64, L in 1 .. 512.  dropout NULL or p_attn == 0: none; else p_attn, seed and step of the struct at the site of `layer` (the
+ * forward entry: layer 0).  D [B, 12, L] fp32 is the backward's scratch, the caller's as in the layer stack (written, then read by the
+ * two kernels behind it on the same stream): the entry allocates nothing and does not wait for the stream.
+ * ------------------------------------------------------------------------------------------- */
+#define ASPIRE_ATTENTION_GEMM 0
+#define ASPIRE_ATTENTION_FLASH 1
+
+size_t aspire_bert_tape_bytes_attn(const aspire_bert_weights* w, int64_t B, int64_t L, int attention);
+size_t aspire_bert_train_workspace_bytes_attn(const aspire_bert_weights* w, int64_t B, int64_t L, int attention);
+int aspire_bert_layers_forward_train_attn_f32(const aspire_bert_weights* w, const float* emb_sum, const int64_t* attn_mask, int64_t B,
+                                              int64_t L, float* hidden_out, void* tape, size_t tape_bytes, void* ws, size_t ws_bytes,
+                                              const aspire_bert_dropout* dropout, int matmul, int attention, void* stream);
+int aspire_bert_layers_backward_attn_f32(const aspire_bert_weights* w, const int64_t* attn_mask, int64_t B, int64_t L,
+                                         const float* grad_hidden, const float* grad_cls, const float* mix, const float* layer_cls,
+                                         const void* tape, size_t tape_bytes, float* grad_emb_sum, const aspire_bert_grads* grads,
+                                         float* grad_mix, void* ws, size_t ws_bytes, const aspire_bert_dropout* dropout, int matmul,
+                                         int attention, void* stream);
+int aspire_bert_cls_mix_train_attn_f32(const aspire_bert_weights* w, int64_t B, int64_t L, const void* tape, size_t tape_bytes,
+                                       const float* hidden_out, const float* mix, float* cls_out, float* layer_cls, int attention,
+                                       void* stream);
+int aspire_debug_flash_attn_train_f32(const float* qkv, const int64_t* mask, int64_t B, int64_t L, const aspire_bert_dropout* dropout,
+                                      float* ctx, float* stats, void* stream);
+int aspire_debug_flash_attn_train_backward_f32(const float* qkv, const int64_t* mask, const float* ctx, const float* stats,
+                                               const float* dctx, int64_t B, int64_t L, const aspire_bert_dropout* dropout, int layer,
+                                               float* D, float* dqkv, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The embedding lookup under training: BertEmbeddings' sum in front of aspire_bert_layers_forward_train_f32 and the three tables'
  * gradients behind aspire_bert_layers_backward_f32 (what nn.Embedding's forward and scatter backward do on the reference path).
  * Hidden size 768.  Token rows m = b L + l, M = B L.  word [vocab, 768], pos [max_pos, 768], type [n_types, 768]; tok, typ int64

@@ -1,5 +1,5 @@
 """One training step of the encoder -- forward + backward of a 12-layer BERT-base (ffn 3072), dropout 0 -- in the three matmul modes of
-aspire_amd.HipBertTrainEncoder, next to HuggingFace BertModel under torch autograd in fp32 and under
+aspire_amd.HipBertTrainEncoder and in its fused-attention mode, next to HuggingFace BertModel under torch autograd in fp32 and under
 torch.autocast('cuda', dtype=torch.bfloat16), on the same card ("bf16 matrix products").
 
 ONE side per process (a process's place on the card moves the step by more than the trees differ: DESIGN.md section 7), so a comparison
@@ -8,6 +8,7 @@ is several runs of this tool in one session on one card:
     python tools/bf16_step_time.py --side fp32          HipBertTrainEncoder(model)                 (also runs on a tree without the mode)
     python tools/bf16_step_time.py --side bf16          HipBertTrainEncoder(model, matmul='bf16')
     python tools/bf16_step_time.py --side bf16x3        HipBertTrainEncoder(model, matmul='bf16x3')
+    python tools/bf16_step_time.py --side flash         HipBertTrainEncoder(model, matmul='bf16', attention='flash')
     python tools/bf16_step_time.py --side hf            BertModel, fp32
     python tools/bf16_step_time.py --side hf-autocast   BertModel under torch.autocast('cuda', dtype=torch.bfloat16)
 
@@ -39,7 +40,7 @@ def window(fn, calls):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--side', choices=['fp32', 'bf16', 'bf16x3', 'hf', 'hf-autocast'], required=True)
+    ap.add_argument('--side', choices=['fp32', 'bf16', 'bf16x3', 'flash', 'hf', 'hf-autocast'], required=True)
     ap.add_argument('--shapes', default='3x512,10x256')
     ap.add_argument('--layers', type=int, default=12)
     ap.add_argument('--windows', type=int, default=5)
@@ -51,10 +52,11 @@ def main():
     cfg = BertConfig(vocab_size=3000, hidden_size=768, num_hidden_layers=a.layers, num_attention_heads=12, intermediate_size=3072,
                      max_position_embeddings=512, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0)
     model = BertModel(cfg, add_pooling_layer=False).cuda().train()
-    ours = a.side in ('fp32', 'bf16', 'bf16x3')
+    ours = a.side in ('fp32', 'bf16', 'bf16x3', 'flash')
     if ours:
         from aspire_amd import HipBertTrainEncoder
-        model = (HipBertTrainEncoder(model) if a.side == 'fp32' else HipBertTrainEncoder(model, matmul=a.side)).train()
+        kw = {'fp32': {}, 'flash': dict(matmul='bf16', attention='flash')}.get(a.side, dict(matmul=a.side))
+        model = HipBertTrainEncoder(model, **kw).train()
     for shape in a.shapes.split(','):
         b, l = (int(x) for x in shape.split('x'))
         g = torch.Generator().manual_seed(b * 1000 + l)
@@ -80,6 +82,7 @@ def main():
             step()
         torch.cuda.synchronize()
         calls = max(int(a.window_s * 1e3 / window(step, 3)), 2)
+        torch.cuda.reset_peak_memory_stats()      # the peak of this shape's steps alone
         t = [window(step, calls) for _ in range(a.windows)]
         print(json.dumps(dict(side=a.side, B=b, L=l, layers=a.layers, ms_median=round(float(np.median(t)), 3),
                               ms_min_max=[round(min(t), 3), round(max(t), 3)], steps_per_window=calls,
