@@ -10,6 +10,7 @@ from .pair_distances import (AllPairMaskedWasserstein, AllPairMaskedAttention, a
                              allpair_masked_dist_l2topk, allpair_joint_sm_negscore, rep_len_tup)
 from .rank_loss import RankLoss, SupAlignRankLoss, cross_doc_l1, sent_reps_from_hidden  # noqa: F401
 from .train_encoder import HipBertTrainEncoder  # noqa: F401
+from .packing import PackedRows, packed_rows  # noqa: F401
 from .cls_train import BiEncTrain, ClsTripletLoss, IctEncTrain, IctLoss, SentEncTrain  # noqa: F401
 from .optim import HipAdam, HipAdamW, HipAdagrad, clip_grad_norm_, grad_norm  # noqa: F401
 from .trainer import RankTrainer  # noqa: F401

@@ -81,6 +81,12 @@ class BertDropout(ctypes.Structure):
     _fields_ = [('p_hidden', ctypes.c_float), ('p_attn', ctypes.c_float), ('seed', ctypes.c_uint64), ('step', ctypes.c_uint32)]
 
 
+class BertPacking(ctypes.Structure):
+    """struct aspire_bert_packing"""
+    _fields_ = [('rows', c_int64), ('max_len', c_int32), ('prefix', c_int32), ('doc_start', c_void_p), ('row_src', c_void_p),
+                ('row_dst', c_void_p)]
+
+
 class BertExtras(ctypes.Structure):
     """struct aspire_bert_extras"""
     _fields_ = [('pos_ids', c_void_p), ('rel_bias', c_void_p), ('rel_span', c_int32)]
@@ -183,6 +189,20 @@ SIGNATURES = {
                                                   c_void_p]),
     'aspire_debug_flash_attn_train_backward_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
                                                            ctypes.POINTER(BertDropout), c_int, c_void_p, c_void_p, c_void_p]),
+    'aspire_bert_tape_bytes_packed': (c_size_t, [ctypes.POINTER(BertWeights), c_int64, c_int64, c_int64]),
+    'aspire_bert_train_workspace_bytes_packed': (c_size_t, [ctypes.POINTER(BertWeights), c_int64, c_int64, c_int64]),
+    'aspire_bert_layers_forward_train_packed_f32': (c_int, [ctypes.POINTER(BertWeights), c_void_p, ctypes.POINTER(BertPacking), c_int64, c_int64,
+                                                            c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, ctypes.POINTER(BertDropout), c_int,
+                                                            c_int, c_void_p]),
+    'aspire_bert_layers_backward_packed_f32': (c_int, [ctypes.POINTER(BertWeights), ctypes.POINTER(BertPacking), c_int64, c_int64, c_void_p,
+                                                       c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, ctypes.POINTER(BertGrads),
+                                                       c_void_p, c_void_p, c_size_t, ctypes.POINTER(BertDropout), c_int, c_int, c_void_p]),
+    'aspire_bert_cls_mix_train_packed_f32': (c_int, [ctypes.POINTER(BertWeights), ctypes.POINTER(BertPacking), c_int64, c_int64, c_void_p,
+                                                     c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'aspire_debug_flash_attn_train_packed_f32': (c_int, [c_void_p, ctypes.POINTER(BertPacking), c_int64, c_int64, ctypes.POINTER(BertDropout),
+                                                         c_void_p, c_void_p, c_void_p]),
+    'aspire_debug_flash_attn_train_packed_backward_f32': (c_int, [c_void_p, ctypes.POINTER(BertPacking), c_void_p, c_void_p, c_void_p, c_int64,
+                                                                  c_int64, ctypes.POINTER(BertDropout), c_int, c_void_p, c_void_p, c_void_p]),
     'aspire_debug_gemm_bf16_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int64,
                                            c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, ctypes.c_float, c_void_p, c_void_p,
                                            c_int64, c_int, c_void_p]),

@@ -12,7 +12,8 @@
 
 ``hip_embeddings`` / ``check_ids`` go to every tower's HipBertTrainEncoder (the embedding tables' gradients in HIP, in a fixed order),
 and so does ``matmul`` ('fp32' | 'bf16' | 'bf16x3': the mode of the layer stack's matrix products; a module's ``matmul`` attribute is its towers')
-and ``attention`` ('gemm' | 'flash': the fused training attention, with ``matmul='bf16'`` alone; the ``attention`` attribute likewise).
+and ``attention`` ('gemm' | 'flash': the fused training attention, with ``matmul='bf16'`` alone; the ``attention`` attribute likewise)
+and ``packed`` (padding-free batches, with ``attention='flash'`` alone: every document's mask must start with a valid token).
 A module's ``forward(bert_batch)`` gives the [B, 768] document (sentence) reps; ``state_dict()`` speaks the reference's key names, so
 ``model_final.pt`` / ``model_cur_best.pt`` load into ``AspireBiEnc`` / ``AspireSentEnc`` unchanged.  What runs where: the layer stack,
 the read-out (with MySPECTER's soft-max layer mix) and their backward are torch.ops.aspire.bert_layers_train_cls; the soft-max over
@@ -67,12 +68,13 @@ class BiEncTrain(_ClsTrainModule):
     towers = ('bert_encoder',)
     own_keys = ('bert_layer_weights.weight',)
 
-    def __init__(self, bert_model, model_hparams=None, dropout=False, seed=None, hip_embeddings=False, check_ids=True, matmul='fp32', attention='gemm'):
+    def __init__(self, bert_model, model_hparams=None, dropout=False, seed=None, hip_embeddings=False, check_ids=True, matmul='fp32', attention='gemm',
+                 packed=False):
         super().__init__()
         self.bert_encoding_dim = 768
         self.bert_encoder = HipBertTrainEncoder(bert_model, dropout=dropout, seed=seed, hip_embeddings=hip_embeddings, check_ids=check_ids,
-                                                matmul=matmul, attention=attention)
-        self.matmul, self.attention = self.bert_encoder.matmul, self.bert_encoder.attention
+                                                matmul=matmul, attention=attention, packed=packed)
+        self.matmul, self.attention, self.packed = self.bert_encoder.matmul, self.bert_encoder.attention, self.bert_encoder.packed
         self.bert_layer_count = self.bert_encoder.config.num_hidden_layers + 1      # plus 1 for the bottom most layer
         if not (model_hparams or {}).get('fine_tune', True):
             for param in self.bert_encoder.parameters():
@@ -89,12 +91,12 @@ class SentEncTrain(_ClsTrainModule):
     """SentBERTWrapper's training side: a sentence's rep is the CLS row of last_hidden_state."""
     towers = ('sent_encoder',)
 
-    def __init__(self, bert_model, dropout=False, seed=None, hip_embeddings=False, check_ids=True, matmul='fp32', attention='gemm'):
+    def __init__(self, bert_model, dropout=False, seed=None, hip_embeddings=False, check_ids=True, matmul='fp32', attention='gemm', packed=False):
         super().__init__()
         self.bert_encoding_dim = 768
         self.sent_encoder = HipBertTrainEncoder(bert_model, dropout=dropout, seed=seed, hip_embeddings=hip_embeddings, check_ids=check_ids,
-                                                matmul=matmul, attention=attention)
-        self.matmul, self.attention = self.sent_encoder.matmul, self.sent_encoder.attention
+                                                matmul=matmul, attention=attention, packed=packed)
+        self.matmul, self.attention, self.packed = self.sent_encoder.matmul, self.sent_encoder.attention, self.sent_encoder.packed
 
     def forward(self, bert_batch):
         """SentBERTWrapper.sent_reps_bert without its squeeze: [B, 768] on the GPU"""
@@ -106,14 +108,15 @@ class IctEncTrain(_ClsTrainModule):
     the two towers never share masks."""
     towers = ('sent_encoder', 'context_encoder')
 
-    def __init__(self, sent_bert, context_bert, dropout=False, seed=None, hip_embeddings=False, check_ids=True, matmul='fp32', attention='gemm'):
+    def __init__(self, sent_bert, context_bert, dropout=False, seed=None, hip_embeddings=False, check_ids=True, matmul='fp32', attention='gemm',
+                 packed=False):
         super().__init__()
         self.bert_encoding_dim = 768
         seed = (torch.initial_seed() if seed is None else int(seed)) % 2 ** 64
-        embed = dict(hip_embeddings=hip_embeddings, check_ids=check_ids, matmul=matmul, attention=attention)
+        embed = dict(hip_embeddings=hip_embeddings, check_ids=check_ids, matmul=matmul, attention=attention, packed=packed)
         self.sent_encoder = HipBertTrainEncoder(sent_bert, dropout=dropout, seed=seed, **embed)
         self.context_encoder = HipBertTrainEncoder(context_bert, dropout=dropout, seed=(seed + 1) % 2 ** 64, **embed)
-        self.matmul, self.attention = self.sent_encoder.matmul, self.sent_encoder.attention
+        self.matmul, self.attention, self.packed = self.sent_encoder.matmul, self.sent_encoder.attention, self.sent_encoder.packed
 
     def forward(self, bert_batch):
         """the sentence tower's reps [B, 768]: what the evaluation encodes with"""

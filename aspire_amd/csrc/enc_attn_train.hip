@@ -38,6 +38,16 @@
 // Dropout (dropout_rng.h): site 1 + 3 l on the logical index ((b H + h) L + i) L + j.  Where the lane is a query its four consecutive
 // keys share one Philox block when L % 4 == 0 (one draw per four elements); otherwise, and wherever the lane is a key, every element
 // is keyed on its own index.  DROP = false instantiations contain no generator.
+//
+// Packed rows (the padding-free mode; the PackedDocs instantiations of the four kernels, the _packed launchers and debug entries): the
+// row tensors hold the valid tokens alone, document b's at rows doc_start[b] .. doc_start[b + 1] - 1.  A workgroup's (document, head,
+// block) comes from the grid as above, sized by the LONGEST document; it reads its document's start and length and leaves at once
+// when its block starts at or beyond the length -- uniform per workgroup, before the first barrier.  Every key of a document is real,
+// so the only bias is -inf on tile padding beyond the length and no mask is read; statistics are [H, rows, 2] and D [H, rows], by
+// packed row.  Dropout keys are the PADDED call's: the positions i, j of ((b H + h) Lpad + i) Lpad + j come from row_src (the keys'
+// through LDS, the queries' of the key-block kernel as whole 64-bit keys through LDS), so a packed step draws the padded step's masks;
+// one draw per four keys only when every document is a prefix and Lpad % 4 == 0.  The padded instantiations are compiled from the
+// same text with every packed branch an `if constexpr`: same instruction counts, registers and LDS as before the second layout.
 #include <math.h>
 
 #include "enc_host.h"
@@ -128,6 +138,20 @@ __device__ __forceinline__ void keep_scale4(const DropSite& d, uint64_t e0, bool
     }
 }
 
+// the same over packed rows: keys key0 .. key0 + 3 of the tile at k0 sit at positions kpos[key0 ..] of the padded document.  quad (every
+// document a prefix, Lpad % 4 == 0): their positions are k0 + key0 .. + 3 and start a Philox block; otherwise every element is keyed on
+// its own index.  The mask bits are the same either way.
+__device__ __forceinline__ void keep_scale4_at(const DropSite& d, uint64_t e_row, int k0, const int* kpos, int key0, bool quad, float (&f)[4]) {
+    if (quad) {
+        const Philox4 r = drop_block(d, (e_row + (uint64_t)(k0 + key0)) >> 2);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) f[i] = r.w[i] >= d.thr ? d.scale : 0.f;
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) f[i] = drop_keep(d, e_row + (uint64_t)kpos[key0 + i]) ? d.scale : 0.f;
+    }
+}
+
 // (document, head, block) of a workgroup
 __device__ __forceinline__ void block_ids(int blocks, int H, int& blk, int& h, int& b) {
     blk = blockIdx.x % blocks;
@@ -135,30 +159,82 @@ __device__ __forceinline__ void block_ids(int blocks, int H, int& blk, int& h, i
     b = blockIdx.x / (blocks * H);
 }
 
-template <bool DROP>
-__global__ void __launch_bounds__(256) flash_train_fwd_kernel(const float* __restrict__ qkv, const int64_t* __restrict__ mask,
+// Where a document's rows lie.  PaddedDocs: document b's L rows at b L of [B L, .] tensors, statistics [B, H, L], the caller's mask.
+// PackedDocs (enc_types.h): its len = doc_start[b + 1] - doc_start[b] rows at doc_start[b] of [rows, .] tensors, statistics [H, rows],
+// no mask (every key is real); L is then the longest document, which sizes the grid alone.  The padded instantiations are the code
+// they were before there was a second layout: every packed branch is an `if constexpr`.
+struct PaddedDocs {
+    const int64_t* mask;
+};
+template <class Docs>
+constexpr bool kPackedDocs = false;
+template <>
+constexpr bool kPackedDocs<PackedDocs> = true;
+
+struct DocRows {
+    int len;          // rows of the document
+    size_t row0;      // its first row in qkv / ctx / dctx / dqkv
+    size_t stat0;     // the index of that row's statistics (and D) for head h
+    int pos0;         // packed: b Lpad, what row_src counts a position from
+};
+__device__ __forceinline__ DocRows doc_rows(const PaddedDocs&, int b, int h, int L, int H) {
+    return DocRows{L, (size_t)b * L, ((size_t)b * H + h) * L, 0};
+}
+// (clamped, so that no content of doc_start takes a row index outside [0, rows] or a length beyond L)
+__device__ __forceinline__ DocRows doc_rows(const PackedDocs& d, int b, int h, int L, int) {
+    const int start = min(max(d.doc_start[b], 0), d.rows), end = min(max(d.doc_start[b + 1], start), d.rows);
+    return DocRows{min(end - start, L), (size_t)start, (size_t)h * d.rows + start, b * d.Lpad};
+}
+// the dropout key of element (query at position pi, key 0) of (document b, head h) in the PADDED tensor [B, H, Lpad, Lpad]
+__device__ __forceinline__ uint64_t packed_e_row(const PackedDocs& d, int b, int h, int H, int pi) {
+    return ((uint64_t)(b * H + h) * d.Lpad + (uint64_t)pi) * d.Lpad;
+}
+
+template <bool DROP, class Docs>
+__global__ void __launch_bounds__(256) flash_train_fwd_kernel(const float* __restrict__ qkv, const Docs docs,
                                                               float* __restrict__ ctx, float* __restrict__ stats, int L, int H, DropSite ds) {
+    constexpr bool PACKED = kPackedDocs<Docs>;
     __shared__ __attribute__((aligned(16))) TrainTile Ks, Vt;          // K [key][dim], V [dim][key]
     __shared__ float kbias[64];
+    __shared__ int kpos[PACKED ? 64 : 1];                              // packed: the keys' positions in their padded document
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 31, lk = lane >> 5;
     int qb, h, b;
     block_ids((L + 127) / 128, H, qb, h, b);
+    const DocRows doc = doc_rows(docs, b, h, L, H);
+    if constexpr (PACKED) {
+        if (qb * 128 >= doc.len) return;                               // uniform per workgroup, before the first barrier
+        L = doc.len;
+    }
     const size_t ld = 3 * kD;
-    const float* base = qkv + (size_t)b * L * ld + h * 64;
+    const float* base = qkv + doc.row0 * ld + h * 64;
     const int q_row = qb * 128 + wave * 32 + lr;                      // this lane's query
     const bool q_ok = q_row < L;
     bf16x8_t qf[4];
     row_frags(base + (size_t)min(q_row, L - 1) * ld, lk, qf);
     f32x16 o[2] = {zero16(), zero16()};
     float m_run = -INFINITY, l_run = 0.f;                              // l_run: this half-wave's share of the sum
-    const uint64_t e_row = ((uint64_t)(b * H + h) * L + (uint64_t)min(q_row, L - 1)) * L;
-    const bool aligned = (L & 3) == 0;
+    uint64_t e_row;
+    bool aligned;
+    if constexpr (PACKED) {
+        e_row = packed_e_row(docs, b, h, H, docs.row_src[doc.row0 + min(q_row, L - 1)] - doc.pos0);
+        aligned = docs.quad != 0;
+    } else {
+        e_row = ((uint64_t)(b * H + h) * L + (uint64_t)min(q_row, L - 1)) * L;
+        aligned = (L & 3) == 0;
+    }
 
     for (int k0 = 0; k0 < L; k0 += 64) {
         __syncthreads();                                               // previous tile fully consumed
         stage_rows(Ks, base + kD, ld, k0, L, tid);
         stage_cols(Vt, base + 2 * kD, ld, k0, L, tid);
-        if (tid < 64) kbias[tid] = train_key_bias(mask + (size_t)b * L, k0 + tid, L);
+        if constexpr (PACKED) {
+            if (tid < 64) {
+                kbias[tid] = k0 + tid >= L ? -INFINITY : 0.f;
+                kpos[tid] = docs.row_src[doc.row0 + min(k0 + tid, L - 1)] - doc.pos0;
+            }
+        } else {
+            if (tid < 64) kbias[tid] = train_key_bias(docs.mask + (size_t)b * L, k0 + tid, L);
+        }
         __syncthreads();
         f32x16 sacc[2] = {zero16(), zero16()};
 #pragma unroll
@@ -202,7 +278,10 @@ __global__ void __launch_bounds__(256) flash_train_fwd_kernel(const float* __res
 #pragma unroll
                     for (int q4 = 0; q4 < 2; ++q4) {
                         float f[4];
-                        keep_scale4(ds, e_row + (uint64_t)(k0 + 32 * rb + 16 * g2 + 8 * q4 + 4 * lk), aligned, f);
+                        if constexpr (PACKED)
+                            keep_scale4_at(ds, e_row, k0, kpos, 32 * rb + 16 * g2 + 8 * q4 + 4 * lk, aligned, f);
+                        else
+                            keep_scale4(ds, e_row + (uint64_t)(k0 + 32 * rb + 16 * g2 + 8 * q4 + 4 * lk), aligned, f);
 #pragma unroll
                         for (int i = 0; i < 4; ++i) pv[4 * q4 + i] *= f[i];
                     }
@@ -216,18 +295,19 @@ __global__ void __launch_bounds__(256) flash_train_fwd_kernel(const float* __res
     const float l_tot = l_run + lane_xor<32>(l_run);
     const float inv = 1.0f / l_tot;
     if (q_ok) {
-        float* op = ctx + ((size_t)b * L + q_row) * kD + h * 64;
+        float* op = ctx + (doc.row0 + q_row) * kD + h * 64;
 #pragma unroll
         for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
             for (int g4 = 0; g4 < 4; ++g4)
                 *reinterpret_cast<float4*>(op + 32 * mb + 8 * g4 + 4 * lk) =
                     make_float4(o[mb][4 * g4 + 0] * inv, o[mb][4 * g4 + 1] * inv, o[mb][4 * g4 + 2] * inv, o[mb][4 * g4 + 3] * inv);
-        if (lk == 0) *reinterpret_cast<float2*>(stats + 2 * (((size_t)b * H + h) * L + q_row)) = make_float2(m_run, l_tot);
+        if (lk == 0) *reinterpret_cast<float2*>(stats + 2 * (doc.stat0 + q_row)) = make_float2(m_run, l_tot);
     }
 }
 
-// 16 lanes per (token row, head)
+// 16 lanes per (token row, head).  PACKED: D [H, L] with L the packed rows, the row tensors' rows as they are
+template <bool PACKED>
 __global__ void __launch_bounds__(256) flash_train_d_kernel(const float* __restrict__ dctx, const float* __restrict__ ctx, float* __restrict__ D,
                                                             int64_t items, int L, int H) {
     const int64_t item = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
@@ -247,30 +327,48 @@ __global__ void __launch_bounds__(256) flash_train_d_kernel(const float* __restr
     s += __shfl_xor(s, 4, 16);
     s += __shfl_xor(s, 2, 16);
     s += __shfl_xor(s, 1, 16);
-    if (l16 == 0 && item < items) D[((row / L) * H + h) * L + row % L] = s;
+    if constexpr (PACKED) {
+        if (l16 == 0 && item < items) D[(int64_t)h * L + row] = s;
+    } else {
+        if (l16 == 0 && item < items) D[((row / L) * H + h) * L + row % L] = s;
+    }
 }
 
-template <bool DROP>
-__global__ void __launch_bounds__(256) flash_train_dq_kernel(const float* __restrict__ qkv, const int64_t* __restrict__ mask,
+template <bool DROP, class Docs>
+__global__ void __launch_bounds__(256) flash_train_dq_kernel(const float* __restrict__ qkv, const Docs docs,
                                                              const float* __restrict__ stats, const float* __restrict__ Dv,
                                                              const float* __restrict__ dctx, float* __restrict__ dqkv, int L, int H, DropSite ds) {
+    constexpr bool PACKED = kPackedDocs<Docs>;
     __shared__ __attribute__((aligned(16))) TrainTile Ks, Vs, Kt;      // K [key][dim], V [key][dim], K [dim][key]
     __shared__ float kbias[64];
+    __shared__ int kpos[PACKED ? 64 : 1];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 31, lk = lane >> 5;
     int qb, h, b;
     block_ids((L + 127) / 128, H, qb, h, b);
+    const DocRows doc = doc_rows(docs, b, h, L, H);
+    if constexpr (PACKED) {
+        if (qb * 128 >= doc.len) return;
+        L = doc.len;
+    }
     const size_t ld = 3 * kD;
-    const float* base = qkv + (size_t)b * L * ld + h * 64;
+    const float* base = qkv + doc.row0 * ld + h * 64;
     const int q_row = qb * 128 + wave * 32 + lr;                      // this lane's query
     const bool q_ok = q_row < L;
     const int q_at = min(q_row, L - 1);
     bf16x8_t qf[4], gf[4];
     row_frags(base + (size_t)q_at * ld, lk, qf);
-    row_frags(dctx + ((size_t)b * L + q_at) * kD + h * 64, lk, gf);
-    const size_t s_at = ((size_t)b * H + h) * L + q_at;
+    row_frags(dctx + (doc.row0 + q_at) * kD + h * 64, lk, gf);
+    const size_t s_at = doc.stat0 + q_at;
     const float m = stats[2 * s_at], linv = 1.0f / stats[2 * s_at + 1], Dq = Dv[s_at];
-    const uint64_t e_row = (uint64_t)s_at * L;
-    const bool aligned = (L & 3) == 0;
+    uint64_t e_row;
+    bool aligned;
+    if constexpr (PACKED) {
+        e_row = packed_e_row(docs, b, h, H, docs.row_src[doc.row0 + q_at] - doc.pos0);
+        aligned = docs.quad != 0;
+    } else {
+        e_row = (uint64_t)s_at * L;
+        aligned = (L & 3) == 0;
+    }
     f32x16 dq[2] = {zero16(), zero16()};
 
     for (int k0 = 0; k0 < L; k0 += 64) {
@@ -278,7 +376,14 @@ __global__ void __launch_bounds__(256) flash_train_dq_kernel(const float* __rest
         stage_rows(Ks, base + kD, ld, k0, L, tid);
         stage_rows(Vs, base + 2 * kD, ld, k0, L, tid);
         stage_cols(Kt, base + kD, ld, k0, L, tid);
-        if (tid < 64) kbias[tid] = train_key_bias(mask + (size_t)b * L, k0 + tid, L);
+        if constexpr (PACKED) {
+            if (tid < 64) {
+                kbias[tid] = k0 + tid >= L ? -INFINITY : 0.f;
+                kpos[tid] = docs.row_src[doc.row0 + min(k0 + tid, L - 1)] - doc.pos0;
+            }
+        } else {
+            if (tid < 64) kbias[tid] = train_key_bias(docs.mask + (size_t)b * L, k0 + tid, L);
+        }
         __syncthreads();
         f32x16 s[2] = {zero16(), zero16()}, dp[2] = {zero16(), zero16()};
 #pragma unroll
@@ -297,7 +402,12 @@ __global__ void __launch_bounds__(256) flash_train_dq_kernel(const float* __rest
                 for (int q4 = 0; q4 < 2; ++q4) {
                     const int key0 = 32 * rb + 16 * g2 + 8 * q4 + 4 * lk;
                     float f[4] = {1.f, 1.f, 1.f, 1.f};
-                    if constexpr (DROP) keep_scale4(ds, e_row + (uint64_t)(k0 + key0), aligned, f);
+                    if constexpr (DROP) {
+                        if constexpr (PACKED)
+                            keep_scale4_at(ds, e_row, k0, kpos, key0, aligned, f);
+                        else
+                            keep_scale4(ds, e_row + (uint64_t)(k0 + key0), aligned, f);
+                    }
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         const int r = 8 * g2 + 4 * q4 + i;
@@ -313,7 +423,7 @@ __global__ void __launch_bounds__(256) flash_train_dq_kernel(const float* __rest
             }
     }
     if (q_ok) {
-        float* op = dqkv + ((size_t)b * L + q_row) * ld + h * 64;
+        float* op = dqkv + (doc.row0 + q_row) * ld + h * 64;
 #pragma unroll
         for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
@@ -323,26 +433,40 @@ __global__ void __launch_bounds__(256) flash_train_dq_kernel(const float* __rest
     }
 }
 
-template <bool DROP>
-__global__ void __launch_bounds__(256) flash_train_dkv_kernel(const float* __restrict__ qkv, const int64_t* __restrict__ mask,
+template <bool DROP, class Docs>
+__global__ void __launch_bounds__(256) flash_train_dkv_kernel(const float* __restrict__ qkv, const Docs docs,
                                                               const float* __restrict__ stats, const float* __restrict__ Dv,
                                                               const float* __restrict__ dctx, float* __restrict__ dqkv, int L, int H, DropSite ds) {
+    constexpr bool PACKED = kPackedDocs<Docs>;
     __shared__ __attribute__((aligned(16))) TrainTile Qs, Gs, Qt, Gt;  // Q, dctx [query][dim]; Q, dctx [dim][query]
     __shared__ float st_m[64], st_linv[64], st_d[64];
+    __shared__ unsigned long long st_e[PACKED && DROP ? 64 : 1];      // packed: the queries' dropout keys at key position 0
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 31, lk = lane >> 5;
     int kb, h, b;
     block_ids((L + 127) / 128, H, kb, h, b);
+    const DocRows doc = doc_rows(docs, b, h, L, H);
+    if constexpr (PACKED) {
+        if (kb * 128 >= doc.len) return;
+        L = doc.len;
+    }
     const size_t ld = 3 * kD;
-    const float* base = qkv + (size_t)b * L * ld + h * 64;
-    const float* gbase = dctx + (size_t)b * L * kD + h * 64;
+    const float* base = qkv + doc.row0 * ld + h * 64;
+    const float* gbase = dctx + doc.row0 * kD + h * 64;
     const int k_row = kb * 128 + wave * 32 + lr;                      // this lane's key
     const bool k_ok = k_row < L;
     const int k_at = min(k_row, L - 1);
     bf16x8_t kf[4], vf[4];
     row_frags(base + kD + (size_t)k_at * ld, lk, kf);
     row_frags(base + 2 * kD + (size_t)k_at * ld, lk, vf);
-    const float kbias = train_key_bias(mask + (size_t)b * L, k_row, L);
-    const size_t s_doc = ((size_t)b * H + h) * L;
+    float kbias;
+    [[maybe_unused]] uint64_t k_pos = 0;                               // packed: this lane's key's position in its padded document
+    if constexpr (PACKED) {
+        kbias = k_row >= L ? -INFINITY : 0.f;
+        if constexpr (DROP) k_pos = (uint64_t)(docs.row_src[doc.row0 + k_at] - doc.pos0);
+    } else {
+        kbias = train_key_bias(docs.mask + (size_t)b * L, k_row, L);
+    }
+    const size_t s_doc = doc.stat0;
     f32x16 dv[2] = {zero16(), zero16()}, dk[2] = {zero16(), zero16()};
 
     for (int q0 = 0; q0 < L; q0 += 64) {
@@ -357,6 +481,8 @@ __global__ void __launch_bounds__(256) flash_train_dkv_kernel(const float* __res
             st_m[tid] = ok ? stats[2 * at] : 0.f;
             st_linv[tid] = ok ? 1.0f / stats[2 * at + 1] : 0.f;
             st_d[tid] = ok ? Dv[at] : 0.f;
+            if constexpr (PACKED && DROP)
+                st_e[tid] = packed_e_row(docs, b, h, H, docs.row_src[doc.row0 + min(q0 + tid, L - 1)] - doc.pos0);
         }
         __syncthreads();
         f32x16 s[2] = {zero16(), zero16()}, dp[2] = {zero16(), zero16()};
@@ -378,7 +504,12 @@ __global__ void __launch_bounds__(256) flash_train_dkv_kernel(const float* __res
                     const bool ok = k_ok && q0 + qi < L;
                     const float p = __builtin_amdgcn_exp2f(fmaf(s[rb][r], kTScaleLog2, kbias) - st_m[qi]) * st_linv[qi];
                     float f = 1.f;
-                    if constexpr (DROP) f = drop_keep(ds, (uint64_t)(s_doc + min(q0 + qi, L - 1)) * L + (uint64_t)k_at) ? ds.scale : 0.f;
+                    if constexpr (DROP) {
+                        if constexpr (PACKED)
+                            f = drop_keep(ds, st_e[qi] + k_pos) ? ds.scale : 0.f;
+                        else
+                            f = drop_keep(ds, (uint64_t)(s_doc + min(q0 + qi, L - 1)) * L + (uint64_t)k_at) ? ds.scale : 0.f;
+                    }
                     const float g = DROP ? dp[rb][r] * f : dp[rb][r];
                     pd[e] = ok ? (DROP ? p * f : p) : 0.f;
                     dsv[e] = ok ? p * (g - st_d[qi]) : 0.f;
@@ -392,7 +523,7 @@ __global__ void __launch_bounds__(256) flash_train_dkv_kernel(const float* __res
             }
     }
     if (k_ok) {
-        float* op = dqkv + ((size_t)b * L + k_row) * ld + kD + h * 64;
+        float* op = dqkv + (doc.row0 + k_row) * ld + kD + h * 64;
 #pragma unroll
         for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
@@ -421,10 +552,60 @@ int launch_flash_attn_train(const float* qkv, const int64_t* mask, float* ctx, f
     if (int rc = check_flash_shape(B, L, H)) return rc;
     if (B == 0) return ASPIRE_OK;
     const dim3 grid((unsigned)(B * H) * (unsigned)((L + 127) / 128));
+    const PaddedDocs docs{mask};
     if (drop)
-        hipLaunchKernelGGL(flash_train_fwd_kernel<true>, grid, dim3(256), 0, st, qkv, mask, ctx, stats, L, H, *drop);
+        hipLaunchKernelGGL((flash_train_fwd_kernel<true, PaddedDocs>), grid, dim3(256), 0, st, qkv, docs, ctx, stats, L, H, *drop);
     else
-        hipLaunchKernelGGL(flash_train_fwd_kernel<false>, grid, dim3(256), 0, st, qkv, mask, ctx, stats, L, H, DropSite{});
+        hipLaunchKernelGGL((flash_train_fwd_kernel<false, PaddedDocs>), grid, dim3(256), 0, st, qkv, docs, ctx, stats, L, H, DropSite{});
+    ASPIRE_LAUNCH_OK();
+    return ASPIRE_OK;
+}
+
+namespace {
+// the packed calls' shape: the grid is sized by the longest document, the row tensors by the packed rows
+int check_flash_packed(int64_t B, const PackedDocs& d, int max_len, int H) {
+    ASPIRE_REQUIRE(d.doc_start && d.row_src, ASPIRE_ERR_INVALID_ARG, "null pointer (doc_start / row_src)");
+    ASPIRE_REQUIRE(d.rows > 0 && max_len > 0 && max_len <= d.Lpad && max_len <= d.rows, ASPIRE_ERR_INVALID_ARG,
+                   "packing: %d rows, longest document %d of %d padded tokens", d.rows, max_len, d.Lpad);
+    if (int rc = check_flash_shape(B, d.Lpad, H)) return rc;
+    ASPIRE_REQUIRE((double)d.rows * 3 * kD < 2147483648.0, ASPIRE_ERR_UNSUPPORTED, "%d packed rows in one call: beyond the grid (split the batch)",
+                   d.rows);
+    return ASPIRE_OK;
+}
+}  // namespace
+
+int launch_flash_attn_train_packed(const float* qkv, const PackedDocs& docs, int max_len, float* ctx, float* stats, int64_t B, int H,
+                                   const DropSite* drop, hipStream_t st) {
+    if (B == 0 || docs.rows == 0) return ASPIRE_OK;
+    if (int rc = check_flash_packed(B, docs, max_len, H)) return rc;
+    const dim3 grid((unsigned)(B * H) * (unsigned)((max_len + 127) / 128));
+    if (drop)
+        hipLaunchKernelGGL((flash_train_fwd_kernel<true, PackedDocs>), grid, dim3(256), 0, st, qkv, docs, ctx, stats, max_len, H, *drop);
+    else
+        hipLaunchKernelGGL((flash_train_fwd_kernel<false, PackedDocs>), grid, dim3(256), 0, st, qkv, docs, ctx, stats, max_len, H, DropSite{});
+    ASPIRE_LAUNCH_OK();
+    return ASPIRE_OK;
+}
+
+int launch_flash_attn_train_backward_packed(const float* qkv, const PackedDocs& docs, int max_len, const float* ctx, const float* stats,
+                                            const float* dctx, float* D, float* dqkv, int64_t B, int H, const DropSite* drop, hipStream_t st) {
+    if (B == 0 || docs.rows == 0) return ASPIRE_OK;
+    if (int rc = check_flash_packed(B, docs, max_len, H)) return rc;
+    const int64_t items = (int64_t)docs.rows * H;
+    hipLaunchKernelGGL(flash_train_d_kernel<true>, dim3((unsigned)((items + 15) / 16)), dim3(256), 0, st, dctx, ctx, D, items, docs.rows, H);
+    ASPIRE_LAUNCH_OK();
+    const dim3 grid((unsigned)(B * H) * (unsigned)((max_len + 127) / 128));
+    if (drop) {
+        hipLaunchKernelGGL((flash_train_dkv_kernel<true, PackedDocs>), grid, dim3(256), 0, st, qkv, docs, stats, D, dctx, dqkv, max_len, H, *drop);
+        ASPIRE_LAUNCH_OK();
+        hipLaunchKernelGGL((flash_train_dq_kernel<true, PackedDocs>), grid, dim3(256), 0, st, qkv, docs, stats, D, dctx, dqkv, max_len, H, *drop);
+    } else {
+        hipLaunchKernelGGL((flash_train_dkv_kernel<false, PackedDocs>), grid, dim3(256), 0, st, qkv, docs, stats, D, dctx, dqkv, max_len, H,
+                           DropSite{});
+        ASPIRE_LAUNCH_OK();
+        hipLaunchKernelGGL((flash_train_dq_kernel<false, PackedDocs>), grid, dim3(256), 0, st, qkv, docs, stats, D, dctx, dqkv, max_len, H,
+                           DropSite{});
+    }
     ASPIRE_LAUNCH_OK();
     return ASPIRE_OK;
 }
@@ -434,17 +615,18 @@ int launch_flash_attn_train_backward(const float* qkv, const int64_t* mask, cons
     if (int rc = check_flash_shape(B, L, H)) return rc;
     if (B == 0) return ASPIRE_OK;
     const int64_t items = B * L * H;
-    hipLaunchKernelGGL(flash_train_d_kernel, dim3((unsigned)((items + 15) / 16)), dim3(256), 0, st, dctx, ctx, D, items, L, H);
+    hipLaunchKernelGGL(flash_train_d_kernel<false>, dim3((unsigned)((items + 15) / 16)), dim3(256), 0, st, dctx, ctx, D, items, L, H);
     ASPIRE_LAUNCH_OK();
     const dim3 grid((unsigned)(B * H) * (unsigned)((L + 127) / 128));
+    const PaddedDocs docs{mask};
     if (drop) {
-        hipLaunchKernelGGL(flash_train_dkv_kernel<true>, grid, dim3(256), 0, st, qkv, mask, stats, D, dctx, dqkv, L, H, *drop);
+        hipLaunchKernelGGL((flash_train_dkv_kernel<true, PaddedDocs>), grid, dim3(256), 0, st, qkv, docs, stats, D, dctx, dqkv, L, H, *drop);
         ASPIRE_LAUNCH_OK();
-        hipLaunchKernelGGL(flash_train_dq_kernel<true>, grid, dim3(256), 0, st, qkv, mask, stats, D, dctx, dqkv, L, H, *drop);
+        hipLaunchKernelGGL((flash_train_dq_kernel<true, PaddedDocs>), grid, dim3(256), 0, st, qkv, docs, stats, D, dctx, dqkv, L, H, *drop);
     } else {
-        hipLaunchKernelGGL(flash_train_dkv_kernel<false>, grid, dim3(256), 0, st, qkv, mask, stats, D, dctx, dqkv, L, H, DropSite{});
+        hipLaunchKernelGGL((flash_train_dkv_kernel<false, PaddedDocs>), grid, dim3(256), 0, st, qkv, docs, stats, D, dctx, dqkv, L, H, DropSite{});
         ASPIRE_LAUNCH_OK();
-        hipLaunchKernelGGL(flash_train_dq_kernel<false>, grid, dim3(256), 0, st, qkv, mask, stats, D, dctx, dqkv, L, H, DropSite{});
+        hipLaunchKernelGGL((flash_train_dq_kernel<false, PaddedDocs>), grid, dim3(256), 0, st, qkv, docs, stats, D, dctx, dqkv, L, H, DropSite{});
     }
     ASPIRE_LAUNCH_OK();
     return ASPIRE_OK;
@@ -488,4 +670,31 @@ extern "C" int aspire_debug_flash_attn_train_backward_f32(const float* qkv, cons
     if (int rc = debug_site(dropout, layer, &site, &on)) return rc;
     if (int rc = check_flash_shape(B, L, 12)) return rc;
     return launch_flash_attn_train_backward(qkv, mask, ctx, stats, dctx, D, dqkv, B, (int)L, 12, on ? &site : nullptr, (hipStream_t)stream);
+}
+
+extern "C" int aspire_debug_flash_attn_train_packed_f32(const float* qkv, const aspire_bert_packing* packing, int64_t B, int64_t L,
+                                                        const aspire_bert_dropout* dropout, float* ctx, float* stats, void* stream) {
+    ASPIRE_REQUIRE(qkv && ctx && stats, ASPIRE_ERR_INVALID_ARG, "null pointer");
+    DropSite site{};
+    bool on;
+    if (int rc = debug_site(dropout, 0, &site, &on)) return rc;
+    PackedDocs docs{};
+    if (int rc = read_packing(packing, B, L, &docs)) return rc;
+    if (int rc = check_flash_shape(B, L, 12)) return rc;
+    return launch_flash_attn_train_packed(qkv, docs, (int)packing->max_len, ctx, stats, B, 12, on ? &site : nullptr, (hipStream_t)stream);
+}
+
+extern "C" int aspire_debug_flash_attn_train_packed_backward_f32(const float* qkv, const aspire_bert_packing* packing, const float* ctx,
+                                                                 const float* stats, const float* dctx, int64_t B, int64_t L,
+                                                                 const aspire_bert_dropout* dropout, int layer, float* D, float* dqkv,
+                                                                 void* stream) {
+    ASPIRE_REQUIRE(qkv && ctx && stats && dctx && D && dqkv, ASPIRE_ERR_INVALID_ARG, "null pointer");
+    DropSite site{};
+    bool on;
+    if (int rc = debug_site(dropout, layer, &site, &on)) return rc;
+    PackedDocs docs{};
+    if (int rc = read_packing(packing, B, L, &docs)) return rc;
+    if (int rc = check_flash_shape(B, L, 12)) return rc;
+    return launch_flash_attn_train_backward_packed(qkv, docs, (int)packing->max_len, ctx, stats, dctx, D, dqkv, B, 12, on ? &site : nullptr,
+                                                   (hipStream_t)stream);
 }

@@ -41,19 +41,28 @@ constexpr int kXentTile = 16;               // rows of s in a row block
 constexpr int kXentThreads = 512;           // eight waves, one per 16-column tile of B <= 128
 constexpr int kSStride = kXentMaxRows + 4;  // LDS row stride of a row block of s (kXStride's padding)
 
-__device__ __forceinline__ const float* cls_row(const ClsStates& s, int l, int64_t b, int64_t L) {
+// the first packed row of document b (clamped into the packed rows: the lists are the caller's device memory)
+__device__ __forceinline__ int64_t first_packed_row(const ClsRows& p, int64_t b) { return min(max(p.doc_start[b], 0), p.rows - 1); }
+
+// packed (p.doc_start not NULL): the tape's states are [rows, 768] and the CLS row is the document's first packed row; the top state is
+// the padded hidden_out, where that row is row_src[first packed row]
+__device__ __forceinline__ const float* cls_row(const ClsStates& s, int l, int64_t b, int64_t L, const ClsRows& p) {
     const float* base = l < s.n_layers ? reinterpret_cast<const float*>(s.x0 + (size_t)l * s.layer_stride) : s.top;
+    if (p.doc_start) {
+        const int64_t m = first_packed_row(p, b);
+        return base + (size_t)(l < s.n_layers ? m : min(max(p.row_src[m], 0), p.padded_rows - 1)) * kD;
+    }
     return base + (size_t)b * L * kD;
 }
 
 __global__ void __launch_bounds__(64 * kTapDocs) cls_mix_tap_kernel(ClsStates s, int64_t B, int64_t L, const float* __restrict__ mix,
-                                                                    float* __restrict__ cls_out, float* __restrict__ layer_cls) {
+                                                                    float* __restrict__ cls_out, float* __restrict__ layer_cls, ClsRows p) {
     const int lane = threadIdx.x & 63;
     const int64_t b = (int64_t)blockIdx.x * kTapDocs + (threadIdx.x >> 6);
     if (b >= B) return;
     Row acc = splat(0.f);
     for (int l = (mix || layer_cls) ? 0 : s.n_layers; l <= s.n_layers; ++l) {
-        const Row v = load_row(cls_row(s, l, b, L), lane);
+        const Row v = load_row(cls_row(s, l, b, L, p), lane);
         if (layer_cls) store_row(layer_cls + ((size_t)l * B + b) * kD, lane, v);
         if (mix) {
             const Row t = scaled(mix[l], v);
@@ -66,11 +75,12 @@ __global__ void __launch_bounds__(64 * kTapDocs) cls_mix_tap_kernel(ClsStates s,
 }
 
 __global__ void __launch_bounds__(64 * kTapDocs) cls_inject_kernel(float* __restrict__ grad, int64_t B, int64_t L,
-                                                                   const float* __restrict__ grad_cls, const float* __restrict__ mix, int l) {
+                                                                   const float* __restrict__ grad_cls, const float* __restrict__ mix, int l,
+                                                                   ClsRows p) {
     const int lane = threadIdx.x & 63;
     const int64_t b = (int64_t)blockIdx.x * kTapDocs + (threadIdx.x >> 6);
     if (b >= B) return;
-    float* row = grad + (size_t)b * L * kD;
+    float* row = grad + (size_t)(p.doc_start ? first_packed_row(p, b) : b * L) * kD;     // (packed: a [rows, 768] gradient)
     Row d = load_row(row, lane);
     add_scaled(d, mix ? mix[l] : 1.0f, load_row(grad_cls + (size_t)b * kD, lane));
     store_row(row, lane, d);
@@ -221,16 +231,17 @@ __global__ void __launch_bounds__(kXentThreads) inbatch_xent_bwd_kernel(const fl
 
 }  // namespace
 
-int launch_cls_mix_tap(const ClsStates& s, int64_t B, int64_t L, const float* mix, float* cls_out, float* layer_cls, hipStream_t st) {
+int launch_cls_mix_tap(const ClsStates& s, int64_t B, int64_t L, const float* mix, float* cls_out, float* layer_cls, hipStream_t st,
+                       const ClsRows* packed) {
     hipLaunchKernelGGL(cls_mix_tap_kernel, dim3((unsigned)((B + kTapDocs - 1) / kTapDocs)), dim3(64 * kTapDocs), 0, st, s, B, L, mix, cls_out,
-                       layer_cls);
+                       layer_cls, packed ? *packed : ClsRows{});
     ASPIRE_LAUNCH_OK();
     return ASPIRE_OK;
 }
 
-int launch_cls_inject(float* grad, int64_t B, int64_t L, const float* grad_cls, const float* mix, int l, hipStream_t st) {
+int launch_cls_inject(float* grad, int64_t B, int64_t L, const float* grad_cls, const float* mix, int l, hipStream_t st, const ClsRows* packed) {
     hipLaunchKernelGGL(cls_inject_kernel, dim3((unsigned)((B + kTapDocs - 1) / kTapDocs)), dim3(64 * kTapDocs), 0, st, grad, B, L, grad_cls, mix,
-                       l);
+                       l, packed ? *packed : ClsRows{});
     ASPIRE_LAUNCH_OK();
     return ASPIRE_OK;
 }

@@ -8,7 +8,8 @@
 //                           owns elements 4 i .. 4 i + 3 = Philox block i, one 16-byte load per operand and one store.  The hidden
 //                           sites both ways (forward: z in place + the residual; backward: dz = keep . scale . ds, and at site 0 the
 //                           two branches' sum), and the probabilities when L % 4 == 0 (then Lp == L: the tape's rows ARE the logical
-//                           tensor).  out may be a.
+//                           tensor).  out may be a.  With a row map (the padding-free mode's packed rows of 768) thread i's block is
+//                           the one its elements have in the padded tensor: row_map[row] x 192 + its index in the row.
 //   dropout_ragged_kernel   the probabilities when L % 4 != 0: rows of L logical elements in a row stride of Lp.  A thread owns four
 //                           padded columns (16-byte aligned in memory); their logical indices row L + j .. + 3 straddle two Philox
 //                           blocks unless they happen to start one, so it draws the second block only then.  Pad columns [L, Lp) are
@@ -22,16 +23,24 @@ namespace {
 
 __device__ __forceinline__ float drop1(float v, uint32_t word, const DropSite& d) { return word >= d.thr ? v * d.scale : 0.f; }
 
+// MAP (the padding-free mode: packed rows of 768 = 192 Philox blocks): thread i's block is the one its elements have in the PADDED
+// tensor, row_map[row] x 192 + the block's index in the row.  MAP = false is the kernel without a map.
+template <bool MAP>
 __global__ void __launch_bounds__(256) dropout_flat_kernel(const float* a, const float* __restrict__ a2, const float* __restrict__ res,
-                                                           float* out, int64_t n4, DropSite d) {
+                                                           float* out, int64_t n4, DropSite d, const int32_t* __restrict__ row_map) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n4) return;
+    uint64_t blk = (uint64_t)i;
+    if constexpr (MAP) {
+        const int64_t row = i / (kD / 4);
+        blk = (uint64_t)row_map[row] * (kD / 4) + (uint64_t)(i - row * (kD / 4));
+    }
     float4 v = reinterpret_cast<const float4*>(a)[i];
     if (a2) {
         const float4 w = reinterpret_cast<const float4*>(a2)[i];
         v = make_float4(v.x + w.x, v.y + w.y, v.z + w.z, v.w + w.w);
     }
-    const Philox4 r = drop_block(d, (uint64_t)i);
+    const Philox4 r = drop_block(d, blk);
     v = make_float4(drop1(v.x, r.w[0], d), drop1(v.y, r.w[1], d), drop1(v.z, r.w[2], d), drop1(v.w, r.w[3], d));
     if (res) {
         const float4 w = reinterpret_cast<const float4*>(res)[i];
@@ -73,9 +82,13 @@ __global__ void __launch_bounds__(256) dropout_mask_kernel(unsigned char* __rest
 
 }  // namespace
 
-int launch_dropout_flat(const float* a, const float* a2, const float* res, float* out, int64_t n, const DropSite& d, hipStream_t st) {
+int launch_dropout_flat(const float* a, const float* a2, const float* res, float* out, int64_t n, const DropSite& d, hipStream_t st,
+                        const int32_t* row_map) {
     const int64_t n4 = n / 4;     // (n = rows x 768, or B H L L with L % 4 == 0)
-    hipLaunchKernelGGL(dropout_flat_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, a, a2, res, out, n4, d);
+    if (row_map)
+        hipLaunchKernelGGL(dropout_flat_kernel<true>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, a, a2, res, out, n4, d, row_map);
+    else
+        hipLaunchKernelGGL(dropout_flat_kernel<false>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, a, a2, res, out, n4, d, row_map);
     ASPIRE_LAUNCH_OK();
     return ASPIRE_OK;
 }

@@ -158,14 +158,15 @@ struct TailSlots {
 // be ctx (the out-projection that reads ctx has finished before LN1 writes h: inference runs so).
 // `matmul` (ASPIRE_MATMUL_*, here and in attention_gemm): the mode of the products alone; every other launch is the same.
 // With `drop` (training, p_hidden > 0; drop[0]: the out-projection's site, drop[1]: FFN2's) the two GEMMs run with their bias and
-// WITHOUT the residual, and a pass of its own forms s = dropout(z) + residual in the same slot.
+// WITHOUT the residual, and a pass of its own forms s = dropout(z) + residual in the same slot.  row_map (the padding-free mode, whose
+// rows are the valid tokens alone): the padded row of each row, which keys its masks.
 int layer_tail(const aspire_bert_weights* w, const aspire_bert_layer& ly, const float* ctx, const float* x, const TailSlots& t, float* out,
-               int64_t rows, hipStream_t st, const DropSite* drop = nullptr, int matmul = ASPIRE_MATMUL_FP32) {
+               int64_t rows, hipStream_t st, const DropSite* drop = nullptr, int matmul = ASPIRE_MATMUL_FP32, const int32_t* row_map = nullptr) {
     const int ffn = w->ffn_dim;
     // 5. attention output projection + residual, LayerNorm
     if (int rc = launch_product(matmul, linear(ctx, ly.w_o, t.s1, ly.b_o, drop ? nullptr : x, rows, kD, kD), 1, kGemmNT, st)) return rc;
     if (drop)
-        if (int rc = launch_dropout_flat(t.s1, nullptr, x, t.s1, rows * kD, drop[0], st)) return rc;
+        if (int rc = launch_dropout_flat(t.s1, nullptr, x, t.s1, rows * kD, drop[0], st, row_map)) return rc;
     if (int rc = launch_layernorm(t.s1, ly.ln1_g, ly.ln1_b, w->ln_eps, t.h, rows, nullptr, st)) return rc;
     // 6. FFN: GELU(h . W1^T + b1) . W2^T + b2 + h, LayerNorm
     if (t.u) {
@@ -176,7 +177,7 @@ int layer_tail(const aspire_bert_weights* w, const aspire_bert_layer& ly, const 
     }
     if (int rc = launch_product(matmul, linear(t.act, ly.w_ffn2, t.s2, ly.b_ffn2, drop ? nullptr : t.h, rows, kD, ffn), 1, kGemmNT, st)) return rc;
     if (drop)
-        if (int rc = launch_dropout_flat(t.s2, nullptr, t.h, t.s2, rows * kD, drop[1], st)) return rc;
+        if (int rc = launch_dropout_flat(t.s2, nullptr, t.h, t.s2, rows * kD, drop[1], st, row_map)) return rc;
     return launch_layernorm(t.s2, ly.ln2_g, ly.ln2_b, w->ln_eps, out, rows, nullptr, st);
 }
 
@@ -188,6 +189,22 @@ int check_bert_shape(const aspire_bert_weights* w, int64_t B, int64_t L) {
     ASPIRE_REQUIRE(B >= 0 && L > 0 && L <= 512, ASPIRE_ERR_INVALID_ARG, "sequence length %lld outside (0, 512] (or a negative batch size)",
                    (long long)L);
     ASPIRE_REQUIRE(w->n_layers >= 0 && (w->n_layers == 0 || w->layers), ASPIRE_ERR_INVALID_ARG, "bad layer table");
+    return ASPIRE_OK;
+}
+
+// The caller's packing (include/aspire_hip.h: aspire_bert_packing) of a [B, L] batch, checked on the host before anything is read
+// through it, as what the kernels take.  The lists themselves are device memory: the kernels clamp what they read from them.
+int read_packing(const aspire_bert_packing* p, int64_t B, int64_t L, PackedDocs* out) {
+    ASPIRE_REQUIRE(p, ASPIRE_ERR_INVALID_ARG, "null pointer (packing)");
+    ASPIRE_REQUIRE(p->doc_start && (p->row_src || p->rows == 0) && (p->row_dst || B == 0), ASPIRE_ERR_INVALID_ARG,
+                   "null pointer (packing: doc_start / row_src / row_dst)");
+    ASPIRE_REQUIRE(B >= 0 && L > 0 && (double)B * (double)L < 2147483648.0, ASPIRE_ERR_UNSUPPORTED,
+                   "%lld x %lld padded token rows: the row lists are 32-bit (split the batch)", (long long)B, (long long)L);
+    ASPIRE_REQUIRE(p->rows >= 0 && p->rows <= B * L, ASPIRE_ERR_INVALID_ARG, "packing: %lld rows of a batch of %lld x %lld", (long long)p->rows,
+                   (long long)B, (long long)L);
+    ASPIRE_REQUIRE(p->max_len >= 0 && p->max_len <= L && p->max_len <= p->rows && (p->max_len > 0) == (p->rows > 0), ASPIRE_ERR_INVALID_ARG,
+                   "packing: longest document %d with %lld rows of %lld-token documents", (int)p->max_len, (long long)p->rows, (long long)L);
+    *out = PackedDocs{p->doc_start, p->row_src, (int)p->rows, (int)L, (p->prefix != 0 && L % 4 == 0) ? 1 : 0};
     return ASPIRE_OK;
 }
 

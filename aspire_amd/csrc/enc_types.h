@@ -108,6 +108,27 @@ int launch_flash_attn_train(const float* qkv, const int64_t* mask, float* ctx, f
                             hipStream_t st);
 int launch_flash_attn_train_backward(const float* qkv, const int64_t* mask, const float* ctx, const float* stats, const float* dctx, float* D,
                                      float* dqkv, int64_t B, int L, int H, const DropSite* drop, hipStream_t st);
+// The same kernels over PACKED rows (ASPIRE padding-free mode): the row tensors hold the `rows` valid tokens alone, document b's at
+// rows doc_start[b] .. doc_start[b + 1] - 1 in position order; qkv / dqkv [rows, 2304], ctx / dctx [rows, 768], stats [H, rows, 2],
+// D [H, rows].  row_src[m] = b Lpad + (the token's position in its padded document): what the dropout keys are made of, so that the
+// masks are the padded call's.  quad: every document is a prefix and Lpad % 4 == 0 (one draw per four keys where the lane is a query).
+// No mask is read: every key of a document is real.  max_len: the longest document (the grid's blocks); 0 launches nothing.
+struct PackedDocs {
+    const int32_t* doc_start;   // [B + 1]
+    const int32_t* row_src;     // [rows]
+    int rows, Lpad, quad;
+};
+int launch_flash_attn_train_packed(const float* qkv, const PackedDocs& docs, int max_len, float* ctx, float* stats, int64_t B, int H,
+                                   const DropSite* drop, hipStream_t st);
+int launch_flash_attn_train_backward_packed(const float* qkv, const PackedDocs& docs, int max_len, const float* ctx, const float* stats,
+                                            const float* dctx, float* D, float* dqkv, int64_t B, int H, const DropSite* drop, hipStream_t st);
+
+// enc_pack.hip: the gather and scatter between the padded [B L, 768] layout and the packed [rows, 768] one (one wave per row, 16-byte
+// accesses, every output row written once)
+//   pack_rows:    out[m, :] = src[row_src[m], :], m < rows
+//   unpack_rows:  out[p, :] = row_dst[p] >= 0 ? src[row_dst[p], :] : 0, p < padded_rows (no zero fill in front)
+int launch_pack_rows(const float* src, const int32_t* row_src, float* out, int64_t rows, int64_t padded_rows, hipStream_t st);
+int launch_unpack_rows(const float* src, const int32_t* row_dst, float* out, int64_t padded_rows, int64_t rows, hipStream_t st);
 
 // enc_rows.hip: one wave per row of 768 -- LayerNorm, embeddings + LayerNorm (pos_ids [rows] or NULL: the row of pos each token takes,
 // NULL = its index in the document), the CLS rows of a hidden state
@@ -137,10 +158,12 @@ int launch_colsum(const float* x, int64_t rows, int N, float* out, float* partia
 
 // enc_dropout.hip: the dropout passes of the encoder under training; d names the site and its mask (dropout_rng.h), which every pass
 // forms again from the element's logical index.  No atomics, every output element has one writer; out may be the first operand.
-//   dropout_flat:   out = keep . scale . (a (+ a2)) (+ res), n % 4 == 0 contiguous elements whose logical index is their offset
+//   dropout_flat:   out = keep . scale . (a (+ a2)) (+ res), n % 4 == 0 contiguous elements whose logical index is their offset; with
+//                   row_map (packed rows of 768: n = rows x 768) element (m, c) is keyed as row_map[m] x 768 + c instead
 //   dropout_probs:  out [rows][ld] = keep . scale . p [rows][ld] with logical index row L + j, j < L; zeros in [L, ld)
 //   dropout_mask:   keep[i] = 1 iff element first + i of the site is kept
-int launch_dropout_flat(const float* a, const float* a2, const float* res, float* out, int64_t n, const DropSite& d, hipStream_t st);
+int launch_dropout_flat(const float* a, const float* a2, const float* res, float* out, int64_t n, const DropSite& d, hipStream_t st,
+                        const int32_t* row_map = nullptr);
 int launch_dropout_probs(const float* p, float* out, int64_t rows, int L, int ld, const DropSite& d, hipStream_t st);
 int launch_dropout_mask(unsigned char* keep, uint64_t first, int64_t n, const DropSite& d, hipStream_t st);
 
@@ -162,8 +185,18 @@ struct ClsStates {
     const float* top;
     int n_layers;
 };
-int launch_cls_mix_tap(const ClsStates& s, int64_t B, int64_t L, const float* mix, float* cls_out, float* layer_cls, hipStream_t st);
-int launch_cls_inject(float* grad, int64_t B, int64_t L, const float* grad_cls, const float* mix, int l, hipStream_t st);
+//   ClsRows:         packed states (the padding-free mode): document b's CLS row is its first packed row doc_start[b] of the [rows, 768]
+//                    states on the tape; the top state stays padded ([B, L, 768], hidden_out), where that row is row_src[doc_start[b]].
+//                    NULL: the padded layout, row b L everywhere
+struct ClsRows {
+    const int32_t* doc_start;
+    const int32_t* row_src;
+    int rows, padded_rows;      // rows > 0; padded_rows = B L
+};
+int launch_cls_mix_tap(const ClsStates& s, int64_t B, int64_t L, const float* mix, float* cls_out, float* layer_cls, hipStream_t st,
+                       const ClsRows* packed = nullptr);
+int launch_cls_inject(float* grad, int64_t B, int64_t L, const float* grad_cls, const float* mix, int l, hipStream_t st,
+                      const ClsRows* packed = nullptr);
 int launch_cls_grad_mix(const float* grad_cls, const float* layer_cls, int64_t B, int n_states, float* grad_mix, hipStream_t st);
 int launch_inbatch_xent(const float* q, const float* c, int B, float* loss, float* row_lse, hipStream_t st);
 int launch_inbatch_xent_backward(const float* q, const float* c, int B, const float* grad_loss, float* grad_q, float* grad_c, hipStream_t st);

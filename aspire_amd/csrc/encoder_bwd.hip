@@ -49,6 +49,13 @@
 // slot): neither buffer has an L^2 term, so carve_tape and carve_train take the mode with the geometry and the _attn size queries
 // answer for it.  ASPIRE_ATTENTION_GEMM: everything above, unchanged.
 //
+// Packed rows (the _packed entry points; include/aspire_hip.h: aspire_bert_packing): with ASPIRE_MATMUL_BF16 and ASPIRE_ATTENTION_FLASH
+// the stack runs over the M = rows valid token rows alone.  Every row-wise launch above takes any M as it is; the entries gather
+// emb_sum / grad_hidden into packed rows and scatter hidden_out / grad_emb_sum back to [B, L, 768] with zeros on masked rows
+// (enc_pack.hip), the attention is the packed instantiation of the fused kernels, the hidden sites' dropout is keyed through row_src
+// (the padded call's masks) and the CLS taps read each document's first packed row.  The tape is the flash tape with M = rows, the
+// forward keeps its packed top state in the workspace's d1.
+//
 // This file is host only (the tape's and the workspace's carve, the two layer loops, the C entry points); the kernels: enc_bwd.hip (rows),
 // enc_gemm.hip (launch_gemm, launch_gemm_tn), enc_gemm_bf16.hip (launch_gemm_bf16), enc_gemm_bf16x3.hip (launch_gemm_bf16x3), enc_attn.hip (launch_softmax_mask), enc_attn_train.hip (the fused training attention), enc_rows.hip
 // (launch_layernorm).
@@ -65,6 +72,13 @@ struct Geometry {
     size_t probs;     // floats of one layer's P; ASPIRE_ATTENTION_FLASH: of its row statistics (m, l) [B, H, L, 2]
     size_t dprobs;    // floats of the workspace's dP / dS; ASPIRE_ATTENTION_FLASH: of D [B, H, L]
     int attention;
+    // the padding-free mode (the _packed entry points): M = the valid token rows, statistics [H, M, 2], D [H, M]
+    bool packed = false;
+    PackedDocs docs{};
+    const int32_t* row_dst = nullptr;
+    int max_len = 0;
+    const int32_t* row_map() const { return packed ? docs.row_src : nullptr; }       // what keys the hidden sites' dropout
+    ClsRows cls_rows() const { return ClsRows{docs.doc_start, docs.row_src, docs.rows, (int)(B * L)}; }
 };
 Geometry geometry(const aspire_bert_weights* w, int64_t B, int64_t L, int attention = ASPIRE_ATTENTION_GEMM) {
     Geometry g;
@@ -75,6 +89,15 @@ Geometry geometry(const aspire_bert_weights* w, int64_t B, int64_t L, int attent
     const bool flash = attention == ASPIRE_ATTENTION_FLASH;
     g.probs = flash ? (size_t)B * g.H * L * 2 : (size_t)B * g.H * L * g.Lp;
     g.dprobs = flash ? (size_t)B * g.H * L : g.probs;
+    return g;
+}
+// `rows` valid token rows of a [B, L] batch (docs may be all zero but for rows: the size queries)
+Geometry geometry_packed(const aspire_bert_weights* w, int64_t B, int64_t L, const PackedDocs& docs, const int32_t* row_dst, int max_len) {
+    Geometry g = geometry(w, B, L, ASPIRE_ATTENTION_FLASH);
+    g.M = docs.rows;
+    g.probs = (size_t)g.H * g.M * 2;
+    g.dprobs = (size_t)g.H * g.M;
+    g.packed = true; g.docs = docs; g.row_dst = row_dst; g.max_len = max_len;
     return g;
 }
 
@@ -223,14 +246,17 @@ int forward_layer(const aspire_bert_weights* w, const Geometry& q, int l, const 
     // 2-4. the three-kernel attention; the masked soft-max runs in place: the tape's P
     // (with dropout the tape keeps the undropped P; the dropped copy the P.V product reads goes to the workspace's dprobs, free here)
     // (ASPIRE_ATTENTION_FLASH: one fused launch; the tape's slot keeps the rows' (m, l) instead of P)
-    if (q.attention == ASPIRE_ATTENTION_FLASH) {
+    // (packed: the same kernels over the documents' own rows; no mask is read)
+    if (q.packed) {
+        if (int rc = launch_flash_attn_train_packed(t.qkv, q.docs, q.max_len, t.ctx, t.probs, q.B, q.H, dr.attn() ? &probs : nullptr, st)) return rc;
+    } else if (q.attention == ASPIRE_ATTENTION_FLASH) {
         if (int rc = launch_flash_attn_train(t.qkv, mask, t.ctx, t.probs, q.B, (int)q.L, q.H, dr.attn() ? &probs : nullptr, st)) return rc;
     } else if (int rc = attention_gemm(t.qkv, t.probs, t.ctx, mask, q.B, q.L, q.Lp, q.H, q.dh, nullptr, 0, st, dr.attn() ? &probs : nullptr,
                                        ws.dprobs, mm))
         return rc;
     // 5. s1 = ctx . Wo^T + bo + x; h = LN1(s1)
     // 6. u = h . W1^T + b1 (GELU epilogue off); a = GELU(u); s2 = a . W2^T + b2 + h; out = LN2(s2)
-    return layer_tail(w, ly, t.ctx, t.x, TailSlots{t.s1, t.h, t.u, act, t.s2}, out, q.M, st, dr.hidden() ? tail : nullptr, mm);
+    return layer_tail(w, ly, t.ctx, t.x, TailSlots{t.s1, t.h, t.u, act, t.s2}, out, q.M, st, dr.hidden() ? tail : nullptr, mm, q.row_map());
 }
 
 // the QKV projection's backward: ws.dqkv -> dbqkv, dWqkv and the gradient of the layer's input in ws.d2
@@ -257,7 +283,7 @@ int backward_layer(const aspire_bert_weights* w, const Geometry& q, int l, const
     // ds2 itself goes down the residual
     const float* dz2 = ws.d1;
     if (dr.hidden()) {
-        if (int rc = launch_dropout_flat(ws.d1, nullptr, nullptr, ws.d2, M * kD, dr.ffn2(l), st)) return rc;
+        if (int rc = launch_dropout_flat(ws.d1, nullptr, nullptr, ws.d2, M * kD, dr.ffn2(l), st, q.row_map())) return rc;
         dz2 = ws.d2;
     }
     if (int rc = launch_colsum(dz2, M, kD, gr.b_ffn2, ws.partial, st)) return rc;
@@ -275,7 +301,7 @@ int backward_layer(const aspire_bert_weights* w, const Geometry& q, int l, const
     // the residual branch's gradient for the layer below
     const float* dz1 = ws.d3;
     if (dr.hidden()) {
-        if (int rc = launch_dropout_flat(ws.d3, nullptr, nullptr, ws.d1, M * kD, dr.proj(l), st)) return rc;
+        if (int rc = launch_dropout_flat(ws.d3, nullptr, nullptr, ws.d1, M * kD, dr.proj(l), st, q.row_map())) return rc;
         dz1 = ws.d1;
     }
     if (int rc = launch_colsum(dz1, M, kD, gr.b_o, ws.partial, st)) return rc;
@@ -285,8 +311,12 @@ int backward_layer(const aspire_bert_weights* w, const Geometry& q, int l, const
     if (q.attention == ASPIRE_ATTENTION_FLASH) {
         // D = rowsum(dctx . ctx) into the workspace, then the key-block and the query-block kernels: every element of dqkv once
         const DropSite site = dr.probs(l);
-        if (int rc = launch_flash_attn_train_backward(t.qkv, mask, t.ctx, t.probs, ws.d2, ws.dprobs, ws.dqkv, B, (int)L, H,
-                                                      dr.attn() ? &site : nullptr, st))
+        if (q.packed) {
+            if (int rc = launch_flash_attn_train_backward_packed(t.qkv, q.docs, q.max_len, t.ctx, t.probs, ws.d2, ws.dprobs, ws.dqkv, B, H,
+                                                                 dr.attn() ? &site : nullptr, st))
+                return rc;
+        } else if (int rc = launch_flash_attn_train_backward(t.qkv, mask, t.ctx, t.probs, ws.d2, ws.dprobs, ws.dqkv, B, (int)L, H,
+                                                             dr.attn() ? &site : nullptr, st))
             return rc;
         return backward_qkv(w, q, l, t, gr, ws, mm, st);
     }
@@ -323,15 +353,23 @@ struct ClsSource {
 int backward_stack(const aspire_bert_weights* w, const Geometry& q, const Tape& t, const TrainWorkspace& tw, const int64_t* mask,
                    const float* grad_hidden, const ClsSource* cls, float* grad_emb_sum, const aspire_bert_grads* grads, const Dropout& dr, int mm, hipStream_t st) {
     const float *dy = grad_hidden, *dy_res = nullptr;
+    const ClsRows cls_rows = q.cls_rows();
+    const ClsRows* packed_rows = q.packed ? &cls_rows : nullptr;
+    if (q.packed && grad_hidden) {
+        // the caller's gradient is padded: its valid rows, gathered into d2 (where the CLS source forms the top gradient as well); its
+        // masked rows are never read
+        if (int rc = launch_pack_rows(grad_hidden, q.docs.row_src, tw.d2, q.M, q.B * q.L, st)) return rc;
+        dy = tw.d2;
+    }
     if (cls) {
         // the top gradient = grad_hidden (or zeros) + the CLS rows, formed in d2: backward_layer writes d2 only after LN2's backward has
         // read dy, and the layers below hand their dy over in d2 as well
         const size_t bytes = (size_t)q.M * kD * sizeof(float);
-        if (grad_hidden)
+        if (grad_hidden && !q.packed)
             ASPIRE_HIP_OK(hipMemcpyAsync(tw.d2, grad_hidden, bytes, hipMemcpyDeviceToDevice, st));
-        else
+        else if (!grad_hidden)
             ASPIRE_HIP_OK(hipMemsetAsync(tw.d2, 0, bytes, st));
-        if (int rc = launch_cls_inject(tw.d2, q.B, q.L, cls->grad_cls, cls->mix, q.n_layers, st)) return rc;
+        if (int rc = launch_cls_inject(tw.d2, q.B, q.L, cls->grad_cls, cls->mix, q.n_layers, st, packed_rows)) return rc;
         dy = tw.d2;
         if (cls->grad_mix)
             if (int rc = launch_cls_grad_mix(cls->grad_cls, cls->layer_cls, q.B, q.n_layers + 1, cls->grad_mix, st)) return rc;
@@ -343,14 +381,21 @@ int backward_stack(const aspire_bert_weights* w, const Geometry& q, const Tape& 
         // hidden state l is this layer's input: its CLS rows' share of the mix lands on the residual branch's gradient, before the
         // LayerNorm backward below (or, for state 0, the backward of site 0's dropout) adds the two branches
         if (cls && cls->mix)
-            if (int rc = launch_cls_inject(tw.d3, q.B, q.L, cls->grad_cls, cls->mix, l, st)) return rc;
+            if (int rc = launch_cls_inject(tw.d3, q.B, q.L, cls->grad_cls, cls->mix, l, st, packed_rows)) return rc;
     }
     // the embedding LayerNorm (grad_emb_sum NULL: its input gradient goes to scratch, the parameter gradients are still wanted)
     float* scratch = tw.d1;
     if (dr.hidden()) {
         // its output's gradient is keep . scale . (dy + dy_res), into d1; d2 is dead after that pass and takes the scratch's place
-        if (int rc = launch_dropout_flat(dy, dy_res, nullptr, tw.d1, q.M * kD, dr.emb(), st)) return rc;
+        if (int rc = launch_dropout_flat(dy, dy_res, nullptr, tw.d1, q.M * kD, dr.emb(), st, q.row_map())) return rc;
         dy = tw.d1; dy_res = nullptr; scratch = tw.d2;
+    }
+    if (q.packed) {
+        // the packed rows' gradient into the scratch, then every padded row once: its packed row, or zeros
+        if (int rc = launch_layernorm_backward(t.emb(), w->emb_ln_g, w->ln_eps, dy, dy_res, scratch, grads->emb_ln_g, grads->emb_ln_b, q.M,
+                                               tw.partial, st))
+            return rc;
+        return grad_emb_sum ? launch_unpack_rows(scratch, q.row_dst, grad_emb_sum, q.B * q.L, q.M, st) : ASPIRE_OK;
     }
     return launch_layernorm_backward(t.emb(), w->emb_ln_g, w->ln_eps, dy, dy_res, grad_emb_sum ? grad_emb_sum : scratch, grads->emb_ln_g,
                                      grads->emb_ln_b, q.M, tw.partial, st);
@@ -532,6 +577,146 @@ extern "C" int aspire_bert_layers_backward_attn_f32(const aspire_bert_weights* w
     const ClsSource cls{grad_cls, mix, layer_cls, grad_mix};
     return backward_entry(w, attn_mask, B, L, grad_hidden, grad_cls ? &cls : nullptr, tape, tape_bytes, grad_emb_sum, grads, ws, ws_bytes, dropout,
                           matmul, attention, stream);
+}
+
+// ---- the padding-free mode: the stack over the valid token rows alone (include/aspire_hip.h: aspire_bert_packing) ----------------------
+namespace {
+// what the packed calls check before anything is read: the modes, the weights and the shape, the packing; -> the call's geometry
+int packed_geometry(const aspire_bert_weights* w, const aspire_bert_packing* packing, int64_t B, int64_t L, int matmul, int attention,
+                    Geometry* out) {
+    if (int rc = check_matmul(matmul)) return rc;
+    if (int rc = check_attention(attention, matmul)) return rc;
+    ASPIRE_REQUIRE(attention == ASPIRE_ATTENTION_FLASH, ASPIRE_ERR_UNSUPPORTED,
+                   "packed rows are built for ASPIRE_ATTENTION_FLASH alone (attention mode %d): the three-kernel attention has per-document "
+                   "[L, L] matrices",
+                   attention);
+    if (int rc = check_bert_shape(w, B, L)) return rc;
+    ASPIRE_REQUIRE(w->emb_ln_g && w->emb_ln_b, ASPIRE_ERR_INVALID_ARG, "null pointer (emb_ln_g / emb_ln_b)");
+    if (int rc = check_layer_pointers(w->layers, w->n_layers, "weights")) return rc;
+    PackedDocs docs{};
+    if (int rc = read_packing(packing, B, L, &docs)) return rc;
+    const int wide = w->ffn_dim > 3 * kD ? w->ffn_dim : 3 * kD;
+    ASPIRE_REQUIRE((double)docs.rows * wide < 2147483648.0, ASPIRE_ERR_UNSUPPORTED,
+                   "%d token rows in one call: row x column indices are 32-bit (split the batch)", docs.rows);
+    *out = geometry_packed(w, B, L, docs, packing->row_dst, (int)packing->max_len);
+    return ASPIRE_OK;
+}
+int check_packed_buffers(const Geometry& q, const void* tape, size_t tape_bytes, const void* ws, size_t ws_bytes) {
+    const size_t need_tape = carve_tape(nullptr, q).total, need_ws = carve_train(nullptr, q).total;
+    ASPIRE_REQUIRE(tape && tape_bytes >= need_tape, ASPIRE_ERR_INVALID_ARG, "tape too small: need %zu bytes (aspire_bert_tape_bytes_packed)",
+                   need_tape);
+    ASPIRE_REQUIRE(ws && ws_bytes >= need_ws, ASPIRE_ERR_INVALID_ARG,
+                   "workspace too small: need %zu bytes (aspire_bert_train_workspace_bytes_packed)", need_ws);
+    return ASPIRE_OK;
+}
+Geometry size_geometry(const aspire_bert_weights* w, int64_t B, int64_t L, int64_t rows) {
+    PackedDocs docs{};
+    docs.rows = (int)rows;
+    return geometry_packed(w, B, L, docs, nullptr, 0);
+}
+bool packed_size_args(const aspire_bert_weights* w, int64_t B, int64_t L, int64_t rows) {
+    return w && B > 0 && L > 0 && rows > 0 && (double)B * (double)L < 2147483648.0 && rows <= B * L;
+}
+// no valid row: every gradient is an exact zero (memory sets, no launch)
+int zero_gradients(const aspire_bert_weights* w, const aspire_bert_grads* g, float* grad_emb_sum, float* grad_mix, int64_t B, int64_t L,
+                   hipStream_t st) {
+    const size_t f = sizeof(float), ffn = (size_t)w->ffn_dim;
+    ASPIRE_HIP_OK(hipMemsetAsync(g->emb_ln_g, 0, kD * f, st));
+    ASPIRE_HIP_OK(hipMemsetAsync(g->emb_ln_b, 0, kD * f, st));
+    for (int l = 0; l < w->n_layers; ++l) {
+        const aspire_bert_layer_grads& y = g->layers[l];
+        float* const ptr[12] = {y.w_qkv, y.b_qkv, y.w_o, y.b_o, y.ln1_g, y.ln1_b, y.w_ffn1, y.b_ffn1, y.w_ffn2, y.b_ffn2, y.ln2_g, y.ln2_b};
+        const size_t n[12] = {(size_t)3 * kD * kD, (size_t)3 * kD, (size_t)kD * kD, kD, kD, kD, ffn * kD, ffn, ffn * kD, kD, kD, kD};
+        for (int i = 0; i < 12; ++i) ASPIRE_HIP_OK(hipMemsetAsync(ptr[i], 0, n[i] * f, st));
+    }
+    if (grad_emb_sum) ASPIRE_HIP_OK(hipMemsetAsync(grad_emb_sum, 0, (size_t)B * L * kD * f, st));
+    if (grad_mix) ASPIRE_HIP_OK(hipMemsetAsync(grad_mix, 0, (size_t)(w->n_layers + 1) * f, st));
+    return ASPIRE_OK;
+}
+}  // namespace
+
+extern "C" size_t aspire_bert_tape_bytes_packed(const aspire_bert_weights* w, int64_t B, int64_t L, int64_t rows) {
+    if (!packed_size_args(w, B, L, rows)) return 0;
+    return carve_tape(nullptr, size_geometry(w, B, L, rows)).total;
+}
+
+extern "C" size_t aspire_bert_train_workspace_bytes_packed(const aspire_bert_weights* w, int64_t B, int64_t L, int64_t rows) {
+    if (!packed_size_args(w, B, L, rows)) return 0;
+    return carve_train(nullptr, size_geometry(w, B, L, rows)).total;
+}
+
+extern "C" int aspire_bert_layers_forward_train_packed_f32(const aspire_bert_weights* w, const float* emb_sum,
+                                                           const aspire_bert_packing* packing, int64_t B, int64_t L, float* hidden_out,
+                                                           void* tape, size_t tape_bytes, void* ws, size_t ws_bytes,
+                                                           const aspire_bert_dropout* dropout, int matmul, int attention, void* stream) {
+    ASPIRE_REQUIRE(w && emb_sum && packing && hidden_out, ASPIRE_ERR_INVALID_ARG, "null pointer");
+    Dropout dr;
+    if (int rc = read_dropout(dropout, &dr)) return rc;
+    Geometry q;
+    if (int rc = packed_geometry(w, packing, B, L, matmul, attention, &q)) return rc;
+    if (B == 0) return ASPIRE_OK;
+    hipStream_t st = (hipStream_t)stream;
+    if (q.M == 0) {       // no valid token: zeros, no launch
+        ASPIRE_HIP_OK(hipMemsetAsync(hidden_out, 0, (size_t)B * L * kD * sizeof(float), st));
+        return ASPIRE_OK;
+    }
+    if (int rc = check_packed_buffers(q, tape, tape_bytes, ws, ws_bytes)) return rc;
+    const Tape t = carve_tape(tape, q);
+    const TrainWorkspace tw = carve_train(ws, q);
+    if (int rc = launch_pack_rows(emb_sum, q.docs.row_src, t.emb(), q.M, B * L, st)) return rc;
+    const int n = q.n_layers;
+    float* top = tw.d1;                    // the packed top state: the forward uses act alone of the workspace
+    float* x0 = n == 0 ? top : t.layer(0).x;
+    if (int rc = launch_layernorm(t.emb(), w->emb_ln_g, w->emb_ln_b, w->ln_eps, x0, q.M, nullptr, st)) return rc;
+    if (dr.hidden())
+        if (int rc = launch_dropout_flat(x0, nullptr, nullptr, x0, q.M * kD, dr.emb(), st, q.row_map())) return rc;
+    for (int l = 0; l < n; ++l)
+        if (int rc = forward_layer(w, q, l, t.layer(l), nullptr, tw, l == n - 1 ? top : t.layer(l + 1).x, dr, matmul, st)) return rc;
+    return launch_unpack_rows(top, q.row_dst, hidden_out, B * L, q.M, st);
+}
+
+extern "C" int aspire_bert_layers_backward_packed_f32(const aspire_bert_weights* w, const aspire_bert_packing* packing, int64_t B, int64_t L,
+                                                      const float* grad_hidden, const float* grad_cls, const float* mix,
+                                                      const float* layer_cls, const void* tape, size_t tape_bytes, float* grad_emb_sum,
+                                                      const aspire_bert_grads* grads, float* grad_mix, void* ws, size_t ws_bytes,
+                                                      const aspire_bert_dropout* dropout, int matmul, int attention, void* stream) {
+    ASPIRE_REQUIRE(w && packing && grads, ASPIRE_ERR_INVALID_ARG, "null pointer");
+    ASPIRE_REQUIRE(grad_hidden || grad_cls, ASPIRE_ERR_INVALID_ARG, "null pointer (grad_hidden and grad_cls: no gradient source)");
+    ASPIRE_REQUIRE(!grad_mix || (layer_cls && mix && grad_cls), ASPIRE_ERR_INVALID_ARG,
+                   "grad_mix needs grad_cls, mix and layer_cls (null pointer)");
+    Dropout dr;
+    if (int rc = read_dropout(dropout, &dr)) return rc;
+    Geometry q;
+    if (int rc = packed_geometry(w, packing, B, L, matmul, attention, &q)) return rc;
+    ASPIRE_REQUIRE(grads->emb_ln_g && grads->emb_ln_b && (w->n_layers == 0 || grads->layers), ASPIRE_ERR_INVALID_ARG,
+                   "null pointer in the gradient table");
+    if (int rc = check_layer_pointers(grads->layers, w->n_layers, "gradients")) return rc;
+    if (B == 0) return ASPIRE_OK;
+    if (q.M == 0) return zero_gradients(w, grads, grad_emb_sum, grad_mix, B, L, (hipStream_t)stream);
+    if (int rc = check_packed_buffers(q, tape, tape_bytes, ws, ws_bytes)) return rc;
+    const ClsSource cls{grad_cls, mix, layer_cls, grad_mix};
+    return backward_stack(w, q, carve_tape(tape, q), carve_train(ws, q), nullptr, grad_hidden, grad_cls ? &cls : nullptr, grad_emb_sum, grads, dr,
+                          matmul, (hipStream_t)stream);
+}
+
+extern "C" int aspire_bert_cls_mix_train_packed_f32(const aspire_bert_weights* w, const aspire_bert_packing* packing, int64_t B, int64_t L,
+                                                    const void* tape, size_t tape_bytes, const float* hidden_out, const float* mix,
+                                                    float* cls_out, float* layer_cls, void* stream) {
+    ASPIRE_REQUIRE(w && packing && hidden_out && cls_out, ASPIRE_ERR_INVALID_ARG, "null pointer (w / packing / hidden_out / cls_out)");
+    ASPIRE_REQUIRE(!mix || layer_cls, ASPIRE_ERR_INVALID_ARG, "null pointer (layer_cls with a mix)");
+    if (int rc = check_bert_shape(w, B, L)) return rc;
+    PackedDocs docs{};
+    if (int rc = read_packing(packing, B, L, &docs)) return rc;
+    if (B == 0) return ASPIRE_OK;
+    // every document's CLS row is its first packed row: a document without rows has none (the caller checks mask[:, 0] on the host)
+    ASPIRE_REQUIRE(docs.rows >= B, ASPIRE_ERR_INVALID_ARG, "packing: %d rows for %lld documents -- a document without a CLS row", docs.rows,
+                   (long long)B);
+    const Geometry q = geometry_packed(w, B, L, docs, packing->row_dst, (int)packing->max_len);
+    const Tape t = carve_tape(tape, q);
+    ASPIRE_REQUIRE(tape && tape_bytes >= t.total, ASPIRE_ERR_INVALID_ARG, "tape too small: need %zu bytes (aspire_bert_tape_bytes_packed)", t.total);
+    const ClsStates s{t.base + t.emb_bytes, t.per_layer, hidden_out, q.n_layers};
+    const ClsRows rows = q.cls_rows();
+    return launch_cls_mix_tap(s, B, L, mix, cls_out, layer_cls, (hipStream_t)stream, &rows);
 }
 
 extern "C" int aspire_bert_layers_backward_cls_f32(const aspire_bert_weights* w, const int64_t* attn_mask, int64_t B, int64_t L,

@@ -60,6 +60,10 @@ implementation so that shapes propagate under FakeTensor / torch.compile tracing
     torch.ops.aspire.bert_layers_train_attn(..., matmul, attention) / bert_layers_backward_attn / bert_layers_train_cls_attn /
     bert_layers_backward_cls_attn        the _prec operators with the attention mode (0 the three-kernel form, 1 the fused training
                                          attention, with matmul 1 alone: HipBertTrainEncoder(matmul='bf16', attention='flash'))
+    torch.ops.aspire.bert_layers_train_packed(emb_sum, doc_start, row_src, row_dst, max_len, prefix, weights, n_heads, ln_eps, p_hidden,
+        p_attn, seed, step) / bert_layers_backward_packed / bert_layers_train_cls_packed / bert_layers_backward_cls_packed
+                                         the _attn operators of (matmul 1, attention 1) over the valid token rows alone, the row lists
+                                         of aspire_amd.packed_rows where the mask was: HipBertTrainEncoder(..., packed=True)
     torch.ops.aspire.inbatch_xent(q, c) -> (loss [1], row_lse [B])                                 sentsim_models.py:81-126
                                          (autograd registered: the gradient of loss with respect to q and c)
     torch.ops.aspire.inbatch_xent_backward(grad_loss, q, c, row_lse) -> (grad_q, grad_c)
@@ -1023,6 +1027,174 @@ def _bert_layers_train_cls_attn_grad(ctx, grad_cls, grad_layer_cls, grad_tape):
 bert_layers_train_cls_attn.register_autograd(_bert_layers_train_cls_attn_grad, setup_context=_bert_layers_train_cls_attn_setup)
 
 
+# ---- the padding-free mode (aspire_bert_layers_forward_train_packed_f32 / aspire_bert_layers_backward_packed_f32) --------------------------
+# The _attn operators of (matmul 1, attention 1) with the row lists of aspire_amd.packed_rows(mask) where the mask was: doc_start int32
+# [B + 1], row_src int32 [R], row_dst int32 [B L], max_len, prefix.  The layer stack, the tape (aspire_bert_tape_bytes_packed: sized by
+# R = row_src.shape[0], a shape, so the fake registrations know it) and the workspace hold the R valid token rows alone; emb_sum,
+# hidden and both [B, L, 768] gradients keep the padded layout, with exact zeros on masked rows.  R == 0: zeros, no launch.
+_PACKED_MODES = (1, _lib.ATTENTION_FLASH)       # ASPIRE_MATMUL_BF16, ASPIRE_ATTENTION_FLASH: the mode's only form
+
+
+def _packing(doc_start, row_src, row_dst, max_len, prefix):
+    """-> (struct aspire_bert_packing, the int32 tensors it points into: keep them alive), B, L"""
+    lists = [t.to(torch.int32).contiguous() for t in (doc_start, row_src, row_dst)]
+    b = lists[0].numel() - 1
+    assert b >= 0 and (lists[2].numel() % b == 0 if b else lists[2].numel() == 0), 'doc_start [B + 1], row_dst [B L]'
+    pk = _lib.BertPacking(lists[1].numel(), max_len, 1 if prefix else 0, *(ctypes.c_void_p(t.data_ptr()) for t in lists))
+    return pk, lists, b, (lists[2].numel() // b if b else 0)
+
+
+def _packed_scratch(query, bw, b, l, rows, device):
+    return torch.empty(max(query(ctypes.byref(bw), b, l, rows), 16), device=device, dtype=torch.uint8)
+
+
+def _packed_forward(emb_sum, doc_start, row_src, row_dst, max_len, prefix, weights, n_heads, ln_eps, drop):
+    bw = pack_layer_stack(weights, n_heads, ln_eps)
+    emb_sum = emb_sum.to(torch.float32).contiguous()
+    pk, lists, b, l = _packing(doc_start, row_src, row_dst, max_len, prefix)
+    assert emb_sum.shape[:2] == (b, l), 'emb_sum [B, L, 768] and the row lists disagree'
+    out = torch.empty_like(emb_sum)
+    tape = _packed_scratch(lib.aspire_bert_tape_bytes_packed, bw, b, l, pk.rows, emb_sum.device)
+    ws = _packed_scratch(lib.aspire_bert_train_workspace_bytes_packed, bw, b, l, pk.rows, emb_sum.device)
+    check(lib.aspire_bert_layers_forward_train_packed_f32(ctypes.byref(bw), ops._ptr(emb_sum), ctypes.byref(pk), b, l, ops._ptr(out), ops._ptr(tape),
+                                                          tape.numel(), ops._ptr(ws), ws.numel(),
+                                                          ctypes.byref(drop) if drop is not None else None, *_PACKED_MODES, ops._stream()))
+    return out, tape
+
+
+def _packed_backward(grad_hidden, grad_cls, layer_cls, tape, doc_start, row_src, row_dst, max_len, prefix, weights, mix, n_heads, ln_eps, drop):
+    bw = pack_layer_stack(weights, n_heads, ln_eps)
+    pk, lists, b, l = _packing(doc_start, row_src, row_dst, max_len, prefix)
+    src = grad_hidden if grad_hidden is not None else grad_cls
+    grads = [torch.empty_like(t, memory_format=torch.contiguous_format) for t in weights]
+    grad_emb = src.new_empty((b, l, src.shape[-1]), dtype=torch.float32)
+    with_mix = mix is not None
+    grad_mix = src.new_empty(mix.numel() if with_mix else 0, dtype=torch.float32)
+    if with_mix:
+        mix = mix.to(torch.float32).contiguous()
+    layers = fill_layers(_lib.BertLayerGrads, grads[2:])
+    bg = _lib.BertGrads(ctypes.c_void_p(grads[0].data_ptr()), ctypes.c_void_p(grads[1].data_ptr()), layers)
+    ws = _packed_scratch(lib.aspire_bert_train_workspace_bytes_packed, bw, b, l, pk.rows, src.device)
+    check(lib.aspire_bert_layers_backward_packed_f32(ctypes.byref(bw), ctypes.byref(pk), b, l, ops._ptr(grad_hidden), ops._ptr(grad_cls),
+                                                     ops._ptr(mix), ops._ptr(layer_cls.contiguous() if with_mix else None), ops._ptr(tape),
+                                                     tape.numel(), ops._ptr(grad_emb), ctypes.byref(bg),
+                                                     ops._ptr(grad_mix if with_mix else None), ops._ptr(ws), ws.numel(),
+                                                     ctypes.byref(drop) if drop is not None else None, *_PACKED_MODES, ops._stream()))
+    return grad_emb, grads, grad_mix
+
+
+def _fake_packed_tape(emb_sum, row_src, weights, n_heads, ln_eps):
+    n_layers = (len(weights) - 2) // 12
+    bw = _lib.BertWeights(None, None, None, None, None, None, n_layers, n_heads, emb_sum.shape[2],
+                          weights[2 + 6].shape[0] if n_layers else 4 * emb_sum.shape[2], 0, 0, 0, float(ln_eps), None)
+    return emb_sum.new_empty(max(lib.aspire_bert_tape_bytes_packed(ctypes.byref(bw), emb_sum.shape[0], emb_sum.shape[1], row_src.shape[0]), 16),
+                             dtype=torch.uint8)
+
+
+@torch.library.custom_op('aspire::bert_layers_train_packed', mutates_args=(), device_types='cuda')
+def bert_layers_train_packed(emb_sum: Tensor, doc_start: Tensor, row_src: Tensor, row_dst: Tensor, max_len: int, prefix: bool,
+                             weights: List[Tensor], n_heads: int, ln_eps: float, p_hidden: float, p_attn: float, seed: int,
+                             step: int) -> Tuple[Tensor, Tensor]:
+    return _packed_forward(emb_sum, doc_start, row_src, row_dst, max_len, prefix, weights, n_heads, ln_eps,
+                           _drop_or_none(p_hidden, p_attn, seed, step))
+
+
+@torch.library.custom_op('aspire::bert_layers_backward_packed', mutates_args=(), device_types='cuda')
+def bert_layers_backward_packed(grad_hidden: Tensor, tape: Tensor, doc_start: Tensor, row_src: Tensor, row_dst: Tensor, max_len: int,
+                                prefix: bool, weights: List[Tensor], n_heads: int, ln_eps: float, p_hidden: float, p_attn: float, seed: int,
+                                step: int) -> Tuple[Tensor, List[Tensor]]:
+    grad_hidden = grad_hidden.to(torch.float32).contiguous()
+    return _packed_backward(grad_hidden, None, None, tape, doc_start, row_src, row_dst, max_len, prefix, weights, None, n_heads, ln_eps,
+                            _drop_or_none(p_hidden, p_attn, seed, step))[:2]
+
+
+@bert_layers_train_packed.register_fake
+def _(emb_sum, doc_start, row_src, row_dst, max_len, prefix, weights, n_heads, ln_eps, p_hidden, p_attn, seed, step):
+    return emb_sum.new_empty(emb_sum.shape, dtype=torch.float32), _fake_packed_tape(emb_sum, row_src, weights, n_heads, ln_eps)
+
+
+@bert_layers_backward_packed.register_fake
+def _(grad_hidden, tape, doc_start, row_src, row_dst, max_len, prefix, weights, n_heads, ln_eps, p_hidden, p_attn, seed, step):
+    return grad_hidden.new_empty(grad_hidden.shape, dtype=torch.float32), [t.new_empty(t.shape) for t in weights]
+
+
+def _bert_layers_train_packed_setup(ctx, inputs, output):
+    emb_sum, doc_start, row_src, row_dst, ctx.max_len, ctx.prefix, weights, ctx.n_heads, ctx.ln_eps, *ctx.dropout = inputs
+    ctx.save_for_backward(output[1], doc_start, row_src, row_dst, *weights)
+
+
+def _bert_layers_train_packed_grad(ctx, grad_hidden, grad_tape):
+    tape, doc_start, row_src, row_dst, *weights = ctx.saved_tensors
+    grad_emb, grads = torch.ops.aspire.bert_layers_backward_packed(grad_hidden, tape, doc_start, row_src, row_dst, ctx.max_len, ctx.prefix,
+                                                                   weights, ctx.n_heads, ctx.ln_eps, *ctx.dropout)
+    return grad_emb, None, None, None, None, None, grads, None, None, None, None, None, None
+
+
+bert_layers_train_packed.register_autograd(_bert_layers_train_packed_grad, setup_context=_bert_layers_train_packed_setup)
+
+
+@torch.library.custom_op('aspire::bert_layers_train_cls_packed', mutates_args=(), device_types='cuda')
+def bert_layers_train_cls_packed(emb_sum: Tensor, doc_start: Tensor, row_src: Tensor, row_dst: Tensor, max_len: int, prefix: bool,
+                                 weights: List[Tensor], mix: Optional[Tensor], n_heads: int, ln_eps: float, p_hidden: float, p_attn: float,
+                                 seed: int, step: int) -> Tuple[Tensor, Tensor, Tensor]:
+    hidden, tape = _packed_forward(emb_sum, doc_start, row_src, row_dst, max_len, prefix, weights, n_heads, ln_eps,
+                                   _drop_or_none(p_hidden, p_attn, seed, step))
+    bw = pack_layer_stack(weights, n_heads, ln_eps)
+    pk, lists, b, l = _packing(doc_start, row_src, row_dst, max_len, prefix)
+    d = hidden.shape[2]
+    cls = hidden.new_empty(b, d)
+    layer_cls = hidden.new_empty(((len(weights) - 2) // 12 + 1, b, d) if mix is not None else (0,))
+    if mix is not None:
+        mix = mix.to(torch.float32).contiguous()
+    check(lib.aspire_bert_cls_mix_train_packed_f32(ctypes.byref(bw), ctypes.byref(pk), b, l, ops._ptr(tape), tape.numel(), ops._ptr(hidden),
+                                                   ops._ptr(mix), ops._ptr(cls), ops._ptr(layer_cls if mix is not None else None),
+                                                   ops._stream()))
+    return cls, layer_cls, tape
+
+
+@torch.library.custom_op('aspire::bert_layers_backward_cls_packed', mutates_args=(), device_types='cuda')
+def bert_layers_backward_cls_packed(grad_cls: Tensor, layer_cls: Tensor, tape: Tensor, doc_start: Tensor, row_src: Tensor, row_dst: Tensor,
+                                    max_len: int, prefix: bool, weights: List[Tensor], mix: Optional[Tensor], n_heads: int, ln_eps: float,
+                                    p_hidden: float, p_attn: float, seed: int, step: int) -> Tuple[Tensor, List[Tensor], Tensor]:
+    grad_cls = grad_cls.to(torch.float32).contiguous()
+    return _packed_backward(None, grad_cls, layer_cls, tape, doc_start, row_src, row_dst, max_len, prefix, weights, mix, n_heads, ln_eps,
+                            _drop_or_none(p_hidden, p_attn, seed, step))
+
+
+@bert_layers_train_cls_packed.register_fake
+def _(emb_sum, doc_start, row_src, row_dst, max_len, prefix, weights, mix, n_heads, ln_eps, p_hidden, p_attn, seed, step):
+    b, _, d = emb_sum.shape
+    return (emb_sum.new_empty((b, d), dtype=torch.float32),
+            emb_sum.new_empty(((len(weights) - 2) // 12 + 1, b, d) if mix is not None else (0,), dtype=torch.float32),
+            _fake_packed_tape(emb_sum, row_src, weights, n_heads, ln_eps))
+
+
+@bert_layers_backward_cls_packed.register_fake
+def _(grad_cls, layer_cls, tape, doc_start, row_src, row_dst, max_len, prefix, weights, mix, n_heads, ln_eps, p_hidden, p_attn, seed, step):
+    b = doc_start.shape[0] - 1
+    return (grad_cls.new_empty((b, row_dst.shape[0] // b, grad_cls.shape[1]), dtype=torch.float32), [t.new_empty(t.shape) for t in weights],
+            grad_cls.new_empty(mix.numel() if mix is not None else 0, dtype=torch.float32))
+
+
+def _bert_layers_train_cls_packed_setup(ctx, inputs, output):
+    emb_sum, doc_start, row_src, row_dst, ctx.max_len, ctx.prefix, weights, mix, ctx.n_heads, ctx.ln_eps, *ctx.dropout = inputs
+    ctx.with_mix = mix is not None
+    ctx.save_for_backward(output[1], output[2], doc_start, row_src, row_dst, *([mix] if ctx.with_mix else []), *weights)
+    ctx.mark_non_differentiable(output[1])
+
+
+def _bert_layers_train_cls_packed_grad(ctx, grad_cls, grad_layer_cls, grad_tape):
+    layer_cls, tape, doc_start, row_src, row_dst, *rest = ctx.saved_tensors
+    mix, weights = (rest[0], rest[1:]) if ctx.with_mix else (None, rest)
+    grad_emb, grads, grad_mix = torch.ops.aspire.bert_layers_backward_cls_packed(grad_cls, layer_cls, tape, doc_start, row_src, row_dst,
+                                                                                 ctx.max_len, ctx.prefix, weights, mix, ctx.n_heads, ctx.ln_eps,
+                                                                                 *ctx.dropout)
+    return grad_emb, None, None, None, None, None, grads, grad_mix if ctx.with_mix else None, None, None, None, None, None, None
+
+
+bert_layers_train_cls_packed.register_autograd(_bert_layers_train_cls_packed_grad, setup_context=_bert_layers_train_cls_packed_setup)
+
+
 # ---- the in-batch cross-entropy (aspire_inbatch_xent_f32 / aspire_inbatch_xent_backward_f32) -----------------------------------------------
 # ICTBERTWrapper.forward_rank's loss (sentsim_models.py:81-126) over two towers' CLS rows q, c [B, 768], B <= 128: loss [1] and the
 # rows' logsumexp [B], which the backward reads.
@@ -1140,4 +1312,5 @@ OPS = ('span_mean_pool', 'span_pool_ranges', 'bert_encoder_forward', 'bert_cls_f
        'bert_layers_train_dropout', 'bert_layers_backward_dropout', 'bert_dropout_mask', 'bert_layers_train_cls', 'bert_layers_backward_cls',
        'bert_layers_train_prec', 'bert_layers_backward_prec', 'bert_layers_train_cls_prec', 'bert_layers_backward_cls_prec',
        'bert_layers_train_attn', 'bert_layers_backward_attn', 'bert_layers_train_cls_attn', 'bert_layers_backward_cls_attn',
+       'bert_layers_train_packed', 'bert_layers_backward_packed', 'bert_layers_train_cls_packed', 'bert_layers_backward_cls_packed',
        'inbatch_xent', 'inbatch_xent_backward', 'bert_embed_sum', 'bert_embed_backward')

@@ -49,6 +49,27 @@ Its operands (Q, K, V, the probabilities, dctx, dS) are rounded to bf16 once eac
 ones ``attention='gemm'`` draws.  With ``matmul='fp32'`` or ``'bf16x3'`` it raises NotImplementedError (a fused attention at fp32
 accuracy does not exist).  The default ``attention='gemm'`` is the launches and bits described above.
 
+Padding-free batches are opt-in as well, with ``attention='flash'`` alone.  ``HipBertTrainEncoder(bert_model, matmul='bf16',
+attention='flash', packed=True)`` runs the layer stack, its tape and its workspace over the ``R = attention_mask.sum()`` valid token rows
+alone (torch.ops.aspire.bert_layers_train_packed / bert_layers_train_cls_packed over the row lists of ``aspire_amd.packed_rows``; the
+gather and scatter: aspire_amd/csrc/enc_pack.hip): rows in document order and, inside a document, in position order, so a mask with
+holes or left padding packs the same way as right padding.  What the mode returns:
+  * ``forward`` returns [B, L, 768] as before.  Valid rows are the mode's result; masked rows are EXACT ZEROS -- a deliberate departure,
+    HuggingFace computes something there (nothing downstream reads it: the rank loss, the span pool and the CLS read-out never touch a
+    pad row).  A document whose mask is all zero has no rows and its output rows are zeros; ``R == 0`` returns zeros and launches
+    nothing.
+  * The gradient with respect to the embedding sum is [B, L, 768] with exact zeros on masked rows (``hip_embeddings=True`` sees those
+    zeros); the incoming gradient of ``last_hidden_state`` is read on valid rows only.
+  * ``forward_cls`` takes each document's CLS row at its first packed row: it requires ``attention_mask[:, 0] == 1`` for every
+    document and raises ValueError on the host otherwise, before a launch.
+  * Dropout is keyed by the PADDED logical index, the one the padded modes use (row ``b L + l`` for the hidden sites,
+    ``((b H + h) L + i) L + j`` with ``i``, ``j`` the tokens' original positions for the probabilities): with the same ``(seed, step)`` a
+    packed step draws, at valid positions, the masks a padded step draws.  A run switches modes only through a fresh encoder;
+    RankTrainer's checkpoint records ``packed`` and refuses a mismatch (a checkpoint without the key means False).
+  * No atomics anywhere: every element of every output has one writer and every sum a fixed order -- the same bits on every run.
+With any other ``attention`` (so with ``matmul='fp32'`` or ``'bf16x3'`` too) it raises NotImplementedError before any launch.  The default
+``packed=False`` is the launches, bits, tape size and operators described above; ``eval()`` and ``torch.no_grad()`` forwards stay padded.
+
 Not supported: activation checkpointing around this module -- the recomputed forward would draw the next step's masks, not the first
 forward's.
 """
@@ -58,13 +79,15 @@ import torch
 
 from . import ops
 from .encoder import _LAYER_KEYS, require_bert_base
+from .packing import packed_rows
 
 
 class HipBertTrainEncoder(torch.nn.Module):
     MATMUL_MODES = {'fp32': 0, 'bf16': 1, 'bf16x3': 3}        # include/aspire_hip.h: ASPIRE_MATMUL_* (2 is not a mode)
     ATTENTION_MODES = {'gemm': 0, 'flash': 1}                 # include/aspire_hip.h: ASPIRE_ATTENTION_*
 
-    def __init__(self, bert_model, dropout=False, seed=None, hip_embeddings=False, check_ids=True, matmul='fp32', attention='gemm'):
+    def __init__(self, bert_model, dropout=False, seed=None, hip_embeddings=False, check_ids=True, matmul='fp32', attention='gemm',
+                 packed=False):
         super().__init__()
         if matmul not in self.MATMUL_MODES:
             raise ValueError(f"HipBertTrainEncoder: matmul={matmul!r}: 'fp32', 'bf16' or 'bf16x3'")
@@ -73,7 +96,10 @@ class HipBertTrainEncoder(torch.nn.Module):
         if attention == 'flash' and matmul != 'bf16':
             raise NotImplementedError(f"HipBertTrainEncoder: attention='flash' is built for matmul='bf16' alone (got matmul={matmul!r}): "
                                       'a fused attention at fp32 accuracy does not exist')
-        self.matmul, self.attention = matmul, attention
+        if packed and attention != 'flash':
+            raise NotImplementedError(f"HipBertTrainEncoder: packed=True is built for attention='flash' alone (got matmul={matmul!r}, "
+                                      f"attention={attention!r}): the three-kernel attention has per-document [L, L] matrices")
+        self.matmul, self.attention, self.packed = matmul, attention, bool(packed)
         dev = ops.require_gpu()
         self.hip_embeddings, self.check_ids = bool(hip_embeddings), bool(check_ids)
         cfg = bert_model.config
@@ -172,10 +198,20 @@ class HipBertTrainEncoder(torch.nn.Module):
         seq_len = tok.shape[1]
         if seq_len > cfg.max_position_embeddings:
             raise IndexError(f'{seq_len} tokens: beyond max_position_embeddings={cfg.max_position_embeddings}')
+        if self.packed:
+            # a document's CLS row is its first packed row: that is position 0 only where position 0 is a valid token
+            if msk.numel() and not bool((msk[:, 0] != 0).all()):
+                raise ValueError('HipBertTrainEncoder(packed=True).forward_cls: every document needs attention_mask[:, 0] == 1 -- the CLS '
+                                 'row is read at the document\'s first packed row')
+            rows = packed_rows(msk)
         emb_sum = self._emb_sum(tok, typ, seq_len)
         seed, step = self._seed, self._step
         if self.dropout:
             self._step = (step + 1) % 2 ** 32
+        if self.packed:
+            return torch.ops.aspire.bert_layers_train_cls_packed(emb_sum, rows.doc_start, rows.row_src, rows.row_dst, rows.max_len, rows.prefix,
+                                                                 self.layer_weights(), mix, cfg.num_attention_heads, cfg.layer_norm_eps,
+                                                                 self.p_hidden, self.p_attn, seed - 2 ** 64 if seed >= 2 ** 63 else seed, step)[0]
         args = (emb_sum, msk, self.layer_weights(), mix, cfg.num_attention_heads, cfg.layer_norm_eps, self.p_hidden, self.p_attn,
                 seed - 2 ** 64 if seed >= 2 ** 63 else seed, step)
         if self.attention != 'gemm':
@@ -212,6 +248,11 @@ class HipBertTrainEncoder(torch.nn.Module):
             seed, step = self._seed, self._step
             if self.dropout:
                 self._step = (step + 1) % 2 ** 32
+            if self.packed:
+                rows = packed_rows(msk)
+                return torch.ops.aspire.bert_layers_train_packed(emb_sum, rows.doc_start, rows.row_src, rows.row_dst, rows.max_len, rows.prefix,
+                                                                 self.layer_weights(), cfg.num_attention_heads, cfg.layer_norm_eps,
+                                                                 self.p_hidden, self.p_attn, seed - 2 ** 64 if seed >= 2 ** 63 else seed, step)[0]
             args = (emb_sum, msk, self.layer_weights(), cfg.num_attention_heads, cfg.layer_norm_eps, self.p_hidden, self.p_attn,
                     seed - 2 ** 64 if seed >= 2 ** 63 else seed, step, self.MATMUL_MODES[self.matmul])
             if self.attention != 'gemm':

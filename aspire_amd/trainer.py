@@ -215,6 +215,7 @@ class RankTrainer:
                  'dropout_state': tuple(self.encoder.dropout_state()) if hasattr(self.encoder, 'dropout_state') else None,
                  'matmul': getattr(self.encoder, 'matmul', 'fp32'),
                  'attention': getattr(self.encoder, 'attention', 'gemm'),
+                 'packed': bool(getattr(self.encoder, 'packed', False)),
                  'last_grad_norm': None if self.last_grad_norm is None else float(self.last_grad_norm),
                  'torch_rng_state': torch.get_rng_state()}
         torch.save(state, path)
@@ -230,6 +231,11 @@ class RankTrainer:
         saved, mine = state.get('attention', 'gemm'), getattr(self.encoder, 'attention', 'gemm')
         if saved != mine:
             raise ValueError(f"checkpoint written with attention={saved!r}, this encoder runs attention={mine!r}: resume with the mode the run "
+                             'was started in')
+        # ... and whether the stack ran over the valid token rows alone (a checkpoint from before the key: False)
+        saved, mine = bool(state.get('packed', False)), bool(getattr(self.encoder, 'packed', False))
+        if saved != mine:
+            raise ValueError(f"checkpoint written with packed={saved!r}, this encoder runs packed={mine!r}: resume with the mode the run "
                              'was started in')
         self.encoder.load_state_dict(state['encoder'])
         self.optimizer.load_state_dict(state['optimizer'])

@@ -511,6 +511,74 @@ int aspire_debug_flash_attn_train_backward_f32(const float* qkv, const int64_t* 
                                                float* D, float* dqkv, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * A1t without padding (opt-in, with ASPIRE_MATMUL_BF16 and ASPIRE_ATTENTION_FLASH only): the layer stack, its tape and its workspace hold
+ * the R = sum(attention mask) valid token rows alone, where the calls above run every launch over B L rows of a batch padded to its
+ * longest document -- what the reference's forward does (disent_models.py:178-205 and sentsim_models.py:62-78 call BertModel on the
+ * padded tokid_tt / attnmask_tt that batchers.py:249 / :627 build).  A pad row buys nothing: no read-out reads one, a masked key has
+ * probability exactly 0, so no parameter gradient depends on one.
+ *
+ * aspire_bert_packing describes the batch (aspire_amd.packed_rows builds it from the mask, with one host read of the totals): packed
+ * rows are in document order and, inside a document, in position order; a mask with holes or left padding packs the same way.
+ *   rows        R, 0 .. B L
+ *   max_len     the longest document's rows (0 iff rows == 0), at most L
+ *   prefix      nonzero iff every document's rows are its positions 0 .. len - 1 (right padding alone)
+ *   doc_start   device int32 [B + 1]: document b's rows are doc_start[b] .. doc_start[b + 1] - 1
+ *   row_src     device int32 [R]: the padded row b L + l of packed row m
+ *   row_dst     device int32 [B L]: the packed row of a padded row, or -1
+ * B L < 2^31.  The host checks the pointers, rows <= B L, max_len <= L and the modes before anything is read; the lists' contents are
+ * the caller's, and the kernels clamp what they read from them into their tensors.
+ *
+ * Semantics.  emb_sum, hidden_out, grad_hidden and grad_emb_sum keep the padded layout [B, L, 768]; the entries gather and scatter
+ * inside the call.  Valid rows of hidden_out are the mode's result; masked rows are EXACT ZEROS (a deliberate departure: HuggingFace
+ * computes something there); a document whose mask is all zero has no rows and its output rows are zeros; rows == 0 returns zeros and
+ * launches nothing.  grad_emb_sum has exact zeros on masked rows, and grad_hidden is read on valid rows only.  The CLS read-out takes
+ * each document's CLS row at its FIRST packed row: the caller guarantees mask[:, 0] == 1 for every document (the Python layer raises
+ * ValueError otherwise, before a launch).  Dropout is keyed by the PADDED logical index, the one the calls above use -- row b L + l for
+ * the hidden sites, ((b 12 + h) L + i) L + j with i, j the tokens' original positions for the probabilities -- so with the same
+ * (seed, step) a packed step draws, at valid positions, the masks a padded step draws (aspire_bert_dropout_mask_u8 serves as it
+ * stands).  One draw per four keys is taken only when prefix != 0 and L % 4 == 0; the mask bits are the same either way.  No atomics:
+ * every element of every output has one writer and every sum a fixed order, the same bits on every run.
+ *
+ * aspire_bert_tape_bytes_packed / aspire_bert_train_workspace_bytes_packed: host only, 0 for rows <= 0 or rows > B L; the tape is that
+ *   of ASPIRE_ATTENTION_FLASH with M = rows (statistics [12, R, 2]), so at most aspire_bert_tape_bytes_attn's and below it as soon as one
+ *   row is masked.
+ * aspire_bert_layers_forward_train_packed_f32 / aspire_bert_layers_backward_packed_f32: the _attn_ entries with `packing` where the mask
+ *   was (no mask is read: every key of a document is real); the backward takes the CLS source arguments of
+ *   aspire_bert_layers_backward_attn_f32.  matmul must be ASPIRE_MATMUL_BF16 and attention ASPIRE_ATTENTION_FLASH: anything else
+ *   -> ASPIRE_ERR_UNSUPPORTED (or ASPIRE_ERR_INVALID_ARG for an unknown mode) before the device is touched.
+ * aspire_bert_cls_mix_train_packed_f32: aspire_bert_cls_mix_train_attn_f32 on a packed tape; hidden_out is the padded [B, L, 768].
+ * aspire_debug_flash_attn_train_packed_f32 / _packed_backward_f32: the bare kernels over packed rows, for tests and tools: qkv / dqkv
+ *   [R, 2304], ctx / dctx [R, 768], stats [12, R, 2], D [12, R]; L is the padded length, which the dropout keys are made of.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct aspire_bert_packing {
+    int64_t rows;
+    int32_t max_len;
+    int32_t prefix;
+    const int32_t* doc_start;
+    const int32_t* row_src;
+    const int32_t* row_dst;
+} aspire_bert_packing;
+
+size_t aspire_bert_tape_bytes_packed(const aspire_bert_weights* w, int64_t B, int64_t L, int64_t rows);
+size_t aspire_bert_train_workspace_bytes_packed(const aspire_bert_weights* w, int64_t B, int64_t L, int64_t rows);
+int aspire_bert_layers_forward_train_packed_f32(const aspire_bert_weights* w, const float* emb_sum, const aspire_bert_packing* packing,
+                                                int64_t B, int64_t L, float* hidden_out, void* tape, size_t tape_bytes, void* ws,
+                                                size_t ws_bytes, const aspire_bert_dropout* dropout, int matmul, int attention, void* stream);
+int aspire_bert_layers_backward_packed_f32(const aspire_bert_weights* w, const aspire_bert_packing* packing, int64_t B, int64_t L,
+                                           const float* grad_hidden, const float* grad_cls, const float* mix, const float* layer_cls,
+                                           const void* tape, size_t tape_bytes, float* grad_emb_sum, const aspire_bert_grads* grads,
+                                           float* grad_mix, void* ws, size_t ws_bytes, const aspire_bert_dropout* dropout, int matmul,
+                                           int attention, void* stream);
+int aspire_bert_cls_mix_train_packed_f32(const aspire_bert_weights* w, const aspire_bert_packing* packing, int64_t B, int64_t L,
+                                         const void* tape, size_t tape_bytes, const float* hidden_out, const float* mix, float* cls_out,
+                                         float* layer_cls, void* stream);
+int aspire_debug_flash_attn_train_packed_f32(const float* qkv, const aspire_bert_packing* packing, int64_t B, int64_t L,
+                                             const aspire_bert_dropout* dropout, float* ctx, float* stats, void* stream);
+int aspire_debug_flash_attn_train_packed_backward_f32(const float* qkv, const aspire_bert_packing* packing, const float* ctx,
+                                                      const float* stats, const float* dctx, int64_t B, int64_t L,
+                                                      const aspire_bert_dropout* dropout, int layer, float* D, float* dqkv, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The embedding lookup under training: BertEmbeddings' sum in front of aspire_bert_layers_forward_train_f32 and the three tables'
  * gradients behind aspire_bert_layers_backward_f32 (what nn.Embedding's forward and scatter backward do on the reference path).
  * Hidden size 768.  Token rows m = b L + l, M = B L.  word [vocab, 768], pos [max_pos, 768], type [n_types, 768]; tok, typ int64
