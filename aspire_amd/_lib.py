@@ -20,6 +20,7 @@ c_void_p, c_int, c_int32, c_int64, c_double, c_size_t = (ctypes.c_void_p, ctypes
 
 ASPIRE_OK, ASPIRE_ERR_INVALID_ARG, ASPIRE_ERR_UNSUPPORTED, ASPIRE_ERR_HIP = 0, 1, 2, 3
 CDIST_AUTO, CDIST_DIRECT, CDIST_MM = 0, 1, 2
+MATMUL_FP32, MATMUL_FP16 = 0, 4                 # ASPIRE_MATMUL_*: the inference forwards' _prec entries
 ATTENTION_GEMM, ATTENTION_FLASH = 0, 1      # ASPIRE_ATTENTION_*: the _attn_ entry points of the training encoder
 CDIST_ONE_FORM = 0x100       # or'ed into cdist_mode of the max-sim entry points: one kernel form whatever the call's size
 OT_FLAG_ONE_FORM = 1         # aspire_ot_params.flags: the same for otAspire
@@ -209,6 +210,18 @@ SIGNATURES = {
     'aspire_debug_gemm_bf16x3_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int64,
                                              c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, ctypes.c_float, c_void_p, c_void_p,
                                              c_int64, c_int, c_void_p]),
+    'aspire_bert_hplanes_bytes': (c_size_t, [ctypes.POINTER(BertWeights)]),
+    'aspire_bert_prepare_hplanes': (c_int, [ctypes.POINTER(BertWeights), c_void_p, c_size_t, c_void_p]),
+    'aspire_bert_workspace_bytes_prec': (c_size_t, [ctypes.POINTER(BertWeights), c_int64, c_int64, c_int]),
+    'aspire_bert_cls_workspace_bytes_prec': (c_size_t, [ctypes.POINTER(BertWeights), c_int64, c_int64, c_int]),
+    'aspire_bert_forward_prec_f32': (c_int, [ctypes.POINTER(BertWeights), ctypes.POINTER(BertExtras), c_void_p, c_int, c_void_p, c_void_p,
+                                             c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'aspire_bert_forward_cls_prec_f32': (c_int, [ctypes.POINTER(BertWeights), c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                                 c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'aspire_debug_hplane_bytes': (c_size_t, [c_int64, c_int64]),
+    'aspire_debug_split_hplane': (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p]),
+    'aspire_debug_gemm_hplane': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int,
+                                         c_void_p]),
     'aspire_inbatch_xent_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     'aspire_inbatch_xent_backward_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'aspire_bert_embed_sum_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64,

@@ -17,7 +17,6 @@ import numpy as np
 import torch
 
 from .batch_prep import MAX_NUM_TOKS, _with_special_tokens, _word_pieces, prepare_eval_ner_seqs, prepare_eval_seqs
-from .encoder import HipBertEncoder
 from .model_front import EncoderFront, add_to_store, check_pid_count, encode_bucketed, load_hf, per_paper
 
 
@@ -39,19 +38,20 @@ class BertMLM(EncoderFront):
     }
     encoding_type = 'abstract'
 
-    def __init__(self, name='specter', hf_model_name=None, bert_model=None, tokenizer=None):
+    def __init__(self, name='specter', hf_model_name=None, bert_model=None, tokenizer=None, matmul='fp32'):
         """
         :param name: a key of MODEL_PATHS: the HF model (and tokenizer) the reference loads for it.
         :param hf_model_name: another HF name or path to load instead of MODEL_PATHS[name].
         :param bert_model: an already constructed transformers BertModel instead (weights are copied to the GPU).
         :param tokenizer: default AutoTokenizer.from_pretrained(the model's name).
+        :param matmul: the encoder's matmul mode, 'fp32' or the opt-in 'fp16' (HipBertEncoder).
         """
         self.name = name
         self.bert_max_seq_len = MAX_NUM_TOKS
         if hf_model_name is None and (bert_model is None or tokenizer is None):
             hf_model_name = self.MODEL_PATHS[name]
         bert_model, self.tokenizer = load_hf(hf_model_name, bert_model, tokenizer)
-        self.bert_encoder = HipBertEncoder(bert_model)
+        self._build_encoder(bert_model, matmul)
 
     def _bert_batch(self, batch_papers):
         """_pre_process_input_batch + _prepare_batch (models.py:259-298)."""

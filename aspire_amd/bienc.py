@@ -17,7 +17,6 @@ import torch
 
 from . import ops
 from .batch_prep import batch_tensors
-from .encoder import HipBertEncoder
 from .model_front import EncoderFront, add_to_store, load_hf, refuse_keys, strip_prefix
 
 
@@ -33,15 +32,16 @@ def split_state_dict(sd):
 
 
 class AspireBiEnc(EncoderFront):
-    def __init__(self, model_hparams=None, bert_model=None, layer_weights=None):
+    def __init__(self, model_hparams=None, bert_model=None, layer_weights=None, matmul='fp32'):
         """
         :param model_hparams: dict with 'base-pt-layer' (the HF model the reference loads, ex_aspire_bienc.py:40).
         :param bert_model: an already constructed transformers BertModel (weights are copied to the GPU).
         :param layer_weights: the SoftmaxMixLayers weight [1, n_layers + 1] (before the softmax), or None: last_hidden_state[:, 0].
+        :param matmul: the encoder's matmul mode, 'fp32' or the opt-in 'fp16' (HipBertEncoder).
         """
         self.bert_encoding_dim = 768
         name = model_hparams['base-pt-layer'] if bert_model is None else None
-        self.bert_encoder = HipBertEncoder(load_hf(name, bert_model, want_tokenizer=False)[0])
+        self._build_encoder(load_hf(name, bert_model, want_tokenizer=False)[0], matmul)
         self.bert_layer_count = self.bert_encoder.config.num_hidden_layers + 1   # plus 1 for the bottom most layer
         self.layer_weights = None
         if layer_weights is not None:
@@ -57,7 +57,7 @@ class AspireBiEnc(EncoderFront):
         """AspireBiEnc / MySPECTER state dict: the encoder is rebuilt from bert_encoder.*, the mix from bert_layer_weights.weight."""
         enc, mix = split_state_dict(sd)
         if enc:
-            self.bert_encoder = HipBertEncoder.from_state_dict(self.bert_encoder.config, enc)
+            self._rebuild_encoder(enc)
             self.bert_layer_count = self.bert_encoder.config.num_hidden_layers + 1
         self.layer_weights = None
         if mix is not None:

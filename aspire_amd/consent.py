@@ -24,19 +24,19 @@ import torch
 
 from . import ops
 from .batch_prep import spans_to_csr
-from .encoder import HipBertEncoder
 from .model_front import EncoderFront, all_finite, check_token_ids, finish_pool, load_hf, pool_layout
 
 
 class AspireConSent(EncoderFront):
-    def __init__(self, hf_model_name=None, bert_model=None):
+    def __init__(self, hf_model_name=None, bert_model=None, matmul='fp32'):
         """
         :param hf_model_name: HuggingFace model name or path, loaded like the reference does (:33).
         :param bert_model: an already constructed transformers BertModel (weights are copied to the GPU).
+        :param matmul: the encoder's matmul mode, 'fp32' or the opt-in 'fp16' (HipBertEncoder).
         """
         self.bert_encoding_dim = 768
         self.bert_layer_count = 12 + 1  # plus 1 for the bottom most layer.
-        self.bert_encoder = HipBertEncoder(load_hf(hf_model_name, bert_model, want_tokenizer=False)[0])
+        self._build_encoder(load_hf(hf_model_name, bert_model, want_tokenizer=False)[0], matmul)
 
     def forward(self, bert_batch, abs_lens, sent_tok_idxs):
         """

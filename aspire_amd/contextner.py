@@ -24,7 +24,6 @@ import torch
 from . import ops
 from .batch_prep import append_entities, prepare_abstracts_entities, span_range_tables
 from .consent import AspireConSent
-from .encoder import HipBertEncoder
 from .model_front import (EncoderFront, add_to_store, all_finite, check_pid_count, check_token_ids, facet_sentence_ids, finish_pool,
                           load_hf, ot_similarity, pool_layout)
 
@@ -73,14 +72,15 @@ class AspireConSenContextual(EncoderFront):
     """Drop-in for the class of the same name (models.py:413-508): contextual sentence reps and contextual entity reps from one
     BERT forward."""
 
-    def __init__(self, hf_model_name=None, bert_model=None):
+    def __init__(self, hf_model_name=None, bert_model=None, matmul='fp32'):
         """
         :param hf_model_name: HuggingFace model name or path, loaded like the reference does (models.py:422).
         :param bert_model: an already constructed transformers BertModel (weights are copied to the GPU).
+        :param matmul: the encoder's matmul mode, 'fp32' or the opt-in 'fp16' (HipBertEncoder).
         """
         self.bert_encoding_dim = 768
         self.bert_layer_count = 12 + 1  # plus 1 for the bottom most layer.
-        self.bert_encoder = HipBertEncoder(load_hf(hf_model_name, bert_model, want_tokenizer=False)[0])
+        self._build_encoder(load_hf(hf_model_name, bert_model, want_tokenizer=False)[0], matmul)
 
     def forward(self, bert_batch, abs_lens, sent_tok_idxs, ner_tok_idxs):
         """
@@ -153,10 +153,10 @@ class _SentenceEntityModel:
 class AspireNER(_SentenceEntityModel):
     """aspire_ner_* (models.py:211-233): every entity string is one more sentence of the abstract; AspireConSent encodes the lot."""
 
-    def __init__(self, hf_model_name=None, bert_model=None, tokenizer=None, name='aspire_ner_compsci'):
+    def __init__(self, hf_model_name=None, bert_model=None, tokenizer=None, name='aspire_ner_compsci', matmul='fp32'):
         self.name = name
         bert_model, self.tokenizer = load_hf(hf_model_name, bert_model, tokenizer)
-        self.model = AspireConSent(bert_model=bert_model)
+        self.model = AspireConSent(bert_model=bert_model, matmul=matmul)
 
     def encode(self, batch_papers, tokenizer=None):
         """:return: per paper [n_kept_sentences (abstract sentences, then entity strings), 768]"""
@@ -167,16 +167,17 @@ class AspireNER(_SentenceEntityModel):
 class AspireContextNER(_SentenceEntityModel):
     """aspire_context_ner_* (models.py:607-735)."""
 
-    def __init__(self, hf_model_name=None, bert_model=None, tokenizer=None, name='aspire_context_ner_compsci'):
+    def __init__(self, hf_model_name=None, bert_model=None, tokenizer=None, name='aspire_context_ner_compsci', matmul='fp32'):
         """
         :param hf_model_name: the HF model (and tokenizer) to load; the reference loads
             'allenai/aspire-contextualsentence-multim-compsci' (models.py:615).
         :param bert_model: an already constructed transformers BertModel instead (weights are copied to the GPU).
         :param tokenizer: default AutoTokenizer.from_pretrained(hf_model_name).
+        :param matmul: the encoder's matmul mode, 'fp32' or the opt-in 'fp16' (HipBertEncoder).
         """
         self.name = name
         bert_model, self.tokenizer = load_hf(hf_model_name, bert_model, tokenizer)
-        self.model = AspireConSenContextual(bert_model=bert_model)
+        self.model = AspireConSenContextual(bert_model=bert_model, matmul=matmul)
 
     def _preprocess_input(self, input_data):
         return prepare_abstracts_entities(input_data, self.tokenizer)

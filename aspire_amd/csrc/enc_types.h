@@ -48,6 +48,18 @@ struct PGemmArgs {
     void* Xp;
 };
 
+// The fp16 matmul mode's GEMM (enc_gemm_h.hip) on single-plane fp16 operands (the H layout: enc_hplane.h)
+struct HGemmArgs {
+    const void* Ah;      // H layout [M, K]
+    const void* Bh;      // H layout [N, K] (nn.Linear weight, scaled by kPWeightScale)
+    float* C;            // fp32 [M, ldc] out (epilogue a)
+    void* Ch;            // H layout [M, N] out (epilogue b: GELU(.), the next GEMM's A operand, its k dimension = N)
+    const float* bias;   // [N] or null
+    const float* res;    // [M, ldr] fp32 residual or null (epilogue a)
+    int M, N, K, ldc, ldr;
+    int n_off;           // first column of this launch (set by the launcher: a GEMM may run as 128-wide and 64-wide column tiles)
+};
+
 namespace {
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
@@ -87,6 +99,14 @@ int launch_gemm_p(const PGemmArgs& g, bool swap, hipStream_t st);
 int launch_gemm_p_qkv(PGemmArgs g, hipStream_t st);
 int launch_gemm_p_ln(const PGemmArgs& g, hipStream_t st);
 bool ln_fused_supported();
+
+// enc_gemm_h.hip: the fp16 matmul mode of the inference encoder (ASPIRE_MATMUL_FP16) -- the GEMM on single-plane fp16 operands (gelu_h:
+// epilogue b, GELU -> g.Ch; else epilogue a -> g.C; any M >= 1, N % 64 == 0, K % 32 == 0), an fp32 matrix (row stride ld) into the H
+// layout (weight: the B side, scaled by kPWeightScale; too_big: optional device flag), and the LayerNorm that writes the fp32 row and
+// its H copy (yh, optional) in one pass.  No device globals, no atomics.
+int launch_gemm_h(const HGemmArgs& g, bool gelu_h, hipStream_t st);
+int launch_split_h(const float* X, int64_t R, int K, int64_t ld, void* H, bool weight, int* too_big, hipStream_t st);
+int launch_layernorm_h(const float* x, const float* gamma, const float* beta, float eps, float* y, int64_t rows, void* yh, hipStream_t st);
 
 // enc_attn.hip: the masked soft-max of the three-kernel form, fused attention on fp32 Q / K / V (f32: fp32-input MFMAs, else fp16
 // planes split in the kernel) and on the QKV GEMM's planes (keys64: 64-key tiles), and the CLS query's attention.

@@ -25,11 +25,13 @@
 //   enc_gemm.hip     gemm_f32_kernel, gemm_bf16x3_kernel: GEMMs on fp32 operands                              launch_gemm
 //   enc_gemm_p.hip   split_planes_kernel, gemm_p_kernel, gemm_p_w8_kernel, gemm_p_qkv_kernel, gemm_p_ln_kernel:
 //                    GEMMs on pre-split fp16 planes                                                          launch_gemm_p, _qkv, _ln, launch_split_planes
+//   enc_gemm_h.hip   split_h_kernel, layernorm_h_kernel, gemm_h_kernel: the opt-in fp16 matmul mode's GEMM on
+//                    single-plane fp16 operands (ASPIRE_MATMUL_FP16, the _prec entries)                      launch_gemm_h, launch_split_h, launch_layernorm_h
 //   enc_attn.hip     flash_attn_p_kernel, flash_attn_p64_kernel, flash_attn_f16x2_kernel, flash_attn_f32_kernel,
 //                    softmax_mask_kernel, cls_attn_kernel                                                    launch_flash_attn_p, launch_flash_attn, launch_softmax_mask, launch_cls_attn
 //   enc_rows.hip     layernorm_kernel, embed_layernorm_kernel, cls_tap_kernel                                launch_layernorm, launch_embed_layernorm, launch_cls_tap
 //   enc_pooler.hip   bert_pooler_kernel: tanh(cls . W^T + b) behind the CLS forward (aspire_bert_pooler_f32)   launch_pooler
-//   enc_planes.h     the fp16-plane layout: constants and device helpers
+//   enc_planes.h     the fp16-plane layout: constants and device helpers; enc_hplane.h: the single-plane layout of the fp16 matmul mode
 //   enc_host.h       host only, shared with encoder_bwd.hip: the buffer carver, the GemmArgs builders (linear, head_gemm), the three-kernel
 //                    attention (attention_gemm), the fp32-operand layer tail (layer_tail), the geometry and null-pointer checks
 // The layer stack under training (the tape-keeping forward over the same enc_host.h launches, and the backward) has a host file of
@@ -37,6 +39,7 @@
 #include <math.h>
 
 #include "enc_host.h"
+#include "enc_hplane.h"
 #include "enc_planes.h"
 #include "tuning.h"
 
@@ -45,7 +48,8 @@ namespace {
 
 struct Workspace {
     float *x, *qkv, *scores, *ctx, *tmp, *ffn;
-    void *actp, *ctxp, *ffnp;       // P-layout activations (pre-split GEMM operands): LayerNorm outputs, attention context, GELU(FFN1)
+    void *actp, *ctxp, *ffnp;       // P-layout activations (pre-split GEMM operands): LayerNorm outputs, attention context, GELU(FFN1);
+                                    // the fp16 matmul mode keeps its H-layout activations (half the bytes: enc_hplane.h) in the same slots
     float2* ln_stats;               // the LayerNorm-epilogue GEMMs' per-row, per-column-tile moments [M][12]
     int* ln_count;                  // their arrival counters [2 n_layers][row blocks], zeroed once per forward
     size_t ln_count_bytes;
@@ -89,6 +93,17 @@ PlaneOffsets plane_offsets(int ffn_dim) {
     return o;
 }
 
+// ... and in the H planes of the fp16 matmul mode (aspire_bert_prepare_hplanes)
+PlaneOffsets hplane_offsets(int ffn_dim) {
+    PlaneOffsets o{};
+    Carver c(nullptr);
+    o.qkv = c.off; c.bytes(h_bytes(3 * kD, kD));
+    o.o = c.off; c.bytes(h_bytes(kD, kD));
+    o.ffn1 = c.off; c.bytes(h_bytes(ffn_dim, kD));
+    o.ffn2 = c.off; c.bytes(h_bytes(kD, ffn_dim));
+    o.per_layer = c.off;
+    return o;
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // One forward's plan -- the form every step takes, decided once from B, L, the weights and the tuning pins -- and one layer of it.
@@ -103,7 +118,9 @@ struct Fwd {
     int64_t B, L, M, row_tiles;
     int Lp, H, dh;
     bool pp, ln_fused, attn_p;
-    PlaneOffsets po;
+    bool hh;                        // the fp16 matmul mode: the four projections on H operands (run_layer's H path), at every M
+    const void* hplanes;
+    PlaneOffsets po, ho;
     Workspace ws;
     hipStream_t st;
 };
@@ -116,7 +133,8 @@ int check_forward_args(const aspire_bert_weights* w, const int64_t* tok_ids, con
     return ASPIRE_OK;
 }
 
-int plan_forward(Fwd& f, const aspire_bert_weights* w, const int64_t* attn_mask, int64_t B, int64_t L, void* workspace, hipStream_t st) {
+int plan_forward(Fwd& f, const aspire_bert_weights* w, const int64_t* attn_mask, int64_t B, int64_t L, void* workspace, hipStream_t st,
+                 const void* hplanes = nullptr, int matmul = ASPIRE_MATMUL_FP32) {
     f.w = w;
     f.mask = attn_mask;
     f.pos_ids = nullptr;
@@ -146,6 +164,14 @@ int plan_forward(Fwd& f, const aspire_bert_weights* w, const int64_t* attn_mask,
     // Round 6 (default on the plane path; ASPIRE_HIP_ATTN=f16x2 pins round 5's form, which splits fp32 Q / K / V inside the attention kernel):
     // the QKV GEMM writes the attention's operands as fp16 planes, the attention stages them by LDS-DMA (flash_attn_p_kernel)
     f.attn_p = f.pp && w->n_layers > 0 && tuning().attn_form != 1 && !tuning().attn_f32 && tuning().gemm_tile == 0;
+    // The fp16 matmul mode (ASPIRE_MATMUL_FP16, opt-in): every nn.Linear operand rounded to fp16 once, one product per term
+    // (gemm_h_kernel), at EVERY M -- the mode has no 1024-row threshold (below it neither path has been measured in this mode).  A
+    // GEMM pin (ASPIRE_HIP_GEMM=..) overrides the mode: run_checked re-encodes an overflowed forward under GEMM=bf16x3, and the plan
+    // above then holds as it stands.  The residual stream, LayerNorm and the attention stay fp32 launches: fp32 x exists at every layer
+    f.hplanes = hplanes;
+    f.ho = hplane_offsets(w->ffn_dim);
+    f.hh = matmul == ASPIRE_MATMUL_FP16 && hplanes != nullptr && w->n_layers > 0 && f.dh == 64 && w->ffn_dim % 128 == 0 && tuning().gemm_form == 0;
+    if (f.hh) f.pp = f.ln_fused = f.attn_p = false;
     return ASPIRE_OK;
 }
 
@@ -159,6 +185,13 @@ int launch_embed(const Fwd& f, const int64_t* tok_ids, const int64_t* type_ids, 
     ASPIRE_REQUIRE(!f.pp || (uint64_t)f.M * (uint64_t)(w->ffn_dim > 3 * kD ? w->ffn_dim : 3 * kD) * 4 < (1ull << 32), ASPIRE_ERR_UNSUPPORTED,
                    "%lld token rows in one forward: the fp16-plane layout addresses < 4 GB per operand (split the batch)", (long long)f.M);
     if (f.ln_fused && w->n_layers > 0) ASPIRE_HIP_OK(hipMemsetAsync(f.ws.ln_count, 0, f.ws.ln_count_bytes, f.st));
+    if (f.hh) {
+        // the H layout's slot offsets are 32-bit byte offsets too (h_slot8): 2 bytes per element
+        ASPIRE_REQUIRE((uint64_t)f.M * (uint64_t)(w->ffn_dim > 3 * kD ? w->ffn_dim : 3 * kD) * 2 < (1ull << 32), ASPIRE_ERR_UNSUPPORTED,
+                       "%lld token rows in one forward: the fp16-plane layout addresses < 4 GB per operand (split the batch)", (long long)f.M);
+        // the embedding LayerNorm's fp32 rows go through split_h_kernel (no fused H writer in embed_layernorm_kernel)
+        if (int rc = launch_split_h(x, f.M, kD, kD, f.ws.actp, false, nullptr, f.st)) return rc;
+    }
     return ASPIRE_OK;
 }
 
@@ -174,6 +207,32 @@ int run_layer(const Fwd& f, int l, const float* x, float* out, bool last, bool q
     const int64_t* attn_mask = f.mask;
     hipStream_t st = f.st;
     const aspire_bert_layer& ly = w->layers[l];
+    if (f.hh) {
+        // The fp16 matmul mode: the !ln_fused plane route below with H buffers where it has P buffers (the workspace's P slots hold them)
+        const PlaneOffsets& ho = f.ho;
+        const char* lh = (const char*)f.hplanes + (size_t)l * ho.per_layer;
+        // 1. QKV projection -> fp32 qkv
+        HGemmArgs hg{ws.actp, lh + ho.qkv, ws.qkv, nullptr, ly.b_qkv, nullptr, (int)M, 3 * kD, kD, 3 * kD, 0, 0};
+        if (int rc = launch_gemm_h(hg, false, st)) return rc;
+        if (qkv_only) return ASPIRE_OK;
+        // 2-4. attention: an existing kernel on fp32 Q / K / V, unchanged; its fp32 context goes to H through split_h_kernel
+        if (!tuning().attn_gemm) {
+            if (int rc = launch_flash_attn(ws.qkv, attn_mask, ws.ctx, B, (int)L, H, nullptr, M, tuning().attn_f32 != 0, f.rel_bias, f.rel_span, st)) return rc;
+        } else {
+            if (int rc = attention_gemm(ws.qkv, ws.scores, ws.ctx, attn_mask, B, L, Lp, H, dh, f.rel_bias, f.rel_span, st)) return rc;
+        }
+        if (int rc = launch_split_h(ws.ctx, M, kD, kD, ws.ctxp, false, nullptr, st)) return rc;
+        // 5. attention output projection + fp32 residual, LayerNorm -> h (fp32 ws.ctx and its H copy)
+        hg = HGemmArgs{ws.ctxp, lh + ho.o, ws.tmp, nullptr, ly.b_o, x, (int)M, kD, kD, kD, kD, 0};
+        if (int rc = launch_gemm_h(hg, false, st)) return rc;
+        if (int rc = launch_layernorm_h(ws.tmp, ly.ln1_g, ly.ln1_b, w->ln_eps, ws.ctx, M, ws.actp, st)) return rc;
+        // 6. FFN: GELU(h . W1^T + b1) straight into the H layout (no fp32 [M, ffn] exists), . W2^T + b2 + h, LayerNorm
+        hg = HGemmArgs{ws.actp, lh + ho.ffn1, nullptr, ws.ffnp, ly.b_ffn1, nullptr, (int)M, w->ffn_dim, kD, 0, 0, 0};
+        if (int rc = launch_gemm_h(hg, true, st)) return rc;
+        hg = HGemmArgs{ws.ffnp, lh + ho.ffn2, ws.tmp, nullptr, ly.b_ffn2, ws.ctx, (int)M, kD, w->ffn_dim, kD, kD, 0};
+        if (int rc = launch_gemm_h(hg, false, st)) return rc;
+        return launch_layernorm_h(ws.tmp, ly.ln2_g, ly.ln2_b, w->ln_eps, out, M, last ? nullptr : ws.actp, st);
+    }
     const char* lp = (const char*)w->planes + (size_t)l * po.per_layer;
     PGemmArgs pg{};
     // 1. fused QKV projection: qkv [M, 2304] = x . Wqkv^T + bqkv
@@ -268,10 +327,28 @@ extern "C" int aspire_bert_forward_f32(const aspire_bert_weights* w, const int64
     return aspire_bert_forward_var_f32(w, nullptr, tok_ids, type_ids, attn_mask, B, L, hidden_out, workspace, workspace_bytes, stream);
 }
 
+// the _prec entries' mode check: ASPIRE_MATMUL_FP32, or ASPIRE_MATMUL_FP16 with the weights' H planes; no device is touched
+static int check_matmul_mode(int matmul, const void* hplanes) {
+    ASPIRE_REQUIRE(matmul == ASPIRE_MATMUL_FP32 || matmul == ASPIRE_MATMUL_FP16, ASPIRE_ERR_INVALID_ARG,
+                   "matmul mode %d: the inference forwards take ASPIRE_MATMUL_FP32 (0) or ASPIRE_MATMUL_FP16 (4)", matmul);
+    ASPIRE_REQUIRE(matmul != ASPIRE_MATMUL_FP16 || hplanes, ASPIRE_ERR_INVALID_ARG,
+                   "ASPIRE_MATMUL_FP16 without hplanes (aspire_bert_prepare_hplanes)");
+    return ASPIRE_OK;
+}
+
 extern "C" int aspire_bert_forward_var_f32(const aspire_bert_weights* w, const aspire_bert_extras* x_, const int64_t* tok_ids,
                                            const int64_t* type_ids, const int64_t* attn_mask, int64_t B, int64_t L, float* hidden_out,
                                            void* workspace, size_t workspace_bytes, void* stream) {
+    return aspire_bert_forward_prec_f32(w, x_, nullptr, ASPIRE_MATMUL_FP32, tok_ids, type_ids, attn_mask, B, L, hidden_out, workspace,
+                                        workspace_bytes, stream);
+}
+
+// The forward in a matmul mode: with ASPIRE_MATMUL_FP32 the body every forward above always ran (hplanes is not read)
+extern "C" int aspire_bert_forward_prec_f32(const aspire_bert_weights* w, const aspire_bert_extras* x_, const void* hplanes, int matmul,
+                                            const int64_t* tok_ids, const int64_t* type_ids, const int64_t* attn_mask, int64_t B, int64_t L,
+                                            float* hidden_out, void* workspace, size_t workspace_bytes, void* stream) {
     if (int rc = check_forward_args(w, tok_ids, attn_mask, hidden_out, B, L)) return rc;
+    if (int rc = check_matmul_mode(matmul, hplanes)) return rc;
     ASPIRE_REQUIRE(!x_ || !x_->rel_bias || x_->rel_span >= L, ASPIRE_ERR_INVALID_ARG,
                    "rel_span %d < sequence length %lld: the bias table does not cover every (query, key) distance", x_ ? x_->rel_span : 0,
                    (long long)L);
@@ -279,7 +356,7 @@ extern "C" int aspire_bert_forward_var_f32(const aspire_bert_weights* w, const a
     const size_t need = carve(nullptr, B, L, w->n_heads, w->ffn_dim, w->n_layers).total;
     ASPIRE_REQUIRE(workspace && workspace_bytes >= need, ASPIRE_ERR_INVALID_ARG, "workspace too small: need %zu bytes", need);
     Fwd f;
-    if (int rc = plan_forward(f, w, attn_mask, B, L, workspace, (hipStream_t)stream)) return rc;
+    if (int rc = plan_forward(f, w, attn_mask, B, L, workspace, (hipStream_t)stream, hplanes, matmul)) return rc;
     if (x_) {
         f.pos_ids = x_->pos_ids;
         f.rel_bias = x_->rel_bias;
@@ -313,7 +390,18 @@ extern "C" size_t aspire_bert_cls_workspace_bytes(const aspire_bert_weights* w, 
 extern "C" int aspire_bert_forward_cls_f32(const aspire_bert_weights* w, const int64_t* tok_ids, const int64_t* type_ids,
                                            const int64_t* attn_mask, int64_t B, int64_t L, const float* layer_mix, float* cls_out,
                                            float* layer_cls, void* workspace, size_t workspace_bytes, void* stream) {
+    return aspire_bert_forward_cls_prec_f32(w, nullptr, ASPIRE_MATMUL_FP32, tok_ids, type_ids, attn_mask, B, L, layer_mix, cls_out, layer_cls,
+                                            workspace, workspace_bytes, stream);
+}
+
+// ... in a matmul mode.  ASPIRE_MATMUL_FP16: layers 0 .. n - 2 and the last layer's QKV GEMM run in the mode; the last layer's tail on
+// the B CLS rows (one query per document and head, then layer_tail) is the existing fp32 one
+extern "C" int aspire_bert_forward_cls_prec_f32(const aspire_bert_weights* w, const void* hplanes, int matmul, const int64_t* tok_ids,
+                                                const int64_t* type_ids, const int64_t* attn_mask, int64_t B, int64_t L,
+                                                const float* layer_mix, float* cls_out, float* layer_cls, void* workspace,
+                                                size_t workspace_bytes, void* stream) {
     if (int rc = check_forward_args(w, tok_ids, attn_mask, cls_out, B, L)) return rc;
+    if (int rc = check_matmul_mode(matmul, hplanes)) return rc;
     if (layer_mix)
         for (int i = 0; i <= w->n_layers; ++i)
             ASPIRE_REQUIRE(isfinite(layer_mix[i]), ASPIRE_ERR_INVALID_ARG, "layer_mix[%d] is not finite", i);
@@ -321,7 +409,7 @@ extern "C" int aspire_bert_forward_cls_f32(const aspire_bert_weights* w, const i
     const size_t need = aspire_bert_cls_workspace_bytes(w, B, L);
     ASPIRE_REQUIRE(workspace && workspace_bytes >= need, ASPIRE_ERR_INVALID_ARG, "workspace too small: need %zu bytes", need);
     Fwd f;
-    if (int rc = plan_forward(f, w, attn_mask, B, L, workspace, (hipStream_t)stream)) return rc;
+    if (int rc = plan_forward(f, w, attn_mask, B, L, workspace, (hipStream_t)stream, hplanes, matmul)) return rc;
     const ClsWorkspace cw = carve_cls((char*)workspace + f.ws.total, B, w->ffn_dim);
     const int n = w->n_layers;
     // hidden state i: its CLS row -> layer_cls[i], cls_out (+)= mix[i] x row, and (i = n - 1) the last layer's residual input
@@ -362,6 +450,64 @@ extern "C" int aspire_bert_pooler_f32(const float* cls, int64_t B, int64_t D, co
     ASPIRE_REQUIRE(((uintptr_t)cls & 15) == 0 && ((uintptr_t)w_pool & 15) == 0, ASPIRE_ERR_INVALID_ARG,
                    "cls and w_pool must be 16-byte aligned");
     return launch_pooler(cls, B, w_pool, b_pool, pooled, (hipStream_t)stream);
+}
+
+// The _prec forwards' workspaces: the mode's H-layout activations live in the default path's P slots (twice their size), and a GEMM pin
+// sends a forward of the mode down the default path, so both modes ask for the same bytes
+extern "C" size_t aspire_bert_workspace_bytes_prec(const aspire_bert_weights* w, int64_t B, int64_t L, int matmul) {
+    if (matmul != ASPIRE_MATMUL_FP32 && matmul != ASPIRE_MATMUL_FP16) return 0;
+    return aspire_bert_workspace_bytes(w, B, L);
+}
+extern "C" size_t aspire_bert_cls_workspace_bytes_prec(const aspire_bert_weights* w, int64_t B, int64_t L, int matmul) {
+    if (matmul != ASPIRE_MATMUL_FP32 && matmul != ASPIRE_MATMUL_FP16) return 0;
+    return aspire_bert_cls_workspace_bytes(w, B, L);
+}
+
+// The weights' single fp16 planes of the fp16 matmul mode (the H layout, 64 w rounded once), formed ONCE when the model is loaded: a
+// device buffer the caller keeps next to the weights and hands to the _prec forwards
+extern "C" size_t aspire_bert_hplanes_bytes(const aspire_bert_weights* w) {
+    if (!w || w->n_layers <= 0 || w->hidden != kD || w->ffn_dim <= 0) return 0;
+    return hplane_offsets(w->ffn_dim).per_layer * (size_t)w->n_layers;
+}
+
+extern "C" int aspire_bert_prepare_hplanes(const aspire_bert_weights* w, void* hplanes, size_t hplanes_bytes, void* stream) {
+    ASPIRE_REQUIRE(w && hplanes, ASPIRE_ERR_INVALID_ARG, "null pointer");
+    ASPIRE_REQUIRE(w->hidden == kD && w->ffn_dim % 128 == 0 && w->ffn_dim > 0, ASPIRE_ERR_UNSUPPORTED,
+                   "fp16 weight planes are built for hidden 768 and an ffn width that is a multiple of 128");
+    ASPIRE_REQUIRE(w->n_layers > 0 && w->layers, ASPIRE_ERR_INVALID_ARG, "bad layer table");
+    ASPIRE_REQUIRE(hplanes_bytes >= aspire_bert_hplanes_bytes(w), ASPIRE_ERR_INVALID_ARG, "hplanes buffer too small");
+    if (int rc = check_layer_pointers(w->layers, w->n_layers, "weights")) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const PlaneOffsets ho = hplane_offsets(w->ffn_dim);
+    int* too_big = nullptr;        // a load-time call: its own 4 bytes, one synchronisation at the end
+    ASPIRE_HIP_OK(hipMalloc((void**)&too_big, sizeof(int)));
+    int rc = ASPIRE_OK;
+    auto split = [&](const float* X, int64_t R, int K, void* P) {
+        if (rc == ASPIRE_OK) rc = launch_split_h(X, R, K, K, P, true, too_big, st);
+    };
+    hipError_t e0 = hipMemsetAsync(too_big, 0, sizeof(int), st);
+    if (e0 == hipSuccess) e0 = hipMemsetAsync(hplanes, 0, aspire_bert_hplanes_bytes(w), st);      // the slack rows behind every matrix
+    if (e0 != hipSuccess) {
+        (void)hipFree(too_big);
+        ASPIRE_HIP_OK(e0);
+    }
+    for (int l = 0; l < w->n_layers; ++l) {
+        const aspire_bert_layer& ly = w->layers[l];
+        char* lh = (char*)hplanes + (size_t)l * ho.per_layer;
+        split(ly.w_qkv, 3 * kD, kD, lh + ho.qkv);
+        split(ly.w_o, kD, kD, lh + ho.o);
+        split(ly.w_ffn1, w->ffn_dim, kD, lh + ho.ffn1);
+        split(ly.w_ffn2, kD, w->ffn_dim, lh + ho.ffn2);
+    }
+    int flag = 0;
+    hipError_t e1 = rc == ASPIRE_OK ? hipMemcpyAsync(&flag, too_big, sizeof(int), hipMemcpyDeviceToHost, st) : hipSuccess;
+    if (e1 == hipSuccess) e1 = hipStreamSynchronize(st);
+    (void)hipFree(too_big);
+    if (rc != ASPIRE_OK) return rc;
+    ASPIRE_HIP_OK(e1);
+    ASPIRE_REQUIRE(flag == 0, ASPIRE_ERR_UNSUPPORTED,
+                   "a weight is not finite or beyond +-1023 (|64 w| > 65504): outside the fp16 matmul mode's range (run such a model with ASPIRE_MATMUL_FP32)");
+    return ASPIRE_OK;
 }
 
 // The weights' fp16 planes, formed ONCE when the model is loaded: a device buffer of aspire_bert_planes_bytes(w) bytes that the

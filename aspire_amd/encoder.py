@@ -21,7 +21,7 @@ from types import SimpleNamespace
 import torch
 
 from . import ops
-from ._lib import BertExtras, BertLayer, BertWeights, check, lib, pinned
+from ._lib import MATMUL_FP16, MATMUL_FP32, BertExtras, BertLayer, BertWeights, check, lib, pinned
 
 _LAYER_KEYS = ('attention.output.dense.weight', 'attention.output.dense.bias', 'attention.output.LayerNorm.weight',
                'attention.output.LayerNorm.bias', 'intermediate.dense.weight', 'intermediate.dense.bias', 'output.dense.weight',
@@ -138,7 +138,14 @@ def run_checked(run, outputs_finite, who, status):
 
 
 class HipBertEncoder:
-    def __init__(self, bert_model):
+    """matmul: 'fp32' (default: every product fp32-accurate) or 'fp16' (opt-in: the four projections of a layer with every operand
+    rounded to fp16 once, one matrix instruction per term -- include/aspire_hip.h, A1h; everything else as in 'fp32').  `matmul`
+    reads the mode in force: 'fp32' when the weights leave the mode's range (a UserWarning says so)."""
+    MATMUL_MODES = {'fp32': MATMUL_FP32, 'fp16': MATMUL_FP16}
+
+    def __init__(self, bert_model, matmul='fp32'):
+        if matmul not in self.MATMUL_MODES:
+            raise ValueError(f"HipBertEncoder: matmul {matmul!r}: 'fp32' or 'fp16' (the training encoder has the bf16 modes)")
         dev = ops.require_gpu()
         cfg = bert_model.config
         require_bert_base(cfg, 1, 'HipBertEncoder')          # (any intermediate_size: the library checks it per call)
@@ -181,14 +188,28 @@ class HipBertEncoder:
             except NotImplementedError as e:        # a weight beyond the fp16 planes' range: the on-the-fly bf16x3 GEMMs take any fp32
                 warnings.warn(f'HipBertEncoder: {e}; running without pre-split weights')
                 self._planes = None
+        # the fp16 matmul mode's single planes of the same weights (aspire_bert_prepare_hplanes): an argument of the _prec entries
+        self.matmul = 'fp32'
+        self.matmul_asked = matmul          # what a rebuilt encoder (load_state_dict) is asked for again
+        self._hplanes = None
+        if matmul == 'fp16':
+            nbytes = lib.aspire_bert_hplanes_bytes(ctypes.byref(self._w))
+            try:
+                if not nbytes or cfg.intermediate_size % 128:
+                    raise NotImplementedError('the fp16 matmul mode needs at least one layer and intermediate_size % 128 == 0')
+                hp = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+                check(lib.aspire_bert_prepare_hplanes(ctypes.byref(self._w), ops._ptr(hp), nbytes, ops._stream()))
+                self._hplanes, self.matmul = hp, 'fp16'
+            except NotImplementedError as e:
+                warnings.warn(f"HipBertEncoder: {e}; running with matmul='fp32'")
 
     @classmethod
-    def from_state_dict(cls, config, sd):
+    def from_state_dict(cls, config, sd, matmul='fp32'):
         """The encoder of a BertModel(config) holding state dict sd (with a pooler when sd has one: load_state_dict is strict)."""
         from transformers import BertModel
         bm = BertModel(config, add_pooling_layer=any(k.startswith('pooler.') for k in sd))
         bm.load_state_dict(sd)
-        return cls(bm)
+        return cls(bm, matmul=matmul)
 
     def eval(self):
         return self
@@ -240,6 +261,15 @@ class HipBertEncoder:
         tok, typ, msk = self.device_inputs(tokid_tt, token_type_ids, attention_mask, check_ids)
         b, l = tok.shape
         out = torch.empty(b, l, 768, device=self.device, dtype=torch.float32)
+        if self.matmul != 'fp32':
+            # the mode's entry (the extras NULL for a BertModel); a GEMM pin -- forward_full_range, run_checked -- overrides the mode inside
+            mode = self.MATMUL_MODES[self.matmul]
+            ws = self._workspace(lib.aspire_bert_workspace_bytes_prec(ctypes.byref(self._w), b, l, mode))
+            x, _pos = self._extras(tok)
+            check(lib.aspire_bert_forward_prec_f32(ctypes.byref(self._w), ctypes.byref(x) if x is not None else None, ops._ptr(self._hplanes),
+                                                   mode, ops._ptr(tok), None if self.kind == 'mpnet' else ops._ptr(typ), ops._ptr(msk), b, l,
+                                                   ops._ptr(out), ops._ptr(ws), ws.numel(), ops._stream()))
+            return out
         ws = self._workspace(lib.aspire_bert_workspace_bytes(ctypes.byref(self._w), b, l))
         if self.kind == 'bert':
             check(lib.aspire_bert_forward_f32(ctypes.byref(self._w), ops._ptr(tok), ops._ptr(typ), ops._ptr(msk), b, l,
@@ -272,6 +302,13 @@ class HipBertEncoder:
         layers = torch.empty(self.config.num_hidden_layers + 1, b, 768, device=dev, dtype=torch.float32) if want_layers else None
         mix = ctypes.cast((ctypes.c_float * len(layer_mix))(*[float(x) for x in layer_mix]), ctypes.c_void_p) \
             if layer_mix is not None else None
+        if self.matmul != 'fp32':
+            mode = self.MATMUL_MODES[self.matmul]
+            ws = self._workspace(lib.aspire_bert_cls_workspace_bytes_prec(ctypes.byref(self._w), b, l, mode))
+            check(lib.aspire_bert_forward_cls_prec_f32(ctypes.byref(self._w), ops._ptr(self._hplanes), mode, ops._ptr(tok), ops._ptr(typ),
+                                                       ops._ptr(msk), b, l, mix, ops._ptr(out), ops._ptr(layers), ops._ptr(ws), ws.numel(),
+                                                       ops._stream()))
+            return out, layers
         ws = self._workspace(lib.aspire_bert_cls_workspace_bytes(ctypes.byref(self._w), b, l))
         check(lib.aspire_bert_forward_cls_f32(ctypes.byref(self._w), ops._ptr(tok), ops._ptr(typ), ops._ptr(msk), b, l, mix,
                                               ops._ptr(out), ops._ptr(layers), ops._ptr(ws), ws.numel(), ops._stream()))

@@ -52,6 +52,17 @@ class EncoderFront:
     def __call__(self, *args, **kwargs):
         return self.forward(*args, **kwargs)
 
+    def _build_encoder(self, bert_model, matmul='fp32'):
+        """self.bert_encoder over bert_model's weights.  matmul: the encoder's matmul mode, 'fp32' or the opt-in 'fp16'
+        (HipBertEncoder); every model class takes it as a keyword and hands it on here."""
+        from .encoder import HipBertEncoder
+        self.bert_encoder = HipBertEncoder(bert_model, matmul=matmul)
+
+    def _rebuild_encoder(self, sd):
+        """self.bert_encoder again from a BertModel state dict (a checkpoint), in the mode the model was built with."""
+        from .encoder import HipBertEncoder
+        self.bert_encoder = HipBertEncoder.from_state_dict(self.bert_encoder.config, sd, matmul=self.bert_encoder.matmul_asked)
+
     def _checked_read(self, read, finite_part, tok, typ, msk, who=None):
         """int64 [B, L] inputs (any device) to the GPU once, then read(tok, typ, msk) under the encoder's fall-back rule
         (encoder.run_checked), which judges finite_part(result): a tensor or a tuple of tensors (None entries skipped)."""

@@ -26,12 +26,12 @@ class AspireModel:
     similarity, encoding_type 'sentence'."""
     encoding_type = 'sentence'
 
-    def __init__(self, name='aspire_compsci', hf_model_name=None, bert_model=None, tokenizer=None):
+    def __init__(self, name='aspire_compsci', hf_model_name=None, bert_model=None, tokenizer=None, matmul='fp32'):
         self.name = name
         if hf_model_name is None and (bert_model is None or tokenizer is None):
             hf_model_name = ASPIRE_MODEL_PATHS[name.split('_')[-1]]
         bert_model, self.tokenizer = load_hf(hf_model_name, bert_model, tokenizer)
-        self.model = AspireConSent(bert_model=bert_model)
+        self.model = AspireConSent(bert_model=bert_model, matmul=matmul)       # matmul: the encoder's mode, 'fp32' or the opt-in 'fp16'
 
     def encode(self, batch_papers):
         """:return: per paper [n_kept_sentences, 768]"""
@@ -63,7 +63,7 @@ def _default_hf_name(kw, name):
 
 def get_model(model_name, trained_model_path=None, **kw):
     """The reference's get_model (models.py:738-768).  **kw goes to the class's constructor (bert_model=, tokenizer=: nothing is
-    downloaded when both are given).  trained_model_path: the run directory of 'cospecter' (run_info.json + model_cur_best.pt,
+    downloaded when both are given; matmul='fp16': the encoder's opt-in fp16 matmul mode, HipBertEncoder).  trained_model_path: the run directory of 'cospecter' (run_info.json + model_cur_best.pt,
     models.py:522-555) or of 'cosentbert' / 'ictsentbert' (sent_encoder_cur_best.pt, models.py:573-582)."""
     if model_name in SENTENCE_TRANSFORMER_NAMES:
         raise NotImplementedError(f'{model_name}: the SentenceTransformer baselines (TinyBERT / RoBERTa / MPNet encoders) are not built '

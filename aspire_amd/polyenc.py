@@ -24,7 +24,7 @@ from .model_front import read_hparams, strip_prefix
 
 
 class WordSentAlignPolyEnc(AspireConSent):
-    def __init__(self, model_hparams=None, bert_config=None, bert_model=None):
+    def __init__(self, model_hparams=None, bert_config=None, bert_model=None, matmul='fp32'):
         """
         :param model_hparams: the run's hyper-parameters (run_info.json 'all_hparams'): 'base-pt-layer' names the HF model to
             load; 'score_aggregation', when given, must be 'jointsm' (disent_models.py:868-871).
@@ -35,13 +35,12 @@ class WordSentAlignPolyEnc(AspireConSent):
         agg = model_hparams.get('score_aggregation', 'jointsm')
         if agg != 'jointsm':
             raise ValueError(f'Unknown aggregation: {agg}')
-        AspireConSent.__init__(self, hf_model_name=model_hparams.get('base-pt-layer'), bert_model=bert_model)
+        AspireConSent.__init__(self, hf_model_name=model_hparams.get('base-pt-layer'), bert_model=bert_model, matmul=matmul)
 
     def load_state_dict(self, sd):
         """model_cur_best.pt: the encoder is rebuilt from its bert_encoder.* keys (the class has no other parameters)."""
-        from .encoder import HipBertEncoder
         enc, _ = strip_prefix(sd, 'bert_encoder.', who='WordSentAlignPolyEnc')
-        self.bert_encoder = HipBertEncoder.from_state_dict(self.bert_encoder.config, enc)
+        self._rebuild_encoder(enc)
         return self
 
     @staticmethod

@@ -17,7 +17,6 @@ import os
 
 import numpy as np
 
-from .encoder import HipBertEncoder
 from .model_front import EncoderFront, add_to_store, check_pid_count, encode_bucketed, load_hf, per_paper, sentence_facet_rows
 
 
@@ -45,7 +44,7 @@ class SentenceModel(EncoderFront):
     }
     encoding_type = 'sentence'
 
-    def __init__(self, name, hf_model_name=None, model=None, tokenizer=None, max_seq_length=None, normalize=None):
+    def __init__(self, name, hf_model_name=None, model=None, tokenizer=None, max_seq_length=None, normalize=None, matmul='fp32'):
         """
         :param name: a key of MODEL_PATHS: the model the reference hands to SentenceTransformer.
         :param hf_model_name: another HF name or a local directory to load instead.
@@ -54,6 +53,7 @@ class SentenceModel(EncoderFront):
         :param tokenizer: default AutoTokenizer.from_pretrained(the model's name).
         :param max_seq_length: tokens per sentence, special tokens included (models.Transformer(max_seq_length)).
         :param normalize: L2-normalise the reps (a Normalize module in the model's modules.json).
+        :param matmul: the encoder's matmul mode, 'fp32' or the opt-in 'fp16' (HipBertEncoder).
         """
         self.name = name
         full_name = hf_model_name if hf_model_name is not None else self.hub_name(name)
@@ -65,7 +65,7 @@ class SentenceModel(EncoderFront):
         model, self.tokenizer = load_hf(full_name, model, tokenizer)
         self.max_seq_length = int(max_seq_length if max_seq_length is not None else seq_default or 512)
         self.normalize = bool(normalize if normalize is not None else norm_default)
-        self.bert_encoder = HipBertEncoder(model)
+        self._build_encoder(model, matmul)
 
     @classmethod
     def hub_name(cls, name):

@@ -15,7 +15,6 @@ import numpy as np
 
 from . import _lib, ops
 from .batch_prep import batch_tensors, tokenize_sentences
-from .encoder import HipBertEncoder
 from .model_front import EncoderFront, add_to_store, check_pid_count, encode_bucketed, load_hf, per_paper, refuse_keys, strip_prefix
 
 
@@ -32,22 +31,23 @@ def split_state_dict(sd):
 
 
 class AspireSentEnc(EncoderFront):
-    def __init__(self, hf_model_name=None, bert_model=None, max_seq_length=512, tokenizer=None):
+    def __init__(self, hf_model_name=None, bert_model=None, max_seq_length=512, tokenizer=None, matmul='fp32'):
         """
         :param hf_model_name: the HF model (and tokenizer) to load, e.g. 'allenai/aspire-sentence-embedder' or, as
             TrainedSentModel does before loading its checkpoint, 'allenai/scibert_scivocab_uncased'.
         :param bert_model: an already constructed transformers BertModel instead (weights are copied to the GPU).
         :param max_seq_length: models.Transformer(max_seq_length=512).
         :param tokenizer: the tokenizer encode() uses (default: AutoTokenizer.from_pretrained(hf_model_name)).
+        :param matmul: the encoder's matmul mode, 'fp32' or the opt-in 'fp16' (HipBertEncoder).
         """
         self.bert_encoding_dim = 768
         self.max_seq_length = int(max_seq_length)
         bert_model, self.tokenizer = load_hf(hf_model_name, bert_model, tokenizer)
-        self.bert_encoder = HipBertEncoder(bert_model)
+        self._build_encoder(bert_model, matmul)
 
     def load_state_dict(self, sd):
         """sent_encoder_cur_best.pt (a BertModel state dict) or a SentBERTWrapper / ICTBERTWrapper one (split_state_dict)."""
-        self.bert_encoder = HipBertEncoder.from_state_dict(self.bert_encoder.config, split_state_dict(sd))
+        self._rebuild_encoder(split_state_dict(sd))
         return self
 
     # ---- the forward ---------------------------------------------------------------------------------------------------

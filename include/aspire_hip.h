@@ -436,7 +436,8 @@ int aspire_inbatch_xent_backward_f32(const float* q, const float* c, int64_t B, 
  * instantiation of the latest B_KN or TN launch of this process as 3 * form + tile (3 .. 8; the tiles and the pin as above), -1
  * before the first; an NT product does not change it.
  * ------------------------------------------------------------------------------------------- */
-enum { ASPIRE_MATMUL_FP32 = 0, ASPIRE_MATMUL_BF16 = 1, ASPIRE_MATMUL_BF16X3 = 3 };       /* 2 is not a mode (above) */
+enum { ASPIRE_MATMUL_FP32 = 0, ASPIRE_MATMUL_BF16 = 1, ASPIRE_MATMUL_BF16X3 = 3,        /* 2 is not a mode (above) */
+       ASPIRE_MATMUL_FP16 = 4 };   /* the INFERENCE forwards' mode (A1h below); the training entries refuse it like any other value */
 enum { ASPIRE_GEMM_NT = 0, ASPIRE_GEMM_BKN = 1, ASPIRE_GEMM_TN = 2 };
 
 int aspire_bert_layers_forward_train_prec_f32(const aspire_bert_weights* w, const float* emb_sum, const int64_t* attn_mask, int64_t B,
@@ -455,6 +456,67 @@ int aspire_debug_gemm_bf16x3_f32(const float* A, const float* B, float* C, int64
                                  int64_t ldc, int form, int64_t batch, int64_t nz2, int64_t sa1, int64_t sa2, int64_t sb1, int64_t sb2,
                                  int64_t sc1, int64_t sc2, float alpha, const float* bias, const float* res, int64_t ldr, int gelu,
                                  void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * A1h  The inference forwards with the matrix products in fp16 (opt-in): "matrix products in 16 bits, everything else fp32", the
+ * trade a user of HuggingFace `.half()` makes, for the encoder calls of examples/ex_aspire_consent.py:72-73 (A1),
+ * examples/ex_aspire_bienc.py:23-58 (A1b) and src/evaluation/utils/models.py:379-410 (A1d).  The default path holds every nn.Linear
+ * operand as two fp16 planes and pays three matrix instructions per term; this mode holds ONE plane and pays one.
+ *
+ * aspire_bert_forward_prec_f32 is aspire_bert_forward_var_f32 (x may be NULL: aspire_bert_forward_f32) and
+ * aspire_bert_forward_cls_prec_f32 is aspire_bert_forward_cls_f32, plus `hplanes` and `matmul`:
+ *   ASPIRE_MATMUL_FP32  those calls: the same launches, the same bits; hplanes is not read
+ *   ASPIRE_MATMUL_FP16  the arithmetic below, at every B x L (the mode has no row threshold); hplanes == NULL ->
+ *                       ASPIRE_ERR_INVALID_ARG
+ *   any other value     ASPIRE_ERR_INVALID_ARG (ASPIRE_MATMUL_BF16 and ASPIRE_MATMUL_BF16X3 are the training entries' modes)
+ * All checks -- those of the plain entries, then these -- run before the first launch and touch no device.
+ *
+ * The mode's arithmetic, and nothing else:
+ *   - in the QKV, attention output, FFN1 and FFN2 projections every operand element is rounded to fp16 ONCE, round to nearest even:
+ *     activations as they are, weights as fp16(64 w) with the factor taken off exactly in the epilogue;
+ *   - a product of two fp16 values is exact in fp32; the sums over K are the matrix cores' fp32 accumulators in a fixed order;
+ *   - bias, residual and GELU are fp32; GELU(FFN1) is rounded to fp16 once, as the operand of FFN2 (no fp32 [B L, ffn] exists);
+ *   - no atomics, no waits inside a kernel (aspire_bert_status plays no part), no device globals, one writer per output element: the
+ *     same bits on every run, also from several streams at once (one workspace per stream);
+ *   - the residual stream, LayerNorm, the embeddings, the attention (Q K^T, soft-max, P V: an existing attention kernel on the fp32
+ *     Q / K / V the mode's QKV projection writes), the CLS forward's last-layer tail on the B CLS rows, the pooler and every read-out
+ *     keep the accuracy they have in ASPIRE_MATMUL_FP32;
+ *   - an activation beyond 65504 becomes inf in the operand and shows as non-finite output: check the output and run again after
+ *     aspire_debug_set("GEMM", "bf16x3") + ("ATTN", "f32") (aspire_amd's run_checked does) -- a GEMM pin (aspire_debug_set("GEMM", ..)
+ *     or ASPIRE_HIP_GEMM) overrides the mode: such a forward runs ASPIRE_MATMUL_FP32's plan.
+ * The mode needs 64-wide heads and ffn_dim % 128 == 0 (BERT-base); otherwise, and with n_layers == 0, the forward is
+ * ASPIRE_MATMUL_FP32's.
+ *
+ *   hplanes   a DEVICE buffer of aspire_bert_hplanes_bytes(w) bytes, filled once by aspire_bert_prepare_hplanes when the model is
+ *             loaded (synchronises the stream; ASPIRE_ERR_UNSUPPORTED for a weight that is not finite or has |64 w| > 65504).  An
+ *             argument, not a field: aspire_bert_weights keeps its layout.
+ *   workspace aspire_bert_workspace_bytes_prec / aspire_bert_cls_workspace_bytes_prec (w, B, L, matmul) bytes (0 for a matmul value
+ *             that is no mode of these entries)
+ *
+ * The layout of an operand ("H layout") of X [R, K], K % 32 == 0: per 32-wide k block kb and row r four 16-byte pieces q = 0 .. 3 = the
+ * 8 fp16 at k = 32 kb + 8 q .. + 7, at piece index (kb R + r) 4 + (q ^ ((r >> 2) & 3)); 256 rows of slack behind the matrix:
+ * (R + 256) K 2 bytes.  For tests and tools:
+ *   aspire_debug_hplane_bytes(R, K)      that size
+ *   aspire_debug_split_hplane            X fp32 [R, K] contiguous -> H (weight != 0: 64 X, the B side of a product)
+ *   aspire_debug_gemm_hplane             one product on H operands A [M, K] and B [N, K] (split with weight != 0); any M >= 1,
+ *                                        N % 64 == 0, K % 32 == 0.  epilogue 0: C [M, N] fp32 = A B^T (+ bias [N]) (+ res [M, N]);
+ *                                        epilogue 1: Ch [M, N] in the H layout = GELU(A B^T + bias), res must be NULL.  Rows of A
+ *                                        behind M (the slack) are read and never written to C / Ch.
+ * ------------------------------------------------------------------------------------------- */
+size_t aspire_bert_hplanes_bytes(const aspire_bert_weights* w);
+int aspire_bert_prepare_hplanes(const aspire_bert_weights* w, void* hplanes, size_t hplanes_bytes, void* stream);
+size_t aspire_bert_workspace_bytes_prec(const aspire_bert_weights* w, int64_t B, int64_t L, int matmul);
+size_t aspire_bert_cls_workspace_bytes_prec(const aspire_bert_weights* w, int64_t B, int64_t L, int matmul);
+int aspire_bert_forward_prec_f32(const aspire_bert_weights* w, const aspire_bert_extras* x, const void* hplanes, int matmul,
+                                 const int64_t* tok_ids, const int64_t* type_ids, const int64_t* attn_mask, int64_t B, int64_t L,
+                                 float* hidden_out, void* workspace, size_t workspace_bytes, void* stream);
+int aspire_bert_forward_cls_prec_f32(const aspire_bert_weights* w, const void* hplanes, int matmul, const int64_t* tok_ids,
+                                     const int64_t* type_ids, const int64_t* attn_mask, int64_t B, int64_t L, const float* layer_mix,
+                                     float* cls_out, float* layer_cls, void* workspace, size_t workspace_bytes, void* stream);
+size_t aspire_debug_hplane_bytes(int64_t R, int64_t K);
+int aspire_debug_split_hplane(const float* X, int64_t R, int64_t K, void* H, int weight, void* stream);
+int aspire_debug_gemm_hplane(const void* Ah, const void* Bh, float* C, void* Ch, const float* bias, const float* res, int64_t M,
+                             int64_t N, int64_t K, int epilogue, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * A1t with a fused attention (opt-in, with ASPIRE_MATMUL_BF16 only): no [L, L] tensor on the tape or in the workspace.

@@ -2,7 +2,8 @@
 -> 128 queries x otAspire + top-100 on it.  The reference's flow: pp_gen_nearest.py:141-202 (encode the papers in batches of 32 via
 disent_models.py:344-371, then score every query against the pool and sort).
 
-  python tools/e2ebench.py [N_DOCS L S N_QUERIES]        (default 16384 256 12 128; synthetic tokens, random-init BERT-base)
+  python tools/e2ebench.py [N_DOCS L S N_QUERIES] [--matmul fp16]     (default 16384 256 12 128; synthetic tokens, random-init BERT-base;
+                                                                       --matmul fp16: the encoder's opt-in fp16 matmul mode)
 
 Prints docs/s of the encode stage, pairs/s of the score + rank stage, the time split (encoder kernels / pooling / host), and
 spot-checks three pairs against HuggingFace BertModel (fp32, CPU) + the CPU oracle.  `run()` is what bench.py's `e2e` key calls."""
@@ -77,14 +78,14 @@ def run_ragged(model, n_docs=2048, S=8, seed=5):
     return out
 
 
-def run(n_docs=16384, L=256, S=12, n_queries=128, k=100, check=True, seed=2, planes=True):
+def run(n_docs=16384, L=256, S=12, n_queries=128, k=100, check=True, seed=2, planes=True, matmul='fp32'):
     from transformers import BertConfig, BertModel
     from aspire_amd import ops, scorer, _lib
     from aspire_amd.consent import AspireConSent
     dev = ops.require_gpu()
     torch.manual_seed(0)
     hf = BertModel(BertConfig(vocab_size=31090), add_pooling_layer=False).eval()
-    model = AspireConSent(bert_model=hf)
+    model = AspireConSent(bert_model=hf) if matmul == 'fp32' else AspireConSent(bert_model=hf, matmul=matmul)
     batches = synthetic_batches(n_docs, L, S, seed)
     qbatches = synthetic_batches(n_queries, L, S, seed + 1)
     # move the token tensors to the GPU first: config 5 keeps everything resident, the PCIe-inclusive rate is not the metric
@@ -231,7 +232,11 @@ def run_sharded(rank, world, group=None, n_docs=8192, L=256, S=12, n_queries=128
 
 
 if __name__ == '__main__':
-    a = [int(v) for v in sys.argv[1:5]]
-    r = run(*a) if a else run()
+    argv = list(sys.argv[1:])
+    mode = argv.pop(argv.index('--matmul') + 1) if '--matmul' in argv else 'fp32'
+    argv = [v for v in argv if v != '--matmul']
+    a = [int(v) for v in argv[:4]]
+    r = run(*a, matmul=mode) if a else run(matmul=mode)
+    r['matmul'] = mode          # (fp16: the spot check's 2e-4 is the fp32 path's tolerance and is expected to be missed)
     import json
     print(json.dumps(r, indent=1))
